@@ -21,8 +21,10 @@ N > 1 : V/w are row-sharded by feature id; every rank sees every example restric
 `--mode hogwild` (asynchronous, metric-level parity only) is printed as an extra key, never as `value`.
 
 The JSON line carries `roofline` (dominant kernel: algorithmic bytes / HIP-event duration vs the 8 TB/s HBM peak, and
-the V-gather read fraction next to the total) and, at N = 1, `cpu_baseline` (the REAL reference's fm_model::predict +
-fm_SGD compiled from its own sources, one thread, bounded sample; the C restatement is the extra key `cpu_port`).
+the V-gather read fraction next to the total).  A plain run does only that: set up, warm up, time `--steps` steps, print.
+`--full` adds, at N = 1, `cpu_baseline` (the REAL reference's fm_model::predict + fm_SGD compiled from its own sources, one
+thread, bounded sample; the C restatement is the extra key `cpu_port`), the secondary figures and the other BASELINE configs.
+`--dump-outputs DIR` writes the model after the last timed step (w0, and w / V of a fixed seeded sample of features) as .npy.
 """
 import argparse
 import ctypes
@@ -109,6 +111,23 @@ def cpu_baseline_rows(h, n, k, rows):
 def v_read_fraction(value, k, nnz, world=1):
     """SURVEY section 8(d) fraction (1): examples/s x z*k*4 bytes of gathered V rows per GPU / HBM peak."""
     return round(value * nnz * k * 4 / world / 1e9 / HBM_PEAK_GBS, 4)
+
+
+DUMP_FEATURES = 65536         # sampled feature ids of --dump-outputs: (k + 1) x 4 B each, 17 MB at k = 64
+
+
+def dump_outputs(h, out_dir):
+    """--dump-outputs: what a caller of the timed path receives, i.e. the model after the last step: w0 (float64) and, for a fixed
+    seeded sample of feature ids (the whole model at n <= DUMP_FEATURES), w and V as the device stores them (float32)."""
+    import numpy as np
+    n, k = h.n, h.k
+    m = min(n, DUMP_FEATURES, (48 << 20) // (4 * (k + 1)))
+    ids = np.arange(n) if m == n else np.unique(np.random.default_rng(20261016).integers(0, n, m))
+    w, v = h.get_param_rows(ids)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "w0.npy"), np.array([h.get_w0()], dtype=np.float64))
+    np.save(os.path.join(out_dir, "w.npy"), w.astype(np.float32))
+    np.save(os.path.join(out_dir, "v.npy"), v.astype(np.float32))
 
 
 def cpu_reference(n, k, nnz, rows):
@@ -377,7 +396,7 @@ def cpu_reference_mcmc(method, k, nnz, rows=150000, n=1500000, gpu_leg="n=1e7 an
             "seconds": round(t["learn_seconds"], 3), "host_cores": os.cpu_count() or 1}
 
 
-def run_als(capi, method, n, k, nnz, rows, steps, warmup, with_cpu, cpu_kw=None):
+def run_als(capi, method, n, k, nnz, rows, steps, warmup, with_cpu, cpu_kw=None, dump_dir=None):
     """one step = one sweep (fmx_als_sweep) over `rows` examples, one GPU; returns the figure as a dict"""
     sample = method == "mcmc"
     h = capi.Handle(n, k, True, True, capi.TASK_REGRESSION, 0.0, 1.0, 10.0, 0.0, -1.0, 1.0, device=0)
@@ -395,6 +414,8 @@ def run_als(capi, method, n, k, nnz, rows, steps, warmup, with_cpu, cpu_kw=None)
         dev += st.device_seconds
     h.synchronize()
     elapsed = time.perf_counter() - t0
+    if dump_dir:
+        dump_outputs(h, dump_dir)
     nnz_total = rows * nnz
     n_seen = min(n, nnz_total)
     per_sweep = als_bytes_per_sweep(rows, nnz_total, n_seen, k)
@@ -428,13 +449,13 @@ def run_als(capi, method, n, k, nnz, rows, steps, warmup, with_cpu, cpu_kw=None)
     return out
 
 
-def bench_als(args, capi):
+def bench_als(args, capi, with_cpu):
     """--method als | mcmc: one step = one sweep (fmx_als_sweep) over `--rows` examples, one GPU"""
     if int(os.environ.get("WORLD_SIZE", "1")) != 1 or args.gpus != 1:
         raise SystemExit("--method als/mcmc: one GPU (feature shards of the sweep go through fmx_group_*, see tests/test_gpu_group.py)")
     if capi.load().fmx_device_count() == 0:
         raise SystemExit("bench.py needs a HIP device (there is no CPU path)")
-    out = run_als(capi, args.method, args.n, args.k, args.nnz, args.rows, args.steps, args.warmup, not args.no_cpu_baseline)
+    out = run_als(capi, args.method, args.n, args.k, args.nnz, args.rows, args.steps, args.warmup, with_cpu, dump_dir=args.dump_outputs)
     print(json.dumps(out), flush=True)
 
 
@@ -547,7 +568,7 @@ def main():
                     help="auto: the minibatch rule everywhere -- `fused` (FMX_APPLY_FUSED, one pass) on one GPU, the split step "
                          "(feature-sharded) on several; minibatch: the two-pass segmented form; hogwild: asynchronous")
     ap.add_argument("--bias-lag", type=int, default=2, help="fused: batches the multipliers' bias lags behind (1..4)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary figures (hogwild, two-pass minibatch)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary figures (hogwild, two-pass minibatch)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo stages the all-reduce through the host (testing the N>1 path without RCCL)")
     ap.add_argument("--same-device", action="store_true", help="testing: every shard / rank on device 0 (several GPUs from one process: the loopback exchange)")
@@ -572,7 +593,7 @@ def main():
                          "oracle fmo_sgd_epoch_minibatch_pipelined).  Default OFF: every N runs the SAME rule as N = 1")
     ap.add_argument("--no-bias-lag", action="store_true", help="minibatch: keep the w0 recurrence on the critical path (exact chunk coupling)")
     ap.add_argument("--cpu-rows", type=int, default=200_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not run the two rocprofv3 --pmc passes that measure roofline.traffic in this run")
     ap.add_argument("--place", type=int, default=None,
                     help="fmx_config::place_candidates: 0 = the library's placement (big tables: chunks of two memory classes), 1 = plain "
@@ -582,7 +603,16 @@ def main():
                     help="PMC HBM bytes per launch of the dominant kernel (default: profiles/traffic.json if it matches)")
     ap.add_argument("--no-cpu-reference", dest="cpu_reference", action="store_false",
                     help="skip timing the REAL reference code (oracle/_ref/ref_harness time_sgd, largest n it can allocate)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baselines, the secondary figures (predict, hogwild, "
+                         "sequential, two-pass minibatch, parity against the online loop, counter traffic), the other BASELINE configs "
+                         "and the shard probe.  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (w0, and w / V of a fixed seeded sample of "
+                         "features) as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
+    cpu_on = args.full and not args.no_cpu_baseline     # the CPU legs and the secondary figures run only with --full
+    extras_on = args.full and not args.no_extras
     if args.place is None:
         args.place = 1 if (args.same_device and args.gpus > 1) else 0
 
@@ -592,11 +622,14 @@ def main():
     if args.nnz is None:
         args.nnz = (39 if criteo else 32) if args.method == "sgd" else 16
 
+    if args.dump_outputs and (args.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1):
+        raise SystemExit("--dump-outputs: one GPU (one handle holds the whole model)")
+
     import torch
     import torch.distributed as dist
     from libfm_amd import capi
     if args.method != "sgd":
-        return bench_als(args, capi)
+        return bench_als(args, capi, cpu_on)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as typed: either all shards from this process (fmx_group_*), or -- the default on N distinct
@@ -633,7 +666,7 @@ def main():
             dist.init_process_group("gloo", rank=rank, world_size=world)
 
     cpu, cpu_ref = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not criteo:   # (the CPU legs time the uniform workload)
+    if rank == 0 and world == 1 and cpu_on and not criteo:   # (the CPU legs time the uniform workload)
         cpu = cpu_baseline(args.n, args.k, args.nnz, args.cpu_rows)
         if args.cpu_reference:
             cpu_ref = cpu_reference(args.n, args.k, args.nnz, args.cpu_rows)
@@ -644,7 +677,7 @@ def main():
                     place_candidates=args.place, exchange_algo=1 if args.exchange == "rsag" else 0)
     h.init_params(0.0, 0.01, 1)
     h.synth_rows(0, 123, 0, args.rows, args.nnz, capi.SYNTH_CRITEO if criteo else capi.SYNTH_UNIFORM)
-    if criteo and rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if criteo and rank == 0 and world == 1 and cpu_on:
         cpu = cpu_baseline_rows(h, args.n, args.k, min(args.cpu_rows, 100_000))
     info = h.info()
     mode = capi.SGD_HOGWILD if args.mode == "hogwild" else capi.SGD_MINIBATCH
@@ -761,9 +794,11 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:                     # before the extras: they run more epochs and start the parameters over
+        dump_outputs(h, args.dump_outputs)
 
     extras = {}
-    if rank == 0 and not sharded and not args.no_extras and not criteo:
+    if rank == 0 and not sharded and extras_on and not criteo:
         # secondary figures, never `value`: the asynchronous mode (metric-level parity only) and the two-pass form of the rule
         def timed_epochs(n, *a):
             h.sgd_epoch(0, *a)
@@ -966,7 +1001,7 @@ def main():
         }
         if fallback_reason:
             out["driver_fallback"] = fallback_reason          # (loud: the line says which driver ran and why, not only stderr)
-        if not sharded and args.mode == "fused" and not criteo:
+        if not sharded and args.mode == "fused" and not criteo and args.full:
             # how far the headline rule ends from the reference's ONLINE loop at this shape (the committed CPU measurement of the oracle's
             # two loops; asserted with the device in place of the rule by tests/test_gpu_configs.py)
             try:
@@ -1054,12 +1089,12 @@ def main():
     h.close()
     if sharded:
         dist.destroy_process_group()
-    if rank == 0 and not sharded and not args.no_extras and not criteo and args.mode == "fused":
+    if rank == 0 and not sharded and extras_on and not criteo and args.mode == "fused":
         # the other two learners north_star names (BASELINE configs[3] / [4] shapes on one GPU): one line each, never `value`
         keep = ("metric", "value", "unit", "ms_per_step", "steps", "dtype", "config", "roofline", "cpu_baseline")
         for method in ("als", "mcmc"):
             try:
-                o = run_als(capi, method, 10_000_000, 64, 16, 1 << 22, 2, 1, not args.no_cpu_baseline)
+                o = run_als(capi, method, 10_000_000, 64, 16, 1 << 22, 2, 1, cpu_on)
                 out[method] = {kk: o[kk] for kk in keep}
             except Exception as exc:                             # a secondary figure must not take the headline down
                 out[method] = {"error": str(exc)[:200]}
@@ -1068,9 +1103,9 @@ def main():
         #   criteo   configs[2]  n = 3.3e7, k = 64, 39 entries/row, Criteo-shaped ids: the library cuts the batch (fmx_sgd_opts::batch = 0)
         #   mcmc_c5  configs[4]  MCMC (Gibbs draws), k = 128, n = 1e8, 16 entries/row -- a 51 GB table on ONE GPU; its CPU baseline is the
         #            reference's chain at the largest n that keeps the leg inside ~20 s (it draws all n * k coordinates per iteration)
-        legs = (("c2", lambda: run_sgd_config(capi, "BASELINE configs[1]", 10_000_000, 32, 16, 1 << 23, False, 5, 2, not args.no_cpu_baseline, args.cpu_rows)),
-                ("criteo", lambda: run_sgd_config(capi, "BASELINE configs[2], Criteo-shaped ids", 33_000_000, 64, 39, 1 << 20, True, 3, 1, not args.no_cpu_baseline, 100_000)),
-                ("mcmc_c5", lambda: run_als(capi, "mcmc", 100_000_000, 128, 16, 1 << 22, 2, 1, not args.no_cpu_baseline,
+        legs = (("c2", lambda: run_sgd_config(capi, "BASELINE configs[1]", 10_000_000, 32, 16, 1 << 23, False, 5, 2, cpu_on, args.cpu_rows)),
+                ("criteo", lambda: run_sgd_config(capi, "BASELINE configs[2], Criteo-shaped ids", 33_000_000, 64, 39, 1 << 20, True, 3, 1, cpu_on, 100_000)),
+                ("mcmc_c5", lambda: run_als(capi, "mcmc", 100_000_000, 128, 16, 1 << 22, 2, 1, cpu_on,
                                             {"rows": 100_000, "n": 1_000_000, "gpu_leg": "n=1e8 (the stock containers stop at k*n < 2^32, i.e. n <= 3.3e7 at k=128, and "
                                              "the chain draws all n*k coordinates per iteration: n=1e6 keeps this leg near 20 s) and 42x the rows"})))
         for key, leg in legs:

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r5c12
 mkdir -p $O
 T0=$(date +%s.%N)
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 T1=$(date +%s.%N)
 echo "python bench.py: $(echo "$T1 - $T0" | bc) s wall on the box" | tee $O/bench_default_seconds.txt
 python -c "

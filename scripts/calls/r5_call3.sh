@@ -8,7 +8,7 @@ O=gpurun_out/r5c3
 mkdir -p $O
 timeout 1500 python -m pytest tests -q -m gpu -x > $O/pytest_all.log 2>&1
 tail -6 $O/pytest_all.log
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python - <<'PY'
 import json
 o = json.load(open("gpurun_out/r5c3/bench_default.json"))

@@ -8,7 +8,7 @@ O=gpurun_out/r5c7
 mkdir -p $O
 timeout 1800 python -m pytest tests -q -m gpu > $O/pytest_all.log 2>&1
 tail -6 $O/pytest_all.log
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python -c "
 import json; o=json.load(open('$O/bench_default.json')); print('default', o['value'], o['roofline']['frac'], o['config']['w0_chunk'], o['roofline'].get('per_config'), {k:v['per_rank_examples_per_s'] for k,v in o['shard_probe']['ranks'].items()})"
 B="python bench.py --no-extras --no-cpu-baseline"

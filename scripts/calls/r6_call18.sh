@@ -8,7 +8,7 @@ mkdir -p $O
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
 timeout 3000 python -m pytest tests -q -m gpu > $O/pytest_gpu.txt 2>&1; echo "suite rc=$?"; tail -4 $O/pytest_gpu.txt | head -2
 T0=$(date +%s)
-timeout 1200 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "default bench rc=$? $(( $(date +%s) - T0 )) s"
+timeout 1200 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "default bench rc=$? $(( $(date +%s) - T0 )) s"
 python - <<'PY'
 import json
 o = json.load(open("gpurun_out/r6c18/bench_default.json"))

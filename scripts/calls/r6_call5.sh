@@ -10,7 +10,7 @@ for i in 1 2; do
 FMX_TRACE_ALLOC=1 FMX_TRACE_SETUP=1 timeout 600 python bench.py --no-extras --no-cpu-baseline --steps 20 --warmup 3 > $O/bench_noextras_$i.json 2> $O/bench_noextras_$i.err; echo "bench $i rc=$?"
 grep "fmx setup\|fmx alloc" $O/bench_noextras_$i.err | head -20
 done
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "default bench rc=$?"
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "default bench rc=$?"
 python - <<'PY'
 import json
 o = json.load(open("gpurun_out/r6c5/bench_default.json"))

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r6c60
 mkdir -p $O
 T0=$(date +%s)
-timeout 1500 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "default bench rc=$? $(( $(date +%s) - T0 )) s"
+timeout 1500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "default bench rc=$? $(( $(date +%s) - T0 )) s"
 python -c "
 import json; o = json.load(open('gpurun_out/r6c60/bench_default.json')); r = o['roofline']
 print(o['value'], r['frac'], r['traffic'], r['step_traffic_ratio'])

@@ -23,7 +23,7 @@ cd $GRAFT_REPO_ROOT
 python scripts/pmc_summary.py $OUT 8 > $OUT/pmc_summary.txt 2>&1
 head -5 $OUT/bench_trace/bench_kernel_stats.csv | cut -c1-160
 grep -A3 "^== pmc" $OUT/pmc_summary.txt | cut -c1-150
-timeout 600 python bench.py 2>/dev/null | grep "^{" > $OUT/bench_default.json
+timeout 600 python bench.py --full 2>/dev/null | grep "^{" > $OUT/bench_default.json
 cat $OUT/bench_default.json
 timeout 200 python bench.py --no-cpu-baseline --no-extras --method als 2>/dev/null | grep "^{" > $OUT/bench_als.json
 timeout 200 python bench.py --no-cpu-baseline --no-extras --force-sharded --mode minibatch 2>/dev/null | grep "^{" > $OUT/bench_one_rank_rccl.json

@@ -21,9 +21,9 @@ cd $GRAFT_REPO_ROOT
 python scripts/pmc_summary.py $OUT 8 > $OUT/pmc_summary.txt 2>&1
 head -5 $OUT/bench_trace/bench_kernel_stats.csv | cut -c1-160
 grep -A3 "^== pmc" $OUT/pmc_summary.txt | cut -c1-150
-timeout 900 python bench.py 2>/dev/null | grep "^{" > $OUT/bench_default.json
+timeout 900 python bench.py --full 2>/dev/null | grep "^{" > $OUT/bench_default.json
 cut -c1-300 $OUT/bench_default.json
-timeout 400 python bench.py --workload criteo --rows 1048576 --steps 3 --warmup 1 2>/dev/null | grep "^{" > $OUT/bench_criteo.json
+timeout 400 python bench.py --full --workload criteo --rows 1048576 --steps 3 --warmup 1 2>/dev/null | grep "^{" > $OUT/bench_criteo.json
 timeout 300 python bench.py --gpus 2 --same-device --no-cpu-baseline 2>/dev/null | grep "^{" > $OUT/bench_two_shards_one_device.json
 cut -c1-200 $OUT/bench_criteo.json; grep -o '"phases_ms_per_batch.*' $OUT/bench_two_shards_one_device.json | cut -c1-200; cut -c1-200 $OUT/bench_two_shards_one_device.json
 cp $OUT/bench_trace/bench_kernel_stats.csv $OUT/bench_kernel_stats.csv; cp $OUT/criteo_trace/criteo_kernel_stats.csv $OUT/criteo_kernel_stats.csv; cp $OUT/als_trace/als_kernel_stats.csv $OUT/als_kernel_stats.csv

@@ -11,7 +11,7 @@ tail -5 $OUT/pytest_gpu.log
 cat $OUT/ab_handoff.txt
 ( timeout 300 python scripts/gpu_ab_handoff.py 262144,131072,65536 10000000 32 16 ) > $OUT/ab_handoff_c2.txt 2>&1
 cat $OUT/ab_handoff_c2.txt
-timeout 900 python bench.py 2>$OUT/bench_default.err | grep "^{" > $OUT/bench_default.json
+timeout 900 python bench.py --full 2>$OUT/bench_default.err | grep "^{" > $OUT/bench_default.json
 cut -c1-600 $OUT/bench_default.json; tail -3 $OUT/bench_default.err
 cd /tmp
 B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-extras"

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 tail -4 $OUT/pytest_gpu.log
 ( timeout 300 python scripts/gpu_ab_wside.py ) > $OUT/ab_wside.txt 2>&1; cat $OUT/ab_wside.txt
 ( timeout 400 python scripts/gpu_ab_variants.py wst 2 fused ) > $OUT/ab_wst.txt 2>&1; tail -3 $OUT/ab_wst.txt
-timeout 900 python bench.py 2>$OUT/bench_default.err | grep "^{" > $OUT/bench_default.json
+timeout 900 python bench.py --full 2>$OUT/bench_default.err | grep "^{" > $OUT/bench_default.json
 python - <<'PY'
 import json,os
 d=json.load(open(os.environ["GRAFT_REPO_ROOT"]+"/gpurun_out/r4b/bench_default.json"))

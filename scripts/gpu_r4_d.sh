@@ -17,7 +17,7 @@ cp $OUT/criteo_trace/*/criteo_kernel_stats.csv $OUT/criteo_kernel_stats.csv 2>/d
 grep "k_fused\|k_apply_seg" $OUT/criteo_kernel_stats.csv | cut -c1-40,180-330
 cd $GRAFT_REPO_ROOT
 timeout 300 python bench.py --workload criteo --rows 1048576 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | grep "^{" | cut -c1-160
-timeout 900 python bench.py 2>$OUT/bench_default.err | grep "^{" > $OUT/bench_default.json
+timeout 900 python bench.py --full 2>$OUT/bench_default.err | grep "^{" > $OUT/bench_default.json
 python - <<'PY'
 import json,os
 d=json.load(open(os.environ["GRAFT_REPO_ROOT"]+"/gpurun_out/r4d/bench_default.json"))

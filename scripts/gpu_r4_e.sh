@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 ( timeout 1500 python -m pytest tests -q -m gpu 2>&1 | grep -v "^RCCL\|^HIP\|^ROCm\|^Hostname\|^Librccl" | tail -12 ) > $OUT/pytest_gpu.log 2>&1
 tail -2 $OUT/pytest_gpu.log
 T0=$(date +%s)
-timeout 1500 python bench.py 2>$OUT/bench_default.err | grep "^{" > $OUT/bench_default.json
+timeout 1500 python bench.py --full 2>$OUT/bench_default.err | grep "^{" > $OUT/bench_default.json
 echo "bench.py default run: $(( $(date +%s) - T0 )) s" | tee $OUT/bench_default_seconds.txt
 python - <<'PY'
 import json,os

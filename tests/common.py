@@ -50,3 +50,11 @@ class Golden:
             if len(np.unique(row)) != len(row):
                 return True
         return False
+
+
+def write_ref_tool_files(name, prefix):
+    """the files the reference's own tools (convert, transpose, libFM -save_model) wrote for a test's rows, stored in
+    tests/golden/ref_tools/<name>.npz by `make_golden.py --ref-tools`: written back as <prefix>.<suffix> (x, y, xt, model)"""
+    z = np.load(os.path.join(GOLDEN_DIR, "ref_tools", name + ".npz"))
+    for suffix in z.files:
+        z[suffix].tofile(prefix + "." + suffix)

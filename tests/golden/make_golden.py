@@ -440,8 +440,49 @@ def make_mcmc_seed_band(seeds=range(101, 113), only=None):
     np.savez_compressed(os.path.join(HERE, "mcmc_ref_seed_band.npz"), **out)
 
 
+REF_TOOLS_DIR = os.path.join(HERE, "ref_tools")
+# name: (datagen generator, kwargs, the reference tools that write the files).  The rows are the ones tests/test_data_formats.py and
+# tests/test_gpu_ingest.py generate; each .npz holds the bytes of every file the tools wrote, keyed by file suffix (uint8).
+REF_TOOLS_CASES = {
+    "convert_ml_seed1": ("movielens_shaped", dict(n_users=50, n_items=40, n_rows=300, seed=1), ("convert",)),
+    "transpose_ml_seed6": ("movielens_shaped", dict(n_users=60, n_items=45, n_rows=400, seed=6), ("convert", "transpose")),
+    "transpose_onehot_seed21": ("onehot_fields", dict(n_features=1600, nnz=8, n_rows=3000, seed=21, classification=False),
+                                ("convert", "transpose")),
+    "libfm_model_seed2": ("movielens_shaped", dict(n_users=30, n_items=20, n_rows=200, seed=2), ("libFM",)),
+}
+LIBFM_MODEL_ARGS = ["-task", "r", "-dim", "1,1,4", "-iter", "3", "-method", "sgd", "-learn_rate", "0.01", "-init_stdev", "0.1", "-seed", "7"]
+
+
+def make_ref_tools():
+    """what the reference's own tools write (tools/convert.cpp, tools/transpose.cpp, libFM -save_model) for the data-format tests"""
+    import subprocess
+    os.makedirs(REF_TOOLS_DIR, exist_ok=True)
+    for name, (gen, kw, tools) in REF_TOOLS_CASES.items():
+        with tempfile.TemporaryDirectory() as td:
+            txt, pre = os.path.join(td, "d.libfm"), os.path.join(td, "d")
+            O.Data(*getattr(datagen, gen)(**kw)).write_libsvm(txt)
+            files = {}
+            if "convert" in tools:
+                subprocess.run([os.path.join(O.REF_DIR, "convert"), "--ifile", txt, "--ofilex", pre + ".x", "--ofiley", pre + ".y"],
+                               check=True, capture_output=True)
+                files.update(x=pre + ".x", y=pre + ".y")
+            if "transpose" in tools:
+                subprocess.run([os.path.join(O.REF_DIR, "transpose"), "--ifile", pre + ".x", "--ofile", pre + ".xt"], check=True, capture_output=True)
+                files["xt"] = pre + ".xt"
+            if "libFM" in tools:
+                subprocess.run([O.REF_LIBFM, "-train", txt, "-test", txt, "-save_model", pre + ".model"] + LIBFM_MODEL_ARGS,
+                               check=True, capture_output=True)
+                files["model"] = pre + ".model"
+            arrays = {k: np.frombuffer(open(p, "rb").read(), dtype=np.uint8) for k, p in files.items()}
+        np.savez_compressed(os.path.join(REF_TOOLS_DIR, name + ".npz"), **arrays)
+        print("%-24s %s" % (name, ", ".join("%s %d B" % (k, len(a)) for k, a in arrays.items())))
+
+
 if __name__ == "__main__":
-    if "--mcmc-only" in sys.argv:    # one MCMC fixture + its 12-seed band, nothing else touched
+    if "--ref-tools" in sys.argv:    # only the reference tools' files of the data-format tests
+        O.build()
+        make_ref_tools()
+    elif "--mcmc-only" in sys.argv:    # one MCMC fixture + its 12-seed band, nothing else touched
         names = sys.argv[sys.argv.index("--mcmc-only") + 1].split(",")
         make_mcmc(only=names)
         make_mcmc_seed_band(only=names)

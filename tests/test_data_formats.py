@@ -1,16 +1,13 @@
-"""CPU: the host-side readers of libFM's data formats against files written by the REFERENCE's own convert tool
-(oracle/_ref/convert, compiled from /root/reference/src/libfm/tools/convert.cpp when the reference is present) and
+"""CPU: the host-side readers of libFM's data formats against files written by the REFERENCE's own tools (tools/convert.cpp,
+tools/transpose.cpp, libFM -save_model; stored in tests/golden/ref_tools/ by tests/golden/make_golden.py --ref-tools) and
 against the documented sizes (.x = 24 + 4N + 8 nnz bytes, .y = 12 + 4N bytes)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import datagen
-from conftest import ROOT
-
-CONVERT = os.path.join(ROOT, "oracle", "_ref", "convert")
+from common import write_ref_tool_files
 
 
 def test_binary_round_trip_and_sizes(tmp_path):
@@ -63,14 +60,11 @@ def test_native_text_reader_against_python_and_reference_errors(tmp_path, oracle
         D.read_libsvm(str(tmp_path / "missing"))
 
 
-@pytest.mark.skipif(not os.path.exists(CONVERT), reason="oracle/_ref/convert not built (needs /root/reference)")
 def test_reads_what_the_reference_convert_tool_writes(tmp_path, oracle):
     from libfm_amd import data as D
     ent, rp, y = datagen.movielens_shaped(50, 40, 300, seed=1)
-    txt = str(tmp_path / "d.libfm")
-    oracle.Data(ent, rp, y).write_libsvm(txt)
     pre = str(tmp_path / "d")
-    subprocess.run([CONVERT, "--ifile", txt, "--ofilex", pre + ".x", "--ofiley", pre + ".y"], check=True, capture_output=True)
+    write_ref_tool_files("convert_ml_seed1", pre)                                  # convert of these rows as libsvm text
     e2, r2, y2 = D.load(pre)
     assert np.array_equal(e2, ent) and np.array_equal(r2, rp) and np.array_equal(y2, y)
     # and our writer produces byte-identical files
@@ -124,19 +118,12 @@ def test_binary_reader_of_the_c_abi(tmp_path, oracle):
         D.read_binary(short)
 
 
-TRANSPOSE = os.path.join(ROOT, "oracle", "_ref", "transpose")
-
-
-@pytest.mark.skipif(not (os.path.exists(CONVERT) and os.path.exists(TRANSPOSE)), reason="oracle/_ref/convert / transpose not built (needs /root/reference)")
 def test_binary_reader_on_the_reference_tools_output(tmp_path, oracle):
-    """convert + transpose of the REFERENCE write the files; fmx_read_binary reads .x and, alone, .xt"""
+    """convert + transpose of the REFERENCE wrote the files; fmx_read_binary reads .x and, alone, .xt"""
     from libfm_amd import data as D
     ent, rp, y = datagen.movielens_shaped(60, 45, 400, seed=6)
-    txt = str(tmp_path / "d.libfm")
-    oracle.Data(ent, rp, y).write_libsvm(txt)
     pre = str(tmp_path / "d")
-    subprocess.run([CONVERT, "--ifile", txt, "--ofilex", pre + ".x", "--ofiley", pre + ".y"], check=True, capture_output=True)
-    subprocess.run([TRANSPOSE, "--ifile", pre + ".x", "--ofile", pre + ".xt"], check=True, capture_output=True)
+    write_ref_tool_files("transpose_ml_seed6", pre)
     e2, r2, y2, nf = D.read_binary(pre)
     assert np.array_equal(e2, ent) and np.array_equal(r2, rp) and np.array_equal(y2, y) and nf == int(ent["id"].max()) + 1
     only_t = str(tmp_path / "t")
@@ -145,20 +132,12 @@ def test_binary_reader_on_the_reference_tools_output(tmp_path, oracle):
     assert np.array_equal(e3, ent) and np.array_equal(r3, rp) and nf3 == nf       # these rows already have ascending ids
 
 
-LIBFM = os.path.join(ROOT, "oracle", "_ref", "libFM")
-
-
-@pytest.mark.skipif(not os.path.exists(LIBFM), reason="oracle/_ref/libFM not built (needs /root/reference)")
 def test_model_file_round_trip_is_byte_identical_to_the_reference_writer(tmp_path, oracle):
-    """-save_model text format (fm_model.h:132-154): read the stock binary's file, write it again, same bytes."""
+    """-save_model text format (fm_model.h:132-154): read the stock binary's file, write it again, same bytes.  The file: libFM -task r
+    -dim 1,1,4 -iter 3 -method sgd -learn_rate 0.01 -init_stdev 0.1 -seed 7 on datagen.movielens_shaped(30, 20, 200, seed=2)."""
     from libfm_amd import learner as L
-    ent, rp, y = datagen.movielens_shaped(30, 20, 200, seed=2)
-    txt = str(tmp_path / "d.libfm")
-    oracle.Data(ent, rp, y).write_libsvm(txt)
-    mf = str(tmp_path / "model")
-    subprocess.run([LIBFM, "-task", "r", "-train", txt, "-test", txt, "-dim", "1,1,4", "-iter", "3", "-method", "sgd",
-                    "-learn_rate", "0.01", "-init_stdev", "0.1", "-seed", "7", "-save_model", mf],
-                   check=True, capture_output=True)
+    write_ref_tool_files("libfm_model_seed2", str(tmp_path / "d"))
+    mf = str(tmp_path / "d.model")
     fm = L.FMModel()
     fm.num_attribute, fm.num_factor = 50, 4
     assert fm.load_model(mf)

@@ -1,22 +1,19 @@
-"""GPU: SURVEY section 8 row f2 end to end -- the REFERENCE's own tools write the binary files (tools/convert.cpp, tools/transpose.cpp;
-LargeSparseMatrixHD format, src/util/fmatrix.h:44-50,165-230), fmx_read_binary lands them in page-locked buffers (Data::load's binary
+"""GPU: SURVEY section 8 row f2 end to end -- the REFERENCE's own tools wrote the binary files (tools/convert.cpp, tools/transpose.cpp;
+LargeSparseMatrixHD format, src/util/fmatrix.h:44-50,165-230; stored in tests/golden/ref_tools/), fmx_read_binary lands them in page-locked buffers (Data::load's binary
 branch, src/libfm/src/Data.h:119-178), fmx_upload_rows takes exactly those buffers, and the learners run on them: one SGD epoch
 and one ALS sweep against the oracle on the same rows.  Also: the upload from the page-locked buffers is not slower than from
 pageable memory (it is a DMA the id check overlaps with)."""
 import ctypes as C
 import os
-import subprocess
 import time
 
 import numpy as np
 import pytest
 
 import datagen
-from conftest import ROOT
+from common import write_ref_tool_files
 
 pytestmark = pytest.mark.gpu
-CONVERT = os.path.join(ROOT, "oracle", "_ref", "convert")
-TRANSPOSE = os.path.join(ROOT, "oracle", "_ref", "transpose")
 
 
 def read_binary_raw(capi, prefix):
@@ -31,17 +28,14 @@ def upload_raw(capi, h, slot, rows):
     assert rc == capi.FMX_OK, h.lib.fmx_last_error(h.h)
 
 
-@pytest.mark.skipif(not (os.path.exists(CONVERT) and os.path.exists(TRANSPOSE)), reason="oracle/_ref/convert / transpose not built (needs /root/reference)")
 @pytest.mark.parametrize("which", ["x", "xt"])
 def test_reference_binary_files_to_learners(tmp_path, oracle, which):
     from libfm_amd import capi
     O = oracle
     n, nnz, n_rows, k = 1600, 8, 3000, 16
     ent, rp, y = datagen.onehot_fields(n, nnz, n_rows, seed=21, classification=False)
-    txt, pre = str(tmp_path / "d.libfm"), str(tmp_path / "d")
-    O.Data(ent, rp, y).write_libsvm(txt)
-    subprocess.run([CONVERT, "--ifile", txt, "--ofilex", pre + ".x", "--ofiley", pre + ".y"], check=True, capture_output=True)
-    subprocess.run([TRANSPOSE, "--ifile", pre + ".x", "--ofile", pre + ".xt"], check=True, capture_output=True)
+    pre = str(tmp_path / "d")
+    write_ref_tool_files("transpose_onehot_seed21", pre)                 # convert + transpose of these rows as libsvm text
     if which == "xt":                               # what an als / mcmc run keeps on disk (libfm.cpp:143-147): the transpose alone
         os.remove(pre + ".x")
     rows = read_binary_raw(capi, pre)
