@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define FMX_ABI_VERSION 7
+#define FMX_ABI_VERSION 8
 
 enum {
   FMX_OK = 0,
@@ -342,7 +342,8 @@ int fmx_upload_rows(fmx_handle h, int slot, const void *entries, const uint64_t 
  * attribute ids start at attr_offset (libfm.cpp:213-216).  The rows are expanded ON THE DEVICE into one CSR
  * (main entries, then the blocks in order) so that the slot behaves like any other; the learners then compute what
  * the reference's per-block caches compute (fm_learn_mcmc.h:478-527, 734-790, 849-909) on the same design matrix.
- * At most 8 relations.  A feature shard (shard_world > 1) joins the rows on the host and keeps its own features. */
+ * At most 8 relations.  A feature shard (shard_world > 1) joins the rows on the host and keeps its own features
+ * (FMX_BLOCKS_EXPAND); to keep the blocks apart on feature shards, upload through fmx_group_upload_block_rows_ex. */
 typedef struct fmx_relation {
   const void     *entries;                    /* the block's own rows: sparse_entry<float>[nnz], ids local to the block */
   const uint64_t *row_ptr;                    /* [n_rows + 1] */
@@ -362,7 +363,8 @@ int fmx_upload_block_rows(fmx_handle h, int slot, const void *entries, const uin
  *                      (fm_learn_mcmc.h:478-527 cache set-up, :734-790 draw_w_rel, :849-909 draw_v_rel, restated): a block
  *                      attribute costs its column in the BLOCK plus two passes over the main rows per block and coordinate
  *                      family, not a column of the joined table.  ALS / MCMC and predict only (the reference's SGD learners
- *                      reject relations too, fm_learn_sgd.h:61-63). */
+ *                      reject relations too, fm_learn_sgd.h:61-63).  A feature shard refuses it here (the sweep needs the
+ *                      group's global view): fmx_group_upload_block_rows_ex keeps the blocks apart on shards. */
 #define FMX_BLOCKS_EXPAND 0u
 #define FMX_BLOCKS_KEEP 1u
 int fmx_upload_block_rows_ex(fmx_handle h, int slot, const void *entries, const uint64_t *row_ptr, const float *target,
@@ -480,6 +482,13 @@ const char *fmx_group_last_error(fmx_group g);
 int fmx_group_set_params(fmx_group g, double w0, const double *w, const double *v);
 int fmx_group_upload_rows(fmx_group g, int slot, const void *entries, const uint64_t *row_ptr, const float *target,
                           uint32_t n_rows, uint64_t nnz);
+/* fmx_upload_block_rows_ex for ALL shards of a group (a one-handle group forwards to it).  FMX_BLOCKS_EXPAND: every shard joins
+ * the rows on the host and keeps its own features.  FMX_BLOCKS_KEEP: the main rows take the fmx_group_upload_rows path; every
+ * shard keeps each block's rows restricted to the block attributes it owns (owner = the shard rule on the global id
+ * attr_offset + j), and the mapping whole -- nothing of the size of the joined table is built on any shard.  fmx_group_predict /
+ * fmx_group_evaluate and fmx_group_als_* then work block-wise; fmx_group_sgd_epoch refuses such a slot (FMX_E_UNSUPPORTED). */
+int fmx_group_upload_block_rows_ex(fmx_group g, int slot, const void *entries, const uint64_t *row_ptr, const float *target,
+                                   uint32_t n_rows, uint64_t nnz, const fmx_relation *relations, uint32_t n_relations, uint32_t flags);
 int fmx_group_sgd_epoch(fmx_group g, int slot, const fmx_sgd_opts *opts, fmx_epoch_stats *stats);
 int fmx_group_predict(fmx_group g, int slot, double *out);
 int fmx_group_evaluate(fmx_group g, int slot, fmx_eval *out);
@@ -539,7 +548,9 @@ int fmx_als_end(fmx_handle h);
  * sweeps its own features, level by level in the GLOBAL dependency order; the {e, q} cache is replicated, one all-reduce per
  * (coordinate family, level) carries the changes of the level's draws, and the re-prediction all-reduces the shards' partial
  * y-hat and q_f (fm_learn_mcmc.h:430-641 with e / q of :46-49 replicated).  Same results as one
- * unsharded handle: ALS to rounding, MCMC draw for draw (the noise of a coordinate is keyed by its GLOBAL feature id). */
+ * unsharded handle: ALS to rounding, MCMC draw for draw (the noise of a coordinate is keyed by its GLOBAL feature id).
+ * Kept `-relation` blocks (fmx_group_upload_block_rows_ex): the per-block-row caches are replicated too, a block's levels are
+ * global over its rows, and one all-reduce of 4 doubles per block row carries the cache changes of each block level. */
 int fmx_group_als_begin(fmx_group g, int train_slot);
 int fmx_group_als_moments(fmx_group g, double *out);
 int fmx_group_als_sweep(fmx_group g, const fmx_als_opts *opts, fmx_als_stats *stats);

@@ -159,6 +159,8 @@ SYMBOLS = [
     ("fmx_group_last_error", C.c_char_p, [H]),
     ("fmx_group_set_params", C.c_int, [H, C.c_double, C.c_void_p, C.c_void_p]),
     ("fmx_group_upload_rows", C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64]),
+    ("fmx_group_upload_block_rows_ex", C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                                                 C.POINTER(Relation), C.c_uint32, C.c_uint32]),
     ("fmx_group_sgd_epoch", C.c_int, [H, C.c_int, C.POINTER(SgdOpts), C.POINTER(EpochStats)]),
     ("fmx_group_predict", C.c_int, [H, C.c_int, C.c_void_p]),
     ("fmx_group_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
@@ -200,6 +202,26 @@ def load():
             fn.argtypes = args
         _lib = L
     return _lib
+
+
+def _block_args(entries, row_ptr, target, relations, keep):
+    """the arguments of fmx_upload_block_rows_ex after the slot, and the arrays they point into (alive while the call runs)"""
+    entries = np.ascontiguousarray(entries, dtype=ENTRY_DTYPE)
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint64)
+    target = None if target is None else np.ascontiguousarray(target, dtype=np.float32)
+    n_rows = len(row_ptr) - 1
+    alive, arr = [entries, row_ptr, target], (Relation * max(len(relations), 1))()
+    for i, (re, rp, mp, off) in enumerate(relations):
+        re = np.ascontiguousarray(re, dtype=ENTRY_DTYPE)
+        rp = np.ascontiguousarray(rp, dtype=np.uint64)
+        mp = np.ascontiguousarray(mp, dtype=np.uint32)
+        if len(mp) != n_rows:
+            raise ValueError("relation %d: the row mapping has %d entries for %d data rows" % (i, len(mp), n_rows))
+        alive += [re, rp, mp]
+        arr[i] = Relation(_ptr(re) if len(re) else None, _ptr(rp), len(rp) - 1, 0, len(re), _ptr(mp), int(off))
+    alive.append(arr)
+    return ((_ptr(entries) if len(entries) else None, _ptr(row_ptr), _ptr(target), n_rows, len(entries), arr, len(relations),
+             1 if keep else 0), alive)
 
 
 def default_w0_chunk(learn_rate, task):
@@ -331,22 +353,9 @@ class Handle:
         """relations: list of (entries, row_ptr, data_row_to_relation_row, attr_offset) -- `-relation` blocks
         (relation.h:32-60).  keep=False: the joined rows are expanded on the device; keep=True (FMX_BLOCKS_KEEP): main rows and
         blocks stay apart, ALS / MCMC sweep the blocks through per-block-row caches like the reference."""
-        entries = np.ascontiguousarray(entries, dtype=ENTRY_DTYPE)
-        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint64)
-        target = None if target is None else np.ascontiguousarray(target, dtype=np.float32)
-        n_rows = len(row_ptr) - 1
-        alive, arr = [], (Relation * max(len(relations), 1))()
-        for i, (re, rp, mp, off) in enumerate(relations):
-            re = np.ascontiguousarray(re, dtype=ENTRY_DTYPE)
-            rp = np.ascontiguousarray(rp, dtype=np.uint64)
-            mp = np.ascontiguousarray(mp, dtype=np.uint32)
-            if len(mp) != n_rows:
-                raise ValueError("relation %d: the row mapping has %d entries for %d data rows" % (i, len(mp), n_rows))
-            alive += [re, rp, mp]
-            arr[i] = Relation(_ptr(re) if len(re) else None, _ptr(rp), len(rp) - 1, 0, len(re), _ptr(mp), int(off))
-        self._chk(self.lib.fmx_upload_block_rows_ex(self.h, slot, _ptr(entries) if len(entries) else None, _ptr(row_ptr),
-                                                    _ptr(target), n_rows, len(entries), arr, len(relations), 1 if keep else 0))
-        return n_rows
+        args, alive = _block_args(entries, row_ptr, target, relations, keep)
+        self._chk(self.lib.fmx_upload_block_rows_ex(self.h, slot, *args))
+        return args[3]
 
     def predict(self, slot, n_rows):
         out = np.zeros(n_rows, dtype=np.float64)
@@ -545,6 +554,11 @@ class Group:
         if rc != FMX_OK:
             raise FmxError(rc, self.lib.fmx_group_last_error(self.g).decode())
 
+    @property
+    def G(self):
+        """attribute groups (set_groups on the member handles)"""
+        return self.handles[0].G
+
     def set_params(self, w0, w, v):
         """the full fm_model block for every shard, crossing PCIe once (fmx_group_set_params)"""
         h0 = self.handles[0]
@@ -559,6 +573,13 @@ class Group:
         target = None if target is None else np.ascontiguousarray(target, dtype=np.float32)
         self._chk(self.lib.fmx_group_upload_rows(self.g, slot, _ptr(entries) if len(entries) else None, _ptr(row_ptr), _ptr(target),
                                                  len(row_ptr) - 1, len(entries)))
+
+    def upload_block_rows(self, slot, entries, row_ptr, target, relations, keep=False):
+        """Handle.upload_block_rows for every shard (fmx_group_upload_block_rows_ex).  keep=True: main rows and blocks stay apart
+        on every shard, each shard holding the block attributes it owns; keep=False: every shard joins the rows on the host."""
+        args, alive = _block_args(entries, row_ptr, target, relations, keep)
+        self._chk(self.lib.fmx_group_upload_block_rows_ex(self.g, slot, *args))
+        return args[3]
 
     def sgd_epoch(self, slot, mode=SGD_MINIBATCH, apply=APPLY_DEFAULT, batch=0, w0_chunk=0, flags=0, bias_lag=0):
         opts = SgdOpts(mode, apply, batch, w0_chunk, flags, bias_lag)
@@ -595,10 +616,11 @@ class Group:
     def als_end(self):
         self._chk(self.lib.fmx_group_als_end(self.g))
 
-    def get_params(self):
+    def get_params(self, w=None, v=None):
         """the full model: every shard writes its own features into the same host arrays"""
         h0 = self.handles[0]
-        w, v = np.zeros(h0.n, dtype=np.float64), np.zeros((h0.k, h0.n), dtype=np.float64)
+        w = np.zeros(h0.n, dtype=np.float64) if w is None else w
+        v = np.zeros((h0.k, h0.n), dtype=np.float64) if v is None else v
         w0 = 0.0
         for h in self.handles:
             w0, w, v = h.get_params(w, v)

@@ -28,6 +28,7 @@ extern "C++" void als_free(fmx_handle h) {
     if (b.cache) fmx_dev_free(b.cache);
     if (b.qb_all) fmx_dev_free(b.qb_all);
     if (b.cpart) fmx_dev_free(b.cpart);
+    if (b.delta) fmx_dev_free(b.delta);
   }
   a = AlsState();
 }
@@ -90,6 +91,17 @@ static int build_levels(fmx_handle h, const Slot& s, std::vector<uint32_t>& leve
   return FMX_OK;
 }
 
+// a kept block's rows: their partial sums (lin - 0.5 * sum of squares -> cpart, factor sums -> qb_all), each block row once
+static int block_eterms(fmx_handle h, const BlockRows& br, AlsBlock& ab) {
+  const uint32_t B = br.rows.n_rows;
+  Tab tb = h->tb;                                            // the block's attribute 0 is global attribute attr_offset (a shard: local rows, offset 0)
+  tb.V += (size_t)br.attr_offset * tb.rs; tb.w += (size_t)br.attr_offset * tb.ws;
+  KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_als_eterms<KP>), ((uint64_t)B + EtermsRows<KP>::R - 1) / EtermsRows<KP>::R, h->stream, br.rows.ent, br.rows.row_ptr, B, tb,
+                                     0, h->cfg.k1, (const double*)h->w0, (EQ*)nullptr, ab.qb_all, ab.cpart));
+  HIPCHK(h, hipGetLastError());
+  return FMX_OK;
+}
+
 // y-hat (and q_f for the coming sweep) of the session's rows.  With kept blocks the main rows and every block's rows are
 // evaluated separately -- a block row once, however many main rows map to it -- and combined through the mappings;
 // the squares are of the COMPLETE factor sums (k_als_set_e).
@@ -102,12 +114,9 @@ static int als_repredict(fmx_handle h, const Slot& s, AlsState& a) {
   for (size_t r = 0; r < s.blocks.size(); r++) {
     const BlockRows& br = *s.blocks[r];
     AlsBlock& ab = a.blk[r];
-    const uint32_t B = br.rows.n_rows;
-    Tab tb = h->tb;                                          // the block's attribute 0 is global attribute attr_offset
-    tb.V += (size_t)br.attr_offset * tb.rs; tb.w += (size_t)br.attr_offset * tb.ws;
-    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_als_eterms<KP>), ((uint64_t)B + EtermsRows<KP>::R - 1) / EtermsRows<KP>::R, h->stream, br.rows.ent, br.rows.row_ptr, B, tb,
-                                       0, h->cfg.k1, (const double*)h->w0, (EQ*)nullptr, ab.qb_all, ab.cpart));
-    hipLaunchKernelGGL(k_rel_combine, g1, b1, 0, h->stream, br.map, N, B, ab.cpart, ab.qb_all, h->cfg.num_factor, a.epart, a.q);
+    rc = block_eterms(h, br, ab);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_rel_combine, g1, b1, 0, h->stream, br.map, N, br.rows.n_rows, ab.cpart, ab.qb_all, h->cfg.num_factor, a.epart, a.q);
   }
   hipLaunchKernelGGL(k_als_set_e, g1, b1, 0, h->stream, a.e, a.epart, a.q, h->cfg.num_factor, N, h->cfg.k0, h->w0);
   HIPCHK(h, hipGetLastError());
@@ -285,6 +294,55 @@ int fmx_als_moments(fmx_handle h, double* out) {
   return rc;
 }
 
+// feature shards: y-hat and q_f of the session's rows.  Every shard sums the main rows and every kept block's rows over its own
+// features (partial sums); the partials are all-reduced, then every shard adds the blocks' sums to the main rows' through the
+// mappings -- identically, so each block counts once -- and finishes e = y-hat (k_als_set_e).  *bad: the shard that failed.
+static int group_repredict(fmx_group g, const std::vector<fmx_handle>& hs, size_t* bad) {
+  const size_t P = hs.size();
+  fmx_handle h0 = hs[0];
+  const Slot& s0 = h0->slots[h0->als.slot];
+  const uint32_t N = s0.n_rows;
+  const int kf = h0->cfg.num_factor;
+  const size_t R = s0.blocks.size();
+  for (size_t i = 0; i < P; i++) {
+    fmx_handle x = hs[i];
+    AlsState& a = x->als;
+    const Slot& s = x->slots[a.slot];
+    *bad = i;
+    HIPCHK(x, hipSetDevice(x->device));
+    int rc = als_eterms(x, s, a.e, a.q, a.epart);
+    for (size_t r = 0; r < R && rc == FMX_OK; r++) rc = block_eterms(x, *s.blocks[r], a.blk[r]);
+    if (rc) return rc;
+  }
+  *bad = 0;
+  std::vector<double*> bq(P), be(P);
+  for (size_t i = 0; i < P; i++) { bq[i] = hs[i]->als.q; be[i] = hs[i]->als.epart; }
+  int rc = kf > 0 ? group_allreduce_f64(g, bq, (size_t)kf * N) : FMX_OK;      // q is [KP][N]: the first k factor rows
+  if (rc == FMX_OK) rc = group_allreduce_f64(g, be, N);
+  for (size_t r = 0; r < R && rc == FMX_OK; r++) {
+    const uint32_t B = s0.blocks[r]->rows.n_rows;
+    for (size_t i = 0; i < P; i++) { bq[i] = hs[i]->als.blk[r].qb_all; be[i] = hs[i]->als.blk[r].cpart; }
+    rc = kf > 0 ? group_allreduce_f64(g, bq, (size_t)kf * B) : FMX_OK;        // qb_all is [KP][B]
+    if (rc == FMX_OK) rc = group_allreduce_f64(g, be, B);
+  }
+  if (rc) return rc;
+  const dim3 g1(std::min<uint32_t>((N + 255) / 256, 2048)), b1(256);
+  for (size_t i = 0; i < P; i++) {
+    fmx_handle x = hs[i];
+    AlsState& a = x->als;
+    const Slot& s = x->slots[a.slot];
+    *bad = i;
+    HIPCHK(x, hipSetDevice(x->device));
+    for (size_t r = 0; r < R; r++)
+      hipLaunchKernelGGL(k_rel_combine, g1, b1, 0, x->stream, s.blocks[r]->map, N, s.blocks[r]->rows.n_rows, a.blk[r].cpart, a.blk[r].qb_all,
+                         kf, a.epart, a.q);
+    hipLaunchKernelGGL(k_als_set_e, g1, b1, 0, x->stream, a.e, a.epart, a.q, kf, N, x->cfg.k0, x->w0);
+    HIPCHK(x, hipGetLastError());
+  }
+  *bad = 0;
+  return FMX_OK;
+}
+
 // one iteration of _learn over a list of feature shards (one unsharded handle: the list has one member and nothing is
 // exchanged).  Shards: the {e, q} cache is replicated; the draws of a (family, level) step record their changes
 // (AlsState::delta), one all-reduce per step sums them and every shard applies the same sum -- the replicas stay identical
@@ -431,49 +489,81 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
     }
     return FMX_OK;
   };
-  // kept `-relation` blocks (one unsharded handle): after the main features of a family, every block in turn -- caches from
-  // the main rows, the block's attributes level by level on the caches, the accumulated changes back (fm_learn_mcmc.h:478-509
-  // for w, :603-633 for v_f)
+  // kept `-relation` blocks: after the main features of a family, every block in turn -- caches from the main rows, the block's
+  // attributes level by level on the caches, the accumulated changes back (fm_learn_mcmc.h:478-509 for w, :603-633 for v_f).
+  // Shards: the caches are replicated (built from the replicated {e, q} and the all-reduced block sums); the block levels are
+  // GLOBAL, each shard draws its own attributes of a level and records the cache changes (AlsBlock::delta), one all-reduce of
+  // 4 B doubles per level sums them and every shard applies the sum
   auto block_steps = [&](int f /* -1: linear weights */) -> int {
-    fmx_handle h = hs[0];
-    AlsState& a = h->als;
-    const Slot& s = h->slots[a.slot];
-    hipStream_t st = h->stream;
-    for (size_t r = 0; r < s.blocks.size(); r++) {
-      const BlockRows& br = *s.blocks[r];
-      AlsBlock& ab = a.blk[r];
-      const uint32_t B = br.rows.n_rows;
+    const size_t R = hs[0]->slots[a0.slot].blocks.size();
+    for (size_t r = 0; r < R; r++) {
+      const uint32_t B = hs[0]->slots[a0.slot].blocks[r]->rows.n_rows;
       if (!B) continue;
-      const dim3 gb(std::min<uint32_t>((B + 31) / 32, 2048));
-      if (f >= 0) {
-        hipLaunchKernelGGL(k_rel_load_qb, dim3(std::min<uint32_t>((B + 255) / 256, 2048)), b1, 0, st, ab.cache, (const double*)(ab.qb_all + (size_t)f * B), B);
-        hipLaunchKernelGGL((k_rel_aggregate<true, 8>), gb, b1, 0, st, br.brow_ptr, br.brow_list, B, (const EQ*)a.e, ab.cache);
-      } else {
-        hipLaunchKernelGGL((k_rel_aggregate<false, 8>), gb, b1, 0, st, br.brow_ptr, br.brow_list, B, (const EQ*)a.e, ab.cache);
+      const dim3 gb(std::min<uint32_t>((B + 31) / 32, 2048)), gq(std::min<uint32_t>((B + 255) / 256, 2048));
+      for (fmx_handle x : hs) {
+        AlsState& a = x->als;
+        const BlockRows& br = *x->slots[a.slot].blocks[r];
+        AlsBlock& ab = a.blk[r];
+        HIPCHK(x, hipSetDevice(x->device));
+        if (f >= 0) {
+          hipLaunchKernelGGL(k_rel_load_qb, gq, b1, 0, x->stream, ab.cache, (const double*)(ab.qb_all + (size_t)f * B), B);
+          hipLaunchKernelGGL((k_rel_aggregate<true, 8>), gb, b1, 0, x->stream, br.brow_ptr, br.brow_list, B, (const EQ*)a.e, ab.cache);
+        } else {
+          hipLaunchKernelGGL((k_rel_aggregate<false, 8>), gb, b1, 0, x->stream, br.brow_ptr, br.brow_list, B, (const EQ*)a.e, ab.cache);
+        }
       }
-      const double* lam = (f < 0) ? a.prior : a.prior + (size_t)(1 + f) * 2 * NG;
-      const double* mu = lam + NG;
-      float* param = (f < 0) ? h->tb.w : h->tb.V + f;
-      const uint32_t pstride = (f < 0) ? h->tb.ws : h->tb.rs;
-      const uint64_t stream_id = (uint64_t)(a.iter * 1024 + (f < 0 ? 1000 : f));
-      const uint32_t nl = (uint32_t)ab.level_ptr.size() - 1;
+      const uint64_t stream_id = (uint64_t)(a0.iter * 1024 + (f < 0 ? 1000 : f));
+      const uint32_t nl = (uint32_t)a0.blk[r].level_ptr.size() - 1;
       for (uint32_t l = 0; l < nl; l++) {
-        const uint32_t cnt = ab.level_ptr[l + 1] - ab.level_ptr[l];
-        if (!cnt) continue;
+        bool any = false;
+        for (size_t i = 0; i < P; i++) {
+          fmx_handle h = hs[i];                                  // (the launch macros refer to `h`)
+          AlsState& a = h->als;
+          const BlockRows& br = *h->slots[a.slot].blocks[r];
+          AlsBlock& ab = a.blk[r];
+          const uint32_t cnt = ab.level_ptr[l + 1] - ab.level_ptr[l];
+          if (!cnt) continue;
+          any = true;
+          HIPCHK(h, hipSetDevice(h->device));
+          hipStream_t st = h->stream;
+          const double* lam = (f < 0) ? a.prior : a.prior + (size_t)(1 + f) * 2 * NG;
+          const double* mu = lam + NG;
+          float* param = (f < 0) ? h->tb.w : h->tb.V + f;
+          const uint32_t pstride = (f < 0) ? h->tb.ws : h->tb.rs;
+          const Shard sh = make_shard(h->cfg);
+          double* delta = sharded ? ab.delta : nullptr;
 #define FMX_REL_DRAW(ISV, GG) FMX_LAUNCH_WAVES((k_rel_draw<ISV, GG>), ((uint64_t)cnt * GG + 63) / 64, st, br.rows.t_ent, br.rows.seg_feat,        \
           br.rows.seg_rel, br.rows.nseg, (uint32_t)br.rows.nnz, ab.level_list + ab.level_ptr[l], cnt, param, pstride, br.attr_offset,             \
-          br.brow_ptr, B, ab.cache, opts->alpha, lam, mu, h->grp, opts->do_sample, opts->seed, stream_id)
-        if (f < 0) { if (ab.lanes <= 4) FMX_REL_DRAW(false, 4); else if (ab.lanes == 8) FMX_REL_DRAW(false, 8); else if (ab.lanes == 16) FMX_REL_DRAW(false, 16); else FMX_REL_DRAW(false, 64); }
-        else       { if (ab.lanes <= 4) FMX_REL_DRAW(true, 4);  else if (ab.lanes == 8) FMX_REL_DRAW(true, 8);  else if (ab.lanes == 16) FMX_REL_DRAW(true, 16);  else FMX_REL_DRAW(true, 64); }
+          br.brow_ptr, B, ab.cache, opts->alpha, lam, mu, h->grp, opts->do_sample, opts->seed, stream_id, sh, delta)
+          if (f < 0) { if (ab.lanes <= 4) FMX_REL_DRAW(false, 4); else if (ab.lanes == 8) FMX_REL_DRAW(false, 8); else if (ab.lanes == 16) FMX_REL_DRAW(false, 16); else FMX_REL_DRAW(false, 64); }
+          else       { if (ab.lanes <= 4) FMX_REL_DRAW(true, 4);  else if (ab.lanes == 8) FMX_REL_DRAW(true, 8);  else if (ab.lanes == 16) FMX_REL_DRAW(true, 16);  else FMX_REL_DRAW(true, 64); }
 #undef FMX_REL_DRAW
+          HIPCHK(h, hipGetLastError());
+        }
+        if (sharded && any) {
+          std::vector<double*> bufs(P);
+          for (size_t i = 0; i < P; i++) bufs[i] = hs[i]->als.blk[r].delta;
+          int rc = group_allreduce_f64(g, bufs, (size_t)4 * B);
+          if (rc) return rc;
+          for (fmx_handle x : hs) {
+            HIPCHK(x, hipSetDevice(x->device));
+            hipLaunchKernelGGL(k_rel_apply_delta, gq, b1, 0, x->stream, x->als.blk[r].cache, x->als.blk[r].delta, B);
+            HIPCHK(x, hipGetLastError());
+          }
+        }
       }
-      if (f >= 0) hipLaunchKernelGGL((k_rel_sync<true>), g1, b1, 0, st, br.map, N, B, (const double*)ab.cache, a.e);
-      else        hipLaunchKernelGGL((k_rel_sync<false>), g1, b1, 0, st, br.map, N, B, (const double*)ab.cache, a.e);
-      HIPCHK(h, hipGetLastError());
+      for (fmx_handle x : hs) {
+        AlsState& a = x->als;
+        const BlockRows& br = *x->slots[a.slot].blocks[r];
+        HIPCHK(x, hipSetDevice(x->device));
+        if (f >= 0) hipLaunchKernelGGL((k_rel_sync<true>), g1, b1, 0, x->stream, br.map, N, B, (const double*)a.blk[r].cache, a.e);
+        else        hipLaunchKernelGGL((k_rel_sync<false>), g1, b1, 0, x->stream, br.map, N, B, (const double*)a.blk[r].cache, a.e);
+        HIPCHK(x, hipGetLastError());
+      }
     }
     return FMX_OK;
   };
-  const bool has_blocks = !sharded && !h->slots[a0.slot].blocks.empty();
+  const bool has_blocks = !h->slots[a0.slot].blocks.empty();
   if (h->cfg.k1) {                                         // draw_w per level, :454-476
     for (uint32_t l = 0; l < n_levels; l++) { int rc = level_step(l, -1); if (rc) return rc; }
     if (has_blocks) { int rc = block_steps(-1); if (rc) return rc; }
@@ -518,21 +608,16 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
   }
 #undef FMX_ALS_DRAW
   // full re-prediction (fm_learn_mcmc_simultaneous.h:122), train metric and new residuals (:139-196)
-  for (fmx_handle x : hs) {
-    AlsState& a = x->als;
-    HIPCHK(x, hipSetDevice(x->device));
-    int rc = sharded ? als_eterms(x, x->slots[a.slot], a.e, a.q, a.epart) : als_repredict(x, x->slots[a.slot], a);
-    if (rc) return rc;
-  }
   if (sharded) {
-    std::vector<double*> bq(P), be(P);
-    for (size_t i = 0; i < P; i++) { bq[i] = hs[i]->als.q; be[i] = hs[i]->als.epart; }
-    int rc = kf > 0 ? group_allreduce_f64(g, bq, (size_t)kf * N) : FMX_OK;      // q is [KP][N]: the first k factor rows
-    if (rc == FMX_OK) rc = group_allreduce_f64(g, be, N);
-    if (rc) return rc;
+    size_t bad = 0;
+    int rc = group_repredict(g, hs, &bad);
+    if (rc) { if (bad) h->err = hs[bad]->err; return rc; }
+  } else {
     for (fmx_handle x : hs) {
+      AlsState& a = x->als;
       HIPCHK(x, hipSetDevice(x->device));
-      hipLaunchKernelGGL(k_als_set_e, g1, b1, 0, x->stream, x->als.e, x->als.epart, x->als.q, x->cfg.num_factor, N, x->cfg.k0, x->w0);
+      int rc = als_repredict(x, x->slots[a.slot], a);
+      if (rc) return rc;
     }
   }
   for (fmx_handle x : hs) {
@@ -560,49 +645,37 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
 }
 
 // ---- fm_learn_mcmc over feature shards (fmx_group) --------------------------------------------------------------
-// fmx_group_als_begin: every shard builds X^T of its own features; the dependency LEVELS are computed over the union of
-// the shards' columns in GLOBAL feature order (level(j) = 1 + max level of the smaller-id features sharing a row with j),
-// so that "level by level, every shard its features of the level" is exactly the reference's sequential sweep.
-int fmx_group_als_begin(fmx_group g, int train_slot) {
-  if (!g) return FMX_E_ARG;
-  for (fmx_handle x : g->hs) if (!x) return FMX_E_STATE;
-  fmx_handle h = g->hs[0];
-  if (g->kind == GROUP_SINGLE) { int rc = fmx_als_begin(h, train_slot); if (rc) g->err = h->err; return rc; }
+// The dependency LEVELS of one set of rows (the main rows, or one kept block's rows) over the union of the shards' columns in
+// GLOBAL feature order: level(j) = 1 + max level of the smaller-id features sharing a row with j -- so that "level by level, every
+// shard its features of the level" is exactly the reference's sequential sweep.  sl[i]: shard i's rows with X^T built
+// (ensure_segments).  Every shard gets the same number of levels (some may be empty): *level_ptr[i], the level-ordered column list
+// *d_list[i] on its device, and seen[i] marks its columns.  *bad: the shard that failed.
+static int global_levels(fmx_group g, const std::vector<Slot*>& sl, uint32_t n_rows, const std::vector<std::vector<uint32_t>*>& level_ptr,
+                         const std::vector<uint32_t**>& d_list, std::vector<std::vector<uint8_t>>& seen, size_t* bad) {
   const size_t P = g->hs.size();
   struct Col { uint32_t gid, shard, seg; };
   std::vector<Col> cols;
   std::vector<std::vector<uint32_t>> seg_feat(P), seg_rel(P);
   std::vector<std::vector<TEntry>> tent(P);
-  uint32_t N = 0;
-  auto bail = [&](int rc, fmx_handle x) { g->err = x->err; for (fmx_handle y : g->hs) als_free(y); return rc; };
   for (size_t i = 0; i < P; i++) {
     fmx_handle x = g->hs[i];
-    int rc = check_slot(x, train_slot, true);
-    if (rc == FMX_OK) rc = lag_flush(x);
-    if (rc) return bail(rc, x);
-    if (hipSetDevice(x->device) != hipSuccess || hipStreamSynchronize(x->stream) != hipSuccess) return bail(fail(x, FMX_E_HIP, "fmx_group_als_begin: device %d", x->device), x);
-    als_free(x);
-    Slot& s = x->slots[train_slot];
-    if (s.n_rows == 0) return bail(fail(x, FMX_E_ARG, "fmx_group_als_begin: empty training set"), x);
-    if (!s.blocks.empty()) return bail(fail(x, FMX_E_UNSUPPORTED, "fmx_group_als_begin: block-structured rows on feature shards are not implemented"), x);
-    if (i == 0) N = s.n_rows; else if (s.n_rows != N) return bail(fail(x, FMX_E_STATE, "the shards hold different numbers of rows"), x);
-    rc = ensure_segments(x, s, s.n_rows);
-    if (rc) return bail(rc, x);
-    x->als.slot = train_slot;
+    const Slot& s = *sl[i];
+    *bad = i;
     const uint32_t nseg = s.nseg;
     seg_feat[i].resize(nseg); seg_rel[i].resize((size_t)nseg + 1); tent[i].resize((size_t)s.nnz);
     if (nseg) {
-      if (hipMemcpy(seg_feat[i].data(), s.seg_feat, (size_t)nseg * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      if (hipSetDevice(x->device) != hipSuccess ||
+          hipMemcpy(seg_feat[i].data(), s.seg_feat, (size_t)nseg * 4, hipMemcpyDeviceToHost) != hipSuccess ||
           hipMemcpy(seg_rel[i].data(), s.seg_rel, (size_t)nseg * 4, hipMemcpyDeviceToHost) != hipSuccess ||
           hipMemcpy(tent[i].data(), s.t_ent, (size_t)s.nnz * sizeof(TEntry), hipMemcpyDeviceToHost) != hipSuccess)
-        return bail(fail(x, FMX_E_HIP, "fmx_group_als_begin: copying the columns of shard %zu failed", i), x);
+        return fail(x, FMX_E_HIP, "fmx_group_als_begin: copying the columns of shard %zu failed", i);
     }
     seg_rel[i][nseg] = (uint32_t)s.nnz;
     const Shard sh = make_shard(x->cfg);
     for (uint32_t sg = 0; sg < nseg; sg++) cols.push_back(Col{sh.global(seg_feat[i][sg]), (uint32_t)i, sg});
   }
   std::sort(cols.begin(), cols.end(), [](const Col& a, const Col& b) { return a.gid < b.gid; });
-  std::vector<uint32_t> rowlevel(N, 0);
+  std::vector<uint32_t> rowlevel(std::max<uint32_t>(n_rows, 1), 0);
   std::vector<std::vector<uint32_t>> lvl(P);
   for (size_t i = 0; i < P; i++) lvl[i].resize(seg_feat[i].size());
   uint32_t n_levels = 0;
@@ -618,21 +691,85 @@ int fmx_group_als_begin(fmx_group g, int train_slot) {
   }
   for (size_t i = 0; i < P; i++) {
     fmx_handle x = g->hs[i];
+    const uint32_t nseg = sl[i]->nseg;
+    *bad = i;
+    std::vector<uint32_t>& lp = *level_ptr[i];
+    lp.assign((size_t)n_levels + 1, 0);                             // the SAME number of levels on every shard (some may be empty)
+    for (uint32_t sg = 0; sg < nseg; sg++) lp[lvl[i][sg] + 1]++;
+    for (uint32_t l = 0; l < n_levels; l++) lp[l + 1] += lp[l];
+    std::vector<uint32_t> list(std::max<uint32_t>(nseg, 1)), fill(lp.begin(), lp.end());
+    for (uint32_t sg = 0; sg < nseg; sg++) list[fill[lvl[i][sg]]++] = sg;
+    for (uint32_t sg = 0; sg < nseg; sg++) seen[i][seg_feat[i][sg]] = 1;
+    HIPCHK(x, hipSetDevice(x->device));
+    HIPCHK(x, fmx_dev_alloc(d_list[i], list.size() * 4));
+    HIPCHK(x, hipMemcpy(*d_list[i], list.data(), list.size() * 4, hipMemcpyHostToDevice));
+  }
+  *bad = 0;
+  return FMX_OK;
+}
+
+// fmx_group_als_begin: every shard builds X^T of its own features (of the main rows and of every kept block's rows); the levels
+// are global (global_levels), the first prediction is all-reduced (group_repredict)
+int fmx_group_als_begin(fmx_group g, int train_slot) {
+  if (!g) return FMX_E_ARG;
+  for (fmx_handle x : g->hs) if (!x) return FMX_E_STATE;
+  fmx_handle h = g->hs[0];
+  if (g->kind == GROUP_SINGLE) { int rc = fmx_als_begin(h, train_slot); if (rc) g->err = h->err; return rc; }
+  const size_t P = g->hs.size();
+  uint32_t N = 0;
+  size_t R = 0;
+  auto bail = [&](int rc, fmx_handle x) { g->err = x->err; for (fmx_handle y : g->hs) als_free(y); return rc; };
+  for (size_t i = 0; i < P; i++) {
+    fmx_handle x = g->hs[i];
+    int rc = check_slot(x, train_slot, true);
+    if (rc == FMX_OK) rc = lag_flush(x);
+    if (rc) return bail(rc, x);
+    if (hipSetDevice(x->device) != hipSuccess || hipStreamSynchronize(x->stream) != hipSuccess) return bail(fail(x, FMX_E_HIP, "fmx_group_als_begin: device %d", x->device), x);
+    als_free(x);
+    Slot& s = x->slots[train_slot];
+    if (s.n_rows == 0) return bail(fail(x, FMX_E_ARG, "fmx_group_als_begin: empty training set"), x);
+    if (i == 0) { N = s.n_rows; R = s.blocks.size(); }
+    else if (s.n_rows != N) return bail(fail(x, FMX_E_STATE, "the shards hold different numbers of rows"), x);
+    if (s.blocks.size() != R) return bail(fail(x, FMX_E_STATE, "the shards hold different relation blocks"), x);
+    for (size_t r = 0; r < R; r++)
+      if (s.blocks[r]->rows.n_rows != g->hs[0]->slots[train_slot].blocks[r]->rows.n_rows)
+        return bail(fail(x, FMX_E_STATE, "the shards hold different relation blocks"), x);
+    rc = ensure_segments(x, s, s.n_rows);
+    for (size_t r = 0; r < R && rc == FMX_OK; r++)                  // (a shard that owns none of a block's attributes has no columns there)
+      if (s.blocks[r]->rows.nnz) rc = ensure_segments(x, s.blocks[r]->rows, std::max<uint32_t>(s.blocks[r]->rows.n_rows, 1));
+    if (rc) return bail(rc, x);
+    x->als.slot = train_slot;
+    x->als.blk.resize(R);
+  }
+  // ---- levels of the main features, then of every block's attributes over the block's own rows (two block attributes conflict
+  //      iff they share a block row)
+  std::vector<std::vector<uint8_t>> seen(P);
+  for (size_t i = 0; i < P; i++) seen[i].assign((size_t)g->hs[i]->n_local, 0);
+  {
+    std::vector<Slot*> sl(P);
+    std::vector<std::vector<uint32_t>*> lp(P);
+    std::vector<uint32_t**> dl(P);
+    size_t bad = 0;
+    for (size_t i = 0; i < P; i++) { sl[i] = &g->hs[i]->slots[train_slot]; lp[i] = &g->hs[i]->als.level_ptr; dl[i] = &g->hs[i]->als.level_list; }
+    int rc = global_levels(g, sl, N, lp, dl, seen, &bad);
+    if (rc) return bail(rc, g->hs[bad]);
+    for (size_t r = 0; r < R; r++) {
+      for (size_t i = 0; i < P; i++) {
+        sl[i] = &g->hs[i]->slots[train_slot].blocks[r]->rows;
+        lp[i] = &g->hs[i]->als.blk[r].level_ptr; dl[i] = &g->hs[i]->als.blk[r].level_list;
+      }
+      rc = global_levels(g, sl, g->hs[0]->slots[train_slot].blocks[r]->rows.n_rows, lp, dl, seen, &bad);
+      if (rc) return bail(rc, g->hs[bad]);
+    }
+  }
+  for (size_t i = 0; i < P; i++) {
+    fmx_handle x = g->hs[i];
     AlsState& a = x->als;
     Slot& s = x->slots[train_slot];
     const uint32_t nseg = s.nseg;
-    a.level_ptr.assign((size_t)n_levels + 1, 0);                  // the SAME number of levels on every shard (some may be empty)
-    for (uint32_t sg = 0; sg < nseg; sg++) a.level_ptr[lvl[i][sg] + 1]++;
-    for (uint32_t l = 0; l < n_levels; l++) a.level_ptr[l + 1] += a.level_ptr[l];
-    std::vector<uint32_t> list(std::max<uint32_t>(nseg, 1)), fill(a.level_ptr.begin(), a.level_ptr.end());
-    for (uint32_t sg = 0; sg < nseg; sg++) list[fill[lvl[i][sg]]++] = sg;
-    std::vector<uint8_t> seen((size_t)x->n_local, 0);
-    for (uint32_t sg = 0; sg < nseg; sg++) seen[seg_feat[i][sg]] = 1;
     hipError_t er = hipSetDevice(x->device);
-    if (er == hipSuccess) er = fmx_dev_alloc(&a.level_list, list.size() * 4);
-    if (er == hipSuccess) er = hipMemcpy(a.level_list, list.data(), list.size() * 4, hipMemcpyHostToDevice);
-    if (er == hipSuccess) er = fmx_dev_alloc(&a.seen, seen.size());
-    if (er == hipSuccess) er = hipMemcpy(a.seen, seen.data(), seen.size(), hipMemcpyHostToDevice);
+    if (er == hipSuccess) er = fmx_dev_alloc(&a.seen, seen[i].size());
+    if (er == hipSuccess) er = hipMemcpy(a.seen, seen[i].data(), seen[i].size(), hipMemcpyHostToDevice);
     if (er == hipSuccess) er = fmx_dev_alloc(&a.e, (size_t)N * sizeof(EQ));
     if (er == hipSuccess) er = fmx_dev_alloc(&a.q, (size_t)N * (size_t)x->KP * sizeof(double));
     if (er == hipSuccess) er = fmx_dev_alloc(&a.delta, (size_t)N * sizeof(EQ));
@@ -642,22 +779,30 @@ int fmx_group_als_begin(fmx_group g, int train_slot) {
       a.vt_stride = ((size_t)nseg + 63) & ~(size_t)63;
       er = fmx_dev_alloc(&a.vt, (size_t)x->cfg.num_factor * a.vt_stride * sizeof(float));
     }
+    for (size_t r = 0; r < R && er == hipSuccess; r++) {         // the kept blocks' caches (replicated) and their per-level changes
+      const BlockRows& br = *s.blocks[r];
+      AlsBlock& ab = a.blk[r];
+      const size_t B = std::max<uint32_t>(br.rows.n_rows, 1);
+      er = fmx_dev_alloc(&ab.cache, (size_t)7 * B * sizeof(double));
+      if (er == hipSuccess) er = hipMemsetAsync(ab.cache, 0, (size_t)7 * B * sizeof(double), x->stream);
+      if (er == hipSuccess) er = fmx_dev_alloc(&ab.qb_all, (size_t)x->KP * B * sizeof(double));
+      if (er == hipSuccess) er = fmx_dev_alloc(&ab.cpart, B * sizeof(double));
+      if (er == hipSuccess) er = fmx_dev_alloc(&ab.delta, (size_t)4 * B * sizeof(double));
+      if (er == hipSuccess) er = hipMemsetAsync(ab.delta, 0, (size_t)4 * B * sizeof(double), x->stream);
+      const double avg_col = br.rows.nseg ? (double)br.rows.nnz / (double)br.rows.nseg : 0.0;
+      ab.lanes = avg_col <= 5.0 ? 4 : (avg_col <= 12.0 ? 8 : (avg_col <= 40.0 ? 16 : 64));
+    }
     if (er != hipSuccess) return bail(fail(x, FMX_E_HIP, "fmx_group_als_begin: %s", hipGetErrorString(er)), x);
-    // first prediction (fm_learn_mcmc_simultaneous.h:69-86): partial sums of this shard
-    int rc = als_eterms(x, s, a.e, a.q, a.epart);
-    if (rc) return bail(rc, x);
   }
+  // ---- first prediction and e -= target (fm_learn_mcmc_simultaneous.h:69-86)
   {
-    std::vector<double*> bq(P), be(P);
-    for (size_t i = 0; i < P; i++) { bq[i] = g->hs[i]->als.q; be[i] = g->hs[i]->als.epart; }
-    int rc = h->cfg.num_factor > 0 ? group_allreduce_f64(g, bq, (size_t)h->cfg.num_factor * N) : FMX_OK;
-    if (rc == FMX_OK) rc = group_allreduce_f64(g, be, N);
-    if (rc) return bail(rc, h);
+    size_t bad = 0;
+    int rc = group_repredict(g, g->hs, &bad);
+    if (rc) return bail(rc, g->hs[bad]);
   }
   const dim3 g1(std::min<uint32_t>((N + 255) / 256, 2048)), b1(256);
   for (fmx_handle x : g->hs) {
     hipSetDevice(x->device);
-    hipLaunchKernelGGL(k_als_set_e, g1, b1, 0, x->stream, x->als.e, x->als.epart, x->als.q, x->cfg.num_factor, N, x->cfg.k0, x->w0);
     hipLaunchKernelGGL(k_als_sub_target, g1, b1, 0, x->stream, x->als.e, x->slots[train_slot].target, N);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(x->stream) != hipSuccess)
       return bail(fail(x, FMX_E_HIP, "fmx_group_als_begin: first prediction failed on shard device %d", x->device), x);

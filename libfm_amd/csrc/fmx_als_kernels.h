@@ -672,14 +672,18 @@ k_rel_aggregate(const uint32_t* __restrict__ brow_ptr, const uint32_t* __restric
   }
 }
 
-// one group of G lanes per block attribute of the current level (columns of the block's X^T: {block row, value})
+// one group of G lanes per block attribute of the current level (columns of the block's X^T: {block row, value}).
+// Feature shards: the block's ids are the shard's local table rows (attr_offset 0) -- the noise is keyed by the GLOBAL id
+// (sh.global), so the chain is the one-handle chain -- and the changes of the caches go to delta ([4][B]: we, weq, qb, dy)
+// instead of into the replicated cache; the caller all-reduces them and applies the sum on every shard (k_rel_apply_delta).
 template <bool IS_V, int G>
 __global__ void __launch_bounds__(256)
 k_rel_draw(const TEntry* __restrict__ t_ent, const uint32_t* __restrict__ seg_feat, const uint32_t* __restrict__ seg_rel,
            uint32_t nseg_total, uint32_t nnz, const uint32_t* __restrict__ seg_list, uint32_t n_list,
            float* __restrict__ param, uint32_t pstride, uint32_t attr_offset, const uint32_t* __restrict__ brow_ptr, uint32_t B,
            double* __restrict__ cache, double alpha, const double* __restrict__ lambda_g, const double* __restrict__ mu_g,
-           const uint32_t* __restrict__ attr_group, int do_sample, uint64_t seed, uint64_t stream) {
+           const uint32_t* __restrict__ attr_group, int do_sample, uint64_t seed, uint64_t stream, const Shard sh,
+           double* __restrict__ delta /* feature shards: [4][B], else null */) {
   constexpr uint32_t GPW = 64 / G;
   const uint32_t lane = (threadIdx.x & 63u) % G, grp = (threadIdx.x & 63u) / G;
   const uint32_t wave0 = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -690,7 +694,7 @@ k_rel_draw(const TEntry* __restrict__ t_ent, const uint32_t* __restrict__ seg_fe
     const uint32_t li = lw + grp;
     const bool have = li < n_list;
     const uint32_t s = seg_list[have ? li : n_list - 1];
-    const uint32_t j = seg_feat[s] + attr_offset;                  // global attribute id (libfm.cpp:213-216)
+    const uint32_t j = seg_feat[s] + attr_offset;                  // table row: the global attribute id (libfm.cpp:213-216), on a shard the local row
     const uint32_t g = attr_group ? attr_group[j] : 0u;
     const double lambda = lambda_g[g], mu = mu_g[g];
     const uint32_t a = seg_rel[s];
@@ -719,7 +723,7 @@ k_rel_draw(const TEntry* __restrict__ t_ent, const uint32_t* __restrict__ seg_fe
     const double mean = -sigma_sqr * (alpha * t_he - mu * lambda);
     double nt;
     if (isnan(sigma_sqr) || isinf(sigma_sqr)) nt = 0.0;
-    else nt = do_sample ? mean + sqrt(sigma_sqr) * gauss_hash(seed, stream, j) : mean;
+    else nt = do_sample ? mean + sqrt(sigma_sqr) * gauss_hash(seed, stream, sh.global(j)) : mean;
     if (isnan(nt) || isinf(nt)) continue;
     const float ntf = (float)nt;
     const double d = th - (double)ntf;                               // theta_old - theta (of the STORED value)
@@ -746,7 +750,8 @@ k_rel_draw(const TEntry* __restrict__ t_ent, const uint32_t* __restrict__ seg_fe
             c_weq -= d * (h * c_wc + x * c_wc2);                     // :901
             c_dy -= d * h;                                           // :902  y += (v - v_old) h
           }
-          weq[r] = c_weq; qb[r] = c_q;
+          if (delta) { delta[(size_t)B + r] = c_weq - weq[r]; delta[(size_t)2 * B + r] = c_q - qb[r]; }
+          else { weq[r] = c_weq; qb[r] = c_q; }
         } else {
           for (uint32_t i2 = i; i2 < b; i2++) {
             const TEntry t2 = t_ent[i2];
@@ -756,8 +761,20 @@ k_rel_draw(const TEntry* __restrict__ t_ent, const uint32_t* __restrict__ seg_fe
             c_dy -= d * x;                                           // :787  y += (w - w_old) h
           }
         }
-        we[r] = c_we; dy[r] = c_dy;
+        if (delta) { delta[r] = c_we - we[r]; delta[(size_t)3 * B + r] = c_dy - dy[r]; }
+        else { we[r] = c_we; dy[r] = c_dy; }
       }
+    }
+  }
+}
+// feature shards: the all-reduced changes of a level's draws (k_rel_draw's delta) into the replicated cache, delta back to 0
+// (at most one attribute of a GLOBAL level touches a block row, so the sum holds one writer's change per row)
+static __global__ void k_rel_apply_delta(double* __restrict__ cache, double* __restrict__ delta, uint32_t B) {
+  for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {
+    const double d0 = delta[b], d1 = delta[(size_t)B + b], d2 = delta[(size_t)2 * B + b], d3 = delta[(size_t)3 * B + b];
+    if (d0 != 0.0 || d1 != 0.0 || d2 != 0.0 || d3 != 0.0) {
+      cache[b] += d0; cache[(size_t)B + b] += d1; cache[(size_t)4 * B + b] += d2; cache[(size_t)5 * B + b] += d3;
+      delta[b] = 0.0; delta[(size_t)B + b] = 0.0; delta[(size_t)2 * B + b] = 0.0; delta[(size_t)3 * B + b] = 0.0;
     }
   }
 }
@@ -794,14 +811,15 @@ k_rel_combine(const uint32_t* __restrict__ map, uint32_t n, uint32_t B, const do
     for (int f = 0; f < k; f++) q[(size_t)f * n + c] += qb_all[(size_t)f * B + b];
   }
 }
-// the fp32 form for fmx_predict / fmx_evaluate: partial buffers [rows][KP] + [rows] (k_rowsums<KP, true, false>)
+// the fp32 form for fmx_predict / fmx_evaluate: partial buffers [rows][KP] + [rows] (k_rowsums<KP, true, false>) of the main
+// rows row0 .. row0 + n - 1
 template <int KP>
 __global__ void __launch_bounds__(256)
-k_rel_add_partial(const uint32_t* __restrict__ map, uint32_t n, uint32_t B, const float* __restrict__ pb, float* __restrict__ pm) {
+k_rel_add_partial(const uint32_t* __restrict__ map, uint64_t row0, uint32_t n, uint32_t B, const float* __restrict__ pb, float* __restrict__ pm) {
   const uint64_t total = (uint64_t)n * (KP + 1);
   for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
     const uint32_t c = (uint32_t)(t / (KP + 1)); const uint32_t f = (uint32_t)(t % (KP + 1));
-    const uint32_t b = map[c];
+    const uint32_t b = map[row0 + c];
     if (f < KP) pm[(size_t)c * KP + f] += pb[(size_t)b * KP + f];
     else pm[(size_t)n * KP + c] += pb[(size_t)B * KP + b];
   }

@@ -653,6 +653,33 @@ int fmx_group_upload_rows(fmx_group g, int slot, const void* entries, const uint
   return FMX_OK;
 }
 
+// block-structured rows over the shards (fmx_upload_block_rows_ex per shard).  FMX_BLOCKS_KEEP: the main rows take the
+// fmx_group_upload_rows path (filtered per shard on its device); every shard then keeps each block's rows restricted to the block
+// attributes it owns, and the mapping and its inverse whole (attach_kept_blocks)
+int fmx_group_upload_block_rows_ex(fmx_group g, int slot, const void* entries, const uint64_t* row_ptr, const float* target, uint32_t n_rows,
+                                   uint64_t nnz, const fmx_relation* relations, uint32_t n_relations, uint32_t flags) {
+  if (!g) return FMX_E_ARG;
+  for (auto m : g->hs) if (!m) return gfail(g, FMX_E_STATE, "a member of the group was destroyed");
+  fmx_handle cur = g->hs[0];
+  if (g->hs.size() == 1 || g->kind == GROUP_SINGLE) {
+    for (auto m : g->hs) { cur = m; GCHK(g, fmx_upload_block_rows_ex(m, slot, entries, row_ptr, target, n_rows, nnz, relations, n_relations, flags)); }
+    return FMX_OK;
+  }
+  if (n_relations == 0) return fmx_group_upload_rows(g, slot, entries, row_ptr, target, n_rows, nnz);
+  if (!(flags & FMX_BLOCKS_KEEP)) {                             // each shard joins the rows on the host and keeps its own features
+    for (auto m : g->hs) { cur = m; GCHK(g, fmx_upload_block_rows_ex(m, slot, entries, row_ptr, target, n_rows, nnz, relations, n_relations, flags)); }
+    return FMX_OK;
+  }
+  if (slot < 0 || slot >= FMX_MAX_SLOTS) return gfail(g, FMX_E_ARG, "slot %d out of range", slot);
+  for (auto m : g->hs) { cur = m; GCHK(g, slot_in_session(m, slot, "fmx_group_upload_block_rows_ex")); }
+  cur = g->hs[0];
+  GCHK(g, check_block_rows(cur, entries, row_ptr, n_rows, nnz, relations, n_relations));
+  int rc = fmx_group_upload_rows(g, slot, entries, row_ptr, target, n_rows, nnz);
+  if (rc) return rc;
+  for (auto m : g->hs) { cur = m; GCHK(g, attach_kept_blocks(m, slot, n_rows, relations, n_relations)); }
+  return FMX_OK;
+}
+
 // ---- small batches, one host thread per shard -------------------------------------------------------------------------------------------
 // A 512-row batch on a feature shard is three launches of a few microseconds each; issued for eight shards by ONE thread the host is the
 // bottleneck twice over (its calls are serial, and on one stream so are the shards' launches).  Here every shard has its own host thread
@@ -751,6 +778,7 @@ int fmx_group_sgd_epoch(fmx_group g, int slot, const fmx_sgd_opts* opts_in, fmx_
   for (size_t i = 0; i < n; i++) {
     cur = g->hs[i];
     GCHK(g, check_slot(cur, slot, true));
+    if (!cur->slots[slot].blocks.empty()) return gfail(g, FMX_E_UNSUPPORTED, "relations are not supported with SGD");   // fm_learn_sgd.h:61-63
     if (cur->slots[slot].n_rows != g->hs[0]->slots[slot].n_rows) return gfail(g, FMX_E_STATE, "the shards hold different numbers of rows in slot %d", slot);
   }
   fmx_sgd_opts opts = *opts_in;
@@ -888,6 +916,35 @@ int fmx_group_sgd_epoch(fmx_group g, int slot, const fmx_sgd_opts* opts_in, fmx_
   return FMX_OK;
 }
 
+// kept blocks on a shard: the partial sums of every block's rows over the shard's own block attributes (into BlockRows::pbuf, once
+// per fmx_group_predict), and of a chunk of main rows (S [nb][KP], c [nb]) plus -- through the mappings -- those block sums
+static int kept_block_partials(fmx_handle h, const Slot& s) {
+  for (BlockRows* br : s.blocks) {
+    const uint32_t B = br->rows.n_rows;
+    if (!B) continue;
+    Tab tb = h->tb;                                            // (a shard's block ids are local rows: attr_offset 0)
+    tb.V += (size_t)br->attr_offset * tb.rs; tb.w += (size_t)br->attr_offset * tb.ws;
+    float* Sb = br->pbuf;
+    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false>), B, h->stream, br->rows.ent, br->rows.row_ptr, (uint64_t)0, B, tb, h->cfg.k1,
+                                       Sb, Sb + (size_t)B * h->KP, (const float*)nullptr));
+  }
+  HIPCHK(h, hipGetLastError());
+  return FMX_OK;
+}
+static int kept_chunk_partial(fmx_handle h, const Slot& s, uint64_t row0, uint32_t nb, float* part) {
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = sgd_partial_rows(h, s, row0, nb, part, part + (size_t)nb * h->KP, h->stream);
+  if (rc) return rc;
+  for (BlockRows* br : s.blocks) {
+    const uint32_t B = br->rows.n_rows;
+    if (!B) continue;
+    KP_SWITCH(h->KP, hipLaunchKernelGGL((k_rel_add_partial<KP>), dim3(std::min<uint32_t>((uint32_t)(((uint64_t)nb * (h->KP + 1) + 255) / 256), 4096)),
+                                          dim3(256), 0, h->stream, br->map, row0, nb, B, (const float*)br->pbuf, part));
+  }
+  HIPCHK(h, hipGetLastError());
+  return FMX_OK;
+}
+
 // y-hat of every row of a slot over the shards (raw, like fmx_predict): partial sums -> exchange -> finish on shard 0
 int fmx_group_predict(fmx_group g, int slot, double* out) {
   if (!g || !out) return FMX_E_ARG;
@@ -900,6 +957,13 @@ int fmx_group_predict(fmx_group g, int slot, double* out) {
   const uint32_t n_rows = h0->slots[slot].n_rows;
   const size_t kp1 = (size_t)h0->KP + 1;
   const uint32_t chunk = 1u << 18;
+  bool kept = false;
+  for (size_t i = 0; i < n; i++) {
+    cur = g->hs[i];
+    if (cur->slots[slot].n_rows != n_rows) return gfail(g, FMX_E_STATE, "the shards hold different numbers of rows in slot %d", slot);
+    if (cur->slots[slot].blocks.size() != h0->slots[slot].blocks.size()) return gfail(g, FMX_E_STATE, "the shards hold different blocks in slot %d", slot);
+    if (!cur->slots[slot].blocks.empty()) { kept = true; HIPCHK(cur, hipSetDevice(cur->device)); GCHK(g, kept_block_partials(cur, cur->slots[slot])); }
+  }
   std::vector<float> tmp(std::min<uint32_t>(chunk, std::max<uint32_t>(n_rows, 1)));
   for (size_t i = 0; i < n; i++) { cur = g->hs[i]; GCHK(g, ensure_xbuf(cur, (size_t)tmp.size() * kp1)); }
   float* d_y = nullptr;
@@ -908,7 +972,10 @@ int fmx_group_predict(fmx_group g, int slot, double* out) {
   int rc = FMX_OK;
   for (uint64_t r0 = 0; r0 < n_rows && rc == FMX_OK; r0 += chunk) {
     const uint32_t nb = (uint32_t)std::min<uint64_t>(chunk, n_rows - r0);
-    for (size_t i = 0; i < n && rc == FMX_OK; i++) { cur = g->hs[i]; rc = fmx_sgd_partial(cur, slot, r0, nb, cur->xbuf[0], cur->stream); }
+    for (size_t i = 0; i < n && rc == FMX_OK; i++) {
+      cur = g->hs[i];
+      rc = kept ? kept_chunk_partial(cur, cur->slots[slot], r0, nb, cur->xbuf[0]) : fmx_sgd_partial(cur, slot, r0, nb, cur->xbuf[0], cur->stream);
+    }
     if (rc == FMX_OK) rc = exchange_begin(g, 0, (size_t)nb * kp1);
     if (rc == FMX_OK) rc = exchange_end(g, 0);
     if (rc == FMX_OK) rc = fmx_predict_finish(h0, nb, sum_of(g, 0, 0), d_y, h0->stream);

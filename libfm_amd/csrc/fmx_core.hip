@@ -190,7 +190,7 @@ int launch_rest(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, float* r
       KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false>), B, st, br->rows.ent, br->rows.row_ptr, (uint64_t)0, B, tb, h->cfg.k1,
                                          Sb, Sb + (size_t)B * h->KP, (const float*)nullptr));
       KP_SWITCH(h->KP, hipLaunchKernelGGL((k_rel_add_partial<KP>), dim3(std::min<uint32_t>((uint32_t)(((uint64_t)n * (h->KP + 1) + 255) / 256), 4096)),
-                                            dim3(256), 0, st, br->map, n, B, (const float*)Sb, S));
+                                            dim3(256), 0, st, br->map, (uint64_t)0, n, B, (const float*)Sb, S));
     }
     KP_SWITCH(h->KP, hipLaunchKernelGGL((k_rest_from_partial<KP>), dim3(wave_grid((n + Map<KP>::EPI - 1) / Map<KP>::EPI)), dim3(256), 0, st,
                                           (const float*)S, (const float*)c, n, rest));
@@ -1291,29 +1291,50 @@ int fmx_upload_rows(fmx_handle h, int slot, const void* entries, const uint64_t*
   return FMX_OK;
 }
 
-// FMX_BLOCKS_KEEP: the main rows and every block stay apart on the device -- nothing of the size of the joined table is
-// built.  fm_model::predict and the ALS / MCMC sweeps then work block-wise (fmx_als.hip, k_rel_*).
-static int upload_blocks_kept(fmx_handle h, int slot, const void* entries, const uint64_t* row_ptr, const float* target,
-                              uint32_t n_rows, uint64_t nnz, const fmx_relation* relations, uint32_t n_relations) {
-  int rc = fmx_upload_rows(h, slot, entries, row_ptr, target, n_rows, nnz);          // the main rows as any other data set
-  if (rc) return rc;
+// The kept blocks of a slot whose main rows are in place (FMX_BLOCKS_KEEP): every block's own rows, the mapping and its inverse.
+// A feature shard keeps the block attributes it owns -- owner = the shard rule on the global id attr_offset + j -- and their ids
+// become its local table rows (the block's attr_offset is 0 there, so the kernels read w, V and the groups at the local row);
+// the mapping and its inverse depend on the rows alone and are the same on every shard, a block none of whose attributes the
+// shard owns included.
+extern "C++" int attach_kept_blocks(fmx_handle h, int slot, uint32_t n_rows, const fmx_relation* relations, uint32_t n_relations) {
+  HIPCHK(h, hipSetDevice(h->device));
   Slot& s = h->slots[slot];
+  const bool sharded = h->cfg.shard_world > 1;
+  const Shard sh = make_shard(h->cfg);
   for (uint32_t r = 0; r < n_relations; r++) {
     const fmx_relation& q = relations[r];
     BlockRows* b = new BlockRows();
     s.blocks.push_back(b);
-    b->attr_offset = (uint32_t)q.attr_offset;
+    const Entry* qe = static_cast<const Entry*>(q.entries);
+    const uint64_t* qp = q.row_ptr;
+    uint64_t qnnz = q.nnz;
+    std::vector<Entry> le;
+    std::vector<uint64_t> lp;
+    if (sharded) {
+      lp.resize((size_t)q.n_rows + 1);
+      le.reserve((size_t)(q.nnz / h->cfg.shard_world + 1));
+      for (uint32_t i = 0; i < q.n_rows; i++) {
+        lp[i] = le.size();
+        for (uint64_t t = q.row_ptr[i]; t < q.row_ptr[i + 1]; t++) {
+          Entry e;
+          if (sh.place((uint32_t)(qe[t].id + q.attr_offset), &e.id)) { e.value = qe[t].value; le.push_back(e); }
+        }
+      }
+      lp[q.n_rows] = le.size();
+      qe = le.data(); qp = lp.data(); qnnz = le.size();
+    }
+    b->attr_offset = sharded ? 0u : (uint32_t)q.attr_offset;
     std::vector<uint32_t> cnt((size_t)q.n_rows + 1, 0), list(std::max<uint32_t>(n_rows, 1));
     for (uint32_t c = 0; c < n_rows; c++) cnt[q.data_row_to_relation_row[c] + 1]++;
     for (uint32_t i = 0; i < q.n_rows; i++) cnt[i + 1] += cnt[i];
     { std::vector<uint32_t> fill(cnt.begin(), cnt.end() - 1);
       for (uint32_t c = 0; c < n_rows; c++) list[fill[q.data_row_to_relation_row[c]]++] = c; }   // ascending main row inside a block row
     uint32_t max_row = 0;
-    for (uint32_t i = 0; i < q.n_rows; i++) max_row = std::max<uint32_t>(max_row, (uint32_t)(q.row_ptr[i + 1] - q.row_ptr[i]));
-    hipError_t er = fmx_dev_alloc(&b->rows.ent, std::max<uint64_t>(q.nnz, 1) * sizeof(Entry));
-    if (er == hipSuccess && q.nnz) er = hipMemcpy(b->rows.ent, q.entries, q.nnz * sizeof(Entry), hipMemcpyHostToDevice);
+    for (uint32_t i = 0; i < q.n_rows; i++) max_row = std::max<uint32_t>(max_row, (uint32_t)(qp[i + 1] - qp[i]));
+    hipError_t er = fmx_dev_alloc(&b->rows.ent, std::max<uint64_t>(qnnz, 1) * sizeof(Entry));
+    if (er == hipSuccess && qnnz) er = hipMemcpy(b->rows.ent, qe, qnnz * sizeof(Entry), hipMemcpyHostToDevice);
     if (er == hipSuccess) er = fmx_dev_alloc(&b->rows.row_ptr, ((size_t)q.n_rows + 1) * sizeof(uint64_t));
-    if (er == hipSuccess) er = hipMemcpy(b->rows.row_ptr, q.row_ptr, ((size_t)q.n_rows + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (er == hipSuccess) er = hipMemcpy(b->rows.row_ptr, qp, ((size_t)q.n_rows + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
     if (er == hipSuccess) er = fmx_dev_alloc(&b->map, std::max<uint32_t>(n_rows, 1) * sizeof(uint32_t));
     if (er == hipSuccess && n_rows) er = hipMemcpy(b->map, q.data_row_to_relation_row, (size_t)n_rows * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (er == hipSuccess) er = fmx_dev_alloc(&b->brow_ptr, cnt.size() * sizeof(uint32_t));
@@ -1322,25 +1343,24 @@ static int upload_blocks_kept(fmx_handle h, int slot, const void* entries, const
     if (er == hipSuccess) er = hipMemcpy(b->brow_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (er == hipSuccess) er = fmx_dev_alloc(&b->pbuf, std::max<size_t>((size_t)q.n_rows, 1) * (size_t)(h->KP + 1) * sizeof(float));
     if (er != hipSuccess) { free_slot(s); return fail(h, FMX_E_HIP, "fmx_upload_block_rows_ex: %s", hipGetErrorString(er)); }
-    b->rows.n_rows = q.n_rows; b->rows.nnz = q.nnz; b->rows.max_row = max_row; b->rows.used = true;
+    b->rows.n_rows = q.n_rows; b->rows.nnz = qnnz; b->rows.max_row = max_row; b->rows.used = true;
   }
   return FMX_OK;
 }
 
-int fmx_upload_block_rows(fmx_handle h, int slot, const void* entries, const uint64_t* row_ptr, const float* target,
-                          uint32_t n_rows, uint64_t nnz, const fmx_relation* relations, uint32_t n_relations) {
-  return fmx_upload_block_rows_ex(h, slot, entries, row_ptr, target, n_rows, nnz, relations, n_relations, FMX_BLOCKS_EXPAND);
+// FMX_BLOCKS_KEEP: the main rows and every block stay apart on the device -- nothing of the size of the joined table is
+// built.  fm_model::predict and the ALS / MCMC sweeps then work block-wise (fmx_als.hip, k_rel_*).
+static int upload_blocks_kept(fmx_handle h, int slot, const void* entries, const uint64_t* row_ptr, const float* target,
+                              uint32_t n_rows, uint64_t nnz, const fmx_relation* relations, uint32_t n_relations) {
+  int rc = fmx_upload_rows(h, slot, entries, row_ptr, target, n_rows, nnz);          // the main rows as any other data set
+  if (rc) return rc;
+  return attach_kept_blocks(h, slot, n_rows, relations, n_relations);
 }
 
-int fmx_upload_block_rows_ex(fmx_handle h, int slot, const void* entries, const uint64_t* row_ptr, const float* target,
-                             uint32_t n_rows, uint64_t nnz, const fmx_relation* relations, uint32_t n_relations, uint32_t flags) {
-  if (!h) return FMX_E_ARG;
-  if (n_relations == 0) return fmx_upload_rows(h, slot, entries, row_ptr, target, n_rows, nnz);
-  if (slot < 0 || slot >= FMX_MAX_SLOTS) return fail(h, FMX_E_ARG, "slot %d out of range", slot);
-  { int _rc = slot_in_session(h, slot, "fmx_upload_block_rows"); if (_rc) return _rc; }
+// what fmx_upload_block_rows_ex checks before anything reaches the device (fmx_group_upload_block_rows_ex checks the same)
+extern "C++" int check_block_rows(fmx_handle h, const void* entries, const uint64_t* row_ptr, uint32_t n_rows, uint64_t nnz,
+                     const fmx_relation* relations, uint32_t n_relations) {
   if (!relations || n_relations > FMX_MAX_RELATIONS) return fail(h, FMX_E_ARG, "fmx_upload_block_rows: 1..%d relations", FMX_MAX_RELATIONS);
-  if (h->cfg.shard_world > 1 && (flags & FMX_BLOCKS_KEEP))
-    return fail(h, FMX_E_UNSUPPORTED, "kept relation blocks on a feature shard are not implemented: upload them with FMX_BLOCKS_EXPAND");
   if (!row_ptr || (nnz > 0 && !entries)) return fail(h, FMX_E_ARG, "fmx_upload_block_rows: null entries/row_ptr");
   if (row_ptr[0] != 0 || row_ptr[n_rows] != nnz) return fail(h, FMX_E_ARG, "row_ptr[0] must be 0 and row_ptr[n_rows] == nnz");
   const uint64_t n = h->cfg.num_attribute;
@@ -1360,6 +1380,25 @@ int fmx_upload_block_rows_ex(fmx_handle h, int slot, const void* entries, const 
       if (q.data_row_to_relation_row[c] >= q.n_rows)
         return fail(h, FMX_E_ARG, "relation %u: main row %u maps to block row %u >= %u", r, c, q.data_row_to_relation_row[c], q.n_rows);
   }
+  return FMX_OK;
+}
+
+int fmx_upload_block_rows(fmx_handle h, int slot, const void* entries, const uint64_t* row_ptr, const float* target,
+                          uint32_t n_rows, uint64_t nnz, const fmx_relation* relations, uint32_t n_relations) {
+  return fmx_upload_block_rows_ex(h, slot, entries, row_ptr, target, n_rows, nnz, relations, n_relations, FMX_BLOCKS_EXPAND);
+}
+
+int fmx_upload_block_rows_ex(fmx_handle h, int slot, const void* entries, const uint64_t* row_ptr, const float* target,
+                             uint32_t n_rows, uint64_t nnz, const fmx_relation* relations, uint32_t n_relations, uint32_t flags) {
+  if (!h) return FMX_E_ARG;
+  if (n_relations == 0) return fmx_upload_rows(h, slot, entries, row_ptr, target, n_rows, nnz);
+  if (slot < 0 || slot >= FMX_MAX_SLOTS) return fail(h, FMX_E_ARG, "slot %d out of range", slot);
+  { int _rc = slot_in_session(h, slot, "fmx_upload_block_rows"); if (_rc) return _rc; }
+  if (!relations || n_relations > FMX_MAX_RELATIONS) return fail(h, FMX_E_ARG, "fmx_upload_block_rows: 1..%d relations", FMX_MAX_RELATIONS);
+  if (h->cfg.shard_world > 1 && (flags & FMX_BLOCKS_KEEP))          // (kept blocks need the group's global view)
+    return fail(h, FMX_E_UNSUPPORTED, "kept relation blocks on a feature shard go through fmx_group_upload_block_rows_ex (or upload them with FMX_BLOCKS_EXPAND)");
+  { int _rc = check_block_rows(h, entries, row_ptr, n_rows, nnz, relations, n_relations); if (_rc) return _rc; }
+  const Entry* src = static_cast<const Entry*>(entries);
   if (flags & FMX_BLOCKS_KEEP) return upload_blocks_kept(h, slot, entries, row_ptr, target, n_rows, nnz, relations, n_relations);
   if (h->cfg.shard_world > 1) {
     // a feature shard: the joined rows (main entries, then every block's mapped row with its ids shifted, libfm.cpp:213-216) are

@@ -77,6 +77,9 @@ struct BlockRows {
   float*    pbuf = nullptr;        // [block rows][KP + 1] partial sums of the block rows (predict)
 };
 void free_block(BlockRows* b);
+int check_block_rows(fmx_handle h, const void* entries, const uint64_t* row_ptr, uint32_t n_rows, uint64_t nnz,
+                     const fmx_relation* relations, uint32_t n_relations);                          // fmx_core.hip
+int attach_kept_blocks(fmx_handle h, int slot, uint32_t n_rows, const fmx_relation* relations, uint32_t n_relations);   // fmx_core.hip
 
 struct AlsBlock {                  // ALS / MCMC state of one kept block (fm_learn_mcmc.h:50-58 relation_cache, restated)
   uint32_t* level_list = nullptr;
@@ -84,6 +87,7 @@ struct AlsBlock {                  // ALS / MCMC state of one kept block (fm_lea
   double*   cache = nullptr;       // [7][block rows]: we, weq, wc, wc2, qb, dy, qb0   (struct of arrays)
   double*   qb_all = nullptr;      // [KP][block rows]: the block rows' factor sums of the latest re-prediction
   double*   cpart = nullptr;       // [block rows]: lin - 0.5 * sum of squares of the block rows
+  double*   delta = nullptr;       // feature shards: [4][block rows] what the draws of the current level change in we, weq, qb, dy
   int       lanes = 8;
 };
 

@@ -236,7 +236,10 @@ class FMLearnALS:
     (libfm.cpp:135-139, 283-290) -- on the GPU.  Fields follow fm_learn_mcmc (fm_learn_mcmc.h:60-88):
     fm, min_target, max_target, task, num_iter; w_lambda / v_lambda are set from -regular like libfm.cpp:326-365.
     `groups` (attribute -> group id, the `-meta` file; fm_learn.h:40, Data.h:39-46) makes them per group:
-    w_lambda [G], v_lambda [G] or [G][k] (libfm.cpp:353-363)."""
+    w_lambda [G], v_lambda [G] or [G][k] (libfm.cpp:353-363).
+    `devices` (None: one handle on `device`) lists device ordinals; with more than one entry the model is split into one feature
+    shard per entry (hashed ownership, like the libFM adapter's gpu_devices; "[0, 0]" = two shards on one device) and the sweeps
+    run over the shards (capi.Group) -- block-structured data keeps its blocks apart there too (Data.keep_blocks)."""
 
     def __init__(self):
         self.fm = None
@@ -248,17 +251,29 @@ class FMLearnALS:
         self.do_sample = False
         self.seed = 0
         self.device = -1
+        self.devices = None            # device ordinals of the feature shards (more than one: a capi.Group)
         self.groups = None             # DataMetaInfo::attr_group (None = one group)
         self.out = sys.stdout
         self.pred_this = None          # fm_learn_mcmc.h:116
         self.pred_sum_all = None       # fm_learn_mcmc.h:114
         self.log = []
-        self._h = None
+        self._h = None                 # a capi.Handle, or the capi.Group of the shards
+        self._shards = []
 
     def init(self):
         fm = self.fm
+        devs = [] if self.devices is None else [int(d) for d in self.devices]
+        if len(devs) > 1:
+            self._shards = [capi.Handle(fm.num_attribute, fm.num_factor, fm.k0, fm.k1, self.task, fm.reg0, fm.regw, fm.regv,
+                                        0.0, self.min_target, self.max_target, device=d, shard_rank=r, shard_world=len(devs),
+                                        shard_hash=1) for r, d in enumerate(devs)]
+            for s in self._shards:
+                s.set_groups(self.groups)
+            self._h = capi.Group(self._shards)
+            self._h.set_params(fm.w0, fm.w, fm.v)
+            return
         self._h = capi.Handle(fm.num_attribute, fm.num_factor, fm.k0, fm.k1, self.task, fm.reg0, fm.regw, fm.regv,
-                              0.0, self.min_target, self.max_target, device=self.device)
+                              0.0, self.min_target, self.max_target, device=devs[0] if devs else self.device)
         self._h.set_params(fm.w0, fm.w, fm.v)
         self._h.set_groups(self.groups)
 
@@ -308,6 +323,9 @@ class FMLearnALS:
         if self._h is not None:
             self._h.close()
             self._h = None
+        for s in self._shards:
+            s.close()
+        self._shards = []
 
 
 class FMLearnMCMC(FMLearnALS):
