@@ -504,7 +504,8 @@ int fmx_group_evaluate(fmx_group g, int slot, fmx_eval *out);
  *   fmx_als_end   : frees the caches (:1192-1200).
  * do_sample = 0 is ALS (alpha = 1, mu = 0, lambdas from -regular: reg0 -> w0, w_lambda, v_lambda; libfm.cpp:326-365).
  * do_sample = 1 draws every coordinate from its posterior N(mean, sigma^2) with a counter-based generator (NOT the
- * reference's libc rand() stream: statistical, not bitwise, parity); alpha and the prior means/precisions are
+ * reference's libc rand() stream: statistical, not bitwise, parity with the reference; the chain itself is deterministic,
+ * keyed by (seed, sweep, coordinate family, global feature id), and restated by the test oracle); alpha and the prior means/precisions are
  * supplied per sweep by the caller (the hyper-prior draws of :911-1097 are scalar work that stays on the host).
  * No relations (block structure) -- out of scope. */
 typedef struct fmx_als_opts {

@@ -453,7 +453,7 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
       if (f < 0) {
         FMX_ALS_DRAW(false, cnt, s.t_ent, unit_rows, a.ldesc + a.level_ptr[l], cnt,
                      h->tb.w, h->tb.ws, 0, 0u, a.e, opts->alpha, a.prior, a.prior + NG, h->grp, opts->do_sample,
-                     opts->seed, (uint64_t)(a.iter * 1024 + 1000), sh, delta, dth);
+                     opts->seed, mcmc_stream(a.iter, MCMC_W), sh, delta, dth);
         if (dth && a.lev_dense[l]) hipLaunchKernelGGL((k_als_rows_dense<false>), dim3(std::min<uint32_t>((n_ent + 255) / 256, 16384)), dim3(256), 0, st,
                                     a.r_pos + a.lev_ent[l], lev_x, n_ent, dth, a.e);
         else if (dth) hipLaunchKernelGGL((k_als_rows<false>), dim3(std::min<uint32_t>((n_ent + 255) / 256, 16384)), dim3(256), 0, st,
@@ -464,11 +464,11 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
         if (a.vt)
           FMX_ALS_DRAW(true, cnt, s.t_ent, unit_rows, a.ldesc + a.level_ptr[l], cnt,
                        a.vt + (size_t)f * a.vt_stride, 1u, 1, a.level_ptr[l], a.e, opts->alpha, v_lambda, v_mu, h->grp, opts->do_sample,
-                       opts->seed, (uint64_t)(a.iter * 1024 + f), sh, delta, dth);
+                       opts->seed, mcmc_stream(a.iter, MCMC_V, f), sh, delta, dth);
         else
           FMX_ALS_DRAW(true, cnt, s.t_ent, unit_rows, a.ldesc + a.level_ptr[l], cnt,
                        h->tb.V + f, h->tb.rs, 0, 0u, a.e, opts->alpha, v_lambda, v_mu, h->grp, opts->do_sample,
-                       opts->seed, (uint64_t)(a.iter * 1024 + f), sh, delta, dth);
+                       opts->seed, mcmc_stream(a.iter, MCMC_V, f), sh, delta, dth);
         if (dth && a.lev_dense[l]) hipLaunchKernelGGL((k_als_rows_dense<true>), dim3(std::min<uint32_t>((n_ent + 255) / 256, 16384)), dim3(256), 0, st,
                                     a.r_pos + a.lev_ent[l], lev_x, n_ent, dth, a.e);
         else if (dth) hipLaunchKernelGGL((k_als_rows<true>), dim3(std::min<uint32_t>((n_ent + 255) / 256, 16384)), dim3(256), 0, st,
@@ -512,7 +512,7 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
           hipLaunchKernelGGL((k_rel_aggregate<false, 8>), gb, b1, 0, x->stream, br.brow_ptr, br.brow_list, B, (const EQ*)a.e, ab.cache);
         }
       }
-      const uint64_t stream_id = (uint64_t)(a0.iter * 1024 + (f < 0 ? 1000 : f));
+      const uint64_t stream_id = f < 0 ? mcmc_stream(a0.iter, MCMC_W) : mcmc_stream(a0.iter, MCMC_V, f);
       const uint32_t nl = (uint32_t)a0.blk[r].level_ptr.size() - 1;
       for (uint32_t l = 0; l < nl; l++) {
         bool any = false;
@@ -571,7 +571,7 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
       HIPCHK(x, hipSetDevice(x->device));
       const dim3 gu((uint32_t)std::min<uint64_t>((x->n_local + 255) / 256, 2048));
       hipLaunchKernelGGL(k_als_unseen, gu, b1, 0, x->stream, x->als.seen, x->n_local, x->tb.w, x->tb.ws, x->als.prior, x->als.prior + NG, x->grp,
-                         opts->do_sample, opts->seed, (uint64_t)(x->als.iter * 1024 + 1001), make_shard(x->cfg));
+                         opts->do_sample, opts->seed, mcmc_stream(x->als.iter, MCMC_W_UNSEEN), make_shard(x->cfg));
     }
   }
   // the factors of the features with a training column, factor-major for the duration of the sweep (k_als_shadow)
@@ -602,7 +602,7 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
       hipStream_t st = h->stream;
       KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_als_unseen_v<KP>), (h->n_local + Map<KP>::EPI - 1) / Map<KP>::EPI, st, a.seen, h->n_local,
                                          h->tb, kf, a.prior, NG, h->grp, opts->do_sample, opts->seed,
-                                         (uint64_t)(a.iter * 1024 + 512), make_shard(h->cfg)));
+                                         mcmc_stream(a.iter, MCMC_V_UNSEEN), make_shard(h->cfg)));
     }
     HIPCHK(h, hipGetLastError());
   }
@@ -626,7 +626,7 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
     HIPCHK(x, hipSetDevice(x->device));
     HIPCHK(x, hipMemsetAsync(x->acc, 0, 4 * sizeof(double), x->stream));
     hipLaunchKernelGGL(k_als_targets, g1, b1, 0, x->stream, a.e, s.target, N, x->cfg.task, x->cfg.min_target, x->cfg.max_target, x->acc,
-                       opts->do_sample, opts->seed, (uint64_t)(a.iter * 1024 + 1002));
+                       opts->do_sample, opts->seed, mcmc_stream(a.iter, MCMC_TARGETS));
     HIPCHK(x, hipGetLastError());
   }
   HIPCHK(h, hipSetDevice(h->device));

@@ -162,7 +162,8 @@ static __global__ void k_als_apply_delta(EQ* __restrict__ eq, EQ* __restrict__ d
   }
 }
 
-// counter-based uniforms / normals for the Gibbs variant (statistical, not bitwise, parity with libc rand())
+// counter-based uniforms / normals for the Gibbs variant (not libc rand(): the reference's own chain is matched statistically,
+// the device's keyed chain exactly by oracle/fm_oracle_noise.c)
 __device__ __forceinline__ double unif_hash(uint64_t seed, uint64_t stream, uint64_t idx, uint32_t attempt) {
   const uint64_t hh = mix64(seed ^ (stream * 0x9E3779B97F4A7C15ULL) ^ (idx * 0xD6E8FEB86659FD93ULL + attempt * 0xA24BAED4963EE407ULL + 0x9FB21C651E98DF25ULL));
   return ((double)(hh >> 11) + 0.5) * (1.0 / 9007199254740992.0);     // (0,1)
@@ -304,11 +305,18 @@ k_group_moments(const Tab tb, uint64_t n_local, int k1, const uint32_t* __restri
   }
 }
 
+// the noise stream of one (sweep, coordinate family) of a sampled chain; a draw is keyed (seed, stream, global id).  The families
+// never share a stream for any k <= 1024 (fmx_config::num_factor's limit): factor f of the features with a training column f, the
+// linear weights 1024, the linear weights without a column 1025, the probit targets 1026, factor f without a column 2048 + f.
+// (oracle/fm_oracle_noise.c restates this layout.)
+enum McmcFamily : uint32_t { MCMC_V = 0, MCMC_W = 1024, MCMC_W_UNSEEN = 1025, MCMC_TARGETS = 1026, MCMC_V_UNSEEN = 2048 };
+static inline uint64_t mcmc_stream(uint64_t iter, McmcFamily family, int f = 0) { return iter * 4096u + (uint64_t)family + (uint64_t)f; }
+
 // counter-based N(0,1) for the sampling variant (MCMC): Box-Muller on two splitmix64 hashes of (seed, stream, index)
 // N(0,1) of a coordinate draw: counter hash -> Box-Muller in fp32 with the hardware log / cos (24-bit uniforms: tails to 5.8 sigma).
-// The draw is stored as an fp32 parameter anyway, and the parity of a sampled chain is statistical; in fp64
-// (software log / cos / sqrt, ~200 instructions) this was 40 % of k_als_draw and most of k_als_unseen_v at configs[4]'s shape
-// (3 M short columns per level, 1.2e10 prior draws per sweep).
+// The draw is stored as an fp32 parameter anyway; in fp64 (software log / cos / sqrt, ~200 instructions) this was 40 % of
+// k_als_draw and most of k_als_unseen_v at configs[4]'s shape (3 M short columns per level, 1.2e10 prior draws per sweep).
+// The host's logf / cosf differ from __logf / __cosf by a few fp32 ulps, so a restated chain follows the device's to ~1e-6.
 __device__ __forceinline__ double gauss_hash(uint64_t seed, uint64_t stream, uint64_t idx) {
   const uint64_t h1 = mix64(seed ^ (stream * 0x9E3779B97F4A7C15ULL) ^ (idx * 0xD6E8FEB86659FD93ULL + 0x632BE59BD9B4E019ULL));
   const uint64_t h2 = mix64(h1 + 0x9E3779B97F4A7C15ULL);
@@ -848,7 +856,7 @@ k_als_unseen(const uint8_t* __restrict__ seen, uint64_t n_local, float* __restri
 // one per factor: at n = 1e8 the per-factor form re-reads seen[] and scatters 4-byte writes k times).  Legal because an
 // unseen feature's draw depends on nothing but its prior (no data rows), and the priors of a sweep are fixed before
 // the sweep starts (the hyper-prior statistics are taken at sweep start).  prior: [1 + k][2][G] (row 1+f: lambda, mu).
-// Random stream of (f, j) = the per-factor kernel's: stream0 + f.
+// Random stream of (f, j): stream0 + f (stream0 = mcmc_stream(iter, MCMC_V_UNSEEN)).
 template <int KP>
 __global__ void __launch_bounds__(256)
 k_als_unseen_v(const uint8_t* __restrict__ seen, uint64_t n_local, const Tab tb, int k, const double* __restrict__ prior, uint32_t G,

@@ -200,7 +200,40 @@ typedef struct {
   const double   *w_lambda;  /* [G] */
   const double   *v_lambda;  /* [G][k] */
 } fmo_als_reg;
-void fmo_als_sweep_groups(fmo_model *m, const fmo_data_t *dt, fmo_eq *cache, const fmo_als_reg *reg);
+
+/* What a sweep of the MCMC learner adds to the ALS one (opts == NULL everywhere: alpha = 1, mu = 0, no sampling -- the results
+ * of the plain ALS functions, bit for bit).
+ *
+ * Restated from the REFERENCE (fm_learn_mcmc.h): the posterior of every coordinate with the noise precision alpha and the prior
+ * mean mu of its group -- sigma^2 = 1 / (lambda + alpha sum h^2), mean = -sigma^2 (alpha sum h e - mu lambda) (draw_w0 :653-654,
+ * draw_w :694-695, draw_v :817-818) --, the order of the coordinates and the cache updates (draw_all :430-641), and the probit
+ * step (_learn :172-194).  The tests pin this part against the real reference with do_sample = 0 (alpha_0 != 1, mu_0 != 0).
+ *
+ * Restated from the DEVICE's noise contract (libfm_amd/csrc/fmx_als_kernels.h, fmx_als.hip -- NOT the reference's libc rand()):
+ * with do_sample, a coordinate becomes mean + sqrt(sigma^2) z, z = gauss_hash(seed, stream, global feature id), stream =
+ * fmo_mcmc_stream(iter, family, f) with the family chosen by whether the feature has a training column (seen[]); the bias takes
+ * z from std::mt19937_64 (fmo_w0_noise); a probit target is drawn from the truncated normal through left_tgauss, keyed by its
+ * row, in the device's order of attempts.  fm_oracle_noise.c restates the hashes; the host's logf / cosf are a few fp32 ulps
+ * from the device's __logf / __cosf. */
+enum { FMO_MCMC_V = 0, FMO_MCMC_W = 1024, FMO_MCMC_W_UNSEEN = 1025, FMO_MCMC_TARGETS = 1026, FMO_MCMC_V_UNSEEN = 2048 };
+typedef struct {
+  double          alpha;     /* draw_alpha's value (alpha_0 with do_multilevel = 0) */
+  const double   *w_mu;      /* [G]    prior means of w  (NULL: 0) */
+  const double   *v_mu;      /* [G][k] prior means of v  (NULL: 0) */
+  int             do_sample;
+  uint64_t        seed;      /* fmx_als_opts::seed */
+  uint64_t        iter;      /* the sweep's index in the device session (fmx_als_begin starts at 0) */
+  const uint8_t  *seen;      /* [m->n] the device's "has a training column"; NULL: a non-empty column of dt */
+} fmo_als_opts;
+void fmo_als_sweep_groups(fmo_model *m, const fmo_data_t *dt, fmo_eq *cache, const fmo_als_reg *reg, const fmo_als_opts *opts);
+
+uint64_t fmo_mcmc_stream(uint64_t iter, uint32_t family, int f);        /* iter * 4096 + family + f */
+double   fmo_unif_hash(uint64_t seed, uint64_t stream, uint64_t idx, uint32_t attempt);
+double   fmo_gauss_hash2(uint64_t seed, uint64_t stream, uint64_t idx, uint32_t attempt);
+double   fmo_gauss_hash(uint64_t seed, uint64_t stream, uint64_t idx);
+double   fmo_left_tgauss(double left, uint64_t seed, uint64_t stream, uint64_t idx);
+void     fmo_gauss_hash_n(uint64_t seed, uint64_t stream, const uint64_t *idx, uint64_t n, double *out);
+double   fmo_w0_noise(uint64_t seed, uint64_t iter);                    /* fm_oracle_w0.cpp */
 
 /* fm_learn_mcmc::learn + fm_learn_mcmc_simultaneous::_learn with do_sample = 0 (fm_learn_mcmc.h:1160-1201,
  * fm_learn_mcmc_simultaneous.h:56-270): num_iter sweeps, e recomputed after each.  task regression: e -= y;
@@ -214,6 +247,10 @@ void fmo_als_learn(fmo_model *m, const fmo_data *train, const fmo_data *test, in
 void fmo_als_learn_groups(fmo_model *m, const fmo_data *train, const fmo_data *test, int task, int num_iter,
                           const fmo_als_reg *reg, double min_target, double max_target,
                           double *test_pred_this, double *train_metric);
+/* the same with fmo_als_opts: sweep it has iter = opts->iter + it; with do_sample the probit targets are the keyed draws */
+void fmo_als_learn_ex(fmo_model *m, const fmo_data *train, const fmo_data *test, int task, int num_iter,
+                      const fmo_als_reg *reg, const fmo_als_opts *opts, double min_target, double max_target,
+                      double *test_pred_this, double *train_metric);
 
 /* the reference's 5-term erf polynomial and cdf_gaussian (random.h:45-67) */
 double fmo_erf(double x);

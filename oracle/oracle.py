@@ -27,7 +27,8 @@ def build(force=False):
     """(Re)build the oracle .so (and oracle/_ref when /root/reference is present)."""
     if force or not os.path.exists(LIB_PATH) or \
             os.path.getmtime(LIB_PATH) < max(os.path.getmtime(os.path.join(HERE, f))
-                                             for f in ("fm_oracle.c", "fm_oracle_als.c", "fm_oracle.h")):
+                                             for f in ("fm_oracle.c", "fm_oracle_als.c", "fm_oracle_noise.c", "fm_oracle_w0.cpp",
+                                                       "fm_oracle.h")):
         subprocess.check_call(["make", "-s", "-C", HERE, os.path.join(HERE, "libfm_oracle.so")])
     if os.path.exists("/root/reference/src/libfm/libfm.cpp"):
         subprocess.check_call(["make", "-s", "-C", HERE, "ref"])
@@ -51,6 +52,11 @@ class _SgdaState(C.Structure):
 
 class _AlsReg(C.Structure):
     _fields_ = [("group", C.c_void_p), ("num_groups", C.c_uint32), ("w_lambda", C.c_void_p), ("v_lambda", C.c_void_p)]
+
+
+class _AlsOpts(C.Structure):
+    _fields_ = [("alpha", C.c_double), ("w_mu", C.c_void_p), ("v_mu", C.c_void_p), ("do_sample", C.c_int),
+                ("seed", C.c_uint64), ("iter", C.c_uint64), ("seen", C.c_void_p)]
 
 
 _lib = None
@@ -83,7 +89,14 @@ def lib():
                                     C.c_double, C.c_double, C.c_void_p, C.c_void_p]
         L.fmo_als_learn_groups.argtypes = [C.POINTER(_Model), C.POINTER(_Data), C.POINTER(_Data), C.c_int, C.c_int, C.POINTER(_AlsReg),
                                            C.c_double, C.c_double, C.c_void_p, C.c_void_p]
-        L.fmo_sgda_epoch.argtypes = [C.POINTER(_Model), C.POINTER(_SgdaState), C.POINTER(_Data), C.POINTER(_Data), C.c_int,
+        L.fmo_als_learn_ex.argtypes = [C.POINTER(_Model), C.POINTER(_Data), C.POINTER(_Data), C.c_int, C.c_int, C.POINTER(_AlsReg),
+                                       C.POINTER(_AlsOpts), C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+        L.fmo_mcmc_stream.argtypes = [C.c_uint64, C.c_uint32, C.c_int]
+        L.fmo_mcmc_stream.restype = C.c_uint64
+        L.fmo_gauss_hash_n.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.fmo_w0_noise.argtypes = [C.c_uint64, C.c_uint64]
+        L.fmo_w0_noise.restype = C.c_double
+        L.fmo_sgda_epoch.argtypes =[C.POINTER(_Model), C.POINTER(_SgdaState), C.POINTER(_Data), C.POINTER(_Data), C.c_int,
                                      C.c_double, C.c_double, C.c_double, C.c_int]
         L.fmo_sgda_epoch_minibatch.argtypes = [C.POINTER(_Model), C.POINTER(_SgdaState), C.POINTER(_Data), C.POINTER(_Data), C.c_int,
                                                C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint32, C.c_uint32]
@@ -338,6 +351,54 @@ def als_learn_groups(m, train, test, task, num_iter, group, w_lambda_g, v_lambda
                                pred.ctypes.data, metric.ctypes.data)
     m.w0 = cm.w0
     return pred, metric
+
+
+MCMC_V, MCMC_W, MCMC_W_UNSEEN, MCMC_TARGETS, MCMC_V_UNSEEN = 0, 1024, 1025, 1026, 2048     # fm_oracle.h FMO_MCMC_*
+
+
+def als_learn_ex(m, train, test, task, num_iter, w_lambda_g, v_lambda_gf, min_target, max_target, group=None,
+                 alpha=1.0, w_mu_g=None, v_mu_gf=None, do_sample=False, seed=0, iter0=0, seen=None):
+    """ALS / one Gibbs chain of the device (fmo_als_learn_ex): alpha and prior means per group (w_mu_g[G], v_mu_gf[G][k]);
+    do_sample draws with the device's keyed noise (seed = fmx_als_opts::seed, sweep it has iter0 + it); seen[n]: the device's
+    "has a training column" (None: a non-empty train column).  Returns (pred_this on test, train metric per iteration)."""
+    wl = np.ascontiguousarray(np.atleast_1d(w_lambda_g), dtype=np.float64)
+    G = len(wl)
+    vl = np.ascontiguousarray(np.broadcast_to(np.asarray(v_lambda_gf, dtype=np.float64), (G, max(m.k, 1))))
+    group = None if group is None else np.ascontiguousarray(group, dtype=np.uint32)
+    assert group is None or (group.shape == (m.n,) and int(group.max()) < G)
+    keep = [wl, vl, group]
+    wmu = None if w_mu_g is None else np.ascontiguousarray(np.broadcast_to(np.asarray(w_mu_g, dtype=np.float64), (G,)))
+    vmu = None if v_mu_gf is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v_mu_gf, dtype=np.float64), (G, max(m.k, 1))))
+    sn = None if seen is None else np.ascontiguousarray(seen, dtype=np.uint8)
+    assert sn is None or sn.shape == (m.n,)
+    keep += [wmu, vmu, sn]
+    reg = _AlsReg(None if group is None else group.ctypes.data, G, wl.ctypes.data, vl.ctypes.data)
+    opts = _AlsOpts(float(alpha), None if wmu is None else wmu.ctypes.data, None if vmu is None else vmu.ctypes.data,
+                    int(bool(do_sample)), int(seed), int(iter0), None if sn is None else sn.ctypes.data)
+    pred = np.zeros(max(test.n_rows, 1), dtype=np.float64)
+    metric = np.zeros(max(num_iter, 1), dtype=np.float64)
+    cm, ctr, cte = m._c(), train._c(), test._c()
+    lib().fmo_als_learn_ex(C.byref(cm), C.byref(ctr), C.byref(cte), task, num_iter, C.byref(reg), C.byref(opts), min_target, max_target,
+                           pred.ctypes.data, metric.ctypes.data)
+    m.w0 = cm.w0
+    del keep
+    return pred[:test.n_rows], metric[:num_iter]
+
+
+def mcmc_stream(it, family, f=0):
+    return int(lib().fmo_mcmc_stream(int(it), int(family), int(f)))
+
+
+def gauss_hash(seed, stream, ids):
+    """the device's coordinate noise z(seed, stream, id) for every id (fp32 Box-Muller, host logf / cosf)"""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    out = np.zeros(len(ids), dtype=np.float64)
+    lib().fmo_gauss_hash_n(int(seed), int(stream), ids.ctypes.data, len(ids), out.ctypes.data)
+    return out
+
+
+def w0_noise(seed, it):
+    return float(lib().fmo_w0_noise(int(seed), int(it)))
 
 
 class SgdaState:

@@ -25,6 +25,7 @@
 //   ref_harness time_sgd_rows <rows.bin> <n> <k> <lr> <regv> <init_stdev>   (the same loop over rows from a file)
 // environment: FMX_META=<file>  attribute groups (`-meta`, one group id per line, Data.h:85-97);
 //              FMX_GROUP_REG=w_1,..,w_G,v_1,..,v_G  per-group lambdas for als (the tail of `-regular`, libfm.cpp:353-363)
+//              FMX_ALS_ALPHA0=a, FMX_ALS_MU0=m  the learner's alpha_0 / mu_0 after init() (als / mcmc)
 //              FMX_RELATIONS=<prefix>[,<prefix>]  block-structured data for als / mcmc (`-relation`, libfm.cpp:172-196)
 // outputs (<out_prefix>.*):
 //   .init.bin / .final.bin : magic 'FMXP', u64 n, i32 k, f64 w0, f64 w[n], f64 v[k][n]  (reference layout)
@@ -352,6 +353,10 @@ int main(int argc, char** argv) {
       if (const char* e = getenv("FMX_RLOG")) { rlog = new RLog(new std::ofstream(e)); fml->log = rlog; }
       fml->init();
       if (rlog) rlog->init();                                  // libfm.cpp:405-407: the header line
+      // hyper-priors other than init()'s alpha_0 = 1, mu_0 = 0 (fm_learn_mcmc.h:1106-1110): with do_multilevel = 0 the sweep
+      // runs at alpha = alpha_0 (draw_alpha) and prior means mu_0 (draw_w_mu, draw_v_mu)
+      if (const char* e = getenv("FMX_ALS_ALPHA0")) fml->alpha_0 = atof(e);
+      if (const char* e = getenv("FMX_ALS_MU0")) fml->mu_0 = atof(e);
       fm.reg0 = reg0; fm.regw = regw; fm.regv = regv;         // libfm.cpp:346-352
       fml->w_lambda.init(fm.regw); fml->v_lambda.init(fm.regv);
       if (getenv("FMX_GROUP_REG")) {                           // -regular 'r0,w_1..w_G,v_1..v_G', libfm.cpp:353-363

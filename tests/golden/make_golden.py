@@ -93,10 +93,39 @@ ALS_CASES = {
 }
 
 
-def make_als():
-    for name, case in ALS_CASES.items():
+# ALS with hyper-priors other than init()'s (alpha_0 = 1, mu_0 = 0): what the MCMC learner's sweep runs at, pinned with
+# do_sample = do_multilevel = 0 (then alpha = alpha_0 and every prior mean = mu_0, fm_learn_mcmc.h:912-915, :942-944, :1020-1022).
+# hole = (first, width): the train ids from `first` on are moved up by `width`, so that ids first .. first + width - 1 have no
+# training column but appear in the test rows, and the test's larger id range reaches above the train's maximum.
+HYP_ALS_CASES = {
+    "hyp_als_reg_ml": dict(gen="movielens_shaped", train=dict(n_users=120, n_items=80, n_rows=600, seed=13), hole=(60, 15),
+                           test=dict(n_users=140, n_items=90, n_rows=150, seed=14), alpha0=1.7, mu0=0.3,
+                           cfg=dict(task="r", k0=1, k1=1, k=8, iters=4, reg=(0.5, 1.0, 5.0), init_stdev=0.1, seed=43)),
+    "hyp_als_cls_fields_groups": dict(gen="onehot_fields", train=dict(n_features=480, nnz=6, n_rows=400, seed=45), hole=(200, 10),
+                                      test=dict(n_features=540, nnz=6, n_rows=100, seed=46), groups=("fields", 6, 480, 2),
+                                      n_nominal=560, group_reg=((0.1, 1.0, 4.0), (2.0, 6.0, 12.0)), alpha0=1.7, mu0=-0.3,
+                                      cfg=dict(task="c", k0=1, k1=1, k=4, iters=3, reg=(0.2, 0.0, 0.0), init_stdev=0.1, seed=9)),
+    "hyp_als_reg_ragged_groups": dict(gen="ragged_real", train=dict(n_features=150, n_rows=300, max_nnz=8, seed=23, classification=False),
+                                      hole=(40, 12), test=dict(n_features=180, n_rows=80, max_nnz=8, seed=24, classification=False),
+                                      groups=("split", 90), n_nominal=200, group_reg=((0.5, 2.0), (3.0, 9.0)), alpha0=0.6, mu0=0.25,
+                                      cfg=dict(task="r", k0=1, k1=1, k=5, iters=3, reg=(0.3, 0.0, 0.0), init_stdev=0.1, seed=17)),
+}
+
+
+def _punch_hole(entries, hole):
+    e = entries.copy()
+    if hole is not None:
+        first, width = hole
+        e["id"] = np.where(e["id"] >= first, e["id"] + width, e["id"]).astype(np.uint32)
+    return e
+
+
+def make_als(cases=ALS_CASES):
+    for name, case in cases.items():
         gen = getattr(datagen, case["gen"])
         tr = O.Data(*gen(**case["train"]))
+        if "hole" in case:
+            tr = O.Data(_punch_hole(tr.entries, case["hole"]), tr.row_ptr, tr.target)
         te = O.Data(*gen(**case["test"]))
         cfg = case["cfg"]
         with tempfile.TemporaryDirectory() as td:
@@ -108,6 +137,9 @@ def make_als():
                 write_meta(os.path.join(td, "meta"), case, case["n_nominal"])
                 env = {"FMX_META": os.path.join(td, "meta"),
                        "FMX_GROUP_REG": ",".join(repr(x) for x in case["group_reg"][0] + case["group_reg"][1])}
+            if "alpha0" in case:
+                env.update(FMX_ALS_ALPHA0=repr(case["alpha0"]), FMX_ALS_MU0=repr(case["mu0"]))
+                extra.update(alpha0=case["alpha0"], mu0=case["mu0"])
             O.run_ref_harness(["als", trf, tef, cfg["task"], cfg["k0"], cfg["k1"], cfg["k"], cfg["iters"],
                                repr(cfg["reg"][0]), repr(cfg["reg"][1]), repr(cfg["reg"][2]), repr(cfg["init_stdev"]),
                                cfg["seed"], pre], env=env)
@@ -115,7 +147,7 @@ def make_als():
             final = O.Model.from_dump(pre + ".final.bin")
             pred_out = np.fromfile(pre + ".pred_out.bin", dtype=np.float64)
             if "groups" in case:
-                extra = dict(group=groups_of(case, init.n), w_lambda_g=np.array(case["group_reg"][0]),
+                extra.update(group=groups_of(case, init.n), w_lambda_g=np.array(case["group_reg"][0]),
                              v_lambda_g=np.array(case["group_reg"][1]))
         np.savez_compressed(
             os.path.join(HERE, name + ".npz"), **extra,
@@ -259,9 +291,16 @@ REL_CASES = {
 }
 
 
-def make_rel():
+HYP_REL_CASES = {
+    # the block sweep (draw_w_rel / draw_v_rel) at alpha_0 != 1, mu_0 != 0
+    "hyp_rel_als_reg": dict(gen=dict(n_users=60, n_items=40, n_rows=700, seed=85), split=550, rel_groups=False, alpha0=1.7, mu0=-0.3,
+                            cfg=dict(task="r", k0=1, k1=1, k=4, iters=3, reg=(0.2, 1.0, 6.0), init_stdev=0.1, seed=13)),
+}
+
+
+def make_rel(cases=REL_CASES):
     from libfm_amd import data as D                            # host-side file formats only (no GPU involved)
-    for name, case in REL_CASES.items():
+    for name, case in cases.items():
         (ent, rp, y), blocks, maps = datagen.block_structured(**case["gen"])
         rp = rp.astype(np.int64)
         ntr = case["split"]
@@ -290,13 +329,15 @@ def make_rel():
             env = {"FMX_RELATIONS": ",".join(prefixes)}
             if "group_reg" in case:
                 env["FMX_GROUP_REG"] = ",".join(repr(x) for x in case["group_reg"][0] + case["group_reg"][1])
+            if "alpha0" in case:
+                env.update(FMX_ALS_ALPHA0=repr(case["alpha0"]), FMX_ALS_MU0=repr(case["mu0"]))
             O.run_ref_harness(["als", trf, tef, cfg["task"], cfg["k0"], cfg["k1"], cfg["k"], cfg["iters"],
                                repr(cfg["reg"][0]), repr(cfg["reg"][1]), repr(cfg["reg"][2]), repr(cfg["init_stdev"]),
                                cfg["seed"], pre], env=env)
             init = O.Model.from_dump(pre + ".init.bin")
             final = O.Model.from_dump(pre + ".final.bin")
             pred_out = np.fromfile(pre + ".pred_out.bin", dtype=np.float64)
-        extra = {}
+        extra = dict(alpha0=case["alpha0"], mu0=case["mu0"]) if "alpha0" in case else {}
         for bi, ((be, bp, nf), mp) in enumerate(zip(blocks, maps)):
             extra.update({"rel%d_entries" % bi: be, "rel%d_row_ptr" % bi: bp, "rel%d_num_feature" % bi: nf,
                           "rel%d_train" % bi: mp[:ntr], "rel%d_test" % bi: mp[ntr:]})
@@ -358,12 +399,18 @@ def make_c1():
 
 def main():
     O.build()
+    if "--hyp" in sys.argv:                                      # the hyper-prior cases alone
+        make_als(HYP_ALS_CASES)
+        make_rel(HYP_REL_CASES)
+        return
     if "--c1" in sys.argv or not os.path.exists(os.path.join(HERE, "c1_ml100k_shaped.npz")):
         make_c1()
     make_rel()
     make_mcmc()
     make_sgda()
     make_als()
+    make_als(HYP_ALS_CASES)
+    make_rel(HYP_REL_CASES)
     for name, case in CASES.items():
         gen = getattr(datagen, case["gen"])
         tr = O.Data(*gen(**case["train"]))
