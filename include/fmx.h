@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define FMX_ABI_VERSION 8
+#define FMX_ABI_VERSION 9
 
 enum {
   FMX_OK = 0,
@@ -191,7 +191,7 @@ typedef struct fmx_epoch_stats {
                                number of features two rows share (value-weighted) */
   double   batch_gain;      /* learn_rate * curvature * batch_used * C (curvature 1 regression, 1/4 classification): the batch
                                rule follows the reference's online loop for <= 1, degrades above and diverges beyond ~2 */
-  uint32_t status;          /* FMX_STAT_* */
+  uint32_t status;          /* FMX_STAT_*; FMX_STAT_WARN_MASK picks the bits that say something about the rule, the others say how the epoch ran */
   uint32_t w0_chunk_used;   /* MINIBATCH / HOGWILD: the micro-chunk of the bias recurrence this epoch ran with */
   double   setup_seconds;   /* host wall-clock this call spent on ONE-TIME work for the slot (not part of device_seconds): the rows' collision mass
                                and the bucketing of the entries by (batch, feature) -- the segments, masks and lists the MINIBATCH forms
@@ -206,6 +206,7 @@ typedef struct fmx_epoch_stats {
 
 #define FMX_STAT_BATCH_CUT 1u   /* batch = 0 resolved below the 262144 default because of the rows' collision mass */
 #define FMX_STAT_UNSTABLE  2u   /* batch_gain > 2: an explicit batch the rule is not stable at on this data */
+#define FMX_STAT_WARN_MASK (FMX_STAT_BATCH_CUT | FMX_STAT_UNSTABLE)
 /* (ABI 7) how the epoch's bias recurrences and stream ordering actually ran -- same numbers in every form; for tests and diagnosis: */
 #define FMX_STAT_SCAN_PIT      4u  /* at least one batch's recurrence was solved parallel in time (k_scan_pit) */
 #define FMX_STAT_SCAN_SERIAL   8u  /* at least one ran as the one-wavefront chain (k_scan1 / k_scan / the small-batch form) */
@@ -227,6 +228,15 @@ typedef struct fmx_epoch_stats {
 #define FMX_STAT_HANDOFF_TIMEOUT 64u /* a device-side hand-off wait ran into its bound all the same: the examples concerned took NO step
                                       (multiplier 0; a recurrence that never saw its batch handed the bias on unchanged), every parameter is a
                                       valid number, the call returns FMX_E_HIP with this status set, and the handle orders by events from now on */
+/* (ABI 9) which kernels FMX_SGD_SEQUENTIAL ran (libfm_amd/csrc/fmx_seq_kernels.h, fmx_kernels.h) -- the same trajectory in every form; for
+   tests and diagnosis.  The environment of fmx_create picks among them: FMX_SEQ_ROWS=0, FMX_SEQ_WG=0, FMX_SEQ_RUNS_FUSED=0, FMX_SEQ_RUNS_ONE=0;
+   FMX_SEQ_RUNS (0: never runs, 1: always) is read at every epoch: */
+#define FMX_STAT_SEQ_ENTRIES   1024u /* entry by entry on one wavefront (k_sequential): the whole slot, or a row that repeats an id inside runs */
+#define FMX_STAT_SEQ_WG        2048u /* one example at a time on eight wavefronts (k_sequential_wg) */
+#define FMX_STAT_SEQ_ROWS      4096u /* one example at a time on one wavefront, a row at a time (k_sequential_rows) */
+#define FMX_STAT_RUN_ONE       8192u /* at least one conflict-free run as ONE launch (k_run_fused) */
+#define FMX_STAT_RUN_TWO      16384u /* at least one run as two launches (k_rowsums + k_run_apply) */
+#define FMX_STAT_RUN_THREE    32768u /* at least one run as three launches (k_rowsums + the recurrence on its own + k_apply) */
 
 /* what fmx_sgd_epoch would use for `batch` on this slot (no training): the rows' collision mass (computed once per slot on the
  * device: one histogram pass over the entries), the resolved batch and its gain.  opts may be NULL (= batch 0). */

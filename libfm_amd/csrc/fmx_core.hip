@@ -799,6 +799,11 @@ int fmx_create(const fmx_config* cfg, fmx_handle* out) {
     h->xcd = (xe && xe[0] == '1');                              // opt-in: measured slower than the two launches per batch (profiles/r06_criteo_hops.txt)
     const char* so = getenv("FMX_SMALL_ONE");
     h->small_one = !(so && so[0] == '0');                       // small batches as one launch per batch (fmx_small_kernels.h); FMX_SMALL_ONE=0: two
+    auto env_on = [](const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); };
+    h->seq_rows = env_on("FMX_SEQ_ROWS");                       // FMX_SGD_SEQUENTIAL (fmx_sgd.hip fmx_sgd_epoch, seq_runs_epoch): =0 turns a form off
+    h->seq_wg = env_on("FMX_SEQ_WG");
+    h->seq_runs_fused = env_on("FMX_SEQ_RUNS_FUSED");
+    h->seq_runs_one = env_on("FMX_SEQ_RUNS_ONE");
     const char* xb = getenv("FMX_XCD_MAX_BATCH");
     if (xb) h->xcd_max_batch = (uint32_t)strtoul(xb, nullptr, 10);
     const char* sp = getenv("FMX_DEBUG_PIT_SPINS");

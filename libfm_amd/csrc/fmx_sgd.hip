@@ -1084,11 +1084,10 @@ static int launch_run_one(fmx_handle h, const Slot& s, const Hyper& hy, uint32_t
 // one epoch over the runs.  A run of up to RUN_ONE_MAX rows that fit the registers is ONE launch (k_run_fused: the rows stay in the wavefronts'
 // registers across the run's bias recurrence); up to RUN_FUSED_MAX rows TWO: the sums, then the update whose every workgroup solves the
 // recurrence for itself (k_run_apply); a longer one three (sums, k_scan_pit on one workgroup at micro-chunk 1, update).
-// FMX_SEQ_RUNS_FUSED=0: always three, with the one-wavefront chain (what the first version did); FMX_SEQ_RUNS_ONE=0: never one.
+// FMX_SEQ_RUNS_FUSED=0: always three, with the one-wavefront chain (what the first version did); FMX_SEQ_RUNS_ONE=0: never one (both read by fmx_create).
 static int seq_runs_epoch(fmx_handle h, Slot& s, const Hyper& hy) {
   hipStream_t st = h->stream;
-  static const bool fused = []() { const char* e = getenv("FMX_SEQ_RUNS_FUSED"); return !(e && e[0] == '0'); }();
-  static const bool one_env = []() { const char* e = getenv("FMX_SEQ_RUNS_ONE"); return !(e && e[0] == '0'); }();
+  const bool fused = h->seq_runs_fused, one_env = h->seq_runs_one;
   uint32_t longest = 1;
   for (size_t i = 0; i + 1 < s.run_start.size(); i++) longest = std::max(longest, s.run_start[i + 1] - s.run_start[i]);
   int rc = ensure_scratch(h, longest, 0);
@@ -1112,12 +1111,13 @@ static int seq_runs_epoch(fmx_handle h, Slot& s, const Hyper& hy) {
     const uint32_t row0 = s.run_start[i], nb = s.run_start[i + 1] - row0;
     if (s.run_single[i]) {                                        // a row that repeats an id: entry by entry (fm_sgd.h:44-50)
       KP_SWITCH(h->KP, hipLaunchKernelGGL((k_sequential<KP>), dim3(1), dim3(64), 0, st, s.ent, s.row_ptr + row0, s.target + row0, nb, h->tb, hy, bias[cur]));
+      h->run_status |= FMX_STAT_SEQ_ENTRIES;
       continue;
     }
     if (one && nb <= RUN_ONE_MAX) {
       rc = launch_run_one(h, s, hy, row0, nb, zr, bias[cur], bias[cur ^ 1], slots, (uint32_t)i + 1u);
       if (rc < 0) return rc;
-      if (rc == 1) { h->run_one_used = true; if (hy.k0) cur ^= 1; continue; }
+      if (rc == 1) { h->run_one_used = true; h->run_status |= FMX_STAT_RUN_ONE; if (hy.k0) cur ^= 1; continue; }
     }
     float* S = h->partial;
     float* rest = S + (size_t)nb * h->KP;
@@ -1127,9 +1127,11 @@ static int seq_runs_epoch(fmx_handle h, Slot& s, const Hyper& hy) {
       const size_t lds = (size_t)nb * 5 * sizeof(float);
       if (hy.task == 0) { KP_SWITCH(h->KP, hipLaunchKernelGGL((k_run_apply<KP, 0>), grid, dim3(256), lds, st, s.ent, s.row_ptr, (uint64_t)row0, nb, h->tb, hy, S, rest, s.target, bias[cur], bias[cur ^ 1])); }
       else              { KP_SWITCH(h->KP, hipLaunchKernelGGL((k_run_apply<KP, 1>), grid, dim3(256), lds, st, s.ent, s.row_ptr, (uint64_t)row0, nb, h->tb, hy, S, rest, s.target, bias[cur], bias[cur ^ 1])); }
+      h->run_status |= FMX_STAT_RUN_TWO;
       if (hy.k0) cur ^= 1;
       continue;
     }
+    h->run_status |= FMX_STAT_RUN_THREE;
     rc = launch_scan(h, rest, s.target + row0, nb, 1u, hy, h->mult, st, bias[cur], bias[cur], Handoff{nullptr, 0ull, nullptr}, fused);
     if (rc) return rc;
     KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_apply<KP, false>), nb, st, s.ent, s.row_ptr, (uint64_t)row0, nb, h->tb, hy, S, h->mult));
@@ -1194,7 +1196,7 @@ int fmx_sgd_epoch(fmx_handle h, int slot, const fmx_sgd_opts* opts, fmx_epoch_st
   if (opts->mode == FMX_SGD_SEQUENTIAL) {
     // rows of 64 / 128 lanes: a row at a time with the next example's rows in flight (fmx_seq_kernels.h: 20 k -> ~1 M examples/s on the
     // reference's own trajectory); FMX_SEQ_ROWS=0 and the other row widths: entry by entry
-    static const bool seq_rows = []() { const char* e = getenv("FMX_SEQ_ROWS"); return !(e && e[0] == '0'); }();
+    const bool seq_rows = h->seq_rows;                          // (FMX_SEQ_ROWS / FMX_SEQ_WG: read by fmx_create)
     // where consecutive rows rarely share a feature: the same trajectory as conflict-free runs at batch speed (fmx_seq_kernels.h); taken when
     // the slot's runs average >= 16 rows (FMX_SEQ_RUNS=0: never, =1: always)
     const char* sr = getenv("FMX_SEQ_RUNS");
@@ -1206,7 +1208,7 @@ int fmx_sgd_epoch(fmx_handle h, int slot, const fmx_sgd_opts* opts, fmx_epoch_st
       use_runs = !(s.run_single.size() == 1 && s.run_single[0] == 2) && ((sr && sr[0] == '1') || (uint64_t)s.n_rows >= 16ull * n_runs);
       HIPCHK(h, hipEventRecord(h->ev0, h->stream));             // (the one-time cut is not the epoch's time)
     }
-    static const bool seq_wg = []() { const char* e = getenv("FMX_SEQ_WG"); return !(e && e[0] == '0'); }();
+    const bool seq_wg = h->seq_wg;
     if (use_runs) {
       rc = seq_runs_epoch(h, s, hy);
       if (rc) return rc;
@@ -1225,15 +1227,19 @@ int fmx_sgd_epoch(fmx_handle h, int slot, const fmx_sgd_opts* opts, fmx_epoch_st
         if (!h->lds_raised.count((const void*)kf)) { HIPCHK(h, hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SeqLds<128>))); h->lds_raised.insert((const void*)kf); }
         hipLaunchKernelGGL(kf, dim3(1), dim3(64 * SEQ_W), sizeof(SeqLds<128>), h->stream, s.ent, s.row_ptr, s.target, s.n_rows, s.nnz, h->tb, hy, h->w0);
       }
+      h->run_status |= FMX_STAT_SEQ_WG;
     } else if (seq_rows && h->KP <= 128) {
+      h->run_status |= FMX_STAT_SEQ_ROWS;
       const bool wide = s.max_row > 32u;
       if (h->KP <= 64) { if (wide) hipLaunchKernelGGL((k_sequential_rows<64, 64>), dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr, s.target, s.n_rows, h->tb, hy, h->w0);
                          else      hipLaunchKernelGGL((k_sequential_rows<64, 32>), dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr, s.target, s.n_rows, h->tb, hy, h->w0); }
       else             { if (wide) hipLaunchKernelGGL((k_sequential_rows<128, 64>), dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr, s.target, s.n_rows, h->tb, hy, h->w0);
                          else      hipLaunchKernelGGL((k_sequential_rows<128, 32>), dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr, s.target, s.n_rows, h->tb, hy, h->w0); }
-    } else
-    KP_SWITCH(h->KP, hipLaunchKernelGGL((k_sequential<KP>), dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr,
-                                          s.target, s.n_rows, h->tb, hy, h->w0));
+    } else {
+      KP_SWITCH(h->KP, hipLaunchKernelGGL((k_sequential<KP>), dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr,
+                                            s.target, s.n_rows, h->tb, hy, h->w0));
+      h->run_status |= FMX_STAT_SEQ_ENTRIES;
+    }
     HIPCHK(h, hipGetLastError());
     if (!use_runs) batches = s.n_rows;
     main_launches = 1;

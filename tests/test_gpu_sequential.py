@@ -1,0 +1,317 @@
+"""GPU: FMX_SGD_SEQUENTIAL in every form it takes, against the reference's online loop (fm_learn_sgd_element.h:56-67, fm_sgd.h:33-51).
+
+The mode is one contract -- the reference's trajectory -- carried by many kernels: conflict-free runs in one, two or three launches, the
+entry-by-entry loop, one example on eight wavefronts or on one (tests/seq_routes.py restates which, from the rows and the FMX_SEQ_*
+switches).  Every test here asserts the form the epoch reports (fmx_epoch_stats::status, ABI 9) and, for runs, the exact number of runs
+the cut must give, then compares two epochs and the predictions with the real reference (tests/golden/sgd_*) or the oracle's fp64 online
+loop:  |gpu - ref| <= 1e-4 |ref| + ATOL, ATOL 2e-5 on parameters (1e-5 against the fixtures), 5e-5 on predictions.
+tests/test_seq_routes.py checks on the CPU that these cases reach every kernel instance of the mode."""
+import zlib
+
+import numpy as np
+import pytest
+
+from common import Golden
+from conftest import golden_cases
+import seq_routes as R
+
+pytestmark = pytest.mark.gpu
+
+RTOL = 1e-4
+ENTRY = np.dtype([("id", np.uint32), ("value", np.float32)])
+FIXTURES = [c for c in golden_cases() if c.startswith("sgd_")]
+FORMS = [{}, {"FMX_SEQ_RUNS": "1"}, {"FMX_SEQ_RUNS": "0"}, {"FMX_SEQ_WG": "0"}, {"FMX_SEQ_ROWS": "0"},
+         {"FMX_SEQ_RUNS_FUSED": "0"}, {"FMX_SEQ_RUNS_ONE": "0"}]
+
+
+def form_id(knobs):
+    return "-".join("%s=%s" % (k[8:].lower(), v) for k, v in sorted(knobs.items())) or "default"
+
+
+# ---------------------------------------------------------------------------------------------
+# the cases (plain numpy, also read by tests/test_seq_routes.py)
+# ---------------------------------------------------------------------------------------------
+def make_rows(seed, rows, max_row, period, fixed=False, dups=0, big=False, task=0, clamp=False):
+    """rows whose ids come from `period` disjoint windows of max_row ids, row r from window r % period: a row can only share a feature
+    with rows a multiple of `period` away, so the conflict-free runs are at most `period` rows long (fixed rows fill their window: exactly
+    that long).  Ragged rows are 0 .. max_row entries long (one of them max_row, every 13th empty).  `dups` rows repeat an id; values in
+    [0.5, 1.5], with `big` 5 % of them up to 10.  Regression targets with `clamp`: the prediction's clamp [lo, hi] is the middle 60 % of the
+    targets, so it binds.  Returns (entries, row_ptr, target, n_features, lo, hi)."""
+    rng = np.random.default_rng(seed)
+    W = max(int(max_row), 1)
+    if fixed:
+        sizes = np.full(rows, max_row, dtype=np.int64)
+    else:
+        sizes = rng.integers(0, max_row + 1, rows).astype(np.int64)
+        sizes[::13] = 0
+        sizes[rows // 2] = max_row
+    rp = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+    ent = np.zeros(int(rp[-1]), dtype=ENTRY)
+    r_of = np.repeat(np.arange(rows), sizes)
+    pos = np.arange(len(ent)) - rp[:-1].astype(np.int64)[r_of]
+    perm = np.argsort(rng.random((rows, W)), axis=1)                  # a random order of each row's window
+    ent["id"] = ((r_of % period) * W + perm[r_of, pos]).astype(np.uint32)
+    for r in rng.choice(np.nonzero(sizes >= 2)[0], min(dups, int((sizes >= 2).sum())), replace=False):
+        a = int(rp[r])
+        ent["id"][a + 1] = ent["id"][a]
+    val = rng.uniform(0.5, 1.5, len(ent))
+    if big:
+        sel = rng.random(len(ent)) < 0.05
+        val[sel] = rng.uniform(1.5, 10.0, int(sel.sum()))
+    ent["value"] = np.round(val, 3).astype(np.float32)
+    if task == 1:
+        y = np.where(rng.random(rows) < 0.5, -1.0, 1.0).astype(np.float32)
+        lo, hi = -1.0, 1.0
+    else:
+        y = np.round(rng.normal(3.0, 1.2, rows), 2).astype(np.float32)
+        lo, hi = (float(np.percentile(y, 20)), float(np.percentile(y, 80))) if clamp else (float(y.min()), float(y.max()))
+    return ent, rp, y, period * W, lo, hi
+
+
+def _case(name, k, k0, k1, task, rows, max_row, period, fixed=False, dups=0, big=False, clamp=False, knobs=None):
+    return dict(name=name, k=k, k0=k0, k1=k1, task=task, rows=rows, max_row=max_row, period=period, fixed=fixed, dups=dups, big=big,
+                clamp=clamp, knobs=dict(knobs or {}))
+
+
+KS = [1, 2, 3, 4, 5, 8, 9, 16, 17, 31, 32, 33, 64, 65, 100, 128, 129, 200, 256, 257, 512, 1000]
+BIAS_LIN = [(1, 1), (0, 1), (1, 0), (0, 0)]
+
+
+def online_cases():
+    """a seeded covering design over k, (k0, k1), task, row shape, row length and form -- not the cross product: every k once as
+    runs and once one example at a time (rotating through the switches), plus every k_run_fused instance, each row-length edge of the
+    register paths, rows that repeat an id, large values and a binding clamp.  tests/test_seq_routes.py checks the coverage."""
+    rng = np.random.default_rng(2024)
+    out = []
+    one_at_a_time = [{}, {"FMX_SEQ_WG": "0"}, {"FMX_SEQ_ROWS": "0"}, {"FMX_SEQ_RUNS": "0"}]
+    row_lens = [16, 17, 40, 41, 64, 65, 150]
+    for i, k in enumerate(KS):
+        k0, k1 = BIAS_LIN[i % 4]
+        task = i % 2
+        kp = R.kp_of(k)
+        big_k = k > 128
+        # runs: windows wide enough for runs of ~100 .. 900 rows; beyond the register path (rows > 64, or no one-launch instance) two launches
+        ml = row_lens[i % len(row_lens)] if not big_k else (16, 41, 65)[i % 3]
+        rows = 3000 if ml <= 64 else 1200
+        out.append(_case("runs_k%d" % k, k, k0, k1, task, rows, ml, int(rng.integers(100, 900)), fixed=(i % 3 == 0),
+                         dups=3 * (i % 2), big=(i % 5 == 1), clamp=(task == 0 and i % 4 == 0),
+                         knobs={"FMX_SEQ_RUNS_ONE": "0"} if kp in (8, 16, 32, 64, 128) and i % 4 == 3 else None))
+        # one example at a time: a few windows, so consecutive rows collide and the runs average < 16 rows
+        k0b, k1b = BIAS_LIN[(i + 1) % 4]
+        mlb = (16, 40, 41, 64, 65)[i % 5]
+        out.append(_case("seq_k%d" % k, k, k0b, k1b, 1 - task, 2000 if k < 512 else 800, mlb, int(rng.integers(2, 6)),
+                         fixed=(i % 3 == 1), dups=4 * ((i + 1) % 2), big=(i % 5 == 2), clamp=((1 - task) == 0 and i % 3 == 0),
+                         knobs=one_at_a_time[i % 4]))
+    # every k_run_fused instance: KP 8 / 16 / 32 (ZR = KP), KP 64 / 128 at rows of <= 16, 17 .. 40, 41 .. 64 entries; both tasks
+    for j, (k, ml) in enumerate([(5, 64), (8, 17), (9, 40), (16, 3), (17, 41), (32, 64),
+                                 (33, 16), (64, 17), (64, 40), (33, 41), (64, 64), (33, 9),
+                                 (65, 16), (128, 40), (100, 41), (128, 64), (100, 12), (65, 33)]):
+        for task in (0, 1):
+            k0, k1 = BIAS_LIN[(j + task) % 4]
+            out.append(_case("fused_k%d_r%d_t%d" % (k, ml, task), k, k0, k1, task, 2500, ml, int(rng.integers(150, 1000)),
+                             fixed=(j % 2 == 0), dups=2 * (j % 3 == 0), clamp=(task == 0 and j % 2 == 1)))
+    # runs beyond the register path (rows of > 64 entries) at the row widths that also have a one-launch instance: two launches
+    out.append(_case("two_k20_r65", 20, 0, 1, 1, 1500, 65, 400))
+    out.append(_case("two_k24_r150", 24, 1, 0, 0, 1200, 150, 300, fixed=True, clamp=True))
+    out.append(_case("two_k6_r100", 6, 0, 0, 1, 1200, 100, 200, dups=2))
+    # one wavefront, a row at a time, at 128 lanes and rows of <= 32 entries
+    out.append(_case("rows_k100_r20", 100, 1, 0, 1, 2000, 20, 3, dups=3, knobs={"FMX_SEQ_WG": "0"}))
+    out.append(_case("rows_k70_r32", 70, 0, 0, 0, 2000, 32, 2, fixed=True, clamp=True, knobs={"FMX_SEQ_WG": "0"}))
+    # long rows: 1 000 and 5 000 entries in runs (two launches, fp32 sums) and one example at a time
+    out.append(_case("long_runs_k64", 64, 1, 1, 0, 300, 1000, 16, knobs={"FMX_SEQ_RUNS": "1"}))
+    out.append(_case("long_runs_k100", 100, 0, 1, 1, 300, 1000, 20, fixed=True))
+    out.append(_case("long_runs_k64_r5000", 64, 1, 1, 0, 120, 5000, 8, knobs={"FMX_SEQ_RUNS": "1"}))
+    out.append(_case("long_runs_k512_r5000", 512, 1, 1, 1, 120, 5000, 8, knobs={"FMX_SEQ_RUNS": "1"}))
+    out.append(_case("long_seq_k16", 16, 1, 0, 0, 300, 1000, 2))
+    out.append(_case("long_seq_k128", 128, 0, 1, 0, 600, 150, 3, dups=3, big=True))
+    out.append(_case("long_seq_k200", 200, 1, 1, 1, 200, 1000, 2, dups=2))
+    # the three-launch form: FMX_SEQ_RUNS_FUSED=0 (every run), and runs of > 2048 rows on their own
+    out.append(_case("three_k8", 8, 0, 1, 0, 3000, 12, 500, knobs={"FMX_SEQ_RUNS_FUSED": "0"}))
+    out.append(_case("three_k100", 100, 1, 0, 1, 3000, 40, 300, dups=3, knobs={"FMX_SEQ_RUNS_FUSED": "0"}))
+    out.append(_case("three_long_k4", 4, 1, 1, 1, 9000, 3, 3000, fixed=True))
+    out.append(_case("three_long_k257", 257, 0, 0, 0, 6000, 5, 2500, clamp=True))
+    return out
+
+
+def case_lr(c):
+    """the online loop's step on a row moves the prediction by ~ lr * sum_i x_i^2: long rows and large values take smaller steps (a fixed 0.002
+    diverges on rows of 1 000 entries -- in the reference as much as here)"""
+    lr = 0.01 if c["task"] == 1 else 0.002
+    return lr * min(1.0, 32.0 / c["max_row"]) * (0.25 if c["big"] else 1.0)
+
+
+def case_rows(c):
+    seed = zlib.crc32(c["name"].encode())
+    return make_rows(seed, c["rows"], c["max_row"], c["period"], c["fixed"], c["dups"], c["big"], c["task"], c["clamp"])
+
+
+def edge_rows(lengths, nnz_lo, nnz_hi, seed):
+    """a slot whose runs are exactly `lengths` long: every row has ids of its own (1 .. nnz entries, never empty), except the first row of
+    each run after the first, which shares ONE id with the row in front of it.  A length above the 4096-row bound stands for a
+    conflict-free stretch the cut must split.  Returns (entries, row_ptr, target, n_features)."""
+    rng = np.random.default_rng(seed)
+    rows = int(sum(lengths))
+    sizes = rng.integers(nnz_lo, nnz_hi + 1, rows).astype(np.int64)
+    rp = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+    ent = np.zeros(int(rp[-1]), dtype=ENTRY)
+    ent["id"] = rng.permutation(len(ent)).astype(np.uint32)             # every id once ...
+    r = 0
+    for L in lengths:
+        if r:                                                           # ... but a breaker row takes one of its predecessor's
+            a, p = int(rp[r]), int(rp[r - 1])
+            ent["id"][a + int(rng.integers(0, sizes[r]))] = ent["id"][p + int(rng.integers(0, sizes[r - 1]))]
+        r += int(L)
+    ent["value"] = np.round(rng.uniform(0.5, 1.5, len(ent)), 3).astype(np.float32)
+    return ent, rp, rng.normal(0, 1, rows).astype(np.float32), len(ent)
+
+
+def split_4096(lengths):
+    out = []
+    for L in lengths:
+        while L > R.RUN_MAX:
+            out.append(R.RUN_MAX)
+            L -= R.RUN_MAX
+        out.append(L)
+    return out
+
+
+EDGE_SLOTS = [[1, 1023, 1024, 1025, 2048, 2049], [4096, 4097]]
+EDGE_CASES = [(16, 1, 1, 0, 4, 4), (64, 0, 1, 1, 1, 6), (128, 1, 0, 0, 2, 5), (512, 0, 0, 1, 4, 4)]   # (k, k0, k1, task, nnz lo, hi)
+
+
+# ---------------------------------------------------------------------------------------------
+# GPU
+# ---------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def capi():
+    from libfm_amd import build, capi
+    build.build()
+    if capi.load().fmx_device_count() == 0:
+        pytest.fail("gpu-marked test without a HIP device")
+    return capi
+
+
+def set_knobs(monkeypatch, knobs):
+    for name in R.KNOBS:
+        if name in knobs:
+            monkeypatch.setenv(name, knobs[name])
+        else:
+            monkeypatch.delenv(name, raising=False)
+
+
+def start_model(oracle, seed, n, k, k0, k1, max_row):
+    m = oracle.Model(n, k, k0, k1, 0.001, 0.002, 0.003)
+    m.v[:] = oracle.init_values(seed, n, k, min(0.05, 0.4 / np.sqrt(k * max(max_row, 1))))
+    m.w[:] = oracle.init_values(seed + 50, n, 1, 0.05)[0]
+    m.w0 = 0.25
+    return m
+
+
+def check_route(st, case_k, k0, k1, task, ent, rp, knobs):
+    runs = R.cut_runs(ent, rp)
+    max_row = int(np.diff(rp.astype(np.int64)).max()) if len(rp) > 1 else 0
+    bits, _, n_runs = R.expected_route(case_k, k0, k1, task, max_row, runs, knobs)
+    assert st.status & R.SEQ_MASK == bits, "status %#x, expected %#x" % (st.status & R.SEQ_MASK, bits)
+    assert st.batches == (n_runs if n_runs is not None else len(rp) - 1)
+
+
+def run_online(capi, oracle, monkeypatch, ent, rp, y, n, k, k0, k1, task, lo, hi, knobs, seed, lr=None, epochs=2, check_ids=None):
+    """`epochs` epochs on the device and the oracle's online loop from the same start; the device's route is checked every epoch"""
+    set_knobs(monkeypatch, knobs)
+    max_row = int(np.diff(rp.astype(np.int64)).max())
+    lr = lr if lr is not None else (0.01 if task == 1 else 0.002)
+    d = oracle.Data(ent, rp, y)
+    m = start_model(oracle, seed, n, k, k0, k1, max_row)
+    h = capi.Handle(n, k, k0, k1, task, 0.001, 0.002, 0.003, lr, lo, hi)
+    try:
+        h.set_params(m.w0, m.w, m.v)
+        h.upload_rows(0, ent, rp, y)
+        for _ in range(epochs):
+            st = h.sgd_epoch(0, capi.SGD_SEQUENTIAL)
+            check_route(st, k, k0, k1, task, ent, rp, knobs)
+            oracle.sgd_epoch_online(m, d, task, lr, lo, hi)
+        w0, w, v = h.get_params()
+        pred = h.predict(0, d.n_rows)
+    finally:
+        h.close()
+    ids = check_ids if check_ids is not None else slice(None)
+    assert abs(w0 - m.w0) <= RTOL * abs(m.w0) + 1e-5, (w0, m.w0)
+    np.testing.assert_allclose(w[ids], m.w[ids], rtol=RTOL, atol=2e-5)
+    np.testing.assert_allclose(v[:, ids], m.v[:, ids], rtol=RTOL, atol=2e-5)
+    np.testing.assert_allclose(pred, oracle.predict_raw(m, d), rtol=RTOL, atol=5e-5)
+    return w0, w, v
+
+
+# ---- the real reference: every sgd_* fixture in every form ----
+@pytest.mark.parametrize("knobs", FORMS, ids=form_id)
+@pytest.mark.parametrize("name", FIXTURES)
+def test_fixture_in_every_form(capi, oracle, monkeypatch, name, knobs):
+    """the reference's own final parameters and predictions (as test_gpu_parity's trajectory test), with the form the switches select"""
+    set_knobs(monkeypatch, knobs)
+    g = Golden(name)
+    m = g.model(oracle, "init")
+    tr, te = g.data(oracle, "train"), g.data(oracle, "test")
+    h = capi.Handle(g.n, g.k, g.k0, g.k1, g.task, g.reg[0], g.reg[1], g.reg[2], g.lr, g.min_target, g.max_target)
+    try:
+        h.set_params(m.w0, m.w, m.v)
+        h.upload_rows(0, tr.entries, tr.row_ptr, tr.target)
+        h.upload_rows(1, te.entries, te.row_ptr, te.target)
+        for _ in range(g.iters):
+            st = h.sgd_epoch(0, capi.SGD_SEQUENTIAL)
+            check_route(st, g.k, g.k0, g.k1, g.task, tr.entries, tr.row_ptr, knobs)
+        w0, w, v = h.get_params()
+        pred = h.predict(1, te.n_rows)
+    finally:
+        h.close()
+    assert abs(w0 - float(g.z["final_w0"])) <= RTOL * abs(float(g.z["final_w0"])) + 1e-5
+    np.testing.assert_allclose(w, g.z["final_w"], rtol=RTOL, atol=1e-5)
+    np.testing.assert_allclose(v, g.z["final_v"], rtol=RTOL, atol=1e-5)
+    np.testing.assert_allclose(pred, g.z["pred_raw"], rtol=RTOL, atol=5e-5)
+
+
+# ---- the oracle's online loop: the covering design ----
+@pytest.mark.parametrize("c", online_cases(), ids=lambda c: c["name"])
+def test_online_loop_in_every_form(capi, oracle, monkeypatch, c):
+    ent, rp, y, n, lo, hi = case_rows(c)
+    run_online(capi, oracle, monkeypatch, ent, rp, y, n, c["k"], c["k0"], c["k1"], c["task"], lo, hi, c["knobs"], seed=c["k"] + 11, lr=case_lr(c))
+
+
+# ---- run-length edges: 1, 1023 | 1024 | 1025 (one / two launches), 2048 | 2049 (two / three), the 4096-row bound ----
+@pytest.mark.parametrize("k,k0,k1,task,lo_nnz,hi_nnz", EDGE_CASES, ids=lambda x: str(x))
+def test_run_length_edges(capi, oracle, monkeypatch, k, k0, k1, task, lo_nnz, hi_nnz):
+    for s, lengths in enumerate(EDGE_SLOTS):
+        ent, rp, y, n = edge_rows(lengths, lo_nnz, hi_nnz, seed=31 * k + s)
+        assert [nb for _, nb, _ in R.cut_runs(ent, rp)] == split_4096(lengths)
+        if task == 1:
+            y = np.where(y > 0, 1.0, -1.0).astype(np.float32)
+        lo, hi = (-1.0, 1.0) if task == 1 else (float(y.min()), float(y.max()))
+        run_online(capi, oracle, monkeypatch, ent, rp, y, n, k, k0, k1, task, lo, hi, {}, seed=k + s)
+
+
+# ---- determinism: two handles, the same input, bit-identical parameters, in every form ----
+DET_CASES = [("runs_k64", {}), ("fused_k9_r40_t1", {}), ("fused_k128_r64_t0", {}), ("runs_k256", {}), ("three_k100", {"FMX_SEQ_RUNS_FUSED": "0"}),
+             ("three_long_k4", {}), ("seq_k16", {}), ("seq_k100", {"FMX_SEQ_WG": "0"}), ("seq_k32", {"FMX_SEQ_WG": "0"}),
+             ("seq_k200", {}), ("seq_k8", {"FMX_SEQ_ROWS": "0"}), ("long_seq_k16", {})]
+
+
+@pytest.mark.parametrize("name,knobs", DET_CASES, ids=lambda x: x if isinstance(x, str) else form_id(x))
+def test_two_handles_bit_identical(capi, oracle, monkeypatch, name, knobs):
+    c = next(c for c in online_cases() if c["name"] == name)
+    ent, rp, y, n, lo, hi = case_rows(c)
+    set_knobs(monkeypatch, knobs)
+    m = start_model(oracle, 5, n, c["k"], c["k0"], c["k1"], c["max_row"])
+    outs, stats = [], []
+    for _ in range(2):
+        h = capi.Handle(n, c["k"], c["k0"], c["k1"], c["task"], 0.001, 0.002, 0.003, case_lr(c), lo, hi)
+        try:
+            h.set_params(m.w0, m.w, m.v)
+            h.upload_rows(0, ent, rp, y)
+            for _ in range(2):
+                st = h.sgd_epoch(0, capi.SGD_SEQUENTIAL)
+            outs.append(h.get_params())
+            stats.append((st.status & R.SEQ_MASK, st.batches))
+        finally:
+            h.close()
+    assert stats[0] == stats[1]
+    assert outs[0][0] == outs[1][0]
+    assert np.array_equal(outs[0][1], outs[1][1]) and np.array_equal(outs[0][2], outs[1][2])
