@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define FMX_ABI_VERSION 9
+#define FMX_ABI_VERSION 10
 
 enum {
   FMX_OK = 0,
@@ -441,6 +441,58 @@ int fmx_sgd_batch_info(fmx_handle h, int slot, const fmx_sgd_opts *opts, fmx_bat
  * requested != 0: that batch, with its gain and status; requested == 0: 262144 cut to the largest power of two (never below 32) with
  * learn_rate * curvature * batch * collision_mass <= 1 (curvature 1 for regression, 1/4 for classification) */
 int fmx_batch_rule(int32_t task, double learn_rate, double collision_mass, uint32_t requested, fmx_batch_info *out);
+
+/* ---- pairwise ranking (BPR) around fm_pairSGD (fm_sgd.h:53-126) ---------------------------------------------------
+ * The reference defines the pairwise update but no learner calls it; the loop around it is this library's.
+ * One epoch visits the slot's pairs t = 0 .. P-1 in stored order.  (a, b) = pairs[t] means "row a is preferred to row b":
+ *
+ *   y_a  = fm.predict(x_a, sum_pos, sum_sqr)            // fm_model.h:105-127, w0 included
+ *   y_b  = fm.predict(x_b, sum_neg, sum_sqr)
+ *   mult = -(1 - sigmoid(y_a - y_b))                    // BPR: descent on -ln sigmoid(y_a - y_b); sigmoid = util.h:52
+ *   fm_pairSGD(&fm, learn_rate, x_a, x_b, mult, sum_pos, sum_neg, grad_visited, grad)
+ *
+ * Properties of fm_pairSGD kept here (not those of fm_SGD): with k0 every pair does w0 -= reg0 * w0, without learning rate, and
+ * nothing else moves w0; a feature's linear gradient is the sum of its values in x_a minus the sum in x_b, its factor gradient
+ * sum_pos(f) x - v x x over its entries in x_a minus the same with sum_neg(f) over x_b (ids repeated inside a row and ids in both
+ * rows included); each distinct feature of the pair is updated once with ONE regularisation term (grad_visited); every sum and
+ * gradient comes from the parameters at the start of the pair; the targets of the rows are not used.
+ *
+ * Batch rule (FMX_SGD_MINIBATCH): the pairs are cut into batches of B consecutive pairs.  Every pair of a batch takes its sums and
+ * multiplier from the parameters at the start of the batch; each feature j touched by the batch is then updated once:
+ *   w_j  -= lr * sum_{t in batch, j in t} ( mult_t * gw_tj  + regw * w_j(start) )
+ *   v_jf -= lr * sum_{t in batch, j in t} ( mult_t * gv_tjf + regv * v_jf(start) )
+ * (gw, gv the per-pair gradients above, one regularisation term per pair); w0 takes w0 -= reg0 * w0 once per pair.  At B = 1 this
+ * rule is exactly the loop.  Sums run in a fixed order (pair order inside a (batch, feature) segment, no float atomics): two runs
+ * are bit-identical.
+ *
+ * fmx_upload_pairs : the pairs of a row slot, row_a[t] preferred to row_b[t], 0-based rows of the slot.  Every index must be
+ *                    < n_rows (FMX_E_ARG otherwise, nothing changes).  A new call replaces the pairs (resampled negatives);
+ *                    fmx_free_rows and a new upload into the slot drop them.
+ * fmx_pair_epoch   : one epoch.  mode FMX_SGD_SEQUENTIAL (one workgroup walks the pairs in order: the parity instrument) or
+ *                    FMX_SGD_MINIBATCH (batch = 0: FMX_PAIR_DEFAULT_BATCH pairs).  fmx_epoch_stats: rows = pairs, batches,
+ *                    batch_used, device_seconds, max_feature_count (MINIBATCH: entries of the longest (batch, feature) segment),
+ *                    setup_seconds (the one-time bucketing of the pair-expanded entries, cached per (slot, pairs, batch)).
+ *                    FMX_E_UNSUPPORTED: FMX_SGD_HOGWILD, a feature shard or communicator rank, a slot with kept `-relation`
+ *                    blocks, more than 2^31 - 1 pair-expanded entries (MINIBATCH).  FMX_E_STATE: no pairs uploaded, an open
+ *                    ALS / MCMC session on the slot, an open SGDA session.
+ * fmx_pair_evaluate: accuracy = fraction of pairs with y_a > y_b, loss = mean of -ln sigmoid(y_a - y_b); computed on the device
+ *                    with fp64 reductions in a fixed order. */
+#define FMX_PAIR_DEFAULT_BATCH 1024u
+typedef struct fmx_pair_opts {
+  int32_t  mode;            /* FMX_SGD_SEQUENTIAL or FMX_SGD_MINIBATCH */
+  uint32_t batch;           /* MINIBATCH: pairs per batch; 0 = FMX_PAIR_DEFAULT_BATCH */
+  uint32_t flags;           /* none defined yet: 0 */
+  uint32_t reserved;
+} fmx_pair_opts;
+typedef struct fmx_pair_eval {
+  double   accuracy;        /* fraction of pairs with y_a > y_b */
+  double   loss;            /* mean of -ln sigmoid(y_a - y_b) */
+  double   device_seconds;
+  uint64_t pairs;
+} fmx_pair_eval;
+int fmx_upload_pairs(fmx_handle h, int slot, const uint32_t *row_a, const uint32_t *row_b, uint64_t n_pairs);
+int fmx_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts *opts, fmx_epoch_stats *stats);
+int fmx_pair_evaluate(fmx_handle h, int slot, fmx_pair_eval *out);
 
 /* ---- minibatch step split at the exchange point, for one-process-per-GPU drivers --------------
  * partial: floats per batch = fmx_partial_floats(h, batch): [batch][KP] partial factor sums followed by

@@ -80,6 +80,17 @@ class Eval(C.Structure):
                 ("device_seconds", C.c_double), ("rows", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class PairOpts(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("batch", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PairEval(C.Structure):
+    _fields_ = [("accuracy", C.c_double), ("loss", C.c_double), ("device_seconds", C.c_double), ("pairs", C.c_uint64)]
+
+
+PAIR_DEFAULT_BATCH = 1024   # FMX_PAIR_DEFAULT_BATCH: fmx_pair_opts::batch = 0
+
+
 class Relation(C.Structure):
     _fields_ = [("entries", C.c_void_p), ("row_ptr", C.c_void_p), ("n_rows", C.c_uint32), ("reserved", C.c_uint32),
                 ("nnz", C.c_uint64), ("data_row_to_relation_row", C.c_void_p), ("attr_offset", C.c_uint64)]
@@ -179,6 +190,9 @@ SYMBOLS = [
     ("fmx_als_moments", C.c_int, [H, C.c_void_p]),
     ("fmx_als_sweep", C.c_int, [H, C.POINTER(AlsOpts), C.POINTER(AlsStats)]),
     ("fmx_als_end", C.c_int, [H]),
+    ("fmx_upload_pairs", C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("fmx_pair_epoch", C.c_int, [H, C.c_int, C.POINTER(PairOpts), C.POINTER(EpochStats)]),
+    ("fmx_pair_evaluate", C.c_int, [H, C.c_int, C.POINTER(PairEval)]),
     ("fmx_get_info", C.c_int, [H, C.POINTER(Info)]),
     ("fmx_synchronize", C.c_int, [H]),
 ]
@@ -402,6 +416,29 @@ class Handle:
 
     def predict_finish(self, n_rows, d_partial_ptr, d_yhat_ptr, stream=None):
         self._chk(self.lib.fmx_predict_finish(self.h, n_rows, d_partial_ptr, d_yhat_ptr, stream))
+
+    # pairwise ranking (BPR) -----------------------------------------------------------------
+    def upload_pairs(self, slot, row_a, row_b):
+        """the pairs of a row slot: row_a[t] is preferred to row_b[t] (0-based rows of the slot); replaces earlier pairs"""
+        row_a = np.ascontiguousarray(row_a, dtype=np.uint32)
+        row_b = np.ascontiguousarray(row_b, dtype=np.uint32)
+        if row_a.shape != row_b.shape or row_a.ndim != 1:
+            raise ValueError("upload_pairs: row_a and row_b must be 1-d arrays of one length")
+        self._chk(self.lib.fmx_upload_pairs(self.h, slot, _ptr(row_a) if len(row_a) else None,
+                                            _ptr(row_b) if len(row_b) else None, len(row_a)))
+
+    def pair_epoch(self, slot, mode=SGD_SEQUENTIAL, batch=0, flags=0):
+        """one epoch of the pairwise learner over the slot's pairs (fmx_pair_epoch); returns EpochStats (rows = pairs)"""
+        opts = PairOpts(int(mode), int(batch), int(flags), 0)
+        st = EpochStats()
+        self._chk(self.lib.fmx_pair_epoch(self.h, slot, C.byref(opts), C.byref(st)))
+        return st
+
+    def pair_evaluate(self, slot):
+        """pair accuracy (y_a > y_b) and mean -ln sigmoid(y_a - y_b) over the slot's pairs (fmx_pair_evaluate)"""
+        ev = PairEval()
+        self._chk(self.lib.fmx_pair_evaluate(self.h, slot, C.byref(ev)))
+        return ev
 
     # SGDA ------------------------------------------------------------------------------------
     def sgda_begin(self):

@@ -28,11 +28,33 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "test": "filename for test data [MANDATORY]", "validation": "", "out": "filename for output",
          "dim": "'k0,k1,k2': k0=use bias, k1=use 1-way interactions, k2=dim of 2-way interactions; default=1,1,8",
          "regular": "'r0,r1,r2' for SGD and ALS", "init_stdev": "stdev for initialization of 2-way factors; default=0.1",
-         "iter": "number of iterations; default=100", "learn_rate": "learn_rate for SGD", "method": "sgd, als, mcmc; default=mcmc",
+         "iter": "number of iterations; default=100", "learn_rate": "learn_rate for SGD", "method": "sgd, sgda, als, mcmc, bpr; default=mcmc",
          "verbosity": "", "rlog": "write measurements within iterations to a file", "seed": "integer value", "help": "",
          "relation": "BS: filenames for the relations, default=''", "cache_size": "", "save_model": "filename for writing the FM model",
          "load_model": "filename for reading the FM model",
-         "gpu_mode": "sequential | minibatch | hogwild (default minibatch)", "batch": "", "w0_chunk": "", "device": ""}
+         "gpu_mode": "sequential | minibatch | hogwild (default minibatch; bpr: sequential | minibatch, default sequential)", "batch": "",
+         "w0_chunk": "", "device": "",
+         "train_pairs": "bpr: pairs of the train rows, one per line 'row_a row_b' (0-based rows; row_a is preferred) [MANDATORY for bpr]",
+         "test_pairs": "bpr: pairs of the test rows, same format [MANDATORY for bpr]"}
+
+
+def read_pairs(path, n_rows):
+    """a pairs file of -method bpr: one pair per line, 'row_a row_b', 0-based row numbers of the matching data file (row_a is
+    preferred to row_b); blank lines and lines starting with '#' are skipped"""
+    a, b = [], []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            t = line.split()
+            if not t or t[0].startswith("#"):
+                continue
+            if len(t) != 2:
+                raise ValueError("cannot parse line %d of %s: want 'row_a row_b'" % (no, path))
+            ra, rb = int(t[0]), int(t[1])
+            if not (0 <= ra < n_rows and 0 <= rb < n_rows):
+                raise ValueError("line %d of %s: row outside the data set (%d rows)" % (no, path, n_rows))
+            a.append(ra)
+            b.append(rb)
+    return np.array(a, dtype=np.uint32), np.array(b, dtype=np.uint32)
 
 
 def parse(argv):
@@ -86,8 +108,13 @@ def _main(argv):
     if method == "mcmc" and ("save_model" in a or "load_model" in a):
         print("WARNING: -save_model / -load_model enabled only for SGD and ALS.")      # libfm.cpp:123-133
         return 0
-    if method not in ("sgd", "sgda", "als", "mcmc"):
+    if method not in ("sgd", "sgda", "als", "mcmc", "bpr"):
         raise ValueError("unknown method")
+    if method == "bpr":                      # pairwise ranking: the targets are not used, so -task is optional
+        a.setdefault("task", "r")
+        for need in ("train_pairs", "test_pairs"):
+            if need not in a:
+                raise ValueError("-%s is mandatory for -method bpr" % need)
     for need in ("task", "train", "test"):
         if need not in a:
             raise ValueError("-%s is mandatory" % need)
@@ -180,7 +207,15 @@ def _main(argv):
     fm.reg0, fm.regw, fm.regv = reg
     num_iter = int(a.get("iter", "100"))
 
-    if method in ("sgd", "sgda"):
+    if method == "bpr":
+        l = L.FMLearnPairSGD()
+        lrs = [float(x) for x in split_list(a.get("learn_rate", ""))]
+        if len(lrs) != 1:
+            raise ValueError("-learn_rate needs 1 value for bpr")
+        l.learn_rate = lrs[0]
+        l.mode = a.get("gpu_mode", "sequential")
+        l.batch = int(a.get("batch", "0"))
+    elif method in ("sgd", "sgda"):
         l = L.FMLearnSGD() if method == "sgd" else L.FMLearnSGDA()
         if method == "sgda":
             l.validation = validation
@@ -209,7 +244,16 @@ def _main(argv):
     l.min_target, l.max_target = min_t, max_t
     l.device = int(a.get("device", "-1"))
     l.init()
-    l.learn(train, test)
+    if method == "bpr":
+        print("Loading pairs...\t")
+        train_pairs = read_pairs(a["train_pairs"], train.num_cases)
+        test_pairs = read_pairs(a["test_pairs"], test.num_cases)
+        print("train_pairs=%d\ttest_pairs=%d" % (len(train_pairs[0]), len(test_pairs[0])))
+        l.learn(train, train_pairs, test, test_pairs)
+    else:
+        l.learn(train, test)
+    if method == "bpr":
+        print("Final\tTrain=%g\tTest=%g" % (l.evaluate_pairs(train), l.evaluate_pairs(test)))
     if method in ("sgd", "sgda"):
         print("Final\tTrain=%g\tTest=%g" % (l.evaluate(train), l.evaluate(test)))   # libfm.cpp:418-420
     if "rlog" in a and a["rlog"]:
@@ -219,7 +263,7 @@ def _main(argv):
             for row in l.log:
                 f.write("\t".join("%g" % row[k] for k in keys) + "\n")
     if "out" in a and a["out"]:
-        pred = l.predict(test)
+        pred = l.predict_raw(test) if method == "bpr" else l.predict(test)      # bpr: raw y per test row (a score)
         with open(a["out"], "w") as f:                                               # DVector::save, matrix.h:332-342
             f.write("".join("%g\n" % p for p in pred))
     if "save_model" in a and a["save_model"]:

@@ -129,6 +129,7 @@ void free_slot(Slot& s) {
   for (BlockRows* b : s.blocks) free_block(b);
   s.blocks.clear();
   free_segments(s);
+  free_pairs(s);
   if (s.ent) fmx_dev_free(s.ent);
   if (s.row_ptr) fmx_dev_free(s.row_ptr);
   if (s.target) fmx_dev_free(s.target);

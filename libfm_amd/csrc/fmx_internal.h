@@ -64,7 +64,23 @@ struct Slot {
   std::vector<uint32_t> run_start;   // [n_runs + 1]; empty: not built
   std::vector<uint8_t>  run_single;  // [n_runs] 1: one row that repeats an id (entry-by-entry kernel)
   std::vector<struct BlockRows*> blocks;   // `-relation` blocks kept apart from these (main) rows; empty: plain / expanded rows
+  // pairwise ranking (fmx_upload_pairs, fmx_pair.hip): row pair_a[t] is preferred to row pair_b[t]
+  bool      pairs_set = false;
+  uint64_t  n_pairs = 0;
+  uint32_t* pair_a = nullptr;
+  uint32_t* pair_b = nullptr;
+  uint64_t* pair_off = nullptr;      // [n_pairs + 1] first entry of every pair in the pair-expanded stream (x_a, then x_b)
+  uint64_t  pair_nnz = 0;            // entries of that stream
+  uint32_t  pair_max_len = 0;        // longest |x_a| + |x_b| of a pair
+  // its (batch, feature) bucketing for FMX_SGD_MINIBATCH, built for one batch size
+  uint32_t  pair_seg_B = 0;
+  TEntry*   pair_t_ent = nullptr;    // [pair_nnz] sorted payload {pair in batch << 1 | side, value}
+  uint32_t* pair_seg_head = nullptr; // [pair_nseg + 1] first sorted entry of every segment
+  uint32_t* pair_seg_feat = nullptr; // [pair_nseg]
+  uint32_t  pair_nseg = 0, pair_max_seg = 0;
+  std::vector<uint32_t> pair_batch_seg;   // [n_batches + 1] first segment of every batch
 };
+void free_pairs(Slot& s);                                                // fmx_pair.hip
 
 // one `-relation` block kept apart from the main rows (fmx_upload_block_rows_ex, FMX_BLOCKS_KEEP): RelationData +
 // RelationJoin, src/libfm/src/relation.h:32-60

@@ -403,6 +403,50 @@ def _keep_finite(new, old):
     return np.where(np.isfinite(new), new, old)
 
 
+class FMLearnPairSGD(FMLearnSGD):
+    """Pairwise ranking (BPR) around the reference's fm_pairSGD (fm_sgd.h:53-126) on the GPU.  The reference has the update but
+    no learner that calls it; the loop is include/fmx.h's: per pair (a, b), "row a preferred to row b", mult = -(1 - sigmoid(y_a - y_b))
+    and one fm_pairSGD step.  Fields: num_iter, learn_rate, mode ('sequential': the pairs in order, 'minibatch': the batch rule),
+    batch (minibatch: pairs per batch, 0 = the library's default).  Pairs are (row_a, row_b) arrays of 0-based rows of their data."""
+
+    MODES = {"sequential": capi.SGD_SEQUENTIAL, "minibatch": capi.SGD_MINIBATCH}
+
+    def __init__(self):
+        super().__init__()
+        self.mode = "sequential"
+        self._pairs = {}
+
+    def _pair_slot(self, data, pairs):
+        slot = self._slot(data)
+        a, b = (np.ascontiguousarray(p, dtype=np.uint32) for p in pairs)
+        key = (a.tobytes(), b.tobytes())
+        if self._pairs.get(slot) != key:                        # (new or resampled pairs replace the old ones)
+            self._h.upload_pairs(slot, a, b)
+            self._pairs[slot] = key
+        return slot
+
+    def evaluate_pairs(self, data, pairs=None):
+        """pair accuracy (fraction of pairs with y_a > y_b) over the pairs last uploaded for `data` (or these)"""
+        slot = self._pair_slot(data, pairs) if pairs is not None else self._slot(data)
+        return self._h.pair_evaluate(slot).accuracy
+
+    def learn(self, train, train_pairs, test, test_pairs):
+        if self.mode not in self.MODES:
+            raise ValueError("unknown mode for pairwise SGD: %s (sequential | minibatch)" % self.mode)
+        print("learnrate=%g" % self.learn_rate, file=self.out)
+        print("#iterations=%d" % self.num_iter, file=self.out)
+        st = self._pair_slot(train, train_pairs)
+        se = self._pair_slot(test, test_pairs)
+        for i in range(self.num_iter):
+            stats = self._h.pair_epoch(st, self.MODES[self.mode], self.batch)
+            tr, te = self._h.pair_evaluate(st), self._h.pair_evaluate(se)
+            print("#Iter=%3d\tTrain=%g\tTest=%g" % (i, tr.accuracy, te.accuracy), file=self.out)
+            print("#Iter=%3d\tloss: Train=%g\tTest=%g" % (i, tr.loss, te.loss), file=sys.stderr)
+            self.log.append({"accuracy_train": tr.accuracy, "accuracy_test": te.accuracy, "loss_train": tr.loss,
+                             "loss_test": te.loss, "time_learn": stats.device_seconds})
+        self.sync_model()
+
+
 class FMLearnSGDA(FMLearnSGD):
     """fm_learn_sgd_element_adapt_reg (`-method sgda`, fm_learn_sgd_element_adapt_reg.h:44-93) on the GPU: theta steps
     on the train rows alternate with lambda steps on `validation` (libfm.cpp:276-279).  gpu_batch = 0: the reference's

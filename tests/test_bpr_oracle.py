@@ -1,0 +1,104 @@
+"""CPU: the fp64 restatement of the pairwise ranking learner (tests/bpr_oracle.py) against the real reference's fm_pairSGD
+(tests/golden/bpr_*.npz, make_bpr_golden.py), the batch rule against the loop, and the new C-ABI surface (ABI 10)."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import bpr_oracle as B
+from conftest import GOLDEN_DIR, ROOT, golden_cases
+
+CASES = [c for c in golden_cases() if c.startswith("bpr_")]
+
+
+class M:
+    """a plain fp64 model (the fields bpr_oracle reads)"""
+
+    def __init__(self, z, which):
+        self.k0, self.k1 = bool(int(z["k0"])), bool(int(z["k1"]))
+        self.reg0, self.regw, self.regv = (float(x) for x in z["reg"])
+        self.w0 = float(z[which + "_w0"])
+        self.w = z[which + "_w"].astype(np.float64).copy()
+        self.v = z[which + "_v"].astype(np.float64).copy()
+
+
+def load(name):
+    return np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
+
+
+def test_fixture_set():
+    assert len(CASES) >= 4
+    ks = {int(load(c)["k"]) for c in CASES}
+    assert {5, 8, 64} <= ks
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_loop_equals_reference(name):
+    z = load(name)
+    m = M(z, "init")
+    lr = float(z["lr"])
+    for it in range(int(z["iters"])):
+        B.pair_epoch_loop(m, z["train_entries"], z["train_row_ptr"], z["pair_a"], z["pair_b"], lr)
+        if it == 0:
+            for f in ("w", "v"):
+                np.testing.assert_allclose(getattr(m, f), z["epoch1_" + f], rtol=1e-12, atol=1e-12)
+            assert abs(m.w0 - float(z["epoch1_w0"])) <= 1e-12 * max(1.0, abs(float(z["epoch1_w0"])))
+    np.testing.assert_allclose(m.w, z["final_w"], rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(m.v, z["final_v"], rtol=1e-12, atol=1e-12)
+    assert abs(m.w0 - float(z["final_w0"])) <= 1e-12 * max(1.0, abs(float(z["final_w0"])))
+    np.testing.assert_allclose(B.predict_rows(m, z["test_entries"], z["test_row_ptr"]), z["test_pred"], rtol=1e-12, atol=1e-12)
+
+
+def test_fixtures_learn_and_keep_their_properties():
+    # the learner ranks the training pairs better than the start; the w0 case decays from 0.5 without learning rate
+    for name in CASES:
+        z = load(name)
+        d0 = B.pair_d(M(z, "init"), z["train_entries"], z["train_row_ptr"], z["pair_a"], z["pair_b"])
+        d1 = B.pair_d(M(z, "final"), z["train_entries"], z["train_row_ptr"], z["pair_a"], z["pair_b"])
+        assert B.pair_metrics(d1)[1] < B.pair_metrics(d0)[1], name
+    z = load("bpr_w0_nolin_k4")
+    P, iters, reg0 = len(z["pair_a"]), int(z["iters"]), float(z["reg"][0])
+    assert float(z["init_w0"]) == 0.5 and not z["final_w"].any()
+    assert abs(float(z["final_w0"]) - 0.5 * (1 - reg0) ** (P * iters)) < 1e-12
+
+
+@pytest.mark.parametrize("name", ["bpr_ml_k8", "bpr_ragged_dup_k5"])
+def test_batch_rule_at_one_is_the_loop_and_at_seven_is_not(name):
+    z = load(name)
+    ent, rp, pa, pb, lr = z["train_entries"], z["train_row_ptr"], z["pair_a"][:150], z["pair_b"][:150], float(z["lr"])
+    loop, one, seven = M(z, "init"), M(z, "init"), M(z, "init")
+    B.pair_epoch_loop(loop, ent, rp, pa, pb, lr)
+    B.pair_epoch_batch(one, ent, rp, pa, pb, lr, 1)
+    B.pair_epoch_batch(seven, ent, rp, pa, pb, lr, 7)
+    for f in ("w", "v"):
+        np.testing.assert_allclose(getattr(one, f), getattr(loop, f), rtol=1e-13, atol=1e-13)
+    assert abs(one.w0 - loop.w0) <= 1e-13
+    assert np.abs(seven.v - loop.v).max() > 1e-6
+
+
+def test_batch_rule_one_term_per_pair():
+    # one feature in both rows of a pair and twice in x_a: ONE regularisation term per pair, the value sums cancel as fm_pairSGD says
+    class Toy:
+        k0, k1, reg0, regw, regv = False, True, 0.0, 0.5, 0.0
+    m = Toy()
+    m.w0, m.w, m.v = 0.0, np.array([1.0, 0.0]), np.zeros((1, 2))
+    ent = np.zeros(3, dtype=[("id", np.uint32), ("value", np.float32)])
+    ent["id"] = [0, 0, 0]
+    ent["value"] = [1.0, 1.0, 2.0]
+    rp = np.array([0, 2, 3], np.uint64)
+    B.pair_epoch_batch(m, ent, rp, np.array([0]), np.array([1]), 0.1, 4)
+    # gw = 1 + 1 - 2 = 0: w -= lr * (mult * 0 + regw * w) once
+    assert m.w[0] == pytest.approx(1.0 - 0.1 * 0.5)
+
+
+def test_abi_version_and_pair_symbols():
+    from libfm_amd import build, capi
+    build.build()
+    lib = capi.load()
+    hdr = open(os.path.join(ROOT, "include", "fmx.h")).read()
+    assert int(re.search(r"#define\s+FMX_ABI_VERSION\s+(\d+)", hdr).group(1)) == 10 == lib.fmx_abi_version()
+    names = {n for n, _, _ in capi.SYMBOLS}
+    for fn in ("fmx_upload_pairs", "fmx_pair_epoch", "fmx_pair_evaluate"):
+        assert fn in names and fn + "(" in hdr.replace(" (", "(") and hasattr(lib, fn)
+    assert int(re.search(r"#define\s+FMX_PAIR_DEFAULT_BATCH\s+(\d+)u", hdr).group(1)) == capi.PAIR_DEFAULT_BATCH
