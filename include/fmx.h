@@ -494,6 +494,46 @@ int fmx_upload_pairs(fmx_handle h, int slot, const uint32_t *row_a, const uint32
 int fmx_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts *opts, fmx_epoch_stats *stats);
 int fmx_pair_evaluate(fmx_handle h, int slot, fmx_pair_eval *out);
 
+/* ---- top-K retrieval of candidate rows per query row ----------------------------------------
+ * For query row q of query_slot and candidate row c of cand_slot, score(q, c) is the raw y-hat of the JOINED row x_q ++ x_c
+ * (fm_model.h:105-127: w0 once, no clamp, no sigmoid; ids repeated inside a row or across the two rows count separately), computed
+ * without the join:
+ *   score(q, c) = a_q + b_c + sum_f S_q[f] S_c[f]          S_r[f] = sum_{i in r} v[id_i][f] x_i
+ *   a_q = k0 w0 + k1 lin_q + 1/2 sum_f (S_q[f]^2 - SS_q[f]),  b_c = k1 lin_c + 1/2 sum_f (S_c[f]^2 - SS_c[f])
+ * evaluated in fp32 on the device (the dot product on the f32 matrix units) and returned widened to double.
+ * Result per query: the topk candidates with the highest score in descending order; equal scores by the lower candidate index
+ * first; NaN scores are never returned; fewer than topk eligible candidates: padded with index UINT32_MAX and score -INFINITY.
+ *   query rows   : [query_row0, query_row0 + n_query) of query_slot; a query's list does not depend on the other queries of the call,
+ *                  nor on how the library splits the candidates (FMX_TOPK_SPLITS at fmx_create forces the split count); two calls
+ *                  with the same inputs are bit-identical.  query_slot may equal cand_slot.
+ *   exclusion    : exclude_ptr (NULL or host [n_query + 1] offsets, query i of THIS call) into exclude_idx: candidate rows that
+ *                  query i must not return; repeats and any order allowed.  An index >= the candidate rows fails the call with
+ *                  FMX_E_ARG and writes nothing.
+ * Preconditions as fmx_predict.  FMX_E_UNSUPPORTED: a feature shard or communicator rank, a slot with kept `-relation` blocks.
+ * FMX_E_ARG: topk = 0 or > FMX_TOPK_MAX, a query range outside the slot, NULL outputs or opts, flags != 0.  FMX_E_STATE: a slot that
+ * was never uploaded.  Device scratch stays bounded (queries are taken in chunks) besides the factor sums of the two row sets.
+ * Added without an ABI version change: a caller detects the feature by the symbol fmx_topk. */
+#define FMX_TOPK_MAX 1024u
+typedef struct fmx_topk_opts {
+  uint32_t topk;                 /* K: results per query, 1 .. FMX_TOPK_MAX */
+  uint32_t flags;                /* none defined yet: 0 */
+  uint64_t query_row0;           /* first query row of the query slot */
+  uint32_t n_query;              /* query rows scored by this call */
+  uint32_t reserved;
+  const uint64_t *exclude_ptr;   /* NULL, or host [n_query + 1] offsets into exclude_idx (query i of THIS call) */
+  const uint32_t *exclude_idx;   /* candidate rows excluded for that query */
+} fmx_topk_opts;
+typedef struct fmx_topk_stats {
+  double   device_seconds;       /* whole call on the device */
+  double   score_seconds;        /* the score-and-select kernels only */
+  uint64_t scores;               /* n_query * n_cand */
+  uint32_t splits;               /* candidate splits the library chose */
+  uint32_t reserved;
+} fmx_topk_stats;
+/* idx_out: uint32 [n_query][topk]; score_out: double [n_query][topk] (the device's fp32 score, widened); stats may be NULL */
+int fmx_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk_opts *opts,
+             uint32_t *idx_out, double *score_out, fmx_topk_stats *stats);
+
 /* ---- minibatch step split at the exchange point, for one-process-per-GPU drivers --------------
  * partial: floats per batch = fmx_partial_floats(h, batch): [batch][KP] partial factor sums followed by
  *          [batch] scalars (linear term - 0.5*sum of squares).  d_partial is DEVICE memory, 16-byte aligned.

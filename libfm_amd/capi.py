@@ -91,6 +91,20 @@ class PairEval(C.Structure):
 PAIR_DEFAULT_BATCH = 1024   # FMX_PAIR_DEFAULT_BATCH: fmx_pair_opts::batch = 0
 
 
+class TopkOpts(C.Structure):
+    _fields_ = [("topk", C.c_uint32), ("flags", C.c_uint32), ("query_row0", C.c_uint64), ("n_query", C.c_uint32),
+                ("reserved", C.c_uint32), ("exclude_ptr", C.c_void_p), ("exclude_idx", C.c_void_p)]
+
+
+class TopkStats(C.Structure):
+    _fields_ = [("device_seconds", C.c_double), ("score_seconds", C.c_double), ("scores", C.c_uint64), ("splits", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+TOPK_MAX = 1024             # FMX_TOPK_MAX: results per query, at most
+TOPK_NONE = 0xFFFFFFFF      # index of a padding entry (its score is -inf)
+
+
 class Relation(C.Structure):
     _fields_ = [("entries", C.c_void_p), ("row_ptr", C.c_void_p), ("n_rows", C.c_uint32), ("reserved", C.c_uint32),
                 ("nnz", C.c_uint64), ("data_row_to_relation_row", C.c_void_p), ("attr_offset", C.c_uint64)]
@@ -193,6 +207,7 @@ SYMBOLS = [
     ("fmx_upload_pairs", C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]),
     ("fmx_pair_epoch", C.c_int, [H, C.c_int, C.POINTER(PairOpts), C.POINTER(EpochStats)]),
     ("fmx_pair_evaluate", C.c_int, [H, C.c_int, C.POINTER(PairEval)]),
+    ("fmx_topk", C.c_int, [H, C.c_int, C.c_int, C.POINTER(TopkOpts), C.c_void_p, C.c_void_p, C.POINTER(TopkStats)]),
     ("fmx_get_info", C.c_int, [H, C.POINTER(Info)]),
     ("fmx_synchronize", C.c_int, [H]),
 ]
@@ -439,6 +454,37 @@ class Handle:
         ev = PairEval()
         self._chk(self.lib.fmx_pair_evaluate(self.h, slot, C.byref(ev)))
         return ev
+
+    # top-K retrieval -------------------------------------------------------------------------
+    def topk(self, query_slot, cand_slot, topk, query_row0=0, n_query=None, exclude=None, stats=False):
+        """the topk best candidate rows of cand_slot for every query row [query_row0, query_row0 + n_query) of query_slot
+        (fmx_topk): returns (idx uint32 [n, topk], score float64 [n, topk]), padded with (TOPK_NONE, -inf); with stats=True
+        also the TopkStats.  exclude: None, or (ptr [n + 1], idx) -- a CSR of candidate rows per query of this call -- or a
+        list of n iterables of candidate rows."""
+        if n_query is None:
+            n_rows = C.c_uint32(0)
+            self._chk(self.lib.fmx_rows_info(self.h, query_slot, C.byref(n_rows), None))
+            n_query = max(n_rows.value - int(query_row0), 0)
+        n_query = int(n_query)
+        topk = int(topk)
+        ex_ptr = ex_idx = None
+        if exclude is not None:
+            if isinstance(exclude, tuple) and len(exclude) == 2:
+                ex_ptr = np.ascontiguousarray(exclude[0], dtype=np.uint64)
+                ex_idx = np.ascontiguousarray(exclude[1], dtype=np.uint32)
+            else:
+                lists = [np.asarray(list(e), dtype=np.uint32) for e in exclude]
+                ex_ptr = np.zeros(len(lists) + 1, dtype=np.uint64)
+                ex_ptr[1:] = np.cumsum([len(e) for e in lists])
+                ex_idx = np.concatenate(lists).astype(np.uint32) if lists else np.zeros(0, dtype=np.uint32)
+            if len(ex_ptr) != n_query + 1:
+                raise ValueError("topk: exclude_ptr must hold n_query + 1 = %d offsets" % (n_query + 1))
+        opts = TopkOpts(topk, 0, int(query_row0), n_query, 0, _ptr(ex_ptr), _ptr(ex_idx) if ex_idx is not None and len(ex_idx) else None)
+        idx = np.zeros((n_query, max(topk, 0)), dtype=np.uint32)
+        score = np.zeros((n_query, max(topk, 0)), dtype=np.float64)
+        st = TopkStats()
+        self._chk(self.lib.fmx_topk(self.h, query_slot, cand_slot, C.byref(opts), _ptr(idx), _ptr(score), C.byref(st)))
+        return (idx, score, st) if stats else (idx, score)
 
     # SGDA ------------------------------------------------------------------------------------
     def sgda_begin(self):

@@ -14,6 +14,8 @@ reference's error convention: "ERROR: ..." on stderr and exit status 0 (:436-441
 <a>.xt, <a>.train, <a>.test and optional <a>.groups; the joined rows are expanded on the device.  `-cache_size` is
 accepted and ignored (everything is resident).
 GPU-only additions: -gpu_mode sequential|minibatch|hogwild (default minibatch), -batch, -w0_chunk, -device.
+Top-K retrieval after training (every method but mcmc): -topk K -candidates F [-queries F] [-exclude F] [-topk_out F] ranks the
+candidate rows for every query row (default: the test rows) by the raw prediction of the joined row (fmx_topk).
 """
 import sys
 import time
@@ -35,7 +37,12 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "gpu_mode": "sequential | minibatch | hogwild (default minibatch; bpr: sequential | minibatch, default sequential)", "batch": "",
          "w0_chunk": "", "device": "",
          "train_pairs": "bpr: pairs of the train rows, one per line 'row_a row_b' (0-based rows; row_a is preferred) [MANDATORY for bpr]",
-         "test_pairs": "bpr: pairs of the test rows, same format [MANDATORY for bpr]"}
+         "test_pairs": "bpr: pairs of the test rows, same format [MANDATORY for bpr]",
+         "candidates": "top-K retrieval after training: filename of the candidate rows (libFM text or binary)",
+         "topk": "results per query row (1 .. 1024); needs -candidates; not with -method mcmc",
+         "topk_out": "filename for the top-K lists: one line per query, 'cand:score cand:score ...'",
+         "queries": "filename of the query rows; default: the test rows",
+         "exclude": "filename of excluded pairs, one per line 'query_row cand_row'"}
 
 
 def read_pairs(path, n_rows):
@@ -55,6 +62,36 @@ def read_pairs(path, n_rows):
             a.append(ra)
             b.append(rb)
     return np.array(a, dtype=np.uint32), np.array(b, dtype=np.uint32)
+
+
+def read_exclude(path, n_query, n_cand):
+    """an -exclude file: one pair per line, 'query_row cand_row' (0-based); returns the CSR (ptr [n_query + 1], idx)"""
+    q, c = [], []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            t = line.split()
+            if not t or t[0].startswith("#"):
+                continue
+            if len(t) != 2:
+                raise ValueError("cannot parse line %d of %s: want 'query_row cand_row'" % (no, path))
+            qr, cr = int(t[0]), int(t[1])
+            if not (0 <= qr < n_query and 0 <= cr < n_cand):
+                raise ValueError("line %d of %s: row outside the query (%d) or candidate (%d) rows" % (no, path, n_query, n_cand))
+            q.append(qr)
+            c.append(cr)
+    q = np.array(q, dtype=np.int64)
+    order = np.argsort(q, kind="stable")
+    ptr = np.zeros(n_query + 1, dtype=np.uint64)
+    ptr[1:] = np.cumsum(np.bincount(q, minlength=n_query))
+    return ptr, np.array(c, dtype=np.uint32)[order]
+
+
+def write_topk(path, idx, score):
+    """one line per query: 'cand:score ...' with %g scores, padding entries left out"""
+    none = np.uint32(0xFFFFFFFF)
+    with open(path, "w") as f:
+        for i, s in zip(idx, score):
+            f.write(" ".join("%d:%g" % (int(c), float(v)) for c, v in zip(i, s) if c != none) + "\n")
 
 
 def parse(argv):
@@ -110,6 +147,12 @@ def _main(argv):
         return 0
     if method not in ("sgd", "sgda", "als", "mcmc", "bpr"):
         raise ValueError("unknown method")
+    want_topk = any(f in a for f in ("topk", "candidates", "topk_out", "queries", "exclude"))
+    if want_topk:
+        if method == "mcmc":
+            raise ValueError("-topk is not supported with -method mcmc: its prediction averages the draws, no single model scores it")
+        if "topk" not in a or "candidates" not in a:
+            raise ValueError("top-K retrieval needs -topk and -candidates")
     if method == "bpr":                      # pairwise ranking: the targets are not used, so -task is optional
         a.setdefault("task", "r")
         for need in ("train_pairs", "test_pairs"):
@@ -269,6 +312,15 @@ def _main(argv):
     if "save_model" in a and a["save_model"]:
         print("Writing FM model to " + a["save_model"])
         fm.save_model(a["save_model"])
+    if want_topk:
+        topk = int(a["topk"])
+        cand = L.Data(*D.load(a["candidates"]))
+        queries = L.Data(*D.load(a["queries"])) if a.get("queries") else test
+        exclude = read_exclude(a["exclude"], queries.num_cases, cand.num_cases) if a.get("exclude") else None
+        idx, score = l.recommend(queries, cand, topk, exclude)
+        print("Top-K\tqueries=%d\tcandidates=%d\tK=%d" % (queries.num_cases, cand.num_cases, topk))
+        if a.get("topk_out"):
+            write_topk(a["topk_out"], idx, score)
     l.close()
     return 0
 

@@ -805,6 +805,8 @@ int fmx_create(const fmx_config* cfg, fmx_handle* out) {
     h->seq_wg = env_on("FMX_SEQ_WG");
     h->seq_runs_fused = env_on("FMX_SEQ_RUNS_FUSED");
     h->seq_runs_one = env_on("FMX_SEQ_RUNS_ONE");
+    const char* ts = getenv("FMX_TOPK_SPLITS");                 // fmx_topk (fmx_topk.hip): force the candidate splits, 1 .. 1024
+    if (ts) h->topk_splits = (uint32_t)std::min<unsigned long>(strtoul(ts, nullptr, 10), 1024ul);
     const char* xb = getenv("FMX_XCD_MAX_BATCH");
     if (xb) h->xcd_max_batch = (uint32_t)strtoul(xb, nullptr, 10);
     const char* sp = getenv("FMX_DEBUG_PIT_SPINS");

@@ -230,6 +230,7 @@ struct fmx_context_s {
   bool run_one = true, run_one_used = false;
   // FMX_SGD_SEQUENTIAL's forms, from the environment of fmx_create (default: all on; fmx_sgd_epoch picks by the slot's rows)
   bool seq_rows = true, seq_wg = true, seq_runs_fused = true, seq_runs_one = true;
+  uint32_t topk_splits = 0;                          // FMX_TOPK_SPLITS at fmx_create: candidate splits of fmx_topk (0: the library's choice)
   unsigned long long* run_slots = nullptr;          // [RUN_ONE_MAX] {tag, rest_e} of a one-launch run's examples
   // small batches of the minibatch rule as ONE launch per batch (k_small_one, fmx_small_kernels.h): {tag, mult_e} and {tag, rest_e} slots; off after a time-out
   unsigned long long* small_slots = nullptr;        // [3 * SMALL_ONE_MAX]: multipliers, rest_e of even / odd batches

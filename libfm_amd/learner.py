@@ -200,6 +200,13 @@ class FMLearnSGD:
         """fm_learn::predict_case over the data set (fm_learn.h:63-65)."""
         return self._h.predict(self._slot(data), data.num_cases)
 
+    def recommend(self, queries, candidates, topk, exclude=None):
+        """the topk best candidate rows for every query row under the current parameters (fmx_topk): score(q, c) is the raw
+        prediction of the joined row queries[q] ++ candidates[c], without ever writing it out.  Returns (idx uint32
+        [queries, topk], score float64 [queries, topk]), padded with (capi.TOPK_NONE, -inf).  exclude: per query, the candidate
+        rows it must not get back (a list of iterables, or a CSR (ptr, idx))."""
+        return self._h.topk(self._slot(queries), self._slot(candidates), topk, 0, queries.num_cases, exclude)
+
     # fm_learn_sgd::predict (fm_learn_sgd.h:76-90)
     def predict(self, data):
         p = self.predict_raw(data)
@@ -312,6 +319,21 @@ class FMLearnALS:
         h.als_end()
         self.fm.w0, self.fm.w, self.fm.v = h.get_params(self.fm.w, self.fm.v)
 
+    TOPK_SLOTS = (2, 3)             # learn() keeps train and test in slots 0 and 1
+
+    def recommend(self, queries, candidates, topk, exclude=None):
+        """as FMLearnSGD.recommend, with the parameters of the last sweep; queries and candidates go into slots 2 and 3"""
+        if len(self._shards) > 1:
+            raise NotImplementedError("recommend: top-K retrieval is not supported on feature shards (devices lists %d GPUs)"
+                                      % len(self._shards))
+        qs, cs = self.TOPK_SLOTS
+        queries.upload(self._h, qs)
+        if candidates is queries:
+            cs = qs
+        else:
+            candidates.upload(self._h, cs)
+        return self._h.topk(qs, cs, topk, 0, queries.num_cases, exclude)
+
     # fm_learn_mcmc::predict (fm_learn_mcmc.h:380-404)
     def predict(self, data):
         out = self.pred_sum_all / self.num_iter if self.do_sample else self.pred_this.copy()
@@ -336,6 +358,10 @@ class FMLearnMCMC(FMLearnALS):
     (:985-1017), w_mu (:941-983), v_lambda (:1061-1097), v_mu (:1019-1059), from statistics reduced on the device
     (fmx_als_moments).  Hyper-priors alpha_0 = gamma_0 = beta_0 = 1, mu_0 = 0 (:1106-1109).  Random numbers come
     from numpy / a counter hash, not libc rand(): parity with the reference is statistical."""
+
+    def recommend(self, queries, candidates, topk, exclude=None):
+        raise NotImplementedError("recommend: the MCMC prediction is the average over the draws (pred_sum_all / num_iter); "
+                                  "no single parameter set scores it")
 
     def __init__(self):
         super().__init__()
