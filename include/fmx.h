@@ -534,6 +534,58 @@ typedef struct fmx_topk_stats {
 int fmx_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk_opts *opts,
              uint32_t *idx_out, double *score_out, fmx_topk_stats *stats);
 
+/* ---- BPR on query x candidate interactions, negatives drawn on the device ---------------------
+ * The training counterpart of fmx_topk: query rows (users) in one slot, candidate rows (items) in another, T observed interactions
+ * (q[t], c[t]) and n_neg >= 1 negatives per interaction.  The pairs of one epoch are p = t * n_neg + s (t = 0 .. T-1,
+ * s = 0 .. n_neg-1, in that order):
+ *   row a_p = x_{q[t]} ++ x_{c[t]}        (query entries first, then candidate entries: fmx_topk's join)
+ *   row b_p = x_{q[t]} ++ x_{neg[p]}
+ * and one epoch is exactly fmx_pair_epoch on those joined rows with the pairs (a_p, b_p), in the same two modes, without the joined
+ * rows being written: w0 only decays; each distinct feature of the pair (the query's included: linear gradient x - x = 0, the regw
+ * term stays) is updated once with one regularisation term; repeated ids count separately; all sums come from the start of the
+ * pair (SEQUENTIAL) or of the batch (MINIBATCH); no float atomics, two runs are bit-identical.
+ *
+ * The sampler is a pure function (libfm_amd.ranking.sample_negatives restates it on the CPU).  With mix64 = the splitmix64
+ * finaliser (x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31), all arithmetic mod 2^64
+ * and C = the candidate rows:
+ *   draw(seed, epoch, p, a) = ( mix64( seed ^ (epoch * 0x9E3779B97F4A7C15)
+ *                                      ^ (p * 0xD6E8FEB86659FD93 + a * 0xA24BAED4963EE407 + 0x9FB21C651E98DF25) ) * C ) >> 64
+ *   neg[p] = draw(seed, epoch, p, a*),  a* = the first attempt a in 0 .. FMX_NEG_ATTEMPTS-1 whose draw is neither c[t] nor in the
+ *   exclusion list of q[t]; when all attempts are rejected the last draw is used as it is and the pair is counted as `forced`.
+ *
+ * fmx_upload_interactions : the interactions live on query_slot and name cand_slot (the two may be equal).  exclude_ptr: NULL, or
+ *                    host [Q + 1] offsets into exclude_idx over ALL Q rows of the query slot: candidate rows that must not be
+ *                    drawn for that query, in any order, repeats allowed (sorted on upload).  An index outside its slot fails with
+ *                    FMX_E_ARG and changes nothing.  A new call replaces the interactions; fmx_upload_rows / fmx_free_rows (and
+ *                    the other uploads) on EITHER slot drop them.
+ * fmx_pair_sample  : the sampler alone: neg_out[n * n_neg] and the forced count of (seed, epoch).
+ * fmx_pair_epoch_sampled : one epoch with the negatives of (seed, epoch).  fmx_epoch_stats: rows = n * n_neg, batches, batch_used
+ *                    and device_seconds as fmx_pair_epoch; setup_seconds = everything that is not the sums / apply launches
+ *                    (sampling, key expansion, sort).  *forced_out = the forced count.
+ * fmx_pair_evaluate_sampled : accuracy and loss over the pairs of (seed, epoch), fixed-order reduction as fmx_pair_evaluate.
+ * FMX_E_UNSUPPORTED: FMX_SGD_HOGWILD, a feature shard or communicator rank, kept `-relation` blocks on either slot, more than
+ * 2^31 - 1 expanded entries (MINIBATCH) or 2^31 - 2 pairs.  FMX_E_STATE: no interactions, an open ALS / MCMC session on either
+ * slot, an open SGDA session.  FMX_E_ARG: n_neg = 0, flags != 0, NULL opts, an empty candidate slot with n > 0.
+ * Device memory: 20 bytes per pair + 40 bytes per expanded entry (an entry of x_q, x_c+ or x_c-; the query's once) + the radix
+ * sort's temporary, kept between epochs; never anything of size Q x C.
+ * Added without an ABI version change: a caller detects the feature by the symbol fmx_pair_epoch_sampled. */
+#define FMX_NEG_ATTEMPTS 16u
+typedef struct fmx_pairneg_opts {
+  int32_t  mode;            /* FMX_SGD_SEQUENTIAL or FMX_SGD_MINIBATCH */
+  uint32_t batch;           /* MINIBATCH: pairs per batch; 0 = FMX_PAIR_DEFAULT_BATCH */
+  uint32_t n_neg;           /* negatives per interaction, >= 1 */
+  uint32_t flags;           /* none defined yet: 0 */
+  uint64_t seed;
+  uint64_t epoch;           /* caller-supplied counter: the same (seed, epoch) gives the same negatives */
+} fmx_pairneg_opts;
+int fmx_upload_interactions(fmx_handle h, int query_slot, int cand_slot, const uint32_t *q_row, const uint32_t *c_row, uint64_t n,
+                            const uint64_t *exclude_ptr, const uint32_t *exclude_idx);
+/* the interactions of query_slot: their candidate slot and their number n (either output may be NULL); FMX_E_STATE without any */
+int fmx_interactions_info(fmx_handle h, int query_slot, int *cand_slot, uint64_t *n);
+int fmx_pair_sample(fmx_handle h, int query_slot, const fmx_pairneg_opts *o, uint32_t *neg_out, uint64_t *forced_out);
+int fmx_pair_epoch_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts *o, fmx_epoch_stats *stats, uint64_t *forced_out);
+int fmx_pair_evaluate_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts *o, fmx_pair_eval *out);
+
 /* ---- minibatch step split at the exchange point, for one-process-per-GPU drivers --------------
  * partial: floats per batch = fmx_partial_floats(h, batch): [batch][KP] partial factor sums followed by
  *          [batch] scalars (linear term - 0.5*sum of squares).  d_partial is DEVICE memory, 16-byte aligned.

@@ -91,6 +91,14 @@ class PairEval(C.Structure):
 PAIR_DEFAULT_BATCH = 1024   # FMX_PAIR_DEFAULT_BATCH: fmx_pair_opts::batch = 0
 
 
+class PairNegOpts(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("batch", C.c_uint32), ("n_neg", C.c_uint32), ("flags", C.c_uint32),
+                ("seed", C.c_uint64), ("epoch", C.c_uint64)]
+
+
+NEG_ATTEMPTS = 16           # FMX_NEG_ATTEMPTS: draws per negative before one is forced
+
+
 class TopkOpts(C.Structure):
     _fields_ = [("topk", C.c_uint32), ("flags", C.c_uint32), ("query_row0", C.c_uint64), ("n_query", C.c_uint32),
                 ("reserved", C.c_uint32), ("exclude_ptr", C.c_void_p), ("exclude_idx", C.c_void_p)]
@@ -208,6 +216,11 @@ SYMBOLS = [
     ("fmx_pair_epoch", C.c_int, [H, C.c_int, C.POINTER(PairOpts), C.POINTER(EpochStats)]),
     ("fmx_pair_evaluate", C.c_int, [H, C.c_int, C.POINTER(PairEval)]),
     ("fmx_topk", C.c_int, [H, C.c_int, C.c_int, C.POINTER(TopkOpts), C.c_void_p, C.c_void_p, C.POINTER(TopkStats)]),
+    ("fmx_upload_interactions", C.c_int, [H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("fmx_interactions_info", C.c_int, [H, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    ("fmx_pair_sample", C.c_int, [H, C.c_int, C.POINTER(PairNegOpts), C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("fmx_pair_epoch_sampled", C.c_int, [H, C.c_int, C.POINTER(PairNegOpts), C.POINTER(EpochStats), C.POINTER(C.c_uint64)]),
+    ("fmx_pair_evaluate_sampled", C.c_int, [H, C.c_int, C.POINTER(PairNegOpts), C.POINTER(PairEval)]),
     ("fmx_get_info", C.c_int, [H, C.POINTER(Info)]),
     ("fmx_synchronize", C.c_int, [H]),
 ]
@@ -453,6 +466,62 @@ class Handle:
         """pair accuracy (y_a > y_b) and mean -ln sigmoid(y_a - y_b) over the slot's pairs (fmx_pair_evaluate)"""
         ev = PairEval()
         self._chk(self.lib.fmx_pair_evaluate(self.h, slot, C.byref(ev)))
+        return ev
+
+    # BPR on query x candidate interactions, negatives drawn on the device ---------------------
+    def upload_interactions(self, query_slot, cand_slot, q_row, c_row, exclude=None):
+        """the observed (query row, candidate row) interactions of query_slot against cand_slot; replaces earlier ones.
+        exclude: None, or (ptr [Q + 1], idx) -- a CSR over ALL query rows of candidate rows never drawn as negatives -- or a
+        list of Q iterables; any order, repeats allowed."""
+        q_row = np.ascontiguousarray(q_row, dtype=np.uint32)
+        c_row = np.ascontiguousarray(c_row, dtype=np.uint32)
+        if q_row.shape != c_row.shape or q_row.ndim != 1:
+            raise ValueError("upload_interactions: q_row and c_row must be 1-d arrays of one length")
+        ex_ptr = ex_idx = None
+        if exclude is not None:
+            if isinstance(exclude, tuple) and len(exclude) == 2:
+                ex_ptr = np.ascontiguousarray(exclude[0], dtype=np.uint64)
+                ex_idx = np.ascontiguousarray(exclude[1], dtype=np.uint32)
+            else:
+                lists = [np.asarray(list(e), dtype=np.uint32) for e in exclude]
+                ex_ptr = np.zeros(len(lists) + 1, dtype=np.uint64)
+                ex_ptr[1:] = np.cumsum([len(e) for e in lists])
+                ex_idx = np.concatenate(lists).astype(np.uint32) if lists else np.zeros(0, dtype=np.uint32)
+            n_rows = C.c_uint32(0)
+            self._chk(self.lib.fmx_rows_info(self.h, query_slot, C.byref(n_rows), None))
+            if len(ex_ptr) != n_rows.value + 1:
+                raise ValueError("upload_interactions: exclude_ptr must hold one offset per query row + 1 = %d" % (n_rows.value + 1))
+        self._chk(self.lib.fmx_upload_interactions(self.h, query_slot, cand_slot, _ptr(q_row) if len(q_row) else None,
+                                                   _ptr(c_row) if len(c_row) else None, len(q_row), _ptr(ex_ptr),
+                                                   _ptr(ex_idx) if ex_idx is not None and len(ex_idx) else None))
+
+    def interactions_info(self, query_slot):
+        """(candidate slot, number of interactions) of the interactions that live on query_slot (fmx_interactions_info)"""
+        cand, n = C.c_int(0), C.c_uint64(0)
+        self._chk(self.lib.fmx_interactions_info(self.h, query_slot, C.byref(cand), C.byref(n)))
+        return cand.value, int(n.value)
+
+    def pair_sample(self, query_slot, n_neg=1, seed=0, epoch=0):
+        """the negatives fmx_pair_epoch_sampled trains on for (seed, epoch): (neg uint32 [n * n_neg], forced) (fmx_pair_sample)"""
+        opts = PairNegOpts(SGD_SEQUENTIAL, 0, int(n_neg), 0, int(seed), int(epoch))
+        neg = np.zeros(self.interactions_info(query_slot)[1] * max(int(n_neg), 0), dtype=np.uint32)
+        forced = C.c_uint64(0)
+        self._chk(self.lib.fmx_pair_sample(self.h, query_slot, C.byref(opts), _ptr(neg) if len(neg) else None, C.byref(forced)))
+        return neg, int(forced.value)
+
+    def pair_epoch_sampled(self, query_slot, mode=SGD_SEQUENTIAL, batch=0, n_neg=1, seed=0, epoch=0, flags=0):
+        """one epoch over the interactions with the negatives of (seed, epoch) (fmx_pair_epoch_sampled): (EpochStats, forced)"""
+        opts = PairNegOpts(int(mode), int(batch), int(n_neg), int(flags), int(seed), int(epoch))
+        st = EpochStats()
+        forced = C.c_uint64(0)
+        self._chk(self.lib.fmx_pair_epoch_sampled(self.h, query_slot, C.byref(opts), C.byref(st), C.byref(forced)))
+        return st, int(forced.value)
+
+    def pair_evaluate_sampled(self, query_slot, n_neg=1, seed=0, epoch=0):
+        """pair accuracy and mean -ln sigmoid(y_a - y_b) over the pairs of (seed, epoch) (fmx_pair_evaluate_sampled)"""
+        opts = PairNegOpts(SGD_SEQUENTIAL, 0, int(n_neg), 0, int(seed), int(epoch))
+        ev = PairEval()
+        self._chk(self.lib.fmx_pair_evaluate_sampled(self.h, query_slot, C.byref(opts), C.byref(ev)))
         return ev
 
     # top-K retrieval -------------------------------------------------------------------------

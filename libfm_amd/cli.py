@@ -16,7 +16,11 @@ accepted and ignored (everything is resident).
 GPU-only additions: -gpu_mode sequential|minibatch|hogwild (default minibatch), -batch, -w0_chunk, -device.
 Top-K retrieval after training (every method but mcmc): -topk K -candidates F [-queries F] [-exclude F] [-topk_out F] ranks the
 candidate rows for every query row (default: the test rows) by the raw prediction of the joined row (fmx_topk).
+Implicit feedback: -method bpr -train Q -test Qtest -candidates C -interactions F [-test_interactions F] [-neg N] trains on the
+observed (query row of -train, candidate row) interactions of F with N negatives per interaction drawn on the device
+(fmx_pair_epoch_sampled); the test interactions name rows of -test.  -train_pairs / -test_pairs are not needed then.
 """
+import os
 import sys
 import time
 
@@ -38,7 +42,10 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "w0_chunk": "", "device": "",
          "train_pairs": "bpr: pairs of the train rows, one per line 'row_a row_b' (0-based rows; row_a is preferred) [MANDATORY for bpr]",
          "test_pairs": "bpr: pairs of the test rows, same format [MANDATORY for bpr]",
-         "candidates": "top-K retrieval after training: filename of the candidate rows (libFM text or binary)",
+         "candidates": "top-K retrieval after training, bpr with -interactions: filename of the candidate rows (libFM text or binary)",
+         "interactions": "bpr: observed interactions, one per line 'query_row cand_row' (0-based rows of -train and -candidates)",
+         "test_interactions": "bpr with -interactions: held-out interactions, same format (rows of -test and -candidates)",
+         "neg": "bpr with -interactions: negatives drawn per interaction; default=1",
          "topk": "results per query row (1 .. 1024); needs -candidates; not with -method mcmc",
          "topk_out": "filename for the top-K lists: one line per query, 'cand:score cand:score ...'",
          "queries": "filename of the query rows; default: the test rows",
@@ -84,6 +91,25 @@ def read_exclude(path, n_query, n_cand):
     ptr = np.zeros(n_query + 1, dtype=np.uint64)
     ptr[1:] = np.cumsum(np.bincount(q, minlength=n_query))
     return ptr, np.array(c, dtype=np.uint32)[order]
+
+
+def read_interactions(path, n_query, n_cand):
+    """an -interactions file: one interaction per line, 'query_row cand_row' (0-based; the format of -exclude), in file order;
+    returns (q_row, c_row)"""
+    q, c = [], []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            t = line.split()
+            if not t or t[0].startswith("#"):
+                continue
+            if len(t) != 2:
+                raise ValueError("cannot parse line %d of %s: want 'query_row cand_row'" % (no, path))
+            qr, cr = int(t[0]), int(t[1])
+            if not (0 <= qr < n_query and 0 <= cr < n_cand):
+                raise ValueError("line %d of %s: row outside the query (%d) or candidate (%d) rows" % (no, path, n_query, n_cand))
+            q.append(qr)
+            c.append(cr)
+    return np.array(q, dtype=np.uint32), np.array(c, dtype=np.uint32)
 
 
 def write_topk(path, idx, score):
@@ -147,7 +173,12 @@ def _main(argv):
         return 0
     if method not in ("sgd", "sgda", "als", "mcmc", "bpr"):
         raise ValueError("unknown method")
-    want_topk = any(f in a for f in ("topk", "candidates", "topk_out", "queries", "exclude"))
+    implicit = method == "bpr" and "interactions" in a
+    if not implicit and any(f in a for f in ("interactions", "test_interactions", "neg")):
+        raise ValueError("-interactions, -test_interactions and -neg belong to -method bpr with -interactions")
+    want_topk = any(f in a for f in ("topk", "topk_out", "queries", "exclude")) or ("candidates" in a and not implicit)
+    if implicit and "candidates" not in a:
+        raise ValueError("-interactions needs -candidates")
     if want_topk:
         if method == "mcmc":
             raise ValueError("-topk is not supported with -method mcmc: its prediction averages the draws, no single model scores it")
@@ -156,7 +187,7 @@ def _main(argv):
     if method == "bpr":                      # pairwise ranking: the targets are not used, so -task is optional
         a.setdefault("task", "r")
         for need in ("train_pairs", "test_pairs"):
-            if need not in a:
+            if need not in a and not implicit:
                 raise ValueError("-%s is mandatory for -method bpr" % need)
     for need in ("task", "train", "test"):
         if need not in a:
@@ -178,8 +209,16 @@ def _main(argv):
         print("Loading validation set...\t")
         validation = L.Data(*D.load(a["validation"]))
 
+    cand = None
+    if implicit:                             # the candidate rows are training data here: their features are model features
+        print("Loading candidates...\t")
+        cand = L.Data(*D.load(a["candidates"]))
+        print("num_rows=%d\tnum_values=%d\tnum_features=%d" % (cand.num_cases, len(cand.entries), cand.num_feature))
+
     fm = L.FMModel()
     fm.num_attribute = max(train.num_feature, test.num_feature)                      # libfm.cpp:203-206
+    if cand is not None:
+        fm.num_attribute = max(fm.num_attribute, cand.num_feature)
     if validation is not None:
         fm.num_attribute = max(fm.num_attribute, validation.num_feature)
     # (1.2) relations (libfm.cpp:172-196): block attributes follow the main attributes (:213-216)
@@ -287,7 +326,19 @@ def _main(argv):
     l.min_target, l.max_target = min_t, max_t
     l.device = int(a.get("device", "-1"))
     l.init()
-    if method == "bpr":
+    if implicit:
+        print("Loading interactions...\t")
+        inter = read_interactions(a["interactions"], train.num_cases, cand.num_cases)
+        test_inter = read_interactions(a["test_interactions"], test.num_cases, cand.num_cases) if a.get("test_interactions") else None
+        n_neg = int(a.get("neg", "1"))
+        if n_neg < 1:
+            raise ValueError("-neg needs at least 1")
+        print("interactions=%d\ttest_interactions=%d\tneg=%d" % (len(inter[0]), 0 if test_inter is None else len(test_inter[0]), n_neg))
+        # -train and -test naming one file are the same query rows: a query's train interactions are then excluded from the test
+        # pairs' negatives too (learn_implicit keeps the test interactions on a copy of the rows)
+        same_rows = os.path.realpath(a["train"]) == os.path.realpath(a["test"])
+        l.learn_implicit(train, cand, inter, test_inter, n_neg=n_neg, seed=seed, test_queries=None if same_rows else test)
+    elif method == "bpr":
         print("Loading pairs...\t")
         train_pairs = read_pairs(a["train_pairs"], train.num_cases)
         test_pairs = read_pairs(a["test_pairs"], test.num_cases)
@@ -295,7 +346,10 @@ def _main(argv):
         l.learn(train, train_pairs, test, test_pairs)
     else:
         l.learn(train, test)
-    if method == "bpr":
+    if implicit:
+        e_tr, e_te = l.evaluate_implicit()
+        print("Final\tTrain=%g\tTest=%g" % (e_tr.accuracy, e_te.accuracy if e_te is not None else float("nan")))
+    elif method == "bpr":
         print("Final\tTrain=%g\tTest=%g" % (l.evaluate_pairs(train), l.evaluate_pairs(test)))
     if method in ("sgd", "sgda"):
         print("Final\tTrain=%g\tTest=%g" % (l.evaluate(train), l.evaluate(test)))   # libfm.cpp:418-420
@@ -314,7 +368,8 @@ def _main(argv):
         fm.save_model(a["save_model"])
     if want_topk:
         topk = int(a["topk"])
-        cand = L.Data(*D.load(a["candidates"]))
+        if cand is None:
+            cand = L.Data(*D.load(a["candidates"]))
         queries = L.Data(*D.load(a["queries"])) if a.get("queries") else test
         exclude = read_exclude(a["exclude"], queries.num_cases, cand.num_cases) if a.get("exclude") else None
         idx, score = l.recommend(queries, cand, topk, exclude)

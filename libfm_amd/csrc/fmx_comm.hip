@@ -603,6 +603,7 @@ int fmx_group_upload_rows(fmx_group g, int slot, const void* entries, const uint
     cur = h;
     hipSetDevice(h->device);
     hipStreamSynchronize(h->stream);
+    drop_interactions(h, slot);
     free_slot(h->slots[slot]);
     Slot s;
     uint32_t* cnt = nullptr; void* tmp = nullptr;

@@ -130,6 +130,7 @@ void free_slot(Slot& s) {
   s.blocks.clear();
   free_segments(s);
   free_pairs(s);
+  free_interactions(s);
   if (s.ent) fmx_dev_free(s.ent);
   if (s.row_ptr) fmx_dev_free(s.row_ptr);
   if (s.target) fmx_dev_free(s.target);
@@ -1224,6 +1225,7 @@ int fmx_free_rows(fmx_handle h, int slot) {
   { int _rc = slot_in_session(h, slot, "fmx_free_rows"); if (_rc) return _rc; }
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  drop_interactions(h, slot);
   free_slot(h->slots[slot]);
   return FMX_OK;
 }
@@ -1237,6 +1239,7 @@ int fmx_upload_rows(fmx_handle h, int slot, const void* entries, const uint64_t*
   if (row_ptr[0] != 0 || row_ptr[n_rows] != nnz) return fail(h, FMX_E_ARG, "row_ptr[0] must be 0 and row_ptr[n_rows] == nnz");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  drop_interactions(h, slot);
   free_slot(h->slots[slot]);
   const Entry* src = static_cast<const Entry*>(entries);
   const uint64_t n = h->cfg.num_attribute;
@@ -1432,6 +1435,7 @@ int fmx_upload_block_rows_ex(fmx_handle h, int slot, const void* entries, const 
   }
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  drop_interactions(h, slot);
   free_slot(h->slots[slot]);
   std::vector<void*> tmp;                                     // staging buffers, freed on every exit path
   auto up = [&](const void* p, size_t bytes) -> void* {
@@ -1536,6 +1540,7 @@ int fmx_synth_rows_ex(fmx_handle h, int slot, uint64_t seed, uint64_t row0, uint
   if (fs == 0) return fail(h, FMX_E_ARG, "fmx_synth_rows: num_attribute < nnz");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  drop_interactions(h, slot);
   free_slot(h->slots[slot]);
   const Shard sh = make_shard(h->cfg);
   Slot s;

@@ -79,8 +79,12 @@ struct Slot {
   uint32_t* pair_seg_feat = nullptr; // [pair_nseg]
   uint32_t  pair_nseg = 0, pair_max_seg = 0;
   std::vector<uint32_t> pair_batch_seg;   // [n_batches + 1] first segment of every batch
+  // interactions (fmx_upload_interactions, fmx_pairneg.hip): this slot's rows are the queries, another slot's the candidates
+  struct PairNeg* pneg = nullptr;
 };
 void free_pairs(Slot& s);                                                // fmx_pair.hip
+void free_interactions(Slot& s);                                         // fmx_pairneg.hip
+void drop_interactions(fmx_handle h, int slot);                          // fmx_pairneg.hip: those that live on `slot` or name it as their candidate slot
 
 // one `-relation` block kept apart from the main rows (fmx_upload_block_rows_ex, FMX_BLOCKS_KEEP): RelationData +
 // RelationJoin, src/libfm/src/relation.h:32-60

@@ -192,8 +192,8 @@ int fmx_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts* opts, fmx_epoch_
     PairEnt* gbuf = nullptr;
     if (!use_lds) HIPCHK(h, fmx_dev_alloc(&gbuf, (size_t)s.pair_max_len * sizeof(PairEnt)));
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(k_pair_seq, dim3(1), dim3(PAIR_SEQ_THREADS), 0, h->stream, s.ent, s.row_ptr, s.pair_a, s.pair_b, P, h->tb, hy, k,
-                       h->w0, gbuf, (uint32_t)(use_lds ? 1u : 0u));
+    hipLaunchKernelGGL(k_pair_seq<PairSlotSrc>, dim3(1), dim3(PAIR_SEQ_THREADS), 0, h->stream, PairSlotSrc{s.ent, s.row_ptr, s.pair_a, s.pair_b}, P,
+                       h->tb, hy, k, h->w0, gbuf, (uint32_t)(use_lds ? 1u : 0u));
     hipError_t le = hipGetLastError();
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     hipError_t se = hipStreamSynchronize(h->stream);

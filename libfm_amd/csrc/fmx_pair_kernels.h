@@ -36,9 +36,23 @@ constexpr int      PAIR_MAX_K = 1024;
 __device__ __forceinline__ double pair_loss(double d) { return d >= 0.0 ? log1p(exp(-d)) : -d + log1p(exp(d)); }
 __device__ __forceinline__ double pair_mult(double d) { return -(1.0 - 1.0 / (1.0 + exp(-d))); }   // util.h:52
 
+// where the sequential kernel takes a pair's rows from: Rows = what is read once per pair, at(r, i) = entry i of x_a ++ x_b
+struct PairSlotSrc {                          // rows pa[t], pb[t] of one slot
+  const Entry* ent; const uint64_t* row_ptr; const uint32_t* pa; const uint32_t* pb;
+  struct Rows { uint64_t a0, b0; uint32_t ma, m; };
+  __device__ __forceinline__ Rows rows(uint64_t t) const {
+    const uint32_t ra = pa[t], rb = pb[t];
+    Rows r;
+    r.a0 = row_ptr[ra]; r.b0 = row_ptr[rb];
+    r.ma = (uint32_t)(row_ptr[ra + 1] - r.a0); r.m = r.ma + (uint32_t)(row_ptr[rb + 1] - r.b0);
+    return r;
+  }
+  __device__ __forceinline__ Entry at(const Rows& r, uint32_t i) const { return (i < r.ma) ? ent[r.a0 + i] : ent[r.b0 + (i - r.ma)]; }
+};
+
+template <class Src>
 __global__ void __launch_bounds__(PAIR_SEQ_THREADS)
-k_pair_seq(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, const uint32_t* __restrict__ pa,
-           const uint32_t* __restrict__ pb, uint64_t n_pairs, const Tab tb, Hyper h, int k, double* w0_ptr, PairEnt* gbuf, uint32_t use_lds) {
+k_pair_seq(const Src src, uint64_t n_pairs, const Tab tb, Hyper h, int k, double* w0_ptr, PairEnt* gbuf, uint32_t use_lds) {
   __shared__ PairEnt lbuf[PAIR_SEQ_LDS_ENT];
   __shared__ double s_a[PAIR_MAX_K], s_b[PAIR_MAX_K];
   __shared__ double red[PAIR_SEQ_THREADS / 64];
@@ -46,11 +60,10 @@ k_pair_seq(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, 
   const uint32_t tid = threadIdx.x;
   double w0 = (h.k0 && tid == 0) ? *w0_ptr : 0.0;
   for (uint64_t t = 0; t < n_pairs; t++) {
-    const uint32_t ra = pa[t], rb = pb[t];
-    const uint64_t a0 = row_ptr[ra], b0 = row_ptr[rb];
-    const uint32_t ma = (uint32_t)(row_ptr[ra + 1] - a0), m = ma + (uint32_t)(row_ptr[rb + 1] - b0);
+    const typename Src::Rows pr = src.rows(t);
+    const uint32_t ma = pr.ma, m = pr.m;
     for (uint32_t i = tid; i < m; i += PAIR_SEQ_THREADS) {
-      const Entry e = (i < ma) ? ent[a0 + i] : ent[b0 + (i - ma)];
+      const Entry e = src.at(pr, i);
       E[i].id = e.id; E[i].x = e.value;
     }
     __syncthreads();
@@ -202,6 +215,28 @@ __device__ __forceinline__ double pair_side(const Entry* __restrict__ ent, uint6
   return wave_sum_d(lin - 0.5 * sq + 0.5 * s2);
 }
 
+// the factor sums of one row alone (what pair_side leaves in sum[], without its scalar)
+template <int KP>
+__device__ __forceinline__ void pair_row_sums(const Entry* __restrict__ ent, uint64_t a, uint32_t m, const Tab& tb, int k, double (&sum)[Map<KP>::VEC]) {
+  constexpr int VEC = Map<KP>::VEC, LPR = Map<KP>::LPR, EPI = Map<KP>::EPI;
+  const uint32_t lane = threadIdx.x & 63u, g = lane / LPR, f = lane % LPR;
+#pragma unroll
+  for (int v = 0; v < VEC; v++) sum[v] = 0.0;
+  for (uint32_t i = g; i < m; i += EPI) {
+    const Entry e = ent[a + i];
+    const double x = (double)e.value;
+    const float* row = tb.V + (size_t)e.id * tb.rs;
+#pragma unroll
+    for (int v = 0; v < VEC; v++) {
+      const int ff = (int)(f * VEC + v);
+      sum[v] += (ff < k) ? (double)row[ff] * x : 0.0;
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < VEC; v++)
+    for (int o = LPR; o < 64; o <<= 1) sum[v] += __shfl_xor(sum[v], o);
+}
+
 // S: [nb][2][KP] floats (x_a's sums, then x_b's), mult: [nb] doubles
 template <int KP>
 __global__ void __launch_bounds__(256)
@@ -231,11 +266,16 @@ k_pair_sums(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr,
 
 // owner apply: segment s = every entry of one feature j in one batch, in pair order.  Per pair the gradient of its entries, then
 // acc += mult_t * grad_t + reg * theta_j(start) (one regularisation term per distinct pair); theta_j -= lr * acc.
-template <int KP>
+// ROWS = sums rows per pair in S and tags an entry can carry: 2 = {x_a, x_b} (payload pair << 1 | tag); 3 adds tag 2, an entry that
+// is in BOTH rows (fmx_pairneg_kernels.h: the query's entries, once): S row 2 holds S_a - S_b, so it adds S[2][f] x to gv and
+// nothing to gw -- the two sides' x and v x x terms cancel (payload pair << 2 | tag).
+template <int KP, int ROWS = 2>
 __global__ void __launch_bounds__(256)
 k_pair_apply(const TEntry* __restrict__ tent, const uint32_t* __restrict__ seg_head, const uint32_t* __restrict__ seg_feat,
              uint32_t s0, uint32_t s1, const float* __restrict__ S, const double* __restrict__ mult, const Tab tb, Hyper h, int k) {
   constexpr int VEC = Map<KP>::VEC, LPR = Map<KP>::LPR;
+  constexpr uint32_t TAG_BITS = ROWS == 2 ? 1u : 2u, TAG_MASK = (1u << TAG_BITS) - 1u;
+  static_assert(ROWS == 2 || ROWS == 3, "tags: x_a, x_b and optionally both");
   const uint32_t lane = threadIdx.x & 63u;
   const bool act = lane < (uint32_t)LPR;
   const uint32_t wave0 = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -252,10 +292,10 @@ k_pair_apply(const TEntry* __restrict__ tent, const uint32_t* __restrict__ seg_h
     }
     const double w0j = h.k1 ? (double)tb.w[(size_t)j * tb.ws] : 0.0;
     double gw = 0.0, aw = 0.0;
-    uint32_t cur = tent[a].e >> 1;
+    uint32_t cur = tent[a].e >> TAG_BITS;
     for (uint32_t i = a; i < b; i++) {
       const TEntry te = tent[i];
-      const uint32_t t = te.e >> 1, side = te.e & 1u;
+      const uint32_t t = te.e >> TAG_BITS, side = te.e & TAG_MASK;
       if (t != cur) {                                        // the previous pair's gradient is complete
         const double mt = mult[cur];
         aw += mt * gw + h.regw_d * w0j;
@@ -264,14 +304,15 @@ k_pair_apply(const TEntry* __restrict__ tent, const uint32_t* __restrict__ seg_h
         gw = 0.0; cur = t;
       }
       const double x = (double)te.x;
-      gw = side ? gw - x : gw + x;
-      const float* Sr = S + ((size_t)t * 2 + side) * KP;
+      if (ROWS == 2 || side < 2u) gw = side ? gw - x : gw + x;
+      const float* Sr = S + ((size_t)t * ROWS + side) * KP;
+      const double xs = (ROWS == 3 && side == 2u) ? 0.0 : x;   // (v x x as (v x) x, the order it always had)
 #pragma unroll
       for (int v = 0; v < VEC; v++) {
         const int ff = (int)(lane * VEC + v);
         const double sf = (act && ff < k) ? (double)Sr[ff] : 0.0;
-        const double gr = sf * x - v0[v] * x * x;
-        gv[v] = side ? gv[v] - gr : gv[v] + gr;
+        const double gr = sf * x - v0[v] * x * xs;
+        gv[v] = (side == 1u) ? gv[v] - gr : gv[v] + gr;
       }
     }
     {

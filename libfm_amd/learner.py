@@ -472,6 +472,87 @@ class FMLearnPairSGD(FMLearnSGD):
                              "loss_test": te.loss, "time_learn": stats.device_seconds})
         self.sync_model()
 
+    # implicit feedback: interactions over query rows x candidate rows, negatives drawn on the device ----------------------
+    EVAL_EPOCH = 1 << 32          # the ONE sampler epoch both evaluations use (no training epoch reaches it)
+
+    @staticmethod
+    def _interactions(x, what):
+        if isinstance(x, tuple) and len(x) == 2:
+            q, c = x
+        else:
+            x = np.asarray(x)
+            if x.ndim != 2 or x.shape[1] != 2:
+                raise ValueError("%s: want (q_row, c_row) or an [n, 2] array" % what)
+            q, c = x[:, 0], x[:, 1]
+        q, c = np.ascontiguousarray(q, dtype=np.uint32), np.ascontiguousarray(c, dtype=np.uint32)
+        if q.shape != c.shape or q.ndim != 1:
+            raise ValueError("%s: q_row and c_row must be 1-d arrays of one length" % what)
+        return q, c
+
+    @staticmethod
+    def _positives_csr(n_query, *inter):
+        """per query row, the candidate rows of its interactions: the CSR (ptr [n_query + 1], idx)"""
+        q = np.concatenate([i[0] for i in inter]).astype(np.int64)
+        c = np.concatenate([i[1] for i in inter]).astype(np.uint32)
+        if len(q) and int(q.max()) >= n_query:
+            raise ValueError("an interaction names query row %d of %d" % (int(q.max()), n_query))
+        ptr = np.zeros(n_query + 1, dtype=np.uint64)
+        ptr[1:] = np.cumsum(np.bincount(q, minlength=n_query))
+        return ptr, c[np.argsort(q, kind="stable")]
+
+    def evaluate_implicit(self):
+        """(train, test) pair metrics (capi.PairEval: accuracy, loss) of the interactions of the last learn_implicit under the
+        current parameters, on the fixed evaluation epoch; test is None without test interactions"""
+        sq, se, n_neg, seed = self._implicit
+        h = self._h
+        return (h.pair_evaluate_sampled(sq, n_neg, seed, self.EVAL_EPOCH),
+                h.pair_evaluate_sampled(se, n_neg, seed, self.EVAL_EPOCH) if se is not None else None)
+
+    def learn_implicit(self, queries, candidates, interactions, test_interactions=None, n_neg=1, seed=0, exclude="positives",
+                       test_queries=None):
+        """BPR on observed (query row, candidate row) interactions (fmx_pair_epoch_sampled): every interaction is paired with
+        n_neg candidate rows drawn on the device, epoch i with the negatives of (seed, i); the joined rows queries[q] ++
+        candidates[c] are never written.  interactions / test_interactions: (q_row, c_row) or an [n, 2] array; the test
+        interactions name rows of test_queries (default: of queries).  exclude: what a query never gets as a negative --
+        "positives" (its own interactions; for the test pairs the train and test interactions together, when both name rows of
+        queries), None, a CSR (ptr, idx) over the query rows or a list of iterables.  The #Iter= lines come from
+        fmx_pair_evaluate_sampled on one fixed epoch number, so the curve compares like with like; recommend() works on the
+        trained model."""
+        if self.mode not in self.MODES:
+            raise ValueError("unknown mode for pairwise SGD: %s (sequential | minibatch)" % self.mode)
+        print("learnrate=%g" % self.learn_rate, file=self.out)
+        print("#iterations=%d" % self.num_iter, file=self.out)
+        h = self._h
+        tr = self._interactions(interactions, "interactions")
+        te = None if test_interactions is None else self._interactions(test_interactions, "test_interactions")
+        sq, sc = self._slot(queries), self._slot(candidates)
+        ex_tr = self._positives_csr(queries.num_cases, tr) if isinstance(exclude, str) and exclude == "positives" else exclude
+        h.upload_interactions(sq, sc, tr[0], tr[1], ex_tr)
+        se = None
+        if te is not None:
+            if test_queries is None or test_queries is queries:   # a slot holds ONE set of interactions: the test set's live on a copy of the rows
+                if not hasattr(self, "_query_copy") or self._query_copy[0] is not queries:
+                    self._query_copy = (queries, Data(queries.entries, queries.row_ptr, queries.target))
+                tq, both = self._query_copy[1], (tr, te)
+            else:
+                tq, both = test_queries, (te,)
+            se = self._slot(tq)
+            ex_te = self._positives_csr(tq.num_cases, *both) if isinstance(exclude, str) and exclude == "positives" else exclude
+            if isinstance(ex_te, tuple) and len(ex_te) == 2 and len(ex_te[0]) != tq.num_cases + 1:
+                raise ValueError("learn_implicit: the exclusion CSR covers %d query rows, test_queries has %d (pass queries of one "
+                                 "row count, or exclude='positives')" % (len(ex_te[0]) - 1, tq.num_cases))
+            h.upload_interactions(se, sc, te[0], te[1], ex_te)
+        self._implicit = (sq, se, n_neg, seed)
+        for i in range(self.num_iter):
+            stats, forced = h.pair_epoch_sampled(sq, self.MODES[self.mode], self.batch, n_neg, seed, i)
+            e_tr, e_te = self.evaluate_implicit()
+            acc_te, loss_te = (e_te.accuracy, e_te.loss) if e_te is not None else (float("nan"), float("nan"))
+            print("#Iter=%3d\tTrain=%g\tTest=%g" % (i, e_tr.accuracy, acc_te), file=self.out)
+            print("#Iter=%3d\tloss: Train=%g\tTest=%g" % (i, e_tr.loss, loss_te), file=sys.stderr)
+            self.log.append({"accuracy_train": e_tr.accuracy, "accuracy_test": acc_te, "loss_train": e_tr.loss, "loss_test": loss_te,
+                             "time_learn": stats.device_seconds, "time_setup": stats.setup_seconds, "forced": forced})
+        self.sync_model()
+
 
 class FMLearnSGDA(FMLearnSGD):
     """fm_learn_sgd_element_adapt_reg (`-method sgda`, fm_learn_sgd_element_adapt_reg.h:44-93) on the GPU: theta steps
