@@ -553,6 +553,20 @@ int fmx_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk_opts *o
  *   neg[p] = draw(seed, epoch, p, a*),  a* = the first attempt a in 0 .. FMX_NEG_ATTEMPTS-1 whose draw is neither c[t] nor in the
  *   exclusion list of q[t]; when all attempts are rejected the last draw is used as it is and the pair is counted as `forced`.
  *
+ * Hardest of M: flags = FMX_NEG_HARDEST | FMX_NEG_DRAWS(M), M = 1 .. FMX_NEG_ATTEMPTS.  An attempt is
+ * ACCEPTED when its draw is neither c[t] nor in the exclusion list of q[t].  The attempts a = 0 .. FMX_NEG_ATTEMPTS-1 are walked in
+ * order and the walk stops after the M-th accepted one; neg[p] is the accepted draw d with the highest
+ *   r(q, d) = b_d + sum_f S_q[f] S_d[f]
+ * (fmx_topk's decomposition score(q, c) = a_q + b_c + <S_q, S_c> without a_q, which all draws of a pair share; S and b in fp32 from
+ * the same kernels as fmx_topk, k0 = 0).  A later draw replaces the current best only when its r is strictly greater -- equal
+ * scores keep the earlier attempt -- or when the best's r is NaN and its own is not.  Fewer than M accepted: the pick is among
+ * those; none accepted: the last draw as it is and the pair is `forced`, as above.  The same candidate drawn twice is harmless.
+ * M = 1 is the uniform sampler, integer for integer.  S and b are taken from the parameters AS THEY ARE WHEN THE CALL STARTS: the
+ * negatives of an epoch are fixed before its first pair in both modes, so fmx_pair_sample with the same options and unchanged
+ * parameters returns exactly what fmx_pair_epoch_sampled trains on (and fmx_pair_evaluate_sampled evaluates).
+ * FMX_NEG_DRAWS without FMX_NEG_HARDEST, M = 0, M > FMX_NEG_ATTEMPTS and every other bit (bit 0 included) are FMX_E_ARG.
+ * libfm_amd.ranking.sample_negatives(..., draws=M, query_sums, cand_sums, cand_scal) restates the rule in float64.
+ *
  * fmx_upload_interactions : the interactions live on query_slot and name cand_slot (the two may be equal).  exclude_ptr: NULL, or
  *                    host [Q + 1] offsets into exclude_idx over ALL Q rows of the query slot: candidate rows that must not be
  *                    drawn for that query, in any order, repeats allowed (sorted on upload).  An index outside its slot fails with
@@ -565,16 +579,21 @@ int fmx_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk_opts *o
  * fmx_pair_evaluate_sampled : accuracy and loss over the pairs of (seed, epoch), fixed-order reduction as fmx_pair_evaluate.
  * FMX_E_UNSUPPORTED: FMX_SGD_HOGWILD, a feature shard or communicator rank, kept `-relation` blocks on either slot, more than
  * 2^31 - 1 expanded entries (MINIBATCH) or 2^31 - 2 pairs.  FMX_E_STATE: no interactions, an open ALS / MCMC session on either
- * slot, an open SGDA session.  FMX_E_ARG: n_neg = 0, flags != 0, NULL opts, an empty candidate slot with n > 0.
+ * slot, an open SGDA session.  FMX_E_ARG: n_neg = 0, flags other than the two below, NULL opts, an empty candidate slot with n > 0.
  * Device memory: 20 bytes per pair + 40 bytes per expanded entry (an entry of x_q, x_c+ or x_c-; the query's once) + the radix
- * sort's temporary, kept between epochs; never anything of size Q x C.
- * Added without an ABI version change: a caller detects the feature by the symbol fmx_pair_epoch_sampled. */
+ * sort's temporary, and with FMX_NEG_HARDEST and M > 1 the two row tables, (Q + C)(KM + 1) * 4 bytes (KM = the factors padded to
+ * a power of two, at least 16; C alone when the query slot is the candidate slot) + at most 64 MiB of raw sums; all kept between
+ * epochs; never anything of size Q x C.
+ * Added without an ABI version change: a caller detects the feature by the symbol fmx_pair_epoch_sampled, hardest-of-M by the
+ * macro FMX_NEG_HARDEST (the struct keeps its layout). */
 #define FMX_NEG_ATTEMPTS 16u
+#define FMX_NEG_HARDEST   2u                          /* pick the best-scoring of several accepted draws */
+#define FMX_NEG_DRAWS(M)  ((uint32_t)(M) << 8)        /* M = 1 .. FMX_NEG_ATTEMPTS, bits 8..15 */
 typedef struct fmx_pairneg_opts {
   int32_t  mode;            /* FMX_SGD_SEQUENTIAL or FMX_SGD_MINIBATCH */
   uint32_t batch;           /* MINIBATCH: pairs per batch; 0 = FMX_PAIR_DEFAULT_BATCH */
   uint32_t n_neg;           /* negatives per interaction, >= 1 */
-  uint32_t flags;           /* none defined yet: 0 */
+  uint32_t flags;           /* 0, or FMX_NEG_HARDEST | FMX_NEG_DRAWS(M) */
   uint64_t seed;
   uint64_t epoch;           /* caller-supplied counter: the same (seed, epoch) gives the same negatives */
 } fmx_pairneg_opts;

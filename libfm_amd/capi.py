@@ -97,6 +97,13 @@ class PairNegOpts(C.Structure):
 
 
 NEG_ATTEMPTS = 16           # FMX_NEG_ATTEMPTS: draws per negative before one is forced
+NEG_HARDEST = 2             # FMX_NEG_HARDEST: the best-scoring of the first M accepted draws (FMX_NEG_DRAWS(M) = M << 8)
+
+
+def neg_flags(draws):
+    """fmx_pairneg_opts::flags of `draws` accepted draws per negative: 1 = the uniform sampler (0), M > 1 = hardest of M"""
+    draws = int(draws)
+    return 0 if draws == 1 else NEG_HARDEST | (draws << 8)
 
 
 class TopkOpts(C.Structure):
@@ -501,25 +508,27 @@ class Handle:
         self._chk(self.lib.fmx_interactions_info(self.h, query_slot, C.byref(cand), C.byref(n)))
         return cand.value, int(n.value)
 
-    def pair_sample(self, query_slot, n_neg=1, seed=0, epoch=0):
-        """the negatives fmx_pair_epoch_sampled trains on for (seed, epoch): (neg uint32 [n * n_neg], forced) (fmx_pair_sample)"""
-        opts = PairNegOpts(SGD_SEQUENTIAL, 0, int(n_neg), 0, int(seed), int(epoch))
+    def pair_sample(self, query_slot, n_neg=1, seed=0, epoch=0, draws=1):
+        """the negatives fmx_pair_epoch_sampled trains on for (seed, epoch): (neg uint32 [n * n_neg], forced) (fmx_pair_sample);
+        draws = M > 1: the hardest of M accepted draws under the current parameters"""
+        opts = PairNegOpts(SGD_SEQUENTIAL, 0, int(n_neg), neg_flags(draws), int(seed), int(epoch))
         neg = np.zeros(self.interactions_info(query_slot)[1] * max(int(n_neg), 0), dtype=np.uint32)
         forced = C.c_uint64(0)
         self._chk(self.lib.fmx_pair_sample(self.h, query_slot, C.byref(opts), _ptr(neg) if len(neg) else None, C.byref(forced)))
         return neg, int(forced.value)
 
-    def pair_epoch_sampled(self, query_slot, mode=SGD_SEQUENTIAL, batch=0, n_neg=1, seed=0, epoch=0, flags=0):
-        """one epoch over the interactions with the negatives of (seed, epoch) (fmx_pair_epoch_sampled): (EpochStats, forced)"""
-        opts = PairNegOpts(int(mode), int(batch), int(n_neg), int(flags), int(seed), int(epoch))
+    def pair_epoch_sampled(self, query_slot, mode=SGD_SEQUENTIAL, batch=0, n_neg=1, seed=0, epoch=0, flags=0, draws=1):
+        """one epoch over the interactions with the negatives of (seed, epoch) (fmx_pair_epoch_sampled): (EpochStats, forced);
+        draws = M > 1: hardest of M, scored with the parameters at the start of the epoch (OR-ed into flags)"""
+        opts = PairNegOpts(int(mode), int(batch), int(n_neg), int(flags) | neg_flags(draws), int(seed), int(epoch))
         st = EpochStats()
         forced = C.c_uint64(0)
         self._chk(self.lib.fmx_pair_epoch_sampled(self.h, query_slot, C.byref(opts), C.byref(st), C.byref(forced)))
         return st, int(forced.value)
 
-    def pair_evaluate_sampled(self, query_slot, n_neg=1, seed=0, epoch=0):
+    def pair_evaluate_sampled(self, query_slot, n_neg=1, seed=0, epoch=0, draws=1):
         """pair accuracy and mean -ln sigmoid(y_a - y_b) over the pairs of (seed, epoch) (fmx_pair_evaluate_sampled)"""
-        opts = PairNegOpts(SGD_SEQUENTIAL, 0, int(n_neg), 0, int(seed), int(epoch))
+        opts = PairNegOpts(SGD_SEQUENTIAL, 0, int(n_neg), neg_flags(draws), int(seed), int(epoch))
         ev = PairEval()
         self._chk(self.lib.fmx_pair_evaluate_sampled(self.h, query_slot, C.byref(opts), C.byref(ev)))
         return ev

@@ -19,6 +19,8 @@ candidate rows for every query row (default: the test rows) by the raw predictio
 Implicit feedback: -method bpr -train Q -test Qtest -candidates C -interactions F [-test_interactions F] [-neg N] trains on the
 observed (query row of -train, candidate row) interactions of F with N negatives per interaction drawn on the device
 (fmx_pair_epoch_sampled); the test interactions name rows of -test.  -train_pairs / -test_pairs are not needed then.
+-neg_draws M (1 .. 16, default 1) trains every negative as the hardest of M accepted draws under the parameters at the start of
+the epoch; the #Iter= lines stay on uniform negatives.
 """
 import os
 import sys
@@ -46,6 +48,7 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "interactions": "bpr: observed interactions, one per line 'query_row cand_row' (0-based rows of -train and -candidates)",
          "test_interactions": "bpr with -interactions: held-out interactions, same format (rows of -test and -candidates)",
          "neg": "bpr with -interactions: negatives drawn per interaction; default=1",
+         "neg_draws": "bpr with -interactions: train each negative as the best-scoring of M accepted draws (1 .. 16); default=1 (uniform)",
          "topk": "results per query row (1 .. 1024); needs -candidates; not with -method mcmc",
          "topk_out": "filename for the top-K lists: one line per query, 'cand:score cand:score ...'",
          "queries": "filename of the query rows; default: the test rows",
@@ -174,8 +177,8 @@ def _main(argv):
     if method not in ("sgd", "sgda", "als", "mcmc", "bpr"):
         raise ValueError("unknown method")
     implicit = method == "bpr" and "interactions" in a
-    if not implicit and any(f in a for f in ("interactions", "test_interactions", "neg")):
-        raise ValueError("-interactions, -test_interactions and -neg belong to -method bpr with -interactions")
+    if not implicit and any(f in a for f in ("interactions", "test_interactions", "neg", "neg_draws")):
+        raise ValueError("-interactions, -test_interactions, -neg and -neg_draws belong to -method bpr with -interactions")
     want_topk = any(f in a for f in ("topk", "topk_out", "queries", "exclude")) or ("candidates" in a and not implicit)
     if implicit and "candidates" not in a:
         raise ValueError("-interactions needs -candidates")
@@ -333,11 +336,16 @@ def _main(argv):
         n_neg = int(a.get("neg", "1"))
         if n_neg < 1:
             raise ValueError("-neg needs at least 1")
-        print("interactions=%d\ttest_interactions=%d\tneg=%d" % (len(inter[0]), 0 if test_inter is None else len(test_inter[0]), n_neg))
+        neg_draws = int(a.get("neg_draws", "1"))
+        if not 1 <= neg_draws <= 16:
+            raise ValueError("-neg_draws needs 1 .. 16")
+        print("interactions=%d\ttest_interactions=%d\tneg=%d\tneg_draws=%d" %
+              (len(inter[0]), 0 if test_inter is None else len(test_inter[0]), n_neg, neg_draws))
         # -train and -test naming one file are the same query rows: a query's train interactions are then excluded from the test
         # pairs' negatives too (learn_implicit keeps the test interactions on a copy of the rows)
         same_rows = os.path.realpath(a["train"]) == os.path.realpath(a["test"])
-        l.learn_implicit(train, cand, inter, test_inter, n_neg=n_neg, seed=seed, test_queries=None if same_rows else test)
+        l.learn_implicit(train, cand, inter, test_inter, n_neg=n_neg, seed=seed, test_queries=None if same_rows else test,
+                         neg_draws=neg_draws)
     elif method == "bpr":
         print("Loading pairs...\t")
         train_pairs = read_pairs(a["train_pairs"], train.num_cases)

@@ -265,6 +265,9 @@ void resolve_batch(const fmx_config& cfg, double coll_mass, uint32_t requested, 
 constexpr uint32_t FMX_DEFAULT_BATCH = 262144u;                          // fmx_sgd_opts::batch = 0, before the stability cut
 int sgd_resolve_batch(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, fmx_batch_info* bi);   // fmx_sgd.hip: + the shards' shares
 int sgd_partial_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n_rows, float* S, float* c, hipStream_t st);   // fmx_sgd.hip
+constexpr size_t PREP_RAW_FLOATS = size_t(1) << 24;                      // prep_rows: raw partial sums of one piece of rows (64 MiB)
+int prep_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, int k0, float* raw, size_t raw_rows, int KM,
+              float* S_out, float* scal, hipStream_t st);                // fmx_topk.hip: the [rows][KM] factor sums and scalars of section 11
 int lag_flush(fmx_handle h);                                             // fmx_sgd.hip
 int scan_error_check(fmx_handle h);                                      // fmx_sgd.hip: the device's error word after k_scan_pit launches (streams drained)
 uint32_t multi_group_size(const Slot& s, int KP);                        // fmx_sgd.hip: examples per wavefront of the short-row kernels (0: rows are long)

@@ -1,5 +1,5 @@
 // fmx_pairneg.hip -- C-ABI (include/fmx.h): BPR on (query row, candidate row) interactions with the negatives drawn on the device
-// (DESIGN.md section 12).  Per epoch: k_neg_sample, then FMX_SGD_SEQUENTIAL (k_pair_seq over the joined rows) or FMX_SGD_MINIBATCH
+// (DESIGN.md sections 12 and 13).  Per epoch: k_neg_sample (FMX_NEG_HARDEST: the row tables of fmx_topk, then k_neg_pick), then FMX_SGD_SEQUENTIAL (k_pair_seq over the joined rows) or FMX_SGD_MINIBATCH
 // (the pairs' entries -- the query's once -- bucketed by (batch, feature), sums + multipliers, owner apply).  Kernels:
 // fmx_pairneg_kernels.h.
 #include "fmx_internal.h"
@@ -7,9 +7,10 @@
 
 static_assert(FMX_NEG_ATTEMPTS == NEG_ATTEMPTS, "include/fmx.h and fmx_pairneg_kernels.h disagree");
 
-// the interactions of a query slot.  The two scratch blocks are kept between epochs (grown, never shrunk): by_pairs holds what is
+// the interactions of a query slot.  The three scratch blocks are kept between epochs (grown, never shrunk): by_pairs holds what is
 // sized by the pairs P = n * n_neg (20 P bytes + the scan's temporary), by_entries what is sized by the expanded entries
-// N = sum over the pairs of |x_q| + |x_c+| + |x_c-| (40 N bytes + the sort's temporary); nothing is sized by Q x C.
+// N = sum over the pairs of |x_q| + |x_c+| + |x_c-| (40 N bytes + the sort's temporary), by_rows (FMX_NEG_HARDEST only) the factor
+// sums of the Q query and C candidate rows, (Q + C)(KM + 1) * 4 bytes + one piece of raw sums; nothing is sized by Q x C.
 struct PairNeg {
   int       cand = -1;
   uint64_t  n = 0;
@@ -19,12 +20,14 @@ struct PairNeg {
   uint32_t* ex_idx = nullptr;
   char*     by_pairs = nullptr;   size_t by_pairs_bytes = 0;
   char*     by_entries = nullptr; size_t by_entries_bytes = 0;
+  char*     by_rows = nullptr;    size_t by_rows_bytes = 0;
 };
 
 extern "C++" void free_interactions(Slot& s) {
   PairNeg* pn = s.pneg;
   if (!pn) return;
-  for (void* p : {(void*)pn->q, (void*)pn->c, (void*)pn->ex_ptr, (void*)pn->ex_idx, (void*)pn->by_pairs, (void*)pn->by_entries})
+  for (void* p : {(void*)pn->q, (void*)pn->c, (void*)pn->ex_ptr, (void*)pn->ex_idx, (void*)pn->by_pairs, (void*)pn->by_entries,
+                  (void*)pn->by_rows})
     if (p) fmx_dev_free(p);
   delete pn;
   s.pneg = nullptr;
@@ -55,11 +58,19 @@ struct SetupClock {                                           // host seconds in
   ~SetupClock() { h->setup_acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
+uint32_t neg_draws(const fmx_pairneg_opts* o) { return (o->flags >> 8) & 0xFFu; }
+// (one draw is the uniform sampler itself: k_neg_sample, no tables)
+bool neg_hardest(const fmx_pairneg_opts* o) { return (o->flags & FMX_NEG_HARDEST) && neg_draws(o) > 1; }
+
 // what every entry point that uses the interactions refuses (the handle stays usable)
 int pairneg_check(fmx_handle h, int slot, const fmx_pairneg_opts* o, const char* what) {
   if (!h) return FMX_E_ARG;
   if (!o) return fail(h, FMX_E_ARG, "%s: opts is NULL", what);
-  if (o->flags != 0) return fail(h, FMX_E_ARG, "%s: unknown flags 0x%x", what, o->flags);
+  if (o->flags & ~(FMX_NEG_HARDEST | FMX_NEG_DRAWS(0xFFu))) return fail(h, FMX_E_ARG, "%s: unknown flags 0x%x", what, o->flags);
+  const uint32_t draws = neg_draws(o);
+  if (!(o->flags & FMX_NEG_HARDEST) && draws) return fail(h, FMX_E_ARG, "%s: FMX_NEG_DRAWS without FMX_NEG_HARDEST", what);
+  if ((o->flags & FMX_NEG_HARDEST) && (draws == 0 || draws > FMX_NEG_ATTEMPTS))
+    return fail(h, FMX_E_ARG, "%s: FMX_NEG_HARDEST with %u draws (1 .. %u)", what, draws, FMX_NEG_ATTEMPTS);
   if (o->n_neg == 0) return fail(h, FMX_E_ARG, "%s: n_neg = 0 (at least one negative per interaction)", what);
   if (o->mode == FMX_SGD_HOGWILD) return fail(h, FMX_E_UNSUPPORTED, "%s: FMX_SGD_HOGWILD is not supported for pairs", what);
   if (o->mode != FMX_SGD_SEQUENTIAL && o->mode != FMX_SGD_MINIBATCH) return fail(h, FMX_E_ARG, "%s: unknown mode %d", what, o->mode);
@@ -91,6 +102,8 @@ JoinSrc join_src(const Slot& qs, const Slot& cs, const PairNeg& pn, const uint32
 
 // the negatives of (seed, epoch) into by_pairs: neg [P] at offset 0; the forced count comes back in *forced.  Layout of by_pairs:
 // neg [P] u32 | off [P + 1] u64 | len [P] u64 | forced partials | forced sum | scan temporary
+// FMX_NEG_HARDEST with more than one draw: the tables S_q [Q][KM], S_c [C][KM], b_c [C] of the parameters as they are NOW
+// (prep_rows, k0 = 0) into by_rows -- once when the query slot is the candidate slot -- and k_neg_pick instead of k_neg_sample.
 struct PairsLayout { size_t o_neg, o_off, o_len, o_part, o_sum, o_tmp, tmp_bytes, bytes; };
 int pairs_layout(fmx_handle h, uint64_t P, PairsLayout* L) {
   size_t tmp = 0;
@@ -99,24 +112,65 @@ int pairs_layout(fmx_handle h, uint64_t P, PairsLayout* L) {
   L->o_neg = off; off += al256(P * 4);
   L->o_off = off; off += al256((P + 1) * 8);
   L->o_len = off; off += al256((P + 1) * 8);
-  L->o_part = off; off += al256(NEG_MAX_BLOCKS * 4);
+  L->o_part = off; off += al256(std::max(NEG_MAX_BLOCKS, 4 * NEG_PICK_MAX_BLOCKS) * 4);
   L->o_sum = off; off += 256;
   L->o_tmp = off; L->tmp_bytes = std::max<size_t>(tmp, 256); off += al256(L->tmp_bytes);
   L->bytes = off;
   return FMX_OK;
 }
 
-int sample(fmx_handle h, const Slot& cs, PairNeg& pn, const fmx_pairneg_opts* o, const PairsLayout& L, uint64_t* forced) {
+int hard_tables(fmx_handle h, const Slot& qs, const Slot& cs, PairNeg& pn, int KM, NegTabs* out) {
+  const bool same = &qs == &cs;
+  const size_t Q = same ? 0 : qs.n_rows, NC = cs.n_rows;
+  const size_t raw_rows = std::min<size_t>(std::max<size_t>(std::max(Q, NC), 1), std::max<size_t>(1, PREP_RAW_FLOATS / (size_t)(h->KP + 1)));
+  size_t off = 0;
+  const size_t o_sc = off; off += al256(NC * KM * sizeof(float));
+  const size_t o_bc = off; off += al256(NC * sizeof(float));
+  const size_t o_sq = off; off += al256(Q * KM * sizeof(float));
+  const size_t o_aq = off; off += al256(Q * sizeof(float));
+  const size_t o_raw = off; off += al256(raw_rows * (size_t)(h->KP + 1) * sizeof(float));
+  HIPCHK(h, grow(&pn.by_rows, &pn.by_rows_bytes, off));
+  char* sc = pn.by_rows;
+  float* raw = (float*)(sc + o_raw);
+  int rc = prep_rows(h, cs, 0, (uint32_t)NC, 0, raw, raw_rows, KM, (float*)(sc + o_sc), (float*)(sc + o_bc), h->stream);
+  if (rc) return rc;
+  if (!same) {
+    rc = prep_rows(h, qs, 0, (uint32_t)Q, 0, raw, raw_rows, KM, (float*)(sc + o_sq), (float*)(sc + o_aq), h->stream);
+    if (rc) return rc;
+  }
+  out->Sc = (const float*)(sc + o_sc);
+  out->bc = (const float*)(sc + o_bc);
+  out->Sq = same ? out->Sc : (const float*)(sc + o_sq);
+  return FMX_OK;
+}
+
+int sample(fmx_handle h, const Slot& qs, const Slot& cs, PairNeg& pn, const fmx_pairneg_opts* o, const PairsLayout& L, uint64_t* forced) {
   const uint64_t P = pn.n * o->n_neg;
   hipStream_t st = h->stream;
   HIPCHK(h, grow(&pn.by_pairs, &pn.by_pairs_bytes, L.bytes));
   uint32_t* neg = (uint32_t*)(pn.by_pairs + L.o_neg);
   uint32_t* part = (uint32_t*)(pn.by_pairs + L.o_part);
   uint64_t* sum = (uint64_t*)(pn.by_pairs + L.o_sum);
-  const uint32_t nblk = (uint32_t)std::min<uint64_t>((P + 255) / 256, NEG_MAX_BLOCKS);
   const NegSrc in{pn.q, pn.c, pn.ex_ptr, pn.ex_idx, pn.n, cs.n_rows};
-  hipLaunchKernelGGL(k_neg_sample, dim3(nblk), dim3(256), 0, st, in, o->n_neg, o->seed, o->epoch, neg, part);
-  hipLaunchKernelGGL(k_neg_forced_sum, dim3(1), dim3(64), 0, st, (const uint32_t*)part, nblk, sum);
+  uint32_t nparts = 0;
+  if (neg_hardest(o)) {
+    const int KM = std::max(h->KP, 16);
+    NegTabs tabs;
+    int rc = hard_tables(h, qs, cs, pn, KM, &tabs);
+    if (rc) return rc;
+    const uint32_t nblk = (uint32_t)std::min<uint64_t>((P + 3) / 4, NEG_PICK_MAX_BLOCKS);
+    nparts = 4 * nblk;
+    switch (KM) {
+#define PICK_CASE(KMV) case KMV: hipLaunchKernelGGL((k_neg_pick<KMV>), dim3(nblk), dim3(256), 0, st, in, tabs, o->n_neg, neg_draws(o), o->seed, o->epoch, neg, part); break;
+      PICK_CASE(16) PICK_CASE(32) PICK_CASE(64) PICK_CASE(128) PICK_CASE(256) PICK_CASE(512) PICK_CASE(1024)
+#undef PICK_CASE
+      default: return fail(h, FMX_E_UNSUPPORTED, "num_factor > 1024 is not supported");
+    }
+  } else {
+    nparts = (uint32_t)std::min<uint64_t>((P + 255) / 256, NEG_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_neg_sample, dim3(nparts), dim3(256), 0, st, in, o->n_neg, o->seed, o->epoch, neg, part);
+  }
+  hipLaunchKernelGGL(k_neg_forced_sum, dim3(1), dim3(64), 0, st, (const uint32_t*)part, nparts, sum);
   HIPCHK(h, hipGetLastError());
   if (forced) {
     HIPCHK(h, hipMemcpyAsync(forced, sum, 8, hipMemcpyDeviceToHost, st));
@@ -289,7 +343,8 @@ int fmx_pair_sample(fmx_handle h, int query_slot, const fmx_pairneg_opts* o, uin
   rc = pairs_layout(h, P, &L);
   if (rc) return rc;
   uint64_t forced = 0;
-  rc = sample(h, h->slots[pn.cand], pn, o, L, &forced);
+  if (neg_hardest(o)) { int _rc = lag_flush(h); if (_rc) return _rc; }   // (the scores read the parameters)
+  rc = sample(h, h->slots[query_slot], h->slots[pn.cand], pn, o, L, &forced);
   if (rc) return rc;
   HIPCHK(h, hipMemcpy(neg_out, pn.by_pairs + L.o_neg, P * 4, hipMemcpyDeviceToHost));
   if (forced_out) *forced_out = forced;
@@ -326,7 +381,7 @@ int fmx_pair_epoch_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts*
     SetupClock clk{h, std::chrono::steady_clock::now()};
     rc = pairs_layout(h, P, &L);
     if (rc) return rc;
-    rc = sample(h, cs, pn, o, L, &forced);
+    rc = sample(h, qs, cs, pn, o, L, &forced);
     if (rc) return rc;
   }
   const JoinSrc js = join_src(qs, cs, pn, (const uint32_t*)(pn.by_pairs + L.o_neg), o->n_neg);
@@ -421,7 +476,7 @@ int fmx_pair_evaluate_sampled(fmx_handle h, int query_slot, const fmx_pairneg_op
   PairsLayout L;
   rc = pairs_layout(h, P, &L);
   if (rc) return rc;
-  rc = sample(h, cs, pn, o, L, nullptr);
+  rc = sample(h, qs, cs, pn, o, L, nullptr);
   if (rc) return rc;
   const JoinSrc js = join_src(qs, cs, pn, (const uint32_t*)(pn.by_pairs + L.o_neg), o->n_neg);
   const uint32_t nblk = (uint32_t)std::min<uint64_t>((P + 3) / 4, PAIR_EVAL_BLOCKS);

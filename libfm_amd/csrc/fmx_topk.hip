@@ -8,7 +8,6 @@
 namespace {
 
 constexpr size_t TOPK_LIST_BYTES = size_t(1) << 30;     // per query chunk: both halves of the split lists
-constexpr size_t TOPK_RAW_FLOATS = size_t(1) << 24;     // raw partial sums of one piece of rows (64 MiB)
 
 struct DevBufs {                                        // the call's device scratch, freed on every return
   std::vector<void*> p;
@@ -28,7 +27,10 @@ size_t score_lds_bytes(int buf) {
   return (size_t)(TOPK_QB + 4) * buf * sizeof(TopkEnt) + TOPK_QB * sizeof(TopkEnt) + (3 * TOPK_QB + 4) * sizeof(uint32_t);
 }
 
-// factor sums of rows [row0, row0 + n) of a slot -> S_out [n][KM] (zero-padded), scal[n] = (k0 w0) + c + 1/2 |S|^2
+}  // namespace
+
+// factor sums of rows [row0, row0 + n) of a slot -> S_out [n][KM] (zero-padded), scal[n] = (k0 w0) + c + 1/2 |S|^2; raw: scratch of
+// raw_rows * (KP + 1) floats (fmx_internal.h: shared with the hardest-of-M sampler of fmx_pairneg.hip)
 int prep_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, int k0, float* raw, size_t raw_rows, int KM,
               float* S_out, float* scal, hipStream_t st) {
   const int KP = h->KP;
@@ -44,8 +46,6 @@ int prep_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, int k0, fl
   }
   return FMX_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -131,7 +131,7 @@ int fmx_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk_opts* o
   uint32_t *lens = nullptr, *d_idx = nullptr;
   uint64_t* d_ex_ptr = nullptr;
   uint32_t* d_ex_idx = nullptr;
-  const size_t raw_rows = std::max<size_t>(TOPK_QB, TOPK_RAW_FLOATS / (size_t)(KP + 1));
+  const size_t raw_rows = std::max<size_t>(TOPK_QB, PREP_RAW_FLOATS / (size_t)(KP + 1));
   HIPCHK(h, db.alloc(&Sc, (size_t)C_pad * KM * sizeof(float)));
   HIPCHK(h, db.alloc(&bc, (size_t)C_pad * sizeof(float)));
   HIPCHK(h, db.alloc(&Sq, (size_t)nq_pad * KM * sizeof(float)));

@@ -509,15 +509,19 @@ class FMLearnPairSGD(FMLearnSGD):
                 h.pair_evaluate_sampled(se, n_neg, seed, self.EVAL_EPOCH) if se is not None else None)
 
     def learn_implicit(self, queries, candidates, interactions, test_interactions=None, n_neg=1, seed=0, exclude="positives",
-                       test_queries=None):
+                       test_queries=None, neg_draws=1):
         """BPR on observed (query row, candidate row) interactions (fmx_pair_epoch_sampled): every interaction is paired with
         n_neg candidate rows drawn on the device, epoch i with the negatives of (seed, i); the joined rows queries[q] ++
         candidates[c] are never written.  interactions / test_interactions: (q_row, c_row) or an [n, 2] array; the test
         interactions name rows of test_queries (default: of queries).  exclude: what a query never gets as a negative --
         "positives" (its own interactions; for the test pairs the train and test interactions together, when both name rows of
-        queries), None, a CSR (ptr, idx) over the query rows or a list of iterables.  The #Iter= lines come from
-        fmx_pair_evaluate_sampled on one fixed epoch number, so the curve compares like with like; recommend() works on the
-        trained model."""
+        queries), None, a CSR (ptr, idx) over the query rows or a list of iterables.  neg_draws = M > 1: every training negative
+        is the hardest of M accepted draws under the parameters at the start of its epoch (FMX_NEG_HARDEST).  The #Iter= lines
+        come from fmx_pair_evaluate_sampled on one fixed epoch number and on UNIFORM negatives whatever neg_draws is, so the curves
+        of different samplers measure the same thing; recommend() works on the trained model."""
+        neg_draws = int(neg_draws)
+        if not 1 <= neg_draws <= capi.NEG_ATTEMPTS:
+            raise ValueError("neg_draws must be in 1 .. %d" % capi.NEG_ATTEMPTS)
         if self.mode not in self.MODES:
             raise ValueError("unknown mode for pairwise SGD: %s (sequential | minibatch)" % self.mode)
         print("learnrate=%g" % self.learn_rate, file=self.out)
@@ -544,13 +548,14 @@ class FMLearnPairSGD(FMLearnSGD):
             h.upload_interactions(se, sc, te[0], te[1], ex_te)
         self._implicit = (sq, se, n_neg, seed)
         for i in range(self.num_iter):
-            stats, forced = h.pair_epoch_sampled(sq, self.MODES[self.mode], self.batch, n_neg, seed, i)
+            stats, forced = h.pair_epoch_sampled(sq, self.MODES[self.mode], self.batch, n_neg, seed, i, draws=neg_draws)
             e_tr, e_te = self.evaluate_implicit()
             acc_te, loss_te = (e_te.accuracy, e_te.loss) if e_te is not None else (float("nan"), float("nan"))
             print("#Iter=%3d\tTrain=%g\tTest=%g" % (i, e_tr.accuracy, acc_te), file=self.out)
             print("#Iter=%3d\tloss: Train=%g\tTest=%g" % (i, e_tr.loss, loss_te), file=sys.stderr)
             self.log.append({"accuracy_train": e_tr.accuracy, "accuracy_test": acc_te, "loss_train": e_tr.loss, "loss_test": loss_te,
-                             "time_learn": stats.device_seconds, "time_setup": stats.setup_seconds, "forced": forced})
+                             "time_learn": stats.device_seconds, "time_setup": stats.setup_seconds, "forced": forced,
+                             "neg_draws": neg_draws})
         self.sync_model()
 
 
