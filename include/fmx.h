@@ -228,7 +228,7 @@ typedef struct fmx_epoch_stats {
 #define FMX_STAT_HANDOFF_TIMEOUT 64u /* a device-side hand-off wait ran into its bound all the same: the examples concerned took NO step
                                       (multiplier 0; a recurrence that never saw its batch handed the bias on unchanged), every parameter is a
                                       valid number, the call returns FMX_E_HIP with this status set, and the handle orders by events from now on */
-/* (ABI 9) which kernels FMX_SGD_SEQUENTIAL ran (libfm_amd/csrc/fmx_seq_kernels.h, fmx_kernels.h) -- the same trajectory in every form; for
+/* (ABI 9) which kernels FMX_SGD_SEQUENTIAL ran (libfm_amd/csrc/fmx_seq_kernels.h, fmx_online_kernels.h) -- the same trajectory in every form; for
    tests and diagnosis.  The environment of fmx_create picks among them: FMX_SEQ_ROWS=0, FMX_SEQ_WG=0, FMX_SEQ_RUNS_FUSED=0, FMX_SEQ_RUNS_ONE=0;
    FMX_SEQ_RUNS (0: never runs, 1: always) is read at every epoch: */
 #define FMX_STAT_SEQ_ENTRIES   1024u /* entry by entry on one wavefront (k_sequential): the whole slot, or a row that repeats an id inside runs */

@@ -1,4 +1,5 @@
-// fmx_internal.h -- shared by the translation units of libfmx.so (fmx_core.hip, fmx_sgd.hip, fmx_als.hip).
+// fmx_internal.h -- shared by the translation units of libfmx.so (fmx_core.hip, fmx_sgd.hip, fmx_als.hip, fmx_comm.hip, fmx_pair.hip, fmx_topk.hip,
+// fmx_pairneg.hip; fmx_io.hip needs none of it).
 // The C-ABI is include/fmx.h; nothing declared here is exported.
 #pragma once
 #pragma GCC visibility push(default)      // the C-ABI is the only thing libfmx.so exports (-fvisibility=hidden)

@@ -240,6 +240,10 @@ template <int VEC, int BIT> __device__ __forceinline__ void row_ld(const Tab& tb
 template <int VEC, int BIT> __device__ __forceinline__ void row_st(const Tab& tb, size_t id, uint32_t off, const float (&in)[VEC]) {
   if (off < tb.rs) store_row<VEC, BIT>(tb.V + id * tb.rs + off, in);
 }
+// the same mask where ONE wavefront covers a row, lane l holding elements [l * VEC, l * VEC + VEC): is this lane one of the row's?
+template <int KP> __device__ __forceinline__ bool row_lane(uint32_t lane, const Tab& tb) {
+  return lane < (uint32_t)Map<KP>::LPR && lane * Map<KP>::VEC < tb.rs;
+}
 
 // the row entries ({id, value}, 8 bytes) and the 4-byte gathers of a linear weight: plain loads.  (Non-temporal / agent-scope variants of
 // both, write-through row stores, a sixth wavefront per SIMD and the in-launch publish of S_e were measured in rounds 1-4 and lost or
@@ -260,6 +264,8 @@ __device__ __forceinline__ double ld_l2(const double* p) {
   return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 __device__ __forceinline__ float ld_l2_stream(const float* p) { return __builtin_nontemporal_load(p); }
+// the store that goes with ld_l2 in the one-wavefront online kernels (fmx_online_kernels.h)
+__device__ __forceinline__ void st_l2(float* p, float x) { __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // (words that cross dies -- the membership counters of a launch -- are read at device scope)
 __device__ __forceinline__ unsigned ld_dev(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // loss multiplier, fm_learn_sgd_element.h:58-65
@@ -270,6 +276,24 @@ __device__ __forceinline__ float multiplier(const Hyper& h, float p, float y) {
     return h.sgda ? 2.0f * (p - y) : -(y - p);
   }
   return -y * (1.0f - 1.0f / (1.0f + __expf(-y * p)));
+}
+// the multipliers of the reference's two online learners in fp64, each in the reference's own algebraic form (the kernels that restate its
+// loops entry by entry: fmx_online_kernels.h, fmx_seq_kernels.h, k_sgda_lambda)
+__device__ __forceinline__ double sgd_mult_d(const Hyper& h, double p, double y) {          // fm_learn_sgd_element.h:58-65
+  if (h.task == 0) {
+    p = fmin(h.max_d, p);
+    p = fmax(h.min_d, p);
+    return -(y - p);
+  }
+  return -y * (1.0 - 1.0 / (1.0 + exp(-y * p)));
+}
+__device__ __forceinline__ double sgda_mult_d(const Hyper& h, double p, double y) {         // fm_learn_sgd_element_adapt_reg.h:138-145 (mult), :203-210 (grad_loss)
+  if (h.task == 0) {
+    p = fmin(h.max_d, p);
+    p = fmax(h.min_d, p);
+    return 2 * (p - y);
+  }
+  return y * ((1.0 / (1.0 + exp(-y * p))) - 1.0);
 }
 
 // same multiplier with the hardware reciprocal (1 ulp) -- used on the serial w0 recurrence where the IEEE
@@ -2066,221 +2090,6 @@ k_place_probe_w(float* __restrict__ tab, uint64_t n, uint64_t total, uint64_t sa
 }
 
 // ----------------------------------------------------------------------------------------------
-// k_sequential: the reference trajectory (batch = 1, storage order) on ONE wavefront, for parity.
-// Loads bypass the per-CU L1 (agent-scope relaxed atomics -> sc1) and every row ends with a drain of
-// the store queue, so row r+1 sees row r's update exactly like fm_learn_sgd_element.h:56-67.
-// Entries are updated one at a time in row order, so a repeated id inside a row sees its own earlier
-// update (fm_sgd.h:44-50 semantics).  Sums are accumulated in fp64; parameters are stored fp32.
-// ----------------------------------------------------------------------------------------------
-template <int KP>
-__global__ void __launch_bounds__(64)
-k_sequential(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, const float* __restrict__ target,
-             uint32_t n_rows, const Tab tb, Hyper h, double* w0_ptr) {
-  constexpr int VEC = Map<KP>::VEC, LPR = Map<KP>::LPR;
-  const uint32_t lane = threadIdx.x;
-  const bool act = lane < LPR && lane * VEC < tb.rs;           // (the lanes of the row's elements: rows are tb.rs floats, row_ld above)
-  double w0 = *w0_ptr;
-  for (uint32_t r = 0; r < n_rows; r++) {
-    const uint64_t a = row_ptr[r];
-    const uint32_t size = (uint32_t)(row_ptr[r + 1] - a);
-    double sum[VEC]; double sq = 0.0, lin = 0.0;
-#pragma unroll
-    for (int v = 0; v < VEC; v++) sum[v] = 0.0;
-    for (uint32_t i = 0; i < size; i++) {
-      const Entry e = ent[a + i];
-      if (h.k1 && lane == 0)
-        lin += (double)__hip_atomic_load(tb.w + (size_t)e.id * tb.ws, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * (double)e.value;
-      if (act) {
-#pragma unroll
-        for (int v = 0; v < VEC; v++) {
-          const float vv = __hip_atomic_load(tb.V + (size_t)e.id * tb.rs + lane * VEC + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const double d = (double)vv * (double)e.value;
-          sum[v] += d;
-          sq += d * d;
-        }
-      }
-    }
-    double part = lin - 0.5 * sq;
-    if (act) {
-#pragma unroll
-      for (int v = 0; v < VEC; v++) part += 0.5 * sum[v] * sum[v];
-    }
-    double p = (h.k0 ? w0 : 0.0) + wave_sum_d(part);
-    const double y = (double)target[r];
-    double mult;
-    if (h.task == 0) {
-      p = fmin(h.max_d, p);
-      p = fmax(h.min_d, p);
-      mult = -(y - p);
-    } else {
-      mult = -y * (1.0 - 1.0 / (1.0 + exp(-y * p)));
-    }
-    if (h.k0) w0 -= h.lr_d * (mult + h.reg0_d * w0);
-    for (uint32_t i = 0; i < size; i++) {
-      const Entry e = ent[a + i];
-      const double x = (double)e.value;
-      if (h.k1 && lane == 0) {
-        const double wv = (double)__hip_atomic_load(tb.w + (size_t)e.id * tb.ws, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(tb.w + (size_t)e.id * tb.ws, (float)(wv - h.lr_d * (mult * x + h.regw_d * wv)),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (act) {
-#pragma unroll
-        for (int v = 0; v < VEC; v++) {
-          float* pv = tb.V + (size_t)e.id * tb.rs + lane * VEC + v;
-          const double vv = (double)__hip_atomic_load(pv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const double grad = sum[v] * x - vv * x * x;
-          __hip_atomic_store(pv, (float)(vv - h.lr_d * (mult * grad + h.regv_d * vv)),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      // a later entry of this row (repeated id) and the next row must observe these stores
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-  }
-  if (lane == 0) *w0_ptr = w0;
-}
-
-// ----------------------------------------------------------------------------------------------
-// k_sgda: fm_learn_sgd_element_adapt_reg (`-method sgda`, src/libfm/src/fm_learn_sgd_element_adapt_reg.h), ONE
-// wavefront, the reference's strictly online interleaving: for every train row a theta step (:136-169: like fm_SGD
-// but mult = 2(p-y), regularisation 2*reg*theta with the LEARNED reg_w / reg_v[f], and the gradient of every
-// touched parameter remembered in grad_w / grad_v), then (from the 2nd epoch on) a lambda step on the next
-// validation row (:201-248 through predict_scaled :171-199).  One attribute group.  Sums in fp64, parameters and
-// shadow gradients stored fp32.  reg: [0] = reg_w, [1+f] = reg_v[f].
-// ----------------------------------------------------------------------------------------------
-template <int KP>
-__global__ void __launch_bounds__(64)
-k_sgda(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, const float* __restrict__ target, uint32_t n_rows,
-       const Entry* __restrict__ vent, const uint64_t* __restrict__ vrow_ptr, const float* __restrict__ vtarget, uint32_t v_rows,
-       const Tab tb, float* gw, float* gv, Hyper h, double* w0_ptr, double* reg, int do_lambda) {
-  constexpr int VEC = Map<KP>::VEC, LPR = Map<KP>::LPR;
-  const uint32_t lane = threadIdx.x;
-  const bool act = lane < LPR && lane * VEC < tb.rs;           // (the lanes of the row's elements: rows are tb.rs floats, row_ld above)
-  double w0 = *w0_ptr;
-  double reg_w = reg[0];
-  double reg_v[VEC];
-#pragma unroll
-  for (int v = 0; v < VEC; v++) reg_v[v] = act ? reg[1 + lane * VEC + v] : 0.0;
-  uint32_t vpos = 0;                                                        // validation->data->begin() (:266)
-#define LD(p) ((double)__hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-#define ST(p, val) __hip_atomic_store((p), (float)(val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-  for (uint32_t r = 0; r < n_rows; r++) {
-    // ---------------- theta step (:136-169)
-    const uint64_t a = row_ptr[r];
-    const uint32_t size = (uint32_t)(row_ptr[r + 1] - a);
-    double sum[VEC]; double sq = 0.0, lin = 0.0;
-#pragma unroll
-    for (int v = 0; v < VEC; v++) sum[v] = 0.0;
-    for (uint32_t i = 0; i < size; i++) {
-      const Entry e = ent[a + i];
-      if (h.k1 && lane == 0) lin += LD(tb.w + (size_t)e.id * tb.ws) * (double)e.value;
-      if (act) {
-#pragma unroll
-        for (int v = 0; v < VEC; v++) {
-          const double d = LD(tb.V + (size_t)e.id * tb.rs + lane * VEC + v) * (double)e.value;
-          sum[v] += d; sq += d * d;
-        }
-      }
-    }
-    double part = lin - 0.5 * sq;
-    if (act) {
-#pragma unroll
-      for (int v = 0; v < VEC; v++) part += 0.5 * sum[v] * sum[v];
-    }
-    double p = (h.k0 ? w0 : 0.0) + wave_sum_d(part);
-    const double y = (double)target[r];
-    double mult;
-    if (h.task == 0) { p = fmin(h.max_d, p); p = fmax(h.min_d, p); mult = 2 * (p - y); }
-    else mult = y * ((1.0 / (1.0 + exp(-y * p))) - 1.0);
-    if (h.k0) w0 -= h.lr_d * (mult + 2 * 0.0 * w0);                          // reg_0 = 0 (:100)
-    for (uint32_t i = 0; i < size; i++) {
-      const Entry e = ent[a + i];
-      const double x = (double)e.value;
-      if (h.k1 && lane == 0) {
-        float* pw = tb.w + (size_t)e.id * tb.ws;
-        const double wv = LD(pw);
-        const double g = mult * x;
-        ST(gw + e.id, g);
-        ST(pw, wv - h.lr_d * ((double)(float)g + 2 * reg_w * wv));
-      }
-      if (act) {
-#pragma unroll
-        for (int v = 0; v < VEC; v++) {
-          float* pv = tb.V + (size_t)e.id * tb.rs + lane * VEC + v;
-          const double vv = LD(pv);
-          const double g = mult * (x * (sum[v] - vv * x));
-          ST(gv + (size_t)e.id * tb.rs + lane * VEC + v, g);
-          ST(pv, vv - h.lr_d * ((double)(float)g + 2 * reg_v[v] * vv));
-        }
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    if (!do_lambda || v_rows == 0) continue;
-    // ---------------- lambda step on the next validation row (:271-276, :201-248)
-    if (vpos >= v_rows) vpos = 0;
-    const uint64_t va = vrow_ptr[vpos];
-    const uint32_t vsize = (uint32_t)(vrow_ptr[vpos + 1] - va);
-    const double vy = (double)vtarget[vpos];
-    vpos++;
-    double lw = 0.0, plin = 0.0;
-    double s_dash[VEC], s_f[VEC], s_df[VEC]; double q_dash = 0.0;
-#pragma unroll
-    for (int v = 0; v < VEC; v++) { s_dash[v] = 0.0; s_f[v] = 0.0; s_df[v] = 0.0; }
-    for (uint32_t i = 0; i < vsize; i++) {
-      const Entry e = vent[va + i];
-      const double x = (double)e.value;
-      if (h.k1 && lane == 0) {
-        const double wv = LD(tb.w + (size_t)e.id * tb.ws);
-        const double w_dash = wv - h.lr_d * (LD(gw + e.id) + 2 * reg_w * wv);   // predict_scaled :178-184
-        plin += w_dash * x;
-        lw += x * wv;                                                            // :215-218
-      }
-      if (act) {
-#pragma unroll
-        for (int v = 0; v < VEC; v++) {
-          const double vv = LD(tb.V + (size_t)e.id * tb.rs + lane * VEC + v);
-          const double v_dash = vv - h.lr_d * (LD(gv + (size_t)e.id * tb.rs + lane * VEC + v) + 2 * reg_v[v] * vv);
-          const double d = v_dash * x;
-          s_dash[v] += d; q_dash += d * d;                                       // :186-196
-          s_f[v] += vv * x;                                                      // :233-238
-          s_df[v] += d * vv * x;
-        }
-      }
-    }
-    double vpart = plin - 0.5 * q_dash;
-    if (act) {
-#pragma unroll
-      for (int v = 0; v < VEC; v++) vpart += 0.5 * s_dash[v] * s_dash[v];
-    }
-    double vp = (h.k0 ? w0 : 0.0) + wave_sum_d(vpart);
-    double grad_loss;
-    if (h.task == 0) { vp = fmin(h.max_d, vp); vp = fmax(h.min_d, vp); grad_loss = 2 * (vp - vy); }
-    else grad_loss = vy * ((1.0 / (1.0 + exp(-vy * vp))) - 1.0);
-    if (h.k1) {                                                                  // :213-224
-      const double lwt = -2 * h.lr_d * wave_sum_d(lw);
-      reg_w -= h.lr_d * grad_loss * lwt;
-      reg_w = fmax(0.0, reg_w);
-    }
-    if (act) {                                                                   // :240-246
-#pragma unroll
-      for (int v = 0; v < VEC; v++) {
-        const double lambda_v_grad = -2 * h.lr_d * (s_dash[v] * s_f[v] - s_df[v]);
-        reg_v[v] -= h.lr_d * grad_loss * lambda_v_grad;
-        reg_v[v] = fmax(0.0, reg_v[v]);
-      }
-    }
-  }
-#undef LD
-#undef ST
-  if (lane == 0) { *w0_ptr = w0; reg[0] = reg_w; }
-  if (act) {
-#pragma unroll
-    for (int v = 0; v < VEC; v++) reg[1 + lane * VEC + v] = reg_v[v];
-  }
-}
-
-// ----------------------------------------------------------------------------------------------
 // SGDA in batch form (oracle fmo_sgda_epoch_minibatch; C-ABI fmx_sgda_epoch_minibatch).  The theta step of a batch is the
 // minibatch rule (k_rowsums -> k_scan -> k_sgda_apply_seg) with the learner's multiplier (Hyper::sgda), reg_0 = 0 and the
 // LEARNED regularisation 2 reg(g[,f]) theta per occurrence; the shadow gradient of a touched parameter becomes the sum of
@@ -2310,14 +2119,14 @@ k_sgda_lambda(const Entry* __restrict__ vent, const uint64_t* __restrict__ vrow_
               uint32_t vpos0, uint32_t n_rows, const Tab tb, const float* __restrict__ gw, const float* __restrict__ gv, Hyper h,
               const double* __restrict__ w0_ptr, const double* __restrict__ reg, double* __restrict__ dpart,
               const uint32_t* __restrict__ grp, uint32_t G) {
-  constexpr int VEC = Map<KP>::VEC, LPR = Map<KP>::LPR, U = 4;
+  constexpr int VEC = Map<KP>::VEC, U = 4;
   extern __shared__ double lam_lds[];
   double* lwg = lam_lds;                       // GROUPED: [G]         sum x w of the row, per group
   double* sfg = lwg + G;                       //          [G][KP]     sum v x
   double* sdfg = sfg + (size_t)G * KP;         //          [G][KP]     sum v' x v x
   double* acc = sdfg + (size_t)G * KP;         //          [G][1 + KP] this workgroup's changes
   const uint32_t lane = threadIdx.x;
-  const bool act = lane < LPR && lane * VEC < tb.rs;           // (the lanes of the row's elements: rows are tb.rs floats, row_ld above)
+  const bool act = row_lane<KP>(lane, tb);
   const double w0 = h.k0 ? *w0_ptr : 0.0;
   const uint32_t cells = G * (1 + KP);
   double acc_w = 0.0, acc_v[VEC];              // !GROUPED: the same in registers (lane 0 / factor lanes)
@@ -2403,10 +2212,7 @@ k_sgda_lambda(const Entry* __restrict__ vent, const uint64_t* __restrict__ vrow_
 #pragma unroll
       for (int v = 0; v < VEC; v++) vpart += 0.5 * s_dash[v] * s_dash[v];
     }
-    double vp = w0 + wave_sum_d(vpart);
-    double grad_loss;
-    if (h.task == 0) { vp = fmin(h.max_d, vp); vp = fmax(h.min_d, vp); grad_loss = 2 * (vp - vy); }
-    else grad_loss = vy * ((1.0 / (1.0 + exp(-vy * vp))) - 1.0);
+    const double grad_loss = sgda_mult_d(h, w0 + wave_sum_d(vpart), vy);
     const double scale = -h.lr_d * grad_loss * (-2 * h.lr_d);
     if (!GROUPED) {
       lw = wave_sum_d(lw);
@@ -2494,176 +2300,6 @@ k_block_fill(const Entry* __restrict__ main_ent, const uint64_t* __restrict__ ma
       for (uint64_t i = b.row_ptr[br]; i < b.row_ptr[br + 1]; i++) { Entry e = b.ent[i]; e.id += b.attr_offset; out[o++] = e; }
     }
   }
-}
-
-// ----------------------------------------------------------------------------------------------
-// k_sgda_groups: the same learner with attribute groups (`-meta`): reg_w(g), reg_v(g,f) and the per-group sums of the
-// lambda step (lambda_w_grad(g), sum_f(g), sum_f_dash_f(g); :96-98, :213-247) live in LDS:
-//   regw[G] | regv[G][KP] | lwg[G] | sfg[G][KP] | sdfg[G][KP] | stamp[G]
-// Only the groups present in a validation row are zeroed / updated: for an absent group the reference's update is
-// reg -= lr * grad_loss * (-0.0), i.e. the identity for every finite grad_loss.  Each (g, factor) cell is owned by
-// one lane; lane 0 owns the linear cells and the stamps, hence the barriers around the stamp reads.
-// reg (global): [G][1 + KP], reg[g*(1+KP)] = reg_w(g), reg[g*(1+KP)+1+f] = reg_v(g,f).
-// ----------------------------------------------------------------------------------------------
-template <int KP>
-__global__ void __launch_bounds__(64)
-k_sgda_groups(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, const float* __restrict__ target, uint32_t n_rows,
-              const Entry* __restrict__ vent, const uint64_t* __restrict__ vrow_ptr, const float* __restrict__ vtarget, uint32_t v_rows,
-              const Tab tb, float* gw, float* gv, Hyper h, double* w0_ptr, double* reg, int do_lambda,
-              const uint32_t* __restrict__ grp, uint32_t G) {
-  constexpr int VEC = Map<KP>::VEC, LPR = Map<KP>::LPR;
-  extern __shared__ double sgda_lds[];
-  double* regw = sgda_lds;
-  double* regv = regw + G;
-  double* lwg = regv + (size_t)G * KP;
-  double* sfg = lwg + G;
-  double* sdfg = sfg + (size_t)G * KP;
-  uint32_t* stamp = (uint32_t*)(sdfg + (size_t)G * KP);
-  const uint32_t lane = threadIdx.x;
-  const bool act = lane < LPR && lane * VEC < tb.rs;           // (the lanes of the row's elements: rows are tb.rs floats, row_ld above)
-  for (uint32_t g = lane; g < G; g += 64) { regw[g] = reg[(size_t)g * (1 + KP)]; stamp[g] = 0; }
-  for (uint32_t i = lane; i < G * KP; i += 64) regv[i] = reg[(size_t)(i / KP) * (1 + KP) + 1 + (i % KP)];
-  __syncthreads();
-  double w0 = *w0_ptr;
-  uint32_t vpos = 0, cur = 0;
-#define LD(p) ((double)__hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-#define ST(p, val) __hip_atomic_store((p), (float)(val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-  for (uint32_t r = 0; r < n_rows; r++) {
-    // ---------------- theta step (:136-169)
-    const uint64_t a = row_ptr[r];
-    const uint32_t size = (uint32_t)(row_ptr[r + 1] - a);
-    double sum[VEC]; double sq = 0.0, lin = 0.0;
-#pragma unroll
-    for (int v = 0; v < VEC; v++) sum[v] = 0.0;
-    for (uint32_t i = 0; i < size; i++) {
-      const Entry e = ent[a + i];
-      if (h.k1 && lane == 0) lin += LD(tb.w + (size_t)e.id * tb.ws) * (double)e.value;
-      if (act) {
-#pragma unroll
-        for (int v = 0; v < VEC; v++) {
-          const double d = LD(tb.V + (size_t)e.id * tb.rs + lane * VEC + v) * (double)e.value;
-          sum[v] += d; sq += d * d;
-        }
-      }
-    }
-    double part = lin - 0.5 * sq;
-    if (act) {
-#pragma unroll
-      for (int v = 0; v < VEC; v++) part += 0.5 * sum[v] * sum[v];
-    }
-    double p = (h.k0 ? w0 : 0.0) + wave_sum_d(part);
-    const double y = (double)target[r];
-    double mult;
-    if (h.task == 0) { p = fmin(h.max_d, p); p = fmax(h.min_d, p); mult = 2 * (p - y); }
-    else mult = y * ((1.0 / (1.0 + exp(-y * p))) - 1.0);
-    if (h.k0) w0 -= h.lr_d * (mult + 2 * 0.0 * w0);                          // reg_0 = 0 (:100)
-    for (uint32_t i = 0; i < size; i++) {
-      const Entry e = ent[a + i];
-      const uint32_t g = grp[e.id];
-      const double x = (double)e.value;
-      if (h.k1 && lane == 0) {
-        float* pw = tb.w + (size_t)e.id * tb.ws;
-        const double wv = LD(pw);
-        const double gr = mult * x;
-        ST(gw + e.id, gr);
-        ST(pw, wv - h.lr_d * ((double)(float)gr + 2 * regw[g] * wv));
-      }
-      if (act) {
-#pragma unroll
-        for (int v = 0; v < VEC; v++) {
-          float* pv = tb.V + (size_t)e.id * tb.rs + lane * VEC + v;
-          const double vv = LD(pv);
-          const double gr = mult * (x * (sum[v] - vv * x));
-          ST(gv + (size_t)e.id * tb.rs + lane * VEC + v, gr);
-          ST(pv, vv - h.lr_d * ((double)(float)gr + 2 * regv[(size_t)g * KP + lane * VEC + v] * vv));
-        }
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    if (!do_lambda || v_rows == 0) continue;
-    // ---------------- lambda step on the next validation row (:271-276, :201-248)
-    if (vpos >= v_rows) vpos = 0;
-    const uint64_t va = vrow_ptr[vpos];
-    const uint32_t vsize = (uint32_t)(vrow_ptr[vpos + 1] - va);
-    const double vy = (double)vtarget[vpos];
-    vpos++;
-    cur += 2;                                                                    // stamp == cur: sums valid; cur+1: updated
-    double plin = 0.0, q_dash = 0.0;
-    double s_dash[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; v++) s_dash[v] = 0.0;
-    for (uint32_t i = 0; i < vsize; i++) {
-      const Entry e = vent[va + i];
-      const uint32_t g = grp[e.id];
-      const double x = (double)e.value;
-      const bool fresh = stamp[g] != cur;
-      __syncthreads();
-      if (fresh) {
-        if (lane == 0) { lwg[g] = 0.0; stamp[g] = cur; }
-        if (act) {
-#pragma unroll
-          for (int v = 0; v < VEC; v++) { sfg[(size_t)g * KP + lane * VEC + v] = 0.0; sdfg[(size_t)g * KP + lane * VEC + v] = 0.0; }
-        }
-      }
-      __syncthreads();
-      if (h.k1 && lane == 0) {
-        const double wv = LD(tb.w + (size_t)e.id * tb.ws);
-        const double w_dash = wv - h.lr_d * (LD(gw + e.id) + 2 * regw[g] * wv);   // predict_scaled :178-184
-        plin += w_dash * x;
-        lwg[g] += x * wv;                                                          // :215-218
-      }
-      if (act) {
-#pragma unroll
-        for (int v = 0; v < VEC; v++) {
-          const size_t c = (size_t)g * KP + lane * VEC + v;
-          const double vv = LD(tb.V + (size_t)e.id * tb.rs + lane * VEC + v);
-          const double v_dash = vv - h.lr_d * (LD(gv + (size_t)e.id * tb.rs + lane * VEC + v) + 2 * regv[c] * vv);
-          const double d = v_dash * x;
-          s_dash[v] += d; q_dash += d * d;                                       // :186-196
-          sfg[c] += vv * x;                                                      // :233-238
-          sdfg[c] += d * vv * x;
-        }
-      }
-    }
-    double vpart = plin - 0.5 * q_dash;
-    if (act) {
-#pragma unroll
-      for (int v = 0; v < VEC; v++) vpart += 0.5 * s_dash[v] * s_dash[v];
-    }
-    double vp = (h.k0 ? w0 : 0.0) + wave_sum_d(vpart);
-    double grad_loss;
-    if (h.task == 0) { vp = fmin(h.max_d, vp); vp = fmax(h.min_d, vp); grad_loss = 2 * (vp - vy); }
-    else grad_loss = vy * ((1.0 / (1.0 + exp(-vy * vp))) - 1.0);
-    for (uint32_t i = 0; i < vsize; i++) {                                       // every group of the row, once
-      const uint32_t g = grp[vent[va + i].id];
-      const bool todo = stamp[g] == cur;
-      __syncthreads();
-      if (todo) {
-        if (lane == 0) {
-          stamp[g] = cur + 1;
-          if (h.k1) {                                                            // :213-224
-            const double lwt = -2 * h.lr_d * lwg[g];
-            regw[g] = fmax(0.0, regw[g] - h.lr_d * grad_loss * lwt);
-          }
-        }
-        if (act) {                                                               // :240-246
-#pragma unroll
-          for (int v = 0; v < VEC; v++) {
-            const size_t c = (size_t)g * KP + lane * VEC + v;
-            const double lambda_v_grad = -2 * h.lr_d * (s_dash[v] * sfg[c] - sdfg[c]);
-            regv[c] = fmax(0.0, regv[c] - h.lr_d * grad_loss * lambda_v_grad);
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-#undef LD
-#undef ST
-  __syncthreads();
-  if (lane == 0) *w0_ptr = w0;
-  for (uint32_t g = lane; g < G; g += 64) reg[(size_t)g * (1 + KP)] = regw[g];
-  for (uint32_t i = lane; i < G * KP; i += 64) reg[(size_t)(i / KP) * (1 + KP) + 1 + (i % KP)] = regv[i];
 }
 
 // ----------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // k_sequential_rows: the reference's own trajectory (fm_learn_sgd_element.h:56-67: one example at a time, in file order; fm_sgd.h:33-51) on ONE
 // wavefront, a row at a time instead of an entry at a time.
 //
-// k_sequential (fmx_kernels.h) walks a row entry by entry and drains the store queue after each: 32 dependent round trips per example,
+// k_sequential (fmx_online_kernels.h) walks a row entry by entry and drains the store queue after each: 32 dependent round trips per example,
 // 46 us per example at the bench shape -- slower than the CPU it is the parity instrument for (21.8 k vs 26.8 k examples/s).  The loop of
 // the reference does not need that: its update of entry i reads the sums of the WHOLE row (fm.m_sum, taken before the first update) and the
 // parameter v_{j_i, f} itself, which only an EARLIER entry of the same row with the same id can have changed.  So for a row without a
@@ -9,7 +9,7 @@
 // order, multiplier, bias step, every row updated from its registers, stored.  What the NEXT example must see is only what it shares with
 // this one -- so its rows are asked for BEFORE this example's stores are issued (their latency runs under this example's arithmetic) and
 // the few it shares with this example (found by comparing the ids) are read again after the stores have drained.
-// Rows with a repeated id, and rows beyond the register path, take the entry-by-entry loop (seq_row_entries: k_sequential's body).
+// Rows with a repeated id, and rows beyond the register path, take the entry-by-entry loop (seq_row_entries: k_sequential's own row step).
 // The update arithmetic is fp32 with its per-example constants formed in fp64 (the parameters are fp32; the sums stay fp64).
 //
 // Second half of the file: CONFLICT-FREE RUNS -- where consecutive rows rarely share a feature the same trajectory runs at batch speed, one
@@ -17,58 +17,6 @@
 #pragma once
 
 namespace fmx {
-
-// one row, entry by entry, every store drained before the next entry (k_sequential's loop body: repeated ids see their own earlier update)
-template <int KP>
-__device__ __forceinline__ void seq_row_entries(const Entry* __restrict__ ent, uint64_t a, uint32_t size, float yf, const Tab& tb, const Hyper& h, double& w0) {
-  constexpr int VEC = Map<KP>::VEC, LPR = Map<KP>::LPR;
-  const uint32_t lane = threadIdx.x & 63u;
-  const bool act = lane < LPR && lane * VEC < tb.rs;
-  double sum[VEC]; double sq = 0.0, lin = 0.0;
-#pragma unroll
-  for (int v = 0; v < VEC; v++) sum[v] = 0.0;
-  for (uint32_t i = 0; i < size; i++) {
-    const Entry e = ent[a + i];
-    if (h.k1 && lane == 0) lin += (double)ld_l2(tb.w + (size_t)e.id * tb.ws) * (double)e.value;
-    if (act) {
-#pragma unroll
-      for (int v = 0; v < VEC; v++) {
-        const double d = (double)ld_l2(tb.V + (size_t)e.id * tb.rs + lane * VEC + v) * (double)e.value;
-        sum[v] += d;
-        sq += d * d;
-      }
-    }
-  }
-  double part = lin - 0.5 * sq;
-  if (act) {
-#pragma unroll
-    for (int v = 0; v < VEC; v++) part += 0.5 * sum[v] * sum[v];
-  }
-  double p = (h.k0 ? w0 : 0.0) + wave_sum_d(part);
-  const double y = (double)yf;
-  double mult;
-  if (h.task == 0) { p = fmin(h.max_d, p); p = fmax(h.min_d, p); mult = -(y - p); }
-  else mult = -y * (1.0 - 1.0 / (1.0 + exp(-y * p)));
-  if (h.k0) w0 -= h.lr_d * (mult + h.reg0_d * w0);
-  for (uint32_t i = 0; i < size; i++) {
-    const Entry e = ent[a + i];
-    const double x = (double)e.value;
-    if (h.k1 && lane == 0) {
-      const double wv = (double)ld_l2(tb.w + (size_t)e.id * tb.ws);
-      tb.w[(size_t)e.id * tb.ws] = (float)(wv - h.lr_d * (mult * x + h.regw_d * wv));
-    }
-    if (act) {
-#pragma unroll
-      for (int v = 0; v < VEC; v++) {
-        float* pv = tb.V + (size_t)e.id * tb.rs + lane * VEC + v;
-        const double vv = (double)ld_l2(pv);
-        const double grad = sum[v] * x - vv * x * x;
-        *pv = (float)(vv - h.lr_d * (mult * grad + h.regv_d * vv));
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // a later entry of this row (repeated id) and the next row must observe these stores
-  }
-}
 
 struct SeqRow { uint64_t a; uint32_t size; float y; Entry en; };
 __device__ __forceinline__ SeqRow seq_meta(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, const float* __restrict__ target, uint32_t r, uint32_t n_rows) {
@@ -184,11 +132,7 @@ __device__ __forceinline__ void seq_step(const Entry* __restrict__ ent, const ui
 #pragma unroll
     for (int v = 0; v < VEC; v++) part += 0.5 * sum[v] * sum[v];
   }
-  double p = (h.k0 ? w0 : 0.0) + wave_sum_d(part);
-  const double y = (double)cur.y;
-  double mult;
-  if (h.task == 0) { p = fmin(h.max_d, p); p = fmax(h.min_d, p); mult = -(y - p); }
-  else mult = -y * (1.0 - 1.0 / (1.0 + exp(-y * p)));
+  const double mult = sgd_mult_d(h, (h.k0 ? w0 : 0.0) + wave_sum_d(part), (double)cur.y);
   if (h.k0) w0 -= h.lr_d * (mult + h.reg0_d * w0);                // fm_sgd.h:34-37
   // ---- the next example's rows: asked for BEFORE this example's stores (their latency runs under the update below) ----
   uint32_t idn = 0;
@@ -396,11 +340,7 @@ __device__ __forceinline__ void seq_wg_step(SeqLds<KP>& L, const Entry* __restri
   double part = ((h.k1 && lane < cur.size) ? (double)wl * (double)xl : 0.0) - 0.5 * tsq;
 #pragma unroll
   for (int v = 0; v < VEC; v++) part += 0.5 * tot[v] * tot[v];
-  double p = (h.k0 ? w0 : 0.0) + wave_sum_d(part);
-  const double y = (double)cur.y;
-  double mult;
-  if (h.task == 0) { p = fmin(h.max_d, p); p = fmax(h.min_d, p); mult = -(y - p); }
-  else mult = -y * (1.0 - 1.0 / (1.0 + exp(-y * p)));
+  const double mult = sgd_mult_d(h, (h.k0 ? w0 : 0.0) + wave_sum_d(part), (double)cur.y);
   if (h.k0) w0 -= h.lr_d * (mult + h.reg0_d * w0);                // fm_sgd.h:34-37
   // ---- this wavefront's part of the update (fm_sgd.h:38-50) ----
   const float lm = (float)(h.lr_d * mult), lrv = (float)(h.lr_d * h.regv_d), lrw = (float)(h.lr_d * h.regw_d);

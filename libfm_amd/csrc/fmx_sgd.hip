@@ -2,6 +2,7 @@
 // the multi-GPU driver, the bias-lag bookkeeping, the (batch, feature) segment build, and SGDA.
 #include "fmx_internal.h"
 #include "fmx_xcd_kernels.h"
+#include "fmx_online_kernels.h"
 #include "fmx_seq_kernels.h"
 #include "fmx_small_kernels.h"
 
@@ -1478,16 +1479,16 @@ int fmx_sgda_epoch(fmx_handle h, int train_slot, int validation_slot, int do_lam
   if (stats) memset(stats, 0, sizeof(*stats));
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   if (h->num_groups <= 1) {
-    KP_SWITCH(h->KP, hipLaunchKernelGGL((k_sgda<KP>), dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr, s.target, s.n_rows,
+    KP_SWITCH(h->KP, hipLaunchKernelGGL((k_sgda<KP, false>), dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr, s.target, s.n_rows,
                                           v.ent, v.row_ptr, v.target, v.n_rows, h->tb, h->sgda.gw, h->sgda.gv, hy, h->w0,
-                                          h->sgda.reg, do_lambda_steps));
+                                          h->sgda.reg, do_lambda_steps, nullptr, 1u));
   } else {
-    // LDS tables of k_sgda_groups: regw[G] regv[G][KP] lwg[G] sfg[G][KP] sdfg[G][KP] (doubles) + stamp[G] (u32)
+    // LDS tables of k_sgda<KP, true>: regw[G] regv[G][KP] lwg[G] sfg[G][KP] sdfg[G][KP] (doubles) + stamp[G] (u32)
     const size_t G = h->num_groups, lds = (2 * G + 3 * G * (size_t)h->KP) * sizeof(double) + G * sizeof(uint32_t);
     const size_t lds_max = h->prop.sharedMemPerBlock ? h->prop.sharedMemPerBlock : 64 * 1024;
     if (lds > lds_max)
       return fail(h, FMX_E_UNSUPPORTED, "SGDA: %zu attribute groups x %d factors need %zu bytes of LDS (limit %zu)", G, h->KP, lds, lds_max);
-    KP_SWITCH(h->KP, hipLaunchKernelGGL((k_sgda_groups<KP>), dim3(1), dim3(64), lds, h->stream, s.ent, s.row_ptr, s.target, s.n_rows,
+    KP_SWITCH(h->KP, hipLaunchKernelGGL((k_sgda<KP, true>), dim3(1), dim3(64), lds, h->stream, s.ent, s.row_ptr, s.target, s.n_rows,
                                           v.ent, v.row_ptr, v.target, v.n_rows, h->tb, h->sgda.gw, h->sgda.gv, hy, h->w0,
                                           h->sgda.reg, do_lambda_steps, h->grp, (uint32_t)G));
   }

@@ -315,3 +315,38 @@ def test_two_handles_bit_identical(capi, oracle, monkeypatch, name, knobs):
     assert stats[0] == stats[1]
     assert outs[0][0] == outs[1][0]
     assert np.array_equal(outs[0][1], outs[1][1]) and np.array_equal(outs[0][2], outs[1][2])
+
+
+# ---- the fallback of the row-at-a-time kernels IS the entry-by-entry kernel: rows that all repeat an id, the same bits in three forms ----
+@pytest.mark.parametrize("k,task", [(64, 0), (100, 1)])
+def test_repeated_ids_same_bits_entry_by_entry_in_every_kernel(capi, oracle, monkeypatch, k, task):
+    rng = np.random.default_rng(900 + k)
+    rows, n = 64, 20
+    sizes = 3 + np.arange(rows) % 3                                     # 3 .. 5 entries
+    rp = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+    ent = np.zeros(int(rp[-1]), dtype=ENTRY)
+    for r in range(rows):
+        ids = rng.choice(n, sizes[r], replace=False)
+        ids[int(rng.integers(1, sizes[r]))] = ids[0]                    # every row repeats an id
+        ent["id"][int(rp[r]):int(rp[r + 1])] = ids
+    ent["value"] = np.round(rng.uniform(0.5, 1.5, len(ent)), 3).astype(np.float32)
+    y = (np.where(rng.random(rows) < 0.5, -1.0, 1.0) if task else np.round(rng.normal(3.0, 1.2, rows), 2)).astype(np.float32)
+    lo, hi = (-1.0, 1.0) if task else (float(y.min()), float(y.max()))
+    m = start_model(oracle, 7, n, k, 1, 1, 5)
+    outs = []
+    for knobs, bit in (({"FMX_SEQ_RUNS": "0", "FMX_SEQ_ROWS": "0"}, R.STAT_SEQ_ENTRIES), ({"FMX_SEQ_RUNS": "0", "FMX_SEQ_WG": "0"}, R.STAT_SEQ_ROWS),
+                       ({"FMX_SEQ_RUNS": "0"}, R.STAT_SEQ_WG)):
+        set_knobs(monkeypatch, knobs)
+        h = capi.Handle(n, k, 1, 1, task, 0.001, 0.002, 0.003, 0.01 if task else 0.002, lo, hi)
+        try:
+            h.set_params(m.w0, m.w, m.v)
+            h.upload_rows(0, ent, rp, y)
+            for _ in range(2):
+                st = h.sgd_epoch(0, capi.SGD_SEQUENTIAL)
+                assert st.status & R.SEQ_MASK == bit, "status %#x, expected %#x" % (st.status & R.SEQ_MASK, bit)
+            outs.append(h.get_params())
+        finally:
+            h.close()
+    for w0, w, v in outs[1:]:
+        assert w0 == outs[0][0]
+        assert np.array_equal(w, outs[0][1]) and np.array_equal(v, outs[0][2])
