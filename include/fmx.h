@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define FMX_ABI_VERSION 10
+#define FMX_ABI_VERSION 11
 
 enum {
   FMX_OK = 0,
@@ -216,8 +216,7 @@ typedef struct fmx_epoch_stats {
 #define FMX_STAT_EVENT_SYNC    32u /* the launch stream and the recurrence's side stream were ordered by events, not by the device-side
                                       hand-off: requested (FMX_FLAG_EVENT_SYNC / FMX_HANDOFF=0), bias_lag 1, or the handle found that its two
                                       streams do not run concurrently (serialised dispatch: a counter-collecting profiler, AMD_SERIALIZE_KERNEL) */
-#define FMX_STAT_XCD_RESIDENT 128u /* small batches (what the stability cut leaves of rows with frequent features): the epoch ran as ONE launch whose
-                                      workgroups sit on one accelerator complex die (libfm_amd/csrc/fmx_xcd_kernels.h) instead of two launches per batch */
+/* (ABI 11) bit 128u is reserved and never set: it was FMX_STAT_XCD_RESIDENT, the status of an experiment that has been removed */
 #define FMX_STAT_SEQ_RUNS 256u     /* FMX_SGD_SEQUENTIAL ran as conflict-free runs: maximal runs of consecutive rows that share no feature, each one
                                       batch step with the bias recurrence coupled example by example -- the same trajectory as the online loop.
                                       fmx_epoch_stats::batches = the number of runs.  (A run whose workgroups never all arrive -- a shared or

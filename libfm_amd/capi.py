@@ -23,7 +23,7 @@ FLAG_KEEP_WSIDE = 32
 EVAL_WSIDE = 1
 STAT_BATCH_CUT, STAT_UNSTABLE = 1, 2
 STAT_WARN = 3   # FMX_STAT_WARN_MASK: the two bits that say something about the RULE; the bits above are how the epoch ran (include/fmx.h, ABI 7, 9)
-STAT_SCAN_PIT, STAT_SCAN_SERIAL, STAT_SCAN_FALLBACK, STAT_EVENT_SYNC, STAT_HANDOFF_TIMEOUT, STAT_XCD_RESIDENT, STAT_SEQ_RUNS, STAT_SMALL_ONE = 4, 8, 16, 32, 64, 128, 256, 512
+STAT_SCAN_PIT, STAT_SCAN_SERIAL, STAT_SCAN_FALLBACK, STAT_EVENT_SYNC, STAT_HANDOFF_TIMEOUT, STAT_SEQ_RUNS, STAT_SMALL_ONE = 4, 8, 16, 32, 64, 256, 512
 # FMX_SGD_SEQUENTIAL: which kernels the epoch ran (ABI 9)
 STAT_SEQ_ENTRIES, STAT_SEQ_WG, STAT_SEQ_ROWS, STAT_RUN_ONE, STAT_RUN_TWO, STAT_RUN_THREE = 1024, 2048, 4096, 8192, 16384, 32768
 SYNTH_UNIFORM, SYNTH_CRITEO = 0, 1

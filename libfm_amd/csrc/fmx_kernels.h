@@ -253,21 +253,44 @@ template <class T> __device__ __forceinline__ T load_stream8(const T* p) {
   return *p;
 }
 __device__ __forceinline__ float load_w(const float* p) { return *p; }
-// loads that are served by the L2 -- they bypass the per-CU L1, which no other CU's store ever refreshes: what a persistent kernel reads the
-// words of other workgroups OF ITS OWN DIE with (fmx_xcd_kernels.h).  Two forms skip the L1 (scripts/ubench/load_flavours.hip: 105-110 ns
-// per dependent load for either, 72 ns for an L1 hit): device scope (sc1) keeps the line in the L2 like a plain load -- for what is read
-// again soon (frequent rows, sums, multipliers, flags); non-temporal marks it to be evicted first -- for the rows that pass through once
-// (ld_l2_stream), so that they do not push the frequent rows out of the die's 4 MiB (profiles/r06_criteo_hops.txt).
+// loads that are served by the L2: a relaxed device-scope load (sc1) bypasses the per-CU L1, which no store ever refreshes, and keeps the
+// line in the L2 like a plain load (scripts/ubench/load_flavours.hip: 105-110 ns per dependent load, 72 ns for an L1 hit).  It is what a
+// kernel reads a parameter with that the SAME launch has written before: the one-wavefront online kernels (fmx_online_kernels.h), where a
+// later entry of a row may name the feature an earlier entry updated, and the sequential kernels (fmx_seq_kernels.h), where an example
+// gathers the rows the example before it stored.
 __device__ __forceinline__ float ld_l2(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned ld_l2(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double ld_l2(const double* p) {
-  return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ float ld_l2_stream(const float* p) { return __builtin_nontemporal_load(p); }
 // the store that goes with ld_l2 in the one-wavefront online kernels (fmx_online_kernels.h)
 __device__ __forceinline__ void st_l2(float* p, float x) { __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// (words that cross dies -- the membership counters of a launch -- are read at device scope)
-__device__ __forceinline__ unsigned ld_dev(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// ld_l2 of a lane's VEC consecutive floats in one request
+template <int VEC> __device__ __forceinline__ void ld_l2_vec(const float* p, float (&out)[VEC]) {
+  static_assert(VEC == 1 || VEC == 2, "rows of 64 or 128 floats");
+  if constexpr (VEC == 1) out[0] = ld_l2(p);
+  else {
+    const unsigned long long u = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    out[0] = __uint_as_float((uint32_t)u); out[1] = __uint_as_float((uint32_t)(u >> 32));
+  }
+}
+// a parameter row where ONE wavefront covers it (the sequential kernels): the L2-served load and the plain vector store (rows are tb.rs
+// floats: the lanes beyond take no part, row_ld)
+template <int VEC> __device__ __forceinline__ void row_ld_l2(const Tab& tb, size_t id, float (&out)[VEC]) {
+  const uint32_t off = (threadIdx.x & 63u) * VEC;
+  if (off < tb.rs) ld_l2_vec<VEC>(tb.V + id * tb.rs + off, out);
+  else {
+#pragma unroll
+    for (int v = 0; v < VEC; v++) out[v] = 0.f;
+  }
+}
+template <int VEC> __device__ __forceinline__ void row_st_l2(const Tab& tb, size_t id, const float (&in)[VEC]) {
+  const uint32_t off = (threadIdx.x & 63u) * VEC;
+  if (off < tb.rs) store_vec<VEC>(tb.V + id * tb.rs + off, in);
+}
+// a wave-uniform value as a scalar (wave-uniform by construction: say so)
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+// a lane's value as a scalar (wave-uniform lane index)
+template <int T> __device__ __forceinline__ uint32_t lane_val(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, T); }
+// the same value behind an empty statement: the compiler would otherwise keep the scalars it broadcast for the gathers alive until the
+// stores (spilled into vector lanes); broadcasts of the copy are separate, short-lived values
+__device__ __forceinline__ uint32_t opaque(uint32_t v) { asm volatile("" : "+v"(v)); return v; }
 // loss multiplier, fm_learn_sgd_element.h:58-65
 __device__ __forceinline__ float multiplier(const Hyper& h, float p, float y) {
   if (h.task == 0) {
@@ -1776,11 +1799,9 @@ __device__ __forceinline__ void apply_seg_block(const SegWork& sw, uint32_t blk,
 // thousand examples) on one wavefront, straight from global memory -- k_scan's arithmetic (micro-chunks of `chunk` examples, every
 // example of a chunk sees the bias of the chunk start, fm_sgd.h:34-37 summed per chunk) without its LDS tiles
 struct ScanSmall { const float* rest; const float* target; const double* w0_in; double* w0_out; uint32_t n_rows, chunk; };
-// COH: rest[] and the incoming bias were written by other workgroups of THIS launch (the XCD-resident epoch): L2-served loads
-template <bool COH = false>
 __device__ __forceinline__ void scan_small(const ScanSmall sc, const Hyper& h) {
   const uint32_t lane = threadIdx.x & 63u;
-  double w0 = COH ? ld_l2(sc.w0_in) : *sc.w0_in;
+  double w0 = *sc.w0_in;
   if (sc.n_rows <= 1024u && ((sc.chunk & 63u) == 0 || sc.chunk == 32u || sc.chunk == 16u)) {
     // the whole batch in registers first (one round trip to memory, not one per micro-chunk): element c0 + i + 64 j of a chunk
     // sits in lane i, register (c0 / 64 + j)
@@ -1788,7 +1809,7 @@ __device__ __forceinline__ void scan_small(const ScanSmall sc, const Hyper& h) {
 #pragma unroll
     for (int j = 0; j < 16; j++) {
       const uint32_t i = (uint32_t)j * 64u + lane;
-      r[j] = (i < sc.n_rows) ? (COH ? ld_l2(sc.rest + i) : sc.rest[i]) : 0.f;
+      r[j] = (i < sc.n_rows) ? sc.rest[i] : 0.f;
       y[j] = (i < sc.n_rows) ? sc.target[i] : 0.f;
     }
     if (sc.chunk < 64u) {
@@ -1829,7 +1850,7 @@ __device__ __forceinline__ void scan_small(const ScanSmall sc, const Hyper& h) {
       const uint32_t nc = min(sc.chunk, sc.n_rows - c0);
       const float w0s = h.k0 ? (float)w0 : 0.f;
       float acc = 0.f;
-      for (uint32_t i = lane; i < nc; i += 64) acc += multiplier_fast(h, w0s + (COH ? ld_l2(sc.rest + c0 + i) : sc.rest[c0 + i]), sc.target[c0 + i]);
+      for (uint32_t i = lane; i < nc; i += 64) acc += multiplier_fast(h, w0s + sc.rest[c0 + i], sc.target[c0 + i]);
       const float tot = wave_sum_dpp(acc);
       if (h.k0) w0 -= (double)h.lr * ((double)tot + (double)nc * (double)h.reg0 * (double)w0s);
     }

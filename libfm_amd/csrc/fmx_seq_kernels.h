@@ -35,7 +35,7 @@ template <int KP, int ZR, int T>
 __device__ __forceinline__ void seq_rows_load(const Tab& tb, uint32_t ids, uint32_t size, float (&vr)[ZR][Map<KP>::VEC]) {
   constexpr int VEC = Map<KP>::VEC;
   if constexpr (T < ZR) {
-    if ((uint32_t)T < size) xcd_row_ld<VEC>(tb, (size_t)lane_val<T>(ids), vr[T]);
+    if ((uint32_t)T < size) row_ld_l2<VEC>(tb, (size_t)lane_val<T>(ids), vr[T]);
     else {
 #pragma unroll
       for (int v = 0; v < VEC; v++) vr[T][v] = 0.f;
@@ -48,7 +48,7 @@ template <int KP, int ZR, int T>
 __device__ __forceinline__ void seq_rows_again(const Tab& tb, uint32_t ids, uint64_t again, float (&vr)[ZR][Map<KP>::VEC]) {
   constexpr int VEC = Map<KP>::VEC;
   if constexpr (T < ZR) {
-    if ((again >> T) & 1ull) xcd_row_ld<VEC>(tb, (size_t)lane_val<T>(ids), vr[T]);
+    if ((again >> T) & 1ull) row_ld_l2<VEC>(tb, (size_t)lane_val<T>(ids), vr[T]);
     seq_rows_again<KP, ZR, T + 1>(tb, ids, again, vr);
   }
 }
@@ -82,7 +82,7 @@ __device__ __forceinline__ void seq_rows_store(const Tab& tb, uint32_t ids, uint
         const float grad = sumf[v] * x - vv * x * x;
         nv[v] = vv - (lm * grad + lrv * vv);
       }
-      xcd_row_st<VEC>(tb, (size_t)lane_val<T>(ids), nv);
+      row_st_l2<VEC>(tb, (size_t)lane_val<T>(ids), nv);
     }
     seq_rows_store<KP, ZR, T + 1>(tb, ids, xs, size, vr, sumf, lm, lrv);
   }
@@ -233,7 +233,7 @@ __device__ __forceinline__ void seq_wg_ask(const Tab& tb, const Hyper& h, const 
     const uint32_t t = wv + (uint32_t)SEQ_W * i;
 #pragma unroll
     for (int v = 0; v < VEC; v++) R[i][v] = 0.f;
-    if (t < m.size) xcd_row_ld<VEC>(tb, (size_t)bcast_u32<1>(ids, t), R[i]);
+    if (t < m.size) row_ld_l2<VEC>(tb, (size_t)bcast_u32<1>(ids, t), R[i]);
   }
 }
 
@@ -356,7 +356,7 @@ __device__ __forceinline__ void seq_wg_step(SeqLds<KP>& L, const Entry* __restri
       float nv[VEC];
 #pragma unroll
       for (int v = 0; v < VEC; v++) { const float vv = R[i][v]; nv[v] = vv - (lm * (totf[v] * x - vv * x * x) + lrv * vv); }
-      xcd_row_st<VEC>(tb, (size_t)bcast_u32<1>(ids, t), nv);
+      row_st_l2<VEC>(tb, (size_t)bcast_u32<1>(ids, t), nv);
     }
   }
   // ---- what the next example shares with this one was read too early (every wavefront finds the same answer) ----
@@ -373,7 +373,7 @@ __device__ __forceinline__ void seq_wg_step(SeqLds<KP>& L, const Entry* __restri
 #pragma unroll
       for (int i = 0; i < SEQ_SLOTS; i++) {
         const uint32_t t = wv + (uint32_t)SEQ_W * i;
-        if (t < nxt.size && ((again >> t) & 1ull)) xcd_row_ld<VEC>(tb, (size_t)bcast_u32<1>(idn, t), Rn[i]);
+        if (t < nxt.size && ((again >> t) & 1ull)) row_ld_l2<VEC>(tb, (size_t)bcast_u32<1>(idn, t), Rn[i]);
       }
     }
   }

@@ -196,7 +196,7 @@ k_small_one(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr,
       if (__any(!ok)) { if (lane == 0) atomicOr(sy.err, RUN_ERR_EXCHANGE); return; }
       ScanSmall s2 = sc_prev;
       s2.rest = s_rest;
-      scan_small<false>(s2, h);
+      scan_small(s2, h);
       if (sc.n_rows) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");   // (the bias it left is what the next one starts from)
     }
     if (sc.n_rows) {
@@ -209,7 +209,7 @@ k_small_one(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr,
       if (__any(!ok)) { if (lane == 0) atomicOr(sy.err, RUN_ERR_EXCHANGE); return; }
       ScanSmall s2 = sc;
       s2.rest = s_rest;
-      scan_small<false>(s2, h);
+      scan_small(s2, h);
     }
     trace_max(sy.trace, 9);
     return;

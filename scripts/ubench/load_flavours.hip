@@ -1,6 +1,7 @@
 // dependent-load latency by load flavour and working-set size on gfx950 (one wavefront, lane 0 chases a random cycle):
-// which global_load forms are served by the per-CU L1, which by the XCD's L2, which go to the fabric.  Used to choose the loads of the
-// XCD-resident epoch (libfm_amd/csrc/fmx_xcd_kernels.h).   hipcc --offload-arch=gfx950 -O3 -o load_flavours load_flavours.hip
+// which global_load forms are served by the per-CU L1, which by the XCD's L2, which go to the fabric.  Used to choose the L2-served loads
+// (ld_l2, libfm_amd/csrc/fmx_kernels.h) of the online and sequential kernels; first written for the XCD-resident epoch, an experiment that has
+// been removed (git show b0b2627:libfm_amd/csrc/fmx_xcd_kernels.h).   hipcc --offload-arch=gfx950 -O3 -o load_flavours load_flavours.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>

@@ -97,7 +97,7 @@ def test_abi_version_and_pair_symbols():
     build.build()
     lib = capi.load()
     hdr = open(os.path.join(ROOT, "include", "fmx.h")).read()
-    assert int(re.search(r"#define\s+FMX_ABI_VERSION\s+(\d+)", hdr).group(1)) == 10 == lib.fmx_abi_version()
+    assert int(re.search(r"#define\s+FMX_ABI_VERSION\s+(\d+)", hdr).group(1)) == 11 == lib.fmx_abi_version()
     names = {n for n, _, _ in capi.SYMBOLS}
     for fn in ("fmx_upload_pairs", "fmx_pair_epoch", "fmx_pair_evaluate"):
         assert fn in names and fn + "(" in hdr.replace(" (", "(") and hasattr(lib, fn)

@@ -108,13 +108,12 @@ def test_short_rows_of_a_shard_several_examples_per_wavefront(capi, oracle, k, w
         h.close()
 
 
-@pytest.mark.parametrize("schedule", ["general", "in_stream", "threads"])
+@pytest.mark.parametrize("schedule", ["general", "in_stream"])
 def test_small_batch_schedules_of_the_group_driver_are_one_rule(capi, oracle, monkeypatch, schedule):
-    """a 512-row batch over 8 shards (BASELINE configs[2]'s shape of the step) through the three schedules fmx_group_sgd_epoch has for it:
-    the general one (~20 host calls per shard and batch: comm-stream events, the recurrence on the side stream), the in-stream one (default:
-    3 launches per shard and batch) and the in-stream one with a host thread per shard (FMX_GROUP_THREADS=1) -- the oracle's rule at 1e-4."""
+    """a 512-row batch over 8 shards (BASELINE configs[2]'s shape of the step) through the two schedules fmx_group_sgd_epoch has for it:
+    the general one (~20 host calls per shard and batch: comm-stream events, the recurrence on the side stream) and the in-stream one (default:
+    3 launches per shard and batch) -- the oracle's rule at 1e-4."""
     monkeypatch.setenv("FMX_GROUP_IN_STREAM", "0" if schedule == "general" else "1")
-    monkeypatch.setenv("FMX_GROUP_THREADS", "1" if schedule == "threads" else "0")
     import datagen as DG
     rows, k, world, lag = 4000, 64, 8, 2
     e, rp, y, n = DG.criteo_shaped(rows, 21, cat_ids=2000)

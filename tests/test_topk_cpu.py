@@ -18,7 +18,7 @@ def test_symbol_declared_bound_exported_abi_unchanged():
     build.build()
     lib = capi.load()
     hdr = open(os.path.join(ROOT, "include", "fmx.h")).read()
-    assert int(re.search(r"#define\s+FMX_ABI_VERSION\s+(\d+)", hdr).group(1)) == 10 == lib.fmx_abi_version()
+    assert int(re.search(r"#define\s+FMX_ABI_VERSION\s+(\d+)", hdr).group(1)) == 11 == lib.fmx_abi_version()
     assert "int fmx_topk(" in hdr
     assert int(re.search(r"#define\s+FMX_TOPK_MAX\s+(\d+)u", hdr).group(1)) == capi.TOPK_MAX == 1024
     assert "fmx_topk" in {n for n, _, _ in capi.SYMBOLS} and hasattr(lib, "fmx_topk")
