@@ -429,6 +429,57 @@ int fmx_predict(fmx_handle h, int slot, double *out);
 /* fm_learn::evaluate (fm_learn.h:93-153) fused on the device */
 int fmx_evaluate(fmx_handle h, int slot, fmx_eval *out);
 
+/* ---- exact AUC and log loss of a slot, reduced on the device -----------------------------------
+ * fm_learn::evaluate knows RMSE / MAE and sign accuracy only (fm_learn.h:113-153); for `-task c` on imbalanced labels the
+ * metrics people read are AUC and log loss.  fmx_evaluate_ex scores the slot like fmx_evaluate (one pass at the predict
+ * roofline, kept `-relation` blocks and the weight side stream included) and reduces on the device.  With p_i the fp32 raw
+ * y-hat fmx_predict returns for row i (w0 + rest, no clamp) and s_i = +1 if target_i >= 0, else -1 (the sign rule of fm_learn.h:118):
+ *   auc_num2 = sum_{i: s_i = +1} sum_{j: s_j = -1} ( 2 [p_i > p_j] + [p_i == p_j] )      float comparisons: +0 == -0
+ *   auc      = auc_num2 / (2 pos neg), NaN when pos neg == 0.  auc_num2 is that INTEGER exactly (tie-aware, no sampling, no
+ *              binning: one radix sort of the scores + two scans); for n_rows < 2^31, 2 pos neg < 2^63.
+ *   logloss  = (1 / rows) sum_i l(s_i p_i), evaluated in fp64 from the fp32 score:
+ *              FMX_LINK_LOGISTIC  l(z) = max(-z, 0) + log1p(exp(-|z|))        = -ln sigmoid(z)
+ *              FMX_LINK_PROBIT    l(z) = -log(0.5 erfc(-z / sqrt(2)))         = -ln Phi(z), AS COMPUTED: +inf where erfc underflows
+ *                                                                               (z below about -38)
+ *              an infinite score gives 0 or +inf accordingly.
+ *   NaN scores: nan_rows > 0 makes auc and logloss NaN and auc_num2 0 (nothing is sorted); rows, nan_rows, pos, neg, correct and
+ *              accuracy are still right -- a diverged model shows up in the metrics instead of vanishing from their denominators.
+ *   regression handles: rmse and mae (clamped, fm_learn.h:138-152); accuracy and the classification counts 0, auc = logloss = NaN,
+ *              no sort.  Classification handles: rmse = mae = 0, as in fmx_eval.
+ *   an empty slot: FMX_OK, rows = 0, auc = logloss = NaN, everything else 0.
+ * Every fp64 sum is taken in a fixed order (per-block partials on a grid that is a fixed function of n_rows, summed in block order
+ * by a final kernel; the integer counts likewise, the AUC numerator with integer atomics): two calls with unchanged parameters are
+ * bit-identical in every field except the two times -- fmx_evaluate, whose partials meet in fp64 atomics, is not.
+ * Device memory, allocated and freed inside the call: 24 bytes per row (8 + 8 the sort's key double buffer, 4 + 4 the two scans) +
+ * the radix sort's temporary (a few MiB of histograms) on classification handles; a few KiB of block partials otherwise.
+ * fmx_group_evaluate_ex: the same over the feature shards of a loopback / RCCL group of ONE process -- the finished y-hat chunks of
+ * fmx_group_predict stay on the first shard's device (no prediction crosses to the host) and are reduced there against the first
+ * shard's targets; a one-handle group forwards.
+ * Refusals: FMX_E_ARG: NULL out, unknown link, flags != 0.  FMX_E_STATE: a slot never uploaded, a slot without targets (as
+ * fmx_evaluate).  FMX_E_UNSUPPORTED: a feature shard or communicator rank passed to fmx_evaluate_ex itself (as fmx_evaluate), more
+ * than 2^31 - 1 rows.  Rows are not weighted.
+ * Added without an ABI version change: a caller detects the feature by the symbol fmx_evaluate_ex. */
+#define FMX_LINK_LOGISTIC 0u   /* q = 1 / (1 + exp(-p)):  fm_learn_sgd::predict, classification (fm_learn_sgd.h:80-87) */
+#define FMX_LINK_PROBIT   1u   /* q = Phi(p):              the als / mcmc learners' cdf_gaussian */
+typedef struct fmx_eval_opts {
+  uint32_t link;            /* FMX_LINK_* */
+  uint32_t flags;           /* none defined: 0 */
+} fmx_eval_opts;
+typedef struct fmx_eval_ex {
+  uint64_t rows, nan_rows;      /* nan_rows: rows whose score is NaN */
+  uint64_t pos, neg;            /* classification: rows with target >= 0 / < 0 */
+  uint64_t correct;             /* classification: rows with (p >= 0) == (target >= 0); a NaN score is never correct */
+  uint64_t auc_num2;            /* the AUC numerator above, exact */
+  double   auc, logloss;        /* classification */
+  double   rmse, mae, accuracy; /* as fmx_eval, reduced in a fixed order */
+  double   device_seconds;      /* whole call */
+  double   rank_seconds;        /* sort + scans + rank-sum kernel only (0 when nothing was sorted) */
+  uint32_t flags;               /* FMX_EVAL_WSIDE as in fmx_eval */
+  uint32_t reserved;
+} fmx_eval_ex;
+/* opts may be NULL (= logistic) */
+int fmx_evaluate_ex(fmx_handle h, int slot, const fmx_eval_opts *opts, fmx_eval_ex *out);
+
 /* ---- fm_learn_sgd_element::learn, one epoch (fm_learn_sgd_element.h:56-67) -------------------- */
 int fmx_sgd_epoch(fmx_handle h, int slot, const fmx_sgd_opts *opts, fmx_epoch_stats *stats);
 /* On a handle that is one rank of a communicator (fmx_comm_init_rank, one process per GPU) this call is COLLECTIVE, every time: the
@@ -664,6 +715,8 @@ int fmx_group_upload_block_rows_ex(fmx_group g, int slot, const void *entries, c
 int fmx_group_sgd_epoch(fmx_group g, int slot, const fmx_sgd_opts *opts, fmx_epoch_stats *stats);
 int fmx_group_predict(fmx_group g, int slot, double *out);
 int fmx_group_evaluate(fmx_group g, int slot, fmx_eval *out);
+/* fmx_evaluate_ex over the shards of a group (see there) */
+int fmx_group_evaluate_ex(fmx_group g, int slot, const fmx_eval_opts *opts, fmx_eval_ex *out);
 
 /* ---- fm_learn_mcmc (ALS = MCMC without sampling, libfm.cpp:135-139) ---------------------------------
  * The learner keeps e(c) = y-hat(c) - target(c) and q_f(c) per training row (e_q_term, fm_learn_mcmc.h:46-49)

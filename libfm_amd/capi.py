@@ -21,6 +21,7 @@ FLAG_REJECT_UNSTABLE = 8
 FLAG_EVENT_SYNC = 16
 FLAG_KEEP_WSIDE = 32
 EVAL_WSIDE = 1
+LINK_LOGISTIC, LINK_PROBIT = 0, 1   # FMX_LINK_*: fmx_eval_opts::link
 STAT_BATCH_CUT, STAT_UNSTABLE = 1, 2
 STAT_WARN = 3   # FMX_STAT_WARN_MASK: the two bits that say something about the RULE; the bits above are how the epoch ran (include/fmx.h, ABI 7, 9)
 STAT_SCAN_PIT, STAT_SCAN_SERIAL, STAT_SCAN_FALLBACK, STAT_EVENT_SYNC, STAT_HANDOFF_TIMEOUT, STAT_SEQ_RUNS, STAT_SMALL_ONE = 4, 8, 16, 32, 64, 256, 512
@@ -78,6 +79,17 @@ class PlaceInfo(C.Structure):
 class Eval(C.Structure):
     _fields_ = [("rmse", C.c_double), ("mae", C.c_double), ("accuracy", C.c_double),
                 ("device_seconds", C.c_double), ("rows", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class EvalOpts(C.Structure):
+    _fields_ = [("link", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class EvalEx(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("nan_rows", C.c_uint64), ("pos", C.c_uint64), ("neg", C.c_uint64), ("correct", C.c_uint64),
+                ("auc_num2", C.c_uint64), ("auc", C.c_double), ("logloss", C.c_double), ("rmse", C.c_double), ("mae", C.c_double),
+                ("accuracy", C.c_double), ("device_seconds", C.c_double), ("rank_seconds", C.c_double),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class PairOpts(C.Structure):
@@ -182,6 +194,7 @@ SYMBOLS = [
     ("fmx_download_rows", C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("fmx_predict", C.c_int, [H, C.c_int, C.c_void_p]),
     ("fmx_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
+    ("fmx_evaluate_ex", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalEx)]),
     ("fmx_sgd_epoch", C.c_int, [H, C.c_int, C.POINTER(SgdOpts), C.POINTER(EpochStats)]),
     ("fmx_sgd_batch_info", C.c_int, [H, C.c_int, C.POINTER(SgdOpts), C.POINTER(BatchInfo)]),
     ("fmx_get_place_info", C.c_int, [H, C.POINTER(PlaceInfo)]),
@@ -206,6 +219,7 @@ SYMBOLS = [
     ("fmx_group_sgd_epoch", C.c_int, [H, C.c_int, C.POINTER(SgdOpts), C.POINTER(EpochStats)]),
     ("fmx_group_predict", C.c_int, [H, C.c_int, C.c_void_p]),
     ("fmx_group_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
+    ("fmx_group_evaluate_ex", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalEx)]),
     ("fmx_group_als_begin", C.c_int, [H, C.c_int]),
     ("fmx_group_als_moments", C.c_int, [H, C.c_void_p]),
     ("fmx_group_als_sweep", C.c_int, [H, C.POINTER(AlsOpts), C.POINTER(AlsStats)]),
@@ -416,6 +430,12 @@ class Handle:
     def evaluate(self, slot):
         ev = Eval()
         self._chk(self.lib.fmx_evaluate(self.h, slot, C.byref(ev)))
+        return ev
+
+    def evaluate_ex(self, slot, link=LINK_LOGISTIC):
+        """exact AUC, log loss and the counts behind them, reduced on the device (fmx_evaluate_ex)"""
+        opts, ev = EvalOpts(link, 0), EvalEx()
+        self._chk(self.lib.fmx_evaluate_ex(self.h, slot, C.byref(opts), C.byref(ev)))
         return ev
 
     def sgd_epoch(self, slot, mode, apply=APPLY_DEFAULT, batch=0, w0_chunk=0, flags=0, bias_lag=0):
@@ -758,6 +778,12 @@ class Group:
     def evaluate(self, slot):
         ev = Eval()
         self._chk(self.lib.fmx_group_evaluate(self.g, slot, C.byref(ev)))
+        return ev
+
+    def evaluate_ex(self, slot, link=LINK_LOGISTIC):
+        """Handle.evaluate_ex over the shards; the predictions stay on the first shard's device (fmx_group_evaluate_ex)"""
+        opts, ev = EvalOpts(link, 0), EvalEx()
+        self._chk(self.lib.fmx_group_evaluate_ex(self.g, slot, C.byref(opts), C.byref(ev)))
         return ev
 
     # ALS / MCMC over the shards ----------------------------------------------------------------

@@ -21,6 +21,9 @@ observed (query row of -train, candidate row) interactions of F with N negatives
 (fmx_pair_epoch_sampled); the test interactions name rows of -test.  -train_pairs / -test_pairs are not needed then.
 -neg_draws M (1 .. 16, default 1) trains every negative as the hardest of M accepted draws under the parameters at the start of
 the epoch; the #Iter= lines stay on uniform negatives.
+-metrics auc,logloss (-task c with sgd, sgda, als): after every iteration the exact AUC and / or the log loss of the train and
+test rows, reduced on the device (fmx_evaluate_ex), as "#Iter=  i\tauc: Train=..\tTest=.." lines on stderr and auc_train /
+auc_test / logloss_train / logloss_test columns of -rlog; stdout stays byte for byte what it is without the flag.
 """
 import os
 import sys
@@ -52,7 +55,8 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "topk": "results per query row (1 .. 1024); needs -candidates; not with -method mcmc",
          "topk_out": "filename for the top-K lists: one line per query, 'cand:score cand:score ...'",
          "queries": "filename of the query rows; default: the test rows",
-         "exclude": "filename of excluded pairs, one per line 'query_row cand_row'"}
+         "exclude": "filename of excluded pairs, one per line 'query_row cand_row'",
+         "metrics": "'auc,logloss': exact AUC / log loss of train and test per iteration on stderr; -task c with sgd, sgda, als"}
 
 
 def read_pairs(path, n_rows):
@@ -195,6 +199,17 @@ def _main(argv):
     for need in ("task", "train", "test"):
         if need not in a:
             raise ValueError("-%s is mandatory" % need)
+    metrics = tuple(split_list(a.get("metrics", "")))
+    if "metrics" in a:
+        for m in metrics:
+            if m not in L.EXTRA_METRICS:
+                raise ValueError("-metrics knows auc and logloss, not '%s'" % m)
+        if method in ("mcmc", "bpr"):
+            raise ValueError("-metrics is not supported with -method %s" % method +
+                             (": its prediction averages the draws, no single model scores it" if method == "mcmc" else
+                              ": the pairwise learner reports its own accuracy and loss"))
+        if a["task"] != "c":
+            raise ValueError("-metrics needs -task c: AUC and log loss are classification metrics")
 
     print("Loading train...\t")
     train = L.Data(*D.load(a["train"]))
@@ -328,6 +343,8 @@ def _main(argv):
     l.fm, l.num_iter, l.task = fm, num_iter, (0 if task == "r" else 1)
     l.min_target, l.max_target = min_t, max_t
     l.device = int(a.get("device", "-1"))
+    if metrics:
+        l.extra_metrics = metrics
     l.init()
     if implicit:
         print("Loading interactions...\t")

@@ -855,12 +855,10 @@ static int kept_chunk_partial(fmx_handle h, const Slot& s, uint64_t row0, uint32
   return FMX_OK;
 }
 
-// y-hat of every row of a slot over the shards (raw, like fmx_predict): partial sums -> exchange -> finish on shard 0
-int fmx_group_predict(fmx_group g, int slot, double* out) {
-  if (!g || !out) return FMX_E_ARG;
-  for (auto m : g->hs) if (!m) return gfail(g, FMX_E_STATE, "a member of the group was destroyed");
+// y-hat of every row of a slot over the shards (raw, like fmx_predict): partial sums -> exchange -> finish on shard 0, chunk by
+// chunk.  The finished chunks go to the host (out) or stay on the first shard's device (d_all, float [n_rows]: fmx_group_evaluate_ex)
+static int group_predict_chunks(fmx_group g, int slot, double* out, float* d_all) {
   fmx_handle cur = g->hs[0];
-  if (g->kind == GROUP_SINGLE) { GCHK(g, fmx_predict(cur, slot, out)); return FMX_OK; }
   const size_t n = g->hs.size();
   for (size_t i = 0; i < n; i++) { cur = g->hs[i]; GCHK(g, check_slot(cur, slot, false)); GCHK(g, lag_flush(cur)); }
   fmx_handle h0 = g->hs[0];
@@ -878,7 +876,7 @@ int fmx_group_predict(fmx_group g, int slot, double* out) {
   for (size_t i = 0; i < n; i++) { cur = g->hs[i]; GCHK(g, ensure_xbuf(cur, (size_t)tmp.size() * kp1)); }
   float* d_y = nullptr;
   HIPCHK(h0, hipSetDevice(h0->device));
-  HIPCHK(h0, fmx_dev_alloc(&d_y, tmp.size() * sizeof(float)));
+  if (!d_all) HIPCHK(h0, fmx_dev_alloc(&d_y, tmp.size() * sizeof(float)));
   int rc = FMX_OK;
   for (uint64_t r0 = 0; r0 < n_rows && rc == FMX_OK; r0 += chunk) {
     const uint32_t nb = (uint32_t)std::min<uint64_t>(chunk, n_rows - r0);
@@ -888,15 +886,23 @@ int fmx_group_predict(fmx_group g, int slot, double* out) {
     }
     if (rc == FMX_OK) rc = exchange_begin(g, 0, (size_t)nb * kp1);
     if (rc == FMX_OK) rc = exchange_end(g, 0);
-    if (rc == FMX_OK) rc = fmx_predict_finish(h0, nb, sum_of(g, 0, 0), d_y, h0->stream);
-    if (rc == FMX_OK && hipMemcpyAsync(tmp.data(), d_y, (size_t)nb * sizeof(float), hipMemcpyDeviceToHost, h0->stream) != hipSuccess) rc = FMX_E_HIP;
+    if (rc == FMX_OK) rc = fmx_predict_finish(h0, nb, sum_of(g, 0, 0), d_all ? d_all + r0 : d_y, h0->stream);
+    if (rc == FMX_OK && !d_all && hipMemcpyAsync(tmp.data(), d_y, (size_t)nb * sizeof(float), hipMemcpyDeviceToHost, h0->stream) != hipSuccess) rc = FMX_E_HIP;
     for (size_t i = 0; i < n && rc == FMX_OK; i++) { hipSetDevice(g->hs[i]->device); if (hipStreamSynchronize(g->hs[i]->stream) != hipSuccess) rc = FMX_E_HIP; }
-    if (rc == FMX_OK) for (uint32_t r = 0; r < nb; r++) out[r0 + r] = (double)tmp[r];
+    if (rc == FMX_OK && !d_all) for (uint32_t r = 0; r < nb; r++) out[r0 + r] = (double)tmp[r];
   }
   hipSetDevice(h0->device);
   fmx_dev_free(d_y);
   if (rc) { g->err = fmx_last_error(cur); return rc; }
   return FMX_OK;
+}
+
+int fmx_group_predict(fmx_group g, int slot, double* out) {
+  if (!g || !out) return FMX_E_ARG;
+  for (auto m : g->hs) if (!m) return gfail(g, FMX_E_STATE, "a member of the group was destroyed");
+  fmx_handle cur = g->hs[0];
+  if (g->kind == GROUP_SINGLE) { GCHK(g, fmx_predict(cur, slot, out)); return FMX_OK; }
+  return group_predict_chunks(g, slot, out, nullptr);
 }
 
 // fm_learn::evaluate (fm_learn.h:93-153) over the shards: predictions as above, metric on the host like the reference
@@ -926,6 +932,32 @@ int fmx_group_evaluate(fmx_group g, int slot, fmx_eval* out) {
   }
   out->rmse = std::sqrt(se / s.n_rows); out->mae = ae / s.n_rows; out->accuracy = nc / s.n_rows;
   return FMX_OK;
+}
+
+// fmx_evaluate_ex over the shards: the finished y-hat chunks stay on the first shard's device and are reduced there (fmx_eval.hip)
+int fmx_group_evaluate_ex(fmx_group g, int slot, const fmx_eval_opts* opts, fmx_eval_ex* out) {
+  static const char who[] = "fmx_group_evaluate_ex";
+  if (!g) return FMX_E_ARG;
+  for (auto m : g->hs) if (!m) return gfail(g, FMX_E_STATE, "a member of the group was destroyed");
+  fmx_handle h0 = g->hs[0];
+  fmx_handle cur = h0;
+  if (g->kind == GROUP_SINGLE) { GCHK(g, fmx_evaluate_ex(cur, slot, opts, out)); return FMX_OK; }
+  if (!out) return gfail(g, FMX_E_ARG, "%s: out is NULL", who);
+  uint32_t link;
+  GCHK(g, eval_ex_check_opts(cur, who, opts, &link));
+  GCHK(g, eval_ex_check_slot(cur, who, slot));
+  const Slot& s = h0->slots[slot];
+  eval_ex_empty(out);
+  if (s.n_rows == 0) return FMX_OK;
+  float* d_all = nullptr;
+  HIPCHK(h0, hipSetDevice(h0->device));
+  HIPCHK(h0, fmx_dev_alloc(&d_all, (size_t)s.n_rows * sizeof(float)));
+  int rc = (hipEventRecord(h0->ev0, h0->stream) == hipSuccess) ? FMX_OK : fail(h0, FMX_E_HIP, "%s: hipEventRecord failed", who);
+  if (rc == FMX_OK) rc = group_predict_chunks(g, slot, nullptr, d_all);
+  if (rc == FMX_OK) { hipSetDevice(h0->device); rc = eval_ex_scores(h0, s, d_all, 0, link, out); if (rc) g->err = fmx_last_error(h0); }
+  hipSetDevice(h0->device);
+  fmx_dev_free(d_all);
+  return rc;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // fmx_internal.h -- shared by the translation units of libfmx.so (fmx_core.hip, fmx_sgd.hip, fmx_als.hip, fmx_comm.hip, fmx_pair.hip, fmx_topk.hip,
-// fmx_pairneg.hip; fmx_io.hip needs none of it).
+// fmx_pairneg.hip, fmx_eval.hip; fmx_io.hip needs none of it).
 // The C-ABI is include/fmx.h; nothing declared here is exported.
 #pragma once
 #pragma GCC visibility push(default)      // the C-ABI is the only thing libfmx.so exports (-fvisibility=hidden)
@@ -265,6 +265,11 @@ constexpr size_t PREP_RAW_FLOATS = size_t(1) << 24;                      // prep
 int prep_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, int k0, float* raw, size_t raw_rows, int KM,
               float* S_out, float* scal, hipStream_t st);                // fmx_topk.hip: the [rows][KM] factor sums and scalars of section 11
 int lag_flush(fmx_handle h);                                             // fmx_sgd.hip
+// fmx_eval.hip: the argument checks, the empty result and the reduction of fmx_evaluate_ex, shared with fmx_group_evaluate_ex (fmx_comm.hip)
+int eval_ex_check_opts(fmx_handle h, const char* who, const fmx_eval_opts* opts, uint32_t* link);
+int eval_ex_check_slot(fmx_handle h, const char* who, int slot);
+void eval_ex_empty(fmx_eval_ex* out);
+int eval_ex_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, uint32_t link, fmx_eval_ex* out);
 int scan_error_check(fmx_handle h);                                      // fmx_sgd.hip: the device's error word after k_scan_pit launches (streams drained)
 uint32_t multi_group_size(const Slot& s, int KP);                        // fmx_sgd.hip: examples per wavefront of the short-row kernels (0: rows are long)
 bool streams_concurrent(fmx_handle h);                                   // fmx_sgd.hip: probed once per handle

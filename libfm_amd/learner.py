@@ -113,6 +113,25 @@ class FMModel:
             return False
 
 
+EXTRA_METRICS = ("auc", "logloss")
+
+
+def _log_extra_metrics(learner, i, train, test):
+    """learner.extra_metrics on a classification task: one stderr line per named metric (where the BPR learner puts its loss
+    lines) and <metric>_train / <metric>_test in the iteration's log row.  stdout is not touched."""
+    names = tuple(learner.extra_metrics)
+    for m in names:
+        if m not in EXTRA_METRICS:
+            raise ValueError("unknown metric %r (want auc, logloss)" % (m,))
+    if not names or learner.task != TASK_CLASSIFICATION:
+        return
+    tr, te = learner.evaluate_ex(train), learner.evaluate_ex(test)
+    for m in names:
+        a, b = getattr(tr, m), getattr(te, m)
+        print("#Iter=%3d\t%s: Train=%g\tTest=%g" % (i, m, a, b), file=sys.stderr)
+        learner.log[-1][m + "_train"], learner.log[-1][m + "_test"] = a, b
+
+
 class FMLearnSGD:
     """fm_learn_sgd_element on the GPU.
 
@@ -139,6 +158,7 @@ class FMLearnSGD:
         self.reject_unstable = True                             # an explicit batch the rule diverges at raises instead of training
         self.device = -1
         self.log = []                                           # one dict per iteration (rlog fields)
+        self.extra_metrics = ()                                 # classification: "auc" and / or "logloss" per iteration, on stderr and in log
         self.out = sys.stdout
         self._h = None
         self._slots = {}
@@ -185,6 +205,7 @@ class FMLearnSGD:
             rmse_test = self.evaluate(test)
             print("#Iter=%3d\tTrain=%g\tTest=%g" % (i, rmse_train, rmse_test), file=self.out)   # :71
             self.log.append({"rmse_train": rmse_train, "time_learn": stats.device_seconds})
+            _log_extra_metrics(self, i, train, test)
         self.sync_model()
 
     def sync_model(self):
@@ -195,6 +216,12 @@ class FMLearnSGD:
     def evaluate(self, data):
         ev = self._h.evaluate(self._slot(data))
         return ev.rmse if self.task == TASK_REGRESSION else ev.accuracy
+
+    EVAL_LINK = capi.LINK_LOGISTIC       # fm_learn_sgd::predict maps a classification score through the sigmoid (fm_learn_sgd.h:80-87)
+
+    def evaluate_ex(self, data):
+        """exact AUC, log loss and the counts behind them under the current parameters, reduced on the device (fmx_evaluate_ex)"""
+        return self._h.evaluate_ex(self._slot(data), self.EVAL_LINK)
 
     def predict_raw(self, data):
         """fm_learn::predict_case over the data set (fm_learn.h:63-65)."""
@@ -264,8 +291,10 @@ class FMLearnALS:
         self.pred_this = None          # fm_learn_mcmc.h:116
         self.pred_sum_all = None       # fm_learn_mcmc.h:114
         self.log = []
+        self.extra_metrics = ()        # classification: "auc" and / or "logloss" per iteration, on stderr and in log
         self._h = None                 # a capi.Handle, or the capi.Group of the shards
         self._shards = []
+        self._train = self._test = None   # the data sets of learn(): slots 0 and 1
 
     def init(self):
         fm = self.fm
@@ -300,6 +329,7 @@ class FMLearnALS:
         h = self._h
         train.upload(h, 0)
         test.upload(h, 1)
+        self._train, self._test = train, test
         self.pred_sum_all = np.zeros(test.num_cases)
         h.als_begin(0)
         for i in range(self.num_iter):
@@ -316,8 +346,16 @@ class FMLearnALS:
                 acc = float(np.mean(((self.pred_sum_all / (i + 1)) >= 0.5) == (test.target >= 0)))
                 print("#Iter=%3d\tTrain=%g\tTest=%g" % (i, st.train_metric, acc), file=self.out)
             self.log.append({"train": st.train_metric, "time_learn": st.device_seconds, "levels": st.levels})
+            _log_extra_metrics(self, i, train, test)
         h.als_end()
         self.fm.w0, self.fm.w, self.fm.v = h.get_params(self.fm.w, self.fm.v)
+
+    def evaluate_ex(self, data):
+        """exact AUC and log loss (probit link: this learner's probability is cdf_gaussian(y-hat)) of the train or test set of the
+        running learn() under the parameters of the last sweep (fmx_evaluate_ex / fmx_group_evaluate_ex)"""
+        if data is not self._train and data is not self._test:
+            raise ValueError("evaluate_ex: the data set is neither the train nor the test set of learn()")
+        return self._h.evaluate_ex(0 if data is self._train else 1, capi.LINK_PROBIT)
 
     TOPK_SLOTS = (2, 3)             # learn() keeps train and test in slots 0 and 1
 
@@ -370,7 +408,14 @@ class FMLearnMCMC(FMLearnALS):
         self.alpha_0 = self.gamma_0 = self.beta_0 = 1.0
         self.mu_0 = 0.0
 
+    def evaluate_ex(self, data):
+        raise NotImplementedError("evaluate_ex: the MCMC prediction is the average over the draws (pred_sum_all / num_iter); "
+                                  "no single device pass scores it")
+
     def learn(self, train, test):
+        if tuple(self.extra_metrics):
+            raise NotImplementedError("extra_metrics: the MCMC prediction is the average over the draws (pred_sum_all / num_iter); "
+                                      "no single device pass scores it")
         h = self._h
         rng = np.random.default_rng(self.seed)
         k, n, G = self.fm.num_factor, self.fm.num_attribute, h.G
@@ -599,5 +644,6 @@ class FMLearnSGDA(FMLearnSGD):
                 for f in range(self.fm.num_factor):
                     row["regv[%d,%d]" % (g, f)] = float(reg[g, 1 + f])
             self.log.append(row)
+            _log_extra_metrics(self, i, train, test)
         h.sgda_end()
         self.sync_model()
