@@ -480,6 +480,79 @@ typedef struct fmx_eval_ex {
 /* opts may be NULL (= logistic) */
 int fmx_evaluate_ex(fmx_handle h, int slot, const fmx_eval_opts *opts, fmx_eval_ex *out);
 
+/* ---- the averaged predictions of `-method mcmc`, kept on the device ----------------------------
+ * The prediction of fm_learn_mcmc_simultaneous is not that of one model but the running mean over the draws (pred_sum_all / (i + 1),
+ * fm_learn_mcmc_simultaneous.h:129-161, 213-264).  A posterior accumulator keeps the three vectors of that file for one slot on the
+ * device -- the last draw (pred_this), the sum over all draws (pred_sum_all) and the sum over the draws from burn_in on
+ * (pred_sum_all_but5) -- so that no prediction crosses to the host between the sweeps.
+ * fmx_post_begin creates the accumulator of a slot with both sums +0 (again = reset; opts NULL = {5, 0, 0}).
+ * fmx_post_accumulate scores the slot like fmx_evaluate_ex (one pass at the predict roofline, kept `-relation` blocks and the weight
+ * side stream included) and adds the draw.  With d the number of draws accumulated before the call and p_i the fp32 raw y-hat
+ * fmx_predict would return for row i now:
+ *   regression      this_i = (double)p_i;   v_i = max(min_target, min(max_target, (double)p_i)) with the config's doubles (:132-133);
+ *                   a NaN p_i stays NaN (numpy's minimum / maximum, not std::min)
+ *   classification  v_i = this_i = 0.5 + 0.5 ref_erf(0.707106781 (double)p_i): the reference's cdf_gaussian with its five-term erf
+ *                   polynomial (random.h:45-67), not erfc
+ *   sum_all_i += v_i;   sum_late_i += v_i when d >= burn_in.   fp64, one add per row per draw: the order is the draw order.
+ * Means: mean = sum * (1.0 / count) -- a product with the reciprocal, as :278 and :296 have it, not a division -- with
+ *   count = draws (FMX_POST_ALL) or late_draws (FMX_POST_LATE); FMX_POST_THIS is this_i itself.
+ *   FMX_POST_LATE with late_draws == 0: rows = 0 and every metric NaN (the reference's 1.0 / (i - 5 + 1) in unsigned arithmetic is
+ *   not reproduced).
+ * Metrics of the three vectors over the rows [0, eval_rows) (fmx_post_stats::m, the reference's _evaluate / _evaluate_class):
+ *   regression      rmse = sqrt(mean (c_i - target_i)^2), mae = mean |c_i - target_i| with c_i the mean clamped again (:279-283)
+ *   classification  correct counts (m_i >= 0.5 && target_i > 0) || (m_i < 0.5 && target_i < 0) (:297), accuracy = correct / rows;
+ *                   ll_ref = -(1 / rows) sum_i [ t log10(q) + (1 - t) log10(1 - q) ], t = (target_i + 1) / 2, q = m_i clamped to
+ *                   [0.01, 0.99] (:300-304: the reference's Test(ll))
+ *   a NaN mean counts in nan_rows, is never correct and makes rmse / mae / ll_ref NaN; the counts stay right.  The metrics of the
+ *   other task are 0, as in fmx_eval_ex; with rows = 0 (an empty slot, FMX_POST_LATE before its first draw) every double is NaN.
+ * fmx_post_evaluate_ex fills fmx_eval_ex for one of the three vectors over the rows [0, eval_rows): rows, nan_rows, pos / neg
+ *   (target >= 0 / < 0), correct / accuracy by the rule above, rmse / mae on regression handles only, and on classification handles
+ *   logloss = (1 / rows) sum_i ( target_i >= 0 ? -ln m_i : -ln(1 - m_i) )   natural log, unclamped: +inf where the mean is 0 or 1 on
+ *             the wrong side; only the term of the row's own class is taken, so 0 * ln 0 never arises
+ *   auc_num2 = the integer of fmx_evaluate_ex with fp64 comparisons of the means (64-bit sort keys: the means are sums of values in
+ *             [0, 1] started from +0, so their bit pattern orders them; a mean below +0 is refused with FMX_E_STATE, never clamped)
+ *   auc = logloss = NaN on regression handles and with NaN means; before the first draw of the vector: rows = 0 and the empty
+ *   result of fmx_evaluate_ex.  rank_seconds / device_seconds as there; flags 0.
+ * fmx_post_get copies out[n_rows]: the SUM (FMX_POST_ALL, FMX_POST_LATE; *draws = its count) or this_i (FMX_POST_THIS; *draws = 1
+ *   after the first draw, else 0).  out or draws may be NULL.
+ * Every fp64 sum of the metrics runs in the fixed order of fmx_evaluate_ex on the same grid: two identical call sequences give
+ * bit-identical structs apart from the times.
+ * State: at most one accumulator per slot; fmx_upload_rows and its siblings and fmx_free_rows drop it (as interactions are
+ * dropped), fmx_destroy frees it.  Resident: 20 bytes per row (8 + 8 the sums, 4 the fp32 last draw; this_i is recomputed from it).
+ * fmx_post_evaluate_ex takes fmx_evaluate_ex's 24 bytes per row inside the call.  The calls work while an ALS / MCMC session is open
+ * on another slot: train on slot 0, accumulate slot 1.
+ * fmx_group_post_*: the same over the feature shards of a loopback / RCCL group of ONE process; the state lives on the first
+ * shard's device, where fmx_group_predict's finished y-hat chunks are accumulated.  A one-handle group forwards.
+ * Refusals: FMX_E_ARG: which > 2, flags != 0, eval_rows > n_rows, NULL out of _evaluate_ex.  FMX_E_STATE: a slot never uploaded or
+ * without targets; _accumulate / _evaluate_ex / _get / _end without _begin.  FMX_E_UNSUPPORTED: a feature shard or communicator rank
+ * passed to the per-handle calls, more than 2^31 - 1 rows.  An empty slot: FMX_OK with zero rows.  Rows are not weighted.
+ * Added without an ABI version change: a caller detects the feature by the symbol fmx_post_begin. */
+#define FMX_POST_THIS 0u   /* the last accumulated draw             (pred_this) */
+#define FMX_POST_ALL  1u   /* mean over all accumulated draws       (pred_sum_all * 1 / draws) */
+#define FMX_POST_LATE 2u   /* mean over the draws d >= burn_in      (pred_sum_all_but5, burn_in = 5) */
+typedef struct fmx_post_opts {
+  uint32_t burn_in;         /* reference: 5 */
+  uint32_t eval_rows;       /* the metrics cover the rows [0, eval_rows); 0 = all (num_eval_cases) */
+  uint32_t flags;           /* none defined: 0 */
+  uint32_t reserved;
+} fmx_post_opts;
+typedef struct fmx_post_metric {
+  uint64_t rows, nan_rows, correct;
+  double   rmse, mae;           /* regression (:272-289) */
+  double   accuracy, ll_ref;    /* classification (:291-309) */
+} fmx_post_metric;
+typedef struct fmx_post_stats {
+  uint64_t draws, late_draws;   /* after this call */
+  fmx_post_metric m[3];         /* indexed by FMX_POST_* */
+  double   device_seconds;
+} fmx_post_stats;
+int fmx_post_begin(fmx_handle h, int slot, const fmx_post_opts *opts);
+/* out may be NULL */
+int fmx_post_accumulate(fmx_handle h, int slot, fmx_post_stats *out);
+int fmx_post_evaluate_ex(fmx_handle h, int slot, uint32_t which, fmx_eval_ex *out);
+int fmx_post_get(fmx_handle h, int slot, uint32_t which, double *out, uint64_t *draws);
+int fmx_post_end(fmx_handle h, int slot);
+
 /* ---- fm_learn_sgd_element::learn, one epoch (fm_learn_sgd_element.h:56-67) -------------------- */
 int fmx_sgd_epoch(fmx_handle h, int slot, const fmx_sgd_opts *opts, fmx_epoch_stats *stats);
 /* On a handle that is one rank of a communicator (fmx_comm_init_rank, one process per GPU) this call is COLLECTIVE, every time: the
@@ -717,6 +790,12 @@ int fmx_group_predict(fmx_group g, int slot, double *out);
 int fmx_group_evaluate(fmx_group g, int slot, fmx_eval *out);
 /* fmx_evaluate_ex over the shards of a group (see there) */
 int fmx_group_evaluate_ex(fmx_group g, int slot, const fmx_eval_opts *opts, fmx_eval_ex *out);
+/* fmx_post_* over the shards of a group (see there) */
+int fmx_group_post_begin(fmx_group g, int slot, const fmx_post_opts *opts);
+int fmx_group_post_accumulate(fmx_group g, int slot, fmx_post_stats *out);
+int fmx_group_post_evaluate_ex(fmx_group g, int slot, uint32_t which, fmx_eval_ex *out);
+int fmx_group_post_get(fmx_group g, int slot, uint32_t which, double *out, uint64_t *draws);
+int fmx_group_post_end(fmx_group g, int slot);
 
 /* ---- fm_learn_mcmc (ALS = MCMC without sampling, libfm.cpp:135-139) ---------------------------------
  * The learner keeps e(c) = y-hat(c) - target(c) and q_f(c) per training row (e_q_term, fm_learn_mcmc.h:46-49)

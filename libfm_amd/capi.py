@@ -92,6 +92,22 @@ class EvalEx(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+POST_THIS, POST_ALL, POST_LATE = 0, 1, 2   # FMX_POST_*: the last draw, the mean over all draws, the mean over the draws from burn_in on
+
+
+class PostOpts(C.Structure):
+    _fields_ = [("burn_in", C.c_uint32), ("eval_rows", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PostMetric(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("nan_rows", C.c_uint64), ("correct", C.c_uint64), ("rmse", C.c_double), ("mae", C.c_double),
+                ("accuracy", C.c_double), ("ll_ref", C.c_double)]
+
+
+class PostStats(C.Structure):
+    _fields_ = [("draws", C.c_uint64), ("late_draws", C.c_uint64), ("m", PostMetric * 3), ("device_seconds", C.c_double)]
+
+
 class PairOpts(C.Structure):
     _fields_ = [("mode", C.c_int32), ("batch", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -195,6 +211,11 @@ SYMBOLS = [
     ("fmx_predict", C.c_int, [H, C.c_int, C.c_void_p]),
     ("fmx_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
     ("fmx_evaluate_ex", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalEx)]),
+    ("fmx_post_begin", C.c_int, [H, C.c_int, C.POINTER(PostOpts)]),
+    ("fmx_post_accumulate", C.c_int, [H, C.c_int, C.POINTER(PostStats)]),
+    ("fmx_post_evaluate_ex", C.c_int, [H, C.c_int, C.c_uint32, C.POINTER(EvalEx)]),
+    ("fmx_post_get", C.c_int, [H, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("fmx_post_end", C.c_int, [H, C.c_int]),
     ("fmx_sgd_epoch", C.c_int, [H, C.c_int, C.POINTER(SgdOpts), C.POINTER(EpochStats)]),
     ("fmx_sgd_batch_info", C.c_int, [H, C.c_int, C.POINTER(SgdOpts), C.POINTER(BatchInfo)]),
     ("fmx_get_place_info", C.c_int, [H, C.POINTER(PlaceInfo)]),
@@ -220,6 +241,11 @@ SYMBOLS = [
     ("fmx_group_predict", C.c_int, [H, C.c_int, C.c_void_p]),
     ("fmx_group_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
     ("fmx_group_evaluate_ex", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalEx)]),
+    ("fmx_group_post_begin", C.c_int, [H, C.c_int, C.POINTER(PostOpts)]),
+    ("fmx_group_post_accumulate", C.c_int, [H, C.c_int, C.POINTER(PostStats)]),
+    ("fmx_group_post_evaluate_ex", C.c_int, [H, C.c_int, C.c_uint32, C.POINTER(EvalEx)]),
+    ("fmx_group_post_get", C.c_int, [H, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("fmx_group_post_end", C.c_int, [H, C.c_int]),
     ("fmx_group_als_begin", C.c_int, [H, C.c_int]),
     ("fmx_group_als_moments", C.c_int, [H, C.c_void_p]),
     ("fmx_group_als_sweep", C.c_int, [H, C.POINTER(AlsOpts), C.POINTER(AlsStats)]),
@@ -437,6 +463,31 @@ class Handle:
         opts, ev = EvalOpts(link, 0), EvalEx()
         self._chk(self.lib.fmx_evaluate_ex(self.h, slot, C.byref(opts), C.byref(ev)))
         return ev
+
+    # the posterior accumulator of a slot (fmx_post_*): MCMC's averaged predictions on the device
+    def post_begin(self, slot, burn_in=5, eval_rows=0):
+        opts = PostOpts(int(burn_in), int(eval_rows), 0, 0)
+        self._chk(self.lib.fmx_post_begin(self.h, slot, C.byref(opts)))
+
+    def post_accumulate(self, slot):
+        """add the draw of the current parameters; the reference's metrics of the three vectors (PostStats.m[POST_*])"""
+        st = PostStats()
+        self._chk(self.lib.fmx_post_accumulate(self.h, slot, C.byref(st)))
+        return st
+
+    def post_evaluate_ex(self, slot, which=POST_ALL):
+        ev = EvalEx()
+        self._chk(self.lib.fmx_post_evaluate_ex(self.h, slot, int(which), C.byref(ev)))
+        return ev
+
+    def post_get(self, slot, which, n_rows):
+        """(the sum over the draws -- or the last draw itself for POST_THIS -- as float64 [n_rows], the number of draws in it)"""
+        out, draws = np.zeros(n_rows, dtype=np.float64), C.c_uint64(0)
+        self._chk(self.lib.fmx_post_get(self.h, slot, int(which), _ptr(out), C.byref(draws)))
+        return out, int(draws.value)
+
+    def post_end(self, slot):
+        self._chk(self.lib.fmx_post_end(self.h, slot))
 
     def sgd_epoch(self, slot, mode, apply=APPLY_DEFAULT, batch=0, w0_chunk=0, flags=0, bias_lag=0):
         opts = SgdOpts(mode, apply, batch, w0_chunk, flags, bias_lag)
@@ -785,6 +836,31 @@ class Group:
         opts, ev = EvalOpts(link, 0), EvalEx()
         self._chk(self.lib.fmx_group_evaluate_ex(self.g, slot, C.byref(opts), C.byref(ev)))
         return ev
+
+    # the posterior accumulator of a slot (fmx_post_*): MCMC's averaged predictions on the device
+    def post_begin(self, slot, burn_in=5, eval_rows=0):
+        opts = PostOpts(int(burn_in), int(eval_rows), 0, 0)
+        self._chk(self.lib.fmx_group_post_begin(self.g, slot, C.byref(opts)))
+
+    def post_accumulate(self, slot):
+        """add the draw of the current parameters; the reference's metrics of the three vectors (PostStats.m[POST_*])"""
+        st = PostStats()
+        self._chk(self.lib.fmx_group_post_accumulate(self.g, slot, C.byref(st)))
+        return st
+
+    def post_evaluate_ex(self, slot, which=POST_ALL):
+        ev = EvalEx()
+        self._chk(self.lib.fmx_group_post_evaluate_ex(self.g, slot, int(which), C.byref(ev)))
+        return ev
+
+    def post_get(self, slot, which, n_rows):
+        """(the sum over the draws -- or the last draw itself for POST_THIS -- as float64 [n_rows], the number of draws in it)"""
+        out, draws = np.zeros(n_rows, dtype=np.float64), C.c_uint64(0)
+        self._chk(self.lib.fmx_group_post_get(self.g, slot, int(which), _ptr(out), C.byref(draws)))
+        return out, int(draws.value)
+
+    def post_end(self, slot):
+        self._chk(self.lib.fmx_group_post_end(self.g, slot))
 
     # ALS / MCMC over the shards ----------------------------------------------------------------
     def als_begin(self, train_slot):

@@ -24,6 +24,9 @@ the epoch; the #Iter= lines stay on uniform negatives.
 -metrics auc,logloss (-task c with sgd, sgda, als): after every iteration the exact AUC and / or the log loss of the train and
 test rows, reduced on the device (fmx_evaluate_ex), as "#Iter=  i\tauc: Train=..\tTest=.." lines on stderr and auc_train /
 auc_test / logloss_train / logloss_test columns of -rlog; stdout stays byte for byte what it is without the flag.
+-device_average 1 (als, mcmc): the test predictions and their running sums stay on the device (fmx_post_accumulate); the #Iter=
+lines gain the reference's Test(ll) column on -task c, -rlog its rmse_mcmc_* / acc_mcmc_* / ll_mcmc_* columns, and -metrics then
+scores the averaged test prediction ("#Iter=  i\tauc: Test=.." on stderr, auc_test / logloss_test) -- with -method mcmc too.
 """
 import os
 import sys
@@ -56,7 +59,9 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "topk_out": "filename for the top-K lists: one line per query, 'cand:score cand:score ...'",
          "queries": "filename of the query rows; default: the test rows",
          "exclude": "filename of excluded pairs, one per line 'query_row cand_row'",
-         "metrics": "'auc,logloss': exact AUC / log loss of train and test per iteration on stderr; -task c with sgd, sgda, als"}
+         "metrics": "'auc,logloss': exact AUC / log loss of train and test per iteration on stderr; -task c with sgd, sgda, als"
+                    " (mcmc: of the averaged test prediction, with -device_average 1)",
+         "device_average": "als, mcmc: 1 = keep the test predictions and their running mean on the device; default=0"}
 
 
 def read_pairs(path, n_rows):
@@ -199,12 +204,18 @@ def _main(argv):
     for need in ("task", "train", "test"):
         if need not in a:
             raise ValueError("-%s is mandatory" % need)
+    dev_avg = a.get("device_average", "0")
+    if dev_avg not in ("0", "1"):
+        raise ValueError("-device_average takes 0 or 1")
+    dev_avg = dev_avg == "1"
+    if dev_avg and method not in ("als", "mcmc"):
+        raise ValueError("-device_average belongs to -method als and mcmc")
     metrics = tuple(split_list(a.get("metrics", "")))
     if "metrics" in a:
         for m in metrics:
             if m not in L.EXTRA_METRICS:
                 raise ValueError("-metrics knows auc and logloss, not '%s'" % m)
-        if method in ("mcmc", "bpr"):
+        if method == "bpr" or (method == "mcmc" and not dev_avg):
             raise ValueError("-metrics is not supported with -method %s" % method +
                              (": its prediction averages the draws, no single model scores it" if method == "mcmc" else
                               ": the pairwise learner reports its own accuracy and loss"))
@@ -345,6 +356,8 @@ def _main(argv):
     l.device = int(a.get("device", "-1"))
     if metrics:
         l.extra_metrics = metrics
+    if dev_avg:
+        l.device_average = True
     l.init()
     if implicit:
         print("Loading interactions...\t")

@@ -960,4 +960,59 @@ int fmx_group_evaluate_ex(fmx_group g, int slot, const fmx_eval_opts* opts, fmx_
   return rc;
 }
 
+// fmx_post_* over the shards (fmx_post.hip): the accumulator lives on the first shard's slot; only _accumulate needs the other
+// shards, for the finished y-hat chunks, which stay on the first shard's device like fmx_group_evaluate_ex's
+#define GROUP_POST_HEAD(who_)                                                                        \
+  static const char who[] = who_;                                                                    \
+  if (!g) return FMX_E_ARG;                                                                          \
+  for (auto m : g->hs) if (!m) return gfail(g, FMX_E_STATE, "a member of the group was destroyed"); \
+  fmx_handle h0 = g->hs[0];                                                                          \
+  fmx_handle cur = h0;                                                                               \
+  (void)who; (void)cur
+
+int fmx_group_post_begin(fmx_group g, int slot, const fmx_post_opts* opts) {
+  GROUP_POST_HEAD("fmx_group_post_begin");
+  if (g->kind == GROUP_SINGLE) { GCHK(g, fmx_post_begin(cur, slot, opts)); return FMX_OK; }
+  GCHK(g, post_begin_impl(cur, who, slot, opts));
+  return FMX_OK;
+}
+
+int fmx_group_post_accumulate(fmx_group g, int slot, fmx_post_stats* out) {
+  GROUP_POST_HEAD("fmx_group_post_accumulate");
+  if (g->kind == GROUP_SINGLE) { GCHK(g, fmx_post_accumulate(cur, slot, out)); return FMX_OK; }
+  GCHK(g, post_check(cur, who, slot, true));
+  Slot& s = h0->slots[slot];
+  if (s.n_rows == 0) { GCHK(g, post_accum_scores(cur, s, nullptr, 0, out)); return FMX_OK; }
+  float* d_all = nullptr;
+  HIPCHK(h0, hipSetDevice(h0->device));
+  HIPCHK(h0, fmx_dev_alloc(&d_all, (size_t)s.n_rows * sizeof(float)));
+  int rc = (hipEventRecord(h0->ev0, h0->stream) == hipSuccess) ? FMX_OK : fail(h0, FMX_E_HIP, "%s: hipEventRecord failed", who);
+  if (rc == FMX_OK) rc = group_predict_chunks(g, slot, nullptr, d_all);
+  if (rc == FMX_OK) { hipSetDevice(h0->device); rc = post_accum_scores(h0, s, d_all, 0, out); if (rc) g->err = fmx_last_error(h0); }
+  hipSetDevice(h0->device);
+  fmx_dev_free(d_all);
+  return rc;
+}
+
+int fmx_group_post_evaluate_ex(fmx_group g, int slot, uint32_t which, fmx_eval_ex* out) {
+  GROUP_POST_HEAD("fmx_group_post_evaluate_ex");
+  if (g->kind == GROUP_SINGLE) { GCHK(g, fmx_post_evaluate_ex(cur, slot, which, out)); return FMX_OK; }
+  GCHK(g, post_evaluate_impl(cur, who, slot, which, out));
+  return FMX_OK;
+}
+
+int fmx_group_post_get(fmx_group g, int slot, uint32_t which, double* out, uint64_t* draws) {
+  GROUP_POST_HEAD("fmx_group_post_get");
+  if (g->kind == GROUP_SINGLE) { GCHK(g, fmx_post_get(cur, slot, which, out, draws)); return FMX_OK; }
+  GCHK(g, post_get_impl(cur, who, slot, which, out, draws));
+  return FMX_OK;
+}
+
+int fmx_group_post_end(fmx_group g, int slot) {
+  GROUP_POST_HEAD("fmx_group_post_end");
+  if (g->kind == GROUP_SINGLE) { GCHK(g, fmx_post_end(cur, slot)); return FMX_OK; }
+  GCHK(g, post_end_impl(cur, who, slot));
+  return FMX_OK;
+}
+
 }  // extern "C"

@@ -131,6 +131,7 @@ void free_slot(Slot& s) {
   free_segments(s);
   free_pairs(s);
   free_interactions(s);
+  free_post(s);
   if (s.ent) fmx_dev_free(s.ent);
   if (s.row_ptr) fmx_dev_free(s.row_ptr);
   if (s.target) fmx_dev_free(s.target);

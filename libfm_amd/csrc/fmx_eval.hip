@@ -8,15 +8,21 @@
 
 namespace {
 
-// everything the call takes from the device: freed on every path out of eval_ex_scores
+// the block partials of the call: freed on every path out of eval_ex_scores
 struct EvalScratch {
   void* part = nullptr;                     // block partials + results
-  unsigned long long* keys[2] = {nullptr, nullptr};
+  unsigned long long* keys = nullptr;
+  ~EvalScratch() { fmx_dev_free(part); fmx_dev_free(keys); }
+};
+
+// everything the rank pipeline takes from the device: freed on every path out of eval_ex_rank
+struct RankScratch {
+  unsigned long long* keys1 = nullptr;      // the sort's second buffer
   uint32_t* negbefore = nullptr; uint32_t* runhead = nullptr;
   void* tmp = nullptr;                      // the larger of the sort's and the scans' temporaries
   hipEvent_t ev[2] = {nullptr, nullptr};
-  ~EvalScratch() {
-    fmx_dev_free(part); fmx_dev_free(keys[0]); fmx_dev_free(keys[1]); fmx_dev_free(negbefore); fmx_dev_free(runhead); fmx_dev_free(tmp);
+  ~RankScratch() {
+    fmx_dev_free(keys1); fmx_dev_free(negbefore); fmx_dev_free(runhead); fmx_dev_free(tmp);
     for (auto e : ev) if (e) hipEventDestroy(e);
   }
 };
@@ -45,6 +51,47 @@ void eval_ex_empty(fmx_eval_ex* out) {
   out->auc = out->logloss = std::numeric_limits<double>::quiet_NaN();
 }
 
+// The rank pipeline of the exact AUC: n keys of key_bits bits on h's device -- the label in bit 0, an order-preserving image of the
+// score above it -- are sorted (one radix sort; `keys` is one of its two buffers and is overwritten), scanned twice and reduced by
+// k_evalx_ranksum into *d_num2, a device word the caller has zeroed on h->stream.  Records h->ev1 after the last kernel and
+// returns with the stream drained.  n >= 1.
+int eval_ex_rank(fmx_handle h, unsigned long long* keys, uint32_t n, int key_bits, unsigned long long* d_num2, uint64_t* num2,
+                 double* rank_seconds) {
+  RankScratch sc;
+  HIPCHK(h, fmx_dev_alloc(&sc.keys1, (size_t)n * 8));
+  HIPCHK(h, fmx_dev_alloc(&sc.negbefore, (size_t)n * 4));
+  HIPCHK(h, fmx_dev_alloc(&sc.runhead, (size_t)n * 4));
+  for (auto& e : sc.ev) HIPCHK(h, hipEventCreate(&e));
+  hipcub::DoubleBuffer<unsigned long long> db(keys, sc.keys1);
+  typedef hipcub::TransformInputIterator<uint32_t, EvalxIsNeg, const unsigned long long*> NegIt;
+  typedef hipcub::TransformInputIterator<uint32_t, EvalxHead, hipcub::CountingInputIterator<uint32_t>> HeadIt;
+  size_t b_sort = 0, b_sum = 0, b_max = 0;
+  HIPCHK(h, hipcub::DeviceRadixSort::SortKeys(nullptr, b_sort, db, (int)n, 0, key_bits, h->stream));
+  HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, b_sum, NegIt(keys, EvalxIsNeg()), sc.negbefore, (int)n, h->stream));
+  HIPCHK(h, hipcub::DeviceScan::InclusiveScan(nullptr, b_max, HeadIt(hipcub::CountingInputIterator<uint32_t>(0), EvalxHead{keys}),
+                                              sc.runhead, hipcub::Max(), (int)n, h->stream));
+  size_t b_tmp = std::max(b_sort, std::max(b_sum, b_max));
+  HIPCHK(h, fmx_dev_alloc(&sc.tmp, std::max<size_t>(b_tmp, 16)));
+  HIPCHK(h, hipEventRecord(sc.ev[0], h->stream));
+  HIPCHK(h, hipcub::DeviceRadixSort::SortKeys(sc.tmp, b_tmp, db, (int)n, 0, key_bits, h->stream));
+  const unsigned long long* ks = db.Current();
+  HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(sc.tmp, b_tmp, NegIt(ks, EvalxIsNeg()), sc.negbefore, (int)n, h->stream));
+  HIPCHK(h, hipcub::DeviceScan::InclusiveScan(sc.tmp, b_tmp, HeadIt(hipcub::CountingInputIterator<uint32_t>(0), EvalxHead{ks}),
+                                              sc.runhead, hipcub::Max(), (int)n, h->stream));
+  hipLaunchKernelGGL(k_evalx_ranksum, dim3(evalx_grid(n)), dim3(256), 0, h->stream, ks, (const uint32_t*)sc.negbefore, (const uint32_t*)sc.runhead, n, d_num2);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(sc.ev[1], h->stream));
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  unsigned long long got = 0;
+  HIPCHK(h, hipMemcpyAsync(&got, d_num2, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float rms = 0;
+  HIPCHK(h, hipEventElapsedTime(&rms, sc.ev[0], sc.ev[1]));
+  *rank_seconds = rms * 1e-3;
+  *num2 = got;
+  return FMX_OK;
+}
+
 // The reduction over n = s.n_rows scores that are already on h's device, on h->stream: score[e] is `rest` (y-hat - w0, add_w0 = 1) or
 // the finished y-hat (add_w0 = 0); the targets are the slot's.  The caller has recorded h->ev0 where the call's device work began
 // and fills out->flags.  n >= 1.
@@ -59,9 +106,9 @@ int eval_ex_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, 
   unsigned long long* cpart = (unsigned long long*)sc.part + (size_t)nblk * 3;
   double* dres = (double*)sc.part + (size_t)nblk * 6;
   unsigned long long* cres = (unsigned long long*)sc.part + (size_t)nblk * 6 + 3;
-  if (cls) HIPCHK(h, fmx_dev_alloc(&sc.keys[0], (size_t)n * 8));
+  if (cls) HIPCHK(h, fmx_dev_alloc(&sc.keys, (size_t)n * 8));
   hipLaunchKernelGGL(k_evalx_score, dim3(nblk), dim3(256), 0, h->stream, score, (const float*)s.target, n, make_hyper(h->cfg), add_w0,
-                     (const double*)h->w0, link, dpart, cpart, sc.keys[0]);
+                     (const double*)h->w0, link, dpart, cpart, sc.keys);
   hipLaunchKernelGGL(k_evalx_final, dim3(1), dim3(64), 0, h->stream, (const double*)dpart, (const unsigned long long*)cpart, nblk, dres, cres);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemsetAsync(cres + 3, 0, 8, h->stream));
@@ -81,36 +128,8 @@ int eval_ex_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, 
     if (nan_rows == 0) out->logloss = res.d[2] / n;
   }
   if (cls && nan_rows == 0 && out->pos != 0 && out->neg != 0) {      // (one class only: the numerator is 0 and the AUC NaN without a sort)
-    HIPCHK(h, fmx_dev_alloc(&sc.keys[1], (size_t)n * 8));
-    HIPCHK(h, fmx_dev_alloc(&sc.negbefore, (size_t)n * 4));
-    HIPCHK(h, fmx_dev_alloc(&sc.runhead, (size_t)n * 4));
-    for (auto& e : sc.ev) HIPCHK(h, hipEventCreate(&e));
-    hipcub::DoubleBuffer<unsigned long long> db(sc.keys[0], sc.keys[1]);
-    typedef hipcub::TransformInputIterator<uint32_t, EvalxIsNeg, const unsigned long long*> NegIt;
-    typedef hipcub::TransformInputIterator<uint32_t, EvalxHead, hipcub::CountingInputIterator<uint32_t>> HeadIt;
-    size_t b_sort = 0, b_sum = 0, b_max = 0;
-    HIPCHK(h, hipcub::DeviceRadixSort::SortKeys(nullptr, b_sort, db, (int)n, 0, EVALX_KEY_BITS, h->stream));
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, b_sum, NegIt(sc.keys[0], EvalxIsNeg()), sc.negbefore, (int)n, h->stream));
-    HIPCHK(h, hipcub::DeviceScan::InclusiveScan(nullptr, b_max, HeadIt(hipcub::CountingInputIterator<uint32_t>(0), EvalxHead{sc.keys[0]}),
-                                                sc.runhead, hipcub::Max(), (int)n, h->stream));
-    size_t b_tmp = std::max(b_sort, std::max(b_sum, b_max));
-    HIPCHK(h, fmx_dev_alloc(&sc.tmp, std::max<size_t>(b_tmp, 16)));
-    HIPCHK(h, hipEventRecord(sc.ev[0], h->stream));
-    HIPCHK(h, hipcub::DeviceRadixSort::SortKeys(sc.tmp, b_tmp, db, (int)n, 0, EVALX_KEY_BITS, h->stream));
-    const unsigned long long* ks = db.Current();
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(sc.tmp, b_tmp, NegIt(ks, EvalxIsNeg()), sc.negbefore, (int)n, h->stream));
-    HIPCHK(h, hipcub::DeviceScan::InclusiveScan(sc.tmp, b_tmp, HeadIt(hipcub::CountingInputIterator<uint32_t>(0), EvalxHead{ks}),
-                                                sc.runhead, hipcub::Max(), (int)n, h->stream));
-    hipLaunchKernelGGL(k_evalx_ranksum, dim3(nblk), dim3(256), 0, h->stream, ks, (const uint32_t*)sc.negbefore, (const uint32_t*)sc.runhead, n, cres + 3);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(sc.ev[1], h->stream));
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&res.c[3], cres + 3, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float rms = 0;
-    HIPCHK(h, hipEventElapsedTime(&rms, sc.ev[0], sc.ev[1]));
-    out->rank_seconds = rms * 1e-3;
-    out->auc_num2 = res.c[3];
+    const int rc = eval_ex_rank(h, sc.keys, n, EVALX_KEY_BITS, cres + 3, &out->auc_num2, &out->rank_seconds);
+    if (rc) return rc;
     out->auc = (double)out->auc_num2 / (2.0 * (double)out->pos * (double)out->neg);
   } else {
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));

@@ -1,5 +1,5 @@
 // fmx_internal.h -- shared by the translation units of libfmx.so (fmx_core.hip, fmx_sgd.hip, fmx_als.hip, fmx_comm.hip, fmx_pair.hip, fmx_topk.hip,
-// fmx_pairneg.hip, fmx_eval.hip; fmx_io.hip needs none of it).
+// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip; fmx_io.hip needs none of it).
 // The C-ABI is include/fmx.h; nothing declared here is exported.
 #pragma once
 #pragma GCC visibility push(default)      // the C-ABI is the only thing libfmx.so exports (-fvisibility=hidden)
@@ -82,6 +82,8 @@ struct Slot {
   std::vector<uint32_t> pair_batch_seg;   // [n_batches + 1] first segment of every batch
   // interactions (fmx_upload_interactions, fmx_pairneg.hip): this slot's rows are the queries, another slot's the candidates
   struct PairNeg* pneg = nullptr;
+  // posterior accumulator (fmx_post_begin, fmx_post.hip); on a group it lives on the first shard's slot
+  struct PostAcc* post = nullptr;
 };
 void free_pairs(Slot& s);                                                // fmx_pair.hip
 void free_interactions(Slot& s);                                         // fmx_pairneg.hip
@@ -270,6 +272,25 @@ int eval_ex_check_opts(fmx_handle h, const char* who, const fmx_eval_opts* opts,
 int eval_ex_check_slot(fmx_handle h, const char* who, int slot);
 void eval_ex_empty(fmx_eval_ex* out);
 int eval_ex_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, uint32_t link, fmx_eval_ex* out);
+// ... and its rank pipeline (sort, two scans, rank sum) over keys of any width, shared with fmx_post_evaluate_ex (fmx_post.hip)
+int eval_ex_rank(fmx_handle h, unsigned long long* keys, uint32_t n, int key_bits, unsigned long long* d_num2, uint64_t* num2,
+                 double* rank_seconds);
+// fmx_post.hip: the posterior accumulator of a slot (include/fmx.h "fmx_post_*").  The *_impl functions are the entry points after
+// the handle-kind check, for the first shard of a group too (fmx_comm.hip); post_accum_scores takes scores that are on h's device.
+struct PostAcc {
+  double*  sum_all = nullptr;      // [n_rows] pred_sum_all
+  double*  sum_late = nullptr;     // [n_rows] pred_sum_all_but5
+  float*   last = nullptr;         // [n_rows] the last draw's raw y-hat
+  uint32_t burn_in = 5, eval_rows = 0;
+  uint64_t draws = 0, late_draws = 0;
+};
+void free_post(Slot& s);
+int post_check(fmx_handle h, const char* who, int slot, bool need_begin);
+int post_begin_impl(fmx_handle h, const char* who, int slot, const fmx_post_opts* opts);
+int post_accum_scores(fmx_handle h, Slot& s, const float* score, int add_w0, fmx_post_stats* out);
+int post_evaluate_impl(fmx_handle h, const char* who, int slot, uint32_t which, fmx_eval_ex* out);
+int post_get_impl(fmx_handle h, const char* who, int slot, uint32_t which, double* out, uint64_t* draws);
+int post_end_impl(fmx_handle h, const char* who, int slot);
 int scan_error_check(fmx_handle h);                                      // fmx_sgd.hip: the device's error word after k_scan_pit launches (streams drained)
 uint32_t multi_group_size(const Slot& s, int KP);                        // fmx_sgd.hip: examples per wavefront of the short-row kernels (0: rows are long)
 bool streams_concurrent(fmx_handle h);                                   // fmx_sgd.hip: probed once per handle

@@ -3,6 +3,9 @@ device to.  Pure Python on purpose -- the AUC numerator is counted with Python i
 
     classification_metrics(scores, target, link="logistic") -> dict with the fields of fmx_eval_ex
 
+... and of the posterior accumulator (fmx_post_*): PosteriorAverage keeps the three prediction vectors of
+fm_learn_mcmc_simultaneous in numpy fp64; posterior_metric / posterior_evaluate_ex score a vector of means.
+
 `scores` are taken as the fp32 raw y-hat the device returns (they are rounded to float32 first, which is the identity on
 fmx_predict's output); s_i = +1 if target_i >= 0 else -1.
 """
@@ -67,3 +70,146 @@ def classification_metrics(scores, target, link="logistic"):
     out["logloss"] = math.fsum(loss_term(x if s else -x, link) for x, s in zip(p, positive)) / rows
     return out
 
+
+
+# ---- the posterior accumulator (include/fmx.h "fmx_post_*") ---------------------------------------------------------------------
+POST_THIS, POST_ALL, POST_LATE = 0, 1, 2
+TASK_REGRESSION, TASK_CLASSIFICATION = 0, 1
+
+
+def _ref_erf(x):
+    """the reference's 5-term erf polynomial (random.h:45-59), vectorised."""
+    x = np.asarray(x, dtype=np.float64)
+    t = np.where(x >= 0, 1.0 / (1.0 + 0.3275911 * x), 1.0 / (1.0 - 0.3275911 * x))
+    r = 1.0 - (t * (0.254829592 + t * (-0.284496736 + t * (1.421413741 + t * (-1.453152027 + t * 1.061405429))))) * np.exp(-x * x)
+    return np.where(x >= 0, r, -r)
+
+
+def ref_cdf_gaussian(x):
+    """random.h:65-67"""
+    return 0.5 + 0.5 * _ref_erf(0.707106781 * np.asarray(x, dtype=np.float64))
+
+
+def posterior_mean(total, count):
+    """sum * (1.0 / count): the product with the reciprocal of fm_learn_mcmc_simultaneous.h:278, :296, not a division"""
+    return np.asarray(total, dtype=np.float64) * (1.0 / count)
+
+
+def _clamp(p, lo, hi):
+    """std::min / std::max of :132-133 with a NaN let through (numpy's minimum / maximum)"""
+    return np.maximum(lo, np.minimum(hi, p))
+
+
+def _correct(m, y):
+    return int(np.count_nonzero(((m >= 0.5) & (y > 0)) | ((m < 0.5) & (y < 0))))               # :297
+
+
+def posterior_metric(task, mean, target, min_target=0.0, max_target=0.0):
+    """fmx_post_metric of a vector of means (None: a vector without draws) against its targets: _evaluate (:272-289) and
+    _evaluate_class (:291-309)"""
+    nan = math.nan
+    if mean is None or len(mean) == 0:
+        return {"rows": 0, "nan_rows": 0, "correct": 0, "rmse": nan, "mae": nan, "accuracy": nan, "ll_ref": nan}
+    m = np.asarray(mean, dtype=np.float64)
+    y = np.asarray(target, dtype=np.float32)[:len(m)].astype(np.float64)
+    rows = len(m)
+    out = {"rows": rows, "nan_rows": int(np.count_nonzero(m != m)), "correct": 0, "rmse": 0.0, "mae": 0.0, "accuracy": 0.0, "ll_ref": 0.0}
+    with np.errstate(all="ignore"):
+        if task == TASK_REGRESSION:
+            err = _clamp(m, min_target, max_target) - y
+            out["rmse"] = math.sqrt(float(np.sum(err * err)) / rows)
+            out["mae"] = float(np.sum(np.abs(err))) / rows
+        else:
+            out["correct"] = _correct(m, y)
+            out["accuracy"] = out["correct"] / rows
+            w = (y + 1.0) * 0.5
+            q = np.where(m > 0.99, 0.99, m)
+            q = np.where(q < 0.01, 0.01, q)                               # (a NaN passes both comparisons, :302-303)
+            out["ll_ref"] = -float(np.sum(w * np.log10(q) + (1.0 - w) * np.log10(1.0 - q))) / rows
+    return out
+
+
+def posterior_evaluate_ex(task, mean, target, min_target=0.0, max_target=0.0):
+    """fmx_eval_ex of a vector of means (None: a vector without draws), as fmx_post_evaluate_ex fills it"""
+    out = {"rows": 0, "nan_rows": 0, "pos": 0, "neg": 0, "correct": 0, "auc_num2": 0, "auc": math.nan, "logloss": math.nan,
+           "rmse": 0.0, "mae": 0.0, "accuracy": 0.0, "device_seconds": 0.0, "rank_seconds": 0.0, "flags": 0}
+    if mean is None or len(mean) == 0:
+        return out
+    m = np.asarray(mean, dtype=np.float64)
+    y = np.asarray(target, dtype=np.float32)[:len(m)].astype(np.float64)
+    rows = out["rows"] = len(m)
+    out["nan_rows"] = int(np.count_nonzero(m != m))
+    with np.errstate(all="ignore"):
+        if task == TASK_REGRESSION:
+            err = _clamp(m, min_target, max_target) - y
+            out["rmse"] = math.sqrt(float(np.sum(err * err)) / rows)
+            out["mae"] = float(np.sum(np.abs(err))) / rows
+            return out
+        positive = y >= 0
+        out["pos"] = int(np.count_nonzero(positive))
+        out["neg"] = rows - out["pos"]
+        out["correct"] = _correct(m, y)
+        out["accuracy"] = out["correct"] / rows
+        if out["nan_rows"]:
+            return out
+        out["logloss"] = float(np.sum(np.where(positive, -np.log(m), -np.log(1.0 - m)))) / rows
+    if out["pos"] and out["neg"]:
+        out["auc_num2"] = auc_numerator2([float(x) for x in m], [bool(b) for b in positive])
+        out["auc"] = out["auc_num2"] / (2 * out["pos"] * out["neg"])
+    return out
+
+
+class PosteriorAverage:
+    """the accumulator of fmx_post_begin / fmx_post_accumulate on the host: pred_this, pred_sum_all and pred_sum_all_but5 of
+    fm_learn_mcmc_simultaneous (:129-161) in numpy fp64, one add per row per draw in draw order"""
+
+    def __init__(self, task, min_target=0.0, max_target=0.0, burn_in=5, eval_rows=0):
+        if task not in (TASK_REGRESSION, TASK_CLASSIFICATION):
+            raise ValueError("unknown task")
+        self.task, self.min_target, self.max_target = task, float(min_target), float(max_target)
+        self.burn_in, self.eval_rows = int(burn_in), int(eval_rows)
+        self.draws = self.late_draws = 0
+        self.this = self.sum_all = self.sum_late = None
+
+    def accumulate(self, p):
+        """add one draw: p is the fp32 raw y-hat of every row (fmx_predict's output)"""
+        p = np.asarray(p, dtype=np.float32).reshape(-1).astype(np.float64)
+        if self.sum_all is None:
+            self.sum_all, self.sum_late = np.zeros(len(p)), np.zeros(len(p))
+        if len(p) != len(self.sum_all):
+            raise ValueError("%d predictions for %d rows" % (len(p), len(self.sum_all)))
+        with np.errstate(all="ignore"):
+            if self.task == TASK_REGRESSION:
+                self.this, v = p, _clamp(p, self.min_target, self.max_target)
+            else:
+                self.this = v = ref_cdf_gaussian(p)
+            self.sum_all = self.sum_all + v
+            if self.draws >= self.burn_in:
+                self.sum_late = self.sum_late + v
+                self.late_draws += 1
+        self.draws += 1
+
+    def count(self, which):
+        return {POST_THIS: min(self.draws, 1), POST_ALL: self.draws, POST_LATE: self.late_draws}[which]
+
+    def get(self, which):
+        """what fmx_post_get copies out: the sum (POST_ALL, POST_LATE) or the last draw itself (POST_THIS)"""
+        v = {POST_THIS: self.this, POST_ALL: self.sum_all, POST_LATE: self.sum_late}[which]
+        if v is None:
+            raise ValueError("no draw has been accumulated")
+        return v if self.draws else np.zeros(len(v))
+
+    def mean(self, which):
+        """the means of a vector, or None before its first draw"""
+        if self.count(which) == 0:
+            return None
+        return self.this if which == POST_THIS else posterior_mean(self.get(which), self.count(which))
+
+    def _rows(self, m):
+        return m if m is None or not self.eval_rows else m[:self.eval_rows]
+
+    def metric(self, which, target):
+        return posterior_metric(self.task, self._rows(self.mean(which)), target, self.min_target, self.max_target)
+
+    def evaluate_ex(self, which, target):
+        return posterior_evaluate_ex(self.task, self._rows(self.mean(which)), target, self.min_target, self.max_target)

@@ -15,7 +15,7 @@ import sys
 
 import numpy as np
 
-from . import capi
+from . import capi, evalmetrics
 
 TASK_REGRESSION = capi.TASK_REGRESSION        # fm_learn.h:46
 TASK_CLASSIFICATION = capi.TASK_CLASSIFICATION  # fm_learn.h:47
@@ -252,17 +252,7 @@ class FMLearnSGD:
             self._h = None
 
 
-def _ref_erf(x):
-    """the reference's 5-term erf polynomial (random.h:45-59), vectorised."""
-    x = np.asarray(x, dtype=np.float64)
-    t = np.where(x >= 0, 1.0 / (1.0 + 0.3275911 * x), 1.0 / (1.0 - 0.3275911 * x))
-    r = 1.0 - (t * (0.254829592 + t * (-0.284496736 + t * (1.421413741 + t * (-1.453152027 + t * 1.061405429))))) * np.exp(-x * x)
-    return np.where(x >= 0, r, -r)
-
-
-def cdf_gaussian(x):
-    """random.h:65-67"""
-    return 0.5 + 0.5 * _ref_erf(0.707106781 * np.asarray(x, dtype=np.float64))
+cdf_gaussian = evalmetrics.ref_cdf_gaussian       # random.h:65-67 with the reference's erf polynomial (:45-59)
 
 
 class FMLearnALS:
@@ -271,6 +261,9 @@ class FMLearnALS:
     fm, min_target, max_target, task, num_iter; w_lambda / v_lambda are set from -regular like libfm.cpp:326-365.
     `groups` (attribute -> group id, the `-meta` file; fm_learn.h:40, Data.h:39-46) makes them per group:
     w_lambda [G], v_lambda [G] or [G][k] (libfm.cpp:353-363).
+    `device_average` = True keeps the test predictions and their running sums on the device (fmx_post_begin / fmx_post_accumulate):
+    the `#Iter=` line then carries the reference's Test(ll) column on classification, the log rows its rmse_mcmc_* / acc_mcmc_* /
+    ll_mcmc_* fields, and extra_metrics / evaluate_ex(test) score the averaged prediction.
     `devices` (None: one handle on `device`) lists device ordinals; with more than one entry the model is split into one feature
     shard per entry (hashed ownership, like the libFM adapter's gpu_devices; "[0, 0]" = two shards on one device) and the sweeps
     run over the shards (capi.Group) -- block-structured data keeps its blocks apart there too (Data.keep_blocks)."""
@@ -292,6 +285,7 @@ class FMLearnALS:
         self.pred_sum_all = None       # fm_learn_mcmc.h:114
         self.log = []
         self.extra_metrics = ()        # classification: "auc" and / or "logloss" per iteration, on stderr and in log
+        self.device_average = False    # keep pred_this / pred_sum_all on the device (fmx_post_*) instead of predicting to the host
         self._h = None                 # a capi.Handle, or the capi.Group of the shards
         self._shards = []
         self._train = self._test = None   # the data sets of learn(): slots 0 and 1
@@ -331,9 +325,17 @@ class FMLearnALS:
         test.upload(h, 1)
         self._train, self._test = train, test
         self.pred_sum_all = np.zeros(test.num_cases)
+        if self.device_average:
+            h.post_begin(1)
         h.als_begin(0)
         for i in range(self.num_iter):
             st = h.als_sweep(self.w_lambda, self._v_table(self.v_lambda), 1.0, 0.0, 0.0, self.do_sample, self.seed)
+            row = {"train": st.train_metric, "time_learn": st.device_seconds, "levels": st.levels}
+            if self.device_average:
+                row.update(self._post_iteration(i, st)[1])
+                self.log.append(row)
+                self._log_post_metrics(i)
+                continue
             p = h.predict(1, test.num_cases)
             if self.task == TASK_REGRESSION:                  # :127-138
                 self.pred_this = p
@@ -345,16 +347,60 @@ class FMLearnALS:
                 self.pred_sum_all += self.pred_this
                 acc = float(np.mean(((self.pred_sum_all / (i + 1)) >= 0.5) == (test.target >= 0)))
                 print("#Iter=%3d\tTrain=%g\tTest=%g" % (i, st.train_metric, acc), file=self.out)
-            self.log.append({"train": st.train_metric, "time_learn": st.device_seconds, "levels": st.levels})
+            self.log.append(row)
             _log_extra_metrics(self, i, train, test)
+        if self.device_average:
+            self._post_download(test)
         h.als_end()
         self.fm.w0, self.fm.w, self.fm.v = h.get_params(self.fm.w, self.fm.v)
 
+    # device_average: the test predictions of fm_learn_mcmc_simultaneous.h:127-161, 213-264 without leaving the device
+    def _post_iteration(self, i, st):
+        """add the sweep's draw to the accumulator of slot 1 and print the reference's `#Iter=` line from the mean over all draws.
+        Returns (the line's test metric, the reference's rlog fields of the three vectors)."""
+        ps = self._h.post_accumulate(1)
+        m, row = ps.m[capi.POST_ALL], {}
+        names = (("this", capi.POST_THIS), ("all", capi.POST_ALL), ("all_but5", capi.POST_LATE))
+        if self.task == TASK_REGRESSION:                      # :213-226
+            metric = m.rmse
+            print("#Iter=%3d\tTrain=%g\tTest=%g" % (i, st.train_metric, metric), file=self.out)
+            for name, q in names:
+                row["rmse_mcmc_" + name] = ps.m[q].rmse
+        else:                                                 # :237-253
+            metric = m.accuracy
+            print("#Iter=%3d\tTrain=%g\tTest=%g\tTest(ll)=%g" % (i, st.train_metric, metric, m.ll_ref), file=self.out)
+            for name, q in names:
+                row["acc_mcmc_" + name], row["ll_mcmc_" + name] = ps.m[q].accuracy, ps.m[q].ll_ref
+        return metric, row
+
+    def _log_post_metrics(self, i):
+        """extra_metrics of the averaged test prediction: one stderr line per named metric, <metric>_test in the log row"""
+        names = tuple(self.extra_metrics)
+        for m in names:
+            if m not in EXTRA_METRICS:
+                raise ValueError("unknown metric %r (want auc, logloss)" % (m,))
+        if not names or self.task != TASK_CLASSIFICATION:
+            return
+        te = self._h.post_evaluate_ex(1, capi.POST_ALL)
+        for m in names:
+            print("#Iter=%3d\t%s: Test=%g" % (i, m, getattr(te, m)), file=sys.stderr)
+            self.log[-1][m + "_test"] = getattr(te, m)
+
+    def _post_download(self, test):
+        """pred_sum_all / pred_this of the finished run, once"""
+        self.pred_sum_all, _ = self._h.post_get(1, capi.POST_ALL, test.num_cases)
+        self.pred_this, _ = self._h.post_get(1, capi.POST_THIS, test.num_cases)
+
     def evaluate_ex(self, data):
         """exact AUC and log loss (probit link: this learner's probability is cdf_gaussian(y-hat)) of the train or test set of the
-        running learn() under the parameters of the last sweep (fmx_evaluate_ex / fmx_group_evaluate_ex)"""
+        running learn() under the parameters of the last sweep (fmx_evaluate_ex / fmx_group_evaluate_ex); with device_average,
+        of the test set's mean over the draws (fmx_post_evaluate_ex)"""
         if data is not self._train and data is not self._test:
             raise ValueError("evaluate_ex: the data set is neither the train nor the test set of learn()")
+        if self.device_average:
+            if data is not self._test:
+                raise NotImplementedError("evaluate_ex: device_average averages the test predictions only, like the reference")
+            return self._h.post_evaluate_ex(1, capi.POST_ALL)
         return self._h.evaluate_ex(0 if data is self._train else 1, capi.LINK_PROBIT)
 
     TOPK_SLOTS = (2, 3)             # learn() keeps train and test in slots 0 and 1
@@ -409,11 +455,13 @@ class FMLearnMCMC(FMLearnALS):
         self.mu_0 = 0.0
 
     def evaluate_ex(self, data):
+        if self.device_average:
+            return super().evaluate_ex(data)
         raise NotImplementedError("evaluate_ex: the MCMC prediction is the average over the draws (pred_sum_all / num_iter); "
                                   "no single device pass scores it")
 
     def learn(self, train, test):
-        if tuple(self.extra_metrics):
+        if tuple(self.extra_metrics) and not self.device_average:
             raise NotImplementedError("extra_metrics: the MCMC prediction is the average over the draws (pred_sum_all / num_iter); "
                                       "no single device pass scores it")
         h = self._h
@@ -421,7 +469,10 @@ class FMLearnMCMC(FMLearnALS):
         k, n, G = self.fm.num_factor, self.fm.num_attribute, h.G
         train.upload(h, 0)
         test.upload(h, 1)
+        self._train, self._test = train, test
         self.pred_sum_all = np.zeros(test.num_cases)
+        if self.device_average:
+            h.post_begin(1)
         N = train.num_cases
         # meta->num_attr_per_group (Data.h:93-95)
         n_g = np.array([float(n)]) if self.groups is None else np.bincount(np.asarray(self.groups), minlength=G).astype(np.float64)
@@ -448,21 +499,30 @@ class FMLearnMCMC(FMLearnALS):
                     mean = (sv + b0 * m0) / (ng + b0)                                             # draw_v_mu :1019-1037
                     v_mu = _keep_finite(mean + rng.standard_normal(mean.shape) * np.sqrt(1.0 / ((ng + b0) * v_lambda)), v_mu)
             st = h.als_sweep(w_lambda, v_lambda, alpha, w_mu, v_mu, self.do_sample, self.seed * 7919 + 13)
-            p = h.predict(1, test.num_cases)
-            if self.task == TASK_REGRESSION:
-                self.pred_this = p
-                self.pred_sum_all += np.maximum(self.min_target, np.minimum(self.max_target, p))
-                metric = float(np.sqrt(np.mean((self.pred_sum_all / (i + 1) - test.target) ** 2)))
+            post_row = {}
+            if self.device_average:
+                metric, post_row = self._post_iteration(i, st)
             else:
-                self.pred_this = cdf_gaussian(p)
-                self.pred_sum_all += self.pred_this
-                metric = float(np.mean(((self.pred_sum_all / (i + 1)) >= 0.5) == (test.target >= 0)))
-            print("#Iter=%3d\tTrain=%g\tTest=%g" % (i, st.train_metric, metric), file=self.out)
+                p = h.predict(1, test.num_cases)
+                if self.task == TASK_REGRESSION:
+                    self.pred_this = p
+                    self.pred_sum_all += np.maximum(self.min_target, np.minimum(self.max_target, p))
+                    metric = float(np.sqrt(np.mean((self.pred_sum_all / (i + 1) - test.target) ** 2)))
+                else:
+                    self.pred_this = cdf_gaussian(p)
+                    self.pred_sum_all += self.pred_this
+                    metric = float(np.mean(((self.pred_sum_all / (i + 1)) >= 0.5) == (test.target >= 0)))
+                print("#Iter=%3d\tTrain=%g\tTest=%g" % (i, st.train_metric, metric), file=self.out)
             row = {"train": st.train_metric, "test": metric, "alpha": alpha, "time_learn": st.device_seconds}
+            row.update(post_row)
             for g in range(G):                                                                    # rlog fields :1145-1157
                 row["wmu[%d]" % g], row["wlambda[%d]" % g] = float(w_mu[g]), float(w_lambda[g])
             row["w_lambda"] = float(w_lambda[0])
             self.log.append(row)
+            if self.device_average:
+                self._log_post_metrics(i)
+        if self.device_average:
+            self._post_download(test)
         self.w_mu, self.w_lambda_last, self.v_mu, self.v_lambda_last = w_mu, w_lambda, v_mu, v_lambda
         h.als_end()
         self.fm.w0, self.fm.w, self.fm.v = h.get_params(self.fm.w, self.fm.v)
