@@ -729,16 +729,19 @@ int fmx_group_sgd_epoch(fmx_group g, int slot, const fmx_sgd_opts* opts_in, fmx_
   // of work per shard, so every call the host makes for it counts.  In-stream schedule: one launch for the shard's sums, the exchange
   // without a comm stream or events (RCCL: on the compute stream; loopback: every shard's launches go to shard 0's stream, in order), two
   // launches for the update (sgd_finish_impl): 3 launches (+ 1 collective call) per shard and batch where the general schedule makes ~20 calls.
-  // FMX_GROUP_IN_STREAM=0 keeps the general schedule.
+  // FMX_GROUP_IN_STREAM=0 keeps the general schedule -- of the EXCHANGE.  A batch takes two decisions: how its sums are gathered and exchanged
+  // (here: sgd_in_stream_batch + the knob, no FMX_FLAG_PIPELINE, short rows on every shard) and how a shard updates its rows (fmx_sgd_finish's step
+  // plan: sgd_in_stream_batch + short rows on that shard).  With the knob at 0 or under FMX_FLAG_PIPELINE the exchange takes the comm stream and its
+  // events and the update STILL rides in-stream: all of a shard's launches land on one stream, so the update needs no event of its own.
   const bool in_stream_ok = []() { const char* e = getenv("FMX_GROUP_IN_STREAM"); return !(e && e[0] == '0'); }();   // (read per epoch: tests switch it)
-  bool small = in_stream_ok && B < 32768u && (opts.flags & FMX_FLAG_BIAS_LAG) && !pipeline;
-  if (small)
-    for (auto m : g->hs) small = small && multi_group_size(m->slots[slot], m->KP) != 0 && (opts.apply == FMX_APPLY_DEFAULT || opts.apply == FMX_APPLY_FUSED);
-  auto stream_of = [&](size_t i) -> void* { return (small && g->kind == GROUP_LOOPBACK) ? (void*)h0->stream : (void*)g->hs[i]->stream; };
+  bool exchange_in_stream = in_stream_ok && sgd_in_stream_batch(B, opts.flags) && !pipeline;
+  if (exchange_in_stream)
+    for (auto m : g->hs) exchange_in_stream = exchange_in_stream && multi_group_size(m->slots[slot], m->KP) != 0 && (opts.apply == FMX_APPLY_DEFAULT || opts.apply == FMX_APPLY_FUSED);
+  auto stream_of = [&](size_t i) -> void* { return (exchange_in_stream && g->kind == GROUP_LOOPBACK) ? (void*)h0->stream : (void*)g->hs[i]->stream; };
   auto gather = [&](uint64_t b) -> int {
     const uint32_t nb = rows_of(b);
     const int which = (int)(b & 1);
-    if (small) {
+    if (exchange_in_stream) {
       for (size_t i = 0; i < n; i++) { cur = g->hs[i]; GCHK(g, fmx_sgd_partial(cur, slot, b * B, nb, cur->xbuf[which], stream_of(i))); }
       return exchange_begin(g, which, (size_t)nb * kp1, true);
     }
@@ -778,7 +781,7 @@ int fmx_group_sgd_epoch(fmx_group g, int slot, const fmx_sgd_opts* opts_in, fmx_
     return erc;
   };
   auto update = [&](uint64_t b) -> int {
-    int erc = exchange_end(g, (int)(b & 1), small);
+    int erc = exchange_end(g, (int)(b & 1), exchange_in_stream);
     if (erc) return erc;
     erc = mark(b, 2);
     if (erc) return erc;

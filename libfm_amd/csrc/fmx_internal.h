@@ -261,6 +261,11 @@ int ensure_wside(fmx_handle h, Slot& s);                                 // fmx_
 inline void touch_w(fmx_handle h) { if (h) h->w_version++; }
 void resolve_batch(const fmx_config& cfg, double coll_mass, uint32_t requested, uint32_t dflt, double curv_scale, fmx_batch_info* out);
 constexpr uint32_t FMX_DEFAULT_BATCH = 262144u;                          // fmx_sgd_opts::batch = 0, before the stability cut
+// batches of this many rows and more give the bias recurrence a stream of its own; below, a batch is microseconds of work and the recurrence
+// rides in the launch stream (k_apply_seg_scan, k_small_one): sgd_epoch_fused, the split step's update (step_plan), the group driver's exchange
+constexpr uint32_t FMX_SIDE_STREAM_BATCH = 32768u;
+// a batch of the bias-lag schedule small enough for the in-stream forms (+ short rows: step_plan; + the group driver's own terms: its exchange)
+inline bool sgd_in_stream_batch(uint32_t batch, uint32_t flags) { return batch != 0 && batch < FMX_SIDE_STREAM_BATCH && (flags & FMX_FLAG_BIAS_LAG); }
 int sgd_resolve_batch(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, fmx_batch_info* bi);   // fmx_sgd.hip: + the shards' shares
 int sgd_partial_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n_rows, float* S, float* c, hipStream_t st);   // fmx_sgd.hip
 constexpr size_t PREP_RAW_FLOATS = size_t(1) << 24;                      // prep_rows: raw partial sums of one piece of rows (64 MiB)

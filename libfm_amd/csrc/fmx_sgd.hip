@@ -279,18 +279,29 @@ done:
   return rc;
 }
 
-// the device's error word after launches of k_scan_pit whose streams have been drained by the caller.  Bit 4 = a grid-wide exchange ran
+// the device's error word (h->handoff_err), read with the streams drained: copies it to the host, clears the bits of `mask` on the device
+// where one of them is set, and returns those
+static int take_error_bits(fmx_handle h, uint32_t mask, uint32_t* bits) {
+  uint32_t e = 0;
+  HIPCHK(h, hipMemcpy(&e, h->handoff_err, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (e & mask) {
+    const uint32_t rest_bits = e & ~mask;
+    (void)hipMemcpy(h->handoff_err, &rest_bits, sizeof(uint32_t), hipMemcpyHostToDevice);
+  }
+  *bits = e & mask;
+  return FMX_OK;
+}
+// ... after launches of k_scan_pit.  Bit 4 = a grid-wide exchange ran
 // into its bound and one workgroup evaluated the batch's chain serially instead (fmx_kernels.h): the numbers are the rule's, so this is
 // not a failure -- the epoch reports FMX_STAT_SCAN_FALLBACK and the handle takes the one-wavefront chain from now on.  Only bit 4 is
 // cleared here (the hand-off's bits 1 and 2 belong to the epoch's own check).
 extern "C++" int scan_error_check(fmx_handle h) {
   if (!h->pit_used) return FMX_OK;
   h->pit_used = false;
-  uint32_t e = 0;
-  HIPCHK(h, hipMemcpy(&e, h->handoff_err, sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (e & 4u) {
-    const uint32_t rest_bits = e & ~4u;
-    (void)hipMemcpy(h->handoff_err, &rest_bits, sizeof(uint32_t), hipMemcpyHostToDevice);
+  uint32_t bits = 0;
+  int rc = take_error_bits(h, 4u, &bits);
+  if (rc) return rc;
+  if (bits) {
     h->scan_pit = false;
     h->run_status |= FMX_STAT_SCAN_FALLBACK;
   }
@@ -318,6 +329,15 @@ extern "C++" bool streams_concurrent(fmx_handle h) {
   h->concurrent = (res[2] == 1u && res[3] == 1u) ? 1 : 0;
   return h->concurrent != 0;
 }
+
+// a kernel that asks for more dynamic LDS than the default limit: that limit is per-device state, raised once per handle and kernel
+static int raise_lds(fmx_handle h, const void* kf, size_t bytes) {
+  if (h->lds_raised.count(kf)) return FMX_OK;
+  HIPCHK(h, hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  h->lds_raised.insert(kf);
+  return FMX_OK;
+}
+#define FMX_RAISE_LDS(kf, bytes) do { int _rc = raise_lds(h, (const void*)(kf), (bytes)); if (_rc) return _rc; } while (0)
 
 // workgroups of k_scan_pit that must be resident TOGETHER on the handle's device: every shard of a loopback group runs the whole
 // recurrence itself, on the same device (round-5 advisor: 16 loopback shards x 32 workgroups on 256 CUs waited for each other)
@@ -376,7 +396,7 @@ static int launch_scan(fmx_handle h, const float* rest, const float* target, uin
             HIPCHK(h, hipMemsetAsync(h->pit_ctr, 0, (PIT_MAX_IT + 1) * sizeof(unsigned long long), st));
             float* mp = mult ? mult + r0 : nullptr;
 #define FMX_PIT(WM, TK) do { auto kf = k_scan_pit<WM, TK>;                                                                       \
-            if (!h->lds_raised.count((const void*)kf)) { HIPCHK(h, hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIT_LDS_BYTES)); h->lds_raised.insert((const void*)kf); } \
+            FMX_RAISE_LDS(kf, PIT_LDS_BYTES);                                                                                      \
             hipLaunchKernelGGL(kf, dim3(nwg), dim3(256), PIT_LDS_BYTES, st, rest + r0, target + r0, rn, chunk, hy, pin, pout, mp, ph, ps); } while (0)
             if (hy.task == 0) { if (mult) FMX_PIT(true, 0); else FMX_PIT(false, 0); }
             else              { if (mult) FMX_PIT(true, 1); else FMX_PIT(false, 1); }
@@ -396,9 +416,8 @@ static int launch_scan(fmx_handle h, const float* rest, const float* target, uin
     // ... or, round 5, the sub-piece form of the same kernel for micro-chunks of 16 / 32 / 64 / 128 examples (the default is now below 256)
     const bool sub = chunk == 16u || chunk == 32u || chunk == 64u || chunk == 128u;
     const bool tiled = n_rows > 8192u && ((chunk % 256u) == 0 || sub);
-    // (function attributes are per-device state: the 128 KiB dynamic-LDS limit is raised once per handle, not per process)
 #define FMX_SCAN1(WM, TK, C256) do { auto kf = k_scan1<WM, TK, C256>;                                                              \
-      if (!h->lds_raised.count((const void*)kf)) { HIPCHK(h, hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCAN4_LDS_BYTES)); h->lds_raised.insert((const void*)kf); } \
+      FMX_RAISE_LDS(kf, SCAN4_LDS_BYTES);                                                                                          \
       hipLaunchKernelGGL(kf, dim3(1), dim3(256), SCAN4_LDS_BYTES, st, rest, target, n_rows, chunk, hy, wi, wo, mult, hw); } while (0)
 #define FMX_SCAN(WM, TK) do { \
       if (tiled && chunk == 256u) FMX_SCAN1(WM, TK, 256); \
@@ -439,11 +458,33 @@ extern "C++" int lag_flush(fmx_handle h) {                      // make h->w0 th
   L.active = false; L.step = 0;
   return scan_error_check(h);                                 // (callers that drive fmx_sgd_partial / _finish themselves and then read parameters)
 }
-// the driver's batch is small (below the size at which the recurrence gets its own stream): in-stream schedule, see sgd_finish_impl
-static bool sgd_small_batch(const fmx_sgd_opts* opts) { return opts && opts->batch != 0 && opts->batch < 32768u && (opts->flags & FMX_FLAG_BIAS_LAG); }
+// ---- the plan of ONE step of the split rule: every route decision, made once (fmx_sgd_finish per step, epoch_split per epoch) and read,
+// not derived again, by lag_prepare and sgd_finish_impl ----
+struct StepPlan {
+  bool     lag;         // FMX_FLAG_BIAS_LAG: multipliers from the bias of `depth` batches ago, the recurrence off the critical path
+  bool     short_rows;  // short rows (a feature shard), library's choice of the update: k_apply_multi (example-major, several examples per wavefront) + the deferred list
+  bool     from_sums;   // lag && short_rows on exchanged sums: rest_e and the multipliers come out of the update kernel (no k_rest_from_partial, no k_mult)
+  bool     in_stream;   // ... of a small batch: the recurrence rides in the launch of the deferred features -- no side stream, no events
+  int      apply;       // fmx_sgd_opts::apply as given
+  int64_t  seg_batch;   // the rows are exactly this batch of the slot's segment structure; -1: per-example apply only
+  uint32_t chunk, depth;
+};
+// has_rest: the caller computed rest[] itself (k_rowsums of an unsharded epoch leaves it); else it holds the sums of an exchange
+static StepPlan step_plan(fmx_handle h, const Slot& s, const fmx_sgd_opts* opts, int64_t seg_batch, bool has_rest) {
+  StepPlan p;
+  p.apply = opts ? opts->apply : FMX_APPLY_DEFAULT; p.seg_batch = seg_batch;
+  p.chunk = (opts && opts->w0_chunk) ? opts->w0_chunk : default_w0_chunk(h->cfg);
+  p.depth = (opts && opts->bias_lag) ? opts->bias_lag : 1u;
+  p.lag = opts && (opts->flags & FMX_FLAG_BIAS_LAG);
+  p.short_rows = (p.apply == FMX_APPLY_DEFAULT || p.apply == FMX_APPLY_FUSED) && seg_batch >= 0 && s.cmask && !s.cbatch.empty() && multi_group_size(s, h->KP) != 0;
+  p.from_sums = p.lag && p.short_rows && !has_rest;
+  p.in_stream = p.from_sums && sgd_in_stream_batch(opts->batch, opts->flags);
+  return p;
+}
 // call BEFORE producing the rest buffer of this step on `st`; returns which of the d + 1 rest buffers to use
-static int lag_prepare(fmx_handle h, hipStream_t st, uint32_t depth, int* slot, bool in_stream = false) {
+static int lag_prepare(fmx_handle h, hipStream_t st, const StepPlan& plan, int* slot) {
   LagState& L = h->lag;
+  const uint32_t depth = plan.depth;
   if (!L.ev_rest) {
     HIPCHK(h, hipEventCreateWithFlags(&L.ev_rest, hipEventDisableTiming));
     for (auto& e : L.ev_scan) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -453,7 +494,7 @@ static int lag_prepare(fmx_handle h, hipStream_t st, uint32_t depth, int* slot, 
     L.depth = depth;
     for (uint32_t r = 0; r <= depth; r++) HIPCHK(h, hipMemcpyAsync(h->w0_pp + r, h->w0, sizeof(double), hipMemcpyDeviceToDevice, st));
     L.active = true; L.step = 0;
-  } else if (L.step > depth && !in_stream) {
+  } else if (L.step > depth && !plan.in_stream) {
     HIPCHK(h, hipStreamWaitEvent(st, L.ev_scan[(L.step - depth - 1) % LagState::RING], 0));   // recurrence (step - d - 1) is done with this rest buffer
   }
   *slot = (int)(L.step % (depth + 1));
@@ -480,18 +521,15 @@ static int lag_start_scan(fmx_handle h, const float* rest, const float* target, 
   if (hy.k0) {
     HIPCHK(h, hipEventRecord(L.ev_rest, st));
     HIPCHK(h, hipStreamWaitEvent(h->stream2, L.ev_rest, 0));
-    int rc = launch_scan(h, rest, target, n_rows, chunk, hy, nullptr, h->stream2, h->w0_pp + (b % R), h->w0_pp + ((b + 1) % R));
-    if (rc) return rc;
+    int rc = launch_scan(h, rest, target, n_rows, chunk, hy, nullptr, h->stream2, h->w0_pp + (b % R), h->w0_pp + ((b + 1) % R)); if (rc) return rc;
     HIPCHK(h, hipEventRecord(L.ev_scan[b % LagState::RING], h->stream2));
   }
   return FMX_OK;
 }
 static int lag_step(fmx_handle h, const float* rest, const float* target, uint32_t n_rows, uint32_t chunk,
                     const Hyper& hy, hipStream_t st) {
-  int rc = lag_start_scan(h, rest, target, n_rows, chunk, hy, st);
-  if (rc) return rc;
-  rc = lag_wait_bias(h, hy, st);
-  if (rc) return rc;
+  int rc = lag_start_scan(h, rest, target, n_rows, chunk, hy, st); if (rc) return rc;
+  rc = lag_wait_bias(h, hy, st); if (rc) return rc;
   hipLaunchKernelGGL(k_mult, dim3(std::min<uint32_t>((n_rows + 255) / 256, 2048)), dim3(256), 0, st, rest, target, n_rows, hy,
                      lag_bias_slot(h), h->mult);
   HIPCHK(h, hipGetLastError());
@@ -499,133 +537,107 @@ static int lag_step(fmx_handle h, const float* rest, const float* target, uint32
   return FMX_OK;
 }
 
-// steps 2 and 3 of the minibatch rule for rows [row0,row0+n_rows); `seg_batch` = batch index when the rows are
-// exactly one batch of the slot's segment structure (else -1: per-example apply only)
-// short rows (a feature shard), library's choice of the update: example-major over the batch-unique features (k_apply_multi: several examples
-// per wavefront, S_e read once per example) + k_apply_seg over the batch's deferred list
-static bool short_row_update(fmx_handle h, const Slot& s, const fmx_sgd_opts* opts, int64_t seg_batch) {
-  const int apply = opts ? opts->apply : FMX_APPLY_DEFAULT;
-  return (apply == FMX_APPLY_DEFAULT || apply == FMX_APPLY_FUSED) && seg_batch >= 0 && s.cmask && !s.cbatch.empty() &&
-         multi_group_size(s, h->KP) != 0;
+// the deferred features of batch b of the slot's segment structure (ensure_segments): those that occur more than once in the batch,
+// finished by their owners (k_apply_seg, k_apply_seg_scan, k_small_one) from the examples' factor sums S and multipliers
+static SegWork seg_work(fmx_handle, const Slot& s, size_t b, const float* S, const float* mult) {
+  const uint32_t c0 = s.cbatch[b], c1 = s.cbatch[b + 1], s0 = s.batch_seg[b], s1 = s.batch_seg[b + 1];
+  const uint64_t base = s.batch_base[b];
+  return SegWork{s.t_ent + base, s.seg_feat + s0, s.seg_rel + s0, s.cseg + c0, c1 - c0, s1 - s0, (uint32_t)(s.batch_base[b + 1] - base), S, mult,
+                 s.cdesc + c0, nullptr, 0ull};
 }
+// ... and EVERY feature of the batch, one owner each (the dense pass of FMX_APPLY_SEGMENTED and of SGDA's batch form)
+static SegWork seg_work_dense(fmx_handle, const Slot& s, size_t b, const float* S, const float* mult) {
+  const uint32_t s0 = s.batch_seg[b], nseg = s.batch_seg[b + 1] - s0;
+  const uint64_t base = s.batch_base[b];
+  return SegWork{s.t_ent + base, s.seg_feat + s0, s.seg_rel + s0, nullptr, nseg, nseg, (uint32_t)(s.batch_base[b + 1] - base), S, mult, nullptr, nullptr, 0ull};
+}
+// the split step's deferred-feature pass (the only place it launches k_apply_seg<KP, 8, 16>)
 static int launch_deferred(fmx_handle h, const Slot& s, const Hyper& hy, const float* S, size_t b, hipStream_t st) {
-  const uint32_t c0 = s.cbatch[b], c1 = s.cbatch[b + 1];
-  if (c1 > c0) {
-    const uint32_t s0 = s.batch_seg[b], s1 = s.batch_seg[b + 1];
-    const uint64_t base = s.batch_base[b];
-    SegWork sw{s.t_ent + base, s.seg_feat + s0, s.seg_rel + s0, s.cseg + c0, c1 - c0, s1 - s0, (uint32_t)(s.batch_base[b + 1] - base), S, h->mult, s.cdesc + c0};
-    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_apply_seg<KP, 8, 16>), ((uint64_t)sw.nseg + 15) / 16, st, sw, h->tb, hy));
-  }
+  const SegWork sw = seg_work(h, s, b, S, h->mult);
+  if (sw.nseg) { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_apply_seg<KP, 8, 16>), ((uint64_t)sw.nseg + 15) / 16, st, sw, h->tb, hy)); }
   return FMX_OK;
 }
-// cpart != nullptr: `rest` has NOT been computed -- the short-row update derives it (and the multipliers) from S and cpart itself
-static int sgd_finish_impl(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n_rows, const float* S,
-                           float* rest, const fmx_sgd_opts* opts, hipStream_t st,
-                           hipEvent_t ev_a, hipEvent_t ev_b, int64_t seg_batch, const float* cpart = nullptr) {
-  const Hyper hy = make_hyper(h->cfg);
-  const uint32_t chunk = (opts && opts->w0_chunk) ? opts->w0_chunk : default_w0_chunk(h->cfg);
-  const bool lag = opts && (opts->flags & FMX_FLAG_BIAS_LAG);
-  int rc = FMX_OK;
-  if (cpart) {
-    // fused short-row step (bias-lag schedule on a feature shard): [wait for the bias of batch b - d] -> k_apply_multi<FUSED> (rest, multipliers,
-    // update of the batch-unique features) -> the recurrence of this batch starts on the side stream -> the deferred features
-    const uint32_t G = multi_group_size(s, h->KP);
-    if (sgd_small_batch(opts)) {
-      // small batches (what the stability cut leaves of rows with frequent features: BASELINE configs[2] runs 512 rows per batch): a batch is a
-      // few microseconds of work and every call the host makes for it costs as much again -- the recurrence leaves the side stream and rides
-      // in the launch of the deferred features (k_apply_seg_scan, as on an unsharded handle), no events: TWO launches per shard and batch.
-      // Same rule, same ring of bias slots: what a batch reads does not depend on which stream wrote it.
-      const LagState& L = h->lag;
-      const uint32_t R = L.depth + 1;
-      const size_t b = (size_t)seg_batch;
-      if (ev_a) HIPCHK(h, hipEventRecord(ev_a, st));
-      KP_SWITCH(h->KP, { if constexpr (KP >= 64 && KP <= 256) { FMX_LAUNCH_WAVES((k_apply_multi<KP, true>), ((uint64_t)n_rows + G - 1) / G, st, s.ent, s.row_ptr, s.target, row0, n_rows,
-                                                                    h->tb, hy, lag_bias_slot(h), S, cpart, rest, h->mult, (const uint64_t*)s.cmask, G); } });
-      const uint32_t c0 = s.cbatch[b], c1 = s.cbatch[b + 1];
-      const uint32_t s0 = s.batch_seg[b], s1 = s.batch_seg[b + 1];
-      const uint64_t base = s.batch_base[b];
-      SegWork sw{s.t_ent + base, s.seg_feat + s0, s.seg_rel + s0, s.cseg + c0, c1 - c0, s1 - s0, (uint32_t)(s.batch_base[b + 1] - base), S, h->mult, s.cdesc + c0};
-      sw.done_ctr = nullptr; sw.done_val = 0ull;
-      const ScanSmall sc{rest, s.target + row0, h->w0_pp + (L.step % R), h->w0_pp + ((L.step + 1) % R), n_rows, chunk};
-      KP_SWITCH(h->KP, hipLaunchKernelGGL((k_apply_seg_scan<KP, 8, 1>), dim3((sw.nseg + 3) / 4 + 1), dim3(256), 0, st, sw, h->tb, hy, sc));
-      h->lag.step++;
-      h->lag.in_stream = st;
-      h->run_status |= FMX_STAT_SCAN_SERIAL;
-      if (ev_b) HIPCHK(h, hipEventRecord(ev_b, st));
-      HIPCHK(h, hipGetLastError());
-      return FMX_OK;
-    }
-    rc = lag_wait_bias(h, hy, st);
-    if (rc) return rc;
-    if (ev_a) HIPCHK(h, hipEventRecord(ev_a, st));
-    KP_SWITCH(h->KP, { if constexpr (KP >= 64 && KP <= 256) { FMX_LAUNCH_WAVES((k_apply_multi<KP, true>), ((uint64_t)n_rows + G - 1) / G, st, s.ent, s.row_ptr, s.target, row0, n_rows,
-                                                                  h->tb, hy, lag_bias_slot(h), S, cpart, rest, h->mult, (const uint64_t*)s.cmask, G); } });
-    HIPCHK(h, hipGetLastError());
-    rc = lag_start_scan(h, rest, s.target + row0, n_rows, chunk, hy, st);
-    if (rc) return rc;
-    h->lag.step++;
-    rc = launch_deferred(h, s, hy, S, (size_t)seg_batch, st);
-    if (rc) return rc;
-    if (ev_b) HIPCHK(h, hipEventRecord(ev_b, st));
-    HIPCHK(h, hipGetLastError());
-    return FMX_OK;
-  }
-  rc = lag ? lag_step(h, rest, s.target + row0, n_rows, chunk, hy, st)
-           : launch_scan(h, rest, s.target + row0, n_rows, chunk, hy, h->mult, st);
-  if (rc) return rc;
-  if (short_row_update(h, s, opts, seg_batch)) {                // (exact chunk coupling: the multipliers came out of the recurrence)
-    const uint32_t G = multi_group_size(s, h->KP);
-    if (ev_a) HIPCHK(h, hipEventRecord(ev_a, st));
-    KP_SWITCH(h->KP, { if constexpr (KP >= 64 && KP <= 256) { FMX_LAUNCH_WAVES((k_apply_multi<KP, false>), ((uint64_t)n_rows + G - 1) / G, st, s.ent, s.row_ptr, s.target, row0, n_rows,
-                                                                  h->tb, hy, (const double*)h->w0, S, (const float*)nullptr, (float*)nullptr, h->mult, (const uint64_t*)s.cmask, G); } });
-    HIPCHK(h, hipGetLastError());
-    rc = launch_deferred(h, s, hy, S, (size_t)seg_batch, st);
-    if (rc) return rc;
-    if (ev_b) HIPCHK(h, hipEventRecord(ev_b, st));
-    HIPCHK(h, hipGetLastError());
-    return FMX_OK;
-  }
-  int apply = opts ? opts->apply : FMX_APPLY_DEFAULT;
+// the short-row update over the batch-unique features.  fused: it derives rest_e (left in `rest` for the recurrence) and the multipliers
+// (left in h->mult for the deferred list) from the exchanged sums S and cpart itself, with the bias in `bias`; else the multipliers are there
+static int launch_apply_multi(fmx_handle h, const Slot& s, const Hyper& hy, uint64_t row0, uint32_t n_rows, bool fused, const double* bias,
+                              const float* S, const float* cpart, float* rest, hipStream_t st) {
+  const uint32_t G = multi_group_size(s, h->KP);
+  KP_SWITCH(h->KP, { if constexpr (KP >= 64 && KP <= 256) { FMX_LAUNCH_WAVES((fused ? k_apply_multi<KP, true> : k_apply_multi<KP, false>), ((uint64_t)n_rows + G - 1) / G, st,
+                                                                s.ent, s.row_ptr, s.target, row0, n_rows, h->tb, hy, bias, S, cpart, rest, h->mult, (const uint64_t*)s.cmask, G); } });
+  return FMX_OK;
+}
+// step 3 where the rows are long enough for one example per wavefront: the update in the form fmx_sgd_opts::apply names
+static int launch_apply(fmx_handle h, const Slot& s, const Hyper& hy, uint64_t row0, uint32_t n_rows, const float* S, const StepPlan& p,
+                        hipStream_t st, hipEvent_t ev_a) {
+  int apply = p.apply, rc = FMX_OK;
   // split step, library's choice (DEFAULT / FUSED): the features that occur once in the batch are written back example-major
   // (k_fused<FUSED_APPLY>: the wavefront holds S_e, no gather per occurrence), the others by their owner (k_apply_seg over the
   // batch's cseg list) -- the second half of what k_fused<EXACT> + k_apply_seg do in one pass on an unsharded handle.
   // FMX_APPLY_SEGMENTED keeps the dense owner-per-feature pass.
   // ... where rows are long enough to fill a wavefront's gather: measured per rank of a P-way sharded step (scripts/gpu_shard_probe.py,
   // dense vs example-major second pass): 32 entries per row +5 %, 16 entries -4 %, 8 entries -18 %, 4 entries -17 %.
-  const bool masked = (apply == FMX_APPLY_DEFAULT || apply == FMX_APPLY_FUSED) && s.cmask && !s.cbatch.empty() &&
-                      s.nnz >= (uint64_t)24 * s.n_rows;
+  const bool masked = (apply == FMX_APPLY_DEFAULT || apply == FMX_APPLY_FUSED) && s.cmask && !s.cbatch.empty() && s.nnz >= (uint64_t)24 * s.n_rows;
   if (apply == FMX_APPLY_DEFAULT || apply == FMX_APPLY_FUSED) apply = FMX_APPLY_SEGMENTED;   // split step: same rule, two passes
-  if (apply == FMX_APPLY_SEGMENTED && seg_batch < 0) return fail(h, FMX_E_STATE, "segmented apply needs batch-aligned rows");
+  if (apply == FMX_APPLY_SEGMENTED && p.seg_batch < 0) return fail(h, FMX_E_STATE, "segmented apply needs batch-aligned rows");
   if (ev_a) HIPCHK(h, hipEventRecord(ev_a, st));
   if (apply == FMX_APPLY_SEGMENTED && masked) {
-    const size_t b = (size_t)seg_batch;
     KP_SWITCH(h->KP, rc = (launch_fused_zr<KP, FUSED_APPLY>(h, s, hy, row0, n_rows, st, (const double*)h->w0, nullptr,
                                                                (const uint64_t*)s.cmask, const_cast<float*>(S), h->mult)));
     if (rc) return rc;
-    const uint32_t c0 = s.cbatch[b], c1 = s.cbatch[b + 1];
-    if (c1 > c0) {
-      const uint32_t s0 = s.batch_seg[b], s1 = s.batch_seg[b + 1];
-      const uint64_t base = s.batch_base[b];
-      SegWork sw{s.t_ent + base, s.seg_feat + s0, s.seg_rel + s0, s.cseg + c0, c1 - c0, s1 - s0, (uint32_t)(s.batch_base[b + 1] - base), S, h->mult, s.cdesc + c0};
-      KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_apply_seg<KP, 8, 16>), ((uint64_t)sw.nseg + 15) / 16, st, sw, h->tb, hy));
-    }
+    return launch_deferred(h, s, hy, S, (size_t)p.seg_batch, st);
   } else if (apply == FMX_APPLY_SEGMENTED) {
-    const uint32_t s0 = s.batch_seg[(size_t)seg_batch], s1 = s.batch_seg[(size_t)seg_batch + 1];
-    const uint64_t base = s.batch_base[(size_t)seg_batch];
-    const uint32_t bnnz = (uint32_t)(s.batch_base[(size_t)seg_batch + 1] - base);
-    const uint32_t nseg = s1 - s0;
-    if (nseg) {
-      SegWork sw{s.t_ent + base, s.seg_feat + s0, s.seg_rel + s0, nullptr, nseg, nseg, bnnz, S, h->mult};
-      KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_apply_seg<KP, 8, 64>), ((uint64_t)nseg + 63) / 64, st, sw, h->tb, hy));
-    }
-  } else if (apply == FMX_APPLY_ATOMIC) {
-    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_apply<KP, true>), n_rows, st,
-                                       s.ent, s.row_ptr, row0, n_rows, h->tb, hy, S, h->mult));
-  } else if (apply == FMX_APPLY_STORE) {
-    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_apply<KP, false>), n_rows, st,
-                                       s.ent, s.row_ptr, row0, n_rows, h->tb, hy, S, h->mult));
+    const SegWork sw = seg_work_dense(h, s, (size_t)p.seg_batch, S, h->mult);
+    if (sw.nseg) { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_apply_seg<KP, 8, 64>), ((uint64_t)sw.nseg + 63) / 64, st, sw, h->tb, hy)); }
+  } else if (apply == FMX_APPLY_ATOMIC || apply == FMX_APPLY_STORE) {
+    const bool atomic = apply == FMX_APPLY_ATOMIC;
+    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((atomic ? k_apply<KP, true> : k_apply<KP, false>), n_rows, st, s.ent, s.row_ptr, row0, n_rows, h->tb, hy, S, h->mult));
   } else {
     return fail(h, FMX_E_ARG, "unknown apply mode %d", apply);
+  }
+  return FMX_OK;
+}
+// steps 2 and 3 of the minibatch rule for rows [row0,row0+n_rows), as the plan says.  p.from_sums: `rest` has NOT been computed -- the
+// short-row update derives it (and the multipliers) from S and cpart itself
+static int sgd_finish_impl(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n_rows, const float* S, float* rest, const float* cpart,
+                           const StepPlan& p, hipStream_t st, hipEvent_t ev_a, hipEvent_t ev_b) {
+  const Hyper hy = make_hyper(h->cfg);
+  const float* target = s.target + row0;
+  int rc = FMX_OK;
+  if (p.in_stream) {
+    // small batches (what the stability cut leaves of rows with frequent features: BASELINE configs[2] runs 512 rows per batch): a batch is a
+    // few microseconds of work and every call the host makes for it costs as much again -- the recurrence leaves the side stream and rides
+    // in the launch of the deferred features (k_apply_seg_scan, as on an unsharded handle), no events: TWO launches per shard and batch.
+    // Same rule, same ring of bias slots: what a batch reads does not depend on which stream wrote it.
+    const LagState& L = h->lag;
+    const uint32_t R = L.depth + 1;
+    if (ev_a) HIPCHK(h, hipEventRecord(ev_a, st));
+    rc = launch_apply_multi(h, s, hy, row0, n_rows, true, lag_bias_slot(h), S, cpart, rest, st); if (rc) return rc;
+    const SegWork sw = seg_work(h, s, (size_t)p.seg_batch, S, h->mult);
+    const ScanSmall sc{rest, target, h->w0_pp + (L.step % R), h->w0_pp + ((L.step + 1) % R), n_rows, p.chunk};
+    KP_SWITCH(h->KP, hipLaunchKernelGGL((k_apply_seg_scan<KP, 8, 1>), dim3((sw.nseg + 3) / 4 + 1), dim3(256), 0, st, sw, h->tb, hy, sc));
+    h->lag.step++; h->lag.in_stream = st;
+    h->run_status |= FMX_STAT_SCAN_SERIAL;
+  } else if (p.from_sums) {
+    // fused short-row step (bias-lag schedule on a feature shard): [wait for the bias of batch b - d] -> k_apply_multi<FUSED> (rest, multipliers,
+    // update of the batch-unique features) -> the recurrence of this batch starts on the side stream -> the deferred features
+    rc = lag_wait_bias(h, hy, st); if (rc) return rc;
+    if (ev_a) HIPCHK(h, hipEventRecord(ev_a, st));
+    rc = launch_apply_multi(h, s, hy, row0, n_rows, true, lag_bias_slot(h), S, cpart, rest, st); if (rc) return rc;
+    HIPCHK(h, hipGetLastError());
+    rc = lag_start_scan(h, rest, target, n_rows, p.chunk, hy, st); if (rc) return rc;
+    h->lag.step++;
+    rc = launch_deferred(h, s, hy, S, (size_t)p.seg_batch, st); if (rc) return rc;
+  } else {
+    rc = p.lag ? lag_step(h, rest, target, n_rows, p.chunk, hy, st) : launch_scan(h, rest, target, n_rows, p.chunk, hy, h->mult, st);
+    if (rc) return rc;
+    if (p.short_rows) {                                         // (exact chunk coupling: the multipliers came out of the recurrence)
+      if (ev_a) HIPCHK(h, hipEventRecord(ev_a, st));
+      rc = launch_apply_multi(h, s, hy, row0, n_rows, false, (const double*)h->w0, S, nullptr, nullptr, st); if (rc) return rc;
+      HIPCHK(h, hipGetLastError());
+      rc = launch_deferred(h, s, hy, S, (size_t)p.seg_batch, st); if (rc) return rc;
+    } else {
+      rc = launch_apply(h, s, hy, row0, n_rows, S, p, st, ev_a); if (rc) return rc;
+    }
   }
   if (ev_b) HIPCHK(h, hipEventRecord(ev_b, st));
   HIPCHK(h, hipGetLastError());
@@ -635,8 +647,7 @@ static int sgd_finish_impl(fmx_handle h, const Slot& s, uint64_t row0, uint32_t 
 int fmx_sgd_finish(fmx_handle h, int slot, uint64_t row0, uint32_t n_rows, const float* d_partial,
                    const fmx_sgd_opts* opts, void* stream) {
   touch_w(h);
-  int rc = check_slot(h, slot, true);
-  if (rc) return rc;
+  int rc = check_slot(h, slot, true); if (rc) return rc;
   Slot& s = h->slots[slot];
   if (row0 + n_rows > s.n_rows) return fail(h, FMX_E_ARG, "fmx_sgd_finish: rows outside slot");
   if (!s.blocks.empty()) return fail(h, FMX_E_UNSUPPORTED, "relations are not supported with SGD");   // fm_learn_sgd.h:61-63
@@ -645,12 +656,10 @@ int fmx_sgd_finish(fmx_handle h, int slot, uint64_t row0, uint32_t n_rows, const
   if (n_rows == 0) return FMX_OK;
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-  const bool lag = opts && (opts->flags & FMX_FLAG_BIAS_LAG);
   const uint32_t Bcap = (opts && opts->batch) ? std::max(opts->batch, n_rows) : n_rows;
-  const uint32_t lag_depth = (opts && opts->bias_lag) ? opts->bias_lag : 1u;
+  const uint32_t lag_depth = (opts && opts->bias_lag) ? opts->bias_lag : 1u;   // (ahead of the plan: it sizes the scratch)
   if (lag_depth > 4) return fail(h, FMX_E_ARG, "bias_lag %u: at most 4 batches", lag_depth);
-  rc = ensure_scratch(h, n_rows, (size_t)Bcap * (lag_depth + 1));
-  if (rc) return rc;
+  rc = ensure_scratch(h, n_rows, (size_t)Bcap * (lag_depth + 1)); if (rc) return rc;
   const float* S = d_partial;
   const float* c = d_partial + (size_t)n_rows * h->KP;
   int64_t seg_batch = -1;
@@ -660,21 +669,20 @@ int fmx_sgd_finish(fmx_handle h, int slot, uint64_t row0, uint32_t n_rows, const
     const uint32_t B = (opts && opts->batch) ? opts->batch : n_rows;
     if (row0 % B != 0 || n_rows > B || n_rows != std::min<uint64_t>(B, s.n_rows - row0))
       return fail(h, FMX_E_ARG, "fmx_sgd_finish: rows [%llu,+%u) are not batch %u of the slot", (unsigned long long)row0, n_rows, B);
-    rc = ensure_segments(h, h->slots[slot], B);
-    if (rc) return rc;
+    rc = ensure_segments(h, h->slots[slot], B); if (rc) return rc;
     seg_batch = (int64_t)(row0 / B);
   }
+  const StepPlan plan = step_plan(h, s, opts, seg_batch, false);   // every route decision of this step (the segments are there: it reads them)
   int rslot = 0;
-  if (lag) { rc = lag_prepare(h, st, lag_depth, &rslot, sgd_small_batch(opts) && short_row_update(h, s, opts, seg_batch)); if (rc) return rc; }
+  if (plan.lag) { rc = lag_prepare(h, st, plan, &rslot); if (rc) return rc; }
   else { rc = lag_flush(h); if (rc) return rc; }
   float* rest_buf = h->rest + (size_t)rslot * Bcap;
-  // short rows under the bias-lag schedule: rest_e and the multipliers come out of the update kernel itself (no k_rest_from_partial, no k_mult)
-  if (lag && short_row_update(h, s, opts, seg_batch))
-    return sgd_finish_impl(h, s, row0, n_rows, S, rest_buf, opts, st, nullptr, nullptr, seg_batch, c);
-  KP_SWITCH(h->KP, hipLaunchKernelGGL((k_rest_from_partial<KP>), dim3(wave_grid((n_rows + Map<KP>::EPI - 1) / Map<KP>::EPI)),
-                                        dim3(256), 0, st, S, c, n_rows, rest_buf));
-  HIPCHK(h, hipGetLastError());
-  return sgd_finish_impl(h, s, row0, n_rows, S, rest_buf, opts, st, nullptr, nullptr, seg_batch);
+  if (!plan.from_sums) {
+    KP_SWITCH(h->KP, hipLaunchKernelGGL((k_rest_from_partial<KP>), dim3(wave_grid((n_rows + Map<KP>::EPI - 1) / Map<KP>::EPI)),
+                                          dim3(256), 0, st, S, c, n_rows, rest_buf));
+    HIPCHK(h, hipGetLastError());
+  }
+  return sgd_finish_impl(h, s, row0, n_rows, S, rest_buf, c, plan, st, nullptr, nullptr);
 }
 
 int fmx_predict_finish(fmx_handle h, uint32_t n_rows, const float* d_partial, float* d_yhat, void* stream) {
@@ -696,45 +704,180 @@ int fmx_predict_finish(fmx_handle h, uint32_t n_rows, const float* d_partial, fl
   return FMX_OK;
 }
 
+// what an epoch driver reports back to fmx_sgd_epoch
+struct EpochCounts { uint64_t batches = 0, launches = 0, deferred = 0; bool kept_wside = false; };
+
 // MINIBATCH rule, FMX_APPLY_FUSED: per batch ONE pass over the examples (k_fused<FUSED_EXACT>: gather, predict, multiplier,
 // write-back of every feature that occurs once in the batch) + k_apply_seg over the features that occur more than once.
 // The multipliers of batch b use the bias as it was after the recurrence of batch b - d (d = opts->bias_lag >= 1; oracle
 // fmo_sgd_epoch_minibatch_ex with bias_lag = d): the recurrence of batch b (k_scan, one workgroup) runs on the side stream
 // under the launches of batches b+1 .. b+d-1 and only the launch of batch b+d waits for it.
-static int sgd_epoch_fused(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, const Hyper& hy, uint64_t* batches,
-                           uint64_t* launches, uint64_t* deferred, bool* kept_wside) {
-  const uint32_t B = opts->batch;                           // resolved by the caller (sgd_resolve_batch)
-  const uint32_t d = opts->bias_lag ? opts->bias_lag : 1u;
-  if (d > 4) return fail(h, FMX_E_ARG, "bias_lag %u: at most 4 batches", d);
-  const uint32_t chunk = opts->w0_chunk ? opts->w0_chunk : default_w0_chunk(h->cfg);
-  int rc = ensure_segments(h, s, B);
+// Three schedules of a batch (fused_batch_*), over what they share:
+struct FusedEpoch {
+  fmx_handle h; Slot* s; Hyper hy;
+  uint32_t B, Bc, d, chunk; uint64_t n_batch;   // batch, min(batch, rows), bias lag, micro-chunk of the recurrence, batches of the epoch
+  bool keep, handoff;             // the slot's weight side stream is kept (FMX_FLAG_KEEP_WSIDE); side stream: device-side hand-off (else events)
+  double* W; unsigned long long hbase;   // hand-off: bias slots W[0 .. n_batch], the completion counter's value before this epoch
+  int szr, small_cap;             // one launch: row slots of the k_small_one instance; workgroups of it the device holds (0: not asked yet)
+  unsigned long long* small_trace;
+};
+static uint32_t rows_of_batch(const FusedEpoch& E, uint64_t b) { return (uint32_t)std::min<uint64_t>(E.B, E.s->n_rows - b * E.B); }
+// FMX_SMALL_TRACE=<file>: device time stamps of the epoch's middle batch (fmx_small_kernels.h SmallSync::trace), appended to the file
+static const char* small_trace_file() { static const char* f = getenv("FMX_SMALL_TRACE"); return f; }
+static int small_trace_arm(fmx_handle h, hipStream_t st, unsigned long long** trace) {
+  if (!small_trace_file()) return FMX_OK;
+  *trace = h->small_slots + (size_t)3 * SMALL_ONE_MAX;
+  unsigned long long init[16];
+  for (int i = 0; i < 16; i++) init[i] = (i == 0 || i == 5) ? ~0ull : 0ull;
+  HIPCHK(h, hipMemcpyAsync(*trace, init, sizeof(init), hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  return FMX_OK;
+}
+static int small_trace_dump(fmx_handle h, hipStream_t st, const unsigned long long* trace, uint64_t n_batch) {
+  unsigned long long tr[16];
+  HIPCHK(h, hipMemcpyAsync(tr, trace, sizeof(tr), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  if (FILE* f = fopen(small_trace_file(), "a")) {
+    const double t0 = (double)tr[0];
+    fprintf(f, "batch %llu of %llu (ns after the first example started): last example started %.0f, rows gathered %.0f, multiplier published %.0f, example done %.0f | "
+               "first owner started %.0f, last owner saw its tags %.0f, holds its S rows %.0f, done %.0f | recurrence done %.0f | last owner started %.0f, has its entry list %.0f\n",
+            (unsigned long long)(n_batch / 2), (unsigned long long)n_batch, tr[1] - t0, tr[2] - t0, tr[3] - t0, tr[4] - t0, (double)tr[5] - t0, tr[6] - t0, tr[7] - t0, tr[8] - t0, tr[9] - t0, tr[10] - t0, tr[11] - t0);
+    fclose(f);
+  }
+  return FMX_OK;
+}
+// small batches as ONE launch per batch across all dies (k_small_one, fmx_small_kernels.h; FMX_SMALL_ONE=0 at fmx_create: two launches)
+static int fused_batch_one_launch(FusedEpoch& E, uint64_t b, EpochCounts* n) {
+  fmx_handle h = E.h; const Slot& s = *E.s; const Hyper& hy = E.hy;
+  const uint32_t B = E.B, d = E.d, chunk = E.chunk, nb = rows_of_batch(E, b);
+  const uint64_t row0 = b * B, n_batch = E.n_batch;
+  float* S = h->partial;                                        // [nb][KP] x {tag, value}: 8 bytes per element (the two batches' worth of the scratch)
+  const SegWork sw = seg_work(h, s, (size_t)b, S, h->mult + (size_t)(b & 1) * E.Bc);
+  n->deferred += sw.nseg;
+  // the recurrence: at lag >= 2 one launch behind (k_small_one), the last launch catches up
+  const bool defer = d >= 2u;
+  const bool own = !defer || b + 1 == n_batch, prev = defer && b >= 1;
+  const ScanSmall sc{nullptr, s.target + row0, h->w0_pp + (b % d), h->w0_pp + ((b + 1) % d), own ? nb : 0u, chunk};
+  const ScanSmall sc_prev{nullptr, s.target + (prev ? row0 - B : 0), h->w0_pp + ((b + d - 1) % d), h->w0_pp + (b % d), prev ? B : 0u, chunk};
+  unsigned long long* rs0 = h->small_slots + SMALL_ONE_MAX;
+  const SmallSync sy{h->small_slots, rs0 + (size_t)(b & 1) * SMALL_ONE_MAX, rs0 + (size_t)((b + 1) & 1) * SMALL_ONE_MAX, (uint32_t)(b + 1), (uint32_t)b,
+                     h->handoff_err, std::min<uint32_t>(h->pit_spins, 1u << 21), (E.small_trace && b == n_batch / 2) ? E.small_trace : nullptr};
+  const uint32_t n_ex_wg = (nb + 3u) / 4u;
+  bool launched = false;
+#define FMX_SMALL1(KPV, ZRV) do { if (h->KP == KPV && E.szr == ZRV) {                                                                    \
+    auto kf = k_small_one<KPV, ZRV>;                                                                                                       \
+    if (!E.small_cap) {                                                                                                                    \
+      int per_cu = 0;                                                                                                                      \
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kf, 256, 0) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; } \
+      E.small_cap = std::max(1, per_cu * h->num_cu);                                                                                       \
+    }                                                                                                                                      \
+    const uint32_t room = (uint32_t)E.small_cap > n_ex_wg + 1u ? (uint32_t)E.small_cap - n_ex_wg - 1u : 1u;                                \
+    const uint32_t own_wg = sw.nseg ? std::max(1u, std::min((sw.nseg + 3u) / 4u, room)) : 0u;                                              \
+    hipLaunchKernelGGL(kf, dim3(n_ex_wg + own_wg + 1u), dim3(256), 0, h->stream, s.ent, s.row_ptr, s.target, row0, nb, h->tb, hy,          \
+                       (const double*)(h->w0_pp + ((b + 1) % d)), (const uint64_t*)s.cmask, S, s.fixed_nnz, sw, sc_prev, sc, sy, n_ex_wg,  \
+                       (const uint64_t*)(E.keep ? s.lmask : nullptr), E.keep ? s.wside : (float*)nullptr);                                 \
+    launched = true; } } while (0)
+  FMX_SMALL1(8, 8);    FMX_SMALL1(16, 16);  FMX_SMALL1(32, 32);
+  FMX_SMALL1(64, 16);  FMX_SMALL1(64, 40);  FMX_SMALL1(64, 64);
+  FMX_SMALL1(128, 16); FMX_SMALL1(128, 40); FMX_SMALL1(128, 64);
+#undef FMX_SMALL1
+  if (!launched) return fail(h, FMX_E_STATE, "no one-launch instance for %d factors and %d row slots", h->KP, E.szr);   // (every width the epoch admits has its instances)
+  HIPCHK(h, hipGetLastError());
+  h->small_one_used = true;
+  h->run_status |= FMX_STAT_SMALL_ONE;
+  return FMX_OK;
+}
+// the example pass of batch b (k_fused<FUSED_EXACT>) into the batch's half of the scratch; leaves the batch's deferred list in *sw
+static int fused_examples(const FusedEpoch& E, uint64_t b, const double* w0_in, float* rest, SegWork* sw, EpochCounts* n) {
+  fmx_handle h = E.h; const Slot& s = *E.s;
+  float* S = h->partial + (size_t)(b & 1) * E.Bc * (size_t)(h->KP + 1);
+  float* mult = h->mult + (size_t)(b & 1) * E.Bc;
+  int rc = FMX_OK;
+  KP_SWITCH(h->KP, { rc = launch_fused_zr<KP, FUSED_EXACT>(h, s, E.hy, b * E.B, rows_of_batch(E, b), h->stream, w0_in, rest, s.cmask, S, mult,
+                                                             E.handoff ? h->handoff_err : nullptr, E.keep); });
   if (rc) return rc;
+  HIPCHK(h, hipGetLastError());
+  *sw = seg_work(h, s, (size_t)b, S, mult);
+  n->deferred += sw->nseg;
+  return FMX_OK;
+}
+// small batches (what the stability cut leaves of data with frequent features): a batch is a few microseconds of work, so
+// the recurrence leaves the side stream and rides in the launch of the deferred features (k_apply_seg_scan) -- no events, two
+// launches per batch.  Same rule, same ring of bias slots: what a batch reads does not depend on which stream wrote it.
+static int fused_batch_in_stream(const FusedEpoch& E, uint64_t b, EpochCounts* n) {
+  fmx_handle h = E.h; const Slot& s = *E.s;
+  const uint32_t d = E.d;
+  float* rest = h->rest + (size_t)(b % d) * E.Bc;
+  SegWork sw;
+  int rc = fused_examples(E, b, h->w0_pp + ((b + 1) % d), rest, &sw, n); if (rc) return rc;   // (the bias of batch b - d; the initial one for b < d)
+  // deferred features and bias recurrence in ONE launch (one workgroup per four segments + one for the recurrence)
+  const ScanSmall sc{rest, s.target + b * E.B, h->w0_pp + (b % d), h->w0_pp + ((b + 1) % d), rows_of_batch(E, b), E.chunk};
+  KP_SWITCH(h->KP, hipLaunchKernelGGL((k_apply_seg_scan<KP, 8, 1>), dim3((sw.nseg + 3) / 4 + 1), dim3(256), 0, h->stream, sw, h->tb, E.hy, sc));
+  HIPCHK(h, hipGetLastError());
+  return FMX_OK;
+}
+// large batches: the recurrence runs on the side stream.  handoff (default; FMX_HANDOFF=0 at fmx_create goes back to events): the two
+// streams are ordered by the DATA -- bias slots W[0 .. n_batch] that start as "pending", a counter the deferred-feature launch of a batch
+// advances (fmx_kernels.h: "Device-side hand-off") -- instead of four event packets per batch; W[i] = the bias after the recurrence of batch
+// i - 1, k_fused of batch b reads W[max(0, b - d + 1)], the recurrence of batch b reads W[b] and publishes W[b + 1].
+static int fused_batch_side(const FusedEpoch& E, uint64_t b, EpochCounts* n) {
+  fmx_handle h = E.h; const Slot& s = *E.s; const Hyper& hy = E.hy;
+  hipStream_t st = h->stream;
+  const uint32_t d = E.d, nb = rows_of_batch(E, b);
+  const uint64_t row0 = b * E.B;
+  const bool handoff = E.handoff;
+  // rest buffers: with events the launch of batch b waits for the recurrence of batch b - d, which was the last reader of buffer b % d;
+  // with the hand-off k_fused writes rest[] BEFORE it asks for that bias, so it takes a buffer whose reader (batch b - d - 1) is known
+  // to be done: every wavefront of the previous launch has consumed its result
+  float* rest = h->rest + (size_t)(handoff ? b % (d + 1) : b % d) * E.Bc;
+  if (!handoff && b >= d) HIPCHK(h, hipStreamWaitEvent(st, h->ev_sync[2 * (b - d) + 1], 0));   // recurrence of batch b - d is done
+  const double* w0_in = handoff ? E.W + (b + 1 >= d ? b + 1 - d : 0)
+                                : h->w0_pp + ((b + 1) % d);    // written by the recurrence of batch b - d (initial bias for b < d)
+  SegWork sw;
+  int rc = fused_examples(E, b, w0_in, rest, &sw, n); if (rc) return rc;
+  if (!handoff) HIPCHK(h, hipEventRecord(h->ev_sync[2 * b], st));
+  if (handoff) { sw.done_ctr = h->handoff_ctr; sw.done_val = E.hbase + b + 1; }
+  if (handoff && !sw.nseg) hipLaunchKernelGGL(k_handoff_signal, dim3(1), dim3(64), 0, st, h->handoff_ctr, E.hbase + b + 1);
+  if (sw.nseg) {
+    // segments per wavefront of the deferred-feature pass: 16 (measured best at the bench shape: 8 / 16 / 32 / 64 -> 244.5 / 245.0 /
+    // 243.0 / 241.0 M examples/s), fewer when the list is short so that the pass still spreads over the chip
+    // (rows in flight per round: 8; round 6 measured 4 / 8 / 16 at the bench shape: 274.7 / 274.3 / 267.2 M examples/s)
+    if (sw.nseg >= 16u * 2048u)     { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_apply_seg<KP, 8, 16>), ((uint64_t)sw.nseg + 15) / 16, st, sw, h->tb, hy)); }
+    else if (sw.nseg >= 4u * 2048u) { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_apply_seg<KP, 8, 4>), ((uint64_t)sw.nseg + 3) / 4, st, sw, h->tb, hy)); }
+    else                            { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_apply_seg<KP, 8, 1>), (uint64_t)sw.nseg, st, sw, h->tb, hy)); }
+    HIPCHK(h, hipGetLastError());
+  }
+  if (handoff)
+    return launch_scan(h, rest, s.target + row0, nb, E.chunk, hy, nullptr, h->stream2, E.W + b, E.W + b + 1,
+                       Handoff{h->handoff_ctr, E.hbase + b + 1, h->handoff_err});
+  HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_sync[2 * b], 0));
+  rc = launch_scan(h, rest, s.target + row0, nb, E.chunk, hy, nullptr, h->stream2, h->w0_pp + (b % d), h->w0_pp + ((b + 1) % d)); if (rc) return rc;
+  HIPCHK(h, hipEventRecord(h->ev_sync[2 * b + 1], h->stream2));
+  return FMX_OK;
+}
+static int sgd_epoch_fused(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, const Hyper& hy, EpochCounts* n) {
+  FusedEpoch E{h, &s, hy};
+  const uint32_t B = E.B = opts->batch;                     // resolved by the caller (sgd_resolve_batch)
+  const uint32_t d = E.d = opts->bias_lag ? opts->bias_lag : 1u;
+  if (d > 4) return fail(h, FMX_E_ARG, "bias_lag %u: at most 4 batches", d);
+  E.chunk = opts->w0_chunk ? opts->w0_chunk : default_w0_chunk(h->cfg);
+  int rc = ensure_segments(h, s, B); if (rc) return rc;
   // FMX_FLAG_KEEP_WSIDE: this epoch keeps the slot's weight side stream current (for the evaluation passes that follow it)
   const bool keep_wside = (opts->flags & FMX_FLAG_KEEP_WSIDE) && hy.k1 && h->cfg.shard_world == 1 && s.blocks.empty();
   if (keep_wside) { rc = ensure_wside(h, s); if (rc) return rc; }
-  const bool keep = keep_wside && s.wside != nullptr;
-  *kept_wside = keep;
-  const uint32_t Bc = std::min<uint32_t>(B, s.n_rows);
-  rc = ensure_scratch(h, (size_t)Bc * 2, (size_t)Bc * (d + 1));       // S / mult of two consecutive batches, d (+ 1: hand-off) rest buffers
-  if (rc) return rc;
-  const uint64_t n_batch = ((uint64_t)s.n_rows + B - 1) / B;
-  // small batches (what the stability cut leaves of data with frequent features): a batch is a few microseconds of work, so
-  // the recurrence leaves the side stream and rides in the launch of the deferred features (k_apply_seg_scan) -- no events, two
-  // launches per batch.  Same rule, same ring of bias slots: what a batch reads does not depend on which stream wrote it.
-  const bool side = B >= 32768u;
-  // large batches: the recurrence runs on the side stream.  handoff (default; FMX_HANDOFF=0 at fmx_create goes back to events): the two
-  // streams are ordered by the DATA -- bias slots W[0 .. n_batch] that start as "pending", a counter the deferred-feature launch of a batch
-  // advances (fmx_kernels.h: "Device-side hand-off") -- instead of four event packets per batch; W[i] = the bias after the recurrence of batch
-  // i - 1, k_fused of batch b reads W[max(0, b - d + 1)], the recurrence of batch b reads W[b] and publishes W[b + 1].
-  // (bias_lag 1 keeps the events: there every wavefront of k_fused WAITS for a slot the one-workgroup recurrence of the previous batch
-  //  publishes, and nothing guarantees that kernel a CU once k_fused has filled the chip -- round-4 advisor; at lag >= 2 the slot is a batch old)
+  n->kept_wside = E.keep = keep_wside && s.wside != nullptr;
+  const uint32_t Bc = E.Bc = std::min<uint32_t>(B, s.n_rows);
+  rc = ensure_scratch(h, (size_t)Bc * 2, (size_t)Bc * (d + 1)); if (rc) return rc;   // S / mult of two consecutive batches, d (+ 1: hand-off) rest buffers
+  const uint64_t n_batch = E.n_batch = ((uint64_t)s.n_rows + B - 1) / B;
+  const bool side = B >= FMX_SIDE_STREAM_BATCH;             // (below: fused_batch_in_stream / fused_batch_one_launch)
+  // the hand-off of fused_batch_side.  bias_lag 1 keeps the events: there every wavefront of k_fused WAITS for a slot the one-workgroup
+  // recurrence of the previous batch publishes, and nothing guarantees that kernel a CU once k_fused has filled the chip -- round-4 advisor;
+  // at lag >= 2 the slot is a batch old
   // ... and only where the two streams really run side by side (streams_concurrent: probed once per handle): under serialised dispatch the
   // waits of the hand-off are satisfied by LATER launches and every batch would run into its bound
-  const bool handoff = side && h->handoff && hy.k0 && d >= 2 && !(opts->flags & FMX_FLAG_EVENT_SYNC) && streams_concurrent(h);
+  const bool handoff = E.handoff = side && h->handoff && hy.k0 && d >= 2 && !(opts->flags & FMX_FLAG_EVENT_SYNC) && streams_concurrent(h);
   if (side && hy.k0 && !handoff) h->run_status |= FMX_STAT_EVENT_SYNC;
   if (!side && hy.k0) h->run_status |= FMX_STAT_SCAN_SERIAL;
-  double* W = nullptr;
-  unsigned long long hbase = 0;
   if (handoff) {
     if (h->w0_slots_cap < n_batch + 1) {
       if (h->w0_slots) HIPCHK(h, fmx_dev_free(h->w0_slots));
@@ -742,161 +885,41 @@ static int sgd_epoch_fused(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, cons
       HIPCHK(h, fmx_dev_alloc(&h->w0_slots, (size_t)(n_batch + 1) * sizeof(double)));
       h->w0_slots_cap = n_batch + 1;
     }
-    W = h->w0_slots;
-    hbase = h->handoff_seq; h->handoff_seq += n_batch + 1;           // the counter only grows: no reset to order against the side stream
+    E.W = h->w0_slots;
+    E.hbase = h->handoff_seq; h->handoff_seq += n_batch + 1;         // the counter only grows: no reset to order against the side stream
   }
   if (side && !handoff) while (h->ev_sync.size() < 2 * n_batch + 1) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->ev_sync.push_back(e); }
   hipStream_t st = h->stream;
   HIPCHK(h, hipEventRecord(h->ev0, st));                    // do not bill the one-time bucketing to the epoch
   for (uint32_t r = 0; r < d; r++) HIPCHK(h, hipMemcpyAsync(h->w0_pp + r, h->w0, sizeof(double), hipMemcpyDeviceToDevice, st));
   if (handoff) {
-    hipLaunchKernelGGL(k_handoff_arm, dim3((unsigned)std::min<uint64_t>((n_batch + 255) / 256, 64)), dim3(256), 0, st, W, (uint32_t)n_batch);
-    HIPCHK(h, hipMemcpyAsync(W, h->w0, sizeof(double), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_handoff_arm, dim3((unsigned)std::min<uint64_t>((n_batch + 255) / 256, 64)), dim3(256), 0, st, E.W, (uint32_t)n_batch);
+    HIPCHK(h, hipMemcpyAsync(E.W, h->w0, sizeof(double), hipMemcpyDeviceToDevice, st));
   }
-  auto seg_work = [&](uint64_t b, SegWork* sw) {                 // the deferred features of batch b
-    const uint32_t c0 = s.cbatch[(size_t)b], c1 = s.cbatch[(size_t)b + 1];
-    const uint32_t s0 = s.batch_seg[(size_t)b], s1 = s.batch_seg[(size_t)b + 1];
-    const uint64_t base = s.batch_base[(size_t)b];
-    sw->t_ent = s.t_ent + base; sw->seg_feat = s.seg_feat + s0; sw->seg_rel = s.seg_rel + s0; sw->seg_idx = s.cseg + c0;
-    sw->nseg = c1 - c0; sw->nseg_batch = s1 - s0; sw->batch_nnz = (uint32_t)(s.batch_base[(size_t)b + 1] - base);
-    sw->S = h->partial + (size_t)(b & 1) * Bc * (size_t)(h->KP + 1);
-    sw->mult = h->mult + (size_t)(b & 1) * Bc;
-    sw->cdesc = s.cdesc + c0;
-    sw->done_ctr = nullptr; sw->done_val = 0ull;
-  };
-  // small batches as ONE launch per batch across all dies (k_small_one, fmx_small_kernels.h; FMX_SMALL_ONE=0 at fmx_create: two launches)
   const bool small_one = !side && h->small_one && (h->KP == 8 || h->KP == 16 || h->KP == 32 || h->KP == 64 || h->KP == 128) && s.cdesc && Bc <= SMALL_ONE_MAX && !hy.sgda;
-  int szr = 0, small_cap = 0;
   if (small_one) {
-    if (h->KP < 64) szr = h->KP;                                  // (k <= 32: 64 / KP entries per row slot, KP slots hold any row of <= 64 entries)
+    if (h->KP < 64) E.szr = h->KP;                                // (k <= 32: 64 / KP entries per row slot, KP slots hold any row of <= 64 entries)
     else {
-      szr = (h->KP == 64) ? fused_zr_select<64>(s.max_row) : fused_zr_select<128>(s.max_row);
-      if (szr == 8) szr = 16;                                     // (three instances per row width: 16, 40, 64 row slots)
-      if (szr == 32) szr = 40;
+      E.szr = (h->KP == 64) ? fused_zr_select<64>(s.max_row) : fused_zr_select<128>(s.max_row);
+      if (E.szr == 8) E.szr = 16;                                 // (three instances per row width: 16, 40, 64 row slots)
+      if (E.szr == 32) E.szr = 40;
     }
     if (!h->small_slots) HIPCHK(h, fmx_dev_alloc(&h->small_slots, ((size_t)3 * SMALL_ONE_MAX + 16) * sizeof(unsigned long long)));
     HIPCHK(h, hipMemsetAsync(h->small_slots, 0, (size_t)3 * SMALL_ONE_MAX * sizeof(unsigned long long), st));
     // ... and the tagged S_e elements (the scratch may hold anything, e.g. last epoch's elements under the same tags)
     HIPCHK(h, hipMemsetAsync(h->partial, 0, (size_t)Bc * (size_t)h->KP * sizeof(unsigned long long), st));
-  }
-  // FMX_SMALL_TRACE=<file>: device time stamps of the epoch's middle batch (fmx_small_kernels.h SmallSync::trace), appended to the file
-  static const char* small_trace_file = getenv("FMX_SMALL_TRACE");
-  unsigned long long* small_trace = nullptr;
-  if (small_one && small_trace_file) {
-    small_trace = h->small_slots + (size_t)3 * SMALL_ONE_MAX;
-    unsigned long long init[16];
-    for (int i = 0; i < 16; i++) init[i] = (i == 0 || i == 5) ? ~0ull : 0ull;
-    HIPCHK(h, hipMemcpyAsync(small_trace, init, sizeof(init), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));
+    rc = small_trace_arm(h, st, &E.small_trace); if (rc) return rc;
   }
   for (uint64_t b = 0; b < n_batch; b++) {
-    const uint64_t row0 = b * B;
-    const uint32_t nb = (uint32_t)std::min<uint64_t>(B, s.n_rows - row0);
-    if (small_one) {
-      SegWork sw;
-      seg_work(b, &sw);
-      *deferred += sw.nseg;
-      float* S = h->partial;                                      // [nb][KP] x {tag, value}: 8 bytes per element (the two batches' worth of the scratch)
-      sw.S = S;
-      // the recurrence: at lag >= 2 one launch behind (k_small_one), the last launch catches up
-      const bool defer = d >= 2u;
-      const bool own = !defer || b + 1 == n_batch, prev = defer && b >= 1;
-      const ScanSmall sc{nullptr, s.target + row0, h->w0_pp + (b % d), h->w0_pp + ((b + 1) % d), own ? nb : 0u, chunk};
-      const ScanSmall sc_prev{nullptr, s.target + (prev ? row0 - B : 0), h->w0_pp + ((b + d - 1) % d), h->w0_pp + (b % d), prev ? B : 0u, chunk};
-      unsigned long long* rs0 = h->small_slots + SMALL_ONE_MAX;
-      const SmallSync sy{h->small_slots, rs0 + (size_t)(b & 1) * SMALL_ONE_MAX, rs0 + (size_t)((b + 1) & 1) * SMALL_ONE_MAX, (uint32_t)(b + 1), (uint32_t)b,
-                         h->handoff_err, std::min<uint32_t>(h->pit_spins, 1u << 21), (small_trace && b == n_batch / 2) ? small_trace : nullptr};
-      const uint32_t n_ex_wg = (nb + 3u) / 4u;
-      bool launched = false;
-#define FMX_SMALL1(KPV, ZRV) do { if (h->KP == KPV && szr == ZRV) {                                                                      \
-        auto kf = k_small_one<KPV, ZRV>;                                                                                                   \
-        if (!small_cap) {                                                                                                                  \
-          int per_cu = 0;                                                                                                                  \
-          if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kf, 256, 0) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; } \
-          small_cap = std::max(1, per_cu * h->num_cu);                                                                                     \
-        }                                                                                                                                  \
-        const uint32_t room = (uint32_t)small_cap > n_ex_wg + 1u ? (uint32_t)small_cap - n_ex_wg - 1u : 1u;                                \
-        const uint32_t own_wg = sw.nseg ? std::max(1u, std::min((sw.nseg + 3u) / 4u, room)) : 0u;                                          \
-        hipLaunchKernelGGL(kf, dim3(n_ex_wg + own_wg + 1u), dim3(256), 0, st, s.ent, s.row_ptr, s.target, row0, nb, h->tb, hy,             \
-                           (const double*)(h->w0_pp + ((b + 1) % d)), (const uint64_t*)s.cmask, S, s.fixed_nnz, sw, sc_prev, sc, sy, n_ex_wg,  \
-                           (const uint64_t*)(keep ? s.lmask : nullptr), keep ? s.wside : (float*)nullptr);                                 \
-        launched = true; } } while (0)
-      FMX_SMALL1(8, 8);    FMX_SMALL1(16, 16);  FMX_SMALL1(32, 32);
-      FMX_SMALL1(64, 16);  FMX_SMALL1(64, 40);  FMX_SMALL1(64, 64);
-      FMX_SMALL1(128, 16); FMX_SMALL1(128, 40); FMX_SMALL1(128, 64);
-#undef FMX_SMALL1
-      if (launched) {
-        HIPCHK(h, hipGetLastError());
-        h->small_one_used = true;
-        h->run_status |= FMX_STAT_SMALL_ONE;
-        (*batches)++; (*launches)++;
-        continue;
-      }
-    }
-    // rest buffers: with events the launch of batch b waits for the recurrence of batch b - d, which was the last reader of buffer b % d;
-    // with the hand-off k_fused writes rest[] BEFORE it asks for that bias, so it takes a buffer whose reader (batch b - d - 1) is known
-    // to be done: every wavefront of the previous launch has consumed its result
-    float* rest = h->rest + (size_t)(handoff ? b % (d + 1) : b % d) * Bc;
-    float* S = h->partial + (size_t)(b & 1) * Bc * (size_t)(h->KP + 1);
-    float* mult = h->mult + (size_t)(b & 1) * Bc;
-    if (side && !handoff && b >= d) HIPCHK(h, hipStreamWaitEvent(st, h->ev_sync[2 * (b - d) + 1], 0));   // recurrence of batch b - d is done
-    const double* w0_in = handoff ? W + (b + 1 >= d ? b + 1 - d : 0)
-                                  : h->w0_pp + ((b + 1) % d);  // written by the recurrence of batch b - d (initial bias for b < d)
-    KP_SWITCH(h->KP, { rc = launch_fused_zr<KP, FUSED_EXACT>(h, s, hy, row0, nb, st, w0_in, rest, s.cmask, S, mult, handoff ? h->handoff_err : nullptr, keep); });
-    if (rc) return rc;
-    HIPCHK(h, hipGetLastError());
-    if (side && !handoff) HIPCHK(h, hipEventRecord(h->ev_sync[2 * b], st));
-    SegWork sw;                                              // the batch's deferred features
-    seg_work(b, &sw);
-    *deferred += sw.nseg;
-    if (!side) {
-      // small batch: deferred features and bias recurrence in ONE launch (one workgroup per four segments + one for the recurrence)
-      const ScanSmall sc{rest, s.target + row0, h->w0_pp + (b % d), h->w0_pp + ((b + 1) % d), nb, chunk};
-      const uint32_t grid = (sw.nseg + 3) / 4 + 1;
-      KP_SWITCH(h->KP, hipLaunchKernelGGL((k_apply_seg_scan<KP, 8, 1>), dim3(grid), dim3(256), 0, st, sw, h->tb, hy, sc));
-      HIPCHK(h, hipGetLastError());
-    } else {
-      if (handoff) { sw.done_ctr = h->handoff_ctr; sw.done_val = hbase + b + 1; }
-      if (handoff && !sw.nseg) hipLaunchKernelGGL(k_handoff_signal, dim3(1), dim3(64), 0, st, h->handoff_ctr, hbase + b + 1);
-      if (sw.nseg) {
-        // segments per wavefront of the deferred-feature pass: 16 (measured best at the bench shape: 8 / 16 / 32 / 64 -> 244.5 / 245.0 /
-        // 243.0 / 241.0 M examples/s), fewer when the list is short so that the pass still spreads over the chip
-        // (rows in flight per round: 8; round 6 measured 4 / 8 / 16 at the bench shape: 274.7 / 274.3 / 267.2 M examples/s)
-        if (sw.nseg >= 16u * 2048u)     { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_apply_seg<KP, 8, 16>), ((uint64_t)sw.nseg + 15) / 16, st, sw, h->tb, hy)); }
-        else if (sw.nseg >= 4u * 2048u) { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_apply_seg<KP, 8, 4>), ((uint64_t)sw.nseg + 3) / 4, st, sw, h->tb, hy)); }
-        else                            { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_apply_seg<KP, 8, 1>), (uint64_t)sw.nseg, st, sw, h->tb, hy)); }
-        HIPCHK(h, hipGetLastError());
-      }
-      if (handoff) {
-        rc = launch_scan(h, rest, s.target + row0, nb, chunk, hy, nullptr, h->stream2, W + b, W + b + 1,
-                         Handoff{h->handoff_ctr, hbase + b + 1, h->handoff_err});
-        if (rc) return rc;
-      } else {
-        HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_sync[2 * b], 0));
-        rc = launch_scan(h, rest, s.target + row0, nb, chunk, hy, nullptr, h->stream2, h->w0_pp + (b % d), h->w0_pp + ((b + 1) % d));
-        if (rc) return rc;
-        HIPCHK(h, hipEventRecord(h->ev_sync[2 * b + 1], h->stream2));
-      }
-    }
-    (*batches)++; (*launches)++;
+    rc = small_one ? fused_batch_one_launch(E, b, n) : side ? fused_batch_side(E, b, n) : fused_batch_in_stream(E, b, n); if (rc) return rc;
+    n->batches++; n->launches++;
   }
-  if (small_trace) {
-    unsigned long long tr[16];
-    HIPCHK(h, hipMemcpyAsync(tr, small_trace, sizeof(tr), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    if (FILE* f = fopen(small_trace_file, "a")) {
-      const double t0 = (double)tr[0];
-      fprintf(f, "batch %llu of %llu (ns after the first example started): last example started %.0f, rows gathered %.0f, multiplier published %.0f, example done %.0f | "
-                 "first owner started %.0f, last owner saw its tags %.0f, holds its S rows %.0f, done %.0f | recurrence done %.0f | last owner started %.0f, has its entry list %.0f\n",
-              (unsigned long long)(n_batch / 2), (unsigned long long)n_batch, tr[1] - t0, tr[2] - t0, tr[3] - t0, tr[4] - t0, (double)tr[5] - t0, tr[6] - t0, tr[7] - t0, tr[8] - t0, tr[9] - t0, tr[10] - t0, tr[11] - t0);
-      fclose(f);
-    }
-  }
+  if (E.small_trace) { rc = small_trace_dump(h, st, E.small_trace, n_batch); if (rc) return rc; }
   if (handoff) {                                              // ONE event per epoch: the last recurrence, then the bias goes home
     if (h->ev_sync.empty()) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->ev_sync.push_back(e); }
     HIPCHK(h, hipEventRecord(h->ev_sync[0], h->stream2));
     HIPCHK(h, hipStreamWaitEvent(st, h->ev_sync[0], 0));
-    HIPCHK(h, hipMemcpyAsync(h->w0, W + n_batch, sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->w0, E.W + n_batch, sizeof(double), hipMemcpyDeviceToDevice, st));
     HIPCHK(h, hipMemcpyAsync(&h->handoff_err_host, h->handoff_err, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     return FMX_OK;
   }
@@ -1047,9 +1070,196 @@ static int seq_runs_epoch(fmx_handle h, Slot& s, const Hyper& hy) {
   return FMX_OK;
 }
 
+// ---- fmx_sgd_epoch: one driver per mode (epoch_sequential, epoch_hogwild, epoch_split, sgd_epoch_fused), then epoch_close ----
+static int epoch_sequential(fmx_handle h, Slot& s, const Hyper& hy, EpochCounts* n) {
+  // rows of 64 / 128 lanes: a row at a time with the next example's rows in flight (fmx_seq_kernels.h: 20 k -> ~1 M examples/s on the
+  // reference's own trajectory); FMX_SEQ_ROWS=0 and the other row widths: entry by entry
+  const bool seq_rows = h->seq_rows, seq_wg = h->seq_wg;      // (FMX_SEQ_ROWS / FMX_SEQ_WG: read by fmx_create)
+  // where consecutive rows rarely share a feature: the same trajectory as conflict-free runs at batch speed (fmx_seq_kernels.h); taken when
+  // the slot's runs average >= 16 rows (FMX_SEQ_RUNS=0: never, =1: always)
+  const char* sr = getenv("FMX_SEQ_RUNS");
+  bool use_runs = !(sr && sr[0] == '0');
+  int rc = FMX_OK;
+  if (use_runs) {
+    rc = ensure_runs(h, s); if (rc) return rc;
+    const size_t n_runs = s.run_start.size() - 1;
+    use_runs = !(s.run_single.size() == 1 && s.run_single[0] == 2) && ((sr && sr[0] == '1') || (uint64_t)s.n_rows >= 16ull * n_runs);
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));             // (the one-time cut is not the epoch's time)
+  }
+  if (use_runs) {
+    rc = seq_runs_epoch(h, s, hy); if (rc) return rc;
+    h->run_status |= FMX_STAT_SEQ_RUNS;
+  } else if (seq_rows && seq_wg && h->KP <= 128) {
+    // eight wavefronts on each example (fmx_seq_kernels.h k_sequential_wg); FMX_SEQ_WG=0: one wavefront, a row at a time.
+    // Fewer than 33 factors run the 64-lane instance too: a row access masks the lanes beyond the row (tb.rs), whatever the lane mapping
+    auto kf = h->KP <= 64 ? k_sequential_wg<64> : k_sequential_wg<128>;
+    const size_t lds = h->KP <= 64 ? sizeof(SeqLds<64>) : sizeof(SeqLds<128>);
+    FMX_RAISE_LDS(kf, lds);
+    hipLaunchKernelGGL(kf, dim3(1), dim3(64 * SEQ_W), lds, h->stream, s.ent, s.row_ptr, s.target, s.n_rows, s.nnz, h->tb, hy, h->w0);
+    h->run_status |= FMX_STAT_SEQ_WG;
+  } else if (seq_rows && h->KP <= 128) {
+    h->run_status |= FMX_STAT_SEQ_ROWS;
+    const bool wide = s.max_row > 32u;
+    auto kf = h->KP <= 64 ? (wide ? k_sequential_rows<64, 64> : k_sequential_rows<64, 32>) : (wide ? k_sequential_rows<128, 64> : k_sequential_rows<128, 32>);
+    hipLaunchKernelGGL(kf, dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr, s.target, s.n_rows, h->tb, hy, h->w0);
+  } else {
+    KP_SWITCH(h->KP, hipLaunchKernelGGL((k_sequential<KP>), dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr,
+                                          s.target, s.n_rows, h->tb, hy, h->w0));
+    h->run_status |= FMX_STAT_SEQ_ENTRIES;
+  }
+  HIPCHK(h, hipGetLastError());
+  n->batches = use_runs ? s.run_start.size() - 1 : s.n_rows;
+  n->launches = 1;
+  return FMX_OK;
+}
+static int epoch_hogwild(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, const Hyper& hy, EpochCounts* n) {
+  if (opts->apply == FMX_APPLY_SEGMENTED) return fail(h, FMX_E_ARG, "HOGWILD has no segmented apply");
+  // rows per launch M: w0 is frozen inside a launch.  The bias recurrence of launch i (k_scan, one wavefront) runs
+  // on a side stream WHILE launches i+1, i+2 stream; launch i reads the w0 produced by scan i-3 (a ring of 3
+  // slots / rest buffers, so the result does not depend on timing and a slow scan has two launches of slack).
+  const uint32_t M = opts->batch ? opts->batch : 262144u;
+  const uint32_t chunk = opts->w0_chunk ? opts->w0_chunk : default_w0_chunk(h->cfg);
+  const uint32_t cap = std::min<uint32_t>(M, s.n_rows);
+  int rc = ensure_scratch(h, 0, (size_t)cap * 3); if (rc) return rc;
+  const uint64_t n_launch = ((uint64_t)s.n_rows + M - 1) / M;
+  while (h->ev_sync.size() < 2 * n_launch) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->ev_sync.push_back(e); }
+  for (int r = 0; r < 3; r++) HIPCHK(h, hipMemcpyAsync(h->w0_pp + r, h->w0, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  for (uint64_t i = 0; i < n_launch; i++) {
+    const uint64_t row0 = i * M;
+    const uint32_t nb = (uint32_t)std::min<uint64_t>(M, s.n_rows - row0);
+    float* rest = h->rest + (size_t)(i % 3) * cap;
+    hipStream_t fs = h->stream;
+    if (i >= 3) HIPCHK(h, hipStreamWaitEvent(fs, h->ev_sync[2 * (i - 3) + 1], 0));   // scan i-3 done
+    // (no per-launch events here: a timing event between two launches costs ~13 % on this path; the epoch is
+    //  bracketed by ev0/ev1 on the launch stream and the average launch time is epoch time / launches)
+    n->launches++;
+    const double* w0_in = h->w0_pp + ((i + 1) % 3);      // slot written by scan i-3 (initial value for i < 3)
+    if (opts->apply == FMX_APPLY_ATOMIC) {
+      KP_SWITCH(h->KP, { rc = launch_fused_zr<KP, FUSED_ATOMIC>(h, s, hy, row0, nb, fs, w0_in, rest); });
+    } else {
+      KP_SWITCH(h->KP, { rc = launch_fused_zr<KP, FUSED_STORE>(h, s, hy, row0, nb, fs, w0_in, rest); });
+    }
+    if (rc) return rc;
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev_sync[2 * i], fs));
+    HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_sync[2 * i], 0));
+    rc = launch_scan(h, rest, s.target + row0, nb, chunk, hy, nullptr, h->stream2, h->w0_pp + (i % 3), h->w0_pp + ((i + 1) % 3)); if (rc) return rc;
+    HIPCHK(h, hipEventRecord(h->ev_sync[2 * i + 1], h->stream2));
+    n->batches++;
+  }
+  // stream2 is in order: its last event covers every scan, and scan i waited for launch i
+  HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_sync[2 * (n_launch - 1) + 1], 0));
+  if (hy.k0) HIPCHK(h, hipMemcpyAsync(h->w0, h->w0_pp + (n_launch % 3), sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  return FMX_OK;
+}
+// the two-pass forms of the MINIBATCH rule on one handle: per batch the sums (k_rowsums leaves rest[] too), then the split step.
+// FMX_FLAG_TIME_MAIN_KERNEL: a pair of events from h->ev_pool around every batch's update (n->launches counts the pairs)
+static int epoch_split(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, EpochCounts* n) {
+  const uint32_t B = opts->batch;
+  const bool timed = (opts->flags & FMX_FLAG_TIME_MAIN_KERNEL) != 0;
+  const bool segmented = (opts->apply == FMX_APPLY_DEFAULT || opts->apply == FMX_APPLY_SEGMENTED);
+  const uint32_t lag_depth = opts->bias_lag ? opts->bias_lag : 1u;
+  if (lag_depth > 4) return fail(h, FMX_E_ARG, "bias_lag %u: at most 4 batches", lag_depth);
+  const uint32_t Bc = std::min<uint32_t>(B, s.n_rows);
+  int rc = ensure_scratch(h, (size_t)Bc * ((opts->flags & FMX_FLAG_BIAS_LAG) ? lag_depth + 1 : 1), 0); if (rc) return rc;
+  if (segmented) {
+    rc = ensure_segments(h, s, B); if (rc) return rc;
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));           // do not bill the one-time bucketing to the epoch
+  }
+  StepPlan plan = step_plan(h, s, opts, segmented ? 0 : -1, true);   // the same for every batch, its index aside
+  while (timed && h->ev_pool.size() < 2 * (((size_t)s.n_rows + B - 1) / B)) { hipEvent_t e; HIPCHK(h, hipEventCreate(&e)); h->ev_pool.push_back(e); }
+  for (uint64_t row0 = 0; row0 < s.n_rows; row0 += B) {
+    const uint32_t nb = (uint32_t)std::min<uint64_t>(B, s.n_rows - row0);
+    int pslot = 0;
+    if (plan.lag) { rc = lag_prepare(h, h->stream, plan, &pslot); if (rc) return rc; }
+    float* S = h->partial + (size_t)pslot * Bc * (size_t)(h->KP + 1);
+    float* rest = S + (size_t)nb * h->KP;
+    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, h->stream,
+                                       s.ent, s.row_ptr, row0, nb, h->tb, h->cfg.k1, S, rest, (const float*)nullptr));
+    hipEvent_t ea = nullptr, eb = nullptr;
+    if (timed) { ea = h->ev_pool[2 * n->launches]; eb = h->ev_pool[2 * n->launches + 1]; n->launches++; }
+    if (segmented) plan.seg_batch = (int64_t)(row0 / B);
+    rc = sgd_finish_impl(h, s, row0, nb, S, rest, nullptr, plan, h->stream, ea, eb); if (rc) return rc;
+    n->batches++;
+  }
+  return FMX_OK;
+}
+
+// the end of every epoch: drain, the bias back in h->w0, what the device's error word says about the epoch, the stats
+static int epoch_close(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, const fmx_batch_info& bi, const EpochCounts& n, fmx_epoch_stats* stats) {
+  if (h->lag.active)       // the last recurrence must finish inside the timed region; then w0 returns to h->w0
+    HIPCHK(h, hipStreamWaitEvent(h->stream, h->lag.ev_scan[(h->lag.step - 1) % LagState::RING], 0));
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipGetLastError());
+  int rc = lag_flush(h); if (rc) return rc;
+  rc = scan_error_check(h); if (rc) return rc;
+  uint32_t bits = 0;
+  // one launch per small batch / per conflict-free run of FMX_SGD_SEQUENTIAL: did every owner, the recurrence, every workgroup see its examples?
+  const struct { bool* used; bool* enabled; const char* text; } one_launch[2] = {
+    {&h->small_one_used, &h->small_one,
+     "a one-launch batch never saw all of its examples (the device is shared or partitioned): the features concerned took no "
+     "step (the parameters are valid numbers, the epoch is not the batch rule's) -- reload the parameters; the handle takes "
+     "two launches per batch from now on"},
+    {&h->run_one_used, &h->run_one,
+     "a conflict-free run never saw all of its workgroups (the device is shared or partitioned): the rows concerned took no "
+     "step (the parameters are valid numbers, the epoch is not the reference's) -- reload the parameters; the handle takes "
+     "two launches per run from now on"}};
+  for (const auto& o : one_launch) {
+    if (!*o.used) continue;
+    *o.used = false;
+    rc = take_error_bits(h, RUN_ERR_EXCHANGE, &bits); if (rc) return rc;
+    if (!bits) continue;
+    *o.enabled = false;
+    h->run_status |= FMX_STAT_HANDOFF_TIMEOUT;
+    if (stats) stats->status = bi.status | h->run_status;
+    return fail(h, FMX_E_HIP, "%s", o.text);
+  }
+  if (h->handoff_err_host & 3u) {
+    // a hand-off wait ran into its bound (the probe said the streams run side by side, and then they did not: the device is shared with
+    // work that starved one of them).  Nothing was computed from a bias that was not there: the examples concerned took no step, a
+    // recurrence that never saw its batch handed the bias on unchanged (fmx_kernels.h) -- every parameter is a valid number, but the
+    // epoch is not the rule's.  The handle orders its streams with events from now on.
+    const uint32_t e = h->handoff_err_host;
+    h->handoff_err_host = 0;
+    (void)take_error_bits(h, 3u, &bits);                        // (only the hand-off's own bits: bit 4 belongs to scan_error_check)
+    h->handoff = false;
+    h->run_status |= FMX_STAT_HANDOFF_TIMEOUT;
+    if (stats) stats->status = bi.status | h->run_status;
+    return fail(h, FMX_E_HIP, "the bias hand-off between the launch stream and the recurrence timed out (flags %u): the examples concerned took no "
+                              "step (the parameters are valid numbers, the epoch is not the batch rule's); the handle orders its streams with "
+                              "events from now on", e);
+  }
+  if (n.kept_wside) s.wside_version = h->w_version;          // the epoch is complete: the stream holds this w
+  if (stats) {
+    float ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    stats->rows = s.n_rows; stats->batches = n.batches; stats->device_seconds = ms * 1e-3;
+    if (opts->mode == FMX_SGD_MINIBATCH && s.seg_B) stats->max_feature_count = s.max_seg_count;
+    stats->deferred_features = n.deferred;
+    if (opts->mode == FMX_SGD_MINIBATCH || opts->mode == FMX_SGD_HOGWILD) {     // (HOGWILD: batch_used = the rows in flight)
+      stats->batch_used = bi.batch; stats->collision_mass = bi.collision_mass; stats->batch_gain = bi.batch_gain; stats->status = bi.status;
+    }
+    stats->status |= h->run_status;
+    stats->setup_seconds = h->setup_acc;
+    if (opts->mode != FMX_SGD_SEQUENTIAL) stats->w0_chunk_used = opts->w0_chunk ? opts->w0_chunk : default_w0_chunk(h->cfg);
+    stats->main_kernel_seconds = stats->device_seconds;
+    stats->main_kernel_launches = n.launches;
+    if (opts->mode == FMX_SGD_MINIBATCH && (opts->flags & FMX_FLAG_TIME_MAIN_KERNEL) && opts->apply != FMX_APPLY_FUSED) {
+      double tot = 0;                                           // epoch_split's event pairs
+      for (size_t i = 0; i < n.launches; i++) {
+        float m2 = 0;
+        HIPCHK(h, hipEventElapsedTime(&m2, h->ev_pool[2 * i], h->ev_pool[2 * i + 1]));
+        tot += m2 * 1e-3;
+      }
+      stats->main_kernel_seconds = tot;
+    }
+  }
+  return FMX_OK;
+}
+
 int fmx_sgd_epoch(fmx_handle h, int slot, const fmx_sgd_opts* opts, fmx_epoch_stats* stats) {
-  int rc = check_slot(h, slot, true);
-  if (rc) return rc;
+  int rc = check_slot(h, slot, true); if (rc) return rc;
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   if (!opts) return fail(h, FMX_E_ARG, "fmx_sgd_epoch: opts is NULL");
   HIPCHK(h, hipSetDevice(h->device));
@@ -1065,8 +1275,7 @@ int fmx_sgd_epoch(fmx_handle h, int slot, const fmx_sgd_opts* opts, fmx_epoch_st
   fmx_sgd_opts ropts = *opts;                               // MINIBATCH: `batch` resolved against the rows' collision mass
   fmx_batch_info bi; memset(&bi, 0, sizeof(bi));
   if (opts->mode == FMX_SGD_MINIBATCH) {
-    rc = sgd_resolve_batch(h, s, opts, &bi);
-    if (rc) return rc;
+    rc = sgd_resolve_batch(h, s, opts, &bi); if (rc) return rc;
     if ((opts->flags & FMX_FLAG_REJECT_UNSTABLE) && (bi.status & FMX_STAT_UNSTABLE)) {
       if (opts->batch == 0)       // the library's own choice is at its floor and still unstable: say THAT, not "let the library choose"
         return fail(h, FMX_E_ARG, "these rows are too dense for the batch rule: at the smallest batch the library takes (%u rows) learn_rate * "
@@ -1080,239 +1289,24 @@ int fmx_sgd_epoch(fmx_handle h, int slot, const fmx_sgd_opts* opts, fmx_epoch_st
   } else if (opts->mode == FMX_SGD_HOGWILD) {
     // the asynchronous step freezes nothing, but an update becomes visible only when its wavefront retires: the rows in flight
     // (5 wavefronts per SIMD x 4 SIMDs x CUs on this part, one example each) are the window the criterion of MINIBATCH applies to
-    rc = ensure_coll_mass(h, s);
-    if (rc) return rc;
+    rc = ensure_coll_mass(h, s); if (rc) return rc;
     const uint32_t in_flight = (uint32_t)std::min<uint64_t>(s.n_rows, (uint64_t)20 * (uint64_t)h->num_cu);
     resolve_batch(h->cfg, s.coll_mass, in_flight, in_flight, 1.0, &bi);
     if ((opts->flags & FMX_FLAG_REJECT_UNSTABLE) && (bi.status & FMX_STAT_UNSTABLE))
       return fail(h, FMX_E_ARG, "HOGWILD on these rows: learn_rate * curvature * %u rows in flight * collision mass = %.3g > 2 -- the asynchronous "
                                 "step diverges (collision mass %.4g; use FMX_SGD_MINIBATCH with batch 0)", in_flight, bi.batch_gain, bi.collision_mass);
   }
-  const bool timed = (opts->flags & FMX_FLAG_TIME_MAIN_KERNEL) != 0;
-  uint64_t batches = 0, main_launches = 0, deferred = 0;
-  bool kept_wside = false;
   touch_w(h);                                                // (every side stream is stale from here on; this epoch may re-validate ITS slot's)
-  size_t ev_used = 0;
-  auto get_event = [&](hipEvent_t* ev) -> hipError_t {
-    if (ev_used == h->ev_pool.size()) { hipEvent_t e; hipError_t er = hipEventCreate(&e); if (er != hipSuccess) return er; h->ev_pool.push_back(e); }
-    *ev = h->ev_pool[ev_used++];
-    return hipSuccess;
-  };
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  if (opts->mode == FMX_SGD_SEQUENTIAL) {
-    // rows of 64 / 128 lanes: a row at a time with the next example's rows in flight (fmx_seq_kernels.h: 20 k -> ~1 M examples/s on the
-    // reference's own trajectory); FMX_SEQ_ROWS=0 and the other row widths: entry by entry
-    const bool seq_rows = h->seq_rows;                          // (FMX_SEQ_ROWS / FMX_SEQ_WG: read by fmx_create)
-    // where consecutive rows rarely share a feature: the same trajectory as conflict-free runs at batch speed (fmx_seq_kernels.h); taken when
-    // the slot's runs average >= 16 rows (FMX_SEQ_RUNS=0: never, =1: always)
-    const char* sr = getenv("FMX_SEQ_RUNS");
-    bool use_runs = !(sr && sr[0] == '0');
-    if (use_runs) {
-      rc = ensure_runs(h, s);
-      if (rc) return rc;
-      const size_t n_runs = s.run_start.size() - 1;
-      use_runs = !(s.run_single.size() == 1 && s.run_single[0] == 2) && ((sr && sr[0] == '1') || (uint64_t)s.n_rows >= 16ull * n_runs);
-      HIPCHK(h, hipEventRecord(h->ev0, h->stream));             // (the one-time cut is not the epoch's time)
-    }
-    const bool seq_wg = h->seq_wg;
-    if (use_runs) {
-      rc = seq_runs_epoch(h, s, hy);
-      if (rc) return rc;
-      h->run_status |= FMX_STAT_SEQ_RUNS;
-      batches = s.run_start.size() - 1; main_launches = 1;
-    } else
-    if (seq_rows && seq_wg && h->KP <= 128) {
-      // eight wavefronts on each example (fmx_seq_kernels.h k_sequential_wg); FMX_SEQ_WG=0: one wavefront, a row at a time.
-      // Fewer than 33 factors run the 64-lane instance too: a row access masks the lanes beyond the row (tb.rs), whatever the lane mapping
-      if (h->KP <= 64) {
-        auto kf = k_sequential_wg<64>;
-        if (!h->lds_raised.count((const void*)kf)) { HIPCHK(h, hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SeqLds<64>))); h->lds_raised.insert((const void*)kf); }
-        hipLaunchKernelGGL(kf, dim3(1), dim3(64 * SEQ_W), sizeof(SeqLds<64>), h->stream, s.ent, s.row_ptr, s.target, s.n_rows, s.nnz, h->tb, hy, h->w0);
-      } else {
-        auto kf = k_sequential_wg<128>;
-        if (!h->lds_raised.count((const void*)kf)) { HIPCHK(h, hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SeqLds<128>))); h->lds_raised.insert((const void*)kf); }
-        hipLaunchKernelGGL(kf, dim3(1), dim3(64 * SEQ_W), sizeof(SeqLds<128>), h->stream, s.ent, s.row_ptr, s.target, s.n_rows, s.nnz, h->tb, hy, h->w0);
-      }
-      h->run_status |= FMX_STAT_SEQ_WG;
-    } else if (seq_rows && h->KP <= 128) {
-      h->run_status |= FMX_STAT_SEQ_ROWS;
-      const bool wide = s.max_row > 32u;
-      if (h->KP <= 64) { if (wide) hipLaunchKernelGGL((k_sequential_rows<64, 64>), dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr, s.target, s.n_rows, h->tb, hy, h->w0);
-                         else      hipLaunchKernelGGL((k_sequential_rows<64, 32>), dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr, s.target, s.n_rows, h->tb, hy, h->w0); }
-      else             { if (wide) hipLaunchKernelGGL((k_sequential_rows<128, 64>), dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr, s.target, s.n_rows, h->tb, hy, h->w0);
-                         else      hipLaunchKernelGGL((k_sequential_rows<128, 32>), dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr, s.target, s.n_rows, h->tb, hy, h->w0); }
-    } else {
-      KP_SWITCH(h->KP, hipLaunchKernelGGL((k_sequential<KP>), dim3(1), dim3(64), 0, h->stream, s.ent, s.row_ptr,
-                                            s.target, s.n_rows, h->tb, hy, h->w0));
-      h->run_status |= FMX_STAT_SEQ_ENTRIES;
-    }
-    HIPCHK(h, hipGetLastError());
-    if (!use_runs) batches = s.n_rows;
-    main_launches = 1;
-  } else if (opts->mode == FMX_SGD_HOGWILD) {
-    if (opts->apply == FMX_APPLY_SEGMENTED) return fail(h, FMX_E_ARG, "HOGWILD has no segmented apply");
-    // rows per launch M: w0 is frozen inside a launch.  The bias recurrence of launch i (k_scan, one wavefront) runs
-    // on a side stream WHILE launches i+1, i+2 stream; launch i reads the w0 produced by scan i-3 (a ring of 3
-    // slots / rest buffers, so the result does not depend on timing and a slow scan has two launches of slack).
-    const uint32_t M = opts->batch ? opts->batch : 262144u;
-    const uint32_t chunk = opts->w0_chunk ? opts->w0_chunk : default_w0_chunk(h->cfg);
-    const uint32_t cap = std::min<uint32_t>(M, s.n_rows);
-    rc = ensure_scratch(h, 0, (size_t)cap * 3);
-    if (rc) return rc;
-    const uint64_t n_launch = ((uint64_t)s.n_rows + M - 1) / M;
-    while (h->ev_sync.size() < 2 * n_launch) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->ev_sync.push_back(e); }
-    for (int r = 0; r < 3; r++) HIPCHK(h, hipMemcpyAsync(h->w0_pp + r, h->w0, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    for (uint64_t i = 0; i < n_launch; i++) {
-      const uint64_t row0 = i * M;
-      const uint32_t nb = (uint32_t)std::min<uint64_t>(M, s.n_rows - row0);
-      float* rest = h->rest + (size_t)(i % 3) * cap;
-      hipStream_t fs = h->stream;
-      if (i >= 3) HIPCHK(h, hipStreamWaitEvent(fs, h->ev_sync[2 * (i - 3) + 1], 0));   // scan i-3 done
-      hipEvent_t ea = nullptr, eb = nullptr;
-      // (no per-launch events here: a timing event between two launches costs ~13 % on this path; the epoch is
-      //  bracketed by ev0/ev1 on the launch stream and the average launch time is epoch time / launches)
-      main_launches++;
-      const double* w0_in = h->w0_pp + ((i + 1) % 3);      // slot written by scan i-3 (initial value for i < 3)
-      if (opts->apply == FMX_APPLY_ATOMIC) {
-        KP_SWITCH(h->KP, { rc = launch_fused_zr<KP, FUSED_ATOMIC>(h, s, hy, row0, nb, fs, w0_in, rest); });
-      } else {
-        KP_SWITCH(h->KP, { rc = launch_fused_zr<KP, FUSED_STORE>(h, s, hy, row0, nb, fs, w0_in, rest); });
-      }
-      if (rc) return rc;
-      HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipEventRecord(h->ev_sync[2 * i], fs));
-      HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_sync[2 * i], 0));
-      rc = launch_scan(h, rest, s.target + row0, nb, chunk, hy, nullptr, h->stream2, h->w0_pp + (i % 3), h->w0_pp + ((i + 1) % 3));
-      if (rc) return rc;
-      HIPCHK(h, hipEventRecord(h->ev_sync[2 * i + 1], h->stream2));
-      batches++;
-    }
-    // stream2 is in order: its last event covers every scan, and scan i waited for launch i
-    HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_sync[2 * (n_launch - 1) + 1], 0));
-    if (hy.k0) HIPCHK(h, hipMemcpyAsync(h->w0, h->w0_pp + (n_launch % 3), sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  } else if (opts->mode == FMX_SGD_MINIBATCH && opts->apply == FMX_APPLY_FUSED) {
-    rc = sgd_epoch_fused(h, s, opts, hy, &batches, &main_launches, &deferred, &kept_wside);
-    if (rc) return rc;
-  } else if (opts->mode == FMX_SGD_MINIBATCH) {
-    const uint32_t B = opts->batch;
-    const bool lag = (opts->flags & FMX_FLAG_BIAS_LAG) != 0;
-    const uint32_t lag_depth = opts->bias_lag ? opts->bias_lag : 1u;
-    if (lag_depth > 4) return fail(h, FMX_E_ARG, "bias_lag %u: at most 4 batches", lag_depth);
-    const uint32_t Bc = std::min<uint32_t>(B, s.n_rows);
-    rc = ensure_scratch(h, (size_t)Bc * (lag ? lag_depth + 1 : 1), 0);
-    if (rc) return rc;
-    const bool segmented = (opts->apply == FMX_APPLY_DEFAULT || opts->apply == FMX_APPLY_SEGMENTED);
-    if (segmented) {
-      rc = ensure_segments(h, h->slots[slot], B);
-      if (rc) return rc;
-      HIPCHK(h, hipEventRecord(h->ev0, h->stream));           // do not bill the one-time bucketing to the epoch
-    }
-    for (uint64_t row0 = 0; row0 < s.n_rows; row0 += B) {
-      const uint32_t nb = (uint32_t)std::min<uint64_t>(B, s.n_rows - row0);
-      int pslot = 0;
-      if (lag) { rc = lag_prepare(h, h->stream, lag_depth, &pslot); if (rc) return rc; }
-      float* S = h->partial + (size_t)pslot * Bc * (size_t)(h->KP + 1);
-      float* rest = S + (size_t)nb * h->KP;
-      KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, h->stream,
-                                         s.ent, s.row_ptr, row0, nb, h->tb, h->cfg.k1, S, rest, (const float*)nullptr));
-      hipEvent_t ea = nullptr, eb = nullptr;
-      if (timed) { HIPCHK(h, get_event(&ea)); HIPCHK(h, get_event(&eb)); main_launches++; }
-      rc = sgd_finish_impl(h, s, row0, nb, S, rest, opts, h->stream, ea, eb, segmented ? (int64_t)(row0 / B) : -1);
-      if (rc) return rc;
-      batches++;
-    }
-  } else {
-    return fail(h, FMX_E_ARG, "unknown SGD mode %d", opts->mode);
+  EpochCounts n;
+  switch (opts->mode) {
+    case FMX_SGD_SEQUENTIAL: rc = epoch_sequential(h, s, hy, &n); break;
+    case FMX_SGD_HOGWILD:    rc = epoch_hogwild(h, s, opts, hy, &n); break;
+    case FMX_SGD_MINIBATCH:  rc = opts->apply == FMX_APPLY_FUSED ? sgd_epoch_fused(h, s, opts, hy, &n) : epoch_split(h, s, opts, &n); break;
+    default: return fail(h, FMX_E_ARG, "unknown SGD mode %d", opts->mode);
   }
-  if (h->lag.active) {     // the last recurrence must finish inside the timed region; then w0 returns to h->w0
-    HIPCHK(h, hipStreamWaitEvent(h->stream, h->lag.ev_scan[(h->lag.step - 1) % LagState::RING], 0));
-  }
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hipGetLastError());
-  rc = lag_flush(h);
   if (rc) return rc;
-  rc = scan_error_check(h);
-  if (rc) return rc;
-  if (h->small_one_used) {                                      // one launch per small batch: did every owner / the recurrence see its examples?
-    h->small_one_used = false;
-    uint32_t e = 0;
-    HIPCHK(h, hipMemcpy(&e, h->handoff_err, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (e & RUN_ERR_EXCHANGE) {
-      const uint32_t rest_bits = e & ~RUN_ERR_EXCHANGE;
-      (void)hipMemcpy(h->handoff_err, &rest_bits, sizeof(uint32_t), hipMemcpyHostToDevice);
-      h->small_one = false;
-      h->run_status |= FMX_STAT_HANDOFF_TIMEOUT;
-      if (stats) stats->status = bi.status | h->run_status;
-      return fail(h, FMX_E_HIP, "a one-launch batch never saw all of its examples (the device is shared or partitioned): the features concerned took no "
-                                "step (the parameters are valid numbers, the epoch is not the batch rule's) -- reload the parameters; the handle takes "
-                                "two launches per batch from now on");
-    }
-  }
-  if (h->run_one_used) {                                        // one-launch runs of FMX_SGD_SEQUENTIAL: did every workgroup see its run arrive?
-    h->run_one_used = false;
-    uint32_t e = 0;
-    HIPCHK(h, hipMemcpy(&e, h->handoff_err, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (e & RUN_ERR_EXCHANGE) {
-      const uint32_t rest_bits = e & ~RUN_ERR_EXCHANGE;
-      (void)hipMemcpy(h->handoff_err, &rest_bits, sizeof(uint32_t), hipMemcpyHostToDevice);
-      h->run_one = false;
-      h->run_status |= FMX_STAT_HANDOFF_TIMEOUT;
-      if (stats) stats->status = bi.status | h->run_status;
-      return fail(h, FMX_E_HIP, "a conflict-free run never saw all of its workgroups (the device is shared or partitioned): the rows concerned took no "
-                                "step (the parameters are valid numbers, the epoch is not the reference's) -- reload the parameters; the handle takes "
-                                "two launches per run from now on");
-    }
-  }
-  if (h->handoff_err_host & 3u) {
-    // a hand-off wait ran into its bound (the probe said the streams run side by side, and then they did not: the device is shared with
-    // work that starved one of them).  Nothing was computed from a bias that was not there: the examples concerned took no step, a
-    // recurrence that never saw its batch handed the bias on unchanged (fmx_kernels.h) -- every parameter is a valid number, but the
-    // epoch is not the rule's.  The handle orders its streams with events from now on.
-    const uint32_t e = h->handoff_err_host;
-    h->handoff_err_host = 0;
-    uint32_t dev = 0;
-    if (hipMemcpy(&dev, h->handoff_err, sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess) {
-      dev &= ~3u;                                               // (only the hand-off's own bits: bit 4 belongs to scan_error_check)
-      (void)hipMemcpy(h->handoff_err, &dev, sizeof(uint32_t), hipMemcpyHostToDevice);
-    }
-    h->handoff = false;
-    h->run_status |= FMX_STAT_HANDOFF_TIMEOUT;
-    if (stats) stats->status = bi.status | h->run_status;
-    return fail(h, FMX_E_HIP, "the bias hand-off between the launch stream and the recurrence timed out (flags %u): the examples concerned took no "
-                              "step (the parameters are valid numbers, the epoch is not the batch rule's); the handle orders its streams with "
-                              "events from now on", e);
-  }
-  if (kept_wside) s.wside_version = h->w_version;            // the epoch is complete: the stream holds this w
-  if (stats) {
-    float ms = 0;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    stats->rows = s.n_rows;
-    stats->batches = batches;
-    stats->device_seconds = ms * 1e-3;
-    if (opts->mode == FMX_SGD_MINIBATCH && s.seg_B) stats->max_feature_count = s.max_seg_count;
-    stats->deferred_features = deferred;
-    if (opts->mode == FMX_SGD_MINIBATCH || opts->mode == FMX_SGD_HOGWILD) {     // (HOGWILD: batch_used = the rows in flight)
-      stats->batch_used = bi.batch; stats->collision_mass = bi.collision_mass; stats->batch_gain = bi.batch_gain; stats->status = bi.status;
-    }
-    stats->status |= h->run_status;
-    stats->setup_seconds = h->setup_acc;
-    if (opts->mode != FMX_SGD_SEQUENTIAL) stats->w0_chunk_used = opts->w0_chunk ? opts->w0_chunk : default_w0_chunk(h->cfg);
-    if (opts->mode == FMX_SGD_MINIBATCH && timed && opts->apply != FMX_APPLY_FUSED) {
-      double tot = 0;
-      for (size_t i = 0; i + 1 < ev_used; i += 2) {
-        float m2 = 0;
-        HIPCHK(h, hipEventElapsedTime(&m2, h->ev_pool[i], h->ev_pool[i + 1]));
-        tot += m2 * 1e-3;
-      }
-      stats->main_kernel_seconds = tot;
-      stats->main_kernel_launches = main_launches;
-    } else {
-      stats->main_kernel_seconds = stats->device_seconds;
-      stats->main_kernel_launches = main_launches;
-    }
-  }
-  return FMX_OK;
+  return epoch_close(h, s, opts, bi, n, stats);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1464,12 +1458,9 @@ int fmx_sgda_epoch_minibatch(fmx_handle h, int train_slot, int validation_slot, 
     KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, st, s.ent, s.row_ptr, row0, nb, h->tb, h->cfg.k1, S, rest, (const float*)nullptr));
     rc = launch_scan(h, rest, s.target + row0, nb, chunk, hy, h->mult, st);
     if (rc) return rc;
-    const size_t bi = (size_t)(row0 / B);
-    const uint32_t s0 = s.batch_seg[bi], s1 = s.batch_seg[bi + 1];
-    const uint64_t base = s.batch_base[bi];
-    if (s1 > s0) {
-      SegWork sw{s.t_ent + base, s.seg_feat + s0, s.seg_rel + s0, nullptr, s1 - s0, s1 - s0, (uint32_t)(s.batch_base[bi + 1] - base), S, h->mult};
-      KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_sgda_apply_seg<KP, 8>), ((uint64_t)(s1 - s0) + 63) / 64, st, sw, h->tb, hy,
+    const SegWork sw = seg_work_dense(h, s, (size_t)(row0 / B), S, h->mult);
+    if (sw.nseg) {
+      KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_sgda_apply_seg<KP, 8>), ((uint64_t)sw.nseg + 63) / 64, st, sw, h->tb, hy,
                                          (const double*)h->sgda.reg, (const uint32_t*)h->grp, h->sgda.gw, h->sgda.gv));
     }
     if (do_lambda_steps && v.n_rows) {
