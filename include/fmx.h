@@ -480,6 +480,68 @@ typedef struct fmx_eval_ex {
 /* opts may be NULL (= logistic) */
 int fmx_evaluate_ex(fmx_handle h, int slot, const fmx_eval_opts *opts, fmx_eval_ex *out);
 
+/* ---- exact per-query AUC (GAUC) of a slot, reduced on the device -------------------------------
+ * The pooled AUC of fmx_evaluate_ex mixes "which query scores higher" with "which row this query prefers".  Click models are
+ * judged by the AUC INSIDE each user or session, averaged with the impressions as weights (GAUC); the BPR paper's metric is the
+ * per-user AUC.  A QUERY here is that user / session: one id per row ("group" already names `-meta` attribute groups and feature
+ * shards).  fmx_set_row_queries attaches the ids to a slot, fmx_evaluate_by_query scores the slot once like fmx_evaluate_ex and
+ * reduces per query.  With p_i, s_i and the float comparison (+0 == -0) of fmx_evaluate_ex:
+ *   auc_num2_q  = sum_{i, j in q, s_i = +1, s_j = -1} ( 2 [p_i > p_j] + [p_i == p_j] )          that INTEGER exactly
+ *   pos_q, neg_q  rows of q with target >= 0 / target < 0
+ *   auc_q       = (double)auc_num2_q / (2.0 * (double)pos_q * (double)neg_q)      both operands exact below 2^53
+ *   a query is VALID when pos_q > 0 and neg_q > 0; one-class and empty queries take no part in the three means:
+ *   auc_within  = num2_within / den2_within = sum_valid auc_num2_q / sum_valid 2 pos_q neg_q
+ *   gauc        = sum_valid (pos_q + neg_q) auc_q / valid_rows                    (impression-weighted)
+ *   auc_macro   = sum_valid auc_q / valid_queries
+ *   NaN scores: with pooled.nan_rows > 0 nothing is sorted: auc_within, gauc and auc_macro are NaN, num2_within, den2_within,
+ *               the three query counts and valid_rows 0, the per-query arrays zero-filled; pooled is exactly fmx_evaluate_ex's
+ *               NaN result.
+ *   valid_queries == 0: the three means are NaN, num2_within, den2_within and valid_rows 0; the counts and the per-query
+ *               pos_q / neg_q are still right -- also when the whole slot holds one class (pooled skips its own sort, the
+ *               by-query pipeline still runs).
+ *   regression handles: pooled as fmx_evaluate_ex fills it; the counts 0, the means NaN, the arrays zero-filled, nothing sorted.
+ *   an empty slot: FMX_OK, pooled = the empty result, queries = empty_queries = n_queries, means NaN, arrays zero-filled.
+ * Pipeline: the score pass of fmx_evaluate_ex fills `pooled`; the same scores then give one 64-bit key per row (query id <<
+ * 33 | fmx_evaluate_ex's 33-bit key), ONE radix sort over 33 + ceil(log2(n_queries)) bits, three library scans and a rank-sum kernel
+ * that reduces the query segments inside each wavefront and issues one 64-bit integer atomic per (wavefront, segment).  Only
+ * integers meet in atomics; the fp64 sums over the queries run in a fixed order (block partials on a grid that is a fixed function
+ * of n_queries): two calls with unchanged parameters are bit-identical in every field except the two times.
+ * Device memory: resident, 4 bytes per row (the ids).  Inside the call, allocated and freed: fmx_evaluate_ex's scratch first, then
+ * 28 bytes per row (8 + 8 the key double buffer, 4 + 4 + 4 the three scans) + the sort's temporary + 16 bytes per QUERY.
+ * fmx_group_set_row_queries puts the ids on the first shard's slot, where the targets live; fmx_group_evaluate_by_query reduces
+ * the finished y-hat chunks there like fmx_group_evaluate_ex; a one-handle group forwards.
+ * Refusals: as fmx_evaluate_ex (FMX_E_ARG: NULL out, unknown link, flags != 0; FMX_E_STATE: a slot never uploaded or without
+ * targets; FMX_E_UNSUPPORTED: a feature shard passed to the per-handle call, more than 2^31 - 1 rows), and FMX_E_STATE when the slot
+ * has no query ids.  fmx_set_row_queries: FMX_E_ARG for n_queries == 0 or > 2^31 - 1 and for any qid >= n_queries (the message
+ * names the first offending row; nothing changes on failure), FMX_E_STATE for a slot never uploaded; an empty slot with a
+ * non-NULL qid is accepted.  Rows are not weighted.
+ * Added without an ABI version change: a caller detects the feature by the symbol fmx_evaluate_by_query. */
+
+/* per-row query ids of a slot: qid[n_rows] (host), every qid < n_queries, 1 <= n_queries <= 2^31 - 1.  Kept on the device
+ * (4 bytes per row).  A new call replaces them; NULL drops them; fmx_upload_rows and its siblings, fmx_synth_rows* and
+ * fmx_free_rows drop them (free_slot), fmx_destroy frees them. */
+int fmx_set_row_queries(fmx_handle h, int slot, const uint32_t *qid, uint32_t n_queries);
+
+typedef struct fmx_eval_query {
+  fmx_eval_ex pooled;        /* field for field what fmx_evaluate_ex returns for this slot and link (times aside) */
+  uint64_t queries;          /* n_queries */
+  uint64_t valid_queries;    /* queries holding at least one positive AND one negative row */
+  uint64_t one_class_queries;/* non-empty, one class only: they take no part in the three means below */
+  uint64_t empty_queries;
+  uint64_t valid_rows;       /* rows of the valid queries */
+  uint64_t num2_within;      /* sum over valid q of auc_num2_q          (exact) */
+  uint64_t den2_within;      /* sum over valid q of 2 pos_q neg_q       (exact) */
+  double   auc_within;       /* num2_within / den2_within: the share of correctly ordered within-query (pos, neg) pairs */
+  double   gauc;             /* sum_valid rows_q auc_q / valid_rows,  auc_q = auc_num2_q / (2 pos_q neg_q)   (impression-weighted) */
+  double   auc_macro;        /* sum_valid auc_q / valid_queries */
+  double   device_seconds;   /* whole call */
+  double   rank_seconds;     /* the by-query sort, scans, rank-sum and final kernels only */
+} fmx_eval_query;
+
+/* opts as fmx_evaluate_ex (NULL = logistic).  num2_q (uint64), pos_q, neg_q (uint32): NULL or host [n_queries], per query. */
+int fmx_evaluate_by_query(fmx_handle h, int slot, const fmx_eval_opts *opts, fmx_eval_query *out,
+                          uint64_t *num2_q, uint32_t *pos_q, uint32_t *neg_q);
+
 /* ---- the averaged predictions of `-method mcmc`, kept on the device ----------------------------
  * The prediction of fm_learn_mcmc_simultaneous is not that of one model but the running mean over the draws (pred_sum_all / (i + 1),
  * fm_learn_mcmc_simultaneous.h:129-161, 213-264).  A posterior accumulator keeps the three vectors of that file for one slot on the
@@ -790,6 +852,10 @@ int fmx_group_predict(fmx_group g, int slot, double *out);
 int fmx_group_evaluate(fmx_group g, int slot, fmx_eval *out);
 /* fmx_evaluate_ex over the shards of a group (see there) */
 int fmx_group_evaluate_ex(fmx_group g, int slot, const fmx_eval_opts *opts, fmx_eval_ex *out);
+/* fmx_set_row_queries / fmx_evaluate_by_query over the shards of a group (see there): the ids live on the first shard's slot */
+int fmx_group_set_row_queries(fmx_group g, int slot, const uint32_t *qid, uint32_t n_queries);
+int fmx_group_evaluate_by_query(fmx_group g, int slot, const fmx_eval_opts *opts, fmx_eval_query *out,
+                                uint64_t *num2_q, uint32_t *pos_q, uint32_t *neg_q);
 /* fmx_post_* over the shards of a group (see there) */
 int fmx_group_post_begin(fmx_group g, int slot, const fmx_post_opts *opts);
 int fmx_group_post_accumulate(fmx_group g, int slot, fmx_post_stats *out);

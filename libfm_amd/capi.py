@@ -92,6 +92,13 @@ class EvalEx(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class EvalQuery(C.Structure):
+    _fields_ = [("pooled", EvalEx), ("queries", C.c_uint64), ("valid_queries", C.c_uint64), ("one_class_queries", C.c_uint64),
+                ("empty_queries", C.c_uint64), ("valid_rows", C.c_uint64), ("num2_within", C.c_uint64), ("den2_within", C.c_uint64),
+                ("auc_within", C.c_double), ("gauc", C.c_double), ("auc_macro", C.c_double),
+                ("device_seconds", C.c_double), ("rank_seconds", C.c_double)]
+
+
 POST_THIS, POST_ALL, POST_LATE = 0, 1, 2   # FMX_POST_*: the last draw, the mean over all draws, the mean over the draws from burn_in on
 
 
@@ -211,6 +218,8 @@ SYMBOLS = [
     ("fmx_predict", C.c_int, [H, C.c_int, C.c_void_p]),
     ("fmx_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
     ("fmx_evaluate_ex", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalEx)]),
+    ("fmx_set_row_queries", C.c_int, [H, C.c_int, C.c_void_p, C.c_uint32]),
+    ("fmx_evaluate_by_query", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalQuery), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("fmx_post_begin", C.c_int, [H, C.c_int, C.POINTER(PostOpts)]),
     ("fmx_post_accumulate", C.c_int, [H, C.c_int, C.POINTER(PostStats)]),
     ("fmx_post_evaluate_ex", C.c_int, [H, C.c_int, C.c_uint32, C.POINTER(EvalEx)]),
@@ -241,6 +250,8 @@ SYMBOLS = [
     ("fmx_group_predict", C.c_int, [H, C.c_int, C.c_void_p]),
     ("fmx_group_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
     ("fmx_group_evaluate_ex", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalEx)]),
+    ("fmx_group_set_row_queries", C.c_int, [H, C.c_int, C.c_void_p, C.c_uint32]),
+    ("fmx_group_evaluate_by_query", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalQuery), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("fmx_group_post_begin", C.c_int, [H, C.c_int, C.POINTER(PostOpts)]),
     ("fmx_group_post_accumulate", C.c_int, [H, C.c_int, C.POINTER(PostStats)]),
     ("fmx_group_post_evaluate_ex", C.c_int, [H, C.c_int, C.c_uint32, C.POINTER(EvalEx)]),
@@ -324,6 +335,38 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
+def _set_row_queries(obj, fn, handle, slot, qid, n_queries):
+    """the body of Handle / Group.set_row_queries; returns n_queries (None after qid=None)"""
+    if qid is None:
+        obj._chk(fn(handle, slot, None, 0))
+        return None
+    q = np.asarray(qid)
+    if q.size and (q.dtype.kind not in "iu" or int(q.min()) < 0 or int(q.max()) > 0xFFFFFFFF):
+        raise ValueError("set_row_queries: query ids are non-negative integers below 2^32")
+    q = np.ascontiguousarray(q, dtype=np.uint32).reshape(-1)
+    if n_queries is None:
+        n_queries = int(q.max()) + 1 if q.size else 1
+    if not 0 <= int(n_queries) <= 0xFFFFFFFF:
+        raise ValueError("set_row_queries: n_queries out of range")
+    obj._chk(fn(handle, slot, _ptr(q) if q.size else _ptr(np.zeros(1, dtype=np.uint32)), int(n_queries)))
+    return int(n_queries)
+
+
+def _evaluate_by_query(obj, fn, handle, slot, link, per_query, n_queries):
+    """the body of Handle / Group.evaluate_by_query"""
+    opts, ev = EvalOpts(link, 0), EvalQuery()
+    if not per_query:
+        obj._chk(fn(handle, slot, C.byref(opts), C.byref(ev), None, None, None))
+        return ev
+    if n_queries is None:                            # no ids were set through this object: the library says so
+        obj._chk(fn(handle, slot, C.byref(opts), C.byref(ev), None, None, None))
+        raise RuntimeError("evaluate_by_query(per_query=True): the query ids of slot %d were not set through this object" % slot)
+    num2 = np.zeros(n_queries, dtype=np.uint64)
+    pos, neg = np.zeros(n_queries, dtype=np.uint32), np.zeros(n_queries, dtype=np.uint32)
+    obj._chk(fn(handle, slot, C.byref(opts), C.byref(ev), _ptr(num2), _ptr(pos), _ptr(neg)))
+    return ev, num2, pos, neg
+
+
 class Handle:
     """Thin OO wrapper over an fmx_handle; every method is one C-ABI call."""
 
@@ -340,6 +383,7 @@ class Handle:
         if rc != FMX_OK:
             raise FmxError(rc, self.lib.fmx_last_error(None).decode())
         self.n, self.k = int(num_attribute), int(num_factor)
+        self._nq = {}                                # slot -> n_queries of the last set_row_queries (sizes the per-query arrays)
         self.G = 1                                   # attribute groups (set_groups)
         self.n_local = int(self.info().n_local)
 
@@ -463,6 +507,15 @@ class Handle:
         opts, ev = EvalOpts(link, 0), EvalEx()
         self._chk(self.lib.fmx_evaluate_ex(self.h, slot, C.byref(opts), C.byref(ev)))
         return ev
+
+    def set_row_queries(self, slot, qid, n_queries=None):
+        """per-row query ids of a slot (fmx_set_row_queries); n_queries None = max + 1, qid None drops them"""
+        self._nq[slot] = _set_row_queries(self, self.lib.fmx_set_row_queries, self.h, slot, qid, n_queries)
+
+    def evaluate_by_query(self, slot, link=LINK_LOGISTIC, per_query=False):
+        """exact AUC inside every query (GAUC), reduced on the device (fmx_evaluate_by_query): the EvalQuery struct, or with
+        per_query (struct, num2_q uint64, pos_q uint32, neg_q uint32), each [n_queries]"""
+        return _evaluate_by_query(self, self.lib.fmx_evaluate_by_query, self.h, slot, link, per_query, self._nq.get(slot))
 
     # the posterior accumulator of a slot (fmx_post_*): MCMC's averaged predictions on the device
     def post_begin(self, slot, burn_in=5, eval_rows=0):
@@ -778,6 +831,7 @@ class Group:
     def __init__(self, handles):
         self.lib = load()
         self.handles = list(handles)
+        self._nq = {}                                # slot -> n_queries of the last set_row_queries
         arr = (H * len(self.handles))(*[h.h for h in self.handles])
         self.g = H()
         rc = self.lib.fmx_group_create(arr, len(self.handles), C.byref(self.g))
@@ -836,6 +890,14 @@ class Group:
         opts, ev = EvalOpts(link, 0), EvalEx()
         self._chk(self.lib.fmx_group_evaluate_ex(self.g, slot, C.byref(opts), C.byref(ev)))
         return ev
+
+    def set_row_queries(self, slot, qid, n_queries=None):
+        """Handle.set_row_queries; the ids go to the first shard's slot, where the targets live (fmx_group_set_row_queries)"""
+        self._nq[slot] = _set_row_queries(self, self.lib.fmx_group_set_row_queries, self.g, slot, qid, n_queries)
+
+    def evaluate_by_query(self, slot, link=LINK_LOGISTIC, per_query=False):
+        """Handle.evaluate_by_query over the shards (fmx_group_evaluate_by_query)"""
+        return _evaluate_by_query(self, self.lib.fmx_group_evaluate_by_query, self.g, slot, link, per_query, self._nq.get(slot))
 
     # the posterior accumulator of a slot (fmx_post_*): MCMC's averaged predictions on the device
     def post_begin(self, slot, burn_in=5, eval_rows=0):

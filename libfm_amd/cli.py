@@ -24,6 +24,10 @@ the epoch; the #Iter= lines stay on uniform negatives.
 -metrics auc,logloss (-task c with sgd, sgda, als): after every iteration the exact AUC and / or the log loss of the train and
 test rows, reduced on the device (fmx_evaluate_ex), as "#Iter=  i\tauc: Train=..\tTest=.." lines on stderr and auc_train /
 auc_test / logloss_train / logloss_test columns of -rlog; stdout stays byte for byte what it is without the flag.
+-test_queries F [-train_queries F] (-task c with sgd, sgda, als): one non-negative integer per row of -test / -train, the row's
+query (user, session).  After every iteration the impression-weighted exact AUC inside the queries (GAUC), reduced on the device
+(fmx_evaluate_by_query), as one "#Iter=  i\tgauc: Train=..\tTest=.." line on stderr (nan for a set without ids) and gauc_* /
+auc_within_* columns of -rlog; stdout stays byte for byte what it is without the flags.
 -device_average 1 (als, mcmc): the test predictions and their running sums stay on the device (fmx_post_accumulate); the #Iter=
 lines gain the reference's Test(ll) column on -task c, -rlog its rmse_mcmc_* / acc_mcmc_* / ll_mcmc_* columns, and -metrics then
 scores the averaged test prediction ("#Iter=  i\tauc: Test=.." on stderr, auc_test / logloss_test) -- with -method mcmc too.
@@ -61,6 +65,9 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "exclude": "filename of excluded pairs, one per line 'query_row cand_row'",
          "metrics": "'auc,logloss': exact AUC / log loss of train and test per iteration on stderr; -task c with sgd, sgda, als"
                     " (mcmc: of the averaged test prediction, with -device_average 1)",
+         "test_queries": "filename with one query id (non-negative integer) per test row: per-query AUC (GAUC) per iteration on"
+                         " stderr; -task c with sgd, sgda, als",
+         "train_queries": "the same for the train rows; needs -test_queries",
          "device_average": "als, mcmc: 1 = keep the test predictions and their running mean on the device; default=0"}
 
 
@@ -81,6 +88,24 @@ def read_pairs(path, n_rows):
             a.append(ra)
             b.append(rb)
     return np.array(a, dtype=np.uint32), np.array(b, dtype=np.uint32)
+
+
+def read_queries(path, n_rows):
+    """a -test_queries / -train_queries file: one non-negative integer per line, the query id of the row with that line number;
+    the line count must equal the rows of the data file"""
+    ids = []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            t = line.split()
+            if len(t) != 1:
+                raise ValueError("cannot parse line %d of %s: want one query id" % (no, path))
+            q = int(t[0])
+            if not 0 <= q < 2 ** 31 - 1:
+                raise ValueError("line %d of %s: a query id is an integer in 0 .. 2^31 - 2 (got %d)" % (no, path, q))
+            ids.append(q)
+    if len(ids) != n_rows:
+        raise ValueError("%s has %d lines, the data set has %d rows" % (path, len(ids), n_rows))
+    return np.array(ids, dtype=np.uint32)
 
 
 def read_exclude(path, n_query, n_cand):
@@ -221,6 +246,19 @@ def _main(argv):
                               ": the pairwise learner reports its own accuracy and loss"))
         if a["task"] != "c":
             raise ValueError("-metrics needs -task c: AUC and log loss are classification metrics")
+    if "test_queries" in a or "train_queries" in a:
+        if method in ("mcmc", "bpr"):
+            raise ValueError("-test_queries / -train_queries are not supported with -method %s" % method +
+                             (": its prediction averages the draws, no single model scores it" if method == "mcmc" else
+                              ": the pairwise learner reports its own accuracy and loss"))
+        if a["task"] != "c":
+            raise ValueError("-test_queries / -train_queries need -task c: the per-query AUC is a classification metric")
+        if dev_avg:
+            raise ValueError("-test_queries / -train_queries are not supported with -device_average 1")
+        if not a.get("test_queries"):
+            raise ValueError("-train_queries needs -test_queries" if "test_queries" not in a else "-test_queries needs a filename")
+        if "train_queries" in a and not a["train_queries"]:
+            raise ValueError("-train_queries needs a filename")
 
     print("Loading train...\t")
     train = L.Data(*D.load(a["train"]))
@@ -230,6 +268,9 @@ def _main(argv):
     test = L.Data(*D.load(a["test"]))
     print("num_rows=%d\tnum_values=%d\tnum_features=%d\tmin_target=%g\tmax_target=%g" %
           (test.num_cases, len(test.entries), test.num_feature, test.min_target, test.max_target))
+
+    test_queries = read_queries(a["test_queries"], test.num_cases) if a.get("test_queries") else None
+    train_queries = read_queries(a["train_queries"], train.num_cases) if a.get("train_queries") else None
 
     validation = None
     if method == "sgda":                                                             # libfm.cpp:173-194
@@ -359,6 +400,10 @@ def _main(argv):
     if dev_avg:
         l.device_average = True
     l.init()
+    if test_queries is not None:
+        l.set_queries(test, test_queries)
+    if train_queries is not None:
+        l.set_queries(train, train_queries)
     if implicit:
         print("Loading interactions...\t")
         inter = read_interactions(a["interactions"], train.num_cases, cand.num_cases)

@@ -963,6 +963,44 @@ int fmx_group_evaluate_ex(fmx_group g, int slot, const fmx_eval_opts* opts, fmx_
   return rc;
 }
 
+// fmx_set_row_queries / fmx_evaluate_by_query over the shards (fmx_evalq.hip): the ids live on the first shard's slot, where the
+// targets are; the finished y-hat chunks stay on the first shard's device like fmx_group_evaluate_ex's and are reduced there
+int fmx_group_set_row_queries(fmx_group g, int slot, const uint32_t* qid, uint32_t n_queries) {
+  static const char who[] = "fmx_group_set_row_queries";
+  if (!g) return FMX_E_ARG;
+  for (auto m : g->hs) if (!m) return gfail(g, FMX_E_STATE, "a member of the group was destroyed");
+  fmx_handle cur = g->hs[0];
+  if (g->kind == GROUP_SINGLE) { GCHK(g, fmx_set_row_queries(cur, slot, qid, n_queries)); return FMX_OK; }
+  GCHK(g, set_row_queries_impl(cur, who, slot, qid, n_queries));
+  return FMX_OK;
+}
+
+int fmx_group_evaluate_by_query(fmx_group g, int slot, const fmx_eval_opts* opts, fmx_eval_query* out,
+                                uint64_t* num2_q, uint32_t* pos_q, uint32_t* neg_q) {
+  static const char who[] = "fmx_group_evaluate_by_query";
+  if (!g) return FMX_E_ARG;
+  for (auto m : g->hs) if (!m) return gfail(g, FMX_E_STATE, "a member of the group was destroyed");
+  fmx_handle h0 = g->hs[0];
+  fmx_handle cur = h0;
+  if (g->kind == GROUP_SINGLE) { GCHK(g, fmx_evaluate_by_query(cur, slot, opts, out, num2_q, pos_q, neg_q)); return FMX_OK; }
+  if (!out) return gfail(g, FMX_E_ARG, "%s: out is NULL", who);
+  uint32_t link;
+  GCHK(g, eval_ex_check_opts(cur, who, opts, &link));
+  GCHK(g, evalq_check_slot(cur, who, slot));
+  const Slot& s = h0->slots[slot];
+  evalq_empty(out, s.n_queries);
+  if (s.n_rows == 0) { out->empty_queries = s.n_queries; evalq_zero_per_query(s.n_queries, num2_q, pos_q, neg_q); return FMX_OK; }
+  float* d_all = nullptr;
+  HIPCHK(h0, hipSetDevice(h0->device));
+  HIPCHK(h0, fmx_dev_alloc(&d_all, (size_t)s.n_rows * sizeof(float)));
+  int rc = (hipEventRecord(h0->ev0, h0->stream) == hipSuccess) ? FMX_OK : fail(h0, FMX_E_HIP, "%s: hipEventRecord failed", who);
+  if (rc == FMX_OK) rc = group_predict_chunks(g, slot, nullptr, d_all);
+  if (rc == FMX_OK) { hipSetDevice(h0->device); rc = evalq_scores(h0, s, d_all, 0, link, out, num2_q, pos_q, neg_q); if (rc) g->err = fmx_last_error(h0); }
+  hipSetDevice(h0->device);
+  fmx_dev_free(d_all);
+  return rc;
+}
+
 // fmx_post_* over the shards (fmx_post.hip): the accumulator lives on the first shard's slot; only _accumulate needs the other
 // shards, for the finished y-hat chunks, which stay on the first shard's device like fmx_group_evaluate_ex's
 #define GROUP_POST_HEAD(who_)                                                                        \

@@ -137,6 +137,7 @@ void free_slot(Slot& s) {
   if (s.target) fmx_dev_free(s.target);
   if (s.wside) fmx_dev_free(s.wside);
   if (s.lmask) fmx_dev_free(s.lmask);
+  if (s.qid) fmx_dev_free(s.qid);
   s = Slot();
 }
 

@@ -84,6 +84,9 @@ struct Slot {
   struct PairNeg* pneg = nullptr;
   // posterior accumulator (fmx_post_begin, fmx_post.hip); on a group it lives on the first shard's slot
   struct PostAcc* post = nullptr;
+  // per-row query ids (fmx_set_row_queries, fmx_evalq.hip); on a group they live on the first shard's slot, next to the targets
+  uint32_t* qid = nullptr;           // [n_rows]
+  uint32_t  n_queries = 0;           // 0: the slot has no query ids
 };
 void free_pairs(Slot& s);                                                // fmx_pair.hip
 void free_interactions(Slot& s);                                         // fmx_pairneg.hip
@@ -280,6 +283,14 @@ int eval_ex_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, 
 // ... and its rank pipeline (sort, two scans, rank sum) over keys of any width, shared with fmx_post_evaluate_ex (fmx_post.hip)
 int eval_ex_rank(fmx_handle h, unsigned long long* keys, uint32_t n, int key_bits, unsigned long long* d_num2, uint64_t* num2,
                  double* rank_seconds);
+// fmx_evalq.hip: the checks, the empty result and the whole reduction of fmx_evaluate_by_query (pooled metrics through eval_ex_scores,
+// then the by-query pipeline over the same scores), shared with fmx_group_evaluate_by_query (fmx_comm.hip)
+int set_row_queries_impl(fmx_handle h, const char* who, int slot, const uint32_t* qid, uint32_t n_queries);
+int evalq_check_slot(fmx_handle h, const char* who, int slot);
+void evalq_empty(fmx_eval_query* out, uint32_t n_queries);
+void evalq_zero_per_query(uint32_t n_queries, uint64_t* num2_q, uint32_t* pos_q, uint32_t* neg_q);
+int evalq_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, uint32_t link, fmx_eval_query* out,
+                 uint64_t* num2_q, uint32_t* pos_q, uint32_t* neg_q);
 // fmx_post.hip: the posterior accumulator of a slot (include/fmx.h "fmx_post_*").  The *_impl functions are the entry points after
 // the handle-kind check, for the first shard of a group too (fmx_comm.hip); post_accum_scores takes scores that are on h's device.
 struct PostAcc {

@@ -2,6 +2,7 @@
 device to.  Pure Python on purpose -- the AUC numerator is counted with Python integers, the log loss summed with `math` in fp64.
 
     classification_metrics(scores, target, link="logistic") -> dict with the fields of fmx_eval_ex
+    query_metrics(scores, target, qid, n_queries, link="logistic") -> dict with the fields of fmx_eval_query
 
 ... and of the posterior accumulator (fmx_post_*): PosteriorAverage keeps the three prediction vectors of
 fm_learn_mcmc_simultaneous in numpy fp64; posterior_metric / posterior_evaluate_ex score a vector of means.
@@ -68,6 +69,64 @@ def classification_metrics(scores, target, link="logistic"):
     if pos and neg:
         out["auc"] = out["auc_num2"] / (2 * pos * neg)
     out["logloss"] = math.fsum(loss_term(x if s else -x, link) for x, s in zip(p, positive)) / rows
+    return out
+
+
+def query_metrics(scores, target, qid, n_queries, link="logistic", per_query=True):
+    """CPU restatement of fmx_evaluate_by_query (include/fmx.h): a dict with the fields of fmx_eval_query
+    (`pooled` is classification_metrics' dict) plus the per-query lists num2_q, pos_q, neg_q [n_queries].  The numerators are
+    auc_numerator2 per query in Python integers, the two fp64 sums math.fsum; only the queries that are present are visited, so a
+    large n_queries with few rows stays cheap (per_query=False leaves the three lists out: None)."""
+    n_queries = int(n_queries)
+    q = [int(x) for x in np.asarray(qid).reshape(-1)]
+    pooled = classification_metrics(scores, target, link)
+    if len(q) != pooled["rows"]:
+        raise ValueError("%d query ids for %d rows" % (len(q), pooled["rows"]))
+    if not 1 <= n_queries <= 2 ** 31 - 1:
+        raise ValueError("n_queries must be in 1 .. 2^31 - 1")
+    if q and not 0 <= min(q) <= max(q) < n_queries:
+        raise ValueError("a query id outside 0 .. n_queries - 1")
+    out = {"pooled": pooled, "queries": n_queries, "valid_queries": 0, "one_class_queries": 0, "empty_queries": 0, "valid_rows": 0,
+           "num2_within": 0, "den2_within": 0, "auc_within": math.nan, "gauc": math.nan, "auc_macro": math.nan,
+           "device_seconds": 0.0, "rank_seconds": 0.0,
+           "num2_q": None, "pos_q": None, "neg_q": None}
+    if per_query:
+        out["num2_q"], out["pos_q"], out["neg_q"] = [0] * n_queries, [0] * n_queries, [0] * n_queries
+    if pooled["rows"] == 0:
+        out["empty_queries"] = n_queries
+        return out
+    if pooled["nan_rows"]:                                            # nothing is sorted: counts 0, arrays zero
+        return out
+    p = [float(x) for x in np.asarray(scores, dtype=np.float32).reshape(-1)]
+    positive = [float(t) >= 0 for t in np.asarray(target, dtype=np.float32).reshape(-1)]
+    members = {}
+    for i, g in enumerate(q):
+        members.setdefault(g, []).append(i)
+    weighted, plain = [], []
+    for g in sorted(members):
+        rows = members[g]
+        pos = sum(1 for i in rows if positive[i])
+        neg = len(rows) - pos
+        if per_query:
+            out["pos_q"][g], out["neg_q"][g] = pos, neg
+        if not (pos and neg):
+            out["one_class_queries"] += 1
+            continue
+        num2 = auc_numerator2([p[i] for i in rows], [positive[i] for i in rows])
+        if per_query:
+            out["num2_q"][g] = num2
+        auc_q = num2 / (2.0 * float(pos) * float(neg))
+        weighted.append(float(len(rows)) * auc_q)
+        plain.append(auc_q)
+        out["valid_queries"] += 1
+        out["valid_rows"] += len(rows)
+        out["num2_within"] += num2
+        out["den2_within"] += 2 * pos * neg
+    out["empty_queries"] = n_queries - len(members)
+    if out["valid_queries"]:
+        out["auc_within"] = out["num2_within"] / out["den2_within"]
+        out["gauc"] = math.fsum(weighted) / out["valid_rows"]
+        out["auc_macro"] = math.fsum(plain) / out["valid_queries"]
     return out
 
 

@@ -132,6 +132,28 @@ def _log_extra_metrics(learner, i, train, test):
         learner.log[-1][m + "_train"], learner.log[-1][m + "_test"] = a, b
 
 
+def _log_query_metrics(learner, i, train, test):
+    """when a data set of learn() has query ids (set_queries) on a classification task: one more stderr line with the
+    impression-weighted per-query AUC (fmx_evaluate_by_query) and gauc_* / auc_within_* in the iteration's log row; a set without
+    ids gives nan.  stdout is not touched."""
+    if learner.task != TASK_CLASSIFICATION or not any(id(d) in learner._queries for d in (train, test)):
+        return
+    vals = []
+    for name, d in (("train", train), ("test", test)):
+        ev = learner.evaluate_by_query(d) if id(d) in learner._queries else None
+        gauc, within = (ev.gauc, ev.auc_within) if ev is not None else (float("nan"), float("nan"))
+        learner.log[-1]["gauc_" + name], learner.log[-1]["auc_within_" + name] = gauc, within
+        vals.append(gauc)
+    print("#Iter=%3d\tgauc: Train=%g\tTest=%g" % (i, vals[0], vals[1]), file=sys.stderr)
+
+
+def _check_queries(data, qid):
+    q = np.asarray(qid).reshape(-1)
+    if len(q) != data.num_cases:
+        raise ValueError("set_queries: %d query ids for %d rows" % (len(q), data.num_cases))
+    return q
+
+
 class FMLearnSGD:
     """fm_learn_sgd_element on the GPU.
 
@@ -162,6 +184,7 @@ class FMLearnSGD:
         self.out = sys.stdout
         self._h = None
         self._slots = {}
+        self._queries = {}                                      # id(data) -> (qid, n_queries) of set_queries
 
     # fm_learn::init (fm_learn.h:73-91): here it creates the device context and uploads the parameters
     def init(self):
@@ -182,7 +205,23 @@ class FMLearnSGD:
                 raise RuntimeError("too many data sets")
             data.upload(self._h, slot)
             self._slots[key] = slot
+            if key in self._queries:
+                self._h.set_row_queries(slot, *self._queries[key])
         return self._slots[key]
+
+    def set_queries(self, data, qid, n_queries=None):
+        """one query id (user, session) per row of `data`: learn() then reports the per-query AUC of the set, and
+        evaluate_by_query(data) works (fmx_set_row_queries).  n_queries None = max id + 1."""
+        self._queries[id(data)] = (_check_queries(data, qid), n_queries)
+        if id(data) in self._slots:
+            self._h.set_row_queries(self._slots[id(data)], *self._queries[id(data)])
+
+    def evaluate_by_query(self, data):
+        """exact AUC inside every query of `data` under the current parameters: gauc, auc_macro, auc_within, the counts and the
+        pooled metrics (capi.EvalQuery), reduced on the device (fmx_evaluate_by_query)"""
+        if id(data) not in self._queries:
+            raise ValueError("evaluate_by_query: the data set has no query ids (set_queries)")
+        return self._h.evaluate_by_query(self._slot(data), self.EVAL_LINK)
 
     # fm_learn_sgd_element::learn (fm_learn_sgd_element.h:48-78)
     def learn(self, train, test):
@@ -206,6 +245,7 @@ class FMLearnSGD:
             print("#Iter=%3d\tTrain=%g\tTest=%g" % (i, rmse_train, rmse_test), file=self.out)   # :71
             self.log.append({"rmse_train": rmse_train, "time_learn": stats.device_seconds})
             _log_extra_metrics(self, i, train, test)
+            _log_query_metrics(self, i, train, test)
         self.sync_model()
 
     def sync_model(self):
@@ -289,6 +329,7 @@ class FMLearnALS:
         self._h = None                 # a capi.Handle, or the capi.Group of the shards
         self._shards = []
         self._train = self._test = None   # the data sets of learn(): slots 0 and 1
+        self._queries = {}             # id(data) -> (qid, n_queries) of set_queries
 
     def init(self):
         fm = self.fm
@@ -321,9 +362,14 @@ class FMLearnALS:
     # fm_learn_mcmc::learn + _learn (fm_learn_mcmc.h:1160-1201, fm_learn_mcmc_simultaneous.h:56-270)
     def learn(self, train, test):
         h = self._h
+        if self._queries and self.device_average:
+            raise NotImplementedError("set_queries: the per-query AUC scores one parameter set, device_average reports the mean over the draws")
         train.upload(h, 0)
         test.upload(h, 1)
         self._train, self._test = train, test
+        for slot, d in ((0, train), (1, test)):
+            if id(d) in self._queries:
+                h.set_row_queries(slot, *self._queries[id(d)])
         self.pred_sum_all = np.zeros(test.num_cases)
         if self.device_average:
             h.post_begin(1)
@@ -349,6 +395,7 @@ class FMLearnALS:
                 print("#Iter=%3d\tTrain=%g\tTest=%g" % (i, st.train_metric, acc), file=self.out)
             self.log.append(row)
             _log_extra_metrics(self, i, train, test)
+            _log_query_metrics(self, i, train, test)
         if self.device_average:
             self._post_download(test)
         h.als_end()
@@ -403,6 +450,22 @@ class FMLearnALS:
             return self._h.post_evaluate_ex(1, capi.POST_ALL)
         return self._h.evaluate_ex(0 if data is self._train else 1, capi.LINK_PROBIT)
 
+    def set_queries(self, data, qid, n_queries=None):
+        """one query id (user, session) per row of the train or test set, before learn(): the iterations then report the
+        per-query AUC of the set under the parameters of the sweep (fmx_set_row_queries)"""
+        self._queries[id(data)] = (_check_queries(data, qid), n_queries)
+        if data is self._train or data is self._test:
+            self._h.set_row_queries(0 if data is self._train else 1, *self._queries[id(data)])
+
+    def evaluate_by_query(self, data):
+        """exact AUC inside every query of the train or test set of learn() under the parameters of the last sweep
+        (fmx_evaluate_by_query / fmx_group_evaluate_by_query; probit link for the pooled log loss)"""
+        if data is not self._train and data is not self._test:
+            raise ValueError("evaluate_by_query: the data set is neither the train nor the test set of learn()")
+        if id(data) not in self._queries:
+            raise ValueError("evaluate_by_query: the data set has no query ids (set_queries)")
+        return self._h.evaluate_by_query(0 if data is self._train else 1, capi.LINK_PROBIT)
+
     TOPK_SLOTS = (2, 3)             # learn() keeps train and test in slots 0 and 1
 
     def recommend(self, queries, candidates, topk, exclude=None):
@@ -453,6 +516,14 @@ class FMLearnMCMC(FMLearnALS):
         self.do_multilevel = True
         self.alpha_0 = self.gamma_0 = self.beta_0 = 1.0
         self.mu_0 = 0.0
+
+    def set_queries(self, data, qid, n_queries=None):
+        raise NotImplementedError("set_queries: the MCMC prediction is the average over the draws (pred_sum_all / num_iter); "
+                                  "no single parameter set scores it")
+
+    def evaluate_by_query(self, data):
+        raise NotImplementedError("evaluate_by_query: the MCMC prediction is the average over the draws (pred_sum_all / num_iter); "
+                                  "no single device pass scores it")
 
     def evaluate_ex(self, data):
         if self.device_average:
@@ -705,5 +776,6 @@ class FMLearnSGDA(FMLearnSGD):
                     row["regv[%d,%d]" % (g, f)] = float(reg[g, 1 + f])
             self.log.append(row)
             _log_extra_metrics(self, i, train, test)
+            _log_query_metrics(self, i, train, test)
         h.sgda_end()
         self.sync_model()
