@@ -949,6 +949,58 @@ int fmx_sgda_epoch_minibatch(fmx_handle h, int train_slot, int validation_slot, 
 int fmx_sgda_get_reg(fmx_handle h, double *reg /* [G][1 + num_factor] */);
 int fmx_sgda_end(fmx_handle h);
 
+/* ---- AdaGrad on the minibatch rule (a per-coordinate step size; no counterpart in the reference) ----------------------
+ * Every other trainer applies one learn_rate to every coordinate, and the batch rule is only stable while
+ * learn_rate * curvature * batch * C <= 1 (fmx_sgd_opts::batch).  Under AdaGrad a coordinate moves by eta * g / sqrt(n + g^2) per
+ * batch: |step| < eta however many occurrences the batch sums.  A caller detects the feature by the symbol fmx_adapt_begin.
+ *
+ * One epoch cuts the slot's rows into batches of `batch` consecutive rows.  Per batch (steps 1 and 2 are exactly the oracle's
+ * fmo_sgd_epoch_minibatch with bias_lag = 0):
+ *   1. from the batch-start parameters, per example e: S_ef, rest_e;
+ *   2. the bias advances in micro-chunks of `w0_chunk` examples with PLAIN SGD at fmx_config::learn_rate and reg0; mult_e is the
+ *      multiplier taken with its micro-chunk's own bias.  The bias deliberately stays non-adaptive: every example touches it,
+ *      and the micro-chunk rule already chooses a stable step for it;
+ *   3. for every feature j that occurs in the batch, from the batch-start w_j, v_jf, its occurrences (e, x) in row order and
+ *      nocc = their number (ids repeated inside a row count as separate occurrences, as everywhere else):
+ *        g_w  = sum_occ mult_e * x                          + nocc * regw * w_j
+ *        g_vf = sum_occ mult_e * (S_ef * x - v_jf * x * x)  + nocc * regv * v_jf
+ *        n_w[j]   += g_w^2;   w_j  -= eta * g_w  / sqrt(n_w[j])       (only with k1)
+ *        n_v[j,f] += g_vf^2;  v_jf -= eta * g_vf / sqrt(n_v[j,f])
+ *      g is the gradient sum the plain rule multiplies by learn_rate.  The accumulators start at init_acc > 0, so there is no
+ *      epsilon.  A feature that no batch touches keeps its parameters and accumulators bit for bit.
+ * The device works in fp32 (n' = fmaf(g, g, n), theta' = theta - eta * g / sqrtf(n'), correctly rounded), one owner per
+ * (batch, feature): no atomics, two runs of the same calls are bit-identical.
+ *
+ *   fmx_adapt_begin : allocates n_w[n_local] and n_v[n_local][row stride] (the stride of V's rows: num_factor rounded up to 16, or
+ *                     to a power of two below 32) and sets every accumulator to init_acc: 4 * n_local * (row stride + 1) bytes stay
+ *                     resident until fmx_adapt_end / fmx_destroy.  Called again it resets the accumulators (and takes the new
+ *                     options).  Unlike fmx_sgda_begin NOTHING in the model is reset.  fmx_set_params, fmx_load_model and plain
+ *                     fmx_sgd_epoch leave the accumulators alone while a session is open.
+ *   fmx_adapt_epoch : one epoch.  batch = 0 resolves exactly as fmx_sgd_opts::batch = 0 does (the plain rule's stability cut --
+ *                     conservative on purpose); an explicit batch is honoured.  w0_chunk = 0: fmx_default_w0_chunk.  The stats are
+ *                     filled as fmx_sgda_epoch_minibatch fills them (rows, batches, device_seconds, main_kernel_*,
+ *                     max_feature_count, batch_used, collision_mass, batch_gain, status) plus w0_chunk_used and setup_seconds.
+ *                     An empty slot returns FMX_OK with zero rows.
+ *   fmx_adapt_get_state_rows : the accumulators of `count` features, gathered on the device; layout of fmx_get_param_rows
+ *                     (nw_out[count], nv_out[count][num_factor]; nv_out may be NULL only when num_factor = 0).
+ *   fmx_adapt_end   : frees the accumulators.
+ * Refusals.  FMX_E_ARG: NULL opts, unknown rule, flags != 0, init_acc negative, NaN or infinite, learn_rate negative or NaN, NULL
+ * outputs of _get_state_rows, an id >= num_attribute.  FMX_E_STATE: _epoch, _get_state_rows or _end without _begin; a slot never
+ * uploaded or without targets; an open SGDA session (and fmx_sgda_begin while this session is open); an open ALS / MCMC session
+ * on the slot.  FMX_E_UNSUPPORTED: a feature shard or communicator rank; kept `-relation` blocks ("relations are not supported
+ * with SGD", fm_learn_sgd.h:61-63).  The handle stays usable after every refusal. */
+#define FMX_ADAPT_ADAGRAD 1u
+typedef struct fmx_adapt_opts {
+  uint32_t rule;        /* FMX_ADAPT_ADAGRAD */
+  uint32_t flags;       /* none defined: 0 */
+  double   init_acc;    /* start value of every accumulator; 0 = 1.0; otherwise finite and > 0 */
+  double   learn_rate;  /* eta of w and V; 0 = fmx_config::learn_rate.  The bias always uses fmx_config::learn_rate */
+} fmx_adapt_opts;
+int fmx_adapt_begin(fmx_handle h, const fmx_adapt_opts *opts);
+int fmx_adapt_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
+int fmx_adapt_get_state_rows(fmx_handle h, const uint32_t *ids, uint32_t count, double *nw_out, double *nv_out);
+int fmx_adapt_end(fmx_handle h);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 typedef struct fmx_info {
   uint64_t n_local;         /* features held by this handle */

@@ -67,6 +67,13 @@ class EpochStats(C.Structure):
                 ("setup_seconds", C.c_double), ("phase_seconds", C.c_double * 4)]
 
 
+ADAPT_ADAGRAD = 1   # FMX_ADAPT_ADAGRAD: fmx_adapt_opts::rule
+
+
+class AdaptOpts(C.Structure):
+    _fields_ = [("rule", C.c_uint32), ("flags", C.c_uint32), ("init_acc", C.c_double), ("learn_rate", C.c_double)]
+
+
 class BatchInfo(C.Structure):
     _fields_ = [("collision_mass", C.c_double), ("batch_gain", C.c_double), ("batch", C.c_uint32), ("status", C.c_uint32)]
 
@@ -266,6 +273,10 @@ SYMBOLS = [
     ("fmx_sgda_epoch_minibatch", C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
     ("fmx_sgda_get_reg", C.c_int, [H, C.c_void_p]),
     ("fmx_sgda_end", C.c_int, [H]),
+    ("fmx_adapt_begin", C.c_int, [H, C.POINTER(AdaptOpts)]),
+    ("fmx_adapt_epoch", C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
+    ("fmx_adapt_get_state_rows", C.c_int, [H, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("fmx_adapt_end", C.c_int, [H]),
     ("fmx_als_begin", C.c_int, [H, C.c_int]),
     ("fmx_als_moments", C.c_int, [H, C.c_void_p]),
     ("fmx_als_sweep", C.c_int, [H, C.POINTER(AlsOpts), C.POINTER(AlsStats)]),
@@ -710,6 +721,32 @@ class Handle:
 
     def sgda_end(self):
         self._chk(self.lib.fmx_sgda_end(self.h))
+
+    # AdaGrad on the minibatch rule (include/fmx.h "fmx_adapt_*") --------------------------------
+    def adapt_begin(self, rule="adagrad", init_acc=0.0, learn_rate=0.0):
+        """opens (or resets) the session: every accumulator = init_acc (0 = 1.0); learn_rate 0 = the handle's"""
+        if isinstance(rule, str):                    # (an integer goes to the library as it is: it refuses the ones it does not know)
+            if rule != "adagrad":
+                raise ValueError("adapt_begin: unknown rule %r (adagrad)" % (rule,))
+            rule = ADAPT_ADAGRAD
+        opts = AdaptOpts(int(rule), 0, float(init_acc), float(learn_rate))
+        self._chk(self.lib.fmx_adapt_begin(self.h, C.byref(opts)))
+
+    def adapt_epoch(self, slot, batch=0, w0_chunk=0):
+        st = EpochStats()
+        self._chk(self.lib.fmx_adapt_epoch(self.h, int(slot), int(batch), int(w0_chunk), C.byref(st)))
+        return st
+
+    def adapt_state_rows(self, ids):
+        """(n_w[ids], n_v[:, ids]): the accumulators, in the layout of get_param_rows"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        nw = np.zeros(len(ids), dtype=np.float64)
+        nv = np.zeros((len(ids), max(self.k, 1)), dtype=np.float64)
+        self._chk(self.lib.fmx_adapt_get_state_rows(self.h, _ptr(ids), len(ids), _ptr(nw), _ptr(nv) if self.k > 0 else None))
+        return nw, nv[:, :self.k].T.copy()
+
+    def adapt_end(self):
+        self._chk(self.lib.fmx_adapt_end(self.h))
 
     # ALS / MCMC ----------------------------------------------------------------------------
     def als_begin(self, train_slot):

@@ -31,6 +31,9 @@ auc_within_* columns of -rlog; stdout stays byte for byte what it is without the
 -device_average 1 (als, mcmc): the test predictions and their running sums stay on the device (fmx_post_accumulate); the #Iter=
 lines gain the reference's Test(ll) column on -task c, -rlog its rmse_mcmc_* / acc_mcmc_* / ll_mcmc_* columns, and -metrics then
 scores the averaged test prediction ("#Iter=  i\tauc: Test=.." on stderr, auc_test / logloss_test) -- with -method mcmc too.
+-optimizer sgd|adagrad [-init_acc X] (-method sgd, -gpu_mode minibatch): adagrad trains w and V with a per-coordinate step size on
+the minibatch rule (fmx_adapt_epoch; -learn_rate is its eta and the bias's plain rate, X the start value of the accumulators,
+default 1); the printed lines are those of sgd.  Without the option nothing changes.
 """
 import os
 import sys
@@ -68,7 +71,9 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "test_queries": "filename with one query id (non-negative integer) per test row: per-query AUC (GAUC) per iteration on"
                          " stderr; -task c with sgd, sgda, als",
          "train_queries": "the same for the train rows; needs -test_queries",
-         "device_average": "als, mcmc: 1 = keep the test predictions and their running mean on the device; default=0"}
+         "device_average": "als, mcmc: 1 = keep the test predictions and their running mean on the device; default=0",
+         "optimizer": "sgd: sgd | adagrad (a per-coordinate step size on the minibatch rule); default=sgd",
+         "init_acc": "-optimizer adagrad: start value of every accumulator (> 0); default=1"}
 
 
 def read_pairs(path, n_rows):
@@ -235,6 +240,19 @@ def _main(argv):
     dev_avg = dev_avg == "1"
     if dev_avg and method not in ("als", "mcmc"):
         raise ValueError("-device_average belongs to -method als and mcmc")
+    optimizer = a.get("optimizer", "sgd")
+    if "optimizer" in a or "init_acc" in a:
+        if optimizer not in L.FMLearnSGD.OPTIMIZERS:
+            raise ValueError("-optimizer knows sgd and adagrad, not '%s'" % optimizer)
+        if method != "sgd":
+            raise ValueError("-optimizer / -init_acc belong to -method sgd, not -method %s" % method)
+        if optimizer == "adagrad" and a.get("gpu_mode", "minibatch") != "minibatch":
+            raise ValueError("-optimizer adagrad runs on the minibatch rule: -gpu_mode %s is not supported" % a["gpu_mode"])
+        if "init_acc" in a:
+            if optimizer != "adagrad":
+                raise ValueError("-init_acc belongs to -optimizer adagrad")
+            if not (0.0 < float(a["init_acc"]) < float("inf")):
+                raise ValueError("-init_acc needs a finite value > 0")
     metrics = tuple(split_list(a.get("metrics", "")))
     if "metrics" in a:
         for m in metrics:
@@ -381,6 +399,9 @@ def _main(argv):
         l.mode = a.get("gpu_mode", "minibatch")
         l.batch = int(a.get("batch", "0"))
         l.w0_chunk = int(a.get("w0_chunk", "0"))
+        if optimizer != "sgd":
+            l.optimizer = optimizer
+            l.init_acc = float(a.get("init_acc", "0"))
     else:
         if method == "als":
             l = L.FMLearnALS()

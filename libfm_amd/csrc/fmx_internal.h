@@ -153,6 +153,8 @@ struct LagState {                 // FMX_FLAG_BIAS_LAG bookkeeping (split step):
 
 struct SgdaState { float* gw = nullptr; float* gv = nullptr; double* reg = nullptr; double* dreg = nullptr;   // dreg: [workgroups][G][1 + KP] partial lambda changes
                    size_t dreg_cap = 0; };
+// an open fmx_adapt_* session (fmx_sgd.hip): the per-coordinate accumulators, n_v with V's row stride
+struct AdaptState { float* nw = nullptr; float* nv = nullptr; float eta = 0.f; };
 
 // The parameter tables of a big model live in an ARENA: one virtual range backed by 1 GiB physical chunks (hipMemCreate) taken
 // alternately from two memory classes of the device (fmx_create)
@@ -174,6 +176,7 @@ struct fmx_context_s {
   fmx_config cfg;
   AlsState   als;
   SgdaState  sgda;
+  AdaptState adapt;
   LagState   lag;
   int        KP = 1;
   double     setup_acc = 0.0;    // host seconds of one-time slot preparation since the epoch entry point last cleared it
@@ -311,6 +314,7 @@ int scan_error_check(fmx_handle h);                                      // fmx_
 uint32_t multi_group_size(const Slot& s, int KP);                        // fmx_sgd.hip: examples per wavefront of the short-row kernels (0: rows are long)
 bool streams_concurrent(fmx_handle h);                                   // fmx_sgd.hip: probed once per handle
 void sgda_free(fmx_handle h);                                            // fmx_sgd.hip
+void adapt_free(fmx_handle h);                                           // fmx_sgd.hip
 void als_free(fmx_handle h);                                             // fmx_als.hip
 enum { GROUP_SINGLE = 0, GROUP_LOOPBACK = 1, GROUP_RCCL = 2 };
 struct fmx_group_s {                      // fmx_comm.hip

@@ -1,9 +1,11 @@
 // fmx_sgd.hip -- C-ABI (include/fmx.h): the SGD family -- sequential / minibatch / hogwild epochs, the split step of
-// the multi-GPU driver, the bias-lag bookkeeping, the (batch, feature) segment build, and SGDA.
+// the multi-GPU driver, the bias-lag bookkeeping, the (batch, feature) segment build, SGDA, and AdaGrad on
+// the minibatch rule (fmx_adapt_*).
 #include "fmx_internal.h"
 #include "fmx_online_kernels.h"
 #include "fmx_seq_kernels.h"
 #include "fmx_small_kernels.h"
+#include "fmx_adapt_kernels.h"
 
 namespace {
 // default micro-chunk of the bias recurrence.  The reference moves w0 after EVERY example (fm_sgd.h:34-37); summing the
@@ -1331,6 +1333,7 @@ int fmx_sgda_end(fmx_handle h) {
 int fmx_sgda_begin(fmx_handle h) {
   touch_w(h);
   if (!h) return FMX_E_ARG;
+  if (h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_sgda_begin: an fmx_adapt session is open (call fmx_adapt_end first)");
   if (h->cfg.shard_world > 1) return fail(h, FMX_E_UNSUPPORTED, "SGDA on a feature shard is not implemented");
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   HIPCHK(h, hipSetDevice(h->device));
@@ -1487,6 +1490,150 @@ int fmx_sgda_epoch_minibatch(fmx_handle h, int train_slot, int validation_slot, 
     stats->main_kernel_seconds = stats->device_seconds; stats->main_kernel_launches = batches;
     stats->max_feature_count = s.max_seg_count;
     stats->batch_used = bi.batch; stats->collision_mass = bi.collision_mass; stats->batch_gain = bi.batch_gain; stats->status = bi.status;
+  }
+  return FMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// AdaGrad on the minibatch rule (include/fmx.h "fmx_adapt_*"; the owner kernel is fmx_adapt_kernels.h)
+// ---------------------------------------------------------------------------------------------
+extern "C++" void adapt_free(fmx_handle h) {
+  if (h->adapt.nw) fmx_dev_free(h->adapt.nw);
+  if (h->adapt.nv) fmx_dev_free(h->adapt.nv);
+  h->adapt = AdaptState();
+}
+
+// what every fmx_adapt_* entry point refuses whatever the session's state
+static int adapt_check_handle(fmx_handle h, const char* what) {
+  if (h->cfg.shard_world > 1 || h->comm || (h->group && !h->owns_group))
+    return fail(h, FMX_E_UNSUPPORTED, "%s: not supported on feature shards / communicator ranks", what);
+  return FMX_OK;
+}
+
+int fmx_adapt_begin(fmx_handle h, const fmx_adapt_opts* opts) {
+  if (!h) return FMX_E_ARG;
+  if (!opts) return fail(h, FMX_E_ARG, "fmx_adapt_begin: opts is NULL");
+  if (opts->rule != FMX_ADAPT_ADAGRAD) return fail(h, FMX_E_ARG, "fmx_adapt_begin: unknown rule %u", opts->rule);
+  if (opts->flags != 0) return fail(h, FMX_E_ARG, "fmx_adapt_begin: flags must be 0");
+  if (!(opts->init_acc >= 0.0) || std::isinf(opts->init_acc)) return fail(h, FMX_E_ARG, "fmx_adapt_begin: init_acc must be finite and >= 0 (0 = 1.0)");
+  if (!(opts->learn_rate >= 0.0)) return fail(h, FMX_E_ARG, "fmx_adapt_begin: learn_rate must be >= 0 (0 = fmx_config::learn_rate)");
+  int rc = adapt_check_handle(h, "fmx_adapt_begin"); if (rc) return rc;
+  if (h->sgda.reg) return fail(h, FMX_E_STATE, "fmx_adapt_begin: an SGDA session is open (call fmx_sgda_end first)");
+  const float init_acc = opts->init_acc > 0.0 ? (float)opts->init_acc : 1.0f;
+  if (!(init_acc > 0.f) || std::isinf(init_acc)) return fail(h, FMX_E_ARG, "fmx_adapt_begin: init_acc %g is not a positive fp32 number", opts->init_acc);
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const size_t nv = h->n_local * (size_t)h->tb.rs;
+  if (!h->adapt.nv) {                                           // (again = reset: the tables are there)
+    HIPCHK(h, fmx_dev_alloc(&h->adapt.nw, h->n_local * sizeof(float)));
+    hipError_t e = fmx_dev_alloc(&h->adapt.nv, nv * sizeof(float));
+    if (e != hipSuccess) { adapt_free(h); return fail(h, FMX_E_HIP, "fmx_adapt_begin: the accumulator table (%zu bytes): %s", nv * sizeof(float), hipGetErrorString(e)); }
+  }
+  h->adapt.eta = (float)(opts->learn_rate > 0.0 ? opts->learn_rate : h->cfg.learn_rate);
+  hipLaunchKernelGGL(k_adapt_fill, dim3((unsigned)std::min<size_t>((h->n_local + 255) / 256, 2048)), dim3(256), 0, h->stream, h->adapt.nw, (uint64_t)h->n_local, init_acc);
+  hipLaunchKernelGGL(k_adapt_fill, dim3((unsigned)std::min<size_t>((nv + 255) / 256, 2048)), dim3(256), 0, h->stream, h->adapt.nv, (uint64_t)nv, init_acc);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return FMX_OK;
+}
+
+int fmx_adapt_end(fmx_handle h) {
+  if (!h) return FMX_E_ARG;
+  if (!h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_adapt_end before fmx_adapt_begin");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  adapt_free(h);
+  return FMX_OK;
+}
+
+int fmx_adapt_get_state_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double* nw_out, double* nv_out) {
+  if (!h) return FMX_E_ARG;
+  const int k = h->cfg.num_factor;
+  if (!ids || !nw_out || (k > 0 && !nv_out)) return fail(h, FMX_E_ARG, "fmx_adapt_get_state_rows: ids / nw_out / nv_out is NULL");
+  if (!h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_adapt_get_state_rows before fmx_adapt_begin");
+  for (uint32_t i = 0; i < count; i++)
+    if (ids[i] >= h->cfg.num_attribute) return fail(h, FMX_E_ARG, "feature id %u >= num_attribute", ids[i]);
+  if (count == 0) return FMX_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  uint32_t* d_ids = nullptr; double* d_out = nullptr;
+  const size_t nout = (size_t)count * (size_t)(k + 1);
+  HIPCHK(h, fmx_dev_alloc(&d_ids, (size_t)count * 4));
+  hipError_t er = fmx_dev_alloc(&d_out, nout * sizeof(double));
+  if (er == hipSuccess) er = hipMemcpyAsync(d_ids, ids, (size_t)count * 4, hipMemcpyHostToDevice, h->stream);
+  if (er == hipSuccess) {                                       // the gather of fmx_get_param_rows over the accumulator tables
+    const Tab ac{h->adapt.nv, h->adapt.nw, h->tb.rs, 1u};
+    hipLaunchKernelGGL(k_fetch_rows, dim3((uint32_t)((nout + 255) / 256)), dim3(256), 0, h->stream, d_ids, count, k,
+                       make_shard(h->cfg), ac, d_out, d_out + count);
+    er = hipGetLastError();
+  }
+  if (er == hipSuccess) er = hipMemcpyAsync(nw_out, d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+  if (er == hipSuccess && k > 0) er = hipMemcpyAsync(nv_out, d_out + count, (size_t)count * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+  if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
+  fmx_dev_free(d_ids); fmx_dev_free(d_out);
+  if (er != hipSuccess) return fail(h, FMX_E_HIP, "fmx_adapt_get_state_rows: %s", hipGetErrorString(er));
+  return FMX_OK;
+}
+
+// one epoch: per batch the batch rule's row sums and bias recurrence (fmx_sgda_epoch_minibatch's three launches), then one owner per
+// (batch, feature) segment takes the AdaGrad step (k_adapt_apply_seg).  The bias stays plain SGD at fmx_config::learn_rate.
+int fmx_adapt_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
+  int rc = check_slot(h, slot, true);
+  if (rc) return rc;
+  if (!h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_adapt_epoch before fmx_adapt_begin");
+  rc = adapt_check_handle(h, "fmx_adapt_epoch"); if (rc) return rc;
+  if (h->sgda.reg) return fail(h, FMX_E_STATE, "fmx_adapt_epoch: an SGDA session is open (call fmx_sgda_end first)");
+  rc = slot_in_session(h, slot, "fmx_adapt_epoch"); if (rc) return rc;
+  { int _rc = lag_flush(h); if (_rc) return _rc; }
+  HIPCHK(h, hipSetDevice(h->device));
+  Slot& s = h->slots[slot];
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (s.n_rows == 0) return FMX_OK;
+  if (!s.blocks.empty()) return fail(h, FMX_E_UNSUPPORTED, "relations are not supported with SGD");   // fm_learn_sgd.h:61-63
+  h->setup_acc = 0.0; h->run_status = 0;
+  const Hyper hy = make_hyper(h->cfg);
+  // batch 0: fmx_sgd_epoch's choice (the plain rule's stability cut, curvature factor 1): conservative on purpose -- the step is bounded
+  // by eta whatever the batch, but whether a larger default pays is a measurement, not this function's decision
+  fmx_batch_info bi;
+  rc = ensure_coll_mass(h, s); if (rc) return rc;
+  resolve_batch(h->cfg, s.coll_mass, batch, FMX_DEFAULT_BATCH, 1.0, &bi);
+  const uint32_t B = bi.batch;
+  const uint32_t chunk = w0_chunk ? w0_chunk : default_w0_chunk(h->cfg);
+  rc = ensure_segments(h, s, B); if (rc) return rc;
+  const uint32_t Bc = std::min<uint32_t>(B, s.n_rows);
+  rc = ensure_scratch(h, Bc, 0); if (rc) return rc;
+  touch_w(h);                                                   // (a side stream kept by FMX_FLAG_KEEP_WSIDE is stale from here on)
+  const Tab ac{h->adapt.nv, h->adapt.nw, h->tb.rs, 1u};
+  const float eta = h->adapt.eta;
+  hipStream_t st = h->stream;
+  HIPCHK(h, hipEventRecord(h->ev0, st));
+  uint64_t batches = 0;
+  for (uint64_t row0 = 0; row0 < s.n_rows; row0 += B) {
+    const uint32_t nb = (uint32_t)std::min<uint64_t>(B, s.n_rows - row0);
+    float* S = h->partial;
+    float* rest = S + (size_t)nb * h->KP;
+    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, st, s.ent, s.row_ptr, row0, nb, h->tb, h->cfg.k1, S, rest, (const float*)nullptr));
+    rc = launch_scan(h, rest, s.target + row0, nb, chunk, hy, h->mult, st);
+    if (rc) return rc;
+    const SegWork sw = seg_work_dense(h, s, (size_t)(row0 / B), S, h->mult);
+    if (sw.nseg) {
+      KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_adapt_apply_seg<KP, AdaptU<KP>::value>), ((uint64_t)sw.nseg + 63) / 64, st, sw, h->tb, ac, hy, eta));
+    }
+    HIPCHK(h, hipGetLastError());
+    batches++;
+  }
+  HIPCHK(h, hipEventRecord(h->ev1, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  rc = scan_error_check(h); if (rc) return rc;
+  if (stats) {
+    float ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    stats->rows = s.n_rows; stats->batches = batches; stats->device_seconds = ms * 1e-3;
+    stats->main_kernel_seconds = stats->device_seconds; stats->main_kernel_launches = batches;
+    stats->max_feature_count = s.max_seg_count;
+    stats->batch_used = bi.batch; stats->collision_mass = bi.collision_mass; stats->batch_gain = bi.batch_gain;
+    stats->status = bi.status | h->run_status;
+    stats->w0_chunk_used = chunk;
+    stats->setup_seconds = h->setup_acc;
   }
   return FMX_OK;
 }

@@ -159,8 +159,11 @@ class FMLearnSGD:
 
     Public knobs are plain fields set by the driver, like libfm.cpp:271-309, 387-403 does by direct writes:
     fm, min_target, max_target, task, num_iter, learn_rate.  GPU-only knobs: mode ('sequential' | 'minibatch' |
-    'hogwild'), batch, w0_chunk, apply ('default' | 'segmented' | 'atomic' | 'store'), device."""
+    'hogwild'), batch, w0_chunk, apply ('default' | 'segmented' | 'atomic' | 'store'), device; optimizer ('sgd': the reference's one
+    learn_rate for every coordinate | 'adagrad': a per-coordinate step on the minibatch rule, fmx_adapt_*, with init_acc the start
+    value of the accumulators (0 = 1.0) and adapt_learn_rate the eta of w and V (0 = learn_rate; the bias keeps learn_rate))."""
 
+    OPTIMIZERS = ("sgd", "adagrad")
     MODES = {"sequential": capi.SGD_SEQUENTIAL, "minibatch": capi.SGD_MINIBATCH, "hogwild": capi.SGD_HOGWILD}
     APPLY = {"default": capi.APPLY_DEFAULT, "atomic": capi.APPLY_ATOMIC, "store": capi.APPLY_STORE,
              "segmented": capi.APPLY_SEGMENTED, "fused": capi.APPLY_FUSED}
@@ -178,6 +181,9 @@ class FMLearnSGD:
         self.apply = "fused"                                    # the batch rule in one pass (hogwild: "default")
         self.bias_lag = 2
         self.reject_unstable = True                             # an explicit batch the rule diverges at raises instead of training
+        self.optimizer = "sgd"
+        self.init_acc = 0.0
+        self.adapt_learn_rate = 0.0
         self.device = -1
         self.log = []                                           # one dict per iteration (rlog fields)
         self.extra_metrics = ()                                 # classification: "auc" and / or "logloss" per iteration, on stderr and in log
@@ -185,6 +191,13 @@ class FMLearnSGD:
         self._h = None
         self._slots = {}
         self._queries = {}                                      # id(data) -> (qid, n_queries) of set_queries
+        self._adapt_open = False
+
+    def _check_optimizer(self):
+        if self.optimizer not in self.OPTIMIZERS:
+            raise ValueError("unknown optimizer for %s: %s (%s)" % (type(self).__name__, self.optimizer, " | ".join(self.OPTIMIZERS)))
+        if self.optimizer == "adagrad" and self.mode != "minibatch":
+            raise ValueError("optimizer adagrad runs on the minibatch rule: mode %s is not supported" % self.mode)
 
     # fm_learn::init (fm_learn.h:73-91): here it creates the device context and uploads the parameters
     def init(self):
@@ -192,10 +205,14 @@ class FMLearnSGD:
             raise ValueError("unknown task")                    # fm_learn.h:81
         if self.learn_rate is None:
             raise ValueError("learn_rate must be set")          # the reference asserts (libfm.cpp:391-392)
+        self._check_optimizer()
         fm = self.fm
         self._h = capi.Handle(fm.num_attribute, fm.num_factor, fm.k0, fm.k1, self.task, fm.reg0, fm.regw, fm.regv,
                               self.learn_rate, self.min_target, self.max_target, device=self.device)
         self._h.set_params(fm.w0, fm.w, fm.v)
+        if self.optimizer == "adagrad":
+            self._h.adapt_begin("adagrad", self.init_acc, self.adapt_learn_rate)
+            self._adapt_open = True
 
     def _slot(self, data):
         key = id(data)
@@ -225,6 +242,9 @@ class FMLearnSGD:
 
     # fm_learn_sgd_element::learn (fm_learn_sgd_element.h:48-78)
     def learn(self, train, test):
+        self._check_optimizer()
+        if (self.optimizer == "adagrad") != self._adapt_open:
+            raise ValueError("optimizer was changed after init()")
         print("learnrate=%g" % self.learn_rate, file=self.out)   # fm_learn_sgd.h:57-59
         print("#iterations=%d" % self.num_iter, file=self.out)
         print("SGD: DON'T FORGET TO SHUFFLE THE ROWS IN TRAINING DATA TO GET THE BEST RESULTS.", file=self.out)
@@ -235,8 +255,11 @@ class FMLearnSGD:
                 apply_ = capi.APPLY_DEFAULT
             flags = capi.FLAG_REJECT_UNSTABLE if (self.reject_unstable and self.mode == "minibatch") else 0
             flags |= capi.FLAG_KEEP_WSIDE                # the train set is evaluated after every epoch (fm_learn_sgd_element.h:69-70)
-            stats = self._h.sgd_epoch(st, self.MODES[self.mode], apply_, self.batch, self.w0_chunk, flags,
-                                      self.bias_lag if apply_ == capi.APPLY_FUSED else 0)
+            if self._adapt_open:
+                stats = self._h.adapt_epoch(st, self.batch, self.w0_chunk)
+            else:
+                stats = self._h.sgd_epoch(st, self.MODES[self.mode], apply_, self.batch, self.w0_chunk, flags,
+                                          self.bias_lag if apply_ == capi.APPLY_FUSED else 0)
             if i == 0 and self.mode == "minibatch" and (stats.status & capi.STAT_BATCH_CUT):
                 print("libfmx: batch %d (collision mass of the rows %.4g, gain %.3g)" % (stats.batch_used, stats.collision_mass,
                                                                                         stats.batch_gain), file=sys.stderr)
@@ -288,6 +311,9 @@ class FMLearnSGD:
 
     def close(self):
         if self._h is not None:
+            if self._adapt_open:
+                self._h.adapt_end()
+                self._adapt_open = False
             self._h.close()
             self._h = None
 
@@ -612,6 +638,7 @@ class FMLearnPairSGD(FMLearnSGD):
     batch (minibatch: pairs per batch, 0 = the library's default).  Pairs are (row_a, row_b) arrays of 0-based rows of their data."""
 
     MODES = {"sequential": capi.SGD_SEQUENTIAL, "minibatch": capi.SGD_MINIBATCH}
+    OPTIMIZERS = ("sgd",)
 
     def __init__(self):
         super().__init__()
@@ -633,6 +660,7 @@ class FMLearnPairSGD(FMLearnSGD):
         return self._h.pair_evaluate(slot).accuracy
 
     def learn(self, train, train_pairs, test, test_pairs):
+        self._check_optimizer()
         if self.mode not in self.MODES:
             raise ValueError("unknown mode for pairwise SGD: %s (sequential | minibatch)" % self.mode)
         print("learnrate=%g" % self.learn_rate, file=self.out)
@@ -740,6 +768,8 @@ class FMLearnSGDA(FMLearnSGD):
     on the train rows alternate with lambda steps on `validation` (libfm.cpp:276-279).  gpu_batch = 0: the reference's
     strictly online order (one wavefront, parity); > 0: the batch form (fmx_sgda_epoch_minibatch)."""
 
+    OPTIMIZERS = ("sgd",)
+
     def __init__(self):
         super().__init__()
         self.gpu_batch, self.gpu_w0_chunk = 0, 0
@@ -751,6 +781,7 @@ class FMLearnSGDA(FMLearnSGD):
     def learn(self, train, test):
         if self.validation is None:
             raise ValueError("sgda needs a validation set")              # the reference asserts (libfm.cpp:277)
+        self._check_optimizer()
         print("Training using self-adaptive-regularization SGD.", file=self.out)
         h = self._h
         st, sv = self._slot(train), self._slot(self.validation)
