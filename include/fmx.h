@@ -1001,6 +1001,79 @@ int fmx_adapt_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, f
 int fmx_adapt_get_state_rows(fmx_handle h, const uint32_t *ids, uint32_t count, double *nw_out, double *nv_out);
 int fmx_adapt_end(fmx_handle h);
 
+/* ---- FTRL-proximal with L1 on the minibatch rule (a sparse model; no counterpart in the reference) ----------------------
+ * Every other trainer's L2 only shrinks a coordinate.  FTRL-proximal (McMahan et al., "Ad click prediction: a view from the
+ * trenches") with an L1 term sets a coordinate whose accumulated gradient stays small to EXACTLY zero, and fmx_param_sparsity
+ * counts the zeros.  A caller detects the feature by the symbol fmx_ftrl_begin.
+ *
+ * One epoch cuts the slot's rows into batches of `batch` consecutive rows.  Steps 1 and 2 of a batch are exactly AdaGrad's (above,
+ * "fmx_adapt_*"): S_ef and rest_e from the batch-start parameters; the bias in micro-chunks with PLAIN SGD at
+ * fmx_config::learn_rate and reg0; mult_e taken with its micro-chunk's bias.  Step 3, for every feature j of the batch, from the
+ * batch-start theta (w_j with k1, every v_jf) and the feature's occurrences (e, x) in row order (an id repeated inside a row counts
+ * as separate occurrences):
+ *        g_w  = sum_occ mult_e * x                  g_vf = sum_occ mult_e * (S_ef * x - v_jf * x * x)
+ *        n'   = n + g^2         sigma = (sqrt(n') - sqrt(n)) / alpha         z' = z + g - sigma * theta
+ *        D'   = (beta + sqrt(n')) / alpha + l2
+ *        theta' = 0                                  if |z'| <= l1     (with l1 = 0 this catches z' == 0 and yields +0)
+ *               = -(z' - sgn(z') * l1) / D'          otherwise
+ *      with (l1, l2) = (l1_w, l2_w) for w and (l1_v, l2_v) for V.  g has NO nocc * reg * theta term and fmx_config::regw / regv are
+ *      not read: L2 lives in the proximal step, ONE strength per coordinate, not one per occurrence as in the plain rule.
+ * Start state.  n = init_acc.  V starts at random non-zero values, and the textbook z = 0 would pull a coordinate most of the way to 0
+ * at its first small gradient (theta_1 ~ theta_0 * |g| / (|g| + beta)).  So fmx_ftrl_begin derives z from the parameters the model
+ * holds at that moment:
+ *        z_0 = -theta_0 * D_0 - sgn(theta_0) * l1,    D_0 = (beta + sqrt(init_acc)) / alpha + l2,    sgn(0) = 0
+ *      at which the closed form returns theta_0; with l1 = 0 every step is theta' = theta - g / D', and for theta_0 = 0 this is the
+ *      textbook rule.  With l1 = l2 = beta = 0, init_acc = a > 0, alpha = eta and regw = regv = 0 the rule IS fmx_adapt's AdaGrad.
+ *      The padding of a V row (f >= num_factor) has theta = z = g = 0 and stays +0.
+ * A feature that no batch touches keeps theta, z and n bit for bit; a touched coordinate is always recomputed from z'.
+ * The device works in fp32 (n' = fmaf(g, g, n), correctly rounded sqrtf and /), one owner per (batch, feature): no atomics, two
+ * runs of the same calls are bit-identical.
+ *
+ *   fmx_ftrl_begin  : allocates z_w, n_w [n_local] and z_v, n_v [n_local][row stride] (V's row stride: fmx_adapt_begin):
+ *                     8 * n_local * (row stride + 1) bytes stay resident until fmx_ftrl_end / fmx_destroy; fills n with init_acc
+ *                     and derives z.  Called again it resets both from the parameters of that moment (and takes the new options).
+ *                     NOTHING in the model is changed.  fmx_set_params, fmx_load_model and plain fmx_sgd_epoch during a session
+ *                     leave z and n alone -- the next epoch then continues from parameters z no longer describes: call
+ *                     fmx_ftrl_begin again after them.
+ *   fmx_ftrl_epoch  : one epoch; batch = 0, w0_chunk = 0, the stats and an empty slot exactly as fmx_adapt_epoch.
+ *   fmx_ftrl_get_state_rows : z and n of `count` features, gathered on the device; each pair in the layout of fmx_get_param_rows
+ *                     (zw[count], zv[count][num_factor], nw[count], nv[count][num_factor]; zv / nv may be NULL only when
+ *                     num_factor = 0).
+ *   fmx_ftrl_end    : frees the tables.
+ * Refusals.  FMX_E_ARG: NULL opts, flags != 0, a negative, NaN or infinite value, alpha (after 0 = fmx_config::learn_rate) not a
+ * positive fp32 number with a finite reciprocal, beta == 0 && init_acc == 0 (D would start at 0), NULL outputs of _get_state_rows,
+ * an id >= num_attribute.  FMX_E_STATE: _epoch, _get_state_rows or _end without _begin; a slot never uploaded or without targets;
+ * an open SGDA or AdaGrad session (and fmx_sgda_begin / fmx_adapt_begin while this session is open); an open ALS / MCMC session
+ * on the slot.  FMX_E_UNSUPPORTED: a feature shard or communicator rank; kept `-relation` blocks.  The handle stays usable after
+ * every refusal. */
+typedef struct fmx_ftrl_opts {
+  uint32_t flags;       /* none defined: 0 */
+  uint32_t reserved;    /* not read */
+  double   alpha;       /* per-coordinate rate; 0 = fmx_config::learn_rate.  The bias always uses fmx_config::learn_rate */
+  double   beta;        /* >= 0 (the Python binding's default is 1) */
+  double   l1_w, l1_v;  /* >= 0: L1 strength of w and of V */
+  double   l2_w, l2_v;  /* >= 0: L2 strength of w and of V, one per coordinate */
+  double   init_acc;    /* start value of every n; >= 0, and > 0 where beta == 0 */
+} fmx_ftrl_opts;
+int fmx_ftrl_begin(fmx_handle h, const fmx_ftrl_opts *opts);
+int fmx_ftrl_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
+int fmx_ftrl_get_state_rows(fmx_handle h, const uint32_t *ids, uint32_t count, double *zw, double *zv, double *nw, double *nv);
+int fmx_ftrl_end(fmx_handle h);
+
+/* How many coordinates of the model are exactly zero -- on any unsharded handle, with or without a training session.  One pass over
+ * both tables on the device, integer sums only.  `== 0.0f` decides: -0 counts, NaN does not; only f < num_factor of a row is looked
+ * at (never its padding).  With num_factor = 0 every row counts as all zero.  FMX_E_ARG: out is NULL.  FMX_E_UNSUPPORTED: a feature
+ * shard or communicator rank. */
+typedef struct fmx_sparsity {
+  uint64_t features;       /* num_attribute */
+  uint64_t w_zero;         /* linear weights that are zero (counted whether or not k1 is set) */
+  uint64_t v_coords;       /* features * num_factor */
+  uint64_t v_zero;         /* factors that are zero */
+  uint64_t v_zero_rows;    /* features whose num_factor factors are all zero */
+  uint64_t dead_features;  /* such features with (w_j == 0 or k1 == 0): they contribute nothing to any prediction */
+} fmx_sparsity;
+int fmx_param_sparsity(fmx_handle h, fmx_sparsity *out);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 typedef struct fmx_info {
   uint64_t n_local;         /* features held by this handle */

@@ -74,6 +74,16 @@ class AdaptOpts(C.Structure):
     _fields_ = [("rule", C.c_uint32), ("flags", C.c_uint32), ("init_acc", C.c_double), ("learn_rate", C.c_double)]
 
 
+class FtrlOpts(C.Structure):                       # fmx_ftrl_opts
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("alpha", C.c_double), ("beta", C.c_double),
+                ("l1_w", C.c_double), ("l1_v", C.c_double), ("l2_w", C.c_double), ("l2_v", C.c_double), ("init_acc", C.c_double)]
+
+
+class Sparsity(C.Structure):                       # fmx_sparsity
+    _fields_ = [("features", C.c_uint64), ("w_zero", C.c_uint64), ("v_coords", C.c_uint64), ("v_zero", C.c_uint64),
+                ("v_zero_rows", C.c_uint64), ("dead_features", C.c_uint64)]
+
+
 class BatchInfo(C.Structure):
     _fields_ = [("collision_mass", C.c_double), ("batch_gain", C.c_double), ("batch", C.c_uint32), ("status", C.c_uint32)]
 
@@ -277,6 +287,11 @@ SYMBOLS = [
     ("fmx_adapt_epoch", C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
     ("fmx_adapt_get_state_rows", C.c_int, [H, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("fmx_adapt_end", C.c_int, [H]),
+    ("fmx_ftrl_begin", C.c_int, [H, C.POINTER(FtrlOpts)]),
+    ("fmx_ftrl_epoch", C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
+    ("fmx_ftrl_get_state_rows", C.c_int, [H, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("fmx_ftrl_end", C.c_int, [H]),
+    ("fmx_param_sparsity", C.c_int, [H, C.POINTER(Sparsity)]),
     ("fmx_als_begin", C.c_int, [H, C.c_int]),
     ("fmx_als_moments", C.c_int, [H, C.c_void_p]),
     ("fmx_als_sweep", C.c_int, [H, C.POINTER(AlsOpts), C.POINTER(AlsStats)]),
@@ -747,6 +762,36 @@ class Handle:
 
     def adapt_end(self):
         self._chk(self.lib.fmx_adapt_end(self.h))
+
+    # FTRL-proximal with L1 on the minibatch rule (include/fmx.h "fmx_ftrl_*") -------------------
+    def ftrl_begin(self, alpha=0.0, beta=1.0, l1_w=0.0, l1_v=0.0, l2_w=0.0, l2_v=0.0, init_acc=0.0):
+        """opens (or resets) the session: n = init_acc, z derived from the parameters the handle holds now; alpha 0 = the handle's
+        learn_rate"""
+        opts = FtrlOpts(0, 0, float(alpha), float(beta), float(l1_w), float(l1_v), float(l2_w), float(l2_v), float(init_acc))
+        self._chk(self.lib.fmx_ftrl_begin(self.h, C.byref(opts)))
+
+    def ftrl_epoch(self, slot, batch=0, w0_chunk=0):
+        st = EpochStats()
+        self._chk(self.lib.fmx_ftrl_epoch(self.h, int(slot), int(batch), int(w0_chunk), C.byref(st)))
+        return st
+
+    def ftrl_state_rows(self, ids):
+        """(z_w[ids], z_v[:, ids], n_w[ids], n_v[:, ids]), each pair in the layout of get_param_rows"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        zw, nw = np.zeros(len(ids), dtype=np.float64), np.zeros(len(ids), dtype=np.float64)
+        zv, nv = (np.zeros((len(ids), max(self.k, 1)), dtype=np.float64) for _ in range(2))
+        self._chk(self.lib.fmx_ftrl_get_state_rows(self.h, _ptr(ids), len(ids), _ptr(zw), _ptr(zv) if self.k > 0 else None,
+                                                   _ptr(nw), _ptr(nv) if self.k > 0 else None))
+        return zw, zv[:, :self.k].T.copy(), nw, nv[:, :self.k].T.copy()
+
+    def ftrl_end(self):
+        self._chk(self.lib.fmx_ftrl_end(self.h))
+
+    def param_sparsity(self):
+        """fmx_sparsity: how many coordinates of the model are exactly zero"""
+        sp = Sparsity()
+        self._chk(self.lib.fmx_param_sparsity(self.h, C.byref(sp)))
+        return sp
 
     # ALS / MCMC ----------------------------------------------------------------------------
     def als_begin(self, train_slot):

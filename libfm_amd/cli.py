@@ -34,6 +34,10 @@ scores the averaged test prediction ("#Iter=  i\tauc: Test=.." on stderr, auc_te
 -optimizer sgd|adagrad [-init_acc X] (-method sgd, -gpu_mode minibatch): adagrad trains w and V with a per-coordinate step size on
 the minibatch rule (fmx_adapt_epoch; -learn_rate is its eta and the bias's plain rate, X the start value of the accumulators,
 default 1); the printed lines are those of sgd.  Without the option nothing changes.
+-optimizer ftrl [-ftrl_alpha A] [-ftrl_beta B] [-l1 W,V] (-method sgd, -gpu_mode minibatch): FTRL-proximal with L1 on the minibatch
+rule (fmx_ftrl_epoch): A the per-coordinate rate (default -learn_rate, which stays the bias's plain rate), B default 1, W and V the L1
+strengths of the linear weights and the factors (default 0,0); the L2 strengths are -regular's regw and regv, one per coordinate.
+After training one line on stderr gives the zero counts of the model (fmx_param_sparsity).
 """
 import os
 import sys
@@ -72,8 +76,12 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
                          " stderr; -task c with sgd, sgda, als",
          "train_queries": "the same for the train rows; needs -test_queries",
          "device_average": "als, mcmc: 1 = keep the test predictions and their running mean on the device; default=0",
-         "optimizer": "sgd: sgd | adagrad (a per-coordinate step size on the minibatch rule); default=sgd",
-         "init_acc": "-optimizer adagrad: start value of every accumulator (> 0); default=1"}
+         "optimizer": "sgd: sgd | adagrad (a per-coordinate step size on the minibatch rule) | ftrl (FTRL-proximal with L1 on the same rule:"
+                      " exact zeros); default=sgd",
+         "init_acc": "-optimizer adagrad: start value of every accumulator (> 0); default=1",
+         "ftrl_alpha": "-optimizer ftrl: per-coordinate rate of w and V (> 0); default=-learn_rate",
+         "ftrl_beta": "-optimizer ftrl: beta (> 0); default=1",
+         "l1": "-optimizer ftrl: 'w,v' = L1 strength of the linear weights and of the factors (>= 0); default=0,0"}
 
 
 def read_pairs(path, n_rows):
@@ -241,11 +249,25 @@ def _main(argv):
     if dev_avg and method not in ("als", "mcmc"):
         raise ValueError("-device_average belongs to -method als and mcmc")
     optimizer = a.get("optimizer", "sgd")
-    if "optimizer" in a or "init_acc" in a:
+    ftrl_flags = [f for f in ("ftrl_alpha", "ftrl_beta", "l1") if f in a]
+    ftrl_l1 = (0.0, 0.0)
+    if "optimizer" in a or "init_acc" in a or ftrl_flags:
         if optimizer not in L.FMLearnSGD.OPTIMIZERS:
-            raise ValueError("-optimizer knows sgd and adagrad, not '%s'" % optimizer)
+            raise ValueError("-optimizer knows sgd and adagrad, not '%s' (ftrl is the third it knows)" % optimizer)
         if method != "sgd":
             raise ValueError("-optimizer / -init_acc belong to -method sgd, not -method %s" % method)
+        if optimizer == "ftrl" and a.get("gpu_mode", "minibatch") != "minibatch":
+            raise ValueError("-optimizer ftrl runs on the minibatch rule: -gpu_mode %s is not supported" % a["gpu_mode"])
+        if ftrl_flags:
+            if optimizer != "ftrl":
+                raise ValueError("-%s belongs to -optimizer ftrl" % ftrl_flags[0])
+            for f in ("ftrl_alpha", "ftrl_beta"):
+                if f in a and not (0.0 < float(a[f]) < float("inf")):
+                    raise ValueError("-%s needs a finite value > 0" % f)
+            if "l1" in a:
+                ftrl_l1 = tuple(float(x) for x in split_list(a["l1"]))
+                if len(ftrl_l1) != 2 or not all(0.0 <= x < float("inf") for x in ftrl_l1):
+                    raise ValueError("-l1 needs 2 finite values >= 0: 'w,v'")
         if optimizer == "adagrad" and a.get("gpu_mode", "minibatch") != "minibatch":
             raise ValueError("-optimizer adagrad runs on the minibatch rule: -gpu_mode %s is not supported" % a["gpu_mode"])
         if "init_acc" in a:
@@ -402,6 +424,9 @@ def _main(argv):
         if optimizer != "sgd":
             l.optimizer = optimizer
             l.init_acc = float(a.get("init_acc", "0"))
+            if optimizer == "ftrl":
+                l.ftrl_alpha, l.ftrl_beta = float(a.get("ftrl_alpha", "0")), float(a.get("ftrl_beta", "1"))
+                l.l1_w, l.l1_v = ftrl_l1
     else:
         if method == "als":
             l = L.FMLearnALS()
@@ -457,6 +482,10 @@ def _main(argv):
         print("Final\tTrain=%g\tTest=%g" % (l.evaluate_pairs(train), l.evaluate_pairs(test)))
     if method in ("sgd", "sgda"):
         print("Final\tTrain=%g\tTest=%g" % (l.evaluate(train), l.evaluate(test)))   # libfm.cpp:418-420
+    if optimizer == "ftrl":
+        sp = l.sparsity()
+        print("sparsity\tfeatures=%d\tw_zero=%d\tv_coords=%d\tv_zero=%d\tv_zero_rows=%d\tdead_features=%d" %
+              (sp.features, sp.w_zero, sp.v_coords, sp.v_zero, sp.v_zero_rows, sp.dead_features), file=sys.stderr)
     if "rlog" in a and a["rlog"]:
         with open(a["rlog"], "w") as f:                                              # rlog.h:60-103: TSV with a header
             keys = sorted(l.log[0].keys()) if l.log else []

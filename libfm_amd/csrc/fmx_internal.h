@@ -155,6 +155,9 @@ struct SgdaState { float* gw = nullptr; float* gv = nullptr; double* reg = nullp
                    size_t dreg_cap = 0; };
 // an open fmx_adapt_* session (fmx_sgd.hip): the per-coordinate accumulators, n_v with V's row stride
 struct AdaptState { float* nw = nullptr; float* nv = nullptr; float eta = 0.f; };
+// an open fmx_ftrl_* session (fmx_sgd.hip): z and n per coordinate, the row tables with V's row stride, and the rule's constants
+struct FtrlState { float* zw = nullptr; float* zv = nullptr; float* nw = nullptr; float* nv = nullptr;
+                   float inv_alpha = 0.f, beta = 0.f, l1_w = 0.f, l1_v = 0.f, l2_w = 0.f, l2_v = 0.f; };
 
 // The parameter tables of a big model live in an ARENA: one virtual range backed by 1 GiB physical chunks (hipMemCreate) taken
 // alternately from two memory classes of the device (fmx_create)
@@ -177,6 +180,7 @@ struct fmx_context_s {
   AlsState   als;
   SgdaState  sgda;
   AdaptState adapt;
+  FtrlState  ftrl;
   LagState   lag;
   int        KP = 1;
   double     setup_acc = 0.0;    // host seconds of one-time slot preparation since the epoch entry point last cleared it
@@ -315,6 +319,7 @@ uint32_t multi_group_size(const Slot& s, int KP);                        // fmx_
 bool streams_concurrent(fmx_handle h);                                   // fmx_sgd.hip: probed once per handle
 void sgda_free(fmx_handle h);                                            // fmx_sgd.hip
 void adapt_free(fmx_handle h);                                           // fmx_sgd.hip
+void ftrl_free(fmx_handle h);                                            // fmx_sgd.hip
 void als_free(fmx_handle h);                                             // fmx_als.hip
 enum { GROUP_SINGLE = 0, GROUP_LOOPBACK = 1, GROUP_RCCL = 2 };
 struct fmx_group_s {                      // fmx_comm.hip

@@ -1,11 +1,12 @@
 // fmx_sgd.hip -- C-ABI (include/fmx.h): the SGD family -- sequential / minibatch / hogwild epochs, the split step of
 // the multi-GPU driver, the bias-lag bookkeeping, the (batch, feature) segment build, SGDA, and AdaGrad on
-// the minibatch rule (fmx_adapt_*).
+// the minibatch rule (fmx_adapt_*), FTRL-proximal with L1 on the same rule (fmx_ftrl_*) and the zero count of the tables.
 #include "fmx_internal.h"
 #include "fmx_online_kernels.h"
 #include "fmx_seq_kernels.h"
 #include "fmx_small_kernels.h"
 #include "fmx_adapt_kernels.h"
+#include "fmx_ftrl_kernels.h"
 
 namespace {
 // default micro-chunk of the bias recurrence.  The reference moves w0 after EVERY example (fm_sgd.h:34-37); summing the
@@ -1334,6 +1335,7 @@ int fmx_sgda_begin(fmx_handle h) {
   touch_w(h);
   if (!h) return FMX_E_ARG;
   if (h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_sgda_begin: an fmx_adapt session is open (call fmx_adapt_end first)");
+  if (h->ftrl.nv) return fail(h, FMX_E_STATE, "fmx_sgda_begin: an fmx_ftrl session is open (call fmx_ftrl_end first)");
   if (h->cfg.shard_world > 1) return fail(h, FMX_E_UNSUPPORTED, "SGDA on a feature shard is not implemented");
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   HIPCHK(h, hipSetDevice(h->device));
@@ -1519,6 +1521,7 @@ int fmx_adapt_begin(fmx_handle h, const fmx_adapt_opts* opts) {
   if (!(opts->learn_rate >= 0.0)) return fail(h, FMX_E_ARG, "fmx_adapt_begin: learn_rate must be >= 0 (0 = fmx_config::learn_rate)");
   int rc = adapt_check_handle(h, "fmx_adapt_begin"); if (rc) return rc;
   if (h->sgda.reg) return fail(h, FMX_E_STATE, "fmx_adapt_begin: an SGDA session is open (call fmx_sgda_end first)");
+  if (h->ftrl.nv) return fail(h, FMX_E_STATE, "fmx_adapt_begin: an fmx_ftrl session is open (call fmx_ftrl_end first)");
   const float init_acc = opts->init_acc > 0.0 ? (float)opts->init_acc : 1.0f;
   if (!(init_acc > 0.f) || std::isinf(init_acc)) return fail(h, FMX_E_ARG, "fmx_adapt_begin: init_acc %g is not a positive fp32 number", opts->init_acc);
   HIPCHK(h, hipSetDevice(h->device));
@@ -1635,6 +1638,195 @@ int fmx_adapt_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, f
     stats->w0_chunk_used = chunk;
     stats->setup_seconds = h->setup_acc;
   }
+  return FMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// FTRL-proximal with L1 on the minibatch rule (include/fmx.h "fmx_ftrl_*"; the kernels are fmx_ftrl_kernels.h)
+// ---------------------------------------------------------------------------------------------
+extern "C++" void ftrl_free(fmx_handle h) {
+  if (h->ftrl.zw) fmx_dev_free(h->ftrl.zw);
+  if (h->ftrl.zv) fmx_dev_free(h->ftrl.zv);
+  if (h->ftrl.nw) fmx_dev_free(h->ftrl.nw);
+  if (h->ftrl.nv) fmx_dev_free(h->ftrl.nv);
+  h->ftrl = FtrlState();
+}
+
+static bool ftrl_value_ok(double x) { return x >= 0.0 && !std::isinf(x); }                  // (NaN fails the comparison)
+
+int fmx_ftrl_begin(fmx_handle h, const fmx_ftrl_opts* opts) {
+  if (!h) return FMX_E_ARG;
+  if (!opts) return fail(h, FMX_E_ARG, "fmx_ftrl_begin: opts is NULL");
+  if (opts->flags != 0) return fail(h, FMX_E_ARG, "fmx_ftrl_begin: flags must be 0");
+  if (!ftrl_value_ok(opts->alpha) || !ftrl_value_ok(opts->beta) || !ftrl_value_ok(opts->l1_w) || !ftrl_value_ok(opts->l1_v) ||
+      !ftrl_value_ok(opts->l2_w) || !ftrl_value_ok(opts->l2_v) || !ftrl_value_ok(opts->init_acc))
+    return fail(h, FMX_E_ARG, "fmx_ftrl_begin: alpha, beta, l1, l2 and init_acc must be finite and >= 0");
+  if (opts->beta == 0.0 && opts->init_acc == 0.0) return fail(h, FMX_E_ARG, "fmx_ftrl_begin: beta = 0 needs init_acc > 0 (D would start at 0)");
+  const double alpha_d = opts->alpha > 0.0 ? opts->alpha : h->cfg.learn_rate;
+  const float alpha = (float)alpha_d, inv_alpha = 1.0f / alpha;
+  if (!(alpha > 0.f) || std::isinf(alpha) || std::isinf(inv_alpha))
+    return fail(h, FMX_E_ARG, "fmx_ftrl_begin: alpha %g (and its reciprocal) must be a positive fp32 number", alpha_d);
+  FtrlState f;
+  f.inv_alpha = inv_alpha; f.beta = (float)opts->beta;
+  f.l1_w = (float)opts->l1_w; f.l1_v = (float)opts->l1_v; f.l2_w = (float)opts->l2_w; f.l2_v = (float)opts->l2_v;
+  const float init_acc = (float)opts->init_acc;
+  const float base = (f.beta + sqrtf(init_acc)) * inv_alpha;
+  if (std::isinf(f.beta) || std::isinf(f.l1_w) || std::isinf(f.l1_v) || std::isinf(init_acc) || std::isinf(base + f.l2_w) || std::isinf(base + f.l2_v) ||
+      !(base + f.l2_w > 0.f) || !(base + f.l2_v > 0.f))
+    return fail(h, FMX_E_ARG, "fmx_ftrl_begin: the options leave the fp32 range ((beta + sqrt(init_acc)) / alpha + l2 = %g)", (double)(base + f.l2_v));
+  int rc = adapt_check_handle(h, "fmx_ftrl_begin"); if (rc) return rc;
+  if (h->sgda.reg) return fail(h, FMX_E_STATE, "fmx_ftrl_begin: an SGDA session is open (call fmx_sgda_end first)");
+  if (h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_ftrl_begin: an fmx_adapt session is open (call fmx_adapt_end first)");
+  { int _rc = lag_flush(h); if (_rc) return _rc; }              // (z is derived from the parameters: they have to be current)
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const size_t nv = h->n_local * (size_t)h->tb.rs, nw = h->n_local;
+  if (!h->ftrl.nv) {                                            // (again = reset: the tables are there)
+    hipError_t e = fmx_dev_alloc(&h->ftrl.zw, nw * sizeof(float));
+    if (e == hipSuccess) e = fmx_dev_alloc(&h->ftrl.nw, nw * sizeof(float));
+    if (e == hipSuccess) e = fmx_dev_alloc(&h->ftrl.zv, nv * sizeof(float));
+    if (e == hipSuccess) e = fmx_dev_alloc(&h->ftrl.nv, nv * sizeof(float));
+    if (e != hipSuccess) { ftrl_free(h); return fail(h, FMX_E_HIP, "fmx_ftrl_begin: the z and n tables (%zu bytes): %s", 2 * (nv + nw) * sizeof(float), hipGetErrorString(e)); }
+  }
+  f.zw = h->ftrl.zw; f.zv = h->ftrl.zv; f.nw = h->ftrl.nw; f.nv = h->ftrl.nv;
+  h->ftrl = f;
+  hipLaunchKernelGGL(k_ftrl_init, dim3((unsigned)std::min<size_t>((nw + 255) / 256, 2048)), dim3(256), 0, h->stream, (const float*)h->tb.w, (size_t)h->tb.ws,
+                     f.zw, f.nw, (uint64_t)nw, base + f.l2_w, f.l1_w, init_acc);
+  hipLaunchKernelGGL(k_ftrl_init, dim3((unsigned)std::min<size_t>((nv + 255) / 256, 2048)), dim3(256), 0, h->stream, (const float*)h->tb.V, (size_t)1,
+                     f.zv, f.nv, (uint64_t)nv, base + f.l2_v, f.l1_v, init_acc);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return FMX_OK;
+}
+
+int fmx_ftrl_end(fmx_handle h) {
+  if (!h) return FMX_E_ARG;
+  if (!h->ftrl.nv) return fail(h, FMX_E_STATE, "fmx_ftrl_end before fmx_ftrl_begin");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  ftrl_free(h);
+  return FMX_OK;
+}
+
+int fmx_ftrl_get_state_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double* zw, double* zv, double* nw, double* nv) {
+  if (!h) return FMX_E_ARG;
+  const int k = h->cfg.num_factor;
+  if (!ids || !zw || !nw || (k > 0 && (!zv || !nv))) return fail(h, FMX_E_ARG, "fmx_ftrl_get_state_rows: ids / zw / zv / nw / nv is NULL");
+  if (!h->ftrl.nv) return fail(h, FMX_E_STATE, "fmx_ftrl_get_state_rows before fmx_ftrl_begin");
+  for (uint32_t i = 0; i < count; i++)
+    if (ids[i] >= h->cfg.num_attribute) return fail(h, FMX_E_ARG, "feature id %u >= num_attribute", ids[i]);
+  if (count == 0) return FMX_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  uint32_t* d_ids = nullptr; double* d_out = nullptr;
+  const size_t nout = (size_t)count * (size_t)(k + 1);
+  HIPCHK(h, fmx_dev_alloc(&d_ids, (size_t)count * 4));
+  hipError_t er = fmx_dev_alloc(&d_out, nout * sizeof(double));
+  if (er == hipSuccess) er = hipMemcpyAsync(d_ids, ids, (size_t)count * 4, hipMemcpyHostToDevice, h->stream);
+  const Tab tabs[2] = {Tab{h->ftrl.zv, h->ftrl.zw, h->tb.rs, 1u}, Tab{h->ftrl.nv, h->ftrl.nw, h->tb.rs, 1u}};
+  double* const outs[2][2] = {{zw, zv}, {nw, nv}};
+  for (int t = 0; t < 2 && er == hipSuccess; t++) {             // the gather of fmx_get_param_rows over the z table, then over the n table
+    hipLaunchKernelGGL(k_fetch_rows, dim3((uint32_t)((nout + 255) / 256)), dim3(256), 0, h->stream, d_ids, count, k,
+                       make_shard(h->cfg), tabs[t], d_out, d_out + count);
+    er = hipGetLastError();
+    if (er == hipSuccess) er = hipMemcpyAsync(outs[t][0], d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (er == hipSuccess && k > 0) er = hipMemcpyAsync(outs[t][1], d_out + count, (size_t)count * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
+  }
+  fmx_dev_free(d_ids); fmx_dev_free(d_out);
+  if (er != hipSuccess) return fail(h, FMX_E_HIP, "fmx_ftrl_get_state_rows: %s", hipGetErrorString(er));
+  return FMX_OK;
+}
+
+// one epoch: fmx_adapt_epoch's three launches per batch with k_ftrl_apply_seg as the owner kernel.  The bias stays plain SGD at
+// fmx_config::learn_rate; regw / regv are not read (L2 lives in the proximal step).
+int fmx_ftrl_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
+  int rc = check_slot(h, slot, true);
+  if (rc) return rc;
+  if (!h->ftrl.nv) return fail(h, FMX_E_STATE, "fmx_ftrl_epoch before fmx_ftrl_begin");
+  rc = adapt_check_handle(h, "fmx_ftrl_epoch"); if (rc) return rc;
+  if (h->sgda.reg || h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_ftrl_epoch: an SGDA or fmx_adapt session is open");
+  rc = slot_in_session(h, slot, "fmx_ftrl_epoch"); if (rc) return rc;
+  { int _rc = lag_flush(h); if (_rc) return _rc; }
+  HIPCHK(h, hipSetDevice(h->device));
+  Slot& s = h->slots[slot];
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (s.n_rows == 0) return FMX_OK;
+  if (!s.blocks.empty()) return fail(h, FMX_E_UNSUPPORTED, "relations are not supported with SGD");   // fm_learn_sgd.h:61-63
+  h->setup_acc = 0.0; h->run_status = 0;
+  const Hyper hy = make_hyper(h->cfg);
+  fmx_batch_info bi;                                            // batch 0: exactly fmx_adapt_epoch's choice
+  rc = ensure_coll_mass(h, s); if (rc) return rc;
+  resolve_batch(h->cfg, s.coll_mass, batch, FMX_DEFAULT_BATCH, 1.0, &bi);
+  const uint32_t B = bi.batch;
+  const uint32_t chunk = w0_chunk ? w0_chunk : default_w0_chunk(h->cfg);
+  rc = ensure_segments(h, s, B); if (rc) return rc;
+  const uint32_t Bc = std::min<uint32_t>(B, s.n_rows);
+  rc = ensure_scratch(h, Bc, 0); if (rc) return rc;
+  touch_w(h);                                                   // (a side stream kept by FMX_FLAG_KEEP_WSIDE is stale from here on)
+  const FtrlState& fs = h->ftrl;
+  const Tab zt{fs.zv, fs.zw, h->tb.rs, 1u}, nt{fs.nv, fs.nw, h->tb.rs, 1u};
+  const FtrlHyper fh{fs.inv_alpha, fs.beta, fs.l1_w, fs.l1_v, fs.l2_w, fs.l2_v};
+  hipStream_t st = h->stream;
+  HIPCHK(h, hipEventRecord(h->ev0, st));
+  uint64_t batches = 0;
+  for (uint64_t row0 = 0; row0 < s.n_rows; row0 += B) {
+    const uint32_t nb = (uint32_t)std::min<uint64_t>(B, s.n_rows - row0);
+    float* S = h->partial;
+    float* rest = S + (size_t)nb * h->KP;
+    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, st, s.ent, s.row_ptr, row0, nb, h->tb, h->cfg.k1, S, rest, (const float*)nullptr));
+    rc = launch_scan(h, rest, s.target + row0, nb, chunk, hy, h->mult, st);
+    if (rc) return rc;
+    const SegWork sw = seg_work_dense(h, s, (size_t)(row0 / B), S, h->mult);
+    if (sw.nseg) {
+      KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_ftrl_apply_seg<KP, FtrlU<KP>::value>), ((uint64_t)sw.nseg + 63) / 64, st, sw, h->tb, zt, nt, hy, fh));
+    }
+    HIPCHK(h, hipGetLastError());
+    batches++;
+  }
+  HIPCHK(h, hipEventRecord(h->ev1, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  rc = scan_error_check(h); if (rc) return rc;
+  if (stats) {
+    float ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    stats->rows = s.n_rows; stats->batches = batches; stats->device_seconds = ms * 1e-3;
+    stats->main_kernel_seconds = stats->device_seconds; stats->main_kernel_launches = batches;
+    stats->max_feature_count = s.max_seg_count;
+    stats->batch_used = bi.batch; stats->collision_mass = bi.collision_mass; stats->batch_gain = bi.batch_gain;
+    stats->status = bi.status | h->run_status;
+    stats->w0_chunk_used = chunk;
+    stats->setup_seconds = h->setup_acc;
+  }
+  return FMX_OK;
+}
+
+// how many coordinates of the model are exactly zero (include/fmx.h "fmx_param_sparsity"): one pass of k_param_sparsity
+int fmx_param_sparsity(fmx_handle h, fmx_sparsity* out) {
+  if (!h) return FMX_E_ARG;
+  if (!out) return fail(h, FMX_E_ARG, "fmx_param_sparsity: out is NULL");
+  int rc = adapt_check_handle(h, "fmx_param_sparsity"); if (rc) return rc;
+  { int _rc = lag_flush(h); if (_rc) return _rc; }
+  HIPCHK(h, hipSetDevice(h->device));
+  const uint64_t n = h->cfg.num_attribute;
+  const int k = h->cfg.num_factor;
+  unsigned long long host[4] = {0ull, 0ull, 0ull, 0ull};
+  if (n) {
+    unsigned long long* d = nullptr;
+    HIPCHK(h, fmx_dev_alloc(&d, sizeof(host)));
+    hipError_t er = hipMemsetAsync(d, 0, sizeof(host), h->stream);
+    if (er == hipSuccess) {
+      const uint32_t L = (uint32_t)std::min(h->KP, 64);          // lanes per feature: a power of two
+      const uint64_t waves = (n + 64 / L - 1) / (64 / L);
+      hipLaunchKernelGGL(k_param_sparsity, dim3((unsigned)std::min<uint64_t>((waves + 3) / 4, 8192)), dim3(256), 0, h->stream, h->tb, n, k, h->cfg.k1, L, d);
+      er = hipGetLastError();
+    }
+    if (er == hipSuccess) er = hipMemcpyAsync(host, d, sizeof(host), hipMemcpyDeviceToHost, h->stream);
+    if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
+    fmx_dev_free(d);
+    if (er != hipSuccess) return fail(h, FMX_E_HIP, "fmx_param_sparsity: %s", hipGetErrorString(er));
+  }
+  out->features = n; out->w_zero = host[0]; out->v_coords = n * (uint64_t)k; out->v_zero = host[1];
+  out->v_zero_rows = host[2]; out->dead_features = host[3];
   return FMX_OK;
 }
 

@@ -161,9 +161,13 @@ class FMLearnSGD:
     fm, min_target, max_target, task, num_iter, learn_rate.  GPU-only knobs: mode ('sequential' | 'minibatch' |
     'hogwild'), batch, w0_chunk, apply ('default' | 'segmented' | 'atomic' | 'store'), device; optimizer ('sgd': the reference's one
     learn_rate for every coordinate | 'adagrad': a per-coordinate step on the minibatch rule, fmx_adapt_*, with init_acc the start
-    value of the accumulators (0 = 1.0) and adapt_learn_rate the eta of w and V (0 = learn_rate; the bias keeps learn_rate))."""
+    value of the accumulators (0 = 1.0) and adapt_learn_rate the eta of w and V (0 = learn_rate; the bias keeps learn_rate) |
+    'ftrl': FTRL-proximal with L1 on the minibatch rule, fmx_ftrl_*, which sets coordinates to exactly zero: ftrl_alpha (0 =
+    learn_rate; the bias keeps learn_rate), ftrl_beta, l1_w / l1_v, l2_w / l2_v (None = fm.regw / fm.regv).  Under 'ftrl' an l2 is ONE
+    strength per coordinate inside the proximal step, not one per occurrence as regw / regv are in the plain rule, and init_acc is the
+    start value of n as it is given (0 stays 0).  sparsity() counts the zeros of the model under any optimizer."""
 
-    OPTIMIZERS = ("sgd", "adagrad")
+    OPTIMIZERS = ("sgd", "adagrad", "ftrl")
     MODES = {"sequential": capi.SGD_SEQUENTIAL, "minibatch": capi.SGD_MINIBATCH, "hogwild": capi.SGD_HOGWILD}
     APPLY = {"default": capi.APPLY_DEFAULT, "atomic": capi.APPLY_ATOMIC, "store": capi.APPLY_STORE,
              "segmented": capi.APPLY_SEGMENTED, "fused": capi.APPLY_FUSED}
@@ -184,6 +188,10 @@ class FMLearnSGD:
         self.optimizer = "sgd"
         self.init_acc = 0.0
         self.adapt_learn_rate = 0.0
+        self.ftrl_alpha = 0.0
+        self.ftrl_beta = 1.0
+        self.l1_w, self.l1_v = 0.0, 0.0
+        self.l2_w, self.l2_v = None, None
         self.device = -1
         self.log = []                                           # one dict per iteration (rlog fields)
         self.extra_metrics = ()                                 # classification: "auc" and / or "logloss" per iteration, on stderr and in log
@@ -192,12 +200,15 @@ class FMLearnSGD:
         self._slots = {}
         self._queries = {}                                      # id(data) -> (qid, n_queries) of set_queries
         self._adapt_open = False
+        self._ftrl_open = False
 
     def _check_optimizer(self):
         if self.optimizer not in self.OPTIMIZERS:
             raise ValueError("unknown optimizer for %s: %s (%s)" % (type(self).__name__, self.optimizer, " | ".join(self.OPTIMIZERS)))
         if self.optimizer == "adagrad" and self.mode != "minibatch":
             raise ValueError("optimizer adagrad runs on the minibatch rule: mode %s is not supported" % self.mode)
+        if self.optimizer == "ftrl" and self.mode != "minibatch":
+            raise ValueError("optimizer ftrl runs on the minibatch rule: mode %s is not supported" % self.mode)
 
     # fm_learn::init (fm_learn.h:73-91): here it creates the device context and uploads the parameters
     def init(self):
@@ -213,6 +224,14 @@ class FMLearnSGD:
         if self.optimizer == "adagrad":
             self._h.adapt_begin("adagrad", self.init_acc, self.adapt_learn_rate)
             self._adapt_open = True
+        if self.optimizer == "ftrl":
+            self._h.ftrl_begin(self.ftrl_alpha, self.ftrl_beta, self.l1_w, self.l1_v, fm.regw if self.l2_w is None else self.l2_w,
+                               fm.regv if self.l2_v is None else self.l2_v, self.init_acc)
+            self._ftrl_open = True
+
+    def sparsity(self):
+        """how many coordinates of the model on the device are exactly zero (capi.Sparsity, fmx_param_sparsity)"""
+        return self._h.param_sparsity()
 
     def _slot(self, data):
         key = id(data)
@@ -243,7 +262,7 @@ class FMLearnSGD:
     # fm_learn_sgd_element::learn (fm_learn_sgd_element.h:48-78)
     def learn(self, train, test):
         self._check_optimizer()
-        if (self.optimizer == "adagrad") != self._adapt_open:
+        if (self.optimizer == "adagrad") != self._adapt_open or (self.optimizer == "ftrl") != self._ftrl_open:
             raise ValueError("optimizer was changed after init()")
         print("learnrate=%g" % self.learn_rate, file=self.out)   # fm_learn_sgd.h:57-59
         print("#iterations=%d" % self.num_iter, file=self.out)
@@ -257,6 +276,8 @@ class FMLearnSGD:
             flags |= capi.FLAG_KEEP_WSIDE                # the train set is evaluated after every epoch (fm_learn_sgd_element.h:69-70)
             if self._adapt_open:
                 stats = self._h.adapt_epoch(st, self.batch, self.w0_chunk)
+            elif self._ftrl_open:
+                stats = self._h.ftrl_epoch(st, self.batch, self.w0_chunk)
             else:
                 stats = self._h.sgd_epoch(st, self.MODES[self.mode], apply_, self.batch, self.w0_chunk, flags,
                                           self.bias_lag if apply_ == capi.APPLY_FUSED else 0)
@@ -314,6 +335,9 @@ class FMLearnSGD:
             if self._adapt_open:
                 self._h.adapt_end()
                 self._adapt_open = False
+            if self._ftrl_open:
+                self._h.ftrl_end()
+                self._ftrl_open = False
             self._h.close()
             self._h = None
 
