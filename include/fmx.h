@@ -1074,6 +1074,59 @@ typedef struct fmx_sparsity {
 } fmx_sparsity;
 int fmx_param_sparsity(fmx_handle h, fmx_sparsity *out);
 
+/* ---- a bf16 serving snapshot of the model (no counterpart in the reference) ------------------------
+ * Every scoring pass is a random gather of factor rows and is paid for in the bytes of those rows.  Training needs them in fp32 (an
+ * update adds learn_rate * g to values a thousand times larger); scoring does not.  fmx_compact_begin takes a frozen, read-only copy
+ * of the model with V rounded to bfloat16 -- half the bytes per gathered row, half the memory of a second resident model -- and the
+ * other fmx_compact_* calls score from that copy.  No other entry point reads it.  A caller detects the feature by the symbol
+ * fmx_compact_begin.
+ *
+ * Format.  bf16 is the upper half of an fp32: round to nearest, ties to even, on bit 16 -- for a bit pattern u that is not a NaN,
+ * (u + 0x7FFF + ((u >> 16) & 1)) >> 16.  +-0, +-inf and fp32 subnormals follow the same rule; a finite value above bf16's largest
+ * becomes +-inf; a NaN stays a NaN with its quiet bit set.  Scoring widens a value back with a 16-bit shift, so a score is fm_model::
+ * predict of the model (w0, w, q(V)) in the arithmetic of fmx_predict.
+ *
+ *   fmx_compact_begin       : brings the model up to date, then copies w0, w (fp32, a plain copy) and V as bf16 rows of V's row
+ *                             stride rs (2 * rs bytes each, the padding behind num_factor kept at +0):
+ *                             n_local * (2 * rs + 4) bytes stay resident until fmx_compact_end / fmx_destroy.  Called again it
+ *                             replaces the snapshot.  The model itself is never written, and nothing that happens to it afterwards
+ *                             -- epochs of any trainer, fmx_set_params, fmx_load_model -- changes what the calls below return.
+ *                             Independent of SGDA / AdaGrad / FTRL / ALS sessions: it may be taken and used while one is open.
+ *   fmx_compact_predict     : fmx_predict from the snapshot (its w0, its w, its rows).
+ *   fmx_compact_evaluate    : fmx_evaluate from the snapshot; device_seconds is filled, FMX_EVAL_WSIDE never set (the weight side
+ *                             stream describes the live w, not the snapshot's).
+ *   fmx_compact_evaluate_ex : fmx_evaluate_ex from the snapshot: the same reduction over the snapshot's scores.
+ *   fmx_compact_topk        : fmx_topk with the factor sums of both slots taken from the snapshot; the score-and-select kernels
+ *                             and every rule of the lists are fmx_topk's.
+ *   fmx_compact_get_rows    : w and the dequantised factors of `count` features in the layout of fmx_get_param_rows (w_out[count],
+ *                             v_out[count][num_factor]; v_out may be NULL only when num_factor = 0).
+ *   fmx_compact_end         : frees the snapshot.
+ * Refusals, each before any launch.  FMX_E_ARG: NULL opts, a format other than FMX_COMPACT_BF16, flags != 0, NULL outputs, an
+ * id >= num_attribute, whatever fmx_evaluate_ex / fmx_topk refuse in their own arguments.  FMX_E_STATE: any call but _begin without
+ * a snapshot; a slot never uploaded, or without targets where targets are needed.  FMX_E_UNSUPPORTED: a feature shard or
+ * communicator rank; a slot with kept `-relation` blocks.  The handle stays usable after every refusal. */
+#define FMX_COMPACT_BF16 1u
+typedef struct fmx_compact_opts {
+  uint32_t format;          /* FMX_COMPACT_BF16 */
+  uint32_t flags;           /* none defined: 0 */
+} fmx_compact_opts;
+typedef struct fmx_compact_info {
+  uint64_t features;        /* n_local */
+  uint64_t bytes_compact;   /* device bytes of the snapshot: n_local * (2 * rs + 4), rs = V's row stride in elements */
+  uint64_t bytes_params;    /* fmx_info::bytes_params, for comparison */
+  uint64_t nonfinite;       /* coordinates f < num_factor whose bf16 value is inf or NaN */
+  double   max_abs_err;     /* max |v - q(v)| over the finite q(v), f < num_factor */
+  double   sum_sq_err;      /* sum (v - q(v))^2 over the same, fp64, partial sums added in a fixed order */
+} fmx_compact_info;
+int fmx_compact_begin(fmx_handle h, const fmx_compact_opts *opts, fmx_compact_info *info /* may be NULL */);
+int fmx_compact_predict(fmx_handle h, int slot, double *out);
+int fmx_compact_evaluate(fmx_handle h, int slot, fmx_eval *out);
+int fmx_compact_evaluate_ex(fmx_handle h, int slot, const fmx_eval_opts *opts, fmx_eval_ex *out);
+int fmx_compact_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk_opts *opts, uint32_t *idx_out, double *score_out,
+                     fmx_topk_stats *stats);
+int fmx_compact_get_rows(fmx_handle h, const uint32_t *ids, uint32_t count, double *w_out, double *v_out);
+int fmx_compact_end(fmx_handle h);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 typedef struct fmx_info {
   uint64_t n_local;         /* features held by this handle */

@@ -84,6 +84,18 @@ class Sparsity(C.Structure):                       # fmx_sparsity
                 ("v_zero_rows", C.c_uint64), ("dead_features", C.c_uint64)]
 
 
+COMPACT_BF16 = 1    # FMX_COMPACT_BF16: fmx_compact_opts::format
+
+
+class CompactOpts(C.Structure):                    # fmx_compact_opts
+    _fields_ = [("format", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class CompactInfo(C.Structure):                    # fmx_compact_info
+    _fields_ = [("features", C.c_uint64), ("bytes_compact", C.c_uint64), ("bytes_params", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("max_abs_err", C.c_double), ("sum_sq_err", C.c_double)]
+
+
 class BatchInfo(C.Structure):
     _fields_ = [("collision_mass", C.c_double), ("batch_gain", C.c_double), ("batch", C.c_uint32), ("status", C.c_uint32)]
 
@@ -292,6 +304,13 @@ SYMBOLS = [
     ("fmx_ftrl_get_state_rows", C.c_int, [H, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("fmx_ftrl_end", C.c_int, [H]),
     ("fmx_param_sparsity", C.c_int, [H, C.POINTER(Sparsity)]),
+    ("fmx_compact_begin", C.c_int, [H, C.POINTER(CompactOpts), C.POINTER(CompactInfo)]),
+    ("fmx_compact_predict", C.c_int, [H, C.c_int, C.c_void_p]),
+    ("fmx_compact_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
+    ("fmx_compact_evaluate_ex", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalEx)]),
+    ("fmx_compact_topk", C.c_int, [H, C.c_int, C.c_int, C.POINTER(TopkOpts), C.c_void_p, C.c_void_p, C.POINTER(TopkStats)]),
+    ("fmx_compact_get_rows", C.c_int, [H, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("fmx_compact_end", C.c_int, [H]),
     ("fmx_als_begin", C.c_int, [H, C.c_int]),
     ("fmx_als_moments", C.c_int, [H, C.c_void_p]),
     ("fmx_als_sweep", C.c_int, [H, C.POINTER(AlsOpts), C.POINTER(AlsStats)]),
@@ -684,7 +703,7 @@ class Handle:
         return ev
 
     # top-K retrieval -------------------------------------------------------------------------
-    def topk(self, query_slot, cand_slot, topk, query_row0=0, n_query=None, exclude=None, stats=False):
+    def topk(self, query_slot, cand_slot, topk, query_row0=0, n_query=None, exclude=None, stats=False, _fn=None):
         """the topk best candidate rows of cand_slot for every query row [query_row0, query_row0 + n_query) of query_slot
         (fmx_topk): returns (idx uint32 [n, topk], score float64 [n, topk]), padded with (TOPK_NONE, -inf); with stats=True
         also the TopkStats.  exclude: None, or (ptr [n + 1], idx) -- a CSR of candidate rows per query of this call -- or a
@@ -711,7 +730,7 @@ class Handle:
         idx = np.zeros((n_query, max(topk, 0)), dtype=np.uint32)
         score = np.zeros((n_query, max(topk, 0)), dtype=np.float64)
         st = TopkStats()
-        self._chk(self.lib.fmx_topk(self.h, query_slot, cand_slot, C.byref(opts), _ptr(idx), _ptr(score), C.byref(st)))
+        self._chk((_fn or self.lib.fmx_topk)(self.h, query_slot, cand_slot, C.byref(opts), _ptr(idx), _ptr(score), C.byref(st)))
         return (idx, score, st) if stats else (idx, score)
 
     # SGDA ------------------------------------------------------------------------------------
@@ -792,6 +811,43 @@ class Handle:
         sp = Sparsity()
         self._chk(self.lib.fmx_param_sparsity(self.h, C.byref(sp)))
         return sp
+
+    # the bf16 serving snapshot (include/fmx.h "fmx_compact_*") ---------------------------------
+    def compact_begin(self, format=COMPACT_BF16, flags=0):
+        """takes (or replaces) the frozen bf16 copy of the model as it stands; returns its CompactInfo"""
+        opts, info = CompactOpts(int(format), int(flags)), CompactInfo()
+        self._chk(self.lib.fmx_compact_begin(self.h, C.byref(opts), C.byref(info)))
+        return info
+
+    def compact_predict(self, slot, n_rows):
+        out = np.zeros(n_rows, dtype=np.float64)
+        self._chk(self.lib.fmx_compact_predict(self.h, slot, _ptr(out)))
+        return out
+
+    def compact_evaluate(self, slot):
+        ev = Eval()
+        self._chk(self.lib.fmx_compact_evaluate(self.h, slot, C.byref(ev)))
+        return ev
+
+    def compact_evaluate_ex(self, slot, link=LINK_LOGISTIC):
+        opts, ev = EvalOpts(link, 0), EvalEx()
+        self._chk(self.lib.fmx_compact_evaluate_ex(self.h, slot, C.byref(opts), C.byref(ev)))
+        return ev
+
+    def compact_topk(self, query_slot, cand_slot, topk, query_row0=0, n_query=None, exclude=None, stats=False):
+        """topk() with the factor sums of both slots taken from the snapshot (fmx_compact_topk)"""
+        return self.topk(query_slot, cand_slot, topk, query_row0, n_query, exclude, stats, _fn=self.lib.fmx_compact_topk)
+
+    def compact_rows(self, ids):
+        """(w[ids], dequantised v[:, ids]) of the snapshot, in the layout of get_param_rows"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        w = np.zeros(len(ids), dtype=np.float64)
+        v = np.zeros((len(ids), max(self.k, 1)), dtype=np.float64)
+        self._chk(self.lib.fmx_compact_get_rows(self.h, _ptr(ids), len(ids), _ptr(w), _ptr(v) if self.k > 0 else None))
+        return w, v[:, :self.k].T.copy()
+
+    def compact_end(self):
+        self._chk(self.lib.fmx_compact_end(self.h))
 
     # ALS / MCMC ----------------------------------------------------------------------------
     def als_begin(self, train_slot):

@@ -38,6 +38,10 @@ default 1); the printed lines are those of sgd.  Without the option nothing chan
 rule (fmx_ftrl_epoch): A the per-coordinate rate (default -learn_rate, which stays the bias's plain rate), B default 1, W and V the L1
 strengths of the linear weights and the factors (default 0,0); the L2 strengths are -regular's regw and regv, one per coordinate.
 After training one line on stderr gives the zero counts of the model (fmx_param_sparsity).
+-serve bf16 (sgd, sgda, bpr, als): after training a frozen bf16 copy of the model is taken on the device (fmx_compact_begin) and the
+-out predictions and the -topk lists come from it.  One "compact" line on stderr carries the copy's bytes next to the fp32 tables',
+max_abs_err and nonfinite of the rounding, and the test metric -- with -metrics each named metric too -- from fp32 and from bf16 side
+by side.  Without the option stdout and stderr are byte for byte what they are.
 """
 import os
 import sys
@@ -45,6 +49,7 @@ import time
 
 import numpy as np
 
+from . import compact as C
 from . import data as D
 from . import learner as L
 from . import refrand as R
@@ -81,7 +86,8 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "init_acc": "-optimizer adagrad: start value of every accumulator (> 0); default=1",
          "ftrl_alpha": "-optimizer ftrl: per-coordinate rate of w and V (> 0); default=-learn_rate",
          "ftrl_beta": "-optimizer ftrl: beta (> 0); default=1",
-         "l1": "-optimizer ftrl: 'w,v' = L1 strength of the linear weights and of the factors (>= 0); default=0,0"}
+         "l1": "-optimizer ftrl: 'w,v' = L1 strength of the linear weights and of the factors (>= 0); default=0,0",
+         "serve": "bf16: score -out, -metrics and -topk after training from a frozen bf16 copy of the model; sgd, sgda, bpr, als"}
 
 
 def read_pairs(path, n_rows):
@@ -275,6 +281,14 @@ def _main(argv):
                 raise ValueError("-init_acc belongs to -optimizer adagrad")
             if not (0.0 < float(a["init_acc"]) < float("inf")):
                 raise ValueError("-init_acc needs a finite value > 0")
+    serve = a.get("serve")
+    if "serve" in a:
+        if serve not in C.FORMATS:
+            raise ValueError("-serve knows %s, not '%s'" % (", ".join(C.FORMATS), serve))
+        if method == "mcmc":
+            raise ValueError("-serve is not supported with -method mcmc: its prediction averages the draws, no single model scores it")
+        if a.get("relation"):
+            raise ValueError("-serve is not supported with -relation: the snapshot does not score kept blocks")
     metrics = tuple(split_list(a.get("metrics", "")))
     if "metrics" in a:
         for m in metrics:
@@ -486,6 +500,16 @@ def _main(argv):
         sp = l.sparsity()
         print("sparsity\tfeatures=%d\tw_zero=%d\tv_coords=%d\tv_zero=%d\tv_zero_rows=%d\tdead_features=%d" %
               (sp.features, sp.w_zero, sp.v_coords, sp.v_zero, sp.v_zero_rows, sp.dead_features), file=sys.stderr)
+    scorer = l                               # what -out and -topk read: the learner, or with -serve the frozen copy
+    if serve:
+        scorer = l.compact(serve)
+        ci = scorer.info
+        line = "compact\tformat=%s\tbytes=%d\tbytes_fp32=%d\tmax_abs_err=%g\tnonfinite=%d\tTest(fp32)=%g\tTest(%s)=%g" % (
+            serve, ci.bytes_compact, ci.bytes_params, ci.max_abs_err, ci.nonfinite, l.evaluate(test), serve, scorer.evaluate(test))
+        if metrics and not dev_avg:
+            ex32, ex16 = l.evaluate_ex(test), scorer.evaluate_ex(test)
+            line += "".join("\t%s(fp32)=%g\t%s(%s)=%g" % (m, getattr(ex32, m), m, serve, getattr(ex16, m)) for m in metrics)
+        print(line, file=sys.stderr)
     if "rlog" in a and a["rlog"]:
         with open(a["rlog"], "w") as f:                                              # rlog.h:60-103: TSV with a header
             keys = sorted(l.log[0].keys()) if l.log else []
@@ -493,7 +517,7 @@ def _main(argv):
             for row in l.log:
                 f.write("\t".join("%g" % row[k] for k in keys) + "\n")
     if "out" in a and a["out"]:
-        pred = l.predict_raw(test) if method == "bpr" else l.predict(test)      # bpr: raw y per test row (a score)
+        pred = scorer.predict_raw(test) if method == "bpr" else scorer.predict(test)      # bpr: raw y per test row (a score)
         with open(a["out"], "w") as f:                                               # DVector::save, matrix.h:332-342
             f.write("".join("%g\n" % p for p in pred))
     if "save_model" in a and a["save_model"]:
@@ -505,10 +529,12 @@ def _main(argv):
             cand = L.Data(*D.load(a["candidates"]))
         queries = L.Data(*D.load(a["queries"])) if a.get("queries") else test
         exclude = read_exclude(a["exclude"], queries.num_cases, cand.num_cases) if a.get("exclude") else None
-        idx, score = l.recommend(queries, cand, topk, exclude)
+        idx, score = scorer.recommend(queries, cand, topk, exclude)
         print("Top-K\tqueries=%d\tcandidates=%d\tK=%d" % (queries.num_cases, cand.num_cases, topk))
         if a.get("topk_out"):
             write_topk(a["topk_out"], idx, score)
+    if scorer is not l:
+        scorer.close()
     l.close()
     return 0
 

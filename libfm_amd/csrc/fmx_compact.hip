@@ -1,0 +1,247 @@
+// fmx_compact.hip -- C-ABI (include/fmx.h "fmx_compact_*"): a frozen bf16 copy of the model to score from.
+// fmx_compact_begin quantises V in one pass (k_compact_quant) and copies w and w0; predict / evaluate / evaluate_ex / topk are the
+// fp32 entry points' pipelines with the row sums taken from the copy (k_rowsums_c): k_yhat, k_eval, eval_ex_scores and topk_impl are
+// shared, not copied.  Kernels: fmx_compact_kernels.h.
+#include "fmx_internal.h"
+#include "fmx_compact_kernels.h"
+
+namespace {
+
+// what every entry point checks first: an unsharded handle, and (all but _begin) a snapshot
+int compact_check(fmx_handle h, const char* who, bool need_snapshot) {
+  if (h->cfg.shard_world > 1 || h->comm)
+    return fail(h, FMX_E_UNSUPPORTED, "%s: not supported on feature shards / communicator ranks", who);
+  if (need_snapshot && !h->compact.w0) return fail(h, FMX_E_STATE, "%s before fmx_compact_begin", who);
+  return FMX_OK;
+}
+
+// a slot the snapshot can score: uploaded, with targets where they are needed, without kept blocks
+int compact_check_slot(fmx_handle h, const char* who, int slot, bool need_target) {
+  if (slot < 0 || slot >= FMX_MAX_SLOTS) return fail(h, FMX_E_ARG, "%s: slot %d out of range", who, slot);
+  const Slot& s = h->slots[slot];
+  if (!s.used) return fail(h, FMX_E_STATE, "%s: slot %d holds no rows (call fmx_upload_rows first)", who, slot);
+  if (need_target && !s.target) return fail(h, FMX_E_STATE, "%s: slot %d was uploaded without targets", who, slot);
+  if (!s.blocks.empty()) return fail(h, FMX_E_UNSUPPORTED, "%s: slots with kept `-relation` blocks are not supported", who);
+  return FMX_OK;
+}
+
+CTab compact_tab(fmx_handle h, const CompactState& c) { return CTab{c.V, c.w, h->tb.rs}; }
+
+// rest[e] (= y-hat - w0) of every row of a slot from the snapshot: launch_rest's plain form
+int compact_rest(fmx_handle h, const Slot& s, float* rest, hipStream_t st) {
+  const CTab ct = compact_tab(h, h->compact);
+  KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums_c<KP, false, true>), s.n_rows, st, s.ent, s.row_ptr, (uint64_t)0, s.n_rows, ct, h->cfg.k1,
+                                     (float*)nullptr, rest));
+  HIPCHK(h, hipGetLastError());
+  return FMX_OK;
+}
+
+void compact_release(CompactState& c) {
+  fmx_dev_free(c.V); fmx_dev_free(c.w); fmx_dev_free(c.w0);
+  c = CompactState();
+}
+
+}  // namespace
+
+void compact_free(fmx_handle h) { compact_release(h->compact); }
+
+int compact_partial_rows(fmx_handle h, const CompactState& snap, const Slot& s, uint64_t row0, uint32_t n_rows, float* S, float* c, hipStream_t st) {
+  if (n_rows == 0) return FMX_OK;
+  const CTab ct = compact_tab(h, snap);
+  KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums_c<KP, true, false>), n_rows, st, s.ent, s.row_ptr, row0, n_rows, ct, h->cfg.k1, S, c));
+  HIPCHK(h, hipGetLastError());
+  return FMX_OK;
+}
+
+extern "C" {
+
+int fmx_compact_begin(fmx_handle h, const fmx_compact_opts* opts, fmx_compact_info* info) {
+  static const char who[] = "fmx_compact_begin";
+  if (!h) return FMX_E_ARG;
+  if (!opts) return fail(h, FMX_E_ARG, "%s: opts is NULL", who);
+  if (opts->format != FMX_COMPACT_BF16) return fail(h, FMX_E_ARG, "%s: unknown format %u (FMX_COMPACT_BF16)", who, opts->format);
+  if (opts->flags != 0) return fail(h, FMX_E_ARG, "%s: flags must be 0 (got %u)", who, opts->flags);
+  int rc = compact_check(h, who, false); if (rc) return rc;
+  if (h->tb.ws != 1) return fail(h, FMX_E_UNSUPPORTED, "%s: the linear weights are not an array of their own", who);
+  { int _rc = lag_flush(h); if (_rc) return _rc; }              // (the copy is of the parameters as they stand: they have to be current)
+  HIPCHK(h, hipSetDevice(h->device));
+  const uint64_t n = h->n_local;
+  const uint32_t rs = h->tb.rs;
+  const int k = h->cfg.num_factor;
+  const uint32_t L = (uint32_t)std::min(h->KP, 64);             // lanes per feature: a power of two
+  const uint64_t waves = (n + 64 / L - 1) / (64 / L);
+  const uint32_t nblk = (uint32_t)std::min<uint64_t>((waves + 3) / 4, COMPACT_BLOCKS);
+  // the new snapshot is built beside the old one, which is replaced only when everything has succeeded
+  CompactState c;
+  void* part = nullptr;                                         // [nblk][2] doubles, [nblk] counts, then 2 doubles and 1 count
+  hipError_t er = fmx_dev_alloc(&c.V, (size_t)n * rs * sizeof(uint16_t));
+  if (er == hipSuccess) er = fmx_dev_alloc(&c.w, (size_t)n * sizeof(float));
+  if (er == hipSuccess) er = fmx_dev_alloc(&c.w0, sizeof(double));
+  if (er == hipSuccess) er = fmx_dev_alloc(&part, ((size_t)nblk * 3 + 3) * 8);
+  struct { double d[2]; unsigned long long c; } res = {{0.0, 0.0}, 0ull};
+  if (er == hipSuccess) {
+    double* dpart = (double*)part;
+    unsigned long long* cpart = (unsigned long long*)part + (size_t)nblk * 2;
+    double* dres = (double*)part + (size_t)nblk * 3;
+    hipLaunchKernelGGL(k_compact_quant, dim3(nblk), dim3(256), 0, h->stream, (const float*)h->tb.V, rs, n, k, L, c.V, dpart, cpart);
+    hipLaunchKernelGGL(k_compact_final, dim3(1), dim3(64), 0, h->stream, (const double*)dpart, (const unsigned long long*)cpart, nblk,
+                       dres, (unsigned long long*)(dres + 2));
+    er = hipGetLastError();
+    if (er == hipSuccess) er = hipMemcpyAsync(c.w, h->tb.w, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
+    if (er == hipSuccess) er = hipMemcpyAsync(c.w0, h->w0, sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+    if (er == hipSuccess) er = hipMemcpyAsync(&res, dres, sizeof(res), hipMemcpyDeviceToHost, h->stream);
+  }
+  if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
+  fmx_dev_free(part);
+  if (er != hipSuccess) {
+    compact_release(c);
+    return fail(h, FMX_E_HIP, "%s: the snapshot (%zu bytes): %s", who, (size_t)n * (2 * (size_t)rs + 4), hipGetErrorString(er));
+  }
+  compact_release(h->compact);
+  h->compact = c;
+  if (info) {
+    memset(info, 0, sizeof(*info));
+    info->features = n;
+    info->bytes_compact = n * (2 * (uint64_t)rs + 4);
+    info->bytes_params = h->n_local * (size_t)(h->tb.rs + (h->w_sep ? 1 : 0)) * sizeof(float);   // fmx_get_info
+    info->nonfinite = res.c;
+    info->max_abs_err = res.d[0];
+    info->sum_sq_err = res.d[1];
+  }
+  return FMX_OK;
+}
+
+int fmx_compact_end(fmx_handle h) {
+  static const char who[] = "fmx_compact_end";
+  if (!h) return FMX_E_ARG;
+  int rc = compact_check(h, who, true); if (rc) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  compact_free(h);
+  return FMX_OK;
+}
+
+int fmx_compact_predict(fmx_handle h, int slot, double* out) {
+  static const char who[] = "fmx_compact_predict";
+  if (!h) return FMX_E_ARG;
+  if (!out) return fail(h, FMX_E_ARG, "%s: out is NULL", who);
+  int rc = compact_check(h, who, true); if (rc) return rc;
+  rc = compact_check_slot(h, who, slot, false); if (rc) return rc;
+  { int _rc = lag_flush(h); if (_rc) return _rc; }              // (the scratch below is shared with a bias-lag epoch still in flight)
+  HIPCHK(h, hipSetDevice(h->device));
+  const Slot& s = h->slots[slot];
+  if (s.n_rows == 0) return FMX_OK;
+  rc = ensure_scratch(h, 0, (size_t)s.n_rows * 2);
+  if (rc) return rc;
+  rc = compact_rest(h, s, h->rest, h->stream);
+  if (rc) return rc;
+  float* yhat = h->rest + s.n_rows;
+  hipLaunchKernelGGL(k_yhat, dim3(std::min<uint32_t>((s.n_rows + 255) / 256, 2048)), dim3(256), 0, h->stream,
+                     h->rest, s.n_rows, h->cfg.k0, h->compact.w0, yhat);
+  HIPCHK(h, hipGetLastError());
+  std::vector<float> tmp(s.n_rows);
+  HIPCHK(h, hipMemcpyAsync(tmp.data(), yhat, (size_t)s.n_rows * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (uint32_t r = 0; r < s.n_rows; r++) out[r] = (double)tmp[r];
+  return FMX_OK;
+}
+
+int fmx_compact_evaluate(fmx_handle h, int slot, fmx_eval* out) {
+  static const char who[] = "fmx_compact_evaluate";
+  if (!h) return FMX_E_ARG;
+  if (!out) return fail(h, FMX_E_ARG, "%s: out is NULL", who);
+  int rc = compact_check(h, who, true); if (rc) return rc;
+  rc = compact_check_slot(h, who, slot, true); if (rc) return rc;
+  { int _rc = lag_flush(h); if (_rc) return _rc; }              // (the scratch below is shared with a bias-lag epoch still in flight)
+  HIPCHK(h, hipSetDevice(h->device));
+  const Slot& s = h->slots[slot];
+  memset(out, 0, sizeof(*out));
+  out->rows = s.n_rows;
+  if (s.n_rows == 0) return FMX_OK;
+  rc = ensure_scratch(h, 0, (size_t)s.n_rows * 2);
+  if (rc) return rc;
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  rc = compact_rest(h, s, h->rest, h->stream);
+  if (rc) return rc;
+  HIPCHK(h, hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));
+  hipLaunchKernelGGL(k_eval, dim3(std::min<uint32_t>((s.n_rows + 255) / 256, 2048)), dim3(256), 0, h->stream,
+                     h->rest, s.target, s.n_rows, make_hyper(h->cfg), h->compact.w0, h->acc);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  double acc[4];
+  HIPCHK(h, hipMemcpyAsync(acc, h->acc, sizeof(acc), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  out->device_seconds = ms * 1e-3;
+  out->rmse = std::sqrt(acc[0] / s.n_rows);          // fm_learn.h:152
+  out->mae = acc[1] / s.n_rows;                      // fm_learn.h:148
+  out->accuracy = acc[2] / s.n_rows;                 // fm_learn.h:129
+  return FMX_OK;
+}
+
+int fmx_compact_evaluate_ex(fmx_handle h, int slot, const fmx_eval_opts* opts, fmx_eval_ex* out) {
+  static const char who[] = "fmx_compact_evaluate_ex";
+  if (!h) return FMX_E_ARG;
+  if (!out) return fail(h, FMX_E_ARG, "%s: out is NULL", who);
+  uint32_t link;
+  int rc = eval_ex_check_opts(h, who, opts, &link); if (rc) return rc;
+  rc = compact_check(h, who, true); if (rc) return rc;
+  rc = eval_ex_check_slot(h, who, slot); if (rc) return rc;
+  rc = compact_check_slot(h, who, slot, true); if (rc) return rc;
+  { int _rc = lag_flush(h); if (_rc) return _rc; }              // (the scratch below is shared with a bias-lag epoch still in flight)
+  HIPCHK(h, hipSetDevice(h->device));
+  const Slot& s = h->slots[slot];
+  eval_ex_empty(out);
+  if (s.n_rows == 0) return FMX_OK;
+  rc = ensure_scratch(h, 0, (size_t)s.n_rows * 2);
+  if (rc) return rc;
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  rc = compact_rest(h, s, h->rest, h->stream);
+  if (rc) return rc;
+  // the finished y-hat with the SNAPSHOT's bias (eval_ex_scores would add the model's): exactly what fmx_compact_predict returns
+  float* yhat = h->rest + s.n_rows;
+  hipLaunchKernelGGL(k_yhat, dim3(std::min<uint32_t>((s.n_rows + 255) / 256, 2048)), dim3(256), 0, h->stream,
+                     h->rest, s.n_rows, h->cfg.k0, h->compact.w0, yhat);
+  HIPCHK(h, hipGetLastError());
+  return eval_ex_scores(h, s, yhat, 0, link, out);
+}
+
+int fmx_compact_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk_opts* opts, uint32_t* idx_out, double* score_out,
+                     fmx_topk_stats* stats) {
+  static const char who[] = "fmx_compact_topk";
+  if (!h) return FMX_E_ARG;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  int rc = compact_check(h, who, true); if (rc) return rc;
+  return topk_impl(h, who, query_slot, cand_slot, opts, idx_out, score_out, stats, &h->compact);
+}
+
+int fmx_compact_get_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double* w_out, double* v_out) {
+  static const char who[] = "fmx_compact_get_rows";
+  if (!h) return FMX_E_ARG;
+  const int k = h->cfg.num_factor;
+  if (!ids || !w_out || (k > 0 && !v_out)) return fail(h, FMX_E_ARG, "%s: ids / w_out / v_out is NULL", who);
+  int rc = compact_check(h, who, true); if (rc) return rc;
+  for (uint32_t i = 0; i < count; i++)
+    if (ids[i] >= h->cfg.num_attribute) return fail(h, FMX_E_ARG, "%s: feature id %u >= num_attribute", who, ids[i]);
+  if (count == 0) return FMX_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  uint32_t* d_ids = nullptr; double* d_out = nullptr;
+  const size_t nout = (size_t)count * (size_t)(k + 1);
+  HIPCHK(h, fmx_dev_alloc(&d_ids, (size_t)count * 4));
+  hipError_t er = fmx_dev_alloc(&d_out, nout * sizeof(double));
+  if (er == hipSuccess) er = hipMemcpyAsync(d_ids, ids, (size_t)count * 4, hipMemcpyHostToDevice, h->stream);
+  if (er == hipSuccess) {
+    hipLaunchKernelGGL(k_fetch_rows_c, dim3((uint32_t)((nout + 255) / 256)), dim3(256), 0, h->stream, (const uint32_t*)d_ids, count, k,
+                       compact_tab(h, h->compact), d_out, d_out + count);
+    er = hipGetLastError();
+  }
+  if (er == hipSuccess) er = hipMemcpyAsync(w_out, d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+  if (er == hipSuccess && k > 0) er = hipMemcpyAsync(v_out, d_out + count, (size_t)count * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+  if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
+  fmx_dev_free(d_ids); fmx_dev_free(d_out);
+  if (er != hipSuccess) return fail(h, FMX_E_HIP, "%s: %s", who, hipGetErrorString(er));
+  return FMX_OK;
+}
+
+}  // extern "C"

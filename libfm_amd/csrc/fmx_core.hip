@@ -865,6 +865,7 @@ int fmx_destroy(fmx_handle h) {
   sgda_free(h);
   adapt_free(h);
   ftrl_free(h);
+  compact_free(h);
   for (auto& s : h->slots) free_slot(s);
   if (h->grp) fmx_dev_free(h->grp);
   if (h->arena.va) arena_free(h);                              // (both tables are parts of it)

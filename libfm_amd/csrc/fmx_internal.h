@@ -1,5 +1,5 @@
 // fmx_internal.h -- shared by the translation units of libfmx.so (fmx_core.hip, fmx_sgd.hip, fmx_als.hip, fmx_comm.hip, fmx_pair.hip, fmx_topk.hip,
-// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip; fmx_io.hip needs none of it).
+// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip; fmx_io.hip needs none of it).
 // The C-ABI is include/fmx.h; nothing declared here is exported.
 #pragma once
 #pragma GCC visibility push(default)      // the C-ABI is the only thing libfmx.so exports (-fvisibility=hidden)
@@ -158,6 +158,8 @@ struct AdaptState { float* nw = nullptr; float* nv = nullptr; float eta = 0.f; }
 // an open fmx_ftrl_* session (fmx_sgd.hip): z and n per coordinate, the row tables with V's row stride, and the rule's constants
 struct FtrlState { float* zw = nullptr; float* zv = nullptr; float* nw = nullptr; float* nv = nullptr;
                    float inv_alpha = 0.f, beta = 0.f, l1_w = 0.f, l1_v = 0.f, l2_w = 0.f, l2_v = 0.f; };
+// the bf16 serving snapshot (fmx_compact_*, fmx_compact.hip): a frozen copy of w0, w (fp32, stride 1) and V as bf16 rows of tb.rs elements
+struct CompactState { uint16_t* V = nullptr; float* w = nullptr; double* w0 = nullptr; };
 
 // The parameter tables of a big model live in an ARENA: one virtual range backed by 1 GiB physical chunks (hipMemCreate) taken
 // alternately from two memory classes of the device (fmx_create)
@@ -181,6 +183,7 @@ struct fmx_context_s {
   SgdaState  sgda;
   AdaptState adapt;
   FtrlState  ftrl;
+  CompactState compact;
   LagState   lag;
   int        KP = 1;
   double     setup_acc = 0.0;    // host seconds of one-time slot preparation since the epoch entry point last cleared it
@@ -279,8 +282,16 @@ inline bool sgd_in_stream_batch(uint32_t batch, uint32_t flags) { return batch !
 int sgd_resolve_batch(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, fmx_batch_info* bi);   // fmx_sgd.hip: + the shards' shares
 int sgd_partial_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n_rows, float* S, float* c, hipStream_t st);   // fmx_sgd.hip
 constexpr size_t PREP_RAW_FLOATS = size_t(1) << 24;                      // prep_rows: raw partial sums of one piece of rows (64 MiB)
+// fmx_topk.hip: the [rows][KM] factor sums and scalars of section 11.  snap: the rows' source -- nullptr = the model (h->tb, h->w0),
+// else the bf16 snapshot (its rows through compact_partial_rows, its w0)
 int prep_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, int k0, float* raw, size_t raw_rows, int KM,
-              float* S_out, float* scal, hipStream_t st);                // fmx_topk.hip: the [rows][KM] factor sums and scalars of section 11
+              float* S_out, float* scal, hipStream_t st, const CompactState* snap = nullptr);
+// fmx_topk.hip: fmx_topk after the handle check, for fmx_compact_topk too (`who` names the entry point in messages; snap as above)
+int topk_impl(fmx_handle h, const char* who, int query_slot, int cand_slot, const fmx_topk_opts* opts, uint32_t* idx_out, double* score_out,
+              fmx_topk_stats* stats, const CompactState* snap);
+// fmx_compact.hip: sgd_partial_rows from the snapshot (k_rowsums_c<KP, true, false>), and the snapshot's release
+int compact_partial_rows(fmx_handle h, const CompactState& snap, const Slot& s, uint64_t row0, uint32_t n_rows, float* S, float* c, hipStream_t st);
+void compact_free(fmx_handle h);
 int lag_flush(fmx_handle h);                                             // fmx_sgd.hip
 // fmx_eval.hip: the argument checks, the empty result and the reduction of fmx_evaluate_ex, shared with fmx_group_evaluate_ex (fmx_comm.hip)
 int eval_ex_check_opts(fmx_handle h, const char* who, const fmx_eval_opts* opts, uint32_t* link);

@@ -32,46 +32,43 @@ size_t score_lds_bytes(int buf) {
 // factor sums of rows [row0, row0 + n) of a slot -> S_out [n][KM] (zero-padded), scal[n] = (k0 w0) + c + 1/2 |S|^2; raw: scratch of
 // raw_rows * (KP + 1) floats (fmx_internal.h: shared with the hardest-of-M sampler of fmx_pairneg.hip)
 int prep_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, int k0, float* raw, size_t raw_rows, int KM,
-              float* S_out, float* scal, hipStream_t st) {
+              float* S_out, float* scal, hipStream_t st, const CompactState* snap) {
   const int KP = h->KP;
   for (uint32_t r = 0; r < n; r += (uint32_t)raw_rows) {
     const uint32_t nr = (uint32_t)std::min<uint64_t>(raw_rows, n - r);
     float* S = raw;
     float* c = raw + (size_t)nr * KP;
-    int rc = sgd_partial_rows(h, s, row0 + r, nr, S, c, st);
+    int rc = snap ? compact_partial_rows(h, *snap, s, row0 + r, nr, S, c, st) : sgd_partial_rows(h, s, row0 + r, nr, S, c, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_topk_prep, dim3(wave_grid(nr)), dim3(256), 0, st, (const float*)S, (const float*)c, nr, KP,
-                       h->cfg.num_factor, KM, k0, (const double*)h->w0, S_out + (size_t)r * KM, scal + r);
+                       h->cfg.num_factor, KM, k0, (const double*)(snap ? snap->w0 : h->w0), S_out + (size_t)r * KM, scal + r);
     HIPCHK(h, hipGetLastError());
   }
   return FMX_OK;
 }
 
-extern "C" {
-
-int fmx_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk_opts* opts, uint32_t* idx_out, double* score_out,
-             fmx_topk_stats* stats) {
-  if (!h) return FMX_E_ARG;
+int topk_impl(fmx_handle h, const char* who, int query_slot, int cand_slot, const fmx_topk_opts* opts, uint32_t* idx_out, double* score_out,
+              fmx_topk_stats* stats, const CompactState* snap) {
   if (stats) memset(stats, 0, sizeof(*stats));
   int rc = check_slot(h, query_slot, false);
   if (rc) return rc;
   rc = check_slot(h, cand_slot, false);
   if (rc) return rc;
   if (h->cfg.shard_world > 1 || h->comm)
-    return fail(h, FMX_E_UNSUPPORTED, "fmx_topk: not supported on feature shards / communicator ranks");
+    return fail(h, FMX_E_UNSUPPORTED, "%s: not supported on feature shards / communicator ranks", who);
   const Slot& qs = h->slots[query_slot];
   const Slot& cs = h->slots[cand_slot];
   if (!qs.blocks.empty() || !cs.blocks.empty())
-    return fail(h, FMX_E_UNSUPPORTED, "fmx_topk: slots with kept `-relation` blocks are not supported");
-  if (!opts) return fail(h, FMX_E_ARG, "fmx_topk: opts is NULL");
-  if (!idx_out || !score_out) return fail(h, FMX_E_ARG, "fmx_topk: idx_out / score_out is NULL");
+    return fail(h, FMX_E_UNSUPPORTED, "%s: slots with kept `-relation` blocks are not supported", who);
+  if (!opts) return fail(h, FMX_E_ARG, "%s: opts is NULL", who);
+  if (!idx_out || !score_out) return fail(h, FMX_E_ARG, "%s: idx_out / score_out is NULL", who);
   const uint32_t K = opts->topk;
-  if (K == 0 || K > FMX_TOPK_MAX) return fail(h, FMX_E_ARG, "fmx_topk: topk = %u (1 .. %u)", K, FMX_TOPK_MAX);
-  if (opts->flags != 0) return fail(h, FMX_E_ARG, "fmx_topk: unknown flags 0x%x", opts->flags);
+  if (K == 0 || K > FMX_TOPK_MAX) return fail(h, FMX_E_ARG, "%s: topk = %u (1 .. %u)", who, K, FMX_TOPK_MAX);
+  if (opts->flags != 0) return fail(h, FMX_E_ARG, "%s: unknown flags 0x%x", who, opts->flags);
   const uint64_t row0 = opts->query_row0;
   const uint32_t NQ = opts->n_query;
   if (row0 > qs.n_rows || NQ > qs.n_rows - row0)
-    return fail(h, FMX_E_ARG, "fmx_topk: query rows [%llu,+%u) outside the slot (%u rows)", (unsigned long long)row0, NQ, qs.n_rows);
+    return fail(h, FMX_E_ARG, "%s: query rows [%llu,+%u) outside the slot (%u rows)", who, (unsigned long long)row0, NQ, qs.n_rows);
   const uint32_t NC = cs.n_rows;
   // exclusion lists: validated (nothing is written on a bad index), then sorted and made unique per query
   std::vector<uint64_t> ex_ptr;
@@ -79,11 +76,11 @@ int fmx_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk_opts* o
   if (opts->exclude_ptr) {
     const uint64_t* p = opts->exclude_ptr;
     for (uint32_t i = 0; i < NQ; i++)
-      if (p[i + 1] < p[i]) return fail(h, FMX_E_ARG, "fmx_topk: exclude_ptr decreases at query %u", i);
-    if (p[NQ] > p[0] && !opts->exclude_idx) return fail(h, FMX_E_ARG, "fmx_topk: exclude_idx is NULL");
+      if (p[i + 1] < p[i]) return fail(h, FMX_E_ARG, "%s: exclude_ptr decreases at query %u", who, i);
+    if (p[NQ] > p[0] && !opts->exclude_idx) return fail(h, FMX_E_ARG, "%s: exclude_idx is NULL", who);
     for (uint64_t t = p[0]; t < p[NQ]; t++)
       if (opts->exclude_idx[t] >= NC)
-        return fail(h, FMX_E_ARG, "fmx_topk: excluded candidate %u >= %u candidate rows", opts->exclude_idx[t], NC);
+        return fail(h, FMX_E_ARG, "%s: excluded candidate %u >= %u candidate rows", who, opts->exclude_idx[t], NC);
     ex_ptr.resize((size_t)NQ + 1);
     ex_ptr[0] = 0;
     ex_idx.reserve(p[NQ] - p[0]);
@@ -151,7 +148,7 @@ int fmx_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk_opts* o
   HIPCHK(h, hipEventRecord(ev.e[0], st));
   HIPCHK(h, hipMemsetAsync(Sc + (size_t)NC * KM, 0, (size_t)(C_pad - NC) * KM * sizeof(float), st));
   HIPCHK(h, hipMemsetAsync(bc + NC, 0, (size_t)(C_pad - NC) * sizeof(float), st));
-  rc = prep_rows(h, cs, 0, NC, 0, raw, raw_rows, KM, Sc, bc, st);
+  rc = prep_rows(h, cs, 0, NC, 0, raw, raw_rows, KM, Sc, bc, st, snap);
   if (rc) return rc;
 
   // the score kernel of this (KM, BUF)
@@ -174,7 +171,7 @@ int fmx_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk_opts* o
     const uint32_t qblocks = (nqc + TOPK_QB - 1) / TOPK_QB;
     HIPCHK(h, hipMemsetAsync(Sq, 0, (size_t)nq_pad * KM * sizeof(float), st));
     HIPCHK(h, hipMemsetAsync(aq, 0, (size_t)nq_pad * sizeof(float), st));
-    rc = prep_rows(h, qs, row0 + qoff, nqc, h->cfg.k0, raw, raw_rows, KM, Sq, aq, st);
+    rc = prep_rows(h, qs, row0 + qoff, nqc, h->cfg.k0, raw, raw_rows, KM, Sq, aq, st, snap);
     if (rc) return rc;
     HIPCHK(h, hipEventRecord(ev.e[2], st));
     const uint64_t* xp = d_ex_ptr ? d_ex_ptr + qoff : nullptr;
@@ -214,6 +211,14 @@ int fmx_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk_opts* o
   HIPCHK(h, hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
   if (stats) { stats->device_seconds = ms * 1e-3; stats->score_seconds = score_s; }
   return FMX_OK;
+}
+
+extern "C" {
+
+int fmx_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk_opts* opts, uint32_t* idx_out, double* score_out,
+             fmx_topk_stats* stats) {
+  if (!h) return FMX_E_ARG;
+  return topk_impl(h, "fmx_topk", query_slot, cand_slot, opts, idx_out, score_out, stats, nullptr);
 }
 
 }  // extern "C"

@@ -15,7 +15,7 @@ import sys
 
 import numpy as np
 
-from . import capi, evalmetrics
+from . import capi, compact as compact_format, evalmetrics
 
 TASK_REGRESSION = capi.TASK_REGRESSION        # fm_learn.h:46
 TASK_CLASSIFICATION = capi.TASK_CLASSIFICATION  # fm_learn.h:47
@@ -152,6 +152,42 @@ def _check_queries(data, qid):
     if len(q) != data.num_cases:
         raise ValueError("set_queries: %d query ids for %d rows" % (len(q), data.num_cases))
     return q
+
+
+class CompactView:
+    """A frozen bf16 copy of a learner's model on the device (fmx_compact_*), scored like the learner itself: predict, evaluate,
+    evaluate_ex and recommend mirror the learner's methods, link and clamping included, and read the copy, so training the
+    learner further does not change what they return.  `info` is the capi.CompactInfo of the copy (bytes, max_abs_err,
+    nonfinite).  A handle holds one copy: learner.compact() again replaces it under every earlier view; close() frees it."""
+
+    def __init__(self, learner, format):
+        if format not in compact_format.FORMATS:
+            raise ValueError("unknown serving format %r (%s)" % (format, " | ".join(compact_format.FORMATS)))
+        self._l = learner
+        self.format = format
+        self.info = learner._h.compact_begin(compact_format.FORMATS[format])
+
+    def predict_raw(self, data):
+        return self._l._h.compact_predict(self._l._compact_slot(data), data.num_cases)
+
+    def predict(self, data):
+        return self._l._link(self.predict_raw(data))
+
+    def evaluate(self, data):
+        ev = self._l._h.compact_evaluate(self._l._compact_slot(data))
+        return ev.rmse if self._l.task == TASK_REGRESSION else ev.accuracy
+
+    def evaluate_ex(self, data):
+        return self._l._h.compact_evaluate_ex(self._l._compact_slot(data), self._l.EVAL_LINK)
+
+    def recommend(self, queries, candidates, topk, exclude=None):
+        qs, cs = self._l._topk_slots(queries, candidates)
+        return self._l._h.compact_topk(qs, cs, topk, 0, queries.num_cases, exclude)
+
+    def close(self):
+        if self._l is not None and self._l._h is not None:
+            self._l._h.compact_end()
+        self._l = None
 
 
 class FMLearnSGD:
@@ -316,11 +352,22 @@ class FMLearnSGD:
         prediction of the joined row queries[q] ++ candidates[c], without ever writing it out.  Returns (idx uint32
         [queries, topk], score float64 [queries, topk]), padded with (capi.TOPK_NONE, -inf).  exclude: per query, the candidate
         rows it must not get back (a list of iterables, or a CSR (ptr, idx))."""
-        return self._h.topk(self._slot(queries), self._slot(candidates), topk, 0, queries.num_cases, exclude)
+        return self._h.topk(*self._topk_slots(queries, candidates), topk, 0, queries.num_cases, exclude)
+
+    def _topk_slots(self, queries, candidates):
+        return self._slot(queries), self._slot(candidates)
+
+    _compact_slot = _slot
+
+    def compact(self, format="bf16"):
+        """a CompactView: a frozen reduced-precision copy of the model as it stands, to score from (fmx_compact_begin)"""
+        return CompactView(self, format)
 
     # fm_learn_sgd::predict (fm_learn_sgd.h:76-90)
     def predict(self, data):
-        p = self.predict_raw(data)
+        return self._link(self.predict_raw(data))
+
+    def _link(self, p):
         if self.task == TASK_REGRESSION:
             p = np.minimum(self.max_target, p)
             p = np.maximum(self.min_target, p)
@@ -523,13 +570,42 @@ class FMLearnALS:
         if len(self._shards) > 1:
             raise NotImplementedError("recommend: top-K retrieval is not supported on feature shards (devices lists %d GPUs)"
                                       % len(self._shards))
+        return self._h.topk(*self._topk_slots(queries, candidates), topk, 0, queries.num_cases, exclude)
+
+    def _topk_slots(self, queries, candidates):
         qs, cs = self.TOPK_SLOTS
         queries.upload(self._h, qs)
         if candidates is queries:
             cs = qs
         else:
             candidates.upload(self._h, cs)
-        return self._h.topk(qs, cs, topk, 0, queries.num_cases, exclude)
+        return qs, cs
+
+    EVAL_LINK = capi.LINK_PROBIT    # this learner's probability is cdf_gaussian(y-hat)
+
+    def evaluate(self, data):
+        """rmse (regression) or accuracy of the train or test set of learn() under the parameters of the last sweep (fmx_evaluate)"""
+        ev = self._h.evaluate(self._compact_slot(data))
+        return ev.rmse if self.task == TASK_REGRESSION else ev.accuracy
+
+    def _compact_slot(self, data):
+        if data is not self._train and data is not self._test:
+            raise ValueError("compact: the data set is neither the train nor the test set of learn()")
+        return 0 if data is self._train else 1
+
+    def _link(self, p):
+        """one parameter set's prediction as fm_learn_mcmc::predict clamps it (fm_learn_mcmc.h:380-404)"""
+        if self.task == TASK_REGRESSION:
+            return np.maximum(self.min_target, np.minimum(self.max_target, p))
+        return np.maximum(0.0, np.minimum(1.0, cdf_gaussian(p)))
+
+    def compact(self, format="bf16"):
+        """a CompactView of the parameters of the last sweep (fmx_compact_begin); its data sets are the train and test set of
+        learn().  Not on feature shards."""
+        if len(self._shards) > 1:
+            raise NotImplementedError("compact: the serving snapshot is not supported on feature shards (devices lists %d GPUs)"
+                                      % len(self._shards))
+        return CompactView(self, format)
 
     # fm_learn_mcmc::predict (fm_learn_mcmc.h:380-404)
     def predict(self, data):
@@ -559,6 +635,10 @@ class FMLearnMCMC(FMLearnALS):
     def recommend(self, queries, candidates, topk, exclude=None):
         raise NotImplementedError("recommend: the MCMC prediction is the average over the draws (pred_sum_all / num_iter); "
                                   "no single parameter set scores it")
+
+    def compact(self, format="bf16"):
+        raise NotImplementedError("compact: the MCMC prediction is the average over the draws (pred_sum_all / num_iter); "
+                                  "a snapshot of one parameter set does not score it")
 
     def __init__(self):
         super().__init__()
