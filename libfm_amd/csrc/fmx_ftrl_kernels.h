@@ -10,14 +10,12 @@
 // in fp32, with the correctly rounded division and square root hipcc emits by default (no rsqrt).  theta is READ, not reconstructed
 // from (z, n): fmx_set_params may have moved it.  A coordinate whose theta, z and g are 0 (the padding of a row) stays +0.
 //
-// Shape: adapt_seg_block's (a wavefront owns 64 consecutive dense segments; U segment groups per round, each group's V row, z row, n row,
-// w_j, z_w[j], n_w[j] and first S row requested together before anything is used; further occurrences added in occurrence order by the
-// same two tail schemes; cross-lane reads outside the idx < cnt guard).  The gradient accumulation is a second copy of
-// adapt_seg_block's, not a shared inline: k_adapt_apply_seg stays textually what it was, so its resource table cannot move.  z and n
-// have V's row stride (Tabs `zt`, `nt`: .V the rows, .w the linear weights' array, .rs = tb.rs, .ws = 1), so row_ld / row_st mask the
-// lanes beyond a row for all three tables.  No atomics, no LDS: one owner per segment, two runs are bit-identical.
+// Shape: the owner block is stateful_seg_block (fmx_adapt_kernels.h) with FtrlRule below: the rule carries two state tables, z then n,
+// as Tabs with V's row stride, keeps L2 out of the gradient, and steps a factor with (l1_v, l2_v) and a linear weight with (l1_w, l2_w).
+// Everything that decides the bits of the gradient sum -- the round structure, the first-occurrence seed, the occurrence tail (seg_tail,
+// fmx_kernels.h) -- is the code AdaGrad and the plain rule run.  No atomics, no LDS: one owner per segment, two runs are bit-identical.
 #pragma once
-#include "fmx_kernels.h"
+#include "fmx_adapt_kernels.h"
 
 namespace fmx {
 
@@ -38,141 +36,25 @@ __device__ __forceinline__ float ftrl_step(float theta, float z, float n, float 
   return (fabsf(zz) <= l1) ? 0.f : -(zz - copysignf(l1, zz)) / D;
 }
 
-template <int KP, int U>
-__device__ __forceinline__ void ftrl_seg_block(const SegWork& sw, uint32_t blk, const Tab tb, const Tab zt, const Tab nt, const Hyper& h,
-                                               const FtrlHyper& fh) {
-  constexpr int VEC = Map<KP>::VEC, LPR = Map<KP>::LPR, EPI = Map<KP>::EPI;
-  const uint32_t lane = threadIdx.x & 63u, g = lane / LPR, f = lane % LPR;
-  const TEntry* __restrict__ t_ent = sw.t_ent;
-  const float* __restrict__ S = sw.S;
-  const float* __restrict__ mult = sw.mult;
-  const uint32_t cnt = min(64u, sw.nseg - blk);
-  uint32_t jl = 0, al = 0, bl = 0, el = 0; float xl = 0.f, ml = 0.f;
-  if (lane < cnt) {
-    const uint32_t s = blk + lane;
-    jl = sw.seg_feat[s];
-    al = sw.seg_rel[s];
-    bl = (s + 1 < sw.nseg_batch) ? sw.seg_rel[s + 1] : sw.batch_nnz;
-    const TEntry te = load_stream8(t_ent + al);
-    el = te.e; xl = te.x;
-    ml = mult[el];
+// FTRL-proximal: two tables (z, then n), no L2 in the gradient (it lives in the proximal step), l1 / l2 per parameter kind
+struct FtrlRule {
+  static constexpr int NT = 2;
+  static constexpr bool REG = false;
+  Tab st[NT]; FtrlHyper fh;
+  __device__ __forceinline__ float step_v(float g, float theta, float (&s)[NT]) const {
+    return ftrl_step(theta, s[0], s[1], g, fh.inv_alpha, fh.beta, fh.l1_v, fh.l2_v, s[0], s[1]);
   }
-  for (uint32_t i = 0; i < cnt; i += EPI * U) {
-    float v0[U][VEC], z0[U][VEC], n0[U][VEC], sf[U][VEC];
-    float wv0[U], zw0[U], nw0[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const uint32_t idx = i + u * EPI + g;
-      const uint32_t j = bcast_u32<EPI>(jl, idx & 63u);
-      const uint32_t e = bcast_u32<EPI>(el, idx & 63u);
-      wv0[u] = 0.f; zw0[u] = 0.f; nw0[u] = 0.f;
-      if (idx < cnt) {
-        if (h.k1 && f == 0) { wv0[u] = tb.w[(size_t)j * tb.ws]; zw0[u] = zt.w[j]; nw0[u] = nt.w[j]; }
-        row_ld<VEC, 8>(tb, (size_t)j, f * VEC, v0[u]);
-        row_ld<VEC, 8>(zt, (size_t)j, f * VEC, z0[u]);
-        row_ld<VEC, 8>(nt, (size_t)j, f * VEC, n0[u]);
-        load_vec<VEC>(S + (size_t)e * KP + f * VEC, sf[u]);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const uint32_t idx = i + u * EPI + g;
-      const uint32_t j = bcast_u32<EPI>(jl, idx & 63u);
-      const uint32_t a = bcast_u32<EPI>(al, idx & 63u);
-      const uint32_t b = bcast_u32<EPI>(bl, idx & 63u);
-      const float x = bcast_f32<EPI>(xl, idx & 63u);               // (cross-lane reads run with every lane enabled: outside the guard)
-      const float m = bcast_f32<EPI>(ml, idx & 63u);
-      if (idx < cnt) {
-        float G[VEC]; float A, Gw;
-        const float mx = m * x;
-#pragma unroll
-        for (int v = 0; v < VEC; v++) G[v] = mx * sf[u][v];
-        A = mx * x; Gw = mx;
-        uint32_t i2 = a + 1;
-        // further occurrences, added in occurrence order (adapt_seg_block's two tail schemes, copied: see the head of this file)
-        if constexpr (EPI == 1) {
-          // one row per wave-wide load: 64 descriptors and their multipliers lane-parallel, the S rows TL at a time, broadcast by v_readlane
-          constexpr int TL = (VEC == 1) ? 16 : 8;
-          for (uint32_t base = i2; base < b; base += 64) {
-            const uint32_t cc = min(64u, b - base);
-            TEntry te; te.e = 0; te.x = 0.f; float tm = 0.f;
-            if (lane < cc) { te = load_stream8(t_ent + base + lane); tm = mult[te.e]; }
-            for (uint32_t q0 = 0; q0 < cc; q0 += TL) {
-              float s2[TL][VEC];
-#pragma unroll
-              for (int q = 0; q < TL; q++) {
-                const uint32_t e2 = bcast_u32<1>(te.e, (q0 + q) & 63u);
-                if (q0 + q < cc) load_vec<VEC>(S + (size_t)e2 * KP + f * VEC, s2[q]);
-                else {
-#pragma unroll
-                  for (int v = 0; v < VEC; v++) s2[q][v] = 0.f;
-                }
-              }
-#pragma unroll
-              for (int q = 0; q < TL; q++) {
-                const float x2 = bcast_f32<1>(te.x, (q0 + q) & 63u), m2 = bcast_f32<1>(tm, (q0 + q) & 63u);
-                if (q0 + q < cc) {
-                  const float mx2 = m2 * x2;
-#pragma unroll
-                  for (int v = 0; v < VEC; v++) G[v] = fmaf(mx2, s2[q][v], G[v]);
-                  A = fmaf(mx2, x2, A); Gw += mx2;
-                }
-              }
-            }
-          }
-        } else {
-          // several rows per wave-wide load (KP < 64): every lane group walks its own segment, TL occurrences at a time
-          constexpr int TL = 8;
-          for (; i2 < b; i2 += TL) {
-            TEntry tt[TL]; float mm[TL]; float s2[TL][VEC];
-#pragma unroll
-            for (int q = 0; q < TL; q++) { tt[q].e = 0; tt[q].x = 0.f; if (i2 + q < b) tt[q] = t_ent[i2 + q]; }
-#pragma unroll
-            for (int q = 0; q < TL; q++) {
-              mm[q] = 0.f;
-              if (i2 + q < b) { mm[q] = mult[tt[q].e]; load_vec<VEC>(S + (size_t)tt[q].e * KP + f * VEC, s2[q]); }
-              else {
-#pragma unroll
-                for (int v = 0; v < VEC; v++) s2[q][v] = 0.f;
-              }
-            }
-#pragma unroll
-            for (int q = 0; q < TL; q++) {
-              if (i2 + q < b) {
-                const float mx2 = mm[q] * tt[q].x;
-#pragma unroll
-                for (int v = 0; v < VEC; v++) G[v] = fmaf(mx2, s2[q][v], G[v]);
-                A = fmaf(mx2, tt[q].x, A); Gw += mx2;
-              }
-            }
-          }
-        }
-        float nv[VEC], zz[VEC], nn[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; v++) {
-          const float vv = v0[u][v];
-          nv[v] = ftrl_step(vv, z0[u][v], n0[u][v], G[v] - vv * A, fh.inv_alpha, fh.beta, fh.l1_v, fh.l2_v, zz[v], nn[v]);
-        }
-        row_st<VEC, 8>(tb, (size_t)j, f * VEC, nv);
-        row_st<VEC, 8>(zt, (size_t)j, f * VEC, zz);
-        row_st<VEC, 8>(nt, (size_t)j, f * VEC, nn);
-        if (h.k1 && f == 0) {
-          float zw, nw;
-          tb.w[(size_t)j * tb.ws] = ftrl_step(wv0[u], zw0[u], nw0[u], Gw, fh.inv_alpha, fh.beta, fh.l1_w, fh.l2_w, zw, nw);
-          zt.w[j] = zw;
-          nt.w[j] = nw;
-        }
-      }
-    }
+  __device__ __forceinline__ float step_w(float g, float theta, float (&s)[NT]) const {
+    return ftrl_step(theta, s[0], s[1], g, fh.inv_alpha, fh.beta, fh.l1_w, fh.l2_w, s[0], s[1]);
   }
-}
+};
 
 template <int KP, int U>
 __global__ void __launch_bounds__(256)
-k_ftrl_apply_seg(const SegWork sw, const Tab tb, const Tab zt, const Tab nt, Hyper h, FtrlHyper fh) {
+k_ftrl_apply_seg(const SegWork sw, const Tab tb, const FtrlRule rule, Hyper h) {
   const uint32_t wave0 = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
   const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
-  for (uint32_t blk = wave0 * 64u; blk < sw.nseg; blk += nwaves * 64u) ftrl_seg_block<KP, U>(sw, blk, tb, zt, nt, h, fh);
+  for (uint32_t blk = wave0 * 64u; blk < sw.nseg; blk += nwaves * 64u) stateful_seg_block<FtrlRule, KP, U>(sw, blk, tb, rule, h);
 }
 
 // the start state (fmx_ftrl_begin): n = init_acc and z0 = -theta0 D0 - sgn(theta0) l1 with D0 = (beta + sqrt(init_acc)) / alpha + l2, the z

@@ -1603,6 +1603,83 @@ struct SegWork {
   const CDesc* cdesc;      // with seg_idx: the listed segments as 32-byte records incl. their first two occurrences (nullptr: look them up)
   unsigned long long* done_ctr; unsigned long long done_val;   // device hand-off: "everything before this launch on its stream has completed"
 };
+
+// The occurrence tail of a segment's gradient walk, once for every owner block (apply_seg_block below, stateful_seg_block in
+// fmx_adapt_kernels.h): occurrences [i2, b) of the segment are added into G (the sums of mult x S_f), A (of mult x x) and Gw (of mult x)
+// in occurrence order -- the order that makes two runs, and the device and its restatements, agree bit for bit.
+// PRE: the caller has already asked for the first 64 descriptors and their multipliers (te_pre, tm_pre: lane-parallel from i2; the
+// one-segment-per-wavefront path of apply_seg_block), so the first wave-wide load is not issued again.
+template <int KP, bool PRE = false>
+__device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const float* __restrict__ S, const float* __restrict__ mult,
+                                         uint32_t i2, const uint32_t b, const uint32_t lane, const uint32_t f,
+                                         float (&G)[Map<KP>::VEC], float& A, float& Gw, const TEntry te_pre = TEntry{0u, 0.f}, const float tm_pre = 0.f) {
+  constexpr int VEC = Map<KP>::VEC, EPI = Map<KP>::EPI;
+  // further occurrences of the feature in this batch (a frequent feature of Criteo-shaped rows has dozens to thousands per
+  // batch).  Added in occurrence order, so the result does not depend on how they are fetched:
+  if constexpr (EPI == 1) {
+    // one row per wave-wide load: the whole wavefront is here together.  64 descriptors and their multipliers arrive
+    // lane-parallel (one coalesced load + one gather), then the S rows TL at a time with the descriptors broadcast by
+    // v_readlane -- per TL occurrences ONE dependent round trip instead of three per occurrence.
+    // (32 rows per round for the one-segment-per-wavefront path was measured in round 4: k_apply_seg_scan 7.6 -> 8.1 us per
+    //  512-row batch of Criteo-shaped rows -- most segments there hold ~8 occurrences and pay for the longer unrolled round)
+    constexpr int TL = (VEC == 1) ? 16 : 8;
+    for (uint32_t base = i2; base < b; base += 64) {
+      const uint32_t cc = min(64u, b - base);
+      TEntry te; te.e = 0; te.x = 0.f; float tm = 0.f;
+      if (PRE && base == i2) { te = te_pre; tm = tm_pre; }          // (asked for with the descriptor, by the caller)
+      else if (lane < cc) { te = load_stream8(t_ent + base + lane); tm = mult[te.e]; }
+      for (uint32_t q0 = 0; q0 < cc; q0 += TL) {
+        float s2[TL][VEC];
+#pragma unroll
+        for (int q = 0; q < TL; q++) {
+          const uint32_t e2 = bcast_u32<1>(te.e, (q0 + q) & 63u);
+          if (q0 + q < cc) load_vec<VEC>(S + (size_t)e2 * KP + f * VEC, s2[q]);
+          else {
+#pragma unroll
+            for (int v = 0; v < VEC; v++) s2[q][v] = 0.f;
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < TL; q++) {
+          const float x2 = bcast_f32<1>(te.x, (q0 + q) & 63u), m2 = bcast_f32<1>(tm, (q0 + q) & 63u);
+          if (q0 + q < cc) {
+            const float mx2 = m2 * x2;
+#pragma unroll
+            for (int v = 0; v < VEC; v++) G[v] = fmaf(mx2, s2[q][v], G[v]);
+            A = fmaf(mx2, x2, A); Gw += mx2;
+          }
+        }
+      }
+    }
+  } else {
+    // several rows per wave-wide load (KP < 64): every lane group walks its own segment, TL occurrences at a time
+    constexpr int TL = 8;
+    for (; i2 < b; i2 += TL) {
+      TEntry tt[TL]; float mm[TL]; float s2[TL][VEC];
+#pragma unroll
+      for (int q = 0; q < TL; q++) { tt[q].e = 0; tt[q].x = 0.f; if (i2 + q < b) tt[q] = t_ent[i2 + q]; }
+#pragma unroll
+      for (int q = 0; q < TL; q++) {
+        mm[q] = 0.f;
+        if (i2 + q < b) { mm[q] = mult[tt[q].e]; load_vec<VEC>(S + (size_t)tt[q].e * KP + f * VEC, s2[q]); }
+        else {
+#pragma unroll
+          for (int v = 0; v < VEC; v++) s2[q][v] = 0.f;
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < TL; q++) {
+        if (i2 + q < b) {
+          const float mx2 = mm[q] * tt[q].x;
+#pragma unroll
+          for (int v = 0; v < VEC; v++) G[v] = fmaf(mx2, s2[q][v], G[v]);
+          A = fmaf(mx2, tt[q].x, A); Gw += mx2;
+        }
+      }
+    }
+  }
+}
+
 // SPW = segments per wavefront-block (<= 64).  64 for the dense form (millions of segments: plenty of wavefronts); 16 for
 // the short list of deferred features (a few 100 000): with 64 the pass ran on ~5 000 wavefronts, each a serial chain of
 // eight dependent gather rounds -- 166 us for 350 MB (2 TB/s, latency-bound) -- four times as many shorter chains fill the chip.
@@ -1693,70 +1770,7 @@ __device__ __forceinline__ void apply_seg_block(const SegWork& sw, uint32_t blk,
           for (int v = 0; v < VEC; v++) G[v] = fmaf(mx2, sf2[u][v], G[v]);
           A = fmaf(mx2, x2, A); Gw += mx2;
         }
-        // further occurrences of the feature in this batch (a frequent feature of Criteo-shaped rows has dozens to thousands per
-        // batch).  Added in occurrence order, so the result does not depend on how they are fetched:
-        if constexpr (EPI == 1) {
-          // one row per wave-wide load: the whole wavefront is here together.  64 descriptors and their multipliers arrive
-          // lane-parallel (one coalesced load + one gather), then the S rows TL at a time with the descriptors broadcast by
-          // v_readlane -- per TL occurrences ONE dependent round trip instead of three per occurrence.
-          // (32 rows per round for the one-segment-per-wavefront path was measured in round 4: k_apply_seg_scan 7.6 -> 8.1 us per
-          //  512-row batch of Criteo-shaped rows -- most segments there hold ~8 occurrences and pay for the longer unrolled round)
-          constexpr int TL = (VEC == 1) ? 16 : 8;
-          for (uint32_t base = i2; base < b; base += 64) {
-            const uint32_t cc = min(64u, b - base);
-            TEntry te; te.e = 0; te.x = 0.f; float tm = 0.f;
-            if (SPW == 1 && PRE2 && base == i2) { te = te_pre; tm = tm_pre; }          // (asked for with the descriptor, above)
-            else if (lane < cc) { te = load_stream8(t_ent + base + lane); tm = mult[te.e]; }
-            for (uint32_t q0 = 0; q0 < cc; q0 += TL) {
-              float s2[TL][VEC];
-#pragma unroll
-              for (int q = 0; q < TL; q++) {
-                const uint32_t e2 = bcast_u32<1>(te.e, (q0 + q) & 63u);
-                if (q0 + q < cc) load_vec<VEC>(S + (size_t)e2 * KP + f * VEC, s2[q]);
-                else {
-#pragma unroll
-                  for (int v = 0; v < VEC; v++) s2[q][v] = 0.f;
-                }
-              }
-#pragma unroll
-              for (int q = 0; q < TL; q++) {
-                const float x2 = bcast_f32<1>(te.x, (q0 + q) & 63u), m2 = bcast_f32<1>(tm, (q0 + q) & 63u);
-                if (q0 + q < cc) {
-                  const float mx2 = m2 * x2;
-#pragma unroll
-                  for (int v = 0; v < VEC; v++) G[v] = fmaf(mx2, s2[q][v], G[v]);
-                  A = fmaf(mx2, x2, A); Gw += mx2;
-                }
-              }
-            }
-          }
-        } else {
-          // several rows per wave-wide load (KP < 64): every lane group walks its own segment, TL occurrences at a time
-          constexpr int TL = 8;
-          for (; i2 < b; i2 += TL) {
-            TEntry tt[TL]; float mm[TL]; float s2[TL][VEC];
-#pragma unroll
-            for (int q = 0; q < TL; q++) { tt[q].e = 0; tt[q].x = 0.f; if (i2 + q < b) tt[q] = t_ent[i2 + q]; }
-#pragma unroll
-            for (int q = 0; q < TL; q++) {
-              mm[q] = 0.f;
-              if (i2 + q < b) { mm[q] = mult[tt[q].e]; load_vec<VEC>(S + (size_t)tt[q].e * KP + f * VEC, s2[q]); }
-              else {
-#pragma unroll
-                for (int v = 0; v < VEC; v++) s2[q][v] = 0.f;
-              }
-            }
-#pragma unroll
-            for (int q = 0; q < TL; q++) {
-              if (i2 + q < b) {
-                const float mx2 = mm[q] * tt[q].x;
-#pragma unroll
-                for (int v = 0; v < VEC; v++) G[v] = fmaf(mx2, s2[q][v], G[v]);
-                A = fmaf(mx2, tt[q].x, A); Gw += mx2;
-              }
-            }
-          }
-        }
+        seg_tail<KP, SPW == 1 && PRE2>(t_ent, S, mult, i2, b, lane, f, G, A, Gw, te_pre, tm_pre);
         const float nocc = (float)(b - a);
         float nv[VEC];
         if constexpr (SGDA) {

@@ -1549,11 +1549,9 @@ int fmx_adapt_end(fmx_handle h) {
   return FMX_OK;
 }
 
-int fmx_adapt_get_state_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double* nw_out, double* nv_out) {
-  if (!h) return FMX_E_ARG;
+// the gather of fmx_get_param_rows over nt state tables, one after the other: outs[t] = {the linear weights' state, the factors' state}
+static int state_rows(fmx_handle h, const char* what, const uint32_t* ids, uint32_t count, const Tab* tabs, double* const (*outs)[2], int nt) {
   const int k = h->cfg.num_factor;
-  if (!ids || !nw_out || (k > 0 && !nv_out)) return fail(h, FMX_E_ARG, "fmx_adapt_get_state_rows: ids / nw_out / nv_out is NULL");
-  if (!h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_adapt_get_state_rows before fmx_adapt_begin");
   for (uint32_t i = 0; i < count; i++)
     if (ids[i] >= h->cfg.num_attribute) return fail(h, FMX_E_ARG, "feature id %u >= num_attribute", ids[i]);
   if (count == 0) return FMX_OK;
@@ -1563,29 +1561,34 @@ int fmx_adapt_get_state_rows(fmx_handle h, const uint32_t* ids, uint32_t count, 
   HIPCHK(h, fmx_dev_alloc(&d_ids, (size_t)count * 4));
   hipError_t er = fmx_dev_alloc(&d_out, nout * sizeof(double));
   if (er == hipSuccess) er = hipMemcpyAsync(d_ids, ids, (size_t)count * 4, hipMemcpyHostToDevice, h->stream);
-  if (er == hipSuccess) {                                       // the gather of fmx_get_param_rows over the accumulator tables
-    const Tab ac{h->adapt.nv, h->adapt.nw, h->tb.rs, 1u};
+  for (int t = 0; t < nt && er == hipSuccess; t++) {
     hipLaunchKernelGGL(k_fetch_rows, dim3((uint32_t)((nout + 255) / 256)), dim3(256), 0, h->stream, d_ids, count, k,
-                       make_shard(h->cfg), ac, d_out, d_out + count);
+                       make_shard(h->cfg), tabs[t], d_out, d_out + count);
     er = hipGetLastError();
+    if (er == hipSuccess) er = hipMemcpyAsync(outs[t][0], d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (er == hipSuccess && k > 0) er = hipMemcpyAsync(outs[t][1], d_out + count, (size_t)count * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
   }
-  if (er == hipSuccess) er = hipMemcpyAsync(nw_out, d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-  if (er == hipSuccess && k > 0) er = hipMemcpyAsync(nv_out, d_out + count, (size_t)count * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-  if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
   fmx_dev_free(d_ids); fmx_dev_free(d_out);
-  if (er != hipSuccess) return fail(h, FMX_E_HIP, "fmx_adapt_get_state_rows: %s", hipGetErrorString(er));
+  if (er != hipSuccess) return fail(h, FMX_E_HIP, "%s: %s", what, hipGetErrorString(er));
   return FMX_OK;
 }
 
-// one epoch: per batch the batch rule's row sums and bias recurrence (fmx_sgda_epoch_minibatch's three launches), then one owner per
-// (batch, feature) segment takes the AdaGrad step (k_adapt_apply_seg).  The bias stays plain SGD at fmx_config::learn_rate.
-int fmx_adapt_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
-  int rc = check_slot(h, slot, true);
-  if (rc) return rc;
-  if (!h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_adapt_epoch before fmx_adapt_begin");
-  rc = adapt_check_handle(h, "fmx_adapt_epoch"); if (rc) return rc;
-  if (h->sgda.reg) return fail(h, FMX_E_STATE, "fmx_adapt_epoch: an SGDA session is open (call fmx_sgda_end first)");
-  rc = slot_in_session(h, slot, "fmx_adapt_epoch"); if (rc) return rc;
+int fmx_adapt_get_state_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double* nw_out, double* nv_out) {
+  if (!h) return FMX_E_ARG;
+  if (!ids || !nw_out || (h->cfg.num_factor > 0 && !nv_out)) return fail(h, FMX_E_ARG, "fmx_adapt_get_state_rows: ids / nw_out / nv_out is NULL");
+  if (!h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_adapt_get_state_rows before fmx_adapt_begin");
+  const Tab tabs[1] = {Tab{h->adapt.nv, h->adapt.nw, h->tb.rs, 1u}};
+  double* const outs[1][2] = {{nw_out, nv_out}};
+  return state_rows(h, "fmx_adapt_get_state_rows", ids, count, tabs, outs, 1);
+}
+
+// one epoch of an optimiser that keeps per-coordinate state (AdaGrad, FTRL), after its entry point's own session checks: per batch the
+// batch rule's row sums and bias recurrence (fmx_sgda_epoch_minibatch's three launches), then launch_owner(sw, hy, st) starts the one
+// kernel in which an owner per (batch, feature) segment takes the rule's step.  The bias stays plain SGD at fmx_config::learn_rate.
+extern "C++" {
+template <class Owner>
+static int stateful_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats, Owner launch_owner) {
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   HIPCHK(h, hipSetDevice(h->device));
   Slot& s = h->slots[slot];
@@ -1597,7 +1600,7 @@ int fmx_adapt_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, f
   // batch 0: fmx_sgd_epoch's choice (the plain rule's stability cut, curvature factor 1): conservative on purpose -- the step is bounded
   // by eta whatever the batch, but whether a larger default pays is a measurement, not this function's decision
   fmx_batch_info bi;
-  rc = ensure_coll_mass(h, s); if (rc) return rc;
+  int rc = ensure_coll_mass(h, s); if (rc) return rc;
   resolve_batch(h->cfg, s.coll_mass, batch, FMX_DEFAULT_BATCH, 1.0, &bi);
   const uint32_t B = bi.batch;
   const uint32_t chunk = w0_chunk ? w0_chunk : default_w0_chunk(h->cfg);
@@ -1605,8 +1608,6 @@ int fmx_adapt_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, f
   const uint32_t Bc = std::min<uint32_t>(B, s.n_rows);
   rc = ensure_scratch(h, Bc, 0); if (rc) return rc;
   touch_w(h);                                                   // (a side stream kept by FMX_FLAG_KEEP_WSIDE is stale from here on)
-  const Tab ac{h->adapt.nv, h->adapt.nw, h->tb.rs, 1u};
-  const float eta = h->adapt.eta;
   hipStream_t st = h->stream;
   HIPCHK(h, hipEventRecord(h->ev0, st));
   uint64_t batches = 0;
@@ -1618,9 +1619,7 @@ int fmx_adapt_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, f
     rc = launch_scan(h, rest, s.target + row0, nb, chunk, hy, h->mult, st);
     if (rc) return rc;
     const SegWork sw = seg_work_dense(h, s, (size_t)(row0 / B), S, h->mult);
-    if (sw.nseg) {
-      KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_adapt_apply_seg<KP, AdaptU<KP>::value>), ((uint64_t)sw.nseg + 63) / 64, st, sw, h->tb, ac, hy, eta));
-    }
+    if (sw.nseg) { rc = launch_owner(sw, hy, st); if (rc) return rc; }
     HIPCHK(h, hipGetLastError());
     batches++;
   }
@@ -1639,6 +1638,21 @@ int fmx_adapt_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, f
     stats->setup_seconds = h->setup_acc;
   }
   return FMX_OK;
+}
+}  // extern "C++"
+
+int fmx_adapt_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
+  int rc = check_slot(h, slot, true);
+  if (rc) return rc;
+  if (!h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_adapt_epoch before fmx_adapt_begin");
+  rc = adapt_check_handle(h, "fmx_adapt_epoch"); if (rc) return rc;
+  if (h->sgda.reg) return fail(h, FMX_E_STATE, "fmx_adapt_epoch: an SGDA session is open (call fmx_sgda_end first)");
+  rc = slot_in_session(h, slot, "fmx_adapt_epoch"); if (rc) return rc;
+  const AdagradRule rule{{Tab{h->adapt.nv, h->adapt.nw, h->tb.rs, 1u}}, h->adapt.eta};
+  return stateful_epoch(h, slot, batch, w0_chunk, stats, [&](const SegWork& sw, const Hyper& hy, hipStream_t st) -> int {
+    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_adapt_apply_seg<KP, AdaptU<KP>::value>), ((uint64_t)sw.nseg + 63) / 64, st, sw, h->tb, rule, hy));
+    return FMX_OK;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1710,35 +1724,14 @@ int fmx_ftrl_end(fmx_handle h) {
 
 int fmx_ftrl_get_state_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double* zw, double* zv, double* nw, double* nv) {
   if (!h) return FMX_E_ARG;
-  const int k = h->cfg.num_factor;
-  if (!ids || !zw || !nw || (k > 0 && (!zv || !nv))) return fail(h, FMX_E_ARG, "fmx_ftrl_get_state_rows: ids / zw / zv / nw / nv is NULL");
+  if (!ids || !zw || !nw || (h->cfg.num_factor > 0 && (!zv || !nv))) return fail(h, FMX_E_ARG, "fmx_ftrl_get_state_rows: ids / zw / zv / nw / nv is NULL");
   if (!h->ftrl.nv) return fail(h, FMX_E_STATE, "fmx_ftrl_get_state_rows before fmx_ftrl_begin");
-  for (uint32_t i = 0; i < count; i++)
-    if (ids[i] >= h->cfg.num_attribute) return fail(h, FMX_E_ARG, "feature id %u >= num_attribute", ids[i]);
-  if (count == 0) return FMX_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  uint32_t* d_ids = nullptr; double* d_out = nullptr;
-  const size_t nout = (size_t)count * (size_t)(k + 1);
-  HIPCHK(h, fmx_dev_alloc(&d_ids, (size_t)count * 4));
-  hipError_t er = fmx_dev_alloc(&d_out, nout * sizeof(double));
-  if (er == hipSuccess) er = hipMemcpyAsync(d_ids, ids, (size_t)count * 4, hipMemcpyHostToDevice, h->stream);
   const Tab tabs[2] = {Tab{h->ftrl.zv, h->ftrl.zw, h->tb.rs, 1u}, Tab{h->ftrl.nv, h->ftrl.nw, h->tb.rs, 1u}};
   double* const outs[2][2] = {{zw, zv}, {nw, nv}};
-  for (int t = 0; t < 2 && er == hipSuccess; t++) {             // the gather of fmx_get_param_rows over the z table, then over the n table
-    hipLaunchKernelGGL(k_fetch_rows, dim3((uint32_t)((nout + 255) / 256)), dim3(256), 0, h->stream, d_ids, count, k,
-                       make_shard(h->cfg), tabs[t], d_out, d_out + count);
-    er = hipGetLastError();
-    if (er == hipSuccess) er = hipMemcpyAsync(outs[t][0], d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (er == hipSuccess && k > 0) er = hipMemcpyAsync(outs[t][1], d_out + count, (size_t)count * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
-  }
-  fmx_dev_free(d_ids); fmx_dev_free(d_out);
-  if (er != hipSuccess) return fail(h, FMX_E_HIP, "fmx_ftrl_get_state_rows: %s", hipGetErrorString(er));
-  return FMX_OK;
+  return state_rows(h, "fmx_ftrl_get_state_rows", ids, count, tabs, outs, 2);
 }
 
-// one epoch: fmx_adapt_epoch's three launches per batch with k_ftrl_apply_seg as the owner kernel.  The bias stays plain SGD at
-// fmx_config::learn_rate; regw / regv are not read (L2 lives in the proximal step).
+// one epoch: stateful_epoch with k_ftrl_apply_seg as the owner kernel.  regw / regv are not read (L2 lives in the proximal step).
 int fmx_ftrl_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
   int rc = check_slot(h, slot, true);
   if (rc) return rc;
@@ -1746,58 +1739,12 @@ int fmx_ftrl_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fm
   rc = adapt_check_handle(h, "fmx_ftrl_epoch"); if (rc) return rc;
   if (h->sgda.reg || h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_ftrl_epoch: an SGDA or fmx_adapt session is open");
   rc = slot_in_session(h, slot, "fmx_ftrl_epoch"); if (rc) return rc;
-  { int _rc = lag_flush(h); if (_rc) return _rc; }
-  HIPCHK(h, hipSetDevice(h->device));
-  Slot& s = h->slots[slot];
-  if (stats) memset(stats, 0, sizeof(*stats));
-  if (s.n_rows == 0) return FMX_OK;
-  if (!s.blocks.empty()) return fail(h, FMX_E_UNSUPPORTED, "relations are not supported with SGD");   // fm_learn_sgd.h:61-63
-  h->setup_acc = 0.0; h->run_status = 0;
-  const Hyper hy = make_hyper(h->cfg);
-  fmx_batch_info bi;                                            // batch 0: exactly fmx_adapt_epoch's choice
-  rc = ensure_coll_mass(h, s); if (rc) return rc;
-  resolve_batch(h->cfg, s.coll_mass, batch, FMX_DEFAULT_BATCH, 1.0, &bi);
-  const uint32_t B = bi.batch;
-  const uint32_t chunk = w0_chunk ? w0_chunk : default_w0_chunk(h->cfg);
-  rc = ensure_segments(h, s, B); if (rc) return rc;
-  const uint32_t Bc = std::min<uint32_t>(B, s.n_rows);
-  rc = ensure_scratch(h, Bc, 0); if (rc) return rc;
-  touch_w(h);                                                   // (a side stream kept by FMX_FLAG_KEEP_WSIDE is stale from here on)
   const FtrlState& fs = h->ftrl;
-  const Tab zt{fs.zv, fs.zw, h->tb.rs, 1u}, nt{fs.nv, fs.nw, h->tb.rs, 1u};
-  const FtrlHyper fh{fs.inv_alpha, fs.beta, fs.l1_w, fs.l1_v, fs.l2_w, fs.l2_v};
-  hipStream_t st = h->stream;
-  HIPCHK(h, hipEventRecord(h->ev0, st));
-  uint64_t batches = 0;
-  for (uint64_t row0 = 0; row0 < s.n_rows; row0 += B) {
-    const uint32_t nb = (uint32_t)std::min<uint64_t>(B, s.n_rows - row0);
-    float* S = h->partial;
-    float* rest = S + (size_t)nb * h->KP;
-    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, st, s.ent, s.row_ptr, row0, nb, h->tb, h->cfg.k1, S, rest, (const float*)nullptr));
-    rc = launch_scan(h, rest, s.target + row0, nb, chunk, hy, h->mult, st);
-    if (rc) return rc;
-    const SegWork sw = seg_work_dense(h, s, (size_t)(row0 / B), S, h->mult);
-    if (sw.nseg) {
-      KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_ftrl_apply_seg<KP, FtrlU<KP>::value>), ((uint64_t)sw.nseg + 63) / 64, st, sw, h->tb, zt, nt, hy, fh));
-    }
-    HIPCHK(h, hipGetLastError());
-    batches++;
-  }
-  HIPCHK(h, hipEventRecord(h->ev1, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-  rc = scan_error_check(h); if (rc) return rc;
-  if (stats) {
-    float ms = 0;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    stats->rows = s.n_rows; stats->batches = batches; stats->device_seconds = ms * 1e-3;
-    stats->main_kernel_seconds = stats->device_seconds; stats->main_kernel_launches = batches;
-    stats->max_feature_count = s.max_seg_count;
-    stats->batch_used = bi.batch; stats->collision_mass = bi.collision_mass; stats->batch_gain = bi.batch_gain;
-    stats->status = bi.status | h->run_status;
-    stats->w0_chunk_used = chunk;
-    stats->setup_seconds = h->setup_acc;
-  }
-  return FMX_OK;
+  const FtrlRule rule{{Tab{fs.zv, fs.zw, h->tb.rs, 1u}, Tab{fs.nv, fs.nw, h->tb.rs, 1u}}, FtrlHyper{fs.inv_alpha, fs.beta, fs.l1_w, fs.l1_v, fs.l2_w, fs.l2_v}};
+  return stateful_epoch(h, slot, batch, w0_chunk, stats, [&](const SegWork& sw, const Hyper& hy, hipStream_t st) -> int {
+    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_ftrl_apply_seg<KP, FtrlU<KP>::value>), ((uint64_t)sw.nseg + 63) / 64, st, sw, h->tb, rule, hy));
+    return FMX_OK;
+  });
 }
 
 // how many coordinates of the model are exactly zero (include/fmx.h "fmx_param_sparsity"): one pass of k_param_sparsity

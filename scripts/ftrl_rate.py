@@ -1,9 +1,9 @@
 """FTRL-proximal with L1 on the minibatch rule (fmx_ftrl_epoch) on the MI355X: what it costs and what it buys.
 
-    python scripts/ftrl_rate.py [--what throughput,convergence] [--reps 3] [--out FILE]
+    python scripts/ftrl_rate.py [--what throughput,convergence] [--reps 3] [--factors 64] [--out FILE]
 
-throughput : scripts/adagrad_rate.py's shape: one handle, n = 1e6 features, k = 64, 2^20 rows of 32 one-hot entries generated on the
-             device, batches 16 384 and 65 536.  fmx_ftrl_epoch against fmx_adapt_epoch and fmx_sgd_epoch(MINIBATCH,
+throughput : scripts/adagrad_rate.py's shape: one handle, n = 1e6 features, k = --factors (64 by default; 8 times the path with several
+             rows per wave-wide load), 2^20 rows of 32 one-hot entries generated on the device, batches 16 384 and 65 536. fmx_ftrl_epoch against fmx_adapt_epoch and fmx_sgd_epoch(MINIBATCH,
              FMX_APPLY_SEGMENTED) -- the three share the row sums and the recurrence and differ in the owner kernel -- taking turns in
              this process (the AdaGrad and the FTRL session exclude each other, so each turn opens and ends its session outside the
              timed epoch), one warm-up epoch each per batch size, then the fastest of --reps epochs by
@@ -36,8 +36,8 @@ def sparsity_dict(sp):
     return {f: int(getattr(sp, f)) for f, _ in capi.Sparsity._fields_}
 
 
-def throughput(reps, out):
-    n, k, nnz, rows = 1_000_000, 64, 32, 1 << 20
+def throughput(reps, k, out):
+    n, nnz, rows = 1_000_000, 32, 1 << 20
     h = capi.Handle(n, k, True, True, capi.TASK_CLASSIFICATION, 0.0, 0.0, 0.001, 0.01, -1.0, 1.0)
     h.init_params(0.0, 0.01, 1)
     h.synth_rows(0, 123, 0, rows, nnz)
@@ -104,13 +104,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", default="throughput,convergence")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--factors", type=int, default=64, help="k of the throughput run")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if capi.load().fmx_device_count() == 0:
         raise SystemExit("ftrl_rate.py needs a HIP device: nothing here is measured on a CPU")
     what = a.what.split(",")
     if "throughput" in what:
-        throughput(a.reps, a.out)
+        throughput(a.reps, a.factors, a.out)
     if "convergence" in what:
         convergence(a.out)
 

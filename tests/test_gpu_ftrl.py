@@ -112,10 +112,14 @@ def run_parity(k, task, k0=True, k1=True, opts=PARITY):
         assert 0.05 < (w == 0).mean() < 0.5
 
 
-@pytest.mark.parametrize("task", [0, 1])
-@pytest.mark.parametrize("k", [1, 8, 64, 100, 128, 256])
+# every width the owner kernel is instantiated for: six of them under both tasks, the other six once (regression 2, 16, 512; classification 4, 32, 1024)
+PARITY_WIDTHS = [(k, task) for k in (1, 8, 64, 100, 128, 256) for task in (0, 1)] + [(2, 0), (16, 0), (512, 0), (4, 1), (32, 1), (1024, 1)]
+
+
+@pytest.mark.parametrize("k, task", PARITY_WIDTHS)
 def test_parity(k, task):
-    """several rows per wave-wide load (k 1, 8), VEC 1, 2 and 4 (k 64, 128, 256), a row shorter than KP (k 100: 112 floats under KP 128)"""
+    """several rows per wave-wide load (k 1, 8), VEC 1, 2 and 4 (k 64, 128, 256), a row shorter than KP (k 100: 112 floats under KP 128);
+    the remaining widths once each (k 2, 4, 16, 32; VEC 8 and 16 with fewer segment groups per round: k 512, 1024)"""
     run_parity(k, task)
 
 
