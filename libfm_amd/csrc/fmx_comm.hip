@@ -838,8 +838,8 @@ static int kept_block_partials(fmx_handle h, const Slot& s) {
     Tab tb = h->tb;                                            // (a shard's block ids are local rows: attr_offset 0)
     tb.V += (size_t)br->attr_offset * tb.rs; tb.w += (size_t)br->attr_offset * tb.ws;
     float* Sb = br->pbuf;
-    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false>), B, h->stream, br->rows.ent, br->rows.row_ptr, (uint64_t)0, B, tb, h->cfg.k1,
-                                       Sb, Sb + (size_t)B * h->KP, (const float*)nullptr));
+    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false>), B, h->stream, br->rows.ent, br->rows.row_ptr, (uint64_t)0, B, RowsF32{tb}, h->cfg.k1,
+                                       Sb, Sb + (size_t)B * h->KP));
   }
   HIPCHK(h, hipGetLastError());
   return FMX_OK;
@@ -900,6 +900,24 @@ static int group_predict_chunks(fmx_group g, int slot, double* out, float* d_all
   return FMX_OK;
 }
 
+// The finished y-hat of all n_rows >= 1 rows of a slot on the first shard's device (h0->ev0 where the device work begins), then
+// reduce(d_all) there: what fmx_group_evaluate_ex, _evaluate_by_query and _post_accumulate do after their checks
+extern "C++" {
+template <class Reduce>
+static int group_reduce_scores(fmx_group g, int slot, const char* who, Reduce reduce) {
+  fmx_handle h0 = g->hs[0];
+  float* d_all = nullptr;
+  HIPCHK(h0, hipSetDevice(h0->device));
+  HIPCHK(h0, fmx_dev_alloc(&d_all, (size_t)h0->slots[slot].n_rows * sizeof(float)));
+  int rc = (hipEventRecord(h0->ev0, h0->stream) == hipSuccess) ? FMX_OK : fail(h0, FMX_E_HIP, "%s: hipEventRecord failed", who);
+  if (rc == FMX_OK) rc = group_predict_chunks(g, slot, nullptr, d_all);
+  if (rc == FMX_OK) { hipSetDevice(h0->device); rc = reduce((const float*)d_all); if (rc) g->err = fmx_last_error(h0); }
+  hipSetDevice(h0->device);
+  fmx_dev_free(d_all);
+  return rc;
+}
+}
+
 int fmx_group_predict(fmx_group g, int slot, double* out) {
   if (!g || !out) return FMX_E_ARG;
   for (auto m : g->hs) if (!m) return gfail(g, FMX_E_STATE, "a member of the group was destroyed");
@@ -937,7 +955,7 @@ int fmx_group_evaluate(fmx_group g, int slot, fmx_eval* out) {
   return FMX_OK;
 }
 
-// fmx_evaluate_ex over the shards: the finished y-hat chunks stay on the first shard's device and are reduced there (fmx_eval.hip)
+// fmx_evaluate_ex over the shards: the finished y-hat chunks stay on the first shard's device and are reduced there (group_reduce_scores; fmx_eval.hip)
 int fmx_group_evaluate_ex(fmx_group g, int slot, const fmx_eval_opts* opts, fmx_eval_ex* out) {
   static const char who[] = "fmx_group_evaluate_ex";
   if (!g) return FMX_E_ARG;
@@ -952,15 +970,7 @@ int fmx_group_evaluate_ex(fmx_group g, int slot, const fmx_eval_opts* opts, fmx_
   const Slot& s = h0->slots[slot];
   eval_ex_empty(out);
   if (s.n_rows == 0) return FMX_OK;
-  float* d_all = nullptr;
-  HIPCHK(h0, hipSetDevice(h0->device));
-  HIPCHK(h0, fmx_dev_alloc(&d_all, (size_t)s.n_rows * sizeof(float)));
-  int rc = (hipEventRecord(h0->ev0, h0->stream) == hipSuccess) ? FMX_OK : fail(h0, FMX_E_HIP, "%s: hipEventRecord failed", who);
-  if (rc == FMX_OK) rc = group_predict_chunks(g, slot, nullptr, d_all);
-  if (rc == FMX_OK) { hipSetDevice(h0->device); rc = eval_ex_scores(h0, s, d_all, 0, link, out); if (rc) g->err = fmx_last_error(h0); }
-  hipSetDevice(h0->device);
-  fmx_dev_free(d_all);
-  return rc;
+  return group_reduce_scores(g, slot, who, [&](const float* y) { return eval_ex_scores(h0, s, y, 0, link, out); });
 }
 
 // fmx_set_row_queries / fmx_evaluate_by_query over the shards (fmx_evalq.hip): the ids live on the first shard's slot, where the
@@ -990,15 +1000,7 @@ int fmx_group_evaluate_by_query(fmx_group g, int slot, const fmx_eval_opts* opts
   const Slot& s = h0->slots[slot];
   evalq_empty(out, s.n_queries);
   if (s.n_rows == 0) { out->empty_queries = s.n_queries; evalq_zero_per_query(s.n_queries, num2_q, pos_q, neg_q); return FMX_OK; }
-  float* d_all = nullptr;
-  HIPCHK(h0, hipSetDevice(h0->device));
-  HIPCHK(h0, fmx_dev_alloc(&d_all, (size_t)s.n_rows * sizeof(float)));
-  int rc = (hipEventRecord(h0->ev0, h0->stream) == hipSuccess) ? FMX_OK : fail(h0, FMX_E_HIP, "%s: hipEventRecord failed", who);
-  if (rc == FMX_OK) rc = group_predict_chunks(g, slot, nullptr, d_all);
-  if (rc == FMX_OK) { hipSetDevice(h0->device); rc = evalq_scores(h0, s, d_all, 0, link, out, num2_q, pos_q, neg_q); if (rc) g->err = fmx_last_error(h0); }
-  hipSetDevice(h0->device);
-  fmx_dev_free(d_all);
-  return rc;
+  return group_reduce_scores(g, slot, who, [&](const float* y) { return evalq_scores(h0, s, y, 0, link, out, num2_q, pos_q, neg_q); });
 }
 
 // fmx_post_* over the shards (fmx_post.hip): the accumulator lives on the first shard's slot; only _accumulate needs the other
@@ -1024,15 +1026,7 @@ int fmx_group_post_accumulate(fmx_group g, int slot, fmx_post_stats* out) {
   GCHK(g, post_check(cur, who, slot, true));
   Slot& s = h0->slots[slot];
   if (s.n_rows == 0) { GCHK(g, post_accum_scores(cur, s, nullptr, 0, out)); return FMX_OK; }
-  float* d_all = nullptr;
-  HIPCHK(h0, hipSetDevice(h0->device));
-  HIPCHK(h0, fmx_dev_alloc(&d_all, (size_t)s.n_rows * sizeof(float)));
-  int rc = (hipEventRecord(h0->ev0, h0->stream) == hipSuccess) ? FMX_OK : fail(h0, FMX_E_HIP, "%s: hipEventRecord failed", who);
-  if (rc == FMX_OK) rc = group_predict_chunks(g, slot, nullptr, d_all);
-  if (rc == FMX_OK) { hipSetDevice(h0->device); rc = post_accum_scores(h0, s, d_all, 0, out); if (rc) g->err = fmx_last_error(h0); }
-  hipSetDevice(h0->device);
-  fmx_dev_free(d_all);
-  return rc;
+  return group_reduce_scores(g, slot, who, [&](const float* y) { return post_accum_scores(h0, s, y, 0, out); });
 }
 
 int fmx_group_post_evaluate_ex(fmx_group g, int slot, uint32_t which, fmx_eval_ex* out) {

@@ -1,9 +1,8 @@
 // fmx_compact.hip -- C-ABI (include/fmx.h "fmx_compact_*"): a frozen bf16 copy of the model to score from.
-// fmx_compact_begin quantises V in one pass (k_compact_quant) and copies w and w0; predict / evaluate / evaluate_ex / topk are the
-// fp32 entry points' pipelines with the row sums taken from the copy (k_rowsums_c): k_yhat, k_eval, eval_ex_scores and topk_impl are
-// shared, not copied.  Kernels: fmx_compact_kernels.h.
+// fmx_compact_begin quantises V in one pass (k_compact_quant) and copies w and w0; predict / evaluate / evaluate_ex / topk / get_rows
+// are their own checks and then the fp32 entry points' code with the snapshot named as the rows' source (slot_scores, predict_out,
+// evaluate_out, eval_ex_scores, topk_impl, gather_rows: k_rowsums and k_fetch_rows over RowsBf16).  Kernels: fmx_compact_kernels.h.
 #include "fmx_internal.h"
-#include "fmx_compact_kernels.h"
 
 namespace {
 
@@ -25,17 +24,6 @@ int compact_check_slot(fmx_handle h, const char* who, int slot, bool need_target
   return FMX_OK;
 }
 
-CTab compact_tab(fmx_handle h, const CompactState& c) { return CTab{c.V, c.w, h->tb.rs}; }
-
-// rest[e] (= y-hat - w0) of every row of a slot from the snapshot: launch_rest's plain form
-int compact_rest(fmx_handle h, const Slot& s, float* rest, hipStream_t st) {
-  const CTab ct = compact_tab(h, h->compact);
-  KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums_c<KP, false, true>), s.n_rows, st, s.ent, s.row_ptr, (uint64_t)0, s.n_rows, ct, h->cfg.k1,
-                                     (float*)nullptr, rest));
-  HIPCHK(h, hipGetLastError());
-  return FMX_OK;
-}
-
 void compact_release(CompactState& c) {
   fmx_dev_free(c.V); fmx_dev_free(c.w); fmx_dev_free(c.w0);
   c = CompactState();
@@ -44,14 +32,6 @@ void compact_release(CompactState& c) {
 }  // namespace
 
 void compact_free(fmx_handle h) { compact_release(h->compact); }
-
-int compact_partial_rows(fmx_handle h, const CompactState& snap, const Slot& s, uint64_t row0, uint32_t n_rows, float* S, float* c, hipStream_t st) {
-  if (n_rows == 0) return FMX_OK;
-  const CTab ct = compact_tab(h, snap);
-  KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums_c<KP, true, false>), n_rows, st, s.ent, s.row_ptr, row0, n_rows, ct, h->cfg.k1, S, c));
-  HIPCHK(h, hipGetLastError());
-  return FMX_OK;
-}
 
 extern "C" {
 
@@ -129,21 +109,7 @@ int fmx_compact_predict(fmx_handle h, int slot, double* out) {
   rc = compact_check_slot(h, who, slot, false); if (rc) return rc;
   { int _rc = lag_flush(h); if (_rc) return _rc; }              // (the scratch below is shared with a bias-lag epoch still in flight)
   HIPCHK(h, hipSetDevice(h->device));
-  const Slot& s = h->slots[slot];
-  if (s.n_rows == 0) return FMX_OK;
-  rc = ensure_scratch(h, 0, (size_t)s.n_rows * 2);
-  if (rc) return rc;
-  rc = compact_rest(h, s, h->rest, h->stream);
-  if (rc) return rc;
-  float* yhat = h->rest + s.n_rows;
-  hipLaunchKernelGGL(k_yhat, dim3(std::min<uint32_t>((s.n_rows + 255) / 256, 2048)), dim3(256), 0, h->stream,
-                     h->rest, s.n_rows, h->cfg.k0, h->compact.w0, yhat);
-  HIPCHK(h, hipGetLastError());
-  std::vector<float> tmp(s.n_rows);
-  HIPCHK(h, hipMemcpyAsync(tmp.data(), yhat, (size_t)s.n_rows * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  for (uint32_t r = 0; r < s.n_rows; r++) out[r] = (double)tmp[r];
-  return FMX_OK;
+  return predict_out(h, h->slots[slot], &h->compact, out);
 }
 
 int fmx_compact_evaluate(fmx_handle h, int slot, fmx_eval* out) {
@@ -158,26 +124,7 @@ int fmx_compact_evaluate(fmx_handle h, int slot, fmx_eval* out) {
   memset(out, 0, sizeof(*out));
   out->rows = s.n_rows;
   if (s.n_rows == 0) return FMX_OK;
-  rc = ensure_scratch(h, 0, (size_t)s.n_rows * 2);
-  if (rc) return rc;
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  rc = compact_rest(h, s, h->rest, h->stream);
-  if (rc) return rc;
-  HIPCHK(h, hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));
-  hipLaunchKernelGGL(k_eval, dim3(std::min<uint32_t>((s.n_rows + 255) / 256, 2048)), dim3(256), 0, h->stream,
-                     h->rest, s.target, s.n_rows, make_hyper(h->cfg), h->compact.w0, h->acc);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  double acc[4];
-  HIPCHK(h, hipMemcpyAsync(acc, h->acc, sizeof(acc), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  float ms = 0;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  out->device_seconds = ms * 1e-3;
-  out->rmse = std::sqrt(acc[0] / s.n_rows);          // fm_learn.h:152
-  out->mae = acc[1] / s.n_rows;                      // fm_learn.h:148
-  out->accuracy = acc[2] / s.n_rows;                 // fm_learn.h:129
-  return FMX_OK;
+  return evaluate_out(h, s, &h->compact, out);
 }
 
 int fmx_compact_evaluate_ex(fmx_handle h, int slot, const fmx_eval_opts* opts, fmx_eval_ex* out) {
@@ -194,16 +141,10 @@ int fmx_compact_evaluate_ex(fmx_handle h, int slot, const fmx_eval_opts* opts, f
   const Slot& s = h->slots[slot];
   eval_ex_empty(out);
   if (s.n_rows == 0) return FMX_OK;
-  rc = ensure_scratch(h, 0, (size_t)s.n_rows * 2);
-  if (rc) return rc;
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  rc = compact_rest(h, s, h->rest, h->stream);
-  if (rc) return rc;
   // the finished y-hat with the SNAPSHOT's bias (eval_ex_scores would add the model's): exactly what fmx_compact_predict returns
-  float* yhat = h->rest + s.n_rows;
-  hipLaunchKernelGGL(k_yhat, dim3(std::min<uint32_t>((s.n_rows + 255) / 256, 2048)), dim3(256), 0, h->stream,
-                     h->rest, s.n_rows, h->cfg.k0, h->compact.w0, yhat);
-  HIPCHK(h, hipGetLastError());
+  const float* yhat;
+  rc = slot_scores(h, s, &h->compact, true, &yhat);
+  if (rc) return rc;
   return eval_ex_scores(h, s, yhat, 0, link, out);
 }
 
@@ -225,23 +166,10 @@ int fmx_compact_get_rows(fmx_handle h, const uint32_t* ids, uint32_t count, doub
   for (uint32_t i = 0; i < count; i++)
     if (ids[i] >= h->cfg.num_attribute) return fail(h, FMX_E_ARG, "%s: feature id %u >= num_attribute", who, ids[i]);
   if (count == 0) return FMX_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  uint32_t* d_ids = nullptr; double* d_out = nullptr;
-  const size_t nout = (size_t)count * (size_t)(k + 1);
-  HIPCHK(h, fmx_dev_alloc(&d_ids, (size_t)count * 4));
-  hipError_t er = fmx_dev_alloc(&d_out, nout * sizeof(double));
-  if (er == hipSuccess) er = hipMemcpyAsync(d_ids, ids, (size_t)count * 4, hipMemcpyHostToDevice, h->stream);
-  if (er == hipSuccess) {
-    hipLaunchKernelGGL(k_fetch_rows_c, dim3((uint32_t)((nout + 255) / 256)), dim3(256), 0, h->stream, (const uint32_t*)d_ids, count, k,
-                       compact_tab(h, h->compact), d_out, d_out + count);
-    er = hipGetLastError();
-  }
-  if (er == hipSuccess) er = hipMemcpyAsync(w_out, d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-  if (er == hipSuccess && k > 0) er = hipMemcpyAsync(v_out, d_out + count, (size_t)count * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-  if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
-  fmx_dev_free(d_ids); fmx_dev_free(d_out);
-  if (er != hipSuccess) return fail(h, FMX_E_HIP, "%s: %s", who, hipGetErrorString(er));
-  return FMX_OK;
+  double* const outs[1][2] = {{w_out, v_out}};
+  return gather_rows(h, who, ids, count, 1, outs, [&](int, dim3 grid, const uint32_t* d_ids, double* d_w, double* d_v) {
+    hipLaunchKernelGGL(k_fetch_rows<RowsBf16>, grid, dim3(256), 0, h->stream, d_ids, count, k, make_shard(h->cfg), compact_rows(h, h->compact), d_w, d_v);
+  });
 }
 
 }  // extern "C"

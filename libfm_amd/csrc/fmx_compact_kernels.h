@@ -3,11 +3,11 @@
 // k_compact_quant   one pass over V: the bf16 rows (same row stride in ELEMENTS, half the bytes) and the three numbers of
 //                   fmx_compact_info as BLOCK PARTIALS (no float atomics).
 // k_compact_final   one wavefront folds the block partials in a fixed order.
-// k_rowsums_c       k_rowsums from the snapshot: the sums of fm_model.h:110-125 over bf16 rows, with a lane map of its own (MapC).
-// k_fetch_rows_c    k_fetch_rows from the snapshot, dequantised.
+// RowsBf16          the snapshot as the row source of k_rowsums and k_fetch_rows (fmx_kernels.h): a lane map of its own (MapC) and
+//                   the load of a bf16 row (row_ld_c).
 //
-// A bf16 is the upper half of an fp32 and widens back with a 16-bit shift, so what k_rowsums_c computes is fm_model::predict of
-// the model (w0, w, q(V)) in k_rowsums' own arithmetic: only the load differs.
+// A bf16 is the upper half of an fp32 and widens back with a 16-bit shift, so what k_rowsums computes from RowsBf16 is
+// fm_model::predict of the model (w0, w, q(V)) in the very code that scores the fp32 model: only the load differs.
 #pragma once
 #include "fmx_kernels.h"
 
@@ -87,11 +87,11 @@ k_compact_final(const double* __restrict__ dpart, const unsigned long long* __re
 //   KP = 1       2-byte loads, 64 rows per wave-wide load
 //   KP = 2 .. 64 4-byte loads, KP / 2 lanes per row (k = 64: a 128-byte row on 32 lanes, two rows per wave-wide load)
 //   KP >= 128    one row per wavefront, 2 * VEC bytes per lane (VEC = KP / 64)
-// U: load rounds in flight, chosen so that a round asks for as many ROWS as row_sums<KP, 8> does (EPI * U = 8 * Map<KP>::EPI).
+// U: load rounds in flight, chosen so that a round asks for as many ROWS as row_sums does of RowsF32 (EPI * U = 8 * Map<KP>::EPI).
 // Lane l of a row's LPR lanes holds elements [l * VEC, l * VEC + VEC); lanes beyond the row's rs elements read zeros.
 // ----------------------------------------------------------------------------------------------
 #ifndef FMX_COMPACT_ROUND
-#define FMX_COMPACT_ROUND 1      // rows a round asks for, in units of row_sums<KP, 8>'s (experiments: -DFMX_COMPACT_ROUND=2)
+#define FMX_COMPACT_ROUND 1      // rows a round asks for, in units of RowsF32's (experiments: -DFMX_COMPACT_ROUND=2)
 #endif
 template <int KP> struct MapC {
   static constexpr int VEC = (KP >= 128) ? KP / 64 : (KP >= 2 ? 2 : 1);
@@ -134,91 +134,15 @@ template <int VEC> __device__ __forceinline__ void row_ld_c(const CTab& ct, size
   }
 }
 
-// row_sums (fmx_kernels.h) over the snapshot: the same sums in the same arithmetic, every load of a round issued before any is used.
-//   sum[v]  : sum_f for the lane's factors (complete over the row only AFTER subgroup_allsum<LPR> when EPI > 1)
-//   sq      : this lane's share of  sum_f sum_i (v x)^2
-//   lin     : this lane's share of  sum_i w[id_i] x_i
-template <int KP>
-__device__ __forceinline__ void row_sums_c(const Entry* __restrict__ ent, uint32_t size, const CTab ct, int k1,
-                                           float (&sum)[MapC<KP>::VEC], float& sq, float& lin) {
-  constexpr int VEC = MapC<KP>::VEC, LPR = MapC<KP>::LPR, EPI = MapC<KP>::EPI, U = MapC<KP>::U;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t g = lane / LPR, f = lane % LPR;
-#pragma unroll
-  for (int v = 0; v < VEC; v++) sum[v] = 0.f;
-  sq = 0.f; lin = 0.f;
-  for (uint32_t base = 0; base < size; base += 64) {
-    const uint32_t cnt = min(64u, size - base);
-    Entry e; e.id = 0; e.value = 0.f;
-    if (lane < cnt) {
-      e = load_stream8(ent + base + lane);
-      if (k1) lin += load_w(ct.w + (size_t)e.id) * e.value;
-    }
-    for (uint32_t i = 0; i < cnt; i += EPI * U) {
-      float vr[U][VEC]; float xs[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const uint32_t idx = i + u * EPI + g;
-        const uint32_t id = bcast_u32<EPI>(e.id, idx & 63u);
-        xs[u] = bcast_f32<EPI>(e.value, idx & 63u);
-        if (idx < cnt) {
-          row_ld_c<VEC>(ct, (size_t)id, f * VEC, vr[u]);
-        } else {
-          xs[u] = 0.f;
-#pragma unroll
-          for (int v = 0; v < VEC; v++) vr[u][v] = 0.f;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; u++)
-#pragma unroll
-        for (int v = 0; v < VEC; v++) {
-          const float d = vr[u][v] * xs[u];
-          sum[v] += d;
-          sq = fmaf(d, d, sq);
-        }
-    }
-  }
-}
-
-// k_rowsums (fmx_kernels.h) from the snapshot: one wavefront per example, the same outputs
-//   S[e][0..KP)  (WRITE_S)     scal[e] = FINISH ? rest_e = lin + 0.5*(sum_f S_ef^2 - Q_e) : c_e = lin - 0.5*Q_e
-// No LDS, no atomics.
-template <int KP, bool WRITE_S, bool FINISH>
-__global__ void __launch_bounds__(256)
-k_rowsums_c(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, uint64_t row0, uint32_t n_rows,
-            const CTab ct, int k1, float* __restrict__ S, float* __restrict__ scal) {
-  constexpr int VEC = MapC<KP>::VEC, LPR = MapC<KP>::LPR;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave0 = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-  const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
-  for (uint32_t e = wave0; e < n_rows; e += nwaves) {
-    const uint64_t a = row_ptr[row0 + e];
-    const uint32_t size = (uint32_t)(row_ptr[row0 + e + 1] - a);
-    float sum[VEC], sq, lin;
-    row_sums_c<KP>(ent + a, size, ct, k1, sum, sq, lin);
-#pragma unroll
-    for (int v = 0; v < VEC; v++) sum[v] = subgroup_allsum<LPR>(sum[v]);
-    if (WRITE_S && lane < LPR) store_vec<VEC>(S + (size_t)e * KP + lane * VEC, sum);
-    float part = lin - 0.5f * sq;
-    if (FINISH && lane < LPR) {
-#pragma unroll
-      for (int v = 0; v < VEC; v++) part = fmaf(0.5f * sum[v], sum[v], part);
-    }
-    part = wave_sum_dpp(part);
-    if (lane == 0) scal[e] = part;
-  }
-}
-
-// k_fetch_rows from the snapshot (unsharded handles only: feature id = row)
-static __global__ void k_fetch_rows_c(const uint32_t* __restrict__ ids, uint32_t count, int k, CTab ct,
-                                      double* __restrict__ w_out, double* __restrict__ v_out) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (uint64_t)count * (uint64_t)(k + 1)) return;
-  const uint32_t i = (uint32_t)(t / (k + 1)); const int f = (int)(t % (k + 1));
-  const size_t j = ids[i];
-  if (f == k) w_out[i] = (double)ct.w[j];
-  else v_out[(size_t)i * k + f] = (double)__uint_as_float((uint32_t)ct.V[j * ct.rs + f] << 16);
-}
+// The snapshot as a row source of row_sums / k_rowsums / k_fetch_rows (fmx_kernels.h "ROW SOURCE"): MapC's lanes and rounds, row_ld_c,
+// and w out of its own array (no side stream; the snapshot is unsharded, so feature id = row).
+struct RowsBf16 {
+  template <int KP> using Lanes = MapC<KP>;
+  CTab ct;
+  template <int VEC> __device__ __forceinline__ void ld(size_t id, uint32_t off, float (&out)[VEC]) const { row_ld_c<VEC>(ct, id, off, out); }
+  __device__ __forceinline__ float w1(size_t row) const { return load_w(ct.w + row); }
+  __device__ __forceinline__ float v1(size_t row, int f) const { return __uint_as_float((uint32_t)ct.V[row * ct.rs + f] << 16); }
+  __device__ __forceinline__ float lin(uint32_t id, uint64_t, uint32_t) const { return w1((size_t)id); }
+};
 
 }  // namespace fmx

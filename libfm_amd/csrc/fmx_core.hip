@@ -1,4 +1,5 @@
 // fmx_core.hip -- C-ABI (include/fmx.h): lifetime, parameters, rows, predict / evaluate.
+// The read side of every unit starts here: launch_rest, slot_scores, predict_out / evaluate_out (the model or the bf16 snapshot).
 // Build: python -m libfm_amd.build   (hipcc --offload-arch=gfx950 -O3 -munsafe-fp-atomics -shared -fPIC)
 //
 // No CPU fallback lives in this library: every compute entry point needs a HIP device and fails with FMX_E_HIP
@@ -175,8 +176,8 @@ int ensure_wside(fmx_handle h, Slot& s) {
 }
 
 // rest[e] (= y-hat - w0) for rows [row0,row0+n) of a slot, single device
-int launch_rest(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, float* rest, hipStream_t st) {
-  if (!s.blocks.empty()) {
+int launch_rest(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, float* rest, hipStream_t st, const CompactState* snap) {
+  if (!s.blocks.empty()) {                                     // (never with a snapshot: its entry points refuse such slots)
     // kept `-relation` blocks: the partial sums of the main rows, plus -- through the mappings -- those of the block rows
     // (every block row is evaluated once, however many main rows use it), then rest = c + 0.5 * sum_f S_f^2
     if (row0 != 0 || n != s.n_rows) return fail(h, FMX_E_ARG, "rows with kept blocks are predicted as a whole");
@@ -184,15 +185,15 @@ int launch_rest(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, float* r
     if (rc) return rc;
     float* S = h->partial;
     float* c = S + (size_t)n * h->KP;
-    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false>), n, st, s.ent, s.row_ptr, (uint64_t)0, n, h->tb, h->cfg.k1, S, c, (const float*)nullptr));
+    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false>), n, st, s.ent, s.row_ptr, (uint64_t)0, n, RowsF32{h->tb}, h->cfg.k1, S, c));
     for (BlockRows* br : s.blocks) {
       const uint32_t B = br->rows.n_rows;
       if (!B) continue;
       Tab tb = h->tb;                                        // the block's attribute 0 is global attribute attr_offset
       tb.V += (size_t)br->attr_offset * tb.rs; tb.w += (size_t)br->attr_offset * tb.ws;
       float* Sb = br->pbuf;
-      KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false>), B, st, br->rows.ent, br->rows.row_ptr, (uint64_t)0, B, tb, h->cfg.k1,
-                                         Sb, Sb + (size_t)B * h->KP, (const float*)nullptr));
+      KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false>), B, st, br->rows.ent, br->rows.row_ptr, (uint64_t)0, B, RowsF32{tb}, h->cfg.k1,
+                                         Sb, Sb + (size_t)B * h->KP));
       KP_SWITCH(h->KP, hipLaunchKernelGGL((k_rel_add_partial<KP>), dim3(std::min<uint32_t>((uint32_t)(((uint64_t)n * (h->KP + 1) + 255) / 256), 4096)),
                                             dim3(256), 0, st, br->map, (uint64_t)0, n, B, (const float*)Sb, S));
     }
@@ -204,9 +205,57 @@ int launch_rest(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, float* r
   // the linear weights come out of the slot's side stream where it is current (it is after a one-pass epoch on THIS slot that kept it,
   // and until anything else touches w): 4 coalesced bytes per entry instead of a 64-byte fabric request
   const float* ws = (s.wside && s.wside_version == h->w_version && h->cfg.shard_world == 1) ? s.wside : nullptr;
-  KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, false, true>), n, st,
-                                     s.ent, s.row_ptr, row0, n, h->tb, h->cfg.k1, (float*)nullptr, rest, ws));
+  if (snap) { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, false, true, RowsBf16>), n, st,
+                                                 s.ent, s.row_ptr, row0, n, compact_rows(h, *snap), h->cfg.k1, (float*)nullptr, rest)); }
+  else { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, false, true>), n, st,
+                                            s.ent, s.row_ptr, row0, n, RowsF32{h->tb, ws}, h->cfg.k1, (float*)nullptr, rest)); }
   HIPCHK(h, hipGetLastError());
+  return FMX_OK;
+}
+
+int slot_scores(fmx_handle h, const Slot& s, const CompactState* snap, bool want_yhat, const float** score) {
+  int rc = ensure_scratch(h, 0, (size_t)s.n_rows * 2); if (rc) return rc;
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  rc = launch_rest(h, s, 0, s.n_rows, h->rest, h->stream, snap); if (rc) return rc;
+  *score = h->rest;
+  if (!want_yhat) return FMX_OK;
+  float* yhat = h->rest + s.n_rows;
+  const int k0 = (h->cfg.shard_world > 1 && h->cfg.shard_rank != 0) ? 0 : h->cfg.k0;
+  hipLaunchKernelGGL(k_yhat, dim3(std::min<uint32_t>((s.n_rows + 255) / 256, 2048)), dim3(256), 0, h->stream,
+                     h->rest, s.n_rows, k0, snap ? snap->w0 : h->w0, yhat);
+  HIPCHK(h, hipGetLastError());
+  *score = yhat;
+  return FMX_OK;
+}
+
+int predict_out(fmx_handle h, const Slot& s, const CompactState* snap, double* out) {
+  if (s.n_rows == 0) return FMX_OK;
+  const float* yhat;
+  const int rc = slot_scores(h, s, snap, true, &yhat); if (rc) return rc;
+  std::vector<float> tmp(s.n_rows);
+  HIPCHK(h, hipMemcpyAsync(tmp.data(), yhat, (size_t)s.n_rows * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (uint32_t r = 0; r < s.n_rows; r++) out[r] = (double)tmp[r];
+  return FMX_OK;
+}
+
+int evaluate_out(fmx_handle h, const Slot& s, const CompactState* snap, fmx_eval* out) {
+  const float* rest;
+  const int rc = slot_scores(h, s, snap, false, &rest); if (rc) return rc;
+  HIPCHK(h, hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));
+  hipLaunchKernelGGL(k_eval, dim3(std::min<uint32_t>((s.n_rows + 255) / 256, 2048)), dim3(256), 0, h->stream,
+                     rest, s.target, s.n_rows, make_hyper(h->cfg), snap ? snap->w0 : h->w0, h->acc);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  double acc[4];
+  HIPCHK(h, hipMemcpyAsync(acc, h->acc, sizeof(acc), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  out->device_seconds = ms * 1e-3;
+  out->rmse = std::sqrt(acc[0] / s.n_rows);          // fm_learn.h:152
+  out->mae = acc[1] / s.n_rows;                      // fm_learn.h:148
+  out->accuracy = acc[2] / s.n_rows;                 // fm_learn.h:129
   return FMX_OK;
 }
 
@@ -1006,23 +1055,10 @@ int fmx_get_param_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double
     if (ids[i] >= h->cfg.num_attribute) return fail(h, FMX_E_ARG, "feature id %u >= num_attribute", ids[i]);
     if (!sh.owns(ids[i])) return fail(h, FMX_E_ARG, "feature id %u is not on this shard", ids[i]);
   }
-  HIPCHK(h, hipSetDevice(h->device));
-  uint32_t* d_ids = nullptr; double* d_out = nullptr;
-  const size_t nout = (size_t)count * (size_t)(k + 1);
-  HIPCHK(h, fmx_dev_alloc(&d_ids, (size_t)count * 4));
-  HIPCHK(h, fmx_dev_alloc(&d_out, nout * sizeof(double)));
-  hipError_t er = hipMemcpyAsync(d_ids, ids, (size_t)count * 4, hipMemcpyHostToDevice, h->stream);
-  if (er == hipSuccess) {
-    hipLaunchKernelGGL(k_fetch_rows, dim3((uint32_t)((nout + 255) / 256)), dim3(256), 0, h->stream, d_ids, count, k,
-                       sh, h->tb, d_out, d_out + count);
-    er = hipGetLastError();
-  }
-  if (er == hipSuccess) er = hipMemcpyAsync(w_out, d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-  if (er == hipSuccess && k > 0) er = hipMemcpyAsync(v_out, d_out + count, (size_t)count * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-  if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
-  fmx_dev_free(d_ids); fmx_dev_free(d_out);
-  if (er != hipSuccess) return fail(h, FMX_E_HIP, "fmx_get_param_rows: %s", hipGetErrorString(er));
-  return FMX_OK;
+  double* const outs[1][2] = {{w_out, v_out}};
+  return gather_rows(h, "fmx_get_param_rows", ids, count, 1, outs, [&](int, dim3 grid, const uint32_t* d_ids, double* d_w, double* d_v) {
+    hipLaunchKernelGGL(k_fetch_rows<RowsF32>, grid, dim3(256), 0, h->stream, d_ids, count, k, sh, RowsF32{h->tb}, d_w, d_v);
+  });
 }
 
 // ---- fm_model::saveModel / loadModel (fm_model.h:132-190) straight from / into the device table ----------------------
@@ -1584,32 +1620,15 @@ int fmx_synth_rows_ex(fmx_handle h, int slot, uint64_t seed, uint64_t row0, uint
 // predict / evaluate
 // ---------------------------------------------------------------------------------------------
 int fmx_predict(fmx_handle h, int slot, double* out) {
-  int rc = check_slot(h, slot, false);
-  if (rc) return rc;
+  int rc = check_slot(h, slot, false); if (rc) return rc;
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   if (!out) return fail(h, FMX_E_ARG, "fmx_predict: out is NULL");
   HIPCHK(h, hipSetDevice(h->device));
-  const Slot& s = h->slots[slot];
-  if (s.n_rows == 0) return FMX_OK;
-  rc = ensure_scratch(h, 0, (size_t)s.n_rows * 2);
-  if (rc) return rc;
-  rc = launch_rest(h, s, 0, s.n_rows, h->rest, h->stream);
-  if (rc) return rc;
-  float* yhat = h->rest + s.n_rows;
-  const int k0 = (h->cfg.shard_world > 1) ? (h->cfg.shard_rank == 0 ? h->cfg.k0 : 0) : h->cfg.k0;
-  hipLaunchKernelGGL(k_yhat, dim3(std::min<uint32_t>((s.n_rows + 255) / 256, 2048)), dim3(256), 0, h->stream,
-                     h->rest, s.n_rows, k0, h->w0, yhat);
-  HIPCHK(h, hipGetLastError());
-  std::vector<float> tmp(s.n_rows);
-  HIPCHK(h, hipMemcpyAsync(tmp.data(), yhat, (size_t)s.n_rows * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  for (uint32_t r = 0; r < s.n_rows; r++) out[r] = (double)tmp[r];
-  return FMX_OK;
+  return predict_out(h, h->slots[slot], nullptr, out);
 }
 
 int fmx_evaluate(fmx_handle h, int slot, fmx_eval* out) {
-  int rc = check_slot(h, slot, true);
-  if (rc) return rc;
+  int rc = check_slot(h, slot, true); if (rc) return rc;
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   if (!out) return fail(h, FMX_E_ARG, "fmx_evaluate: out is NULL");
   if (h->cfg.shard_world > 1) return fail(h, FMX_E_UNSUPPORTED, "fmx_evaluate on a feature shard: use fmx_sgd_partial + all-reduce + fmx_predict_finish");
@@ -1618,27 +1637,8 @@ int fmx_evaluate(fmx_handle h, int slot, fmx_eval* out) {
   memset(out, 0, sizeof(*out));
   out->rows = s.n_rows;
   if (s.n_rows == 0) return FMX_OK;
-  rc = ensure_scratch(h, 0, (size_t)s.n_rows * 2);
-  if (rc) return rc;
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  rc = launch_rest(h, s, 0, s.n_rows, h->rest, h->stream);
-  if (rc) return rc;
-  HIPCHK(h, hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));
-  hipLaunchKernelGGL(k_eval, dim3(std::min<uint32_t>((s.n_rows + 255) / 256, 2048)), dim3(256), 0, h->stream,
-                     h->rest, s.target, s.n_rows, make_hyper(h->cfg), h->w0, h->acc);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  double acc[4];
-  HIPCHK(h, hipMemcpyAsync(acc, h->acc, sizeof(acc), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  float ms = 0;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  out->device_seconds = ms * 1e-3;
-  out->rmse = std::sqrt(acc[0] / s.n_rows);          // fm_learn.h:152
-  out->mae = acc[1] / s.n_rows;                      // fm_learn.h:148
-  out->accuracy = acc[2] / s.n_rows;                 // fm_learn.h:129
   if (s.wside && s.wside_version == h->w_version && s.blocks.empty()) out->flags |= FMX_EVAL_WSIDE;
-  return FMX_OK;
+  return evaluate_out(h, s, nullptr, out);
 }
 
 }  // extern "C"

@@ -1,31 +1,13 @@
 // fmx_evalq.hip -- fmx_set_row_queries / fmx_evaluate_by_query: the exact AUC inside every query of a slot (GAUC) on the device
-// (DESIGN.md section 16).  The scores come from launch_rest and the pooled metrics from eval_ex_scores, both fmx_evaluate_ex's
-// (fmx_eval.hip); the same scores then feed this unit's pipeline: 64-bit keys with the query id above the score, one radix sort,
-// three library scans, the segmented rank sum and the reduction over the queries (fmx_evalq_kernels.h).
+// (DESIGN.md section 16).  The scores come from slot_scores and the pooled metrics from eval_ex_scores, both fmx_evaluate_ex's
+// (fmx_eval.hip); the same scores then feed this unit's pipeline: 64-bit keys with the query id above the score, fmx_evaluate_ex's
+// sort and two scans (rank_sort_scan), a third scan for the query heads, the segmented rank sum and the reduction over the queries
+// (fmx_evalq_kernels.h).
 // The group entry points are in fmx_comm.hip, next to fmx_group_evaluate_ex.
 #include "fmx_internal.h"
 #include "fmx_evalq_kernels.h"
 
 #include <limits>
-
-namespace {
-
-// everything the by-query pipeline takes from the device: freed on every path out of evalq_scores
-struct QueryScratch {
-  unsigned long long* keys0 = nullptr; unsigned long long* keys1 = nullptr;   // the sort's key double buffer
-  uint32_t* negbefore = nullptr; uint32_t* runhead = nullptr; uint32_t* qhead = nullptr;
-  void* tmp = nullptr;                      // the larger of the sort's and the scans' temporaries
-  void* perq = nullptr;                     // [n_queries] num2 (8 bytes), then pos, neg (4 + 4)
-  void* part = nullptr;                     // block partials + results of the reduction over the queries
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~QueryScratch() {
-    fmx_dev_free(keys0); fmx_dev_free(keys1); fmx_dev_free(negbefore); fmx_dev_free(runhead); fmx_dev_free(qhead);
-    fmx_dev_free(tmp); fmx_dev_free(perq); fmx_dev_free(part);
-    for (auto e : ev) if (e) hipEventDestroy(e);
-  }
-};
-
-}  // namespace
 
 void evalq_zero_per_query(uint32_t n_queries, uint64_t* num2_q, uint32_t* pos_q, uint32_t* neg_q) {
   if (num2_q) memset(num2_q, 0, (size_t)n_queries * 8);
@@ -92,15 +74,11 @@ int evalq_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, ui
   while ((1ull << id_bits) < nq) id_bits++;                                    // ceil(log2(n_queries)): 0 .. 31
   const int key_bits = EVALQ_QID_SHIFT + id_bits;
   const uint32_t qblk = evalx_grid(nq);
-  QueryScratch sc;
+  EvalScratch sc;
   HIPCHK(h, fmx_dev_alloc(&sc.keys0, (size_t)n * 8));
-  HIPCHK(h, fmx_dev_alloc(&sc.keys1, (size_t)n * 8));
-  HIPCHK(h, fmx_dev_alloc(&sc.negbefore, (size_t)n * 4));
-  HIPCHK(h, fmx_dev_alloc(&sc.runhead, (size_t)n * 4));
   HIPCHK(h, fmx_dev_alloc(&sc.qhead, (size_t)n * 4));
   HIPCHK(h, fmx_dev_alloc(&sc.perq, (size_t)nq * 16));
   HIPCHK(h, fmx_dev_alloc(&sc.part, ((size_t)qblk * 8 + 8) * 8));            // [qblk][2] doubles, [qblk][6] counts, then 2 doubles and 6 counts
-  for (auto& e : sc.ev) HIPCHK(h, hipEventCreate(&e));
   unsigned long long* d_num2 = (unsigned long long*)sc.perq;
   uint32_t* d_pos = (uint32_t*)(d_num2 + nq);
   uint32_t* d_neg = d_pos + nq;
@@ -109,29 +87,18 @@ int evalq_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, ui
   double* dres = (double*)sc.part + (size_t)qblk * 8;
   unsigned long long* cres = (unsigned long long*)sc.part + (size_t)qblk * 8 + 2;
 
-  hipcub::DoubleBuffer<unsigned long long> db(sc.keys0, sc.keys1);
-  typedef hipcub::TransformInputIterator<uint32_t, EvalxIsNeg, const unsigned long long*> NegIt;
-  typedef hipcub::TransformInputIterator<uint32_t, EvalxHead, hipcub::CountingInputIterator<uint32_t>> HeadIt;
   typedef hipcub::TransformInputIterator<uint32_t, EvalqQHead, hipcub::CountingInputIterator<uint32_t>> QHeadIt;
   const hipcub::CountingInputIterator<uint32_t> pos0(0);
-  size_t b_sort = 0, b_sum = 0, b_max = 0, b_qmax = 0;
-  HIPCHK(h, hipcub::DeviceRadixSort::SortKeys(nullptr, b_sort, db, (int)n, 0, key_bits, h->stream));
-  HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, b_sum, NegIt(sc.keys0, EvalxIsNeg()), sc.negbefore, (int)n, h->stream));
-  HIPCHK(h, hipcub::DeviceScan::InclusiveScan(nullptr, b_max, HeadIt(pos0, EvalxHead{sc.keys0}), sc.runhead, hipcub::Max(), (int)n, h->stream));
+  size_t b_qmax = 0;
   HIPCHK(h, hipcub::DeviceScan::InclusiveScan(nullptr, b_qmax, QHeadIt(pos0, EvalqQHead{sc.keys0}), sc.qhead, hipcub::Max(), (int)n, h->stream));
-  size_t b_tmp = std::max(std::max(b_sort, b_sum), std::max(b_max, b_qmax));
-  HIPCHK(h, fmx_dev_alloc(&sc.tmp, std::max<size_t>(b_tmp, 16)));
-
   hipLaunchKernelGGL(k_evalq_keys, dim3(evalx_grid(n)), dim3(256), 0, h->stream, score, (const float*)s.target, (const uint32_t*)s.qid, n,
                      make_hyper(h->cfg), add_w0, (const double*)h->w0, sc.keys0);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemsetAsync(sc.perq, 0, (size_t)nq * 16, h->stream));
-  HIPCHK(h, hipEventRecord(sc.ev[0], h->stream));
-  HIPCHK(h, hipcub::DeviceRadixSort::SortKeys(sc.tmp, b_tmp, db, (int)n, 0, key_bits, h->stream));
-  const unsigned long long* ks = db.Current();
-  HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(sc.tmp, b_tmp, NegIt(ks, EvalxIsNeg()), sc.negbefore, (int)n, h->stream));
-  HIPCHK(h, hipcub::DeviceScan::InclusiveScan(sc.tmp, b_tmp, HeadIt(pos0, EvalxHead{ks}), sc.runhead, hipcub::Max(), (int)n, h->stream));
-  HIPCHK(h, hipcub::DeviceScan::InclusiveScan(sc.tmp, b_tmp, QHeadIt(pos0, EvalqQHead{ks}), sc.qhead, hipcub::Max(), (int)n, h->stream));
+  const unsigned long long* ks;
+  rc = rank_sort_scan(h, sc, sc.keys0, n, key_bits, b_qmax, &ks);            // (rank_seconds starts at its sort, as fmx_evaluate_ex's does)
+  if (rc) return rc;
+  HIPCHK(h, hipcub::DeviceScan::InclusiveScan(sc.tmp, sc.tmp_bytes, QHeadIt(pos0, EvalqQHead{ks}), sc.qhead, hipcub::Max(), (int)n, h->stream));
   hipLaunchKernelGGL(k_evalq_ranksum, dim3(evalx_grid(n)), dim3(256), 0, h->stream, ks, (const uint32_t*)sc.negbefore, (const uint32_t*)sc.runhead,
                      (const uint32_t*)sc.qhead, n, d_num2, d_pos, d_neg);
   hipLaunchKernelGGL(k_evalq_final, dim3(qblk), dim3(256), 0, h->stream, (const unsigned long long*)d_num2, (const uint32_t*)d_pos,
@@ -188,14 +155,12 @@ int fmx_evaluate_by_query(fmx_handle h, int slot, const fmx_eval_opts* opts, fmx
     evalq_zero_per_query(s.n_queries, num2_q, pos_q, neg_q);
     return FMX_OK;
   }
-  rc = ensure_scratch(h, 0, (size_t)s.n_rows * 2);
-  if (rc) return rc;
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  rc = launch_rest(h, s, 0, s.n_rows, h->rest, h->stream);
+  const float* rest;
+  rc = slot_scores(h, s, nullptr, false, &rest);
   if (rc) return rc;
   const uint32_t flags = (s.wside && s.wside_version == h->w_version && s.blocks.empty()) ? FMX_EVAL_WSIDE : 0u;
   out->pooled.flags = flags;
-  return evalq_scores(h, s, h->rest, 1, link, out, num2_q, pos_q, neg_q);
+  return evalq_scores(h, s, rest, 1, link, out, num2_q, pos_q, neg_q);
 }
 
 }  // extern "C"

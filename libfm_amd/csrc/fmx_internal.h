@@ -7,6 +7,7 @@
 #pragma GCC visibility pop
 #include "fmx_kernels.h"
 #include "fmx_als_kernels.h"
+#include "fmx_compact_kernels.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -267,7 +268,18 @@ int check_slot(fmx_handle h, int slot, bool need_target);
 int slot_in_session(fmx_handle h, int slot, const char* what);
 void free_segments(Slot& s);
 void free_slot(Slot& s);
-int launch_rest(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, float* rest, hipStream_t st);
+// fmx_core.hip, the read side.  snap names the rows' source everywhere: nullptr = the model (h->tb, h->w0, the slot's side stream where
+// it is current), else the bf16 snapshot (its tables, its w0).
+int launch_rest(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, float* rest, hipStream_t st, const CompactState* snap = nullptr);
+// the scores of all n_rows >= 1 rows of a slot, on h->stream and in h->rest: ensure_scratch, h->ev0 (where the call's device work begins),
+// the rest pass, and *score = rest (y-hat minus the bias: the reductions add it, add_w0 = 1) or, with want_yhat, the finished y-hat
+// (the source's own bias; on a feature shard rank 0 alone adds it)
+int slot_scores(fmx_handle h, const Slot& s, const CompactState* snap, bool want_yhat, const float** score);
+// fmx_predict / fmx_evaluate after their checks, for the snapshot's entry points too: slot_scores, then the y-hat to the host /
+// k_eval with the source's bias to rmse, mae, accuracy and device_seconds (n_rows >= 1; predict_out takes an empty slot too)
+int predict_out(fmx_handle h, const Slot& s, const CompactState* snap, double* out);
+int evaluate_out(fmx_handle h, const Slot& s, const CompactState* snap, fmx_eval* out);
+inline RowsBf16 compact_rows(fmx_handle h, const CompactState& c) { return RowsBf16{CTab{c.V, c.w, h->tb.rs}}; }
 int ensure_segments(fmx_handle h, Slot& s, uint32_t B);                 // fmx_sgd.hip
 int ensure_coll_mass(fmx_handle h, Slot& s);                             // fmx_core.hip
 int ensure_wside(fmx_handle h, Slot& s);                                 // fmx_core.hip
@@ -280,27 +292,31 @@ constexpr uint32_t FMX_SIDE_STREAM_BATCH = 32768u;
 // a batch of the bias-lag schedule small enough for the in-stream forms (+ short rows: step_plan; + the group driver's own terms: its exchange)
 inline bool sgd_in_stream_batch(uint32_t batch, uint32_t flags) { return batch != 0 && batch < FMX_SIDE_STREAM_BATCH && (flags & FMX_FLAG_BIAS_LAG); }
 int sgd_resolve_batch(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, fmx_batch_info* bi);   // fmx_sgd.hip: + the shards' shares
-int sgd_partial_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n_rows, float* S, float* c, hipStream_t st);   // fmx_sgd.hip
+int sgd_partial_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n_rows, float* S, float* c, hipStream_t st,
+                     const CompactState* snap = nullptr);                // fmx_sgd.hip (snap: as launch_rest)
 constexpr size_t PREP_RAW_FLOATS = size_t(1) << 24;                      // prep_rows: raw partial sums of one piece of rows (64 MiB)
-// fmx_topk.hip: the [rows][KM] factor sums and scalars of section 11.  snap: the rows' source -- nullptr = the model (h->tb, h->w0),
-// else the bf16 snapshot (its rows through compact_partial_rows, its w0)
+// fmx_topk.hip: the [rows][KM] factor sums and scalars of section 11 (snap: as launch_rest)
 int prep_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, int k0, float* raw, size_t raw_rows, int KM,
               float* S_out, float* scal, hipStream_t st, const CompactState* snap = nullptr);
 // fmx_topk.hip: fmx_topk after the handle check, for fmx_compact_topk too (`who` names the entry point in messages; snap as above)
 int topk_impl(fmx_handle h, const char* who, int query_slot, int cand_slot, const fmx_topk_opts* opts, uint32_t* idx_out, double* score_out,
               fmx_topk_stats* stats, const CompactState* snap);
-// fmx_compact.hip: sgd_partial_rows from the snapshot (k_rowsums_c<KP, true, false>), and the snapshot's release
-int compact_partial_rows(fmx_handle h, const CompactState& snap, const Slot& s, uint64_t row0, uint32_t n_rows, float* S, float* c, hipStream_t st);
-void compact_free(fmx_handle h);
+void compact_free(fmx_handle h);                                         // fmx_compact.hip
 int lag_flush(fmx_handle h);                                             // fmx_sgd.hip
 // fmx_eval.hip: the argument checks, the empty result and the reduction of fmx_evaluate_ex, shared with fmx_group_evaluate_ex (fmx_comm.hip)
 int eval_ex_check_opts(fmx_handle h, const char* who, const fmx_eval_opts* opts, uint32_t* link);
 int eval_ex_check_slot(fmx_handle h, const char* who, int slot);
 void eval_ex_empty(fmx_eval_ex* out);
 int eval_ex_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, uint32_t link, fmx_eval_ex* out);
-// ... and its rank pipeline (sort, two scans, rank sum) over keys of any width, shared with fmx_post_evaluate_ex (fmx_post.hip)
+// ... its rank pipeline (sort, two scans, rank sum) over keys of any width and the finish of an fmx_eval_ex from reduced sums and
+// counts, shared with fmx_post_evaluate_ex (fmx_post.hip); the sort and the two scans alone, shared with evalq_scores (fmx_evalq.hip)
+struct EvalScratch;
+int rank_sort_scan(fmx_handle h, EvalScratch& sc, unsigned long long* keys, uint32_t n, int key_bits, size_t b_more,
+                   const unsigned long long** sorted);
 int eval_ex_rank(fmx_handle h, unsigned long long* keys, uint32_t n, int key_bits, unsigned long long* d_num2, uint64_t* num2,
                  double* rank_seconds);
+int eval_ex_finish(fmx_handle h, uint32_t n, const double* d, uint64_t pos, uint64_t nan_rows, uint64_t correct,
+                   unsigned long long* keys, int key_bits, unsigned long long* d_num2, fmx_eval_ex* out);
 // fmx_evalq.hip: the checks, the empty result and the whole reduction of fmx_evaluate_by_query (pooled metrics through eval_ex_scores,
 // then the by-query pipeline over the same scores), shared with fmx_group_evaluate_by_query (fmx_comm.hip)
 int set_row_queries_impl(fmx_handle h, const char* who, int slot, const uint32_t* qid, uint32_t n_queries);
@@ -360,12 +376,53 @@ hipError_t fmx_dev_alloc_bytes(void** p, size_t bytes);                  // fmx_
 hipError_t fmx_dev_free(void* p);                                        // fmx_core.hip
 template <class T> inline hipError_t fmx_dev_alloc(T** p, size_t bytes) { return fmx_dev_alloc_bytes(reinterpret_cast<void**>(p), bytes); }
 
-#define HIPCHK(h, expr)                                                                         \
+// everything a call of the exact metrics (fmx_eval.hip, fmx_evalq.hip) takes from the device, freed on every path out of the call:
+// each function allocates the members it uses and the others stay null
+struct EvalScratch {
+  void* part = nullptr;                     // block partials + results
+  unsigned long long* keys0 = nullptr; unsigned long long* keys1 = nullptr;   // the keys and the sort's second buffer
+  uint32_t* negbefore = nullptr; uint32_t* runhead = nullptr; uint32_t* qhead = nullptr;
+  void* tmp = nullptr; size_t tmp_bytes = 0;   // the larger of the sort's and the scans' temporaries
+  void* perq = nullptr;                     // [n_queries] num2 (8 bytes), then pos, neg (4 + 4)
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~EvalScratch() {
+    fmx_dev_free(part); fmx_dev_free(keys0); fmx_dev_free(keys1); fmx_dev_free(negbefore); fmx_dev_free(runhead); fmx_dev_free(qhead);
+    fmx_dev_free(tmp); fmx_dev_free(perq);
+    for (auto e : ev) if (e) hipEventDestroy(e);
+  }
+};
+
+#define HIPCHK(h, expr)                                                                        \
   do {                                                                                          \
     hipError_t _e = (expr);                                                                     \
     if (_e != hipSuccess)                                                                       \
       return fail((h), FMX_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
   } while (0)
+
+// The gather of rows by feature id (fmx_get_param_rows, the optimisers' state rows, fmx_compact_get_rows) from nt tables, one after the
+// other: the ids go up once; launch(t, grid, d_ids, d_w, d_v) starts table t's k_fetch_rows on h->stream, and its w and v parts come back
+// to outs[t] = {w_out, v_out}.  Checks nothing about the ids, returns with the stream drained, frees both device buffers on every path;
+// count >= 1.
+template <class Launch>
+int gather_rows(fmx_handle h, const char* who, const uint32_t* ids, uint32_t count, int nt, double* const (*outs)[2], Launch launch) {
+  const int k = h->cfg.num_factor;
+  HIPCHK(h, hipSetDevice(h->device));
+  uint32_t* d_ids = nullptr; double* d_out = nullptr;
+  const size_t nout = (size_t)count * (size_t)(k + 1);
+  HIPCHK(h, fmx_dev_alloc(&d_ids, (size_t)count * 4));
+  hipError_t er = fmx_dev_alloc(&d_out, nout * sizeof(double));
+  if (er == hipSuccess) er = hipMemcpyAsync(d_ids, ids, (size_t)count * 4, hipMemcpyHostToDevice, h->stream);
+  for (int t = 0; t < nt && er == hipSuccess; t++) {
+    launch(t, dim3((uint32_t)((nout + 255) / 256)), (const uint32_t*)d_ids, d_out, d_out + count);
+    er = hipGetLastError();
+    if (er == hipSuccess) er = hipMemcpyAsync(outs[t][0], d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (er == hipSuccess && k > 0) er = hipMemcpyAsync(outs[t][1], d_out + count, (size_t)count * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
+  }
+  fmx_dev_free(d_ids); fmx_dev_free(d_out);
+  if (er != hipSuccess) return fail(h, FMX_E_HIP, "%s: %s", who, hipGetErrorString(er));
+  return FMX_OK;
+}
 
 // wave-per-example grids: 4 waves per 256-thread block, capped so that the launch is >> 256 workgroups
 // but grid-strides the rest (guide: memory-bound ops, 256 CUs x 8 blocks).

@@ -413,15 +413,36 @@ static __global__ void k_handoff_arm(double* W, uint32_t n) {         // W[1 .. 
 //   sq      : this lane's share of  sum_f sum_i (v x)^2
 //   lin     : this lane's share of  sum_i w[id_i] x_i
 // ----------------------------------------------------------------------------------------------
-// wside (optional): the row's slice of the slot's WEIGHT SIDE STREAM -- wside[i] is either w[id_i] as it stands or NaN ("gather it").
+// The rows come from a ROW SOURCE, which supplies
+//   Lanes<KP>            the lane map (VEC, LPR, EPI) and U, the load rounds in flight
+//   ld<VEC>(id, off, out) VEC factors of row id from element offset off, zeros beyond the row's rs elements
+//   lin(id, i0, i)       the linear weight of entry i0 + i of the slot's stream, whose feature is id
+//   w1(row), v1(row, f)  one weight / one factor (k_fetch_rows)
+// RowsF32 is the model (Tab); RowsBf16 (fmx_compact_kernels.h) the bf16 snapshot.  The sums, their order and what k_rowsums does with
+// them are written once, here.
+// wside (optional): the slot's WEIGHT SIDE STREAM -- wside[i] is either w[id_i] as it stands or NaN ("gather it").
 // A 4-byte w_j out of its own array costs a 64-byte fabric request per entry (a third of a predict pass's requests for 1.5 % of its
 // bytes); the stream costs 4 coalesced bytes.  Maintained by k_fused<EXACT> for the entries that are the LAST occurrence of their
 // feature in the slot and are updated by their own example (FMX_FLAG_KEEP_WSIDE; fmx_sgd.hip), NaN for everything else.
-template <int KP, int U>
-__device__ __forceinline__ void row_sums(const Entry* __restrict__ ent, uint32_t size,
-                                         const Tab tb, int k1,
-                                         float (&sum)[Map<KP>::VEC], float& sq, float& lin, const float* __restrict__ wside = nullptr) {
-  constexpr int VEC = Map<KP>::VEC, LPR = Map<KP>::LPR, EPI = Map<KP>::EPI;
+struct RowsF32 {
+  template <int KP> struct Lanes : Map<KP> { static constexpr int U = 8; };
+  Tab tb; const float* wside = nullptr;
+  template <int VEC> __device__ __forceinline__ void ld(size_t id, uint32_t off, float (&out)[VEC]) const { row_ld<VEC, 4>(tb, id, off, out); }
+  __device__ __forceinline__ float w1(size_t row) const { return load_w(tb.w + row * tb.ws); }
+  __device__ __forceinline__ float v1(size_t row, int f) const { return tb.V[row * tb.rs + f]; }
+  __device__ __forceinline__ float lin(uint32_t id, uint64_t i0, uint32_t i) const {
+    float wv = wside ? __builtin_nontemporal_load(wside + i0 + i) : __builtin_nanf("");
+    if (wv != wv) wv = w1((size_t)id);
+    return wv;
+  }
+};
+
+// i0: where the row's first entry stands in the slot's stream (the side stream's index)
+template <int KP, class Src>
+__device__ __forceinline__ void row_sums(const Entry* __restrict__ ent, uint32_t size, const Src src, int k1,
+                                         float (&sum)[Src::template Lanes<KP>::VEC], float& sq, float& lin, uint64_t i0 = 0) {
+  typedef typename Src::template Lanes<KP> L;
+  constexpr int VEC = L::VEC, LPR = L::LPR, EPI = L::EPI, U = L::U;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t g = lane / LPR, f = lane % LPR;
 #pragma unroll
@@ -432,11 +453,7 @@ __device__ __forceinline__ void row_sums(const Entry* __restrict__ ent, uint32_t
     Entry e; e.id = 0; e.value = 0.f;
     if (lane < cnt) {
       e = load_stream8(ent + base + lane);
-      if (k1) {
-        float wv = wside ? __builtin_nontemporal_load(wside + base + lane) : __builtin_nanf("");
-        if (wv != wv) wv = load_w(tb.w + (size_t)e.id * tb.ws);
-        lin += wv * e.value;
-      }
+      if (k1) lin += src.lin(e.id, i0, base + lane) * e.value;
     }
     for (uint32_t i = 0; i < cnt; i += EPI * U) {
       float vr[U][VEC]; float xs[U];
@@ -446,7 +463,7 @@ __device__ __forceinline__ void row_sums(const Entry* __restrict__ ent, uint32_t
         const uint32_t id = bcast_u32<EPI>(e.id, idx & 63u);
         xs[u] = bcast_f32<EPI>(e.value, idx & 63u);
         if (idx < cnt) {
-          row_ld<VEC, 4>(tb, (size_t)id, f * VEC, vr[u]);
+          src.template ld<VEC>((size_t)id, f * VEC, vr[u]);
         } else {
           xs[u] = 0.f;
 #pragma unroll
@@ -520,14 +537,14 @@ __device__ __forceinline__ void row_apply(const Entry* __restrict__ ent, uint32_
 //   S[e][0..KP)           (WRITE_S)  the (partial) factor sums
 //   scal[e]               FINISH ? rest_e = lin + 0.5*(sum_f S_ef^2 - Q_e)   (single device)
 //                                : c_e    = lin - 0.5*Q_e                    (feature shard; all-reduced later)
-// Used by predict / evaluate (WRITE_S = false, FINISH = true) and by the minibatch step.
+// Used by predict / evaluate (WRITE_S = false, FINISH = true) and by the minibatch step; from the bf16 snapshot with Src = RowsBf16.
+// No LDS, no atomics.
 // ----------------------------------------------------------------------------------------------
-template <int KP, bool WRITE_S, bool FINISH>
+template <int KP, bool WRITE_S, bool FINISH, class Src = RowsF32>
 __global__ void __launch_bounds__(256)
 k_rowsums(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, uint64_t row0, uint32_t n_rows,
-          const Tab tb, int k1,
-          float* __restrict__ S, float* __restrict__ scal, const float* __restrict__ wside) {
-  constexpr int VEC = Map<KP>::VEC, LPR = Map<KP>::LPR;
+          const Src src, int k1, float* __restrict__ S, float* __restrict__ scal) {
+  constexpr int VEC = Src::template Lanes<KP>::VEC, LPR = Src::template Lanes<KP>::LPR;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave0 = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
   const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
@@ -535,7 +552,7 @@ k_rowsums(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, u
     const uint64_t a = row_ptr[row0 + e];
     const uint32_t size = (uint32_t)(row_ptr[row0 + e + 1] - a);
     float sum[VEC], sq, lin;
-    row_sums<KP, 8>(ent + a, size, tb, k1, sum, sq, lin, wside ? wside + a : nullptr);
+    row_sums<KP>(ent + a, size, src, k1, sum, sq, lin, a);
 #pragma unroll
     for (int v = 0; v < VEC; v++) sum[v] = subgroup_allsum<LPR>(sum[v]);
     if (WRITE_S && lane < LPR) store_vec<VEC>(S + (size_t)e * KP + lane * VEC, sum);
@@ -2051,7 +2068,7 @@ k_fused(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, con
     } else if constexpr (!APPLY) {                             // (APPLY: such a row is deferred as a whole, cm == ~0)
       if (w0_late) { w0s = (float)handoff_wait(w0_ptr, w0u, handoff_err, &w0_bad); w0_late = false; }
       float sum[VEC], sq, lin;
-      row_sums<KP, 8>(row, size, tb, h.k1, sum, sq, lin);
+      row_sums<KP>(row, size, RowsF32{tb}, h.k1, sum, sq, lin);
 #pragma unroll
       for (int v = 0; v < VEC; v++) sum[v] = subgroup_allsum<LPR>(sum[v]);
       float part = lin - 0.5f * sq;
@@ -2406,14 +2423,16 @@ static __global__ void k_w_out(double* __restrict__ stage, uint64_t j0, uint32_t
   if (sh.place((uint32_t)(j0 + t), &jl)) stage[t] = (double)tb.w[(size_t)jl * tb.ws];
 }
 
-static __global__ void k_fetch_rows(const uint32_t* __restrict__ ids, uint32_t count, int k, Shard sh, Tab tb,
+// rows named by feature id out of a row source (RowsF32: the model or a state table; RowsBf16: the snapshot, dequantised)
+template <class Src>
+__global__ void k_fetch_rows(const uint32_t* __restrict__ ids, uint32_t count, int k, Shard sh, Src src,
                              double* __restrict__ w_out, double* __restrict__ v_out) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (uint64_t)count * (uint64_t)(k + 1)) return;
   const uint32_t i = (uint32_t)(t / (k + 1)); const int f = (int)(t % (k + 1));
   const size_t jl = sh.local(ids[i]);
-  if (f == k) w_out[i] = (double)tb.w[jl * tb.ws];
-  else v_out[(size_t)i * k + f] = (double)tb.V[jl * tb.rs + f];
+  if (f == k) w_out[i] = (double)src.w1(jl);
+  else v_out[(size_t)i * k + f] = (double)src.v1(jl, f);
 }
 
 // counter-hash helpers: identical definitions in oracle/fm_oracle.c (fmo_synth_id, ...)

@@ -1,7 +1,7 @@
 // fmx_post.hip -- the posterior accumulator of a slot (include/fmx.h "fmx_post_*"): the three prediction
-// vectors of fm_learn_mcmc_simultaneous on the device.  The scores come from launch_rest like fmx_evaluate_ex's; one fused pass
+// vectors of fm_learn_mcmc_simultaneous on the device.  The scores come from slot_scores like fmx_evaluate_ex's; one fused pass
 // (k_post_accum) adds the draw and carries the reference's metrics of all three vectors; fmx_post_evaluate_ex builds 64-bit keys of
-// one vector's means (k_post_key) and hands them to the rank pipeline of fmx_evaluate_ex (eval_ex_rank, fmx_eval.hip).
+// one vector's means (k_post_key) and hands them and its counts to the finish of fmx_evaluate_ex (eval_ex_finish, fmx_eval.hip).
 // The group entry points are in fmx_comm.hip, next to fmx_group_evaluate_ex.
 #include "fmx_internal.h"
 #include "fmx_post_kernels.h"
@@ -171,27 +171,8 @@ int post_evaluate_impl(fmx_handle h, const char* who, int slot, uint32_t which, 
   HIPCHK(h, hipMemcpyAsync(&res, dres, sizeof(res), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));                        // the counts decide whether anything is sorted
   out->rows = n; out->nan_rows = res.c[1];
-  if (!cls) {
-    out->rmse = std::sqrt(res.d[0] / n);
-    out->mae = res.d[1] / n;
-  } else {
-    if (res.c[3]) return fail(h, FMX_E_STATE, "%s: %llu means lie below +0 (their bit patterns do not order them)", who, res.c[3]);
-    out->pos = res.c[0]; out->neg = n - res.c[0]; out->correct = res.c[2];
-    out->accuracy = (double)out->correct / n;
-    if (out->nan_rows == 0) out->logloss = res.d[2] / n;
-  }
-  if (cls && out->nan_rows == 0 && out->pos != 0 && out->neg != 0) {   // (one class only: the numerator is 0 and the AUC NaN without a sort)
-    rc = eval_ex_rank(h, sc.keys, n, 64, cres + 4, &out->auc_num2, &out->rank_seconds);
-    if (rc) return rc;
-    out->auc = (double)out->auc_num2 / (2.0 * (double)out->pos * (double)out->neg);
-  } else {
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipEventSynchronize(h->ev1));
-  }
-  float ms = 0;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  out->device_seconds = ms * 1e-3;
-  return FMX_OK;
+  if (cls && res.c[3]) return fail(h, FMX_E_STATE, "%s: %llu means lie below +0 (their bit patterns do not order them)", who, res.c[3]);
+  return eval_ex_finish(h, n, res.d, res.c[0], res.c[1], res.c[2], sc.keys, 64, cres + 4, out);
 }
 
 int post_get_impl(fmx_handle h, const char* who, int slot, uint32_t which, double* out, uint64_t* draws) {
@@ -250,14 +231,12 @@ int fmx_post_accumulate(fmx_handle h, int slot, fmx_post_stats* out) {
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   HIPCHK(h, hipSetDevice(h->device));
   Slot& s = h->slots[slot];
+  const float* rest = nullptr;
   if (s.n_rows) {
-    rc = ensure_scratch(h, 0, (size_t)s.n_rows * 2);
-    if (rc) return rc;
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    rc = launch_rest(h, s, 0, s.n_rows, h->rest, h->stream);
+    rc = slot_scores(h, s, nullptr, false, &rest);
     if (rc) return rc;
   }
-  return post_accum_scores(h, s, h->rest, 1, out);
+  return post_accum_scores(h, s, rest, 1, out);
 }
 
 int fmx_post_evaluate_ex(fmx_handle h, int slot, uint32_t which, fmx_eval_ex* out) {

@@ -105,15 +105,21 @@ int fmx_sgd_partial(fmx_handle h, int slot, uint64_t row0, uint32_t n_rows, floa
 
 // a run of rows of a batch into the batch's partial buffer (S: [batch rows][KP], c: [batch rows]) -- the chunked exchange of
 // fmx_group_sgd_epoch enqueues the all-reduce of one run while the next one is being summed
-extern "C++" int sgd_partial_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n_rows, float* S, float* c, hipStream_t st) {
+extern "C++" int sgd_partial_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n_rows, float* S, float* c, hipStream_t st,
+                                  const CompactState* snap) {
   if (n_rows == 0) return FMX_OK;
+  if (snap) {
+    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false, RowsBf16>), n_rows, st, s.ent, s.row_ptr, row0, n_rows, compact_rows(h, *snap), h->cfg.k1, S, c));
+    HIPCHK(h, hipGetLastError());
+    return FMX_OK;
+  }
   if (const uint32_t G = multi_group_size(s, h->KP)) {          // short rows: several examples per wavefront
     KP_SWITCH(h->KP, { if constexpr (KP >= 64 && KP <= 256) { FMX_LAUNCH_WAVES((k_rowsums_multi<KP, true, false>), ((uint64_t)n_rows + G - 1) / G, st,
                                                                   s.ent, s.row_ptr, row0, n_rows, h->tb, h->cfg.k1, S, c, G); } });
     HIPCHK(h, hipGetLastError());
     return FMX_OK;
   }
-  KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false>), n_rows, st, s.ent, s.row_ptr, row0, n_rows, h->tb, h->cfg.k1, S, c, (const float*)nullptr));
+  KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false>), n_rows, st, s.ent, s.row_ptr, row0, n_rows, RowsF32{h->tb}, h->cfg.k1, S, c));
   HIPCHK(h, hipGetLastError());
   return FMX_OK;
 }
@@ -1053,7 +1059,7 @@ static int seq_runs_epoch(fmx_handle h, Slot& s, const Hyper& hy) {
     }
     float* S = h->partial;
     float* rest = S + (size_t)nb * h->KP;
-    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, st, s.ent, s.row_ptr, (uint64_t)row0, nb, h->tb, h->cfg.k1, S, rest, (const float*)nullptr));
+    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, st, s.ent, s.row_ptr, (uint64_t)row0, nb, RowsF32{h->tb}, h->cfg.k1, S, rest));
     if (fused && nb <= RUN_FUSED_MAX) {
       const dim3 grid((nb + 3u) / 4u);
       const size_t lds = (size_t)nb * 5 * sizeof(float);
@@ -1178,7 +1184,7 @@ static int epoch_split(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, EpochCou
     float* S = h->partial + (size_t)pslot * Bc * (size_t)(h->KP + 1);
     float* rest = S + (size_t)nb * h->KP;
     KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, h->stream,
-                                       s.ent, s.row_ptr, row0, nb, h->tb, h->cfg.k1, S, rest, (const float*)nullptr));
+                                       s.ent, s.row_ptr, row0, nb, RowsF32{h->tb}, h->cfg.k1, S, rest));
     hipEvent_t ea = nullptr, eb = nullptr;
     if (timed) { ea = h->ev_pool[2 * n->launches]; eb = h->ev_pool[2 * n->launches + 1]; n->launches++; }
     if (segmented) plan.seg_batch = (int64_t)(row0 / B);
@@ -1460,7 +1466,7 @@ int fmx_sgda_epoch_minibatch(fmx_handle h, int train_slot, int validation_slot, 
     const uint32_t nb = (uint32_t)std::min<uint64_t>(B, s.n_rows - row0);
     float* S = h->partial;
     float* rest = S + (size_t)nb * h->KP;
-    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, st, s.ent, s.row_ptr, row0, nb, h->tb, h->cfg.k1, S, rest, (const float*)nullptr));
+    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, st, s.ent, s.row_ptr, row0, nb, RowsF32{h->tb}, h->cfg.k1, S, rest));
     rc = launch_scan(h, rest, s.target + row0, nb, chunk, hy, h->mult, st);
     if (rc) return rc;
     const SegWork sw = seg_work_dense(h, s, (size_t)(row0 / B), S, h->mult);
@@ -1551,27 +1557,12 @@ int fmx_adapt_end(fmx_handle h) {
 
 // the gather of fmx_get_param_rows over nt state tables, one after the other: outs[t] = {the linear weights' state, the factors' state}
 static int state_rows(fmx_handle h, const char* what, const uint32_t* ids, uint32_t count, const Tab* tabs, double* const (*outs)[2], int nt) {
-  const int k = h->cfg.num_factor;
   for (uint32_t i = 0; i < count; i++)
     if (ids[i] >= h->cfg.num_attribute) return fail(h, FMX_E_ARG, "feature id %u >= num_attribute", ids[i]);
   if (count == 0) return FMX_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  uint32_t* d_ids = nullptr; double* d_out = nullptr;
-  const size_t nout = (size_t)count * (size_t)(k + 1);
-  HIPCHK(h, fmx_dev_alloc(&d_ids, (size_t)count * 4));
-  hipError_t er = fmx_dev_alloc(&d_out, nout * sizeof(double));
-  if (er == hipSuccess) er = hipMemcpyAsync(d_ids, ids, (size_t)count * 4, hipMemcpyHostToDevice, h->stream);
-  for (int t = 0; t < nt && er == hipSuccess; t++) {
-    hipLaunchKernelGGL(k_fetch_rows, dim3((uint32_t)((nout + 255) / 256)), dim3(256), 0, h->stream, d_ids, count, k,
-                       make_shard(h->cfg), tabs[t], d_out, d_out + count);
-    er = hipGetLastError();
-    if (er == hipSuccess) er = hipMemcpyAsync(outs[t][0], d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (er == hipSuccess && k > 0) er = hipMemcpyAsync(outs[t][1], d_out + count, (size_t)count * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
-  }
-  fmx_dev_free(d_ids); fmx_dev_free(d_out);
-  if (er != hipSuccess) return fail(h, FMX_E_HIP, "%s: %s", what, hipGetErrorString(er));
-  return FMX_OK;
+  return gather_rows(h, what, ids, count, nt, outs, [&](int t, dim3 grid, const uint32_t* d_ids, double* d_w, double* d_v) {
+    hipLaunchKernelGGL(k_fetch_rows<RowsF32>, grid, dim3(256), 0, h->stream, d_ids, count, h->cfg.num_factor, make_shard(h->cfg), RowsF32{tabs[t]}, d_w, d_v);
+  });
 }
 
 int fmx_adapt_get_state_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double* nw_out, double* nv_out) {
@@ -1615,7 +1606,7 @@ static int stateful_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_ch
     const uint32_t nb = (uint32_t)std::min<uint64_t>(B, s.n_rows - row0);
     float* S = h->partial;
     float* rest = S + (size_t)nb * h->KP;
-    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, st, s.ent, s.row_ptr, row0, nb, h->tb, h->cfg.k1, S, rest, (const float*)nullptr));
+    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, st, s.ent, s.row_ptr, row0, nb, RowsF32{h->tb}, h->cfg.k1, S, rest));
     rc = launch_scan(h, rest, s.target + row0, nb, chunk, hy, h->mult, st);
     if (rc) return rc;
     const SegWork sw = seg_work_dense(h, s, (size_t)(row0 / B), S, h->mult);

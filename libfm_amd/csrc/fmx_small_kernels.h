@@ -158,7 +158,7 @@ k_small_one(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr,
       trace_max(sy.trace, 4);
     } else {                                                         // a row beyond the register path: deferred as a whole (cm = all ones)
       float sum[VEC], sq, lin;
-      row_sums<KP, 8>(row, size, tb, h.k1, sum, sq, lin);
+      row_sums<KP>(row, size, RowsF32{tb}, h.k1, sum, sq, lin);
 #pragma unroll
       for (int v = 0; v < VEC; v++) sum[v] = subgroup_allsum<LPR>(sum[v]);
       float part = lin - 0.5f * sq;

@@ -38,7 +38,7 @@ int prep_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, int k0, fl
     const uint32_t nr = (uint32_t)std::min<uint64_t>(raw_rows, n - r);
     float* S = raw;
     float* c = raw + (size_t)nr * KP;
-    int rc = snap ? compact_partial_rows(h, *snap, s, row0 + r, nr, S, c, st) : sgd_partial_rows(h, s, row0 + r, nr, S, c, st);
+    int rc = sgd_partial_rows(h, s, row0 + r, nr, S, c, st, snap);
     if (rc) return rc;
     hipLaunchKernelGGL(k_topk_prep, dim3(wave_grid(nr)), dim3(256), 0, st, (const float*)S, (const float*)c, nr, KP,
                        h->cfg.num_factor, KM, k0, (const double*)(snap ? snap->w0 : h->w0), S_out + (size_t)r * KM, scal + r);

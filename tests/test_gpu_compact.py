@@ -1,9 +1,10 @@
-"""GPU: the bf16 serving snapshot (fmx_compact_*, k_compact_quant, k_rowsums_c, k_fetch_rows_c; include/fmx.h)
+"""GPU: the bf16 serving snapshot (fmx_compact_*, k_compact_quant, k_rowsums and k_fetch_rows over RowsBf16; include/fmx.h)
 against libfm_amd/compact.py (itself pinned to torch's bfloat16 conversion and to the fp64 oracle in tests/test_compact_cpu.py).
 
-Shapes.  k in {0, 1, 2, 8, 16, 64, 100, 128, 256}: every lane map of k_rowsums_c (2-byte loads, 4-byte loads on 1 .. 32 lanes per
-row, one row per wavefront with 4 / 8-byte loads) and a row stride that is not the padded power of two (k = 100: 112 elements).
-n in {1, 200, 4099}.  Slots of 47 rows whose lengths include 0, 1, 2, 33, 64, 65 and 130: the second 64-entry block and every tail of
+Shapes.  k in {0, 1, 2, 4, 8, 16, 32, 64, 100, 128, 256, 300, 512, 1000}: every lane map of the bf16 row source (MapC: 2-byte loads,
+4-byte loads on 1 .. 32 lanes per row, one row per wavefront with 4 / 8 / 16 / 2 x 16-byte loads) and row strides that are not the
+padded power of two (k = 100: 112 elements; k = 300: 304 of 512, whole lanes past the row read zeros; k = 1000: 1008 of 1024, lane
+63 is empty).  n in {1, 200, 4099}.  Slots of 47 rows whose lengths include 0, 1, 2, 33, 64, 65 and 130: the second 64-entry block and every tail of
 the round loop; one row repeats an id; values are seeded reals.
 
 Tolerances.  Scores: the project's predict tolerance rtol 1e-4 / atol 2e-5 (tests/test_gpu_parity.py::test_predict_matches_reference)
@@ -39,7 +40,9 @@ LENGTHS = (0, 1, 2, 33, 64, 65, 130)
 # (k, n, k1, task): every k, every n, k1 on and off, both tasks
 CASES = [(0, 200, True, 0), (1, 4099, True, 1), (2, 200, False, 0), (8, 4099, True, 1), (16, 200, True, 0), (64, 4099, True, 1),
          (64, 200, False, 0), (100, 4099, True, 0), (128, 200, True, 1), (256, 200, False, 1), (8, 1, True, 0), (64, 1, True, 1),
-         (0, 1, False, 1)]
+         (0, 1, False, 1),
+         # the widths whose lane maps nothing else runs: 2 and 16 lanes per row, and row_ld_c's 16-byte loads with lanes past the row
+         (4, 200, True, 1), (32, 200, False, 0), (300, 200, True, 0), (512, 200, False, 1), (1000, 200, True, 1)]
 IDS = ["k%d-n%d-%s-%s" % (k, n, "k1" if k1 else "nok1", "cr"[1 - t]) for k, n, k1, t in CASES]
 
 
@@ -292,7 +295,7 @@ def test_metrics_equal_the_formulas_on_the_snapshots_own_scores(capi, k, n, k1, 
 
 
 # ---- 5. top-K -------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("k, K", [(0, 5), (1, 10), (8, 100), (64, 10), (100, 33), (256, 10)])
+@pytest.mark.parametrize("k, K", [(0, 5), (1, 10), (8, 100), (64, 10), (100, 33), (256, 10), (512, 10), (1000, 10)])
 def test_topk_from_the_snapshot(capi, oracle, k, K):
     n, nq, nc = 200, 20, 130
     rng = np.random.default_rng(40 + k)
