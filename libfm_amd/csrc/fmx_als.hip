@@ -1,6 +1,7 @@
 // fmx_als.hip -- C-ABI (include/fmx.h): the ALS / MCMC learner (level-scheduled coordinate sweeps, fmx_als_kernels.h).
 #define FMX_GRID_OVER_DEFAULT 2                    // = FMX_GRID_OVER_ALS (fmx_internal.h): the column kernels keep grid-stride workgroups
 #include "fmx_internal.h"
+#include "fmx_als_levels.h"
 
 extern "C" {
 
@@ -9,26 +10,11 @@ extern "C" {
 // ---------------------------------------------------------------------------------------------
 extern "C++" void als_free(fmx_handle h) {
   AlsState& a = h->als;
-  if (a.e) fmx_dev_free(a.e);
-  if (a.q) fmx_dev_free(a.q);
-  if (a.seen) fmx_dev_free(a.seen);
-  if (a.level_list) fmx_dev_free(a.level_list);
-  if (a.ldesc) fmx_dev_free(a.ldesc);
-  if (a.prior) fmx_dev_free(a.prior);
-  if (a.vt) fmx_dev_free(a.vt);
-  if (a.delta) fmx_dev_free(a.delta);
-  if (a.epart) fmx_dev_free(a.epart);
-  if (a.r_row) fmx_dev_free(a.r_row);
-  if (a.r_pos) fmx_dev_free(a.r_pos);
-  if (a.r_x) fmx_dev_free(a.r_x);
-  if (a.t_row) fmx_dev_free(a.t_row);
-  if (a.dth) fmx_dev_free(a.dth);
+  fmx_dev_free(a.e); fmx_dev_free(a.q); fmx_dev_free(a.seen); fmx_dev_free(a.level_list); fmx_dev_free(a.ldesc);
+  fmx_dev_free(a.prior); fmx_dev_free(a.vt); fmx_dev_free(a.delta); fmx_dev_free(a.epart);
+  fmx_dev_free(a.r_row); fmx_dev_free(a.r_pos); fmx_dev_free(a.r_x); fmx_dev_free(a.t_row); fmx_dev_free(a.dth);
   for (AlsBlock& b : a.blk) {
-    if (b.level_list) fmx_dev_free(b.level_list);
-    if (b.cache) fmx_dev_free(b.cache);
-    if (b.qb_all) fmx_dev_free(b.qb_all);
-    if (b.cpart) fmx_dev_free(b.cpart);
-    if (b.delta) fmx_dev_free(b.delta);
+    fmx_dev_free(b.level_list); fmx_dev_free(b.cache); fmx_dev_free(b.qb_all); fmx_dev_free(b.cpart); fmx_dev_free(b.delta);
   }
   a = AlsState();
 }
@@ -49,46 +35,83 @@ static int als_eterms(fmx_handle h, const Slot& s, EQ* e, double* q, double* e_p
   return FMX_OK;
 }
 
-// the dependency levels of the columns of a (transposed) data set: level(j) = 1 + max level of the earlier columns sharing a
-// row with j (host, O(nnz)); fills level_ptr and uploads the level-ordered column list; marks seen[id_offset + feature]
-static int build_levels(fmx_handle h, const Slot& s, std::vector<uint32_t>& level_ptr, uint32_t** d_level_list, std::vector<uint8_t>* seen,
-                        uint32_t id_offset, std::vector<uint32_t>* seg_level = nullptr, std::vector<uint32_t>* seg_pos = nullptr,
-                        std::vector<uint32_t>* lev_ent = nullptr) {
-  const uint32_t N = s.n_rows, nseg = s.nseg;
-  std::vector<uint32_t> seg_feat(nseg), seg_rel((size_t)nseg + 1), lvl(nseg), rowlevel(std::max<uint32_t>(N, 1), 0);
-  std::vector<TEntry> tent((size_t)s.nnz);
-  if (nseg) {
-    HIPCHK(h, hipMemcpy(seg_feat.data(), s.seg_feat, (size_t)nseg * 4, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(seg_rel.data(), s.seg_rel, (size_t)nseg * 4, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy(tent.data(), s.t_ent, (size_t)s.nnz * sizeof(TEntry), hipMemcpyDeviceToHost));
+// the rows whose columns a level build orders: the session's main rows (r < 0) or kept block r's own rows
+static const Slot& als_rows(fmx_handle x, int r) {
+  const Slot& s = x->slots[x->als.slot];
+  return r < 0 ? s : s.blocks[r]->rows;
+}
+
+struct SegLevels { std::vector<uint32_t> rel, level; };   // a member's segments: first entry [nseg + 1] and level [nseg]
+
+// The dependency LEVELS of one set of rows (r as in als_rows; their X^T is built, ensure_segments) over the union of the members'
+// columns in GLOBAL feature order (assign_levels; host, O(nnz)).  Every member gets the same number of levels (on a shard some may be
+// empty): its level_ptr and the level-ordered list of its columns on its device; seen[i] marks its columns at id offset + feature
+// -- the block's attr_offset, which is 0 on a shard (its block attributes are local table rows) like the main rows'.
+// segs[i]: what the split step needs of member i's segments.  *bad: the member that failed.
+static int build_levels(const std::vector<fmx_handle>& hs, int r, std::vector<std::vector<uint8_t>>& seen, std::vector<SegLevels>& segs,
+                        size_t* bad) {
+  const size_t P = hs.size();
+  std::vector<LevelCols<TEntry>> parts;
+  std::vector<std::vector<uint32_t>> seg_feat(P), gid(P);
+  std::vector<std::vector<TEntry>> tent(P);
+  segs.assign(P, SegLevels());
+  for (size_t i = 0; i < P; i++) {
+    fmx_handle x = hs[i];
+    const Slot& s = als_rows(x, r);
+    const uint32_t nseg = s.nseg;
+    std::vector<uint32_t>& rel = segs[i].rel;
+    *bad = i;
+    seg_feat[i].resize(nseg); rel.resize((size_t)nseg + 1); segs[i].level.resize(nseg); tent[i].resize((size_t)s.nnz);
+    if (nseg) {
+      HIPCHK(x, hipSetDevice(x->device));
+      HIPCHK(x, hipMemcpy(seg_feat[i].data(), s.seg_feat, (size_t)nseg * 4, hipMemcpyDeviceToHost));
+      HIPCHK(x, hipMemcpy(rel.data(), s.seg_rel, (size_t)nseg * 4, hipMemcpyDeviceToHost));
+      HIPCHK(x, hipMemcpy(tent[i].data(), s.t_ent, (size_t)s.nnz * sizeof(TEntry), hipMemcpyDeviceToHost));
+    }
+    rel[nseg] = (uint32_t)s.nnz;
+    const Shard sh = make_shard(x->cfg);
+    if (sh.world > 1) {                                              // (unsharded: the table row is the global id)
+      gid[i].resize(nseg);
+      for (uint32_t sg = 0; sg < nseg; sg++) gid[i][sg] = sh.global(seg_feat[i][sg]);
+    }
+    parts.push_back({nseg, sh.world > 1 ? gid[i].data() : seg_feat[i].data(), rel.data(), tent[i].data(), segs[i].level.data()});
   }
-  seg_rel[nseg] = (uint32_t)s.nnz;
-  uint32_t n_levels = 0;
-  for (uint32_t sg = 0; sg < nseg; sg++) {
-    uint32_t l = 0;
-    for (uint32_t i = seg_rel[sg]; i < seg_rel[sg + 1]; i++) l = std::max(l, rowlevel[tent[i].e]);
-    l += 1;
-    for (uint32_t i = seg_rel[sg]; i < seg_rel[sg + 1]; i++) rowlevel[tent[i].e] = l;
-    lvl[sg] = l - 1;
-    n_levels = std::max(n_levels, l);
+  const uint32_t n_levels = assign_levels(parts, als_rows(hs[0], r).n_rows);
+  for (size_t i = 0; i < P; i++) {
+    fmx_handle x = hs[i];
+    AlsState& a = x->als;
+    const uint32_t nseg = als_rows(x, r).nseg;
+    const uint32_t id_offset = r < 0 ? 0u : x->slots[a.slot].blocks[r]->attr_offset;
+    const std::vector<uint32_t>& lvl = segs[i].level;
+    std::vector<uint32_t>& lp = r < 0 ? a.level_ptr : a.blk[r].level_ptr;
+    uint32_t** d_list = r < 0 ? &a.level_list : &a.blk[r].level_list;
+    *bad = i;
+    lp.assign((size_t)n_levels + 1, 0);
+    for (uint32_t sg = 0; sg < nseg; sg++) lp[lvl[sg] + 1]++;
+    for (uint32_t l = 0; l < n_levels; l++) lp[l + 1] += lp[l];
+    std::vector<uint32_t> list(std::max<uint32_t>(nseg, 1)), fill(lp.begin(), lp.end());
+    for (uint32_t sg = 0; sg < nseg; sg++) list[fill[lvl[sg]]++] = sg;
+    for (uint32_t sg = 0; sg < nseg; sg++) seen[i][(size_t)id_offset + seg_feat[i][sg]] = 1;
+    HIPCHK(x, hipSetDevice(x->device));
+    HIPCHK(x, fmx_dev_alloc(d_list, list.size() * 4));
+    HIPCHK(x, hipMemcpy(*d_list, list.data(), list.size() * 4, hipMemcpyHostToDevice));
   }
-  level_ptr.assign((size_t)n_levels + 1, 0);
-  for (uint32_t sg = 0; sg < nseg; sg++) level_ptr[lvl[sg] + 1]++;
-  for (uint32_t l = 0; l < n_levels; l++) level_ptr[l + 1] += level_ptr[l];
-  std::vector<uint32_t> list(std::max<uint32_t>(nseg, 1)), fill(level_ptr.begin(), level_ptr.end());
-  if (seg_pos) seg_pos->assign(std::max<uint32_t>(nseg, 1), 0);
-  if (lev_ent) lev_ent->assign((size_t)n_levels + 1, 0);
-  for (uint32_t sg = 0; sg < nseg; sg++) {
-    if (seg_pos) (*seg_pos)[sg] = fill[lvl[sg]] - level_ptr[lvl[sg]];      // position inside its level's list
-    if (lev_ent) (*lev_ent)[lvl[sg] + 1] += seg_rel[sg + 1] - seg_rel[sg];
-    list[fill[lvl[sg]]++] = sg;
-  }
-  if (lev_ent) for (uint32_t l = 0; l < n_levels; l++) (*lev_ent)[l + 1] += (*lev_ent)[l];
-  if (seg_level) seg_level->swap(lvl);
-  if (seen) for (uint32_t sg = 0; sg < nseg; sg++) (*seen)[(size_t)id_offset + seg_feat[sg]] = 1;
-  HIPCHK(h, fmx_dev_alloc(d_level_list, list.size() * 4));
-  HIPCHK(h, hipMemcpy(*d_level_list, list.data(), list.size() * 4, hipMemcpyHostToDevice));
+  *bad = 0;
   return FMX_OK;
+}
+
+// the split step's view of one member's levels: where every segment sits inside its level's list (seg_pos) and the entry range of
+// every level (AlsState::lev_ent)
+static void level_entries(const SegLevels& sl, AlsState& a, std::vector<uint32_t>& seg_pos) {
+  const size_t nseg = sl.level.size(), n_levels = a.level_ptr.size() - 1;
+  std::vector<uint32_t> fill(n_levels, 0);
+  seg_pos.assign(std::max<size_t>(nseg, 1), 0);
+  a.lev_ent.assign(n_levels + 1, 0);
+  for (size_t sg = 0; sg < nseg; sg++) {
+    seg_pos[sg] = fill[sl.level[sg]]++;
+    a.lev_ent[sl.level[sg] + 1] += sl.rel[sg + 1] - sl.rel[sg];
+  }
+  for (size_t l = 0; l < n_levels; l++) a.lev_ent[l + 1] += a.lev_ent[l];
 }
 
 // a kept block's rows: their partial sums (lin - 0.5 * sum of squares -> cpart, factor sums -> qb_all), each block row once
@@ -102,24 +125,58 @@ static int block_eterms(fmx_handle h, const BlockRows& br, AlsBlock& ab) {
   return FMX_OK;
 }
 
-// y-hat (and q_f for the coming sweep) of the session's rows.  With kept blocks the main rows and every block's rows are
-// evaluated separately -- a block row once, however many main rows map to it -- and combined through the mappings;
-// the squares are of the COMPLETE factor sums (k_als_set_e).
-static int als_repredict(fmx_handle h, const Slot& s, AlsState& a) {
-  if (s.blocks.empty()) return als_eterms(h, s, a.e, a.q);
-  const uint32_t N = s.n_rows;
-  const dim3 g1(std::min<uint32_t>((N + 255) / 256, 2048)), b1(256);
-  int rc = als_eterms(h, s, a.e, a.q, a.epart);
-  if (rc) return rc;
-  for (size_t r = 0; r < s.blocks.size(); r++) {
-    const BlockRows& br = *s.blocks[r];
-    AlsBlock& ab = a.blk[r];
-    rc = block_eterms(h, br, ab);
+// y-hat (and q_f for the coming sweep) of the session's rows, on every member.  The main rows and every kept block's rows are
+// summed separately -- a block row once, however many main rows map to it -- over the member's own features; feature shards (g)
+// all-reduce these partial sums; then every member adds the blocks' sums to the main rows' through the mappings -- identically, so
+// each block counts once -- and squares the COMPLETE factor sums (k_als_set_e).  One member without blocks has nothing to add:
+// k_als_eterms finishes e itself (no pass over epart, and e keeps that kernel's order of sums).  *bad: the member that failed.
+static int als_repredict(const std::vector<fmx_handle>& hs, fmx_group g /* nullptr: nothing is exchanged */, size_t* bad) {
+  const size_t P = hs.size();
+  fmx_handle h0 = hs[0];
+  const Slot& s0 = h0->slots[h0->als.slot];
+  const uint32_t N = s0.n_rows;
+  const int kf = h0->cfg.num_factor;
+  const size_t R = s0.blocks.size();
+  const bool direct = !g && R == 0;
+  for (size_t i = 0; i < P; i++) {
+    fmx_handle x = hs[i];
+    AlsState& a = x->als;
+    const Slot& s = x->slots[a.slot];
+    *bad = i;
+    HIPCHK(x, hipSetDevice(x->device));
+    int rc = als_eterms(x, s, a.e, a.q, direct ? nullptr : a.epart);
+    for (size_t r = 0; r < R && rc == FMX_OK; r++) rc = block_eterms(x, *s.blocks[r], a.blk[r]);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_rel_combine, g1, b1, 0, h->stream, br.map, N, br.rows.n_rows, ab.cpart, ab.qb_all, h->cfg.num_factor, a.epart, a.q);
   }
-  hipLaunchKernelGGL(k_als_set_e, g1, b1, 0, h->stream, a.e, a.epart, a.q, h->cfg.num_factor, N, h->cfg.k0, h->w0);
-  HIPCHK(h, hipGetLastError());
+  *bad = 0;
+  if (direct) return FMX_OK;
+  if (g) {
+    std::vector<double*> bq(P), be(P);
+    for (size_t i = 0; i < P; i++) { bq[i] = hs[i]->als.q; be[i] = hs[i]->als.epart; }
+    int rc = kf > 0 ? group_allreduce_f64(g, bq, (size_t)kf * N) : FMX_OK;      // q is [KP][N]: the first k factor rows
+    if (rc == FMX_OK) rc = group_allreduce_f64(g, be, N);
+    for (size_t r = 0; r < R && rc == FMX_OK; r++) {
+      const uint32_t B = s0.blocks[r]->rows.n_rows;
+      for (size_t i = 0; i < P; i++) { bq[i] = hs[i]->als.blk[r].qb_all; be[i] = hs[i]->als.blk[r].cpart; }
+      rc = kf > 0 ? group_allreduce_f64(g, bq, (size_t)kf * B) : FMX_OK;        // qb_all is [KP][B]
+      if (rc == FMX_OK) rc = group_allreduce_f64(g, be, B);
+    }
+    if (rc) return rc;
+  }
+  const dim3 g1(std::min<uint32_t>((N + 255) / 256, 2048)), b1(256);
+  for (size_t i = 0; i < P; i++) {
+    fmx_handle x = hs[i];
+    AlsState& a = x->als;
+    const Slot& s = x->slots[a.slot];
+    *bad = i;
+    HIPCHK(x, hipSetDevice(x->device));
+    for (size_t r = 0; r < R; r++)
+      hipLaunchKernelGGL(k_rel_combine, g1, b1, 0, x->stream, s.blocks[r]->map, N, s.blocks[r]->rows.n_rows, a.blk[r].cpart, a.blk[r].qb_all,
+                         kf, a.epart, a.q);
+    hipLaunchKernelGGL(k_als_set_e, g1, b1, 0, x->stream, a.e, a.epart, a.q, kf, N, x->cfg.k0, x->w0);
+    HIPCHK(x, hipGetLastError());
+  }
+  *bad = 0;
   return FMX_OK;
 }
 
@@ -181,77 +238,129 @@ done:
   return rc;
 }
 
-static int als_begin_impl(fmx_handle h, int train_slot);
-int fmx_als_begin(fmx_handle h, int train_slot) {
-  const int rc = als_begin_impl(h, train_slot);
-  if (rc != FMX_OK && h && h->als.slot == train_slot) als_free(h);      // a failed set-up leaves no half-built session behind
-  return rc;
+// lanes per column of a kept block's draws (k_rel_draw) from the mean column length
+static int block_lanes(const Slot& rows) {
+  const double avg_col = rows.nseg ? (double)rows.nnz / (double)rows.nseg : 0.0;
+  return avg_col <= 5.0 ? 4 : (avg_col <= 12.0 ? 8 : (avg_col <= 40.0 ? 16 : 64));
 }
-static int als_begin_impl(fmx_handle h, int train_slot) {
-  touch_w(h);
-  int rc = check_slot(h, train_slot, true);
-  if (rc) return rc;
-  { int _rc = lag_flush(h); if (_rc) return _rc; }
-  if (h->cfg.shard_world > 1) return fail(h, FMX_E_STATE, "ALS / MCMC on a feature shard: use fmx_group_als_begin (the dependency levels are global)");
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  als_free(h);
-  Slot& s = h->slots[train_slot];
-  if (s.n_rows == 0) return fail(h, FMX_E_ARG, "fmx_als_begin: empty training set");
-  rc = ensure_segments(h, s, s.n_rows);          // one "batch" = the whole data set: X^T with columns in id order
-  if (rc) return rc;
-  AlsState& a = h->als;
-  a.slot = train_slot;
-  const uint32_t N = s.n_rows;
+
+// The set-up of a session over a list of members: one unsharded handle (g == nullptr: nothing is exchanged) or the feature shards
+// of g.  Every member builds X^T of its own features -- of the main rows and of every kept block's rows; the levels are global
+// (build_levels) and the first prediction is all-reduced (als_repredict).  `who`: the entry point, for the messages.  *bad: the
+// member that failed; the entry points take a failed set-up's session down again.
+static int als_begin_shards(const std::vector<fmx_handle>& hs, fmx_group g, int train_slot, const char* who, size_t* bad) {
+  const size_t P = hs.size();
+  const bool sharded = g != nullptr;
+  for (size_t i = 0; i < P; i++) {
+    fmx_handle x = hs[i];
+    *bad = i;
+    int rc = check_slot(x, train_slot, true);
+    if (rc == FMX_OK) rc = lag_flush(x);
+    if (rc) return rc;
+    if (!sharded && x->cfg.shard_world > 1)
+      return fail(x, FMX_E_STATE, "ALS / MCMC on a feature shard: use fmx_group_als_begin (the dependency levels are global)");
+    HIPCHK(x, hipSetDevice(x->device));
+    HIPCHK(x, hipStreamSynchronize(x->stream));
+    als_free(x);
+    Slot& s = x->slots[train_slot];
+    const Slot& s0 = hs[0]->slots[train_slot];
+    if (s.n_rows == 0) return fail(x, FMX_E_ARG, "%s: empty training set", who);
+    if (s.n_rows != s0.n_rows) return fail(x, FMX_E_STATE, "the shards hold different numbers of rows");
+    if (s.blocks.size() != s0.blocks.size()) return fail(x, FMX_E_STATE, "the shards hold different relation blocks");
+    for (size_t r = 0; r < s.blocks.size(); r++)
+      if (s.blocks[r]->rows.n_rows != s0.blocks[r]->rows.n_rows) return fail(x, FMX_E_STATE, "the shards hold different relation blocks");
+    rc = ensure_segments(x, s, s.n_rows);          // one "batch" = the whole data set: X^T with columns in id order
+    for (size_t r = 0; r < s.blocks.size() && rc == FMX_OK; r++) {        // X^T of every block (a shard that owns none of a block's
+      Slot& rows = s.blocks[r]->rows;                                     // attributes has no columns there)
+      if (!sharded || rows.nnz) rc = ensure_segments(x, rows, std::max<uint32_t>(rows.n_rows, 1));
+    }
+    if (rc) return rc;
+    x->als.slot = train_slot;
+    x->als.blk.resize(s.blocks.size());
+  }
+  const Slot& s0 = hs[0]->slots[train_slot];
+  const uint32_t N = s0.n_rows;
+  const size_t R = s0.blocks.size();
   // ---- dependency levels of the main features, then -- kept `-relation` blocks -- of every block's attributes over
   //      the block's own rows (two block attributes conflict iff they share a block row)
-  std::vector<uint8_t> seen((size_t)h->n_local, 0);
-  {
+  std::vector<std::vector<uint8_t>> seen(P);
+  for (size_t i = 0; i < P; i++) seen[i].assign((size_t)hs[i]->n_local, 0);
+  std::vector<SegLevels> segs;
+  int rc = build_levels(hs, -1, seen, segs, bad);
+  if (rc) return rc;
+  if (!sharded) {
     // levels with many entries take the split step (column sums + draw, then the {e, q} update as a row-ordered stream):
     // a fused draw pays two random touches of the {e, q} cache per entry, the split one.  fmx_config::als_split_min: threshold in
     // entries per level; small levels are launch-bound and stay fused.
+    fmx_handle h = hs[0];
+    AlsState& a = h->als;
     a.split_min = h->cfg.als_split_min == 0 ? 65536u : (h->cfg.als_split_min == 0xFFFFFFFFu ? 0u : h->cfg.als_split_min);
-    std::vector<uint32_t> seg_level, seg_pos;
-    rc = build_levels(h, s, a.level_ptr, &a.level_list, &seen, 0, &seg_level, &seg_pos, &a.lev_ent);
-    if (rc) return rc;
+    std::vector<uint32_t> seg_pos;
+    level_entries(segs[0], a, seg_pos);
     bool any = false;
     for (size_t l = 0; a.split_min && l + 1 < a.lev_ent.size(); l++) any = any || (a.lev_ent[l + 1] - a.lev_ent[l] >= a.split_min);
-    if (any && s.nnz > 0 && s.nnz < (1ull << 32)) { rc = als_build_rows(h, s, a, seg_level, seg_pos); if (rc) return rc; }
+    if (any && s0.nnz > 0 && s0.nnz < (1ull << 32)) { rc = als_build_rows(h, s0, a, segs[0].level, seg_pos); if (rc) return rc; }
     else a.split_min = 0;
   }
-  a.blk.resize(s.blocks.size());
-  for (size_t r = 0; r < s.blocks.size(); r++) {
-    BlockRows& br = *s.blocks[r];
-    AlsBlock& ab = a.blk[r];
-    const uint32_t B = br.rows.n_rows;
-    rc = ensure_segments(h, br.rows, std::max<uint32_t>(B, 1));            // X^T of the block (device radix sort)
-    if (rc) return rc;
-    rc = build_levels(h, br.rows, ab.level_ptr, &ab.level_list, &seen, br.attr_offset);
-    if (rc) return rc;
-    HIPCHK(h, fmx_dev_alloc(&ab.cache, (size_t)7 * std::max<uint32_t>(B, 1) * sizeof(double)));
-    HIPCHK(h, hipMemsetAsync(ab.cache, 0, (size_t)7 * std::max<uint32_t>(B, 1) * sizeof(double), h->stream));
-    HIPCHK(h, fmx_dev_alloc(&ab.qb_all, (size_t)h->KP * std::max<uint32_t>(B, 1) * sizeof(double)));
-    HIPCHK(h, fmx_dev_alloc(&ab.cpart, (size_t)std::max<uint32_t>(B, 1) * sizeof(double)));
-    const double avg_col = br.rows.nseg ? (double)br.rows.nnz / (double)br.rows.nseg : 0.0;
-    ab.lanes = avg_col <= 5.0 ? 4 : (avg_col <= 12.0 ? 8 : (avg_col <= 40.0 ? 16 : 64));
-  }
-  const uint32_t nseg = s.nseg;
-  HIPCHK(h, fmx_dev_alloc(&a.seen, seen.size()));
-  HIPCHK(h, hipMemcpy(a.seen, seen.data(), seen.size(), hipMemcpyHostToDevice));
-  if (!s.blocks.empty()) HIPCHK(h, fmx_dev_alloc(&a.epart, (size_t)N * sizeof(double)));
-  HIPCHK(h, fmx_dev_alloc(&a.e, (size_t)N * sizeof(EQ)));
-  HIPCHK(h, fmx_dev_alloc(&a.q, (size_t)N * (size_t)h->KP * sizeof(double)));
-  if (h->cfg.num_factor > 0 && nseg > 0) {      // (the env switch is the A/B knob of the profile)
-    a.vt_stride = ((size_t)nseg + 63) & ~(size_t)63;
-    HIPCHK(h, fmx_dev_alloc(&a.vt, (size_t)h->cfg.num_factor * a.vt_stride * sizeof(float)));
+  for (size_t r = 0; r < R; r++) { rc = build_levels(hs, (int)r, seen, segs, bad); if (rc) return rc; }
+  // ---- the session's buffers; a sharded one also records what a step's draws change (delta) and all-reduces partial sums (epart)
+  for (size_t i = 0; i < P; i++) {
+    fmx_handle x = hs[i];
+    AlsState& a = x->als;
+    const Slot& s = x->slots[train_slot];
+    *bad = i;
+    HIPCHK(x, hipSetDevice(x->device));
+    HIPCHK(x, fmx_dev_alloc(&a.seen, seen[i].size()));
+    HIPCHK(x, hipMemcpy(a.seen, seen[i].data(), seen[i].size(), hipMemcpyHostToDevice));
+    HIPCHK(x, fmx_dev_alloc(&a.e, (size_t)N * sizeof(EQ)));
+    HIPCHK(x, fmx_dev_alloc(&a.q, (size_t)N * (size_t)x->KP * sizeof(double)));
+    if (sharded) {
+      HIPCHK(x, fmx_dev_alloc(&a.delta, (size_t)N * sizeof(EQ)));
+      HIPCHK(x, hipMemsetAsync(a.delta, 0, (size_t)N * sizeof(EQ), x->stream));
+    }
+    if (sharded || R) HIPCHK(x, fmx_dev_alloc(&a.epart, (size_t)N * sizeof(double)));
+    if (x->cfg.num_factor > 0 && s.nseg > 0) {
+      a.vt_stride = ((size_t)s.nseg + 63) & ~(size_t)63;
+      HIPCHK(x, fmx_dev_alloc(&a.vt, (size_t)x->cfg.num_factor * a.vt_stride * sizeof(float)));
+    }
+    for (size_t r = 0; r < R; r++) {         // the kept blocks' caches (on shards: replicated, with their per-level changes)
+      const Slot& rows = s.blocks[r]->rows;
+      AlsBlock& ab = a.blk[r];
+      const size_t B = std::max<uint32_t>(rows.n_rows, 1);
+      HIPCHK(x, fmx_dev_alloc(&ab.cache, (size_t)7 * B * sizeof(double)));
+      HIPCHK(x, hipMemsetAsync(ab.cache, 0, (size_t)7 * B * sizeof(double), x->stream));
+      HIPCHK(x, fmx_dev_alloc(&ab.qb_all, (size_t)x->KP * B * sizeof(double)));
+      HIPCHK(x, fmx_dev_alloc(&ab.cpart, B * sizeof(double)));
+      if (sharded) {
+        HIPCHK(x, fmx_dev_alloc(&ab.delta, (size_t)4 * B * sizeof(double)));
+        HIPCHK(x, hipMemsetAsync(ab.delta, 0, (size_t)4 * B * sizeof(double), x->stream));
+      }
+      ab.lanes = block_lanes(rows);
+    }
   }
   // ---- first prediction and e -= target (fm_learn_mcmc_simultaneous.h:69-86)
-  rc = als_repredict(h, s, a);
+  rc = als_repredict(hs, g, bad);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_als_sub_target, dim3(std::min<uint32_t>((N + 255) / 256, 2048)), dim3(256), 0, h->stream, a.e, s.target, N);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const dim3 g1(std::min<uint32_t>((N + 255) / 256, 2048)), b1(256);
+  for (size_t i = 0; i < P; i++) {
+    fmx_handle x = hs[i];
+    *bad = i;
+    HIPCHK(x, hipSetDevice(x->device));
+    hipLaunchKernelGGL(k_als_sub_target, g1, b1, 0, x->stream, x->als.e, x->slots[train_slot].target, N);
+    HIPCHK(x, hipGetLastError());
+    HIPCHK(x, hipStreamSynchronize(x->stream));
+  }
+  *bad = 0;
   return FMX_OK;
+}
+
+int fmx_als_begin(fmx_handle h, int train_slot) {
+  touch_w(h);
+  if (!h) return FMX_E_ARG;
+  size_t bad = 0;
+  const int rc = als_begin_shards(std::vector<fmx_handle>(1, h), nullptr, train_slot, "fmx_als_begin", &bad);
+  if (rc != FMX_OK && h->als.slot == train_slot) als_free(h);      // a failed set-up leaves no half-built session behind
+  return rc;
 }
 
 int fmx_als_moments(fmx_handle h, double* out) {
@@ -272,17 +381,14 @@ int fmx_als_moments(fmx_handle h, double* out) {
   const bool grouped = G > 1;
   const int lds_ok = cells * sizeof(double) <= 64 * 1024;
   const size_t lds = (grouped && lds_ok) ? cells * sizeof(double) : 0;
-  int rc = FMX_OK;
-  do {
-    KP_SWITCH(h->KP, {
-      const uint64_t waves = (h->n_local + Map<KP>::EPI - 1) / Map<KP>::EPI;
-      if (grouped) { auto kf = k_group_moments<KP, true>;
-        hipLaunchKernelGGL(kf, dim3(resident_grid(h, (const void*)kf, waves)), b1, lds, st, h->tb, h->n_local, h->cfg.k1, h->grp, G, lds_ok, d + 2);
-      } else { auto kf = k_group_moments<KP, false>;
-        hipLaunchKernelGGL(kf, dim3(resident_grid(h, (const void*)kf, waves)), b1, 0, st, h->tb, h->n_local, h->cfg.k1, h->grp, G, 0, d + 2);
-      }
-    });
-  } while (0);
+  KP_SWITCH(h->KP, {
+    const uint64_t waves = (h->n_local + Map<KP>::EPI - 1) / Map<KP>::EPI;
+    if (grouped) { auto kf = k_group_moments<KP, true>;
+      hipLaunchKernelGGL(kf, dim3(resident_grid(h, (const void*)kf, waves)), b1, lds, st, h->tb, h->n_local, h->cfg.k1, h->grp, G, lds_ok, d + 2);
+    } else { auto kf = k_group_moments<KP, false>;
+      hipLaunchKernelGGL(kf, dim3(resident_grid(h, (const void*)kf, waves)), b1, 0, st, h->tb, h->n_local, h->cfg.k1, h->grp, G, 0, d + 2);
+    }
+  });
   std::vector<double> host(2 + cells);
   if (er == hipSuccess) er = hipGetLastError();
   if (er == hipSuccess) er = hipMemcpyAsync(host.data(), d, (2 + cells) * sizeof(double), hipMemcpyDeviceToHost, st);
@@ -291,57 +397,17 @@ int fmx_als_moments(fmx_handle h, double* out) {
   if (er != hipSuccess) return fail(h, FMX_E_HIP, "fmx_als_moments: %s", hipGetErrorString(er));
   out[0] = host[1]; out[1] = host[0];                                          // documented order: sum e^2 first
   memcpy(out + 2, host.data() + 2, (size_t)(1 + k) * G * 2 * sizeof(double)); // rows 0..k of [1 + KP][G][2]
-  return rc;
-}
-
-// feature shards: y-hat and q_f of the session's rows.  Every shard sums the main rows and every kept block's rows over its own
-// features (partial sums); the partials are all-reduced, then every shard adds the blocks' sums to the main rows' through the
-// mappings -- identically, so each block counts once -- and finishes e = y-hat (k_als_set_e).  *bad: the shard that failed.
-static int group_repredict(fmx_group g, const std::vector<fmx_handle>& hs, size_t* bad) {
-  const size_t P = hs.size();
-  fmx_handle h0 = hs[0];
-  const Slot& s0 = h0->slots[h0->als.slot];
-  const uint32_t N = s0.n_rows;
-  const int kf = h0->cfg.num_factor;
-  const size_t R = s0.blocks.size();
-  for (size_t i = 0; i < P; i++) {
-    fmx_handle x = hs[i];
-    AlsState& a = x->als;
-    const Slot& s = x->slots[a.slot];
-    *bad = i;
-    HIPCHK(x, hipSetDevice(x->device));
-    int rc = als_eterms(x, s, a.e, a.q, a.epart);
-    for (size_t r = 0; r < R && rc == FMX_OK; r++) rc = block_eterms(x, *s.blocks[r], a.blk[r]);
-    if (rc) return rc;
-  }
-  *bad = 0;
-  std::vector<double*> bq(P), be(P);
-  for (size_t i = 0; i < P; i++) { bq[i] = hs[i]->als.q; be[i] = hs[i]->als.epart; }
-  int rc = kf > 0 ? group_allreduce_f64(g, bq, (size_t)kf * N) : FMX_OK;      // q is [KP][N]: the first k factor rows
-  if (rc == FMX_OK) rc = group_allreduce_f64(g, be, N);
-  for (size_t r = 0; r < R && rc == FMX_OK; r++) {
-    const uint32_t B = s0.blocks[r]->rows.n_rows;
-    for (size_t i = 0; i < P; i++) { bq[i] = hs[i]->als.blk[r].qb_all; be[i] = hs[i]->als.blk[r].cpart; }
-    rc = kf > 0 ? group_allreduce_f64(g, bq, (size_t)kf * B) : FMX_OK;        // qb_all is [KP][B]
-    if (rc == FMX_OK) rc = group_allreduce_f64(g, be, B);
-  }
-  if (rc) return rc;
-  const dim3 g1(std::min<uint32_t>((N + 255) / 256, 2048)), b1(256);
-  for (size_t i = 0; i < P; i++) {
-    fmx_handle x = hs[i];
-    AlsState& a = x->als;
-    const Slot& s = x->slots[a.slot];
-    *bad = i;
-    HIPCHK(x, hipSetDevice(x->device));
-    for (size_t r = 0; r < R; r++)
-      hipLaunchKernelGGL(k_rel_combine, g1, b1, 0, x->stream, s.blocks[r]->map, N, s.blocks[r]->rows.n_rows, a.blk[r].cpart, a.blk[r].qb_all,
-                         kf, a.epart, a.q);
-    hipLaunchKernelGGL(k_als_set_e, g1, b1, 0, x->stream, a.e, a.epart, a.q, kf, N, x->cfg.k0, x->w0);
-    HIPCHK(x, hipGetLastError());
-  }
-  *bad = 0;
   return FMX_OK;
 }
+
+// the draw kernels' lanes per column as a constant, in KP_SWITCH's style: inside the statement LANES is 4, 8, 16 or 64
+#define LANES_SWITCH(LV, ...)                                      \
+  switch (LV) {                                                    \
+    case 4:  { constexpr int LANES = 4;  __VA_ARGS__; } break;     \
+    case 8:  { constexpr int LANES = 8;  __VA_ARGS__; } break;     \
+    case 16: { constexpr int LANES = 16; __VA_ARGS__; } break;     \
+    default: { constexpr int LANES = 64; __VA_ARGS__; } break;     \
+  }
 
 // one iteration of _learn over a list of feature shards (one unsharded handle: the list has one member and nothing is
 // exchanged).  Shards: the {e, q} cache is replicated; the draws of a (family, level) step record their changes
@@ -423,13 +489,6 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
     // (measured at 6.7 entries per column, inside one process: 4 lanes 161.4 ms per sweep, 8 lanes 164.4, 16 lanes 195)
     lanes[i] = avg_col <= 8.0 ? 4 : (avg_col <= 16.0 ? 8 : (avg_col <= 40.0 ? 16 : 64));
   }
-#define FMX_ALS_DRAW(ISV, cnt, ...)                                                                          \
-  do {                                                                                                        \
-    if (G == 4)       FMX_LAUNCH_WAVES((k_als_draw<ISV, 4>), ((uint64_t)(cnt) + 15) / 16, st, __VA_ARGS__);    \
-    else if (G == 8)  FMX_LAUNCH_WAVES((k_als_draw<ISV, 8>), ((uint64_t)(cnt) + 7) / 8, st, __VA_ARGS__);      \
-    else if (G == 16) FMX_LAUNCH_WAVES((k_als_draw<ISV, 16>), ((uint64_t)(cnt) + 3) / 4, st, __VA_ARGS__);     \
-    else              FMX_LAUNCH_WAVES((k_als_draw<ISV, 64>), (uint64_t)(cnt), st, __VA_ARGS__);               \
-  } while (0)
   // one (family, level) step on every shard, then -- shards only -- the exchange of the recorded changes
   auto level_step = [&](uint32_t l, int f /* -1: linear weights */) -> int {
     bool any = false;
@@ -442,7 +501,6 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
       any = true;
       HIPCHK(h, hipSetDevice(h->device));
       hipStream_t st = h->stream;
-      const int G = lanes[i];
       const Shard sh = make_shard(h->cfg);
       EQ* delta = sharded ? a.delta : nullptr;
       const uint32_t n_ent = (!sharded && a.split_min && a.r_row) ? a.lev_ent[l + 1] - a.lev_ent[l] : 0u;
@@ -450,30 +508,23 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
       const bool unit = dth && l < a.lev_dense.size() && a.lev_dense[l] == 2 && a.t_row;   // every value of the level is 1: 4-byte streams
       const uint32_t* unit_rows = unit ? a.t_row : nullptr;
       const float* lev_x = (dth && !unit) ? a.r_x + a.lev_ent[l] : nullptr;   // (no split step: the row-ordered lists do not exist)
-      if (f < 0) {
-        FMX_ALS_DRAW(false, cnt, s.t_ent, unit_rows, a.ldesc + a.level_ptr[l], cnt,
-                     h->tb.w, h->tb.ws, 0, 0u, a.e, opts->alpha, a.prior, a.prior + NG, h->grp, opts->do_sample,
-                     opts->seed, mcmc_stream(a.iter, MCMC_W), sh, delta, dth);
-        if (dth && a.lev_dense[l]) hipLaunchKernelGGL((k_als_rows_dense<false>), dim3(std::min<uint32_t>((n_ent + 255) / 256, 16384)), dim3(256), 0, st,
-                                    a.r_pos + a.lev_ent[l], lev_x, n_ent, dth, a.e);
-        else if (dth) hipLaunchKernelGGL((k_als_rows<false>), dim3(std::min<uint32_t>((n_ent + 255) / 256, 16384)), dim3(256), 0, st,
-                                    a.r_row + a.lev_ent[l], a.r_pos + a.lev_ent[l], a.r_x + a.lev_ent[l], n_ent, dth, a.e);
-      } else {
-        const double* v_lambda = a.prior + (size_t)(1 + f) * 2 * NG;
-        const double* v_mu = v_lambda + NG;
-        if (a.vt)
-          FMX_ALS_DRAW(true, cnt, s.t_ent, unit_rows, a.ldesc + a.level_ptr[l], cnt,
-                       a.vt + (size_t)f * a.vt_stride, 1u, 1, a.level_ptr[l], a.e, opts->alpha, v_lambda, v_mu, h->grp, opts->do_sample,
-                       opts->seed, mcmc_stream(a.iter, MCMC_V, f), sh, delta, dth);
-        else
-          FMX_ALS_DRAW(true, cnt, s.t_ent, unit_rows, a.ldesc + a.level_ptr[l], cnt,
-                       h->tb.V + f, h->tb.rs, 0, 0u, a.e, opts->alpha, v_lambda, v_mu, h->grp, opts->do_sample,
-                       opts->seed, mcmc_stream(a.iter, MCMC_V, f), sh, delta, dth);
-        if (dth && a.lev_dense[l]) hipLaunchKernelGGL((k_als_rows_dense<true>), dim3(std::min<uint32_t>((n_ent + 255) / 256, 16384)), dim3(256), 0, st,
-                                    a.r_pos + a.lev_ent[l], lev_x, n_ent, dth, a.e);
-        else if (dth) hipLaunchKernelGGL((k_als_rows<true>), dim3(std::min<uint32_t>((n_ent + 255) / 256, 16384)), dim3(256), 0, st,
-                                    a.r_row + a.lev_ent[l], a.r_pos + a.lev_ent[l], a.r_x + a.lev_ent[l], n_ent, dth, a.e);
-      }
+      // the family's parameter of a column -- v_f by its position in the level-ordered shadow where the session keeps one -- its
+      // priors and its random stream
+      const bool by_pos = f >= 0 && a.vt;
+      float* param = f < 0 ? h->tb.w : (by_pos ? a.vt + (size_t)f * a.vt_stride : h->tb.V + f);
+      const uint32_t pstride = f < 0 ? h->tb.ws : (by_pos ? 1u : h->tb.rs);
+      const double* lam = f < 0 ? a.prior : a.prior + (size_t)(1 + f) * 2 * NG;
+      const uint64_t stream_id = f < 0 ? mcmc_stream(a.iter, MCMC_W) : mcmc_stream(a.iter, MCMC_V, f);
+      const uint32_t e0 = dth ? a.lev_ent[l] : 0u;
+      const dim3 gr(std::min<uint32_t>((n_ent + 255) / 256, 16384));
+#define FMX_LEVEL_STEP(ISV)                                                                                                                  \
+      LANES_SWITCH(lanes[i], FMX_LAUNCH_WAVES((k_als_draw<ISV, LANES>), ((uint64_t)cnt * LANES + 63) / 64, st, s.t_ent, unit_rows,              \
+                   a.ldesc + a.level_ptr[l], cnt, param, pstride, by_pos ? 1 : 0, by_pos ? a.level_ptr[l] : 0u, a.e, opts->alpha, lam, lam + NG, \
+                   h->grp, opts->do_sample, opts->seed, stream_id, sh, delta, dth));                                                            \
+      if (dth && a.lev_dense[l]) hipLaunchKernelGGL((k_als_rows_dense<ISV>), gr, b1, 0, st, a.r_pos + e0, lev_x, n_ent, dth, a.e);              \
+      else if (dth) hipLaunchKernelGGL((k_als_rows<ISV>), gr, b1, 0, st, a.r_row + e0, a.r_pos + e0, a.r_x + e0, n_ent, dth, a.e)
+      if (f < 0) { FMX_LEVEL_STEP(false); } else { FMX_LEVEL_STEP(true); }
+#undef FMX_LEVEL_STEP
       HIPCHK(h, hipGetLastError());
     }
     if (sharded && any) {
@@ -532,11 +583,12 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
           const uint32_t pstride = (f < 0) ? h->tb.ws : h->tb.rs;
           const Shard sh = make_shard(h->cfg);
           double* delta = sharded ? ab.delta : nullptr;
-#define FMX_REL_DRAW(ISV, GG) FMX_LAUNCH_WAVES((k_rel_draw<ISV, GG>), ((uint64_t)cnt * GG + 63) / 64, st, br.rows.t_ent, br.rows.seg_feat,        \
-          br.rows.seg_rel, br.rows.nseg, (uint32_t)br.rows.nnz, ab.level_list + ab.level_ptr[l], cnt, param, pstride, br.attr_offset,             \
-          br.brow_ptr, B, ab.cache, opts->alpha, lam, mu, h->grp, opts->do_sample, opts->seed, stream_id, sh, delta)
-          if (f < 0) { if (ab.lanes <= 4) FMX_REL_DRAW(false, 4); else if (ab.lanes == 8) FMX_REL_DRAW(false, 8); else if (ab.lanes == 16) FMX_REL_DRAW(false, 16); else FMX_REL_DRAW(false, 64); }
-          else       { if (ab.lanes <= 4) FMX_REL_DRAW(true, 4);  else if (ab.lanes == 8) FMX_REL_DRAW(true, 8);  else if (ab.lanes == 16) FMX_REL_DRAW(true, 16);  else FMX_REL_DRAW(true, 64); }
+#define FMX_REL_DRAW(ISV)                                                                                                                    \
+          LANES_SWITCH(ab.lanes, FMX_LAUNCH_WAVES((k_rel_draw<ISV, LANES>), ((uint64_t)cnt * LANES + 63) / 64, st, br.rows.t_ent,              \
+                       br.rows.seg_feat, br.rows.seg_rel, br.rows.nseg, (uint32_t)br.rows.nnz, ab.level_list + ab.level_ptr[l], cnt, param,    \
+                       pstride, br.attr_offset, br.brow_ptr, B, ab.cache, opts->alpha, lam, mu, h->grp, opts->do_sample, opts->seed,           \
+                       stream_id, sh, delta))
+          if (f < 0) { FMX_REL_DRAW(false); } else { FMX_REL_DRAW(true); }
 #undef FMX_REL_DRAW
           HIPCHK(h, hipGetLastError());
         }
@@ -606,19 +658,11 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
     }
     HIPCHK(h, hipGetLastError());
   }
-#undef FMX_ALS_DRAW
   // full re-prediction (fm_learn_mcmc_simultaneous.h:122), train metric and new residuals (:139-196)
-  if (sharded) {
+  {
     size_t bad = 0;
-    int rc = group_repredict(g, hs, &bad);
+    int rc = als_repredict(hs, sharded ? g : nullptr, &bad);
     if (rc) { if (bad) h->err = hs[bad]->err; return rc; }
-  } else {
-    for (fmx_handle x : hs) {
-      AlsState& a = x->als;
-      HIPCHK(x, hipSetDevice(x->device));
-      int rc = als_repredict(x, x->slots[a.slot], a);
-      if (rc) return rc;
-    }
   }
   for (fmx_handle x : hs) {
     AlsState& a = x->als;
@@ -645,169 +689,17 @@ static int als_sweep_shards(const std::vector<fmx_handle>& hs, fmx_group g, cons
 }
 
 // ---- fm_learn_mcmc over feature shards (fmx_group) --------------------------------------------------------------
-// The dependency LEVELS of one set of rows (the main rows, or one kept block's rows) over the union of the shards' columns in
-// GLOBAL feature order: level(j) = 1 + max level of the smaller-id features sharing a row with j -- so that "level by level, every
-// shard its features of the level" is exactly the reference's sequential sweep.  sl[i]: shard i's rows with X^T built
-// (ensure_segments).  Every shard gets the same number of levels (some may be empty): *level_ptr[i], the level-ordered column list
-// *d_list[i] on its device, and seen[i] marks its columns.  *bad: the shard that failed.
-static int global_levels(fmx_group g, const std::vector<Slot*>& sl, uint32_t n_rows, const std::vector<std::vector<uint32_t>*>& level_ptr,
-                         const std::vector<uint32_t**>& d_list, std::vector<std::vector<uint8_t>>& seen, size_t* bad) {
-  const size_t P = g->hs.size();
-  struct Col { uint32_t gid, shard, seg; };
-  std::vector<Col> cols;
-  std::vector<std::vector<uint32_t>> seg_feat(P), seg_rel(P);
-  std::vector<std::vector<TEntry>> tent(P);
-  for (size_t i = 0; i < P; i++) {
-    fmx_handle x = g->hs[i];
-    const Slot& s = *sl[i];
-    *bad = i;
-    const uint32_t nseg = s.nseg;
-    seg_feat[i].resize(nseg); seg_rel[i].resize((size_t)nseg + 1); tent[i].resize((size_t)s.nnz);
-    if (nseg) {
-      if (hipSetDevice(x->device) != hipSuccess ||
-          hipMemcpy(seg_feat[i].data(), s.seg_feat, (size_t)nseg * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-          hipMemcpy(seg_rel[i].data(), s.seg_rel, (size_t)nseg * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-          hipMemcpy(tent[i].data(), s.t_ent, (size_t)s.nnz * sizeof(TEntry), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(x, FMX_E_HIP, "fmx_group_als_begin: copying the columns of shard %zu failed", i);
-    }
-    seg_rel[i][nseg] = (uint32_t)s.nnz;
-    const Shard sh = make_shard(x->cfg);
-    for (uint32_t sg = 0; sg < nseg; sg++) cols.push_back(Col{sh.global(seg_feat[i][sg]), (uint32_t)i, sg});
-  }
-  std::sort(cols.begin(), cols.end(), [](const Col& a, const Col& b) { return a.gid < b.gid; });
-  std::vector<uint32_t> rowlevel(std::max<uint32_t>(n_rows, 1), 0);
-  std::vector<std::vector<uint32_t>> lvl(P);
-  for (size_t i = 0; i < P; i++) lvl[i].resize(seg_feat[i].size());
-  uint32_t n_levels = 0;
-  for (const Col& c : cols) {
-    const auto& rel = seg_rel[c.shard];
-    const auto& te = tent[c.shard];
-    uint32_t l = 0;
-    for (uint32_t q = rel[c.seg]; q < rel[c.seg + 1]; q++) l = std::max(l, rowlevel[te[q].e]);
-    l += 1;
-    for (uint32_t q = rel[c.seg]; q < rel[c.seg + 1]; q++) rowlevel[te[q].e] = l;
-    lvl[c.shard][c.seg] = l - 1;
-    n_levels = std::max(n_levels, l);
-  }
-  for (size_t i = 0; i < P; i++) {
-    fmx_handle x = g->hs[i];
-    const uint32_t nseg = sl[i]->nseg;
-    *bad = i;
-    std::vector<uint32_t>& lp = *level_ptr[i];
-    lp.assign((size_t)n_levels + 1, 0);                             // the SAME number of levels on every shard (some may be empty)
-    for (uint32_t sg = 0; sg < nseg; sg++) lp[lvl[i][sg] + 1]++;
-    for (uint32_t l = 0; l < n_levels; l++) lp[l + 1] += lp[l];
-    std::vector<uint32_t> list(std::max<uint32_t>(nseg, 1)), fill(lp.begin(), lp.end());
-    for (uint32_t sg = 0; sg < nseg; sg++) list[fill[lvl[i][sg]]++] = sg;
-    for (uint32_t sg = 0; sg < nseg; sg++) seen[i][seg_feat[i][sg]] = 1;
-    HIPCHK(x, hipSetDevice(x->device));
-    HIPCHK(x, fmx_dev_alloc(d_list[i], list.size() * 4));
-    HIPCHK(x, hipMemcpy(*d_list[i], list.data(), list.size() * 4, hipMemcpyHostToDevice));
-  }
-  *bad = 0;
-  return FMX_OK;
-}
-
-// fmx_group_als_begin: every shard builds X^T of its own features (of the main rows and of every kept block's rows); the levels
-// are global (global_levels), the first prediction is all-reduced (group_repredict)
 int fmx_group_als_begin(fmx_group g, int train_slot) {
   if (!g) return FMX_E_ARG;
   for (fmx_handle x : g->hs) if (!x) return FMX_E_STATE;
-  fmx_handle h = g->hs[0];
-  if (g->kind == GROUP_SINGLE) { int rc = fmx_als_begin(h, train_slot); if (rc) g->err = h->err; return rc; }
-  const size_t P = g->hs.size();
-  uint32_t N = 0;
-  size_t R = 0;
-  auto bail = [&](int rc, fmx_handle x) { g->err = x->err; for (fmx_handle y : g->hs) als_free(y); return rc; };
-  for (size_t i = 0; i < P; i++) {
-    fmx_handle x = g->hs[i];
-    int rc = check_slot(x, train_slot, true);
-    if (rc == FMX_OK) rc = lag_flush(x);
-    if (rc) return bail(rc, x);
-    if (hipSetDevice(x->device) != hipSuccess || hipStreamSynchronize(x->stream) != hipSuccess) return bail(fail(x, FMX_E_HIP, "fmx_group_als_begin: device %d", x->device), x);
-    als_free(x);
-    Slot& s = x->slots[train_slot];
-    if (s.n_rows == 0) return bail(fail(x, FMX_E_ARG, "fmx_group_als_begin: empty training set"), x);
-    if (i == 0) { N = s.n_rows; R = s.blocks.size(); }
-    else if (s.n_rows != N) return bail(fail(x, FMX_E_STATE, "the shards hold different numbers of rows"), x);
-    if (s.blocks.size() != R) return bail(fail(x, FMX_E_STATE, "the shards hold different relation blocks"), x);
-    for (size_t r = 0; r < R; r++)
-      if (s.blocks[r]->rows.n_rows != g->hs[0]->slots[train_slot].blocks[r]->rows.n_rows)
-        return bail(fail(x, FMX_E_STATE, "the shards hold different relation blocks"), x);
-    rc = ensure_segments(x, s, s.n_rows);
-    for (size_t r = 0; r < R && rc == FMX_OK; r++)                  // (a shard that owns none of a block's attributes has no columns there)
-      if (s.blocks[r]->rows.nnz) rc = ensure_segments(x, s.blocks[r]->rows, std::max<uint32_t>(s.blocks[r]->rows.n_rows, 1));
-    if (rc) return bail(rc, x);
-    x->als.slot = train_slot;
-    x->als.blk.resize(R);
+  if (g->kind == GROUP_SINGLE) { int rc = fmx_als_begin(g->hs[0], train_slot); if (rc) g->err = g->hs[0]->err; return rc; }
+  size_t bad = 0;
+  const int rc = als_begin_shards(g->hs, g, train_slot, "fmx_group_als_begin", &bad);
+  if (rc != FMX_OK) {                                                // a failed set-up leaves no session behind on any shard
+    g->err = g->hs[bad]->err;
+    for (fmx_handle y : g->hs) als_free(y);
   }
-  // ---- levels of the main features, then of every block's attributes over the block's own rows (two block attributes conflict
-  //      iff they share a block row)
-  std::vector<std::vector<uint8_t>> seen(P);
-  for (size_t i = 0; i < P; i++) seen[i].assign((size_t)g->hs[i]->n_local, 0);
-  {
-    std::vector<Slot*> sl(P);
-    std::vector<std::vector<uint32_t>*> lp(P);
-    std::vector<uint32_t**> dl(P);
-    size_t bad = 0;
-    for (size_t i = 0; i < P; i++) { sl[i] = &g->hs[i]->slots[train_slot]; lp[i] = &g->hs[i]->als.level_ptr; dl[i] = &g->hs[i]->als.level_list; }
-    int rc = global_levels(g, sl, N, lp, dl, seen, &bad);
-    if (rc) return bail(rc, g->hs[bad]);
-    for (size_t r = 0; r < R; r++) {
-      for (size_t i = 0; i < P; i++) {
-        sl[i] = &g->hs[i]->slots[train_slot].blocks[r]->rows;
-        lp[i] = &g->hs[i]->als.blk[r].level_ptr; dl[i] = &g->hs[i]->als.blk[r].level_list;
-      }
-      rc = global_levels(g, sl, g->hs[0]->slots[train_slot].blocks[r]->rows.n_rows, lp, dl, seen, &bad);
-      if (rc) return bail(rc, g->hs[bad]);
-    }
-  }
-  for (size_t i = 0; i < P; i++) {
-    fmx_handle x = g->hs[i];
-    AlsState& a = x->als;
-    Slot& s = x->slots[train_slot];
-    const uint32_t nseg = s.nseg;
-    hipError_t er = hipSetDevice(x->device);
-    if (er == hipSuccess) er = fmx_dev_alloc(&a.seen, seen[i].size());
-    if (er == hipSuccess) er = hipMemcpy(a.seen, seen[i].data(), seen[i].size(), hipMemcpyHostToDevice);
-    if (er == hipSuccess) er = fmx_dev_alloc(&a.e, (size_t)N * sizeof(EQ));
-    if (er == hipSuccess) er = fmx_dev_alloc(&a.q, (size_t)N * (size_t)x->KP * sizeof(double));
-    if (er == hipSuccess) er = fmx_dev_alloc(&a.delta, (size_t)N * sizeof(EQ));
-    if (er == hipSuccess) er = hipMemsetAsync(a.delta, 0, (size_t)N * sizeof(EQ), x->stream);
-    if (er == hipSuccess) er = fmx_dev_alloc(&a.epart, (size_t)N * sizeof(double));
-    if (er == hipSuccess && x->cfg.num_factor > 0 && nseg > 0) {
-      a.vt_stride = ((size_t)nseg + 63) & ~(size_t)63;
-      er = fmx_dev_alloc(&a.vt, (size_t)x->cfg.num_factor * a.vt_stride * sizeof(float));
-    }
-    for (size_t r = 0; r < R && er == hipSuccess; r++) {         // the kept blocks' caches (replicated) and their per-level changes
-      const BlockRows& br = *s.blocks[r];
-      AlsBlock& ab = a.blk[r];
-      const size_t B = std::max<uint32_t>(br.rows.n_rows, 1);
-      er = fmx_dev_alloc(&ab.cache, (size_t)7 * B * sizeof(double));
-      if (er == hipSuccess) er = hipMemsetAsync(ab.cache, 0, (size_t)7 * B * sizeof(double), x->stream);
-      if (er == hipSuccess) er = fmx_dev_alloc(&ab.qb_all, (size_t)x->KP * B * sizeof(double));
-      if (er == hipSuccess) er = fmx_dev_alloc(&ab.cpart, B * sizeof(double));
-      if (er == hipSuccess) er = fmx_dev_alloc(&ab.delta, (size_t)4 * B * sizeof(double));
-      if (er == hipSuccess) er = hipMemsetAsync(ab.delta, 0, (size_t)4 * B * sizeof(double), x->stream);
-      const double avg_col = br.rows.nseg ? (double)br.rows.nnz / (double)br.rows.nseg : 0.0;
-      ab.lanes = avg_col <= 5.0 ? 4 : (avg_col <= 12.0 ? 8 : (avg_col <= 40.0 ? 16 : 64));
-    }
-    if (er != hipSuccess) return bail(fail(x, FMX_E_HIP, "fmx_group_als_begin: %s", hipGetErrorString(er)), x);
-  }
-  // ---- first prediction and e -= target (fm_learn_mcmc_simultaneous.h:69-86)
-  {
-    size_t bad = 0;
-    int rc = group_repredict(g, g->hs, &bad);
-    if (rc) return bail(rc, g->hs[bad]);
-  }
-  const dim3 g1(std::min<uint32_t>((N + 255) / 256, 2048)), b1(256);
-  for (fmx_handle x : g->hs) {
-    hipSetDevice(x->device);
-    hipLaunchKernelGGL(k_als_sub_target, g1, b1, 0, x->stream, x->als.e, x->slots[train_slot].target, N);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(x->stream) != hipSuccess)
-      return bail(fail(x, FMX_E_HIP, "fmx_group_als_begin: first prediction failed on shard device %d", x->device), x);
-  }
-  return FMX_OK;
+  return rc;
 }
 
 int fmx_group_als_sweep(fmx_group g, const fmx_als_opts* opts, fmx_als_stats* stats) {
