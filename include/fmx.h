@@ -542,6 +542,73 @@ typedef struct fmx_eval_query {
 int fmx_evaluate_by_query(fmx_handle h, int slot, const fmx_eval_opts *opts, fmx_eval_query *out,
                           uint64_t *num2_q, uint32_t *pos_q, uint32_t *neg_q);
 
+/* ---- exact per-query NDCG, recall and precision at K of a slot, reduced on the device ----------
+ * Of the rows of a query, how good are the K the model puts on top?  Relevance of a row is binary, target >= 0 (fm_learn.h:118);
+ * the scores are the fp32 raw y-hat of fmx_predict, compared as floats (+0 == -0); the query ids are fmx_set_row_queries'.
+ * Inside query q the rows are ranked by descending score.  Rows of equal score form a TIE RUN that occupies the 0-based ranks
+ * [a, b), t = b - a rows of which p are relevant.  The metric is the EXPECTATION over a uniformly random order inside every tie
+ * run (McSherry & Najork, "Computing information retrieval performance measures efficiently in the presence of tied scores",
+ * ECIR 2008), so it does not depend on how a sort placed equal scores.  With the discount table
+ *   D[0] = 0,  D[r + 1] = D[r] + 1.0 / log2((double)r + 2.0)            (fmx_rank_discounts: sequential, fp64)
+ * and a' = min(a, K), b' = min(b, K), in exactly this operation order:
+ *   hits_q@K      = sum over the runs with a < K of ((double)p * (double)(b' - a')) / (double)t
+ *   dcg_q@K       = sum over the runs with a < K of ((double)p * (D[b'] - D[a']))   / (double)t
+ *   ndcg_q@K      = dcg_q / D[min(pos_q, K)]
+ *   recall_q@K    = hits_q / pos_q
+ *   precision_q@K = hits_q / K                    (/ K even when the query has fewer rows)
+ * Without ties every run is one row and a term is p * (D[a + 1] - D[a]): the textbook 1 / log2(a + 2) up to the rounding of
+ * that difference.  A query is RELEVANT when pos_q > 0; only relevant queries enter the means: ndcg, recall and precision are
+ * the plain means over the relevant queries, hits is the sum of hits_q over them, tied_queries counts the relevant queries in
+ * which some run with a < K has 0 < p < t (where breaking the ties would have changed the classic metric).
+ *   NaN scores (pooled.nan_rows > 0) and regression handles: nothing is sorted, every mean is NaN, every count 0, the arrays
+ *               zero-filled, topk_seconds 0; by_query is exactly fmx_evaluate_by_query's result for that state.
+ *   relevant_queries == 0: the means are NaN, hits and tied_queries 0.
+ *   an empty slot: FMX_OK, by_query = the empty result, the means NaN, the arrays zero-filled.
+ *   a slot of one class still runs the by-query pipeline.
+ * Pipeline: ONE scoring pass and ONE sort -- the call does what fmx_evaluate_by_query does (by_query is field for field its
+ * result) and then reduces the top min(rows_q, k_max) sorted positions of every query segment over the same sorted keys and
+ * scans: one wavefront per query, the lane at the tail of a tie run adds the run's terms, fp64 sums lane -> wavefront (xor
+ * butterfly) -> block partials -> one final wavefront, on a grid that is a fixed function of n_queries.  No float atomics: two
+ * calls with unchanged parameters are bit-identical in every field except the times.
+ * Device memory beyond fmx_evaluate_by_query's, allocated and freed inside the call: at most 4 + 16 * n_cutoffs bytes per
+ * query (4: the end of the query's segment; 16 per cutoff only when dcg_q / hits_q are asked for), 8 * (k_max + 1) bytes of
+ * discount table (k_max = the largest cutoff; at most 512 KiB) and (blocks + 1) x 21 x 8 bytes of block partials with the result
+ * row behind them (blocks = ceil(n_queries / 4), at most 2048: 344 KiB at most).
+ * Refusals: everything fmx_evaluate_by_query refuses, with the same codes; FMX_E_ARG for NULL opts or out, n_cutoffs outside
+ * 1 .. FMX_RANK_MAX_CUTOFFS, a k of 0 or above FMX_RANK_MAX_K, cutoffs that are not strictly ascending; FMX_E_UNSUPPORTED for a
+ * feature shard passed to the per-handle call.  fmx_rank_discounts: FMX_E_ARG for NULL out or k_max above FMX_RANK_MAX_K.
+ * Rows are not weighted; relevance is not graded.
+ * Added without an ABI version change: a caller detects the feature by the symbol fmx_evaluate_rank. */
+#define FMX_RANK_MAX_CUTOFFS 4
+#define FMX_RANK_MAX_K 65536u
+typedef struct fmx_rank_opts {
+  uint32_t link, flags;                       /* as fmx_eval_opts; flags 0 */
+  uint32_t n_cutoffs;                         /* 1 .. FMX_RANK_MAX_CUTOFFS */
+  uint32_t k[FMX_RANK_MAX_CUTOFFS];           /* strictly ascending, 1 .. FMX_RANK_MAX_K */
+  uint32_t reserved;
+} fmx_rank_opts;
+
+typedef struct fmx_rank_at {
+  uint32_t k, reserved;
+  uint64_t tied_queries;                      /* relevant queries with a mixed tie run that begins above the cutoff */
+  double hits, ndcg, recall, precision;       /* hits: a sum; the others: means over the relevant queries */
+} fmx_rank_at;
+
+typedef struct fmx_eval_rank {
+  fmx_eval_query by_query;                    /* field for field what fmx_evaluate_by_query returns, times aside */
+  uint64_t relevant_queries;                  /* pos_q > 0 */
+  uint32_t n_cutoffs, reserved;
+  fmx_rank_at at[FMX_RANK_MAX_CUTOFFS];
+  double device_seconds, topk_seconds;        /* whole call / the added kernels only */
+} fmx_eval_rank;
+
+/* D[0 .. k_max] as above into out[k_max + 1].  Host arithmetic: no device, no handle.  The device call uploads this table. */
+int fmx_rank_discounts(uint32_t k_max, double *out);
+
+/* dcg_q, hits_q: NULL or host double[n_queries * n_cutoffs], query-major */
+int fmx_evaluate_rank(fmx_handle h, int slot, const fmx_rank_opts *opts, fmx_eval_rank *out,
+                      double *dcg_q, double *hits_q);
+
 /* ---- the averaged predictions of `-method mcmc`, kept on the device ----------------------------
  * The prediction of fm_learn_mcmc_simultaneous is not that of one model but the running mean over the draws (pred_sum_all / (i + 1),
  * fm_learn_mcmc_simultaneous.h:129-161, 213-264).  A posterior accumulator keeps the three vectors of that file for one slot on the
@@ -856,6 +923,8 @@ int fmx_group_evaluate_ex(fmx_group g, int slot, const fmx_eval_opts *opts, fmx_
 int fmx_group_set_row_queries(fmx_group g, int slot, const uint32_t *qid, uint32_t n_queries);
 int fmx_group_evaluate_by_query(fmx_group g, int slot, const fmx_eval_opts *opts, fmx_eval_query *out,
                                 uint64_t *num2_q, uint32_t *pos_q, uint32_t *neg_q);
+/* fmx_evaluate_rank over the shards of a group (see there): the finished y-hat chunks are reduced on the first shard's device */
+int fmx_group_evaluate_rank(fmx_group g, int slot, const fmx_rank_opts *opts, fmx_eval_rank *out, double *dcg_q, double *hits_q);
 /* fmx_post_* over the shards of a group (see there) */
 int fmx_group_post_begin(fmx_group g, int slot, const fmx_post_opts *opts);
 int fmx_group_post_accumulate(fmx_group g, int slot, fmx_post_stats *out);

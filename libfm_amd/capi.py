@@ -128,6 +128,24 @@ class EvalQuery(C.Structure):
                 ("device_seconds", C.c_double), ("rank_seconds", C.c_double)]
 
 
+RANK_MAX_CUTOFFS, RANK_MAX_K = 4, 65536             # FMX_RANK_MAX_CUTOFFS, FMX_RANK_MAX_K
+
+
+class RankOpts(C.Structure):                       # fmx_rank_opts
+    _fields_ = [("link", C.c_uint32), ("flags", C.c_uint32), ("n_cutoffs", C.c_uint32), ("k", C.c_uint32 * RANK_MAX_CUTOFFS),
+                ("reserved", C.c_uint32)]
+
+
+class RankAt(C.Structure):                         # fmx_rank_at
+    _fields_ = [("k", C.c_uint32), ("reserved", C.c_uint32), ("tied_queries", C.c_uint64), ("hits", C.c_double), ("ndcg", C.c_double),
+                ("recall", C.c_double), ("precision", C.c_double)]
+
+
+class EvalRank(C.Structure):                       # fmx_eval_rank
+    _fields_ = [("by_query", EvalQuery), ("relevant_queries", C.c_uint64), ("n_cutoffs", C.c_uint32), ("reserved", C.c_uint32),
+                ("at", RankAt * RANK_MAX_CUTOFFS), ("device_seconds", C.c_double), ("topk_seconds", C.c_double)]
+
+
 POST_THIS, POST_ALL, POST_LATE = 0, 1, 2   # FMX_POST_*: the last draw, the mean over all draws, the mean over the draws from burn_in on
 
 
@@ -249,6 +267,8 @@ SYMBOLS = [
     ("fmx_evaluate_ex", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalEx)]),
     ("fmx_set_row_queries", C.c_int, [H, C.c_int, C.c_void_p, C.c_uint32]),
     ("fmx_evaluate_by_query", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalQuery), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("fmx_rank_discounts", C.c_int, [C.c_uint32, C.c_void_p]),
+    ("fmx_evaluate_rank", C.c_int, [H, C.c_int, C.POINTER(RankOpts), C.POINTER(EvalRank), C.c_void_p, C.c_void_p]),
     ("fmx_post_begin", C.c_int, [H, C.c_int, C.POINTER(PostOpts)]),
     ("fmx_post_accumulate", C.c_int, [H, C.c_int, C.POINTER(PostStats)]),
     ("fmx_post_evaluate_ex", C.c_int, [H, C.c_int, C.c_uint32, C.POINTER(EvalEx)]),
@@ -281,6 +301,7 @@ SYMBOLS = [
     ("fmx_group_evaluate_ex", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalEx)]),
     ("fmx_group_set_row_queries", C.c_int, [H, C.c_int, C.c_void_p, C.c_uint32]),
     ("fmx_group_evaluate_by_query", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalQuery), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("fmx_group_evaluate_rank", C.c_int, [H, C.c_int, C.POINTER(RankOpts), C.POINTER(EvalRank), C.c_void_p, C.c_void_p]),
     ("fmx_group_post_begin", C.c_int, [H, C.c_int, C.POINTER(PostOpts)]),
     ("fmx_group_post_accumulate", C.c_int, [H, C.c_int, C.POINTER(PostStats)]),
     ("fmx_group_post_evaluate_ex", C.c_int, [H, C.c_int, C.c_uint32, C.POINTER(EvalEx)]),
@@ -410,6 +431,44 @@ def _evaluate_by_query(obj, fn, handle, slot, link, per_query, n_queries):
     pos, neg = np.zeros(n_queries, dtype=np.uint32), np.zeros(n_queries, dtype=np.uint32)
     obj._chk(fn(handle, slot, C.byref(opts), C.byref(ev), _ptr(num2), _ptr(pos), _ptr(neg)))
     return ev, num2, pos, neg
+
+
+def _rank_opts(cutoffs, link):
+    """fmx_rank_opts of a sequence of cutoffs; what the struct cannot hold is left for the library to refuse"""
+    ks = [int(k) for k in cutoffs]
+    if any(not 0 <= k <= 0xFFFFFFFF for k in ks):
+        raise ValueError("evaluate_rank: cutoffs are non-negative integers below 2^32")
+    opts = RankOpts(link, 0, len(ks))
+    for j, k in enumerate(ks[:RANK_MAX_CUTOFFS]):
+        opts.k[j] = k
+    return opts
+
+
+def _evaluate_rank(obj, fn, handle, slot, cutoffs, link, per_query, n_queries):
+    """the body of Handle / Group.evaluate_rank"""
+    opts, ev = _rank_opts(cutoffs, link), EvalRank()
+    if not per_query:
+        obj._chk(fn(handle, slot, C.byref(opts), C.byref(ev), None, None))
+        return ev
+    if n_queries is None:                            # no ids were set through this object: the library says so
+        obj._chk(fn(handle, slot, C.byref(opts), C.byref(ev), None, None))
+        raise RuntimeError("evaluate_rank(per_query=True): the query ids of slot %d were not set through this object" % slot)
+    shape = (n_queries, min(max(opts.n_cutoffs, 1), RANK_MAX_CUTOFFS))
+    dcg, hits = np.zeros(shape, dtype=np.float64), np.zeros(shape, dtype=np.float64)
+    obj._chk(fn(handle, slot, C.byref(opts), C.byref(ev), _ptr(dcg), _ptr(hits)))
+    return ev, dcg, hits
+
+
+def rank_discounts(k_max):
+    """D[0 .. k_max] of fmx_evaluate_rank: D[r + 1] = D[r] + 1 / log2(r + 2) (fmx_rank_discounts; host arithmetic, no device)"""
+    if not 0 <= int(k_max) <= 0xFFFFFFFF:
+        raise ValueError("rank_discounts: k_max out of range")
+    out = np.zeros(min(int(k_max), RANK_MAX_K) + 1, dtype=np.float64)
+    lib = load()
+    rc = lib.fmx_rank_discounts(int(k_max), _ptr(out))
+    if rc:
+        raise FmxError(rc, (lib.fmx_last_error(None) or b"").decode())
+    return out
 
 
 class Handle:
@@ -561,6 +620,11 @@ class Handle:
         """exact AUC inside every query (GAUC), reduced on the device (fmx_evaluate_by_query): the EvalQuery struct, or with
         per_query (struct, num2_q uint64, pos_q uint32, neg_q uint32), each [n_queries]"""
         return _evaluate_by_query(self, self.lib.fmx_evaluate_by_query, self.h, slot, link, per_query, self._nq.get(slot))
+
+    def evaluate_rank(self, slot, cutoffs, link=LINK_LOGISTIC, per_query=False):
+        """exact tie-averaged NDCG / recall / precision at up to four ascending cutoffs inside every query, reduced on the device
+        (fmx_evaluate_rank): the EvalRank struct, or with per_query=True (EvalRank, dcg_q, hits_q), float64 [n_queries, n_cutoffs]"""
+        return _evaluate_rank(self, self.lib.fmx_evaluate_rank, self.h, slot, cutoffs, link, per_query, self._nq.get(slot))
 
     # the posterior accumulator of a slot (fmx_post_*): MCMC's averaged predictions on the device
     def post_begin(self, slot, burn_in=5, eval_rows=0):
@@ -1036,6 +1100,10 @@ class Group:
     def evaluate_by_query(self, slot, link=LINK_LOGISTIC, per_query=False):
         """Handle.evaluate_by_query over the shards (fmx_group_evaluate_by_query)"""
         return _evaluate_by_query(self, self.lib.fmx_group_evaluate_by_query, self.g, slot, link, per_query, self._nq.get(slot))
+
+    def evaluate_rank(self, slot, cutoffs, link=LINK_LOGISTIC, per_query=False):
+        """Handle.evaluate_rank over the shards (fmx_group_evaluate_rank)"""
+        return _evaluate_rank(self, self.lib.fmx_group_evaluate_rank, self.g, slot, cutoffs, link, per_query, self._nq.get(slot))
 
     # the posterior accumulator of a slot (fmx_post_*): MCMC's averaged predictions on the device
     def post_begin(self, slot, burn_in=5, eval_rows=0):

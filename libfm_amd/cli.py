@@ -28,6 +28,10 @@ auc_test / logloss_train / logloss_test columns of -rlog; stdout stays byte for 
 query (user, session).  After every iteration the impression-weighted exact AUC inside the queries (GAUC), reduced on the device
 (fmx_evaluate_by_query), as one "#Iter=  i\tgauc: Train=..\tTest=.." line on stderr (nan for a set without ids) and gauc_* /
 auc_within_* columns of -rlog; stdout stays byte for byte what it is without the flags.
+-rank_at K1,K2,... (needs -test_queries; at most 4 ascending integers in 1 .. 65536): after every iteration the exact tie-averaged
+NDCG at each K inside the queries, reduced on the device (fmx_evaluate_rank: rows of equal score share their ranks in expectation,
+so the figure does not depend on a sort's tie order), as one "#Iter=  i\tndcg@K: Train=..\tTest=.." line per K on stderr and
+ndcg@K_* / recall@K_* / precision@K_* columns of -rlog; stdout stays byte for byte what it is without the flag.
 -device_average 1 (als, mcmc): the test predictions and their running sums stay on the device (fmx_post_accumulate); the #Iter=
 lines gain the reference's Test(ll) column on -task c, -rlog its rmse_mcmc_* / acc_mcmc_* / ll_mcmc_* columns, and -metrics then
 scores the averaged test prediction ("#Iter=  i\tauc: Test=.." on stderr, auc_test / logloss_test) -- with -method mcmc too.
@@ -80,6 +84,8 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "test_queries": "filename with one query id (non-negative integer) per test row: per-query AUC (GAUC) per iteration on"
                          " stderr; -task c with sgd, sgda, als",
          "train_queries": "the same for the train rows; needs -test_queries",
+         "rank_at": "'K1,K2,...' (at most 4, ascending, 1 .. 65536): tie-averaged NDCG / recall / precision at K inside the queries per"
+                    " iteration on stderr and in -rlog; needs -test_queries",
          "device_average": "als, mcmc: 1 = keep the test predictions and their running mean on the device; default=0",
          "optimizer": "sgd: sgd | adagrad (a per-coordinate step size on the minibatch rule) | ftrl (FTRL-proximal with L1 on the same rule:"
                       " exact zeros); default=sgd",
@@ -313,6 +319,26 @@ def _main(argv):
             raise ValueError("-train_queries needs -test_queries" if "test_queries" not in a else "-test_queries needs a filename")
         if "train_queries" in a and not a["train_queries"]:
             raise ValueError("-train_queries needs a filename")
+    rank_at = ()
+    if "rank_at" in a:
+        if method in ("mcmc", "bpr"):
+            raise ValueError("-rank_at is not supported with -method %s" % method +
+                             (": its prediction averages the draws, no single model scores it" if method == "mcmc" else
+                              ": the pairwise learner reports its own accuracy and loss"))
+        if a["task"] != "c":
+            raise ValueError("-rank_at needs -task c: a row is relevant by the sign of its classification target")
+        if not a.get("test_queries"):
+            raise ValueError("-rank_at needs -test_queries")
+        try:
+            rank_at = tuple(int(x) for x in split_list(a["rank_at"]))
+        except ValueError:
+            raise ValueError("-rank_at needs integers: 'K1,K2,...' (got '%s')" % a["rank_at"])
+        if not 1 <= len(rank_at) <= L.RANK_MAX_CUTOFFS:
+            raise ValueError("-rank_at takes 1 .. %d cutoffs (got %d)" % (L.RANK_MAX_CUTOFFS, len(rank_at)))
+        if any(not 1 <= k <= L.RANK_MAX_K for k in rank_at):
+            raise ValueError("-rank_at: a cutoff is an integer in 1 .. %d" % L.RANK_MAX_K)
+        if any(y <= x for x, y in zip(rank_at, rank_at[1:])):
+            raise ValueError("-rank_at: the cutoffs must be strictly ascending")
 
     print("Loading train...\t")
     train = L.Data(*D.load(a["train"]))
@@ -464,6 +490,8 @@ def _main(argv):
         l.set_queries(test, test_queries)
     if train_queries is not None:
         l.set_queries(train, train_queries)
+    if rank_at:
+        l.rank_cutoffs = rank_at
     if implicit:
         print("Loading interactions...\t")
         inter = read_interactions(a["interactions"], train.num_cases, cand.num_cases)

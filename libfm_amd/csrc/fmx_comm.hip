@@ -1003,6 +1003,24 @@ int fmx_group_evaluate_by_query(fmx_group g, int slot, const fmx_eval_opts* opts
   return group_reduce_scores(g, slot, who, [&](const float* y) { return evalq_scores(h0, s, y, 0, link, out, num2_q, pos_q, neg_q); });
 }
 
+// fmx_evaluate_rank over the shards (fmx_rankq.hip): the by-query reduction above, then the top of every query segment
+int fmx_group_evaluate_rank(fmx_group g, int slot, const fmx_rank_opts* opts, fmx_eval_rank* out, double* dcg_q, double* hits_q) {
+  static const char who[] = "fmx_group_evaluate_rank";
+  if (!g) return FMX_E_ARG;
+  for (auto m : g->hs) if (!m) return gfail(g, FMX_E_STATE, "a member of the group was destroyed");
+  fmx_handle h0 = g->hs[0];
+  fmx_handle cur = h0;
+  if (g->kind == GROUP_SINGLE) { GCHK(g, fmx_evaluate_rank(cur, slot, opts, out, dcg_q, hits_q)); return FMX_OK; }
+  if (!out) return gfail(g, FMX_E_ARG, "%s: out is NULL", who);
+  uint32_t link;
+  GCHK(g, rankq_check_opts(cur, who, opts, &link));
+  GCHK(g, evalq_check_slot(cur, who, slot));
+  const Slot& s = h0->slots[slot];
+  rankq_empty(out, opts, s.n_queries, dcg_q, hits_q);
+  if (s.n_rows == 0) { out->by_query.empty_queries = s.n_queries; return FMX_OK; }
+  return group_reduce_scores(g, slot, who, [&](const float* y) { return rankq_scores(h0, s, y, 0, link, opts, out, dcg_q, hits_q); });
+}
+
 // fmx_post_* over the shards (fmx_post.hip): the accumulator lives on the first shard's slot; only _accumulate needs the other
 // shards, for the finished y-hat chunks, which stay on the first shard's device like fmx_group_evaluate_ex's
 #define GROUP_POST_HEAD(who_)                                                                        \

@@ -2,7 +2,7 @@
 // (DESIGN.md section 16).  The scores come from slot_scores and the pooled metrics from eval_ex_scores, both fmx_evaluate_ex's
 // (fmx_eval.hip); the same scores then feed this unit's pipeline: 64-bit keys with the query id above the score, fmx_evaluate_ex's
 // sort and two scans (rank_sort_scan), a third scan for the query heads, the segmented rank sum and the reduction over the queries
-// (fmx_evalq_kernels.h).
+// (fmx_evalq_kernels.h).  fmx_evaluate_rank (fmx_rankq.hip) runs the same pipeline through evalq_scores_keep and reads its scratch.
 // The group entry points are in fmx_comm.hip, next to fmx_group_evaluate_ex.
 #include "fmx_internal.h"
 #include "fmx_evalq_kernels.h"
@@ -60,9 +60,13 @@ int set_row_queries_impl(fmx_handle h, const char* who, int slot, const uint32_t
 // finished y-hat (add_w0 = 0), exactly as eval_ex_scores takes them -- which fills out->pooled first and leaves the scores as they
 // are, so the rows are scored once.  The caller has recorded h->ev0 where the call's device work began, zeroed *out (evalq_empty)
 // and set out->pooled.flags.  n >= 1, s.n_queries >= 1.
-int evalq_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, uint32_t link, fmx_eval_query* out,
-                 uint64_t* num2_q, uint32_t* pos_q, uint32_t* neg_q) {
+// The scratch is the caller's and outlives the call (fmx_evaluate_rank reduces the top of every query segment from it, fmx_rankq.hip):
+// *sorted is the buffer that holds the sorted keys, or nullptr when nothing was sorted; sc.negbefore, sc.runhead and sc.qhead are
+// the three scans over it and sc.perq holds num2 [n_queries] (8 bytes each), then pos and neg (4 + 4).  The stream is drained.
+int evalq_scores_keep(fmx_handle h, const Slot& s, const float* score, int add_w0, uint32_t link, fmx_eval_query* out,
+                      uint64_t* num2_q, uint32_t* pos_q, uint32_t* neg_q, EvalScratch& sc, const unsigned long long** sorted) {
   const uint32_t n = s.n_rows, nq = s.n_queries;
+  *sorted = nullptr;
   int rc = eval_ex_scores(h, s, score, add_w0, link, &out->pooled);
   if (rc) return rc;
   out->device_seconds = out->pooled.device_seconds;
@@ -74,7 +78,6 @@ int evalq_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, ui
   while ((1ull << id_bits) < nq) id_bits++;                                    // ceil(log2(n_queries)): 0 .. 31
   const int key_bits = EVALQ_QID_SHIFT + id_bits;
   const uint32_t qblk = evalx_grid(nq);
-  EvalScratch sc;
   HIPCHK(h, fmx_dev_alloc(&sc.keys0, (size_t)n * 8));
   HIPCHK(h, fmx_dev_alloc(&sc.qhead, (size_t)n * 4));
   HIPCHK(h, fmx_dev_alloc(&sc.perq, (size_t)nq * 16));
@@ -125,7 +128,15 @@ int evalq_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, ui
     out->gauc = res.d[0] / (double)out->valid_rows;
     out->auc_macro = res.d[1] / (double)out->valid_queries;
   }
+  *sorted = ks;
   return FMX_OK;
+}
+
+int evalq_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, uint32_t link, fmx_eval_query* out,
+                 uint64_t* num2_q, uint32_t* pos_q, uint32_t* neg_q) {
+  EvalScratch sc;
+  const unsigned long long* ks;
+  return evalq_scores_keep(h, s, score, add_w0, link, out, num2_q, pos_q, neg_q, sc, &ks);
 }
 
 extern "C" {

@@ -1,5 +1,5 @@
 // fmx_internal.h -- shared by the translation units of libfmx.so (fmx_core.hip, fmx_sgd.hip, fmx_als.hip, fmx_comm.hip, fmx_pair.hip, fmx_topk.hip,
-// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip; fmx_io.hip needs none of it).
+// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip; fmx_io.hip needs none of it).
 // The C-ABI is include/fmx.h; nothing declared here is exported.
 #pragma once
 #pragma GCC visibility push(default)      // the C-ABI is the only thing libfmx.so exports (-fvisibility=hidden)
@@ -325,6 +325,15 @@ void evalq_empty(fmx_eval_query* out, uint32_t n_queries);
 void evalq_zero_per_query(uint32_t n_queries, uint64_t* num2_q, uint32_t* pos_q, uint32_t* neg_q);
 int evalq_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, uint32_t link, fmx_eval_query* out,
                  uint64_t* num2_q, uint32_t* pos_q, uint32_t* neg_q);
+// ... the same with the caller's scratch left alive (the sorted keys, the three scans, the per-query counts), for rankq_scores
+int evalq_scores_keep(fmx_handle h, const Slot& s, const float* score, int add_w0, uint32_t link, fmx_eval_query* out,
+                      uint64_t* num2_q, uint32_t* pos_q, uint32_t* neg_q, EvalScratch& sc, const unsigned long long** sorted);
+// fmx_rankq.hip: the checks, the empty result and the whole reduction of fmx_evaluate_rank (evalq_scores_keep, then the top-K
+// reduction over the same sorted keys), shared with fmx_group_evaluate_rank (fmx_comm.hip)
+int rankq_check_opts(fmx_handle h, const char* who, const fmx_rank_opts* opts, uint32_t* link);
+void rankq_empty(fmx_eval_rank* out, const fmx_rank_opts* opts, uint32_t n_queries, double* dcg_q, double* hits_q);
+int rankq_scores(fmx_handle h, const Slot& s, const float* score, int add_w0, uint32_t link, const fmx_rank_opts* opts,
+                 fmx_eval_rank* out, double* dcg_q, double* hits_q);
 // fmx_post.hip: the posterior accumulator of a slot (include/fmx.h "fmx_post_*").  The *_impl functions are the entry points after
 // the handle-kind check, for the first shard of a group too (fmx_comm.hip); post_accum_scores takes scores that are on h's device.
 struct PostAcc {

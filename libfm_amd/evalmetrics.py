@@ -3,6 +3,7 @@ device to.  Pure Python on purpose -- the AUC numerator is counted with Python i
 
     classification_metrics(scores, target, link="logistic") -> dict with the fields of fmx_eval_ex
     query_metrics(scores, target, qid, n_queries, link="logistic") -> dict with the fields of fmx_eval_query
+    rank_metrics(scores, target, qid, n_queries, cutoffs, link="logistic") -> dict with the fields of fmx_eval_rank (section 20)
 
 ... and of the posterior accumulator (fmx_post_*): PosteriorAverage keeps the three prediction vectors of
 fm_learn_mcmc_simultaneous in numpy fp64; posterior_metric / posterior_evaluate_ex score a vector of means.
@@ -129,6 +130,97 @@ def query_metrics(scores, target, qid, n_queries, link="logistic", per_query=Tru
         out["auc_macro"] = math.fsum(plain) / out["valid_queries"]
     return out
 
+
+# FMX_RANK_MAX_CUTOFFS, FMX_RANK_MAX_K of include/fmx.h, restated: this module is the oracle of the binding and imports none of it
+# (tests/test_rank_metrics_cpu.py holds the two pairs equal)
+RANK_MAX_CUTOFFS, RANK_MAX_K = 4, 65536
+
+
+def rank_discounts(k_max):
+    """D[0 .. k_max] as fmx_rank_discounts computes it: D[r + 1] = D[r] + 1.0 / log2(r + 2.0), sequentially in fp64"""
+    d = [0.0] * (int(k_max) + 1)
+    for r in range(int(k_max)):
+        d[r + 1] = d[r] + 1.0 / math.log2(float(r) + 2.0)
+    return d
+
+
+def rank_runs(scores, positive):
+    """the tie runs of one query by descending score: (a, b, p) with the 0-based ranks [a, b) and p relevant rows among them"""
+    order = sorted(range(len(scores)), key=lambda i: -scores[i])
+    runs, i = [], 0
+    while i < len(order):
+        j = i
+        while j < len(order) and scores[order[j]] == scores[order[i]]:
+            j += 1
+        runs.append((i, j, sum(1 for x in order[i:j] if positive[x])))
+        i = j
+    return runs
+
+
+def rank_metrics(scores, target, qid, n_queries, cutoffs, link="logistic", discounts=None, per_query=True):
+    """CPU restatement of fmx_evaluate_rank (include/fmx.h): a dict with the fields of fmx_eval_rank
+    (`by_query` is query_metrics' dict, `at` a list of dicts, one per cutoff) plus the per-query lists dcg_q and hits_q
+    [n_queries][n_cutoffs] (per_query=False leaves them out: None).  A tie run at the ranks [a, b) with p relevant rows among its
+    t = b - a adds ((double)p * (double)(b' - a')) / (double)t to hits_q and ((double)p * (D[b'] - D[a'])) / (double)t to dcg_q in
+    exactly that operation order; a query's sum over its runs and the means over the relevant queries are math.fsum.
+    `discounts` is the table D (libfm_amd.capi.rank_discounts gives the library's bits); None computes it here."""
+    ks = [int(k) for k in cutoffs]
+    if not 1 <= len(ks) <= RANK_MAX_CUTOFFS:
+        raise ValueError("1 .. %d cutoffs" % RANK_MAX_CUTOFFS)
+    if any(not 1 <= k <= RANK_MAX_K for k in ks) or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError("the cutoffs are strictly ascending integers in 1 .. %d" % RANK_MAX_K)
+    D = rank_discounts(ks[-1]) if discounts is None else [float(x) for x in discounts]
+    if len(D) < ks[-1] + 1:
+        raise ValueError("the discount table has %d entries, the largest cutoff needs %d" % (len(D), ks[-1] + 1))
+    n_queries = int(n_queries)
+    by_query = query_metrics(scores, target, qid, n_queries, link, per_query=False)
+    nan = math.nan
+    out = {"by_query": by_query, "relevant_queries": 0, "n_cutoffs": len(ks),
+           "at": [{"k": k, "tied_queries": 0, "hits": 0.0, "ndcg": nan, "recall": nan, "precision": nan} for k in ks],
+           "device_seconds": 0.0, "topk_seconds": 0.0, "dcg_q": None, "hits_q": None}
+    if per_query:
+        out["dcg_q"] = [[0.0] * len(ks) for _ in range(n_queries)]
+        out["hits_q"] = [[0.0] * len(ks) for _ in range(n_queries)]
+    pooled = by_query["pooled"]
+    if pooled["rows"] == 0 or pooled["nan_rows"]:                     # nothing is sorted
+        return out
+    p = [float(x) for x in np.asarray(scores, dtype=np.float32).reshape(-1)]
+    positive = [float(t) >= 0 for t in np.asarray(target, dtype=np.float32).reshape(-1)]
+    members = {}
+    for i, g in enumerate(int(x) for x in np.asarray(qid).reshape(-1)):
+        members.setdefault(g, []).append(i)
+    sums = [{"hits": [], "ndcg": [], "recall": [], "precision": []} for _ in ks]
+    for g in sorted(members):
+        rows = members[g]
+        pos = sum(1 for i in rows if positive[i])
+        if not pos:
+            continue
+        out["relevant_queries"] += 1
+        runs = rank_runs([p[i] for i in rows], [positive[i] for i in rows])
+        for j, K in enumerate(ks):
+            hit_terms, dcg_terms, tied = [], [], False
+            for a, b, rel in runs:
+                if a >= K:
+                    break
+                t, b1 = b - a, min(b, K)
+                hit_terms.append((float(rel) * float(b1 - a)) / float(t))
+                dcg_terms.append((float(rel) * (D[b1] - D[a])) / float(t))
+                tied = tied or 0 < rel < t
+            hits_q, dcg_q = math.fsum(hit_terms), math.fsum(dcg_terms)
+            if per_query:
+                out["hits_q"][g][j], out["dcg_q"][g][j] = hits_q, dcg_q
+            sums[j]["hits"].append(hits_q)
+            sums[j]["ndcg"].append(dcg_q / D[min(pos, K)])
+            sums[j]["recall"].append(hits_q / float(pos))
+            sums[j]["precision"].append(hits_q / float(K))
+            out["at"][j]["tied_queries"] += 1 if tied else 0
+    R = out["relevant_queries"]
+    if R:
+        for j in range(len(ks)):
+            out["at"][j]["hits"] = math.fsum(sums[j]["hits"])
+            for name in ("ndcg", "recall", "precision"):
+                out["at"][j][name] = math.fsum(sums[j][name]) / float(R)
+    return out
 
 
 # ---- the posterior accumulator (include/fmx.h "fmx_post_*") ---------------------------------------------------------------------

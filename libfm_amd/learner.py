@@ -114,6 +114,7 @@ class FMModel:
 
 
 EXTRA_METRICS = ("auc", "logloss")
+RANK_MAX_CUTOFFS, RANK_MAX_K = capi.RANK_MAX_CUTOFFS, capi.RANK_MAX_K   # of rank_cutoffs (fmx_evaluate_rank)
 
 
 def _log_extra_metrics(learner, i, train, test):
@@ -135,16 +136,27 @@ def _log_extra_metrics(learner, i, train, test):
 def _log_query_metrics(learner, i, train, test):
     """when a data set of learn() has query ids (set_queries) on a classification task: one more stderr line with the
     impression-weighted per-query AUC (fmx_evaluate_by_query) and gauc_* / auc_within_* in the iteration's log row; a set without
-    ids gives nan.  stdout is not touched."""
+    ids gives nan.  With rank_cutoffs the same scoring pass and sort also give the tie-averaged NDCG, recall and precision at every
+    cutoff (fmx_evaluate_rank, whose by_query is fmx_evaluate_by_query's result): one more stderr line per cutoff and ndcg@K_* /
+    recall@K_* / precision@K_* in the log row.  stdout is not touched."""
     if learner.task != TASK_CLASSIFICATION or not any(id(d) in learner._queries for d in (train, test)):
         return
-    vals = []
+    nan = float("nan")
+    cutoffs = tuple(learner.rank_cutoffs)
+    row, evs = learner.log[-1], {}
     for name, d in (("train", train), ("test", test)):
-        ev = learner.evaluate_by_query(d) if id(d) in learner._queries else None
-        gauc, within = (ev.gauc, ev.auc_within) if ev is not None else (float("nan"), float("nan"))
-        learner.log[-1]["gauc_" + name], learner.log[-1]["auc_within_" + name] = gauc, within
-        vals.append(gauc)
-    print("#Iter=%3d\tgauc: Train=%g\tTest=%g" % (i, vals[0], vals[1]), file=sys.stderr)
+        ev = rk = None
+        if id(d) in learner._queries:
+            rk = learner.evaluate_rank(d, cutoffs) if cutoffs else None
+            ev = rk.by_query if cutoffs else learner.evaluate_by_query(d)
+        evs[name] = rk
+        row["gauc_" + name], row["auc_within_" + name] = (ev.gauc, ev.auc_within) if ev is not None else (nan, nan)
+    print("#Iter=%3d\tgauc: Train=%g\tTest=%g" % (i, row["gauc_train"], row["gauc_test"]), file=sys.stderr)
+    for j, k in enumerate(cutoffs):
+        for name, rk in evs.items():
+            for m in ("ndcg", "recall", "precision"):
+                row["%s@%d_%s" % (m, k, name)] = getattr(rk.at[j], m) if rk is not None else nan
+        print("#Iter=%3d\tndcg@%d: Train=%g\tTest=%g" % (i, k, row["ndcg@%d_train" % k], row["ndcg@%d_test" % k]), file=sys.stderr)
 
 
 def _check_queries(data, qid):
@@ -235,6 +247,7 @@ class FMLearnSGD:
         self._h = None
         self._slots = {}
         self._queries = {}                                      # id(data) -> (qid, n_queries) of set_queries
+        self.rank_cutoffs = ()                                  # with query ids: ndcg / recall / precision at these K per iteration
         self._adapt_open = False
         self._ftrl_open = False
 
@@ -294,6 +307,14 @@ class FMLearnSGD:
         if id(data) not in self._queries:
             raise ValueError("evaluate_by_query: the data set has no query ids (set_queries)")
         return self._h.evaluate_by_query(self._slot(data), self.EVAL_LINK)
+
+    def evaluate_rank(self, data, cutoffs):
+        """exact tie-averaged NDCG, recall and precision at the cutoffs (at most four, ascending) inside every query of `data` under
+        the current parameters (capi.EvalRank: at[j].ndcg / .recall / .precision / .hits / .tied_queries, by_query), reduced on the
+        device (fmx_evaluate_rank)"""
+        if id(data) not in self._queries:
+            raise ValueError("evaluate_rank: the data set has no query ids (set_queries)")
+        return self._h.evaluate_rank(self._slot(data), cutoffs, self.EVAL_LINK)
 
     # fm_learn_sgd_element::learn (fm_learn_sgd_element.h:48-78)
     def learn(self, train, test):
@@ -427,6 +448,7 @@ class FMLearnALS:
         self._shards = []
         self._train = self._test = None   # the data sets of learn(): slots 0 and 1
         self._queries = {}             # id(data) -> (qid, n_queries) of set_queries
+        self.rank_cutoffs = ()         # with query ids: ndcg / recall / precision at these K per iteration
 
     def init(self):
         fm = self.fm
@@ -563,6 +585,15 @@ class FMLearnALS:
             raise ValueError("evaluate_by_query: the data set has no query ids (set_queries)")
         return self._h.evaluate_by_query(0 if data is self._train else 1, capi.LINK_PROBIT)
 
+    def evaluate_rank(self, data, cutoffs):
+        """exact tie-averaged NDCG, recall and precision at the cutoffs inside every query of the train or test set of learn() under
+        the parameters of the last sweep (fmx_evaluate_rank / fmx_group_evaluate_rank)"""
+        if data is not self._train and data is not self._test:
+            raise ValueError("evaluate_rank: the data set is neither the train nor the test set of learn()")
+        if id(data) not in self._queries:
+            raise ValueError("evaluate_rank: the data set has no query ids (set_queries)")
+        return self._h.evaluate_rank(0 if data is self._train else 1, cutoffs, capi.LINK_PROBIT)
+
     TOPK_SLOTS = (2, 3)             # learn() keeps train and test in slots 0 and 1
 
     def recommend(self, queries, candidates, topk, exclude=None):
@@ -653,6 +684,10 @@ class FMLearnMCMC(FMLearnALS):
 
     def evaluate_by_query(self, data):
         raise NotImplementedError("evaluate_by_query: the MCMC prediction is the average over the draws (pred_sum_all / num_iter); "
+                                  "no single device pass scores it")
+
+    def evaluate_rank(self, data, cutoffs):
+        raise NotImplementedError("evaluate_rank: the MCMC prediction is the average over the draws (pred_sum_all / num_iter); "
                                   "no single device pass scores it")
 
     def evaluate_ex(self, data):
