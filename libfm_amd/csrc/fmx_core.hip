@@ -5,8 +5,6 @@
 // No CPU fallback lives in this library: every compute entry point needs a HIP device and fails with FMX_E_HIP
 // otherwise.  Nothing here links or calls oracle/.
 #include "fmx_internal.h"
-#include <atomic>
-#include <mutex>
 
 static thread_local std::string g_create_error = "";
 
@@ -310,404 +308,9 @@ void resolve_batch(const fmx_config& cfg, double coll_mass, uint32_t requested, 
   out->status = status;
 }
 
-// ---- placement of big parameter tables: an arena of chunks from two memory classes ---------------------------------------------
-// scripts/ubench/placement_chunks / _order / _classes.hip (profiles/r03_placement_*.txt): the rate of random 256-byte row traffic is a
-// property of the PHYSICAL memory (the same chunks mapped elsewhere keep it) and of its SPREAD: any 1 GB piece of any table runs at
-// 4.9 TB/s, and so does a table whose pieces all come from one of three classes of ~96 GB the device's memory falls into; pieces of
-// two classes evenly mixed run at 6.1 (3 : 1 -> 5.8, 7 : 1 -> 5.4; three classes are no better than two).  A plain allocation lies in
-// one class or straddles two by luck.  Here: chunks are taken one at a time, each is classified by probing it together with the
-// reference chunk of every class seen so far (k_place_pair), until two classes can supply half of the arena each; those are mapped
-// alternately into one range, everything else goes back.  Any failure of the virtual-memory API leaves nothing behind and the caller
-// falls back to plain allocations.
-namespace {
-constexpr size_t ARENA_CHUNK = (size_t)1 << 30;
-struct ArenaPool {
-  void* va = nullptr; size_t cap = 0;                              // scratch range the pool's chunks are mapped into
-  std::vector<hipMemGenericAllocationHandle_t> hnd;                // chunk i is mapped at va + i * ARENA_CHUNK while mapped[i]
-  std::vector<char> mapped;
-  std::vector<int> cls;
-};
-void arena_pool_release(ArenaPool& P) {
-  for (size_t i = 0; i < P.hnd.size(); i++) {
-    if (P.mapped[i]) (void)hipMemUnmap((char*)P.va + i * ARENA_CHUNK, ARENA_CHUNK);
-    (void)hipMemRelease(P.hnd[i]);
-  }
-  if (P.va) (void)hipMemAddressFree(P.va, P.cap * ARENA_CHUNK);
-  P.hnd.clear(); P.mapped.clear(); P.cls.clear(); P.va = nullptr;
-}
-}  // namespace
-
-// One classified arena per device outlives its handle: the next fmx_create on that device that needs no more chunks takes it over (a
-// prefix of an alternating sequence alternates) instead of probing again -- the bench's later legs, a learner's second handle.  The
-// memory stays allocated until it is reused, fmx_release_cached_memory() is called, an arena_build runs short of memory, or the
-// process ends; FMX_ARENA_CACHE=0 turns the cache off.
-namespace {
-struct ArenaCacheEntry { Arena a; bool full = false; };
-std::mutex g_arena_mu;
-ArenaCacheEntry g_arena_cache[16];
-void arena_release(Arena& A, std::string* err) {
-  if (!A.va) return;
-  // chunk by chunk, as mapped: a failing unmap must not keep the other chunks
-  for (size_t c = 0; c < A.n_chunks; c++) {
-    const hipError_t e = hipMemUnmap((char*)A.va + c * A.chunk_bytes, A.chunk_bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); if (err) *err = std::string("arena_free: hipMemUnmap failed: ") + hipGetErrorString(e); }
-  }
-  (void)hipMemAddressFree(A.va, A.reserved_bytes ? A.reserved_bytes : A.bytes);
-  A = Arena();
-}
-bool arena_cache_on() { const char* e = getenv("FMX_ARENA_CACHE"); return !(e && e[0] == '0'); }
-}  // namespace
-
-void arena_cache_drop(int device) {
-  std::lock_guard<std::mutex> lk(g_arena_mu);
-  for (int d = 0; d < 16; d++)
-    if ((device < 0 || d == device) && g_arena_cache[d].full) {
-      int cur = 0; (void)hipGetDevice(&cur); (void)hipSetDevice(d);
-      arena_release(g_arena_cache[d].a, nullptr);
-      g_arena_cache[d].full = false;
-      (void)hipSetDevice(cur);
-    }
-}
-
-void arena_free(fmx_handle h) {
-  Arena& A = h->arena;
-  if (!A.va) return;
-  if (A.method == 2 && h->device >= 0 && h->device < 16 && arena_cache_on()) {
-    (void)hipStreamSynchronize(h->stream);
-    std::lock_guard<std::mutex> lk(g_arena_mu);
-    ArenaCacheEntry& c = g_arena_cache[h->device];
-    if (!c.full || c.a.n_chunks < A.n_chunks) {                    // keep the larger one
-      if (c.full) arena_release(c.a, nullptr);
-      c.a = A; c.full = true;
-      A = Arena();
-      return;
-    }
-  }
-  arena_release(A, &h->err);
-}
-
-// V (v_bytes) at the start of the arena, w (w_bytes) centred on a chunk boundary behind it (both classes under it too)
-static hipError_t arena_build(fmx_handle h, size_t v_bytes, size_t w_bytes, int bound_tables, float** V_out, float** w_out) {
-  const auto t_start = std::chrono::steady_clock::now();
-  const size_t CH = ARENA_CHUNK;
-  uint64_t ch_ = 0, w_off_ = 0; uint32_t T = 0;
-  if (fmx_place_layout(v_bytes, w_bytes, &ch_, &T, &w_off_) != FMX_OK) return hipErrorInvalidValue;
-  const size_t w_off = (size_t)w_off_;
-  hipError_t er = hipSuccess;
-  if (h->device >= 0 && h->device < 16) {                            // an arena this device's previous handle left behind?
-    std::lock_guard<std::mutex> lk(g_arena_mu);
-    ArenaCacheEntry& c = g_arena_cache[h->device];
-    // a PREFIX of the cached chunk order serves a smaller model only if it still spreads both tables over both classes: the order is a
-    // Bresenham spread (X X Y X Y ... for odd T or a short second class), so the prefix is recounted, never assumed to alternate
-    auto prefix_ok = [&](const Arena& A) -> bool {
-      if (A.cls.size() < T) return false;
-      auto both = [&](size_t c0, size_t c1) {                        // chunks [c0, c1]: one chunk cannot span two classes; more must
-        if (c1 <= c0) return true;
-        bool s0 = false, s1 = false;
-        for (size_t k = c0; k <= c1 && k < T; k++) { s0 |= A.cls[k] == 0; s1 |= A.cls[k] == 1; }
-        return s0 && s1;
-      };
-      const size_t v_last = v_bytes ? (v_bytes - 1) / CH : 0;
-      const size_t w_first = w_off / CH, w_last = w_bytes ? (w_off + w_bytes - 1) / CH : w_first;
-      return both(0, v_last) && both(w_first, w_last);
-    };
-    if (c.full && c.a.chunk_bytes == CH && c.a.n_chunks >= T && !prefix_ok(c.a)) { arena_release(c.a, nullptr); c.full = false; }   // probe again
-    if (c.full && c.a.chunk_bytes == CH && c.a.n_chunks >= T) {
-      Arena A = c.a;
-      c.a = Arena(); c.full = false;
-      for (size_t k = T; k < A.n_chunks; k++) (void)hipMemUnmap((char*)A.va + k * CH, CH);   // the tail goes back to the device
-      A.n_chunks = T; A.bytes = (size_t)T * CH;
-      A.cls.resize(T);
-      A.per_class[0] = A.per_class[1] = 0;
-      for (uint8_t cc : A.cls) if (cc < 2) A.per_class[cc]++;       // (recounted from the prefix actually taken)
-      A.pool = 0;                                                    // nothing probed this time
-      er = hipMemsetAsync(A.va, 0, A.bytes, h->stream);
-      if (er == hipSuccess) {
-        h->arena = A;
-        *V_out = (float*)A.va;
-        *w_out = (float*)((char*)A.va + w_off);
-        h->arena.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-        return hipSuccess;
-      }
-      (void)hipGetLastError();
-      arena_release(A, nullptr);
-    }
-  }
-  size_t free_b = 0, total_b = 0;
-  er = hipMemGetInfo(&free_b, &total_b);
-  if (er != hipSuccess) return er;
-  if ((size_t)T * CH + ((size_t)2 << 30) > free_b) {                  // short of memory: whatever the cache holds goes back first
-    arena_cache_drop(h->device);
-    er = hipMemGetInfo(&free_b, &total_b);
-    if (er != hipSuccess) return er;
-  }
-  if ((size_t)T * CH + ((size_t)2 << 30) > free_b) return hipErrorOutOfMemory;    // (the caller's plain allocation reports it properly)
-  // the pool: at most bound_tables arenas' worth + 64 chunks (a class comes in runs of up to 64 GB in allocation order), at most
-  // half of what is free beyond the arena itself
-  size_t max_pool = std::min<size_t>((size_t)bound_tables * T + 64, T + (free_b - (size_t)T * CH) / CH / 2);
-  max_pool = std::max<size_t>(max_pool, T);
-  hipMemAllocationProp prop = {};
-  prop.type = hipMemAllocationTypePinned; prop.location.type = hipMemLocationTypeDevice; prop.location.id = h->device;
-  hipMemAccessDesc acc = {};
-  acc.location.type = hipMemLocationTypeDevice; acc.location.id = h->device; acc.flags = hipMemAccessFlagsProtReadWrite;
-  ArenaPool P;
-  P.cap = max_pool;
-  er = hipMemAddressReserve(&P.va, P.cap * CH, CH, nullptr, 0);
-  if (er != hipSuccess) { P.va = nullptr; return er; }
-  auto chunk_va = [&](size_t i) { return (float*)((char*)P.va + i * CH); };
-  const uint32_t rows_shift = 22;                                   // 1 GiB / 256 B
-  const uint32_t waves = 1u << 17;                                  // 2.1 GB of traffic per probe, ~0.4 ms
-  auto pair_ms = [&](size_t i, size_t j, float* ms) -> hipError_t {
-    float best = 1e30f;
-    for (int rep = 0; rep < 2; rep++) {                             // (first launch: page-table warm-up; the second one is the measurement)
-      hipError_t e = hipEventRecord(h->ev0, h->stream);
-      hipLaunchKernelGGL(k_place_pair, dim3(waves / 4), dim3(256), 0, h->stream, chunk_va(i), chunk_va(j), rows_shift, waves, (uint64_t)rep * 7919 + 1);
-      if (e == hipSuccess) e = hipGetLastError();
-      if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
-      if (e == hipSuccess) e = hipEventSynchronize(h->ev1);
-      float t = 0.f;
-      if (e == hipSuccess) e = hipEventElapsedTime(&t, h->ev0, h->ev1);
-      if (e != hipSuccess) return e;
-      if (rep && t < best) best = t;
-    }
-    *ms = best;
-    return hipSuccess;
-  };
-  std::vector<size_t> refs;                                          // first chunk of every class
-  std::vector<std::vector<size_t>> of;                               // chunks per class
-  std::vector<size_t> mixed;                                         // chunks that straddle a border between classes: fillers only
-  std::vector<float> alone;                                          // a chunk's time under the probe on its own
-  float slow_ms = 0.f;                                               // ... of a chunk that lies in ONE class (the median of the first eight)
-  auto enough = [&](size_t* x, size_t* y) -> bool {                  // two classes with ceil(T/2) and floor(T/2) chunks?
-    size_t a = SIZE_MAX, b = SIZE_MAX;
-    for (size_t k = 0; k < of.size(); k++) {
-      if (a == SIZE_MAX || of[k].size() > of[a].size()) { b = a; a = k; }
-      else if (b == SIZE_MAX || of[k].size() > of[b].size()) b = k;
-    }
-    *x = a; *y = b;
-    return a != SIZE_MAX && b != SIZE_MAX && of[a].size() >= (T + 1) / 2 && of[b].size() >= T / 2;
-  };
-  auto take = [&]() -> hipError_t {                                  // one more chunk: created, mapped into the pool's range, written, timed alone
-    const size_t i = P.hnd.size();
-    hipMemGenericAllocationHandle_t hd;
-    hipError_t e = hipMemCreate(&hd, CH, &prop, 0);
-    if (e != hipSuccess) return e;
-    P.hnd.push_back(hd); P.mapped.push_back(0); P.cls.push_back(-1); alone.push_back(0.f);
-    e = hipMemMap((char*)P.va + i * CH, CH, 0, hd, 0);
-    if (e != hipSuccess) return e;
-    P.mapped[i] = 1;
-    e = hipMemSetAccess((char*)P.va + i * CH, CH, &acc, 1);
-    if (e == hipSuccess) e = hipMemsetAsync(chunk_va(i), 0, CH, h->stream);   // (a never-written allocation answers a probe in microseconds)
-    // timed on its own only while the one-class rate is being established (the first eight): later chunks go straight to the pair probe --
-    // a chunk that straddles a class border then matches no reference and opens a class of its own, which never gets stocked
-    if (e == hipSuccess && i < 8) e = pair_ms(i, i, &alone[i]);
-    return e;
-  };
-  // same class <=> the two chunks together are no faster than one alone; a chunk that is faster ALONE straddles a border (it must not
-  // become a reference: everything would look like its class)
-  int last_cls = -1;                                                 // classes come in runs of 32 / 64 chunks in allocation order: try the
-  auto classify = [&](size_t i) -> hipError_t {                      // previous chunk's class first (one probe per chunk inside a run)
-    if (alone[i] > 0.f && alone[i] < 0.95f * slow_ms) { P.cls[i] = -2; mixed.push_back(i); return hipSuccess; }
-    for (size_t t = 0; t < refs.size() && P.cls[i] < 0; t++) {
-      const size_t k = (last_cls >= 0) ? (t == 0 ? (size_t)last_cls : (t <= (size_t)last_cls ? t - 1 : t)) : t;
-      float ms = 0.f;
-      const hipError_t e = pair_ms(refs[k], i, &ms);
-      if (e != hipSuccess) return e;
-      if (ms > slow_ms / 1.08f) { P.cls[i] = (int)k; of[k].push_back(i); last_cls = (int)k; }
-    }
-    if (P.cls[i] < 0) { refs.push_back(i); of.push_back({i}); P.cls[i] = (int)refs.size() - 1; last_cls = P.cls[i]; }
-    return hipSuccess;
-  };
-  size_t cx = SIZE_MAX, cy = SIZE_MAX;
-  bool out_of_memory = false;
-  const size_t first = std::min<size_t>(8, max_pool);
-  while (er == hipSuccess && P.hnd.size() < first) er = take();
-  if (er == hipSuccess) {
-    std::vector<float> srt(alone);
-    std::sort(srt.begin(), srt.end());
-    slow_ms = srt[srt.size() / 2];
-    for (size_t i = 0; i < first && er == hipSuccess; i++) er = classify(i);
-  }
-  while (er == hipSuccess && P.hnd.size() < max_pool && !enough(&cx, &cy)) {
-    er = take();
-    if (er != hipSuccess) {                                           // memory ran out: go with the pool in hand
-      if (P.hnd.size() > T) { (void)hipGetLastError(); er = hipSuccess; out_of_memory = true;
-        if (!P.mapped.back()) { (void)hipMemRelease(P.hnd.back()); P.hnd.pop_back(); P.mapped.pop_back(); P.cls.pop_back(); alone.pop_back(); } }
-      break;
-    }
-    er = classify(P.hnd.size() - 1);
-  }
-  (void)out_of_memory;
-  if (er != hipSuccess || P.hnd.size() < T) { arena_pool_release(P); return er != hipSuccess ? er : hipErrorOutOfMemory; }
-  (void)enough(&cx, &cy);
-  // the arena's chunks in mapping order: the two best-stocked classes alternately; when the second runs short (pool bound reached)
-  // its chunks are spread evenly among the first's, then any other class fills up
-  std::vector<size_t> pick;
-  std::vector<uint8_t> pick_cls;
-  {
-    std::vector<size_t> X = (cx != SIZE_MAX) ? of[cx] : std::vector<size_t>(), Y = (cy != SIZE_MAX) ? of[cy] : std::vector<size_t>();
-    std::vector<size_t> rest;
-    for (size_t k = 0; k < of.size(); k++) if (k != cx && k != cy) rest.insert(rest.end(), of[k].begin(), of[k].end());
-    rest.insert(rest.end(), mixed.begin(), mixed.end());
-    const size_t ny = std::min<size_t>(Y.size(), T / 2);
-    size_t nx = std::min<size_t>(X.size(), T - ny);
-    size_t ix = 0, iy = 0, ir = 0, err_acc = 0;
-    for (uint32_t c = 0; c < T; c++) {
-      err_acc += ny;
-      if (iy < ny && err_acc >= T) { err_acc -= T; pick.push_back(Y[iy++]); pick_cls.push_back(1); }
-      else if (ix < nx) { pick.push_back(X[ix++]); pick_cls.push_back(0); }
-      else if (iy < Y.size()) { pick.push_back(Y[iy++]); pick_cls.push_back(1); }
-      else if (ir < rest.size()) { pick.push_back(rest[ir++]); pick_cls.push_back(2); }
-    }
-    if (pick.size() < T) { arena_pool_release(P); return hipErrorOutOfMemory; }
-    h->arena.per_class[0] = (uint32_t)ix; h->arena.per_class[1] = (uint32_t)iy;
-  }
-  void* va = nullptr;
-  er = hipMemAddressReserve(&va, (size_t)T * CH, CH, nullptr, 0);
-  if (er != hipSuccess) { arena_pool_release(P); return er; }
-  er = hipStreamSynchronize(h->stream);
-  uint32_t moved = 0;                                                // chunks mapped into the arena's range so far (counted AFTER a successful map)
-  while (moved < T && er == hipSuccess) {
-    const size_t i = pick[moved];
-    er = hipMemUnmap((char*)P.va + i * CH, CH);
-    if (er != hipSuccess) break;
-    P.mapped[i] = 0;
-    er = hipMemMap((char*)va + (size_t)moved * CH, CH, 0, P.hnd[i], 0);
-    if (er == hipSuccess) moved++;
-  }
-  if (er == hipSuccess) er = hipMemSetAccess(va, (size_t)T * CH, &acc, 1);
-  if (er != hipSuccess) {
-    for (uint32_t c = 0; c < moved; c++) (void)hipMemUnmap((char*)va + (size_t)c * CH, CH);   // chunk by chunk: exactly what was mapped
-    (void)hipMemAddressFree(va, (size_t)T * CH);
-    arena_pool_release(P);
-    return er;
-  }
-  const uint32_t pool = (uint32_t)P.hnd.size();
-  arena_pool_release(P);                                             // the unused chunks go back; the mapped ones live on through their mapping
-  Arena& A = h->arena;
-  A.va = va; A.bytes = (size_t)T * CH; A.reserved_bytes = A.bytes; A.chunk_bytes = CH; A.n_chunks = T; A.pool = pool; A.classes_seen = (uint32_t)refs.size(); A.method = 2;
-  A.cls = pick_cls;
-  er = hipMemsetAsync(va, 0, A.bytes, h->stream);
-  if (er != hipSuccess) { arena_free(h); return er; }
-  *V_out = (float*)va;
-  *w_out = (float*)((char*)va + w_off);
-  A.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-  return hipSuccess;
-}
-
 extern "C" {
 
 int fmx_abi_version(void) { return FMX_ABI_VERSION; }
-
-
-// ---- device allocations (fmx_internal.h: fmx_dev_alloc / fmx_dev_free) -----------------------------------------------------------
-namespace {
-std::atomic<uint64_t> g_devices_used{0};                              // devices fmx_create has opened a handle on in this process
-struct BigAlloc { size_t reserved = 0; int device = 0; std::vector<hipMemGenericAllocationHandle_t> hnd; std::vector<size_t> sz; };
-std::mutex g_big_mu;
-std::unordered_map<void*, BigAlloc> g_big;
-constexpr size_t BIG_MIN = (size_t)768 << 20, BIG_CHUNK = (size_t)1 << 30, BIG_ALIGN = (size_t)2 << 20;
-bool big_alloc_on() { static const bool on = []() { const char* e = getenv("FMX_BIG_ALLOC"); return !(e && e[0] == '0'); }(); return on; }
-
-hipError_t plain_alloc(void** p, size_t bytes) {          // hipMalloc; out of memory: the idle arena cache of the device goes back, once
-  hipError_t e = hipMalloc(p, bytes);
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    int d = 0;
-    if (hipGetDevice(&d) == hipSuccess) { arena_cache_drop(d); e = hipMalloc(p, bytes); }
-  }
-  return e;
-}
-void big_release(void* va, BigAlloc& b) {
-  size_t off = 0;
-  for (size_t i = 0; i < b.hnd.size(); i++) { (void)hipMemUnmap((char*)va + off, b.sz[i]); (void)hipMemRelease(b.hnd[i]); off += b.sz[i]; }
-  if (va) (void)hipMemAddressFree(va, b.reserved);
-}
-// one virtual range backed by physical chunks of at most 1 GiB; false: nothing is left behind and the caller takes hipMalloc
-bool big_alloc(void** p, size_t bytes) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return false;
-  hipMemAllocationProp prop = {};
-  prop.type = hipMemAllocationTypePinned; prop.location.type = hipMemLocationTypeDevice; prop.location.id = dev;
-  BigAlloc b; b.device = dev;
-  b.reserved = (bytes + BIG_ALIGN - 1) / BIG_ALIGN * BIG_ALIGN;
-  void* va = nullptr;
-  static const bool trace = getenv("FMX_TRACE_ALLOC") != nullptr;
-  const auto t0 = std::chrono::steady_clock::now();
-  auto ms = [&]() { return 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
-  if (hipMemAddressReserve(&va, b.reserved, BIG_ALIGN, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); return false; }
-  const double t_res = ms();
-  bool ok = true;
-  for (size_t off = 0; off < b.reserved && ok; off += BIG_CHUNK) {
-    const size_t sz = std::min(BIG_CHUNK, b.reserved - off);
-    hipMemGenericAllocationHandle_t hd;
-    if (hipMemCreate(&hd, sz, &prop, 0) != hipSuccess) { ok = false; break; }
-    if (hipMemMap((char*)va + off, sz, 0, hd, 0) != hipSuccess) { (void)hipMemRelease(hd); ok = false; break; }
-    b.hnd.push_back(hd); b.sz.push_back(sz);
-  }
-  const double t_map = ms();
-  if (ok) {
-    // read / write for the owning device and -- where the runtime grants it -- for the OTHER DEVICES THIS PROCESS HOLDS HANDLES ON
-    // (fmx_group_upload_rows copies staged rows between the devices of a one-process group); a peer the runtime refuses is not an error
-    // here.  A process that drives one GPU (one process per GPU: the multi-GPU bench) never touches another device.
-    int ndev = 0; (void)hipGetDeviceCount(&ndev);
-    hipMemAccessDesc acc = {}; acc.location.type = hipMemLocationTypeDevice; acc.location.id = dev; acc.flags = hipMemAccessFlagsProtReadWrite;
-    ok = hipMemSetAccess(va, b.reserved, &acc, 1) == hipSuccess;
-    const uint64_t used = g_devices_used.load(std::memory_order_relaxed);
-    for (int d = 0; ok && d < ndev && d < 64; d++) {
-      if (d == dev || !((used >> d) & 1ull)) continue;
-      int can = 0;
-      if (hipDeviceCanAccessPeer(&can, d, dev) != hipSuccess || !can) { (void)hipGetLastError(); continue; }
-      acc.location.id = d;
-      if (hipMemSetAccess(va, b.reserved, &acc, 1) != hipSuccess) (void)hipGetLastError();
-    }
-  }
-  if (trace) fprintf(stderr, "[fmx alloc] big %zu bytes: reserve %.3f ms, create+map %.3f ms, access %.3f ms\n", bytes, t_res, t_map - t_res, ms() - t_map);
-  if (!ok) { (void)hipGetLastError(); big_release(va, b); return false; }
-  { std::lock_guard<std::mutex> lk(g_big_mu); g_big.emplace(va, std::move(b)); }
-  *p = va;
-  return true;
-}
-}  // namespace
-
-static hipError_t dev_alloc_untraced(void** p, size_t bytes);
-extern "C++" hipError_t fmx_dev_alloc_bytes(void** p, size_t bytes) {
-  static const bool trace = getenv("FMX_TRACE_ALLOC") != nullptr;
-  if (!trace) return dev_alloc_untraced(p, bytes);
-  const auto t0 = std::chrono::steady_clock::now();
-  const hipError_t e = dev_alloc_untraced(p, bytes);
-  const double ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  if (ms > 0.5) fprintf(stderr, "[fmx alloc] %12zu bytes %9.3f ms%s\n", bytes, ms, e == hipSuccess ? "" : " FAILED");
-  return e;
-}
-static hipError_t dev_alloc_untraced(void** p, size_t bytes) {
-  if (!p) return hipErrorInvalidValue;
-  *p = nullptr;
-  if (bytes >= BIG_MIN && big_alloc_on()) {
-    if (big_alloc(p, bytes)) return hipSuccess;
-    int d = 0;                                               // (out of memory next to an idle cached arena? give it back and try once more)
-    if (hipGetDevice(&d) == hipSuccess) { arena_cache_drop(d); if (big_alloc(p, bytes)) return hipSuccess; }
-  }
-  return plain_alloc(p, bytes);
-}
-extern "C++" hipError_t fmx_dev_free(void* p) {
-  if (!p) return hipSuccess;
-  BigAlloc b; bool big = false;
-  {
-    std::lock_guard<std::mutex> lk(g_big_mu);
-    auto it = g_big.find(p);
-    if (it != g_big.end()) { b = std::move(it->second); g_big.erase(it); big = true; }
-  }
-  if (!big) return hipFree(p);
-  int cur = 0; (void)hipGetDevice(&cur);
-  if (cur != b.device) (void)hipSetDevice(b.device);
-  (void)hipDeviceSynchronize();                              // (hipFree waits for the device's work too: nothing may still read the range)
-  big_release(p, b);
-  if (cur != b.device) (void)hipSetDevice(cur);
-  return hipSuccess;
-}
-
-int fmx_release_cached_memory(void) { arena_cache_drop(-1); return FMX_OK; }
 
 int fmx_device_count(void) {
   int n = 0;
@@ -754,7 +357,7 @@ int fmx_create(const fmx_config* cfg, fmx_handle* out) {
       fail(nullptr, FMX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));               \
       fmx_destroy(h); return FMX_E_HIP; } } while (0)
   CREATE_CHK(hipSetDevice(dev));
-  if (dev >= 0 && dev < 64) g_devices_used.fetch_or(1ull << dev, std::memory_order_relaxed);
+  mark_device_used(dev);
   CREATE_CHK(hipGetDeviceProperties(&h->prop, dev));
   CREATE_CHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   CREATE_CHK(hipEventCreate(&h->ev0));
@@ -767,72 +370,7 @@ int fmx_create(const fmx_config* cfg, fmx_handle* out) {
     h->tb.rs = (uint32_t)h->KP;
     { const char* rk = getenv("FMX_ROW_STRIDE_KP");
       if (h->KP >= 32 && !(rk && rk[0] == '1')) h->tb.rs = std::min<uint32_t>((uint32_t)h->KP, ((uint32_t)cfg->num_factor + 15u) / 16u * 16u); }
-    // Placement of the parameter tables: big ones (>= 2 GiB) in an arena of chunks from two memory classes (arena_build above).  Smaller
-    // ones, and every table when the virtual-memory API fails: a table of >= 256 MB is allocated up to fmx_config::place_candidates
-    // times (default 2; the earlier candidate is held meanwhile, so that the later one is other memory), each candidate is zeroed and
-    // timed under a probe with the step's traffic shape, the fastest is kept (a plain allocation straddles two classes or not, by
-    // luck).  place_candidates = 1: first fit, no probe.
-    auto alloc_placed = [&](float** out, size_t bytes, int max_tries, bool rows, const char* what) -> hipError_t {
-      constexpr int MAXC = 6;
-      int tries = 1;
-      if (bytes >= ((size_t)256 << 20) && max_tries > 1) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-          tries = (int)std::min<size_t>((size_t)std::min(max_tries, MAXC), std::max<size_t>(1, free_b / (bytes + ((size_t)4 << 30))));   // candidates sit side by side
-      }
-      float* cand[MAXC] = {};
-      float ms_of[MAXC] = {};
-      int n_cand = 0, best = 0;
-      hipError_t er = hipSuccess;
-      for (int c = 0; c < tries && er == hipSuccess; c++) {
-        if (plain_alloc((void**)&cand[c], bytes) != hipSuccess) { (void)hipGetLastError(); cand[c] = nullptr; break; }
-        n_cand = c + 1;
-        er = hipMemsetAsync(cand[c], 0, bytes, h->stream);   // (also: a never-written allocation answers the probe in 30 us)
-        if (tries == 1 || er != hipSuccess) break;
-        for (int rep = 0; rep < 2 && er == hipSuccess; rep++) {           // (first launch: page-table warm-up)
-          er = hipEventRecord(h->ev0, h->stream);
-          if (rows) {                                         // 2^19 wavefronts x 32 rows: 8 GB of traffic at k = 64, ~1.5 ms
-            const uint32_t waves = 1u << 19;
-            hipLaunchKernelGGL(k_place_probe, dim3(waves / 4), dim3(256), 0, h->stream, cand[c], (uint64_t)h->n_local, h->tb.rs, waves, (uint64_t)rep * 7919 + 1);
-          } else {                                            // 2^24 random 4-byte read-modify-writes, ~0.5 ms
-            const uint64_t total = 1ull << 24;
-            hipLaunchKernelGGL(k_place_probe_w, dim3((unsigned)(total / 256)), dim3(256), 0, h->stream, cand[c], (uint64_t)(bytes / sizeof(float)), total, (uint64_t)rep * 7919 + 1);
-          }
-          if (er == hipSuccess) er = hipGetLastError();
-          if (er == hipSuccess) er = hipEventRecord(h->ev1, h->stream);
-          if (er == hipSuccess) er = hipEventSynchronize(h->ev1);
-          if (er == hipSuccess) er = hipEventElapsedTime(&ms_of[c], h->ev0, h->ev1);
-        }
-        if (ms_of[c] < ms_of[best]) best = c;
-        float worst = 0.f;
-        for (int i = 0; i <= c; i++) worst = std::max(worst, ms_of[i]);
-        if (c >= 1 && ms_of[best] < 0.95f * worst) break;     // two classes seen: the fast one is in hand
-      }
-      if (er == hipSuccess && !cand[0]) {                                    // out of memory: whatever the arena cache holds goes back first
-        arena_cache_drop(h->device);
-        er = plain_alloc((void**)&cand[0], bytes);                                   // (reports the allocation failure)
-        if (er == hipSuccess) er = hipMemsetAsync(cand[0], 0, bytes, h->stream);
-      }
-      (void)what;
-      for (int c = 0; c < MAXC; c++) if ((c != best || er != hipSuccess) && cand[c]) { fmx_dev_free(cand[c]); cand[c] = nullptr; }
-      *out = cand[best];
-      return er;
-    };
-    const auto t_place = std::chrono::steady_clock::now();
-    const size_t v_bytes = h->n_local * (size_t)h->tb.rs * sizeof(float), w_bytes = h->n_local * sizeof(float);
-    bool placed = false;
-    if (cfg->place_candidates != 1 && v_bytes >= ((size_t)2 << 30)) {
-      // big tables: an arena of 1 GiB chunks from two memory classes (arena_build above); on any failure plain allocations below
-      const hipError_t ae = arena_build(h, v_bytes, w_bytes, cfg->place_candidates > 1 ? cfg->place_candidates : 3, &h->tb.V, &h->w_sep);
-      if (ae == hipSuccess) placed = true; else { (void)hipGetLastError(); h->tb.V = nullptr; h->w_sep = nullptr; }
-    }
-    if (!placed) {
-      const int cand = cfg->place_candidates > 0 ? std::min(cfg->place_candidates, 6) : 2;
-      CREATE_CHK(alloc_placed(&h->tb.V, v_bytes, cand, true, "factor table"));
-      CREATE_CHK(alloc_placed(&h->w_sep, w_bytes, cand, false, "linear weights"));
-      h->arena.method = (cand > 1 && v_bytes >= ((size_t)256 << 20)) ? 1 : 0;
-      h->arena.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_place).count();
-    }
+    if (place_tables(h) != FMX_OK) { fmx_destroy(h); return FMX_E_HIP; }      // fmx_mem.hip: the arena, or the best of place_candidates allocations
     h->tb.w = h->w_sep; h->tb.ws = 1;
   }
   CREATE_CHK(fmx_dev_alloc(&h->w0, sizeof(double)));
@@ -875,33 +413,11 @@ int fmx_create(const fmx_config* cfg, fmx_handle* out) {
   return FMX_OK;
 }
 
-// the arena of a model: V from offset 0, w centred on the first chunk boundary behind it (half of it in either chunk: chunks alternate
-// between two memory classes, so w lies in both like V does), whole chunks.  Host arithmetic, no device needed.
-int fmx_place_layout(uint64_t v_bytes, uint64_t w_bytes, uint64_t* chunk_bytes, uint32_t* chunks, uint64_t* w_offset) {
-  if (!chunk_bytes || !chunks || !w_offset || v_bytes == 0) return FMX_E_ARG;
-  const uint64_t CH = ARENA_CHUNK;
-  const uint64_t w_half = ((w_bytes / 2) + 255) & ~(uint64_t)255;                // (256-byte granules: w stays aligned like V's rows)
-  const uint64_t boundary = (v_bytes + w_half + CH - 1) / CH;                     // w straddles the start of chunk `boundary`
-  const uint64_t w_off = boundary * CH - w_half;
-  const uint64_t T = (w_off + w_bytes + CH - 1) / CH;
-  if (T > 0xFFFFFFFFull) return FMX_E_ARG;
-  *chunk_bytes = CH; *chunks = (uint32_t)T; *w_offset = w_off;
-  return FMX_OK;
-}
-
 int fmx_batch_rule(int32_t task, double learn_rate, double collision_mass, uint32_t requested, fmx_batch_info* out) {
   if (!out || (task != FMX_TASK_REGRESSION && task != FMX_TASK_CLASSIFICATION) || !(learn_rate >= 0.0) || !(collision_mass >= 0.0)) return FMX_E_ARG;
   fmx_config c = {};
   c.task = task; c.learn_rate = learn_rate;
   resolve_batch(c, collision_mass, requested, FMX_DEFAULT_BATCH, 1.0, out);
-  return FMX_OK;
-}
-
-int fmx_get_place_info(fmx_handle h, fmx_place_info* out) {
-  if (!h || !out) return FMX_E_ARG;
-  const Arena& A = h->arena;
-  out->method = A.method; out->chunks = A.n_chunks; out->per_class[0] = A.per_class[0]; out->per_class[1] = A.per_class[1];
-  out->pool = A.pool; out->classes_seen = A.classes_seen; out->seconds = A.seconds;
   return FMX_OK;
 }
 
@@ -917,8 +433,7 @@ int fmx_destroy(fmx_handle h) {
   compact_free(h);
   for (auto& s : h->slots) free_slot(s);
   if (h->grp) fmx_dev_free(h->grp);
-  if (h->arena.va) arena_free(h);                              // (both tables are parts of it)
-  else { if (h->tb.V) fmx_dev_free(h->tb.V); if (h->w_sep) fmx_dev_free(h->w_sep); }
+  free_tables(h);
   if (h->w0) fmx_dev_free(h->w0);
   if (h->w0_pp) fmx_dev_free(h->w0_pp);
   if (h->handoff_ctr) fmx_dev_free(h->handoff_ctr);

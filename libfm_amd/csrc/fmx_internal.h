@@ -1,5 +1,5 @@
 // fmx_internal.h -- shared by the translation units of libfmx.so (fmx_core.hip, fmx_sgd.hip, fmx_als.hip, fmx_comm.hip, fmx_pair.hip, fmx_topk.hip,
-// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip; fmx_io.hip needs none of it).
+// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip; fmx_io.hip needs none of it).
 // The C-ABI is include/fmx.h; nothing declared here is exported.
 #pragma once
 #pragma GCC visibility push(default)      // the C-ABI is the only thing libfmx.so exports (-fvisibility=hidden)
@@ -8,6 +8,7 @@
 #include "fmx_kernels.h"
 #include "fmx_als_kernels.h"
 #include "fmx_compact_kernels.h"
+#include "fmx_place_plan.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -162,22 +163,6 @@ struct FtrlState { float* zw = nullptr; float* zv = nullptr; float* nw = nullptr
 // the bf16 serving snapshot (fmx_compact_*, fmx_compact.hip): a frozen copy of w0, w (fp32, stride 1) and V as bf16 rows of tb.rs elements
 struct CompactState { uint16_t* V = nullptr; float* w = nullptr; double* w0 = nullptr; };
 
-// The parameter tables of a big model live in an ARENA: one virtual range backed by 1 GiB physical chunks (hipMemCreate) taken
-// alternately from two memory classes of the device (fmx_create)
-struct Arena {
-  void*    va = nullptr;         // reserved range; chunk i is mapped at va + i * chunk_bytes
-  size_t   bytes = 0, chunk_bytes = 0;
-  size_t   reserved_bytes = 0;   // size of the virtual range (>= bytes: a range taken over from the per-device cache may be longer)
-  uint32_t n_chunks = 0;
-  uint32_t per_class[2] = {0, 0};   // chunks of the two classes the tables are built from
-  uint32_t pool = 0;             // chunks that were taken and classified to get them (the others were returned)
-  uint32_t classes_seen = 0;
-  double   seconds = 0.0;        // host time of the whole placement
-  int      method = 0;           // fmx_place_info::method
-  std::vector<uint8_t> cls;      // [n_chunks] which class chunk i came from (0 / 1: the two the tables are built from, 2: a filler) -- what a
-                                 // later, smaller model that takes over a PREFIX of this arena recounts per_class from (arena_build)
-};
-
 struct fmx_context_s {
   fmx_config cfg;
   AlsState   als;
@@ -195,7 +180,8 @@ struct fmx_context_s {
   hipStream_t stream = nullptr;
   Tab        tb = {nullptr, nullptr, 0, 0};   // V rows (+ co-located w), see fmx_kernels.h
   float*     w_sep = nullptr;    // the w[] array
-  Arena      arena;              // when arena.va != nullptr both tables are parts of it (nothing to hipFree)
+  Placed     placed;             // fmx_place_plan.h: the report, and for a big model the ARENA both tables are parts of (nothing to hipFree): one
+                                 // virtual range of 1 GiB physical chunks taken alternately from two memory classes
   double*    w0 = nullptr;       // device scalar
   double*    w0_pp = nullptr;    // 8 doubles: ring of bias copies for the overlapped recurrence (hogwild, fused, bias lag)
   hipStream_t stream2 = nullptr; // side stream of the hogwild bias scan
@@ -372,17 +358,20 @@ void comm_free(fmx_handle h);                                            // fmx_
 int comm_sgd_epoch(fmx_handle h, int slot, const fmx_sgd_opts* opts, fmx_epoch_stats* stats);   // fmx_comm.hip
 int comm_sum_double(fmx_handle h, double* v);                            // fmx_comm.hip
 
-// Device allocations of the library go through fmx_dev_alloc / fmx_dev_free (fmx_core.hip), never through hipMalloc directly:
-//   * one classified arena per device outlives its handle (fmx_core.hip, "arena cache") and can hold tens of GB that nothing uses; an
+// Device allocations of the library go through fmx_dev_alloc / fmx_dev_free (fmx_mem.hip), never through hipMalloc directly:
+//   * one classified arena per device outlives its handle (fmx_mem.hip, "arena cache") and can hold tens of GB that nothing uses; an
 //     allocation that runs out of memory gives that cache back and tries once more (round-4 advisor);
 //   * allocations of 768 MiB and more are built from <= 1 GiB physical chunks through the virtual-memory API (hipMemCreate + hipMemMap):
 //     once a process has taken and returned a pool of chunks (what the table placement of fmx_create does), a plain hipMalloc of more
 //     than 1 GiB takes 0.5 - 1.6 SECONDS on this part (scripts/ubench/alloc_cost.hip, profiles/r06_alloc_cost.txt: 4 GiB 1566 ms, through
 //     the virtual-memory API 0.05 ms) -- that was 96 % of the 1.3 - 2.5 s of one-time slot preparation the round-5 verdict found.
 // fmx_dev_free takes either kind (and nullptr).
-void arena_cache_drop(int device);                                       // fmx_core.hip
-hipError_t fmx_dev_alloc_bytes(void** p, size_t bytes);                  // fmx_core.hip
-hipError_t fmx_dev_free(void* p);                                        // fmx_core.hip
+void arena_cache_drop(int device);                                       // fmx_mem.hip
+hipError_t fmx_dev_alloc_bytes(void** p, size_t bytes);                  // fmx_mem.hip
+hipError_t fmx_dev_free(void* p);                                        // fmx_mem.hip
+void mark_device_used(int dev);                                          // fmx_mem.hip: fmx_create has opened a handle on it
+int place_tables(fmx_handle h);                                          // fmx_mem.hip: h->tb.V, h->w_sep and the placement report
+void free_tables(fmx_handle h);                                          // fmx_mem.hip
 template <class T> inline hipError_t fmx_dev_alloc(T** p, size_t bytes) { return fmx_dev_alloc_bytes(reinterpret_cast<void**>(p), bytes); }
 
 // everything a call of the exact metrics (fmx_eval.hip, fmx_evalq.hip) takes from the device, freed on every path out of the call:

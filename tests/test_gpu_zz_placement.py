@@ -19,15 +19,14 @@ def capi():
     return capi
 
 
-def _run(capi, place):
-    h = capi.Handle(N, K, True, True, capi.TASK_CLASSIFICATION, 0.0, 0.0, 0.001, 0.01, -1.0, 1.0, place_candidates=place)
+def _run(capi, place, n=N, rows=1 << 18):
+    h = capi.Handle(n, K, True, True, capi.TASK_CLASSIFICATION, 0.0, 0.0, 0.001, 0.01, -1.0, 1.0, place_candidates=place)
     pi = h.place_info()
     h.init_params(0.0, 0.05, 5)
-    rows = 1 << 18
     h.synth_rows(0, 31, 0, rows, NNZ)
     h.sgd_epoch(0, capi.SGD_MINIBATCH, capi.APPLY_FUSED, 65536, 0, 0, 2)
     p = h.predict(0, rows)
-    ids = np.array([0, 1, N // 2, N - 2, N - 1], dtype=np.uint64)       # both ends of both tables
+    ids = np.array([0, 1, n // 2, n - 2, n - 1], dtype=np.uint64)       # both ends of both tables
     w, v = h.get_param_rows(ids)
     out = (p.tobytes(), w.tobytes(), v.tobytes(), h.get_w0())
     h.close()
@@ -91,3 +90,32 @@ def test_candidate_bound_is_honoured(capi):
     h.close()
     with pytest.raises(capi.FmxError):
         capi.Handle(N, K, place_candidates=7)
+
+
+def test_candidate_placement_is_reported_and_changes_no_result(capi):
+    """V of 281.6 MB: over the 256 MB from which candidates are tried, far under the arena's 2 GiB; w takes the first fit"""
+    capi.release_cached_memory()
+    n = 1_100_000
+    (pi0, out0), (pi2, out2), (pi1, out1) = (_run(capi, place, n, 1 << 16) for place in (0, 2, 1))
+    assert pi0.method == 1 and pi0.chunks == 0
+    assert pi2.method == 1 and pi2.chunks == 0
+    assert pi1.method == 0
+    assert out0 == out1 and out2 == out1
+
+
+def test_big_allocation_is_built_from_chunks_and_goes_back(capi):
+    """rows whose entry array (839 MB) is the first size over the 768 MiB from which fmx_dev_alloc builds a range from 1 GiB chunks"""
+    import ctypes
+    import torch
+    capi.release_cached_memory()
+    free0 = torch.cuda.mem_get_info()[0]
+    rows, nnz = 1 << 22, 25
+    h = capi.Handle(1 << 20, 8)
+    h.synth_rows(0, 31, 0, rows, nnz)
+    assert np.isfinite(h.predict(0, rows)).all()
+    n_rows, n_ent = ctypes.c_uint32(0), ctypes.c_uint64(0)
+    assert h.lib.fmx_rows_info(h.h, 0, ctypes.byref(n_rows), ctypes.byref(n_ent)) == 0
+    assert n_rows.value == rows and n_ent.value == nnz << 22
+    h.free_rows(0)
+    h.close()
+    assert abs(free0 - torch.cuda.mem_get_info()[0]) <= 64 << 20
