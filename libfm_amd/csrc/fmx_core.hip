@@ -136,6 +136,7 @@ void free_slot(Slot& s) {
   if (s.target) fmx_dev_free(s.target);
   if (s.wside) fmx_dev_free(s.wside);
   if (s.lmask) fmx_dev_free(s.lmask);
+  if (s.ids) fmx_dev_free(s.ids);
   if (s.qid) fmx_dev_free(s.qid);
   s = Slot();
 }
@@ -170,6 +171,40 @@ int ensure_wside(fmx_handle h, Slot& s) {
   }
   s.wside_version = 0;
   if (getenv("FMX_TRACE_SETUP")) fprintf(stderr, "[fmx setup] weight side stream %8.3f ms\n", 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - acc_.t0).count());
+  return FMX_OK;
+}
+
+// the slot's id-only stream (load_entry, fmx_kernels.h): where every row has the same length and every value is 1.0f -- one-hot field
+// data, libFM's usual input -- the value half of the {id, value} entries carries nothing, and k_fused streams 4 bytes per entry instead of
+// 8.  The rows of a slot never change between epochs (fm_learn_sgd_element.h:56), so it is built once, by the first one-pass epoch after an
+// upload: one pass over the entries that copies the ids and looks at every value; one value that is not 1.0f and the stream is dropped.
+// 4 bytes per entry stay resident until the slot is replaced or freed (free_slot).  Single handles only: a feature shard's rows vary.
+int ensure_ids(fmx_handle h, Slot& s) {
+  if (s.ids_asked) return FMX_OK;
+  s.ids_asked = true;
+  if (!h->ids || !s.fixed_nnz || s.nnz == 0 || h->cfg.shard_world != 1 || !s.blocks.empty()) return FMX_OK;
+  if (s.nnz != (uint64_t)s.n_rows * s.fixed_nnz) return FMX_OK;
+  struct Acc { fmx_handle h; std::chrono::steady_clock::time_point t0;
+               ~Acc() { h->setup_acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } acc_{h, std::chrono::steady_clock::now()};
+  uint32_t* flag = nullptr;
+  uint32_t not_one = 1u;
+  hipError_t er = fmx_dev_alloc(&flag, 256);
+  if (er == hipSuccess) er = fmx_dev_alloc(&s.ids, (size_t)s.nnz * 4);
+  if (er == hipSuccess) er = hipMemsetAsync(flag, 0, 4, h->stream);
+  if (er == hipSuccess) {
+    hipLaunchKernelGGL(k_ids_build, dim3((unsigned)std::min<uint64_t>((s.nnz + 255) / 256, 8192)), dim3(256), 0, h->stream, s.ent, s.nnz, s.ids, flag);
+    er = hipGetLastError();
+  }
+  if (er == hipSuccess) er = hipMemcpyAsync(&not_one, flag, 4, hipMemcpyDeviceToHost, h->stream);
+  if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
+  if (flag) fmx_dev_free(flag);
+  if (er != hipSuccess || not_one) {
+    if (s.ids) fmx_dev_free(s.ids);
+    s.ids = nullptr;
+    if (er != hipSuccess) return fail(h, FMX_E_HIP, "id-only stream of the slot: %s", hipGetErrorString(er));
+  }
+  if (getenv("FMX_TRACE_SETUP")) fprintf(stderr, "[fmx setup] id-only stream %s %8.3f ms\n", s.ids ? "built" : "not unit-valued",
+                                         1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - acc_.t0).count());
   return FMX_OK;
 }
 
@@ -388,6 +423,8 @@ int fmx_create(const fmx_config* cfg, fmx_handle* out) {
     h->scan_pit = !(sc && strcmp(sc, "serial") == 0);
     const char* so = getenv("FMX_SMALL_ONE");
     h->small_one = !(so && so[0] == '0');                       // small batches as one launch per batch (fmx_small_kernels.h); FMX_SMALL_ONE=0: two
+    const char* si = getenv("FMX_IDS");
+    h->ids = !(si && si[0] == '0');                             // id-only entry stream of unit-valued fixed-length slots (ensure_ids); FMX_IDS=0: entries
     auto env_on = [](const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); };
     h->seq_rows = env_on("FMX_SEQ_ROWS");                       // FMX_SGD_SEQUENTIAL (fmx_sgd.hip fmx_sgd_epoch, seq_runs_epoch): =0 turns a form off
     h->seq_wg = env_on("FMX_SEQ_WG");

@@ -35,6 +35,10 @@ struct Slot {
   uint64_t  nnz = 0;
   uint32_t  max_row = 0;
   uint32_t  fixed_nnz = 0;           // != 0: every row holds exactly this many entries (row r starts at r * fixed_nnz)
+  // id-only stream of the one-pass SGD kernel (ensure_ids, fmx_core.hip): ids[i] = ent[i].id where fixed_nnz != 0 and EVERY value is 1.0f
+  // (one-hot field data), else nullptr.  4 bytes per entry next to the entries' 8; built once per upload, freed with the slot.
+  uint32_t* ids = nullptr;
+  bool      ids_asked = false;       // the slot's values have been looked at (ids == nullptr then: not such a slot, or FMX_IDS=0)
   bool      used = false;
   double    coll_mass = -1.0;        // collision mass of the rows (ensure_coll_mass); < 0: not computed yet
   double    coll_mass_world = -1.0;  // one process per GPU: the shards' shares summed over the communicator (one collective per slot)
@@ -237,6 +241,7 @@ struct fmx_context_s {
   // small batches of the minibatch rule as ONE launch per batch (k_small_one, fmx_small_kernels.h): {tag, mult_e} and {tag, rest_e} slots; off after a time-out
   unsigned long long* small_slots = nullptr;        // [3 * SMALL_ONE_MAX]: multipliers, rest_e of even / odd batches
   bool small_one = true, small_one_used = false;
+  bool ids = true;                                  // FMX_IDS=0 in the environment of fmx_create: k_fused keeps reading {id, value} entries (Slot::ids is never built)
 };
 
 // ---- helpers shared between the translation units -------------------------------------------------------------
@@ -269,6 +274,7 @@ inline RowsBf16 compact_rows(fmx_handle h, const CompactState& c) { return RowsB
 int ensure_segments(fmx_handle h, Slot& s, uint32_t B);                 // fmx_sgd.hip
 int ensure_coll_mass(fmx_handle h, Slot& s);                             // fmx_core.hip
 int ensure_wside(fmx_handle h, Slot& s);                                 // fmx_core.hip
+int ensure_ids(fmx_handle h, Slot& s);                                   // fmx_core.hip
 inline void touch_w(fmx_handle h) { if (h) h->w_version++; }
 void resolve_batch(const fmx_config& cfg, double coll_mass, uint32_t requested, uint32_t dflt, double curv_scale, fmx_batch_info* out);
 constexpr uint32_t FMX_DEFAULT_BATCH = 262144u;                          // fmx_sgd_opts::batch = 0, before the stability cut

@@ -252,6 +252,13 @@ template <class T> __device__ __forceinline__ T load_stream8(const T* p) {
   static_assert(sizeof(T) == 8, "8-byte records");
   return *p;
 }
+// entry i of a slot's stream for the one-pass kernel.  ids != nullptr: the slot's ID-ONLY stream (Slot::ids -- every value of the slot
+// is 1.0f and every row has the same length, one-hot field data): 4 bytes per entry instead of 8, read once per launch (streaming
+// hint), the value is the constant.  The arithmetic sees the same operands either way.
+__device__ __forceinline__ Entry load_entry(const Entry* __restrict__ ent, const uint32_t* __restrict__ ids, uint64_t i) {
+  if (ids) { Entry e; e.id = __builtin_nontemporal_load(ids + i); e.value = 1.0f; return e; }
+  return load_stream8(ent + i);
+}
 __device__ __forceinline__ float load_w(const float* p) { return *p; }
 // loads that are served by the L2: a relaxed device-scope load (sc1) bypasses the per-CU L1, which no store ever refreshes, and keeps the
 // line in the L2 like a plain load (scripts/ubench/load_flavours.hip: 105-110 ns per dependent load, 72 ns for an L1 hit).  It is what a
@@ -367,7 +374,8 @@ __device__ __forceinline__ double handoff_wait(const double* p, unsigned long lo
 __device__ __forceinline__ void handoff_publish(double* p, double v) {
   __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// counter side: the waiter is ONE thread of the recurrence workgroup (the others sit at the barrier behind it)
+// counter side: the waiter is ONE thread of the recurrence workgroup (the others sit at the barrier behind it).  (A one-wavefront gate kernel
+// in front of the recurrence, so that its 32 workgroups are not resident while they wait, was measured and bought nothing: DESIGN.md section 4.)
 struct Handoff { const unsigned long long* ctr; unsigned long long need; uint32_t* err; };
 // returns false when the counter never arrived (bounded wait; error bit 2): rest[] of the batch may be incomplete then, and the caller
 // must NOT evaluate the recurrence on it -- it hands the incoming bias on unchanged (handoff_pass_on) so that nothing downstream waits
@@ -1524,6 +1532,18 @@ k_wside_mask(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr
   }
 }
 
+// ---- id-only stream (load_entry): ids[i] = the id of entry i; *not_one becomes 1 when some value of the slot is not 1.0f ---------
+static __global__ void __launch_bounds__(256)
+k_ids_build(const Entry* __restrict__ ent, uint64_t nnz, uint32_t* __restrict__ ids, uint32_t* __restrict__ not_one) {
+  bool bad = false;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += (uint64_t)gridDim.x * blockDim.x) {
+    const Entry e = ent[i];
+    ids[i] = e.id;
+    bad = bad || __float_as_uint(e.value) != 0x3F800000u;
+  }
+  if (__ballot(bad) != 0ull && (threadIdx.x & 63u) == 0u) __hip_atomic_store(not_one, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ---- what FUSED_EXACT needs to know about a batch (built once with the segments) ----------------------------------
 // rows that do not fit the register path of k_fused are deferred as a whole
 static __global__ void __launch_bounds__(256)
@@ -1940,7 +1960,9 @@ k_fused(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, con
         uint64_t row0, uint32_t n_rows, const Tab tb, Hyper h,
         const double* __restrict__ w0_ptr, float* __restrict__ rest_out,
         const uint64_t* __restrict__ cmask, float* __restrict__ S_out, float* __restrict__ mult_out, uint32_t fixed_nnz,
-        uint32_t* __restrict__ handoff_err, const uint64_t* __restrict__ lmask, float* __restrict__ wside) {
+        uint32_t* __restrict__ handoff_err, const uint64_t* __restrict__ lmask, float* __restrict__ wside,
+        const uint32_t* __restrict__ ids) {
+  // ids != nullptr: the slot's id-only stream stands in for the entries of the register path (load_entry; needs fixed_nnz != 0)
   // wside != nullptr (FUSED_EXACT, FMX_FLAG_KEEP_WSIDE): the slot's weight side stream is kept current -- entry i of a row gets the NEW
   // w_j when lmask says it is the last occurrence of its feature in the slot and this wavefront is the one that updates it (not deferred),
   // NaN otherwise: 128 coalesced bytes per example (see row_sums)
@@ -1973,7 +1995,7 @@ k_fused(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, con
       Entry en; en.id = 0; en.value = 0.f;
       float wv = 0.f;
       if (lane < size) {
-        en = load_stream8(row + lane);
+        en = load_entry(ent, ids, a + lane);
         if (h.k1) wv = load_w(tb.w + (size_t)en.id * tb.ws);
       }
       // hand-off: the bias slot was asked for before the entry list, so it is here when the entries are (loads return in order) and leaves

@@ -42,7 +42,8 @@ int launch_fused_zr(fmx_handle h, const Slot& s, const Hyper& hy, uint64_t row0,
   if constexpr (fused_zr_ok<KP>(ZRV)) {                                                                     \
     FMX_LAUNCH_WAVES((k_fused<KP, ZRV, VAR>), n_rows, st, s.ent, s.row_ptr, s.target, row0,                 \
                      n_rows, h->tb, hy, w0_in, rest_out, cmask, S_out, mult_out, s.fixed_nnz, handoff_err,                  \
-                     (const uint64_t*)(keep_wside ? s.lmask : nullptr), keep_wside ? s.wside : (float*)nullptr); }
+                     (const uint64_t*)(keep_wside ? s.lmask : nullptr), keep_wside ? s.wside : (float*)nullptr,             \
+                     (const uint32_t*)s.ids); }
   switch (fused_zr_select<KP>(s.max_row)) {
     case 8:  FMX_LAUNCH_ZR(8);  break;
     case 16: FMX_LAUNCH_ZR(16); break;
@@ -871,6 +872,7 @@ static int sgd_epoch_fused(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, cons
   if (d > 4) return fail(h, FMX_E_ARG, "bias_lag %u: at most 4 batches", d);
   E.chunk = opts->w0_chunk ? opts->w0_chunk : default_w0_chunk(h->cfg);
   int rc = ensure_segments(h, s, B); if (rc) return rc;
+  rc = ensure_ids(h, s); if (rc) return rc;                 // unit-valued fixed-length rows: k_fused streams the ids alone
   // FMX_FLAG_KEEP_WSIDE: this epoch keeps the slot's weight side stream current (for the evaluation passes that follow it)
   const bool keep_wside = (opts->flags & FMX_FLAG_KEEP_WSIDE) && hy.k1 && h->cfg.shard_world == 1 && s.blocks.empty();
   if (keep_wside) { rc = ensure_wside(h, s); if (rc) return rc; }
@@ -1130,6 +1132,10 @@ static int epoch_hogwild(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, const 
   const uint32_t chunk = opts->w0_chunk ? opts->w0_chunk : default_w0_chunk(h->cfg);
   const uint32_t cap = std::min<uint32_t>(M, s.n_rows);
   int rc = ensure_scratch(h, 0, (size_t)cap * 3); if (rc) return rc;
+  if (!s.ids_asked) {
+    rc = ensure_ids(h, s); if (rc) return rc;               // unit-valued fixed-length rows: k_fused streams the ids alone
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));           // (the one-time copy is not the epoch's time)
+  }
   const uint64_t n_launch = ((uint64_t)s.n_rows + M - 1) / M;
   while (h->ev_sync.size() < 2 * n_launch) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->ev_sync.push_back(e); }
   for (int r = 0; r < 3; r++) HIPCHK(h, hipMemcpyAsync(h->w0_pp + r, h->w0, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
