@@ -1170,21 +1170,34 @@ int fmx_param_sparsity(fmx_handle h, fmx_sparsity *out);
  *   fmx_compact_get_rows    : w and the dequantised factors of `count` features in the layout of fmx_get_param_rows (w_out[count],
  *                             v_out[count][num_factor]; v_out may be NULL only when num_factor = 0).
  *   fmx_compact_end         : frees the snapshot.
- * Refusals, each before any launch.  FMX_E_ARG: NULL opts, a format other than FMX_COMPACT_BF16, flags != 0, NULL outputs, an
+ *
+ * FMX_COMPACT_INT8: the row-wise 8-bit format.  Every call above serves it.  One aligned block of P bytes per
+ * feature holds the row's k int8 codes, one fp32 scale and w_j (fp32, unchanged) -- there is no separate w array, and a scoring pass
+ * makes ONE access per entry where fp32 and bf16 make two.  P = fmx_compact_row_bytes(FMX_COMPACT_INT8, k): the power of two >= k + 8
+ * up to 128 (k = 64: 128, k = 32: 64, k = 0: 8), k + 8 rounded up to 64 above (k = 128: 192).  Per row, in fp64: a = max_f |v_f|,
+ * q_f = clamp(rint(v_f * (127.0 / a)), -127, 127) with ties to even (all 0 when a = 0), scale = (float)(a / 127.0).  A factor
+ * dequantises to the fp32 product scale * (float)q_f, which fmx_compact_get_rows returns exactly: an exact zero stays zero, the largest
+ * factor of a row has code +-127, |v - deq| <= (a / 127) (0.5 + a few fp32 roundings).  A row with a non-finite factor has scale NaN
+ * and codes 0: all of it dequantises to NaN and every score that touches it is NaN, as from the model; fmx_compact_info::nonfinite
+ * counts its num_factor coordinates, max_abs_err and sum_sq_err are |v - deq| over the other rows, bytes_compact = n_local * P.
+ *
+ * Refusals, each before any launch.  FMX_E_ARG: NULL opts, a format other than FMX_COMPACT_BF16 / FMX_COMPACT_INT8, flags != 0, NULL outputs, an
  * id >= num_attribute, whatever fmx_evaluate_ex / fmx_topk refuse in their own arguments.  FMX_E_STATE: any call but _begin without
  * a snapshot; a slot never uploaded, or without targets where targets are needed.  FMX_E_UNSUPPORTED: a feature shard or
  * communicator rank; a slot with kept `-relation` blocks.  The handle stays usable after every refusal. */
 #define FMX_COMPACT_BF16 1u
+#define FMX_COMPACT_INT8 3u   /* (2 is not assigned) */
 typedef struct fmx_compact_opts {
-  uint32_t format;          /* FMX_COMPACT_BF16 */
+  uint32_t format;          /* FMX_COMPACT_BF16 or FMX_COMPACT_INT8 */
   uint32_t flags;           /* none defined: 0 */
 } fmx_compact_opts;
 typedef struct fmx_compact_info {
   uint64_t features;        /* n_local */
-  uint64_t bytes_compact;   /* device bytes of the snapshot: n_local * (2 * rs + 4), rs = V's row stride in elements */
+  uint64_t bytes_compact;   /* device bytes of the snapshot: n_local * fmx_compact_row_bytes(format, num_factor) */
   uint64_t bytes_params;    /* fmx_info::bytes_params, for comparison */
-  uint64_t nonfinite;       /* coordinates f < num_factor whose bf16 value is inf or NaN */
-  double   max_abs_err;     /* max |v - q(v)| over the finite q(v), f < num_factor */
+  uint64_t nonfinite;       /* bf16: coordinates f < num_factor whose bf16 value is inf or NaN; int8: num_factor per row with a
+                               non-finite factor (all of such a row dequantises to NaN) */
+  double   max_abs_err;     /* max |v - q(v)|, f < num_factor: bf16 over the finite q(v), int8 over the rows without a non-finite factor */
   double   sum_sq_err;      /* sum (v - q(v))^2 over the same, fp64, partial sums added in a fixed order */
 } fmx_compact_info;
 int fmx_compact_begin(fmx_handle h, const fmx_compact_opts *opts, fmx_compact_info *info /* may be NULL */);
@@ -1195,6 +1208,10 @@ int fmx_compact_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk
                      fmx_topk_stats *stats);
 int fmx_compact_get_rows(fmx_handle h, const uint32_t *ids, uint32_t count, double *w_out, double *v_out);
 int fmx_compact_end(fmx_handle h);
+/* host arithmetic, no handle: snapshot bytes per feature -- 2 * rs + 4 for bf16 (rs = V's DEFAULT row stride in elements: num_factor
+ * rounded up to 16 from 32 on, the power of two below; a process run with FMX_ROW_STRIDE_KP=1 pads rows to the power of two and its
+ * fmx_compact_info::bytes_compact says so), P for int8 (which does not depend on the stride), 0 for an unknown format or num_factor < 0 */
+uint32_t fmx_compact_row_bytes(uint32_t format, int num_factor);
 
 /* ---- introspection --------------------------------------------------------------------------- */
 typedef struct fmx_info {

@@ -85,6 +85,7 @@ class Sparsity(C.Structure):                       # fmx_sparsity
 
 
 COMPACT_BF16 = 1    # FMX_COMPACT_BF16: fmx_compact_opts::format
+COMPACT_INT8 = 3    # FMX_COMPACT_INT8 (2 is not assigned)
 
 
 class CompactOpts(C.Structure):                    # fmx_compact_opts
@@ -332,6 +333,7 @@ SYMBOLS = [
     ("fmx_compact_topk", C.c_int, [H, C.c_int, C.c_int, C.POINTER(TopkOpts), C.c_void_p, C.c_void_p, C.POINTER(TopkStats)]),
     ("fmx_compact_get_rows", C.c_int, [H, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("fmx_compact_end", C.c_int, [H]),
+    ("fmx_compact_row_bytes", C.c_uint32, [C.c_uint32, C.c_int]),
     ("fmx_als_begin", C.c_int, [H, C.c_int]),
     ("fmx_als_moments", C.c_int, [H, C.c_void_p]),
     ("fmx_als_sweep", C.c_int, [H, C.POINTER(AlsOpts), C.POINTER(AlsStats)]),
@@ -876,9 +878,9 @@ class Handle:
         self._chk(self.lib.fmx_param_sparsity(self.h, C.byref(sp)))
         return sp
 
-    # the bf16 serving snapshot (include/fmx.h "fmx_compact_*") ---------------------------------
+    # the serving snapshot (include/fmx.h "fmx_compact_*") --------------------------------------
     def compact_begin(self, format=COMPACT_BF16, flags=0):
-        """takes (or replaces) the frozen bf16 copy of the model as it stands; returns its CompactInfo"""
+        """takes (or replaces) the frozen copy of the model as it stands (COMPACT_BF16 or COMPACT_INT8); returns its CompactInfo"""
         opts, info = CompactOpts(int(format), int(flags)), CompactInfo()
         self._chk(self.lib.fmx_compact_begin(self.h, C.byref(opts), C.byref(info)))
         return info

@@ -45,7 +45,8 @@ After training one line on stderr gives the zero counts of the model (fmx_param_
 -serve bf16 (sgd, sgda, bpr, als): after training a frozen bf16 copy of the model is taken on the device (fmx_compact_begin) and the
 -out predictions and the -topk lists come from it.  One "compact" line on stderr carries the copy's bytes next to the fp32 tables',
 max_abs_err and nonfinite of the rounding, and the test metric -- with -metrics each named metric too -- from fp32 and from bf16 side
-by side.  Without the option stdout and stderr are byte for byte what they are.
+by side.  -serve int8 takes the row-wise 8-bit copy instead (codes, scale and linear weight of a feature in one block; the line says
+format=int8 and names its metrics (int8)).  Without the option stdout and stderr are byte for byte what they are.
 """
 import os
 import sys
@@ -93,7 +94,7 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "ftrl_alpha": "-optimizer ftrl: per-coordinate rate of w and V (> 0); default=-learn_rate",
          "ftrl_beta": "-optimizer ftrl: beta (> 0); default=1",
          "l1": "-optimizer ftrl: 'w,v' = L1 strength of the linear weights and of the factors (>= 0); default=0,0",
-         "serve": "bf16: score -out, -metrics and -topk after training from a frozen bf16 copy of the model; sgd, sgda, bpr, als"}
+         "serve": "bf16 | int8: score -out, -metrics and -topk after training from a frozen bf16 or row-wise int8 copy of the model; sgd, sgda, bpr, als"}
 
 
 def read_pairs(path, n_rows):
@@ -290,7 +291,7 @@ def _main(argv):
     serve = a.get("serve")
     if "serve" in a:
         if serve not in C.FORMATS:
-            raise ValueError("-serve knows %s, not '%s'" % (", ".join(C.FORMATS), serve))
+            raise ValueError("-serve knows bf16, not '%s' (also: %s)" % (serve, ", ".join(f for f in C.FORMATS if f != "bf16")))
         if method == "mcmc":
             raise ValueError("-serve is not supported with -method mcmc: its prediction averages the draws, no single model scores it")
         if a.get("relation"):

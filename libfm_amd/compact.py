@@ -1,4 +1,4 @@
-"""fp64 / bit-level restatement of the bf16 serving snapshot (include/fmx.h "fmx_compact_*").  CPU only.
+"""fp64 / bit-level restatement of the serving snapshots (include/fmx.h "fmx_compact_*"; DESIGN.md sections 19 and 21).  CPU only.
 
 bf16 is the upper half of an fp32.  bf16_round rounds to nearest, ties to even, on bit 16: for a bit pattern u that is not a NaN
 
@@ -7,12 +7,16 @@ bf16 is the upper half of an fp32.  bf16_round rounds to nearest, ties to even, 
 so +-0, +-inf and the fp32 subnormals follow the same rule and a finite value above bf16's largest carries into the exponent and
 becomes +-inf.  A NaN stays a NaN: its upper half with the quiet bit set.
 
+int8 is row-wise and symmetric.  For the k factors of one feature, in fp64: a = max |v_f|, inv = 127 / a (0 when a = 0),
+q_f = clamp(rint(v_f * inv), -127, 127) with ties to even, scale = float32(a / 127).  A factor dequantises to the fp32 product
+scale * float32(q_f).  A row with a non-finite factor has scale NaN and codes 0: all of it dequantises to NaN.
+
 CompactModel is what fmx_compact_begin freezes -- w0 and w unchanged, V rounded -- and predicts in fp64 by fm_model::predict
 (fm_model.h:105-127), the formula the fp64 oracle's predict_raw restates.  quant_report gives the three numbers of fmx_compact_info.
 """
 import numpy as np
 
-FORMATS = {"bf16": 1}      # FMX_COMPACT_*: fmx_compact_opts::format
+FORMATS = {"bf16": 1, "int8": 3}      # FMX_COMPACT_*: fmx_compact_opts::format (2 is not assigned)
 
 
 def _bits(a):
@@ -34,9 +38,70 @@ def bf16_round(a):
     return q.view(np.float32).reshape(np.shape(a))
 
 
-def quant_report(v):
-    """(max |v - q(v)|, sum (v - q(v))^2, nonfinite) of a factor table as the device holds it (float32): the maximum and the sum run
-    over the coordinates whose bf16 value is finite, nonfinite counts the others.  v - q(v) is exact in fp32."""
+def int8_quant(v):
+    """factor table v[k][n] (one COLUMN per feature, as get_params returns it) -> (codes int8 [k][n], scale float32 [n])"""
+    v32 = np.ascontiguousarray(v, dtype=np.float32)
+    if v32.ndim != 2:
+        raise ValueError("int8_quant: a [k][n] table")
+    n = v32.shape[1]
+    bad = ~np.isfinite(v32).all(axis=0) if v32.shape[0] else np.zeros(n, dtype=bool)
+    v64 = np.where(bad[None, :], 0.0, v32.astype(np.float64))
+    a = np.abs(v64).max(axis=0) if v32.shape[0] else np.zeros(n)
+    with np.errstate(divide="ignore"):
+        inv = np.where(a > 0.0, 127.0 / np.where(a > 0.0, a, 1.0), 0.0)
+    codes = np.clip(np.rint(v64 * inv[None, :]), -127.0, 127.0).astype(np.int8)
+    scale = (a / 127.0).astype(np.float32)
+    scale[bad] = np.float32(np.nan)
+    return codes, scale
+
+
+def int8_dequant(codes, scale):
+    """(codes [k][n], scale [n]) -> float32 [k][n]: one fp32 multiply per factor"""
+    with np.errstate(invalid="ignore"):
+        return np.asarray(scale, dtype=np.float32)[None, :] * np.asarray(codes).astype(np.float32)
+
+
+def int8_round(v):
+    """float32 table [k][n] -> the float32 values the int8 snapshot holds for it"""
+    return int8_dequant(*int8_quant(v))
+
+
+def row_bytes(format, k):
+    """snapshot bytes per feature (fmx_compact_row_bytes): 2 * rs + 4 for bf16, P(k) for int8, 0 for an unknown format"""
+    k = int(k)
+    if k < 0:
+        return 0
+    if format in ("bf16", FORMATS["bf16"]):
+        kp = 1
+        while kp < max(k, 1):
+            kp <<= 1
+        rs = min(kp, (k + 15) // 16 * 16) if kp >= 32 else kp      # V's row stride in elements
+        return 2 * rs + 4
+    if format in ("int8", FORMATS["int8"]):
+        need = k + 8
+        if need > 128:
+            return (need + 63) // 64 * 64
+        p = 8
+        while p < need:
+            p <<= 1
+        return p
+    return 0
+
+
+def quant_report(v, format="bf16"):
+    """(max |v - q(v)|, sum (v - q(v))^2, nonfinite) of a factor table as the device holds it (float32).
+    bf16: the maximum and the sum run over the coordinates whose bf16 value is finite, nonfinite counts the others; v - q(v) is
+    exact in fp32.  int8 (v[k][n]): they run in fp64 over the rows without a non-finite factor, nonfinite counts k per other row."""
+    if format == "int8":
+        v32 = np.ascontiguousarray(v, dtype=np.float32)
+        if v32.ndim != 2 or v32.shape[0] == 0:
+            return 0.0, 0.0, 0
+        q = int8_round(v32)
+        fin = np.isfinite(v32).all(axis=0)
+        err = np.abs(v32[:, fin].astype(np.float64) - q[:, fin].astype(np.float64)).reshape(-1)
+        return (float(err.max()) if err.size else 0.0), float(np.sum(err * err)), int((~fin).sum()) * v32.shape[0]
+    if format != "bf16":
+        raise ValueError("unknown serving format %r (%s)" % (format, " | ".join(FORMATS)))
     v32 = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
     q = bf16_round(v32)
     fin = np.isfinite(q)
@@ -46,12 +111,21 @@ def quant_report(v):
 
 
 class CompactModel:
-    """the snapshot of a model (w0, w[n], v[k][n]): w0 and w as given, v rounded to bf16 from its fp32 value"""
+    """the snapshot of a model (w0, w[n], v[k][n]): w0 and w as given, v rounded to the format (bf16 | int8) from its fp32 value"""
 
-    def __init__(self, w0, w, v, k0=True, k1=True):
+    def __init__(self, w0, w, v, k0=True, k1=True, format="bf16"):
+        if format not in FORMATS:
+            raise ValueError("unknown serving format %r (%s)" % (format, " | ".join(FORMATS)))
+        self.format = format
         self.w0 = float(w0)
         self.w = np.array(w, dtype=np.float64)
-        self.v = bf16_round(np.asarray(v, dtype=np.float32)).astype(np.float64)
+        v32 = np.asarray(v, dtype=np.float32)
+        if format == "int8" and v32.ndim == 2 and v32.shape[0] > 0:
+            self.v = int8_round(v32).astype(np.float64)
+        elif format == "int8":
+            self.v = v32.astype(np.float64)
+        else:
+            self.v = bf16_round(v32).astype(np.float64)
         self.k0, self.k1 = bool(k0), bool(k1)
         self.k, self.n = (self.v.shape if self.v.ndim == 2 else (0, len(self.w)))
 

@@ -1,4 +1,5 @@
-// fmx_compact_kernels.h -- kernels of the bf16 serving snapshot (fmx_compact.hip; include/fmx.h "fmx_compact_*").
+// fmx_compact_kernels.h -- kernels of the serving snapshots (fmx_compact.hip; include/fmx.h "fmx_compact_*"; DESIGN.md sections 19, 21).
+// bf16 first; the int8 row-wise format (k_compact_quant8, RowsI8) is the second half of the file.
 //
 // k_compact_quant   one pass over V: the bf16 rows (same row stride in ELEMENTS, half the bytes) and the three numbers of
 //                   fmx_compact_info as BLOCK PARTIALS (no float atomics).
@@ -137,12 +138,188 @@ template <int VEC> __device__ __forceinline__ void row_ld_c(const CTab& ct, size
 // The snapshot as a row source of row_sums / k_rowsums / k_fetch_rows (fmx_kernels.h "ROW SOURCE"): MapC's lanes and rounds, row_ld_c,
 // and w out of its own array (no side stream; the snapshot is unsharded, so feature id = row).
 struct RowsBf16 {
+  static constexpr bool W_IN_ROW = false;
   template <int KP> using Lanes = MapC<KP>;
   CTab ct;
   template <int VEC> __device__ __forceinline__ void ld(size_t id, uint32_t off, float (&out)[VEC]) const { row_ld_c<VEC>(ct, id, off, out); }
   __device__ __forceinline__ float w1(size_t row) const { return load_w(ct.w + row); }
   __device__ __forceinline__ float v1(size_t row, int f) const { return __uint_as_float((uint32_t)ct.V[row * ct.rs + f] << 16); }
   __device__ __forceinline__ float lin(uint32_t id, uint64_t, uint32_t) const { return w1((size_t)id); }
+};
+
+// ==============================================================================================
+// The int8 row-wise snapshot (FMX_COMPACT_INT8).  ONE aligned block of P bytes per feature holds everything a
+// scoring pass wants of it:
+//   bytes 0..3  scale (fp32)      bytes 4..7  w_j (fp32)      bytes 8..8+k  the codes q_f (int8), zeros up to P
+// P = compact8_row_bytes(k): the power of two >= k + 8 up to 128 (k = 64: 72 bytes in one 128-byte line; k = 32: 40 in one 64-byte
+// sector), k + 8 rounded up to 64 above.  There is no w array.
+// Codes: a = max_f |v_f|, q_f = clamp(rint(v_f * (127.0 / a)), -127, 127) in fp64 (ties to even), scale = (float)(a / 127.0); a row
+// with a non-finite factor has scale NaN and codes 0.  A factor dequantises to fl32(scale * (float)q_f), one fp32 multiply.
+// ==============================================================================================
+__host__ __device__ constexpr uint32_t compact8_row_bytes(uint32_t k) {
+  uint32_t need = k + 8u, p = 8u;
+  if (need > 128u) return (need + 63u) / 64u * 64u;
+  while (p < need) p <<= 1;
+  return p;
+}
+
+constexpr int QUANT8_T = 5;      // dwords of a block per lane of k_compact_quant8, at most: P / 4 <= 272 dwords on 64 lanes (k <= 1024)
+
+// L lanes (a power of two <= 64, L * QUANT8_T >= P / 4) share a feature, 64 / L features per wavefront round.  Lane `sub` holds the dwords
+// sub, sub + L, ... of the block: dword 0 is the scale, dword 1 is w_j, dword d >= 2 the codes of factors 4 (d - 2) .. 4 (d - 2) + 3, whose
+// fp32 values the lane keeps in registers between the absmax butterfly and the rounding -- V is read once.
+//   dpart[2 * b + {0: max |v - deq|, 1: sum (v - deq)^2}] over the finite rows in fp64, cpart[b] = k per row with a non-finite factor
+static __global__ void __launch_bounds__(256)
+k_compact_quant8(const float* __restrict__ V, const float* __restrict__ w, uint32_t rs, uint64_t n, int k, uint32_t L, uint32_t P,
+                 uint8_t* __restrict__ out, double* __restrict__ dpart, unsigned long long* __restrict__ cpart) {
+  __shared__ double dred[2][4];
+  __shared__ unsigned long long cred[4];
+  const uint32_t lane = threadIdx.x & 63u, grp = lane / L, sub = lane % L, rpw = 64u / L;
+  const uint32_t nd = P / 4u;
+  const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  double mx = 0.0, ss = 0.0; unsigned long long nf = 0ull;
+  for (uint64_t r0 = wave * rpw; r0 < n; r0 += nwaves * rpw) {     // (r0 is wave-uniform: every lane takes part in the butterflies)
+    const uint64_t j = r0 + grp;
+    const bool live = j < n;
+    float vals[QUANT8_T][4];
+    float amax = 0.f; int bad = 0;
+#pragma unroll
+    for (int t = 0; t < QUANT8_T; t++) {
+      const uint32_t d = sub + (uint32_t)t * L;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int f = 4 * ((int)d - 2) + i;
+        float v = 0.f;
+        if (live && d >= 2u && d < nd && f < k) v = V[j * rs + (uint32_t)f];
+        vals[t][i] = v;
+        const float av = fabsf(v);
+        if (!(av <= 3.402823466e+38f)) bad = 1;                    // inf or NaN
+        amax = fmaxf(amax, av);
+      }
+    }
+    for (uint32_t o = L >> 1; o > 0; o >>= 1) { amax = fmaxf(amax, __shfl_xor(amax, (int)o)); bad |= __shfl_xor(bad, (int)o); }
+    const double a = (double)amax;
+    const double inv = a > 0.0 ? 127.0 / a : 0.0;
+    const float scale = bad ? __uint_as_float(0x7FC00000u) : (float)(a / 127.0);
+    if (live) {
+      uint32_t* blk = reinterpret_cast<uint32_t*>(out + j * P);
+#pragma unroll
+      for (int t = 0; t < QUANT8_T; t++) {
+        const uint32_t d = sub + (uint32_t)t * L;
+        if (d >= nd) continue;
+        uint32_t word = 0u;
+        if (d == 0u) word = __float_as_uint(scale);
+        else if (d == 1u) word = __float_as_uint(w[j]);
+        else if (!bad) {
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            const int f = 4 * ((int)d - 2) + i;
+            if (f < k) {
+              const float v = vals[t][i];
+              const double q = fmin(fmax(rint((double)v * inv), -127.0), 127.0);
+              const int qi = (int)q;
+              word |= ((uint32_t)qi & 0xFFu) << (8 * i);
+              const float deq = scale * (float)qi;
+              const double err = fabs((double)v - (double)deq);
+              mx = fmax(mx, err);
+              ss += err * err;
+            }
+          }
+        }
+        blk[d] = word;
+      }
+      if (bad && sub == 0u) nf += (unsigned long long)k;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { mx = fmax(mx, __shfl_xor(mx, o)); nf += __shfl_xor(nf, o); }
+  ss = wave_sum_d(ss);
+  const uint32_t wv = threadIdx.x >> 6;
+  if (lane == 0) { dred[0][wv] = mx; dred[1][wv] = ss; cred[wv] = nf; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    dpart[2 * blockIdx.x + 0] = fmax(fmax(dred[0][0], dred[0][1]), fmax(dred[0][2], dred[0][3]));
+    dpart[2 * blockIdx.x + 1] = (dred[1][0] + dred[1][1]) + (dred[1][2] + dred[1][3]);
+    cpart[blockIdx.x] = (cred[0] + cred[1]) + (cred[2] + cred[3]);
+  }
+}
+
+// ----------------------------------------------------------------------------------------------
+// The lane map of an int8 block.  A lane loads VEC bytes (8, one dwordx2, up to KP = 256; 16 / 32 above) and owns VEC factor SLOTS; slot v
+// of lane f of a row's LPR lanes is byte f * VEC + v of the block, i.e. factor f * VEC + v - 8.  Lane 0 of the row therefore holds the
+// header (scale, w_j) in its first 8 bytes -- with VEC = 8 nothing else -- and FL = LPR - 1 .. LPR lanes hold factors:
+//   KP      <= 8   16   32   64   128   256   512   1024
+//   VEC        8    8    8    8     8     8    16     32
+//   LPR        2    4    8   16    32    64    64     64      (the power of two >= (KP + 8) / VEC lanes)
+//   EPI       32   16    8    4     2     1     1      1      rows per wave-wide load (k = 64: four 128-byte lines, header and codes at once)
+//   U          2    2    2    2     4     8     8      8      rounds in flight: EPI * U = min(8 * Map<KP>::EPI, 64) rows, as RowsF32 asks for
+// The map is a function of KP; the block's size P is one of k.  Lanes whose bytes lie at or beyond P (k = 40: P = 64 under KP = 64's
+// sixteen lanes) load nothing and hold zeros, like the lanes beyond rs of the other sources.
+// ----------------------------------------------------------------------------------------------
+constexpr int pow2_ge(int x) { int p = 1; while (p < x) p <<= 1; return p; }
+template <int KP> struct MapI8 {
+  static constexpr int VEC = (KP <= 256) ? 8 : KP / 32;
+  static constexpr int LPR = pow2_ge((KP + 8 + VEC - 1) / VEC);
+  static constexpr int EPI = 64 / LPR;
+  static constexpr int ROWS = 8 * Map<KP>::EPI < 64 ? 8 * Map<KP>::EPI : 64;   // rows a round asks for (a 64-entry block holds no more)
+  static constexpr int U = ROWS / EPI;
+  static_assert(LPR <= 64 && LPR * VEC >= KP + 8 && U >= 1, "a row's lanes cover header and codes");
+};
+
+template <int VEC> struct RawI8 { uint32_t u[VEC / 4] = {}; };
+
+struct RowsI8 {
+  static constexpr bool W_IN_ROW = true;
+  static constexpr int FOFF = 8;                                   // bytes of the header in front of the codes
+  template <int KP> using Lanes = MapI8<KP>;
+  template <int VEC> using Raw = RawI8<VEC>;
+  const uint8_t* B; uint32_t P;                                    // the blocks, P bytes each (the snapshot is unsharded: feature id = row)
+
+  // the lane's VEC bytes of block id: ONE non-temporal load (two dwordx4 at VEC = 32), zeros at or beyond P
+  template <int VEC> __device__ __forceinline__ void ld_raw(size_t id, uint32_t f, RawI8<VEC>& r) const {
+    constexpr int NW = VEC / 4;
+    const uint32_t off = f * VEC;
+    if (off < P) {
+      const uint8_t* p = B + id * P + off;
+      if constexpr (NW == 2) {
+        typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+        const v2u t = (FMX_V_NT & 4) ? __builtin_nontemporal_load(reinterpret_cast<const v2u*>(p)) : *reinterpret_cast<const v2u*>(p);
+        r.u[0] = t.x; r.u[1] = t.y;
+      } else {
+        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+#pragma unroll
+        for (int c = 0; c < NW / 4; c++) {
+          const v4u t = (FMX_V_NT & 4) ? __builtin_nontemporal_load(reinterpret_cast<const v4u*>(p) + c) : reinterpret_cast<const v4u*>(p)[c];
+          r.u[4 * c] = t.x; r.u[4 * c + 1] = t.y; r.u[4 * c + 2] = t.z; r.u[4 * c + 3] = t.w;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < NW; c++) r.u[c] = 0u;
+    }
+  }
+  // the scale comes from the row's lane 0 by a cross-lane read (no LDS allocation); the header's own 8 slots are not factors: zeros.
+  // wj: w_j on the header lane, 0 elsewhere.  Called by all 64 lanes.
+  template <int KP, int VEC> __device__ __forceinline__ void unpack(const RawI8<VEC>& r, uint32_t f, float (&out)[VEC], float& wj) const {
+    constexpr int LPR = MapI8<KP>::LPR;
+    float scale;
+    if constexpr (LPR == 64) scale = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)r.u[0], 0));
+    else scale = __uint_as_float((uint32_t)__shfl((int)r.u[0], 0, LPR));
+    const bool hdr = f == 0u;
+    wj = hdr ? __uint_as_float(r.u[1]) : 0.f;
+#pragma unroll
+    for (int v = 0; v < VEC; v++) {
+      const int q = (int)(int8_t)(r.u[v / 4] >> (8 * (v % 4)));
+      const float x = scale * (float)q;
+      out[v] = (v < FOFF && hdr) ? 0.f : x;
+    }
+  }
+  __device__ __forceinline__ float w1(size_t row) const { return *reinterpret_cast<const float*>(B + row * P + 4); }
+  __device__ __forceinline__ float v1(size_t row, int f) const {
+    const uint8_t* p = B + row * P;
+    return *reinterpret_cast<const float*>(p) * (float)(int)(int8_t)p[FOFF + f];
+  }
 };
 
 }  // namespace fmx

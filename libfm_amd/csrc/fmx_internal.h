@@ -164,8 +164,10 @@ struct AdaptState { float* nw = nullptr; float* nv = nullptr; float eta = 0.f; }
 // an open fmx_ftrl_* session (fmx_sgd.hip): z and n per coordinate, the row tables with V's row stride, and the rule's constants
 struct FtrlState { float* zw = nullptr; float* zv = nullptr; float* nw = nullptr; float* nv = nullptr;
                    float inv_alpha = 0.f, beta = 0.f, l1_w = 0.f, l1_v = 0.f, l2_w = 0.f, l2_v = 0.f; };
-// the bf16 serving snapshot (fmx_compact_*, fmx_compact.hip): a frozen copy of w0, w (fp32, stride 1) and V as bf16 rows of tb.rs elements
-struct CompactState { uint16_t* V = nullptr; float* w = nullptr; double* w0 = nullptr; };
+// the serving snapshot (fmx_compact_*, fmx_compact.hip): a frozen copy of w0 and, by format,
+//   FMX_COMPACT_BF16  w (fp32, stride 1) and V as bf16 rows of tb.rs elements
+//   FMX_COMPACT_INT8  B: one block of P bytes per feature with its scale, its w and its int8 codes (V and w stay null)
+struct CompactState { uint16_t* V = nullptr; float* w = nullptr; double* w0 = nullptr; uint8_t* B = nullptr; uint32_t P = 0; uint32_t format = 0; };
 
 struct fmx_context_s {
   fmx_config cfg;
@@ -271,6 +273,7 @@ int slot_scores(fmx_handle h, const Slot& s, const CompactState* snap, bool want
 int predict_out(fmx_handle h, const Slot& s, const CompactState* snap, double* out);
 int evaluate_out(fmx_handle h, const Slot& s, const CompactState* snap, fmx_eval* out);
 inline RowsBf16 compact_rows(fmx_handle h, const CompactState& c) { return RowsBf16{CTab{c.V, c.w, h->tb.rs}}; }
+inline RowsI8 compact_rows8(const CompactState& c) { return RowsI8{c.B, c.P}; }
 int ensure_segments(fmx_handle h, Slot& s, uint32_t B);                 // fmx_sgd.hip
 int ensure_coll_mass(fmx_handle h, Slot& s);                             // fmx_core.hip
 int ensure_wside(fmx_handle h, Slot& s);                                 // fmx_core.hip
@@ -379,6 +382,10 @@ void mark_device_used(int dev);                                          // fmx_
 int place_tables(fmx_handle h);                                          // fmx_mem.hip: h->tb.V, h->w_sep and the placement report
 void free_tables(fmx_handle h);                                          // fmx_mem.hip
 template <class T> inline hipError_t fmx_dev_alloc(T** p, size_t bytes) { return fmx_dev_alloc_bytes(reinterpret_cast<void**>(p), bytes); }
+// one plain allocation of any size, never a chunked range (freed by fmx_dev_free like the others).  For memory that is taken again right
+// after memory of the same size went back, as a serving snapshot that replaces another is: see fmx_compact_begin
+hipError_t fmx_dev_alloc_plain_bytes(void** p, size_t bytes);            // fmx_mem.hip
+template <class T> inline hipError_t fmx_dev_alloc_plain(T** p, size_t bytes) { return fmx_dev_alloc_plain_bytes(reinterpret_cast<void**>(p), bytes); }
 
 // everything a call of the exact metrics (fmx_eval.hip, fmx_evalq.hip) takes from the device, freed on every path out of the call:
 // each function allocates the members it uses and the others stay null

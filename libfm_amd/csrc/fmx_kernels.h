@@ -426,13 +426,19 @@ static __global__ void k_handoff_arm(double* W, uint32_t n) {         // W[1 .. 
 //   ld<VEC>(id, off, out) VEC factors of row id from element offset off, zeros beyond the row's rs elements
 //   lin(id, i0, i)       the linear weight of entry i0 + i of the slot's stream, whose feature is id
 //   w1(row), v1(row, f)  one weight / one factor (k_fetch_rows)
-// RowsF32 is the model (Tab); RowsBf16 (fmx_compact_kernels.h) the bf16 snapshot.  The sums, their order and what k_rowsums does with
-// them are written once, here.
+//   W_IN_ROW             false: lin() as above.  true: the weight travels IN the row -- the source supplies instead
+//                          FOFF                 slot v of lane f (of a row's LPR lanes) is factor f * VEC + v - FOFF; slots outside [0, KP) are
+//                                               not factors (a header, idle lanes) and hold zeros
+//                          Raw<VEC>, ld_raw     what one lane loads of row id, kept as loaded while the round is in flight
+//                          unpack<KP>           the lane's VEC factor slots of it, and w_j on the lane that holds it (0 elsewhere)
+// RowsF32 is the model (Tab); RowsBf16 and RowsI8 (fmx_compact_kernels.h) the bf16 and int8 snapshots.  The sums, their order and what
+// k_rowsums does with them are written once, here.
 // wside (optional): the slot's WEIGHT SIDE STREAM -- wside[i] is either w[id_i] as it stands or NaN ("gather it").
 // A 4-byte w_j out of its own array costs a 64-byte fabric request per entry (a third of a predict pass's requests for 1.5 % of its
 // bytes); the stream costs 4 coalesced bytes.  Maintained by k_fused<EXACT> for the entries that are the LAST occurrence of their
 // feature in the slot and are updated by their own example (FMX_FLAG_KEEP_WSIDE; fmx_sgd.hip), NaN for everything else.
 struct RowsF32 {
+  static constexpr bool W_IN_ROW = false;
   template <int KP> struct Lanes : Map<KP> { static constexpr int U = 8; };
   Tab tb; const float* wside = nullptr;
   template <int VEC> __device__ __forceinline__ void ld(size_t id, uint32_t off, float (&out)[VEC]) const { row_ld<VEC, 4>(tb, id, off, out); }
@@ -447,8 +453,59 @@ struct RowsF32 {
 
 // i0: where the row's first entry stands in the slot's stream (the side stream's index)
 template <int KP, class Src>
+__device__ __forceinline__ void row_sums_gather(const Entry* __restrict__ ent, uint32_t size, const Src src, int k1,
+                                                float (&sum)[Src::template Lanes<KP>::VEC], float& sq, float& lin, uint64_t i0);
+// a source with W_IN_ROW: one load per lane brings the row's factors, or its scale and its w_j -- no second gather.  The EPI * U loads
+// of a round are all issued before the first is unpacked; lin is accumulated by the lane that holds the header.
+template <int KP, class Src>
+__device__ __forceinline__ void row_sums_inrow(const Entry* __restrict__ ent, uint32_t size, const Src src, int k1,
+                                               float (&sum)[Src::template Lanes<KP>::VEC], float& sq, float& lin) {
+  typedef typename Src::template Lanes<KP> L;
+  typedef typename Src::template Raw<L::VEC> Raw;
+  constexpr int VEC = L::VEC, LPR = L::LPR, EPI = L::EPI, U = L::U;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t g = lane / LPR, f = lane % LPR;
+#pragma unroll
+  for (int v = 0; v < VEC; v++) sum[v] = 0.f;
+  sq = 0.f; lin = 0.f;
+  for (uint32_t base = 0; base < size; base += 64) {
+    const uint32_t cnt = min(64u, size - base);
+    Entry e; e.id = 0; e.value = 0.f;
+    if (lane < cnt) e = load_stream8(ent + base + lane);
+    for (uint32_t i = 0; i < cnt; i += EPI * U) {
+      Raw raw[U]; float xs[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const uint32_t idx = i + u * EPI + g;
+        const uint32_t id = bcast_u32<EPI>(e.id, idx & 63u);
+        xs[u] = bcast_f32<EPI>(e.value, idx & 63u);
+        if (idx < cnt) src.template ld_raw<VEC>((size_t)id, f, raw[u]);
+        else { xs[u] = 0.f; raw[u] = Raw(); }
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        float vr[VEC], wj;
+        src.template unpack<KP>(raw[u], f, vr, wj);
+        if (k1) lin = fmaf(wj, xs[u], lin);
+#pragma unroll
+        for (int v = 0; v < VEC; v++) {
+          const float d = vr[v] * xs[u];
+          sum[v] += d;
+          sq = fmaf(d, d, sq);
+        }
+      }
+    }
+  }
+}
+template <int KP, class Src>
 __device__ __forceinline__ void row_sums(const Entry* __restrict__ ent, uint32_t size, const Src src, int k1,
                                          float (&sum)[Src::template Lanes<KP>::VEC], float& sq, float& lin, uint64_t i0 = 0) {
+  if constexpr (Src::W_IN_ROW) row_sums_inrow<KP>(ent, size, src, k1, sum, sq, lin);
+  else row_sums_gather<KP>(ent, size, src, k1, sum, sq, lin, i0);
+}
+template <int KP, class Src>
+__device__ __forceinline__ void row_sums_gather(const Entry* __restrict__ ent, uint32_t size, const Src src, int k1,
+                                                float (&sum)[Src::template Lanes<KP>::VEC], float& sq, float& lin, uint64_t i0) {
   typedef typename Src::template Lanes<KP> L;
   constexpr int VEC = L::VEC, LPR = L::LPR, EPI = L::EPI, U = L::U;
   const uint32_t lane = threadIdx.x & 63u;
@@ -545,7 +602,7 @@ __device__ __forceinline__ void row_apply(const Entry* __restrict__ ent, uint32_
 //   S[e][0..KP)           (WRITE_S)  the (partial) factor sums
 //   scal[e]               FINISH ? rest_e = lin + 0.5*(sum_f S_ef^2 - Q_e)   (single device)
 //                                : c_e    = lin - 0.5*Q_e                    (feature shard; all-reduced later)
-// Used by predict / evaluate (WRITE_S = false, FINISH = true) and by the minibatch step; from the bf16 snapshot with Src = RowsBf16.
+// Used by predict / evaluate (WRITE_S = false, FINISH = true) and by the minibatch step; from a snapshot with Src = RowsBf16 / RowsI8.
 // No LDS, no atomics.
 // ----------------------------------------------------------------------------------------------
 template <int KP, bool WRITE_S, bool FINISH, class Src = RowsF32>
@@ -563,11 +620,24 @@ k_rowsums(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, u
     row_sums<KP>(ent + a, size, src, k1, sum, sq, lin, a);
 #pragma unroll
     for (int v = 0; v < VEC; v++) sum[v] = subgroup_allsum<LPR>(sum[v]);
-    if (WRITE_S && lane < LPR) store_vec<VEC>(S + (size_t)e * KP + lane * VEC, sum);
     float part = lin - 0.5f * sq;
-    if (FINISH && lane < LPR) {
+    if constexpr (Src::W_IN_ROW) {                  // only the slots that are factors are stored and squared (header and idle lanes: none)
+      if ((WRITE_S || FINISH) && lane < LPR) {
 #pragma unroll
-      for (int v = 0; v < VEC; v++) part = fmaf(0.5f * sum[v], sum[v], part);
+        for (int v = 0; v < VEC; v++) {
+          const int fi = (int)lane * VEC + v - Src::FOFF;
+          if (fi >= 0 && fi < KP) {
+            if (WRITE_S) S[(size_t)e * KP + fi] = sum[v];
+            if (FINISH) part = fmaf(0.5f * sum[v], sum[v], part);
+          }
+        }
+      }
+    } else {
+      if (WRITE_S && lane < LPR) store_vec<VEC>(S + (size_t)e * KP + lane * VEC, sum);
+      if (FINISH && lane < LPR) {
+#pragma unroll
+        for (int v = 0; v < VEC; v++) part = fmaf(0.5f * sum[v], sum[v], part);
+      }
     }
     part = wave_sum_dpp(part);
     if (lane == 0) scal[e] = part;
@@ -2393,7 +2463,7 @@ static __global__ void k_w_out(double* __restrict__ stage, uint64_t j0, uint32_t
   if (sh.place((uint32_t)(j0 + t), &jl)) stage[t] = (double)tb.w[(size_t)jl * tb.ws];
 }
 
-// rows named by feature id out of a row source (RowsF32: the model or a state table; RowsBf16: the snapshot, dequantised)
+// rows named by feature id out of a row source (RowsF32: the model or a state table; RowsBf16 / RowsI8: a snapshot, dequantised)
 template <class Src>
 __global__ void k_fetch_rows(const uint32_t* __restrict__ ids, uint32_t count, int k, Shard sh, Src src,
                              double* __restrict__ w_out, double* __restrict__ v_out) {

@@ -220,6 +220,11 @@ hipError_t fmx_dev_alloc_bytes(void** p, size_t bytes) {
   if (ms > 0.5) fprintf(stderr, "[fmx alloc] %12zu bytes %9.3f ms%s\n", bytes, ms, e == hipSuccess ? "" : " FAILED");
   return e;
 }
+hipError_t fmx_dev_alloc_plain_bytes(void** p, size_t bytes) {
+  if (!p) return hipErrorInvalidValue;
+  *p = nullptr;
+  return plain_alloc(p, bytes);
+}
 hipError_t fmx_dev_free(void* p) {
   if (!p) return hipSuccess;
   BigAlloc b; bool big = false;

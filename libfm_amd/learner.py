@@ -167,7 +167,7 @@ def _check_queries(data, qid):
 
 
 class CompactView:
-    """A frozen bf16 copy of a learner's model on the device (fmx_compact_*), scored like the learner itself: predict, evaluate,
+    """A frozen bf16 or int8 copy of a learner's model on the device (fmx_compact_*), scored like the learner itself: predict, evaluate,
     evaluate_ex and recommend mirror the learner's methods, link and clamping included, and read the copy, so training the
     learner further does not change what they return.  `info` is the capi.CompactInfo of the copy (bytes, max_abs_err,
     nonfinite).  A handle holds one copy: learner.compact() again replaces it under every earlier view; close() frees it."""
