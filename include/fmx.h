@@ -1044,7 +1044,9 @@ int fmx_sgda_end(fmx_handle h);
  *                     to a power of two below 32) and sets every accumulator to init_acc: 4 * n_local * (row stride + 1) bytes stay
  *                     resident until fmx_adapt_end / fmx_destroy.  Called again it resets the accumulators (and takes the new
  *                     options).  Unlike fmx_sgda_begin NOTHING in the model is reset.  fmx_set_params, fmx_load_model and plain
- *                     fmx_sgd_epoch leave the accumulators alone while a session is open.
+ *                     fmx_sgd_epoch leave the accumulators alone while a session is open; so do plain fmx_pair_epoch and
+ *                     fmx_pair_epoch_sampled, which still train with learn_rate (the session's pairwise epochs are
+ *                     fmx_adapt_pair_epoch / fmx_adapt_pair_epoch_sampled, below).
  *   fmx_adapt_epoch : one epoch.  batch = 0 resolves exactly as fmx_sgd_opts::batch = 0 does (the plain rule's stability cut --
  *                     conservative on purpose); an explicit batch is honoured.  w0_chunk = 0: fmx_default_w0_chunk.  The stats are
  *                     filled as fmx_sgda_epoch_minibatch fills them (rows, batches, device_seconds, main_kernel_*,
@@ -1103,7 +1105,9 @@ int fmx_adapt_end(fmx_handle h);
  *                     and derives z.  Called again it resets both from the parameters of that moment (and takes the new options).
  *                     NOTHING in the model is changed.  fmx_set_params, fmx_load_model and plain fmx_sgd_epoch during a session
  *                     leave z and n alone -- the next epoch then continues from parameters z no longer describes: call
- *                     fmx_ftrl_begin again after them.
+ *                     fmx_ftrl_begin again after them.  The same holds for plain fmx_pair_epoch / fmx_pair_epoch_sampled, which
+ *                     still train with learn_rate (the session's pairwise epochs are fmx_ftrl_pair_epoch /
+ *                     fmx_ftrl_pair_epoch_sampled, below).
  *   fmx_ftrl_epoch  : one epoch; batch = 0, w0_chunk = 0, the stats and an empty slot exactly as fmx_adapt_epoch.
  *   fmx_ftrl_get_state_rows : z and n of `count` features, gathered on the device; each pair in the layout of fmx_get_param_rows
  *                     (zw[count], zv[count][num_factor], nw[count], nv[count][num_factor]; zv / nv may be NULL only when
@@ -1128,6 +1132,34 @@ int fmx_ftrl_begin(fmx_handle h, const fmx_ftrl_opts *opts);
 int fmx_ftrl_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
 int fmx_ftrl_get_state_rows(fmx_handle h, const uint32_t *ids, uint32_t count, double *zw, double *zv, double *nw, double *nv);
 int fmx_ftrl_end(fmx_handle h);
+
+/* ---- pairwise ranking (BPR) stepped by an open session's per-coordinate rule ------------------------------------------------
+ * The pairwise batch rule multiplies a (batch, feature) segment's summed gradient by ONE learn_rate; a popular item's segment sums
+ * thousands of pair gradients and there is no stability cut.  These four calls run the epoch of fmx_pair_epoch /
+ * fmx_pair_epoch_sampled in FMX_SGD_MINIBATCH unchanged up to the owner -- the same pairs, the same negatives (FMX_NEG_HARDEST
+ * included), the same sums, multipliers and (batch, feature) bucketing, w0 -= reg0 * w0 once per pair in fp64 -- and then step every
+ * touched coordinate with the open session's rule.  For every feature j of a batch, from the batch-start theta (w_j with k1, every
+ * v_jf) and the segment's entries in pair order:
+ *   fmx_adapt_pair_epoch*  g = sum over the pairs t of the batch that contain j of (mult_t * grad_tj + reg * theta): the sum the plain
+ *                          rule multiplies by learn_rate, one regularisation term per distinct pair, in fp64; g32 = (float)g; then
+ *                          n' = fmaf(g32, g32, n), theta' = theta - eta * g32 / sqrtf(n') in fp32: |theta' - theta| <= eta whatever
+ *                          the batch sums.
+ *   fmx_ftrl_pair_epoch*   the same sum WITHOUT the regularisation terms (L2 lives in the proximal step), g32 = (float)g, then the
+ *                          proximal step of "fmx_ftrl_*" with the session's constants; a touched coordinate is recomputed from z'.
+ * The state is the session's own tables: pointwise fmx_adapt_epoch / fmx_ftrl_epoch and these pairwise epochs may alternate within
+ * one session.  The padding of a row beyond num_factor is never read or written; a feature that no batch touches keeps theta and
+ * its state bit for bit; batch = 1 gives the per-pair rule (there is no sequential form); one owner per (batch, feature) segment, no
+ * atomics: two runs of the same calls are bit-identical.  opts, flags, the stats and forced_out are those of the plain calls.
+ * Refusals, each before any launch, the handle usable afterwards: everything the plain counterpart refuses; FMX_E_STATE without the
+ * matching open session (and for the fmx_ftrl_ calls while an fmx_adapt session is open); FMX_E_UNSUPPORTED for FMX_SGD_SEQUENTIAL
+ * and FMX_SGD_HOGWILD (the rule runs on FMX_SGD_MINIBATCH; batch = 1 is the per-pair rule).
+ * The plain fmx_pair_epoch / fmx_pair_epoch_sampled are unchanged: during a session they still train with learn_rate and leave the
+ * state alone (after them an FTRL session's z no longer describes the parameters: fmx_ftrl_begin again).
+ * Added without an ABI version change: a caller detects the feature by the symbol fmx_adapt_pair_epoch. */
+int fmx_adapt_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts *opts, fmx_epoch_stats *stats);
+int fmx_adapt_pair_epoch_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts *o, fmx_epoch_stats *stats, uint64_t *forced_out);
+int fmx_ftrl_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts *opts, fmx_epoch_stats *stats);
+int fmx_ftrl_pair_epoch_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts *o, fmx_epoch_stats *stats, uint64_t *forced_out);
 
 /* How many coordinates of the model are exactly zero -- on any unsharded handle, with or without a training session.  One pass over
  * both tables on the device, integer sums only.  `== 0.0f` decides: -0 counts, NaN does not; only f < num_factor of a row is looked

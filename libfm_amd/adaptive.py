@@ -113,3 +113,112 @@ def epoch(model, data, task, lr, min_target, max_target, batch, w0_chunk, state,
                 max_step = max(max_step, float(np.abs(new.astype(np.float64) - vj.astype(np.float64)).max()))
             model.v[:, feats] = new.T
     return max_step
+
+
+# ---- pairwise ranking (BPR) on the batch rule, stepped per coordinate (the CPU reference of fmx_adapt_pair_epoch) ----------------
+# One epoch cuts the pairs (row pa[t] preferred to row pb[t]) into batches of `batch` consecutive pairs.  Per batch, from the
+# batch-start parameters: per pair d = y_a - y_b (fm_model::predict on both rows), mult = -(1 - sigmoid(d)) and the gradients of
+# fm_pairSGD for every DISTINCT feature of the pair (fm_sgd.h:53-126); per feature j of the batch
+#     g = sum over the pairs t of the batch that contain j of (mult_t grad_tj [+ reg theta_j])       (float64, pair order)
+# -- the sum the plain batch rule multiplies by its learning rate, one regularisation term per distinct pair -- and then one step of
+# the rule per coordinate.  w0 -= reg0 w0 once per pair.  batch = 1 is the per-pair rule.
+
+def _pair_row(entries, row_ptr, r):
+    a, b = int(row_ptr[r]), int(row_ptr[r + 1])
+    e = entries[a:b]
+    return e["id"].astype(np.int64), e["value"].astype(np.float32).astype(np.float64)
+
+
+def _pair_predict(model, ids, xs):
+    """fm_model::predict (fm_model.h:105-127) in its order, without the bias (it cancels in y_a - y_b): (y, sum[k])"""
+    y = 0.0
+    if model.k1 and len(ids):
+        y = float(np.cumsum(model.w[ids] * xs)[-1])
+    k = model.v.shape[0]
+    if k == 0:
+        return y, np.zeros(0)
+    if len(ids) == 0:
+        return y, np.zeros(k)
+    d = model.v[:, ids] * xs                                                        # [k][entries]
+    s = np.cumsum(d, axis=1)[:, -1]
+    q = np.cumsum(d * d, axis=1)[:, -1]
+    return float(np.cumsum(np.concatenate([[y], 0.5 * (s * s - q)]))[-1]), s
+
+
+def pair_batch_sums(model, entries, row_ptr, pa, pb, t0, t1, reg=True):
+    """the gradient sums of the pairs [t0, t1) from the parameters `model` holds now: (feats int64 [m] in first-touch order,
+    g_w float64 [m], g_v float64 [m][k]); reg=False leaves the regularisation terms out"""
+    k = model.v.shape[0]
+    index, gw, gv = {}, [], []
+    for t in range(t0, t1):
+        ia, xa = _pair_row(entries, row_ptr, int(pa[t]))
+        ib, xb = _pair_row(entries, row_ptr, int(pb[t]))
+        ya, sa = _pair_predict(model, ia, xa)
+        yb, sb = _pair_predict(model, ib, xb)
+        mult = -(1.0 - 1.0 / (1.0 + np.exp(-(ya - yb))))                            # util.h:52
+        pw, pv, order = {}, {}, []
+        for ids, xs, s, sign in ((ia, xa, sa, 1.0), (ib, xb, sb, -1.0)):
+            for j, x in zip(ids, xs):
+                j = int(j)
+                if j not in pw:
+                    order.append(j)
+                    pw[j] = 0.0
+                    pv[j] = np.zeros(k)
+                pw[j] += sign * x                                                   # fm_sgd.h:67-72
+                pv[j] += sign * (s * x - model.v[:, j] * x * x)                     # :100-105
+        for j in order:
+            if j not in index:
+                index[j] = len(gw)
+                gw.append(0.0)
+                gv.append(np.zeros(k))
+            i = index[j]
+            gw[i] += mult * pw[j] + (model.regw * model.w[j] if reg else 0.0)
+            gv[i] += mult * pv[j] + (model.regv * model.v[:, j] if reg else 0.0)
+    feats = np.fromiter(index.keys(), dtype=np.int64, count=len(index))
+    return feats, np.array(gw, dtype=np.float64), (np.array(gv, dtype=np.float64).reshape(len(gw), k))
+
+
+def pair_decay_w0(model, n_pairs):
+    """fm_sgd.h:56 once per pair, without a learning rate"""
+    if model.k0:
+        for _ in range(n_pairs):
+            model.w0 -= model.reg0 * model.w0
+
+
+def pair_epoch(model, entries, row_ptr, pa, pb, eta, batch, state, rule="adagrad", step_dtype=np.float64):
+    """one epoch over the pairs, in place on `model` and `state` (AdaptState).  rule "adagrad": n += g^2, theta -= eta g / sqrt(n);
+    "sgd": theta -= eta g, the plain batch rule (the state is not touched).  The sums are float64; the step runs in step_dtype --
+    float32 is the device's arithmetic: g32 = float32(g), theta and n in fp32.  Returns the largest |change| of a w / v coordinate
+    over the epoch's batches."""
+    if rule not in ("adagrad", "sgd"):
+        raise ValueError("unknown rule %r (adagrad | sgd)" % (rule,))
+    if int(batch) < 1:
+        raise ValueError("batch must be >= 1")
+    T = np.dtype(step_dtype).type
+    P, batch = len(pa), int(batch)
+    max_step = 0.0
+
+    def step(theta, n, g):
+        if rule == "sgd":
+            return theta - eta * g, n
+        g, n, theta = g.astype(T), n.astype(T), theta.astype(T)
+        n1 = (n + g * g).astype(T)
+        return (theta - T(eta) * g / np.sqrt(n1)).astype(T), n1
+
+    for t0 in range(0, P, batch):
+        t1 = min(t0 + batch, P)
+        feats, gw, gv = pair_batch_sums(model, entries, row_ptr, pa, pb, t0, t1, reg=True)
+        if len(feats):
+            if model.k1:
+                old = model.w[feats]
+                new, state.n_w[feats] = step(old, state.n_w[feats], gw)
+                max_step = max(max_step, float(np.abs(new.astype(np.float64) - old).max()))
+                model.w[feats] = new
+            if model.v.shape[0]:
+                old = model.v[:, feats].T
+                new, n1 = step(old, state.n_v[:, feats].T, gv)
+                state.n_v[:, feats] = n1.T
+                max_step = max(max_step, float(np.abs(new.astype(np.float64) - old).max()))
+                model.v[:, feats] = new.T
+        pair_decay_w0(model, t1 - t0)
+    return max_step

@@ -347,6 +347,10 @@ SYMBOLS = [
     ("fmx_pair_sample", C.c_int, [H, C.c_int, C.POINTER(PairNegOpts), C.c_void_p, C.POINTER(C.c_uint64)]),
     ("fmx_pair_epoch_sampled", C.c_int, [H, C.c_int, C.POINTER(PairNegOpts), C.POINTER(EpochStats), C.POINTER(C.c_uint64)]),
     ("fmx_pair_evaluate_sampled", C.c_int, [H, C.c_int, C.POINTER(PairNegOpts), C.POINTER(PairEval)]),
+    ("fmx_adapt_pair_epoch", C.c_int, [H, C.c_int, C.POINTER(PairOpts), C.POINTER(EpochStats)]),
+    ("fmx_adapt_pair_epoch_sampled", C.c_int, [H, C.c_int, C.POINTER(PairNegOpts), C.POINTER(EpochStats), C.POINTER(C.c_uint64)]),
+    ("fmx_ftrl_pair_epoch", C.c_int, [H, C.c_int, C.POINTER(PairOpts), C.POINTER(EpochStats)]),
+    ("fmx_ftrl_pair_epoch_sampled", C.c_int, [H, C.c_int, C.POINTER(PairNegOpts), C.POINTER(EpochStats), C.POINTER(C.c_uint64)]),
     ("fmx_get_info", C.c_int, [H, C.POINTER(Info)]),
     ("fmx_synchronize", C.c_int, [H]),
 ]
@@ -871,6 +875,38 @@ class Handle:
 
     def ftrl_end(self):
         self._chk(self.lib.fmx_ftrl_end(self.h))
+
+    # pairwise ranking stepped by the open session's rule (include/fmx.h "fmx_adapt_pair_epoch") --
+    def _rule_pair_epoch(self, fn, slot, batch, mode):
+        opts = PairOpts(int(mode), int(batch), 0, 0)
+        st = EpochStats()
+        self._chk(fn(self.h, int(slot), C.byref(opts), C.byref(st)))
+        return st
+
+    def _rule_pair_epoch_sampled(self, fn, query_slot, batch, n_neg, seed, epoch, draws, mode):
+        opts = PairNegOpts(int(mode), int(batch), int(n_neg), neg_flags(draws), int(seed), int(epoch))
+        st = EpochStats()
+        forced = C.c_uint64(0)
+        self._chk(fn(self.h, int(query_slot), C.byref(opts), C.byref(st), C.byref(forced)))
+        return st, int(forced.value)
+
+    def adapt_pair_epoch(self, slot, batch=0, mode=SGD_MINIBATCH):
+        """one epoch over the slot's pairs by the batch rule, every touched coordinate stepped by the open AdaGrad session
+        (fmx_adapt_pair_epoch); returns EpochStats.  mode is there for the library's refusal of the other schedules."""
+        return self._rule_pair_epoch(self.lib.fmx_adapt_pair_epoch, slot, batch, mode)
+
+    def adapt_pair_epoch_sampled(self, query_slot, batch=0, n_neg=1, seed=0, epoch=0, draws=1, mode=SGD_MINIBATCH):
+        """the same over the interactions with the negatives of (seed, epoch) (fmx_adapt_pair_epoch_sampled): (EpochStats, forced)"""
+        return self._rule_pair_epoch_sampled(self.lib.fmx_adapt_pair_epoch_sampled, query_slot, batch, n_neg, seed, epoch, draws, mode)
+
+    def ftrl_pair_epoch(self, slot, batch=0, mode=SGD_MINIBATCH):
+        """one epoch over the slot's pairs by the batch rule, every touched coordinate stepped by the open FTRL session
+        (fmx_ftrl_pair_epoch); returns EpochStats"""
+        return self._rule_pair_epoch(self.lib.fmx_ftrl_pair_epoch, slot, batch, mode)
+
+    def ftrl_pair_epoch_sampled(self, query_slot, batch=0, n_neg=1, seed=0, epoch=0, draws=1, mode=SGD_MINIBATCH):
+        """the same over the interactions with the negatives of (seed, epoch) (fmx_ftrl_pair_epoch_sampled): (EpochStats, forced)"""
+        return self._rule_pair_epoch_sampled(self.lib.fmx_ftrl_pair_epoch_sampled, query_slot, batch, n_neg, seed, epoch, draws, mode)
 
     def param_sparsity(self):
         """fmx_sparsity: how many coordinates of the model are exactly zero"""

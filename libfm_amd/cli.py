@@ -42,6 +42,9 @@ default 1); the printed lines are those of sgd.  Without the option nothing chan
 rule (fmx_ftrl_epoch): A the per-coordinate rate (default -learn_rate, which stays the bias's plain rate), B default 1, W and V the L1
 strengths of the linear weights and the factors (default 0,0); the L2 strengths are -regular's regw and regv, one per coordinate.
 After training one line on stderr gives the zero counts of the model (fmx_param_sparsity).
+-method bpr -optimizer adagrad|ftrl (with the same options): the pairwise batch rule with that per-coordinate step
+(fmx_adapt_pair_epoch* / fmx_ftrl_pair_epoch*, learner.FMLearnPairAdaptive), on -train_pairs and on -interactions; -gpu_mode then
+defaults to minibatch (batch 1 is the per-pair rule) and sequential is refused.
 -serve bf16 (sgd, sgda, bpr, als): after training a frozen bf16 copy of the model is taken on the device (fmx_compact_begin) and the
 -out predictions and the -topk lists come from it.  One "compact" line on stderr carries the copy's bytes next to the fp32 tables',
 max_abs_err and nonfinite of the rounding, and the test metric -- with -metrics each named metric too -- from fp32 and from bf16 side
@@ -88,8 +91,8 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "rank_at": "'K1,K2,...' (at most 4, ascending, 1 .. 65536): tie-averaged NDCG / recall / precision at K inside the queries per"
                     " iteration on stderr and in -rlog; needs -test_queries",
          "device_average": "als, mcmc: 1 = keep the test predictions and their running mean on the device; default=0",
-         "optimizer": "sgd: sgd | adagrad (a per-coordinate step size on the minibatch rule) | ftrl (FTRL-proximal with L1 on the same rule:"
-                      " exact zeros); default=sgd",
+         "optimizer": "sgd, bpr: sgd | adagrad (a per-coordinate step size on the minibatch rule) | ftrl (FTRL-proximal with L1 on the same"
+                      " rule: exact zeros); default=sgd.  bpr with adagrad | ftrl: -gpu_mode defaults to minibatch",
          "init_acc": "-optimizer adagrad: start value of every accumulator (> 0); default=1",
          "ftrl_alpha": "-optimizer ftrl: per-coordinate rate of w and V (> 0); default=-learn_rate",
          "ftrl_beta": "-optimizer ftrl: beta (> 0); default=1",
@@ -267,7 +270,7 @@ def _main(argv):
     if "optimizer" in a or "init_acc" in a or ftrl_flags:
         if optimizer not in L.FMLearnSGD.OPTIMIZERS:
             raise ValueError("-optimizer knows sgd and adagrad, not '%s' (ftrl is the third it knows)" % optimizer)
-        if method != "sgd":
+        if method not in ("sgd", "bpr"):                     # (bpr: the pairwise batch rule with the same two rules, FMLearnPairAdaptive)
             raise ValueError("-optimizer / -init_acc belong to -method sgd, not -method %s" % method)
         if optimizer == "ftrl" and a.get("gpu_mode", "minibatch") != "minibatch":
             raise ValueError("-optimizer ftrl runs on the minibatch rule: -gpu_mode %s is not supported" % a["gpu_mode"])
@@ -441,13 +444,19 @@ def _main(argv):
     num_iter = int(a.get("iter", "100"))
 
     if method == "bpr":
-        l = L.FMLearnPairSGD()
+        l = L.FMLearnPairSGD() if optimizer == "sgd" else L.FMLearnPairAdaptive()
         lrs = [float(x) for x in split_list(a.get("learn_rate", ""))]
         if len(lrs) != 1:
             raise ValueError("-learn_rate needs 1 value for bpr")
         l.learn_rate = lrs[0]
-        l.mode = a.get("gpu_mode", "sequential")
+        l.mode = a.get("gpu_mode", "sequential" if optimizer == "sgd" else "minibatch")
         l.batch = int(a.get("batch", "0"))
+        if optimizer != "sgd":
+            l.optimizer = optimizer
+            l.init_acc = float(a.get("init_acc", "0"))
+            if optimizer == "ftrl":
+                l.ftrl_alpha, l.ftrl_beta = float(a.get("ftrl_alpha", "0")), float(a.get("ftrl_beta", "1"))
+                l.l1_w, l.l1_v = ftrl_l1
     elif method in ("sgd", "sgda"):
         l = L.FMLearnSGD() if method == "sgd" else L.FMLearnSGDA()
         if method == "sgda":

@@ -349,6 +349,13 @@ int scan_error_check(fmx_handle h);                                      // fmx_
 uint32_t multi_group_size(const Slot& s, int KP);                        // fmx_sgd.hip: examples per wavefront of the short-row kernels (0: rows are long)
 bool streams_concurrent(fmx_handle h);                                   // fmx_sgd.hip: probed once per handle
 void sgda_free(fmx_handle h);                                            // fmx_sgd.hip
+// which owner a pair epoch ends in (fmx_pair.hip, fmx_pairneg.hip; launch_pair_owner, fmx_pair_rule_kernels.h): the plain batch rule,
+// or the rule of the open fmx_adapt / fmx_ftrl session on the session's own tables
+enum PairRule { PAIR_PLAIN = 0, PAIR_ADAGRAD = 1, PAIR_FTRL = 2 };
+// fmx_pair.hip, what the rule epochs refuse beyond their plain counterparts: the schedules without a rule form (before the plain
+// checks: their own message), then the session (after them)
+int pair_rule_check_mode(fmx_handle h, PairRule r, int mode, const char* what);
+int pair_rule_check_session(fmx_handle h, PairRule r, const char* what);
 void adapt_free(fmx_handle h);                                           // fmx_sgd.hip
 void ftrl_free(fmx_handle h);                                            // fmx_sgd.hip
 void als_free(fmx_handle h);                                             // fmx_als.hip

@@ -1,8 +1,10 @@
 // fmx_pair.hip -- C-ABI (include/fmx.h): pairwise ranking (BPR) around fm_pairSGD -- the pairs of a slot, one epoch in order
 // (FMX_SGD_SEQUENTIAL) or by the batch rule (FMX_SGD_MINIBATCH: the (batch, feature) bucketing of the pair-expanded entries,
-// sums + multipliers, owner apply), and the pair metrics.  Kernels: fmx_pair_kernels.h.
+// sums + multipliers, owner apply), the same epoch stepped by an open fmx_adapt / fmx_ftrl session's rule (fmx_adapt_pair_epoch,
+// fmx_ftrl_pair_epoch), and the pair metrics.  Kernels: fmx_pair_kernels.h, fmx_pair_rule_kernels.h.
 #include "fmx_internal.h"
 #include "fmx_pair_kernels.h"
+#include "fmx_pair_rule_kernels.h"
 
 static void free_pair_segments(Slot& s) {
   if (s.pair_t_ent) fmx_dev_free(s.pair_t_ent);
@@ -34,6 +36,19 @@ static int pair_check(fmx_handle h, int slot, const char* what) {
   if (rc) return rc;
   if (h->sgda.reg) return fail(h, FMX_E_STATE, "%s: an SGDA session is open (call fmx_sgda_end first)", what);
   if (!s.pairs_set) return fail(h, FMX_E_STATE, "%s: slot %d holds no pairs (call fmx_upload_pairs first)", what, slot);
+  return FMX_OK;
+}
+
+extern "C++" int pair_rule_check_mode(fmx_handle h, PairRule r, int mode, const char* what) {
+  if (r != PAIR_PLAIN && (mode == FMX_SGD_SEQUENTIAL || mode == FMX_SGD_HOGWILD))
+    return fail(h, FMX_E_UNSUPPORTED, "%s: a per-coordinate rule runs on FMX_SGD_MINIBATCH only (batch = 1 gives the per-pair rule); "
+                "FMX_SGD_SEQUENTIAL and FMX_SGD_HOGWILD have no such form", what);
+  return FMX_OK;
+}
+extern "C++" int pair_rule_check_session(fmx_handle h, PairRule r, const char* what) {
+  if (r == PAIR_ADAGRAD && !h->adapt.nv) return fail(h, FMX_E_STATE, "%s before fmx_adapt_begin", what);
+  if (r == PAIR_FTRL && !h->ftrl.nv) return fail(h, FMX_E_STATE, "%s before fmx_ftrl_begin", what);
+  if (r == PAIR_FTRL && h->adapt.nv) return fail(h, FMX_E_STATE, "%s: an fmx_adapt session is open", what);
   return FMX_OK;
 }
 
@@ -168,13 +183,19 @@ int fmx_upload_pairs(fmx_handle h, int slot, const uint32_t* row_a, const uint32
   return FMX_OK;
 }
 
-int fmx_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts* opts, fmx_epoch_stats* stats) {
+// one epoch over the pairs of a slot for `what` (fmx_pair_epoch and the rule epochs): they differ in their refusals and in the
+// owner launch of a batch (launch_pair_owner), nothing else
+static int pair_epoch_run(fmx_handle h, int slot, const fmx_pair_opts* opts, fmx_epoch_stats* stats, const char* what, PairRule rule) {
   if (stats) memset(stats, 0, sizeof(*stats));
   if (!h) return FMX_E_ARG;
-  if (!opts) return fail(h, FMX_E_ARG, "fmx_pair_epoch: opts is NULL");
-  if (opts->mode == FMX_SGD_HOGWILD) return fail(h, FMX_E_UNSUPPORTED, "fmx_pair_epoch: FMX_SGD_HOGWILD is not supported for pairs");
-  if (opts->mode != FMX_SGD_SEQUENTIAL && opts->mode != FMX_SGD_MINIBATCH) return fail(h, FMX_E_ARG, "fmx_pair_epoch: unknown mode %d", opts->mode);
-  int rc = pair_check(h, slot, "fmx_pair_epoch");
+  if (!opts) return fail(h, FMX_E_ARG, "%s: opts is NULL", what);
+  int rc = pair_rule_check_mode(h, rule, opts->mode, what);
+  if (rc) return rc;
+  if (opts->mode == FMX_SGD_HOGWILD) return fail(h, FMX_E_UNSUPPORTED, "%s: FMX_SGD_HOGWILD is not supported for pairs", what);
+  if (opts->mode != FMX_SGD_SEQUENTIAL && opts->mode != FMX_SGD_MINIBATCH) return fail(h, FMX_E_ARG, "%s: unknown mode %d", what, opts->mode);
+  rc = pair_check(h, slot, what);
+  if (rc) return rc;
+  rc = pair_rule_check_session(h, rule, what);
   if (rc) return rc;
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   HIPCHK(h, hipSetDevice(h->device));
@@ -203,7 +224,7 @@ int fmx_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts* opts, fmx_epoch_
     batches = P;
   } else {
     B = opts->batch ? opts->batch : FMX_PAIR_DEFAULT_BATCH;
-    if (B >= (1u << 31)) return fail(h, FMX_E_ARG, "fmx_pair_epoch: batch %u (2^31 - 1 at most)", B);
+    if (B >= (1u << 31)) return fail(h, FMX_E_ARG, "%s: batch %u (2^31 - 1 at most)", what, B);
     rc = ensure_pair_segments(h, s, B);
     if (rc) return rc;
     const uint32_t nbc = (uint32_t)std::min<uint64_t>(B, P);
@@ -219,10 +240,8 @@ int fmx_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts* opts, fmx_epoch_
       const uint32_t nb = (uint32_t)std::min<uint64_t>(B, P - t0);
       const uint64_t b = t0 / B;
       const uint32_t s0 = s.pair_batch_seg[b], s1 = s.pair_batch_seg[b + 1];
-      KP_SWITCH(h->KP, {
-        FMX_LAUNCH_WAVES((k_pair_sums<KP>), nb, h->stream, s.ent, s.row_ptr, s.pair_a, s.pair_b, t0, nb, h->tb, k, h->cfg.k1, S, mult);
-        if (s1 > s0) FMX_LAUNCH_WAVES((k_pair_apply<KP>), s1 - s0, h->stream, s.pair_t_ent, s.pair_seg_head, s.pair_seg_feat, s0, s1, S, mult, h->tb, hy, k);
-      });
+      KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_pair_sums<KP>), nb, h->stream, s.ent, s.row_ptr, s.pair_a, s.pair_b, t0, nb, h->tb, k, h->cfg.k1, S, mult));
+      if (s1 > s0) launch_pair_owner<2>(h, rule, s.pair_t_ent, s.pair_seg_head, s.pair_seg_feat, s0, s1, S, mult, hy, h->stream);
       er = hipGetLastError();
       batches++;
     }
@@ -248,6 +267,16 @@ int fmx_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts* opts, fmx_epoch_
     stats->setup_seconds = h->setup_acc;
   }
   return FMX_OK;
+}
+
+int fmx_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts* opts, fmx_epoch_stats* stats) {
+  return pair_epoch_run(h, slot, opts, stats, "fmx_pair_epoch", PAIR_PLAIN);
+}
+int fmx_adapt_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts* opts, fmx_epoch_stats* stats) {
+  return pair_epoch_run(h, slot, opts, stats, "fmx_adapt_pair_epoch", PAIR_ADAGRAD);
+}
+int fmx_ftrl_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts* opts, fmx_epoch_stats* stats) {
+  return pair_epoch_run(h, slot, opts, stats, "fmx_ftrl_pair_epoch", PAIR_FTRL);
 }
 
 int fmx_pair_evaluate(fmx_handle h, int slot, fmx_pair_eval* out) {

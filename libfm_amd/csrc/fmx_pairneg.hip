@@ -1,9 +1,11 @@
 // fmx_pairneg.hip -- C-ABI (include/fmx.h): BPR on (query row, candidate row) interactions with the negatives drawn on the device
 // (DESIGN.md sections 12 and 13).  Per epoch: k_neg_sample (FMX_NEG_HARDEST: the row tables of fmx_topk, then k_neg_pick), then FMX_SGD_SEQUENTIAL (k_pair_seq over the joined rows) or FMX_SGD_MINIBATCH
 // (the pairs' entries -- the query's once -- bucketed by (batch, feature), sums + multipliers, owner apply).  Kernels:
-// fmx_pairneg_kernels.h.
+// fmx_pairneg_kernels.h.  fmx_adapt_pair_epoch_sampled / fmx_ftrl_pair_epoch_sampled: the same epoch with the open session's rule in
+// the owner (fmx_pair_rule_kernels.h).
 #include "fmx_internal.h"
 #include "fmx_pairneg_kernels.h"
+#include "fmx_pair_rule_kernels.h"
 
 static_assert(FMX_NEG_ATTEMPTS == NEG_ATTEMPTS, "include/fmx.h and fmx_pairneg_kernels.h disagree");
 
@@ -351,15 +353,22 @@ int fmx_pair_sample(fmx_handle h, int query_slot, const fmx_pairneg_opts* o, uin
   return FMX_OK;
 }
 
-int fmx_pair_epoch_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts* o, fmx_epoch_stats* stats, uint64_t* forced_out) {
+// one epoch over the interactions of a query slot for `what` (fmx_pair_epoch_sampled and the rule epochs): they differ in their
+// refusals and in the owner launch of a batch (launch_pair_owner), nothing else
+static int pairneg_epoch_run(fmx_handle h, int query_slot, const fmx_pairneg_opts* o, fmx_epoch_stats* stats, uint64_t* forced_out,
+                             const char* what, PairRule rule) {
   if (stats) memset(stats, 0, sizeof(*stats));
   if (forced_out) *forced_out = 0;
-  int rc = pairneg_check(h, query_slot, o, "fmx_pair_epoch_sampled");
+  int rc = (h && o) ? pair_rule_check_mode(h, rule, o->mode, what) : FMX_OK;
+  if (rc) return rc;
+  rc = pairneg_check(h, query_slot, o, what);
+  if (rc) return rc;
+  rc = pair_rule_check_session(h, rule, what);
   if (rc) return rc;
   uint32_t B = 1;
   if (o->mode == FMX_SGD_MINIBATCH) {
     B = o->batch ? o->batch : FMX_PAIR_DEFAULT_BATCH;
-    if (B >= (1u << 30)) return fail(h, FMX_E_ARG, "fmx_pair_epoch_sampled: batch %u (2^30 - 1 at most)", B);
+    if (B >= (1u << 30)) return fail(h, FMX_E_ARG, "%s: batch %u (2^30 - 1 at most)", what, B);
   }
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   HIPCHK(h, hipSetDevice(h->device));
@@ -421,15 +430,8 @@ int fmx_pair_epoch_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts*
       const uint32_t nb = (uint32_t)std::min<uint64_t>(B, P - p0);
       const uint64_t b = p0 / B;
       const uint32_t s0 = bk.batch_seg[b], s1 = bk.batch_seg[b + 1];
-      switch (h->KP) {
-#define PN_CASE(KPV) case KPV: \
-        FMX_LAUNCH_WAVES((k_pn_sums<KPV>), nb, st, js, p0, nb, h->tb, k, h->cfg.k1, S, mult); \
-        if (s1 > s0) FMX_LAUNCH_WAVES((k_pair_apply<KPV, 3>), s1 - s0, st, bk.t_ent, bk.seg_head, bk.seg_feat, s0, s1, (const float*)S, (const double*)mult, h->tb, hy, k); \
-        break;
-        PN_CASE(1) PN_CASE(2) PN_CASE(4) PN_CASE(8) PN_CASE(16) PN_CASE(32) PN_CASE(64) PN_CASE(128) PN_CASE(256) PN_CASE(512) PN_CASE(1024)
-#undef PN_CASE
-        default: fmx_dev_free(scr); return fail(h, FMX_E_UNSUPPORTED, "num_factor > 1024 is not supported");
-      }
+      KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_pn_sums<KP>), nb, st, js, p0, nb, h->tb, k, h->cfg.k1, S, mult));
+      if (s1 > s0) launch_pair_owner<3>(h, rule, bk.t_ent, bk.seg_head, bk.seg_feat, s0, s1, S, mult, hy, st);
       er = hipGetLastError();
       batches++;
     }
@@ -456,6 +458,16 @@ int fmx_pair_epoch_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts*
     stats->setup_seconds = h->setup_acc;
   }
   return FMX_OK;
+}
+
+int fmx_pair_epoch_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts* o, fmx_epoch_stats* stats, uint64_t* forced_out) {
+  return pairneg_epoch_run(h, query_slot, o, stats, forced_out, "fmx_pair_epoch_sampled", PAIR_PLAIN);
+}
+int fmx_adapt_pair_epoch_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts* o, fmx_epoch_stats* stats, uint64_t* forced_out) {
+  return pairneg_epoch_run(h, query_slot, o, stats, forced_out, "fmx_adapt_pair_epoch_sampled", PAIR_ADAGRAD);
+}
+int fmx_ftrl_pair_epoch_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts* o, fmx_epoch_stats* stats, uint64_t* forced_out) {
+  return pairneg_epoch_run(h, query_slot, o, stats, forced_out, "fmx_ftrl_pair_epoch_sampled", PAIR_FTRL);
 }
 
 int fmx_pair_evaluate_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts* o, fmx_pair_eval* out) {

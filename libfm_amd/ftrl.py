@@ -121,3 +121,37 @@ def epoch(model, data, task, lr, min_target, max_target, batch, w0_chunk, state,
                 max_step = max(max_step, float(np.abs(new.astype(np.float64) - vj.astype(np.float64)).max()))
             model.v[:, feats] = new.T
     return max_step
+
+
+def pair_epoch(model, entries, row_ptr, pa, pb, batch, state, step_dtype=np.float64):
+    """pairwise ranking (BPR) on the batch rule with the proximal step per coordinate (the CPU reference of fmx_ftrl_pair_epoch): one
+    epoch over the pairs (row pa[t] preferred to row pb[t]) in batches of `batch` consecutive pairs, in place on `model` and `state`
+    (FtrlState).  Per feature of a batch the gradient sum of adaptive.pair_batch_sums WITHOUT the regularisation terms (float64, pair
+    order; regw / regv are not read: L2 lives in D), then _step in step_dtype -- float32 is the device's arithmetic: g32 = float32(g),
+    theta, z and n in fp32.  w0 -= reg0 w0 once per pair.  Returns the largest |change| of a w / v coordinate over the epoch's batches."""
+    from .adaptive import pair_batch_sums, pair_decay_w0
+    if int(batch) < 1:
+        raise ValueError("batch must be >= 1")
+    T = np.dtype(step_dtype).type
+    P, batch, st = len(pa), int(batch), state
+    max_step = 0.0
+    for t0 in range(0, P, batch):
+        t1 = min(t0 + batch, P)
+        feats, gw, gv = pair_batch_sums(model, entries, row_ptr, pa, pb, t0, t1, reg=False)
+        if len(feats):
+            if model.k1:
+                old = model.w[feats]
+                new, z1, n1 = _step(old.astype(T), st.z_w[feats].astype(T), st.n_w[feats].astype(T), gw.astype(T), st.alpha, st.beta,
+                                    st.l1_w, st.l2_w, T)
+                st.z_w[feats], st.n_w[feats] = z1, n1
+                max_step = max(max_step, float(np.abs(new.astype(np.float64) - old).max()))
+                model.w[feats] = new
+            if model.v.shape[0]:
+                old = model.v[:, feats].T
+                new, z1, n1 = _step(old.astype(T), st.z_v[:, feats].T.astype(T), st.n_v[:, feats].T.astype(T), gv.astype(T), st.alpha,
+                                    st.beta, st.l1_v, st.l2_v, T)
+                st.z_v[:, feats], st.n_v[:, feats] = z1.T, n1.T
+                max_step = max(max_step, float(np.abs(new.astype(np.float64) - old).max()))
+                model.v[:, feats] = new.T
+        pair_decay_w0(model, t1 - t0)
+    return max_step

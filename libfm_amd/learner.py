@@ -798,6 +798,13 @@ class FMLearnPairSGD(FMLearnSGD):
         slot = self._pair_slot(data, pairs) if pairs is not None else self._slot(data)
         return self._h.pair_evaluate(slot).accuracy
 
+    # the epoch calls of learn() and learn_implicit(): what a subclass with another update rule overrides
+    def _pair_epoch(self, slot):
+        return self._h.pair_epoch(slot, self.MODES[self.mode], self.batch)
+
+    def _pair_epoch_sampled(self, query_slot, n_neg, seed, epoch, neg_draws):
+        return self._h.pair_epoch_sampled(query_slot, self.MODES[self.mode], self.batch, n_neg, seed, epoch, draws=neg_draws)
+
     def learn(self, train, train_pairs, test, test_pairs):
         self._check_optimizer()
         if self.mode not in self.MODES:
@@ -807,7 +814,7 @@ class FMLearnPairSGD(FMLearnSGD):
         st = self._pair_slot(train, train_pairs)
         se = self._pair_slot(test, test_pairs)
         for i in range(self.num_iter):
-            stats = self._h.pair_epoch(st, self.MODES[self.mode], self.batch)
+            stats = self._pair_epoch(st)
             tr, te = self._h.pair_evaluate(st), self._h.pair_evaluate(se)
             print("#Iter=%3d\tTrain=%g\tTest=%g" % (i, tr.accuracy, te.accuracy), file=self.out)
             print("#Iter=%3d\tloss: Train=%g\tTest=%g" % (i, tr.loss, te.loss), file=sys.stderr)
@@ -891,7 +898,7 @@ class FMLearnPairSGD(FMLearnSGD):
             h.upload_interactions(se, sc, te[0], te[1], ex_te)
         self._implicit = (sq, se, n_neg, seed)
         for i in range(self.num_iter):
-            stats, forced = h.pair_epoch_sampled(sq, self.MODES[self.mode], self.batch, n_neg, seed, i, draws=neg_draws)
+            stats, forced = self._pair_epoch_sampled(sq, n_neg, seed, i, neg_draws)
             e_tr, e_te = self.evaluate_implicit()
             acc_te, loss_te = (e_te.accuracy, e_te.loss) if e_te is not None else (float("nan"), float("nan"))
             print("#Iter=%3d\tTrain=%g\tTest=%g" % (i, e_tr.accuracy, acc_te), file=self.out)
@@ -900,6 +907,47 @@ class FMLearnPairSGD(FMLearnSGD):
                              "time_learn": stats.device_seconds, "time_setup": stats.setup_seconds, "forced": forced,
                              "neg_draws": neg_draws})
         self.sync_model()
+
+
+class FMLearnPairAdaptive(FMLearnPairSGD):
+    """FMLearnPairSGD with a per-coordinate step on the pairwise batch rule: optimizer 'adagrad' (fmx_adapt_pair_epoch*: the step of a
+    coordinate stays below eta per batch whatever a popular item's segment sums) or 'ftrl' (fmx_ftrl_pair_epoch*: FTRL-proximal with
+    L1, exact zeros), with FMLearnSGD's fields for them (init_acc, adapt_learn_rate, ftrl_alpha, ftrl_beta, l1_w / l1_v, l2_w / l2_v);
+    'sgd' is FMLearnPairSGD's plain rule.  init() opens the session; both rules run on mode 'minibatch' only (batch = 1 is the
+    per-pair rule).  Everything else -- learn(), learn_implicit(), sparsity(), recommend(), compact() -- is inherited."""
+
+    OPTIMIZERS = FMLearnSGD.OPTIMIZERS
+
+    def __init__(self):
+        super().__init__()
+        self.mode = "minibatch"
+
+    def _pair_epoch(self, slot):
+        if self._adapt_open:
+            return self._h.adapt_pair_epoch(slot, self.batch)
+        if self._ftrl_open:
+            return self._h.ftrl_pair_epoch(slot, self.batch)
+        return super()._pair_epoch(slot)
+
+    def _pair_epoch_sampled(self, query_slot, n_neg, seed, epoch, neg_draws):
+        if self._adapt_open:
+            return self._h.adapt_pair_epoch_sampled(query_slot, self.batch, n_neg, seed, epoch, neg_draws)
+        if self._ftrl_open:
+            return self._h.ftrl_pair_epoch_sampled(query_slot, self.batch, n_neg, seed, epoch, neg_draws)
+        return super()._pair_epoch_sampled(query_slot, n_neg, seed, epoch, neg_draws)
+
+    def _check_session(self):
+        self._check_optimizer()
+        if (self.optimizer == "adagrad") != self._adapt_open or (self.optimizer == "ftrl") != self._ftrl_open:
+            raise ValueError("optimizer was changed after init()")
+
+    def learn(self, train, train_pairs, test, test_pairs):
+        self._check_session()
+        super().learn(train, train_pairs, test, test_pairs)
+
+    def learn_implicit(self, *args, **kw):
+        self._check_session()
+        super().learn_implicit(*args, **kw)
 
 
 class FMLearnSGDA(FMLearnSGD):
