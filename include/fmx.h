@@ -236,6 +236,8 @@ typedef struct fmx_epoch_stats {
 #define FMX_STAT_RUN_ONE       8192u /* at least one conflict-free run as ONE launch (k_run_fused) */
 #define FMX_STAT_RUN_TWO      16384u /* at least one run as two launches (k_rowsums + k_run_apply) */
 #define FMX_STAT_RUN_THREE    32768u /* at least one run as three launches (k_rowsums + the recurrence on its own + k_apply) */
+#define FMX_STAT_WEIGHTED     65536u /* fmx_adapt_epoch / fmx_ftrl_epoch on a slot with row weights (fmx_set_row_weights): every batch's recurrence ran as
+                                        k_scan_weighted, a one-wavefront chain (FMX_STAT_SCAN_SERIAL is set with it, FMX_STAT_SCAN_PIT never) */
 
 /* what fmx_sgd_epoch would use for `batch` on this slot (no training): the rows' collision mass (computed once per slot on the
  * device: one histogram pass over the entries), the resolved batch and its gain.  opts may be NULL (= batch 0). */
@@ -457,7 +459,8 @@ int fmx_evaluate(fmx_handle h, int slot, fmx_eval *out);
  * shard's targets; a one-handle group forwards.
  * Refusals: FMX_E_ARG: NULL out, unknown link, flags != 0.  FMX_E_STATE: a slot never uploaded, a slot without targets (as
  * fmx_evaluate).  FMX_E_UNSUPPORTED: a feature shard or communicator rank passed to fmx_evaluate_ex itself (as fmx_evaluate), more
- * than 2^31 - 1 rows.  Rows are not weighted.
+ * than 2^31 - 1 rows.  Row weights (fmx_set_row_weights) are ignored: every row counts once; fmx_evaluate_weighted is the
+ * weighted log loss.
  * Added without an ABI version change: a caller detects the feature by the symbol fmx_evaluate_ex. */
 #define FMX_LINK_LOGISTIC 0u   /* q = 1 / (1 + exp(-p)):  fm_learn_sgd::predict, classification (fm_learn_sgd.h:80-87) */
 #define FMX_LINK_PROBIT   1u   /* q = Phi(p):              the als / mcmc learners' cdf_gaussian */
@@ -514,7 +517,7 @@ int fmx_evaluate_ex(fmx_handle h, int slot, const fmx_eval_opts *opts, fmx_eval_
  * targets; FMX_E_UNSUPPORTED: a feature shard passed to the per-handle call, more than 2^31 - 1 rows), and FMX_E_STATE when the slot
  * has no query ids.  fmx_set_row_queries: FMX_E_ARG for n_queries == 0 or > 2^31 - 1 and for any qid >= n_queries (the message
  * names the first offending row; nothing changes on failure), FMX_E_STATE for a slot never uploaded; an empty slot with a
- * non-NULL qid is accepted.  Rows are not weighted.
+ * non-NULL qid is accepted.  Row weights (fmx_set_row_weights) are ignored: every row counts once.
  * Added without an ABI version change: a caller detects the feature by the symbol fmx_evaluate_by_query. */
 
 /* per-row query ids of a slot: qid[n_rows] (host), every qid < n_queries, 1 <= n_queries <= 2^31 - 1.  Kept on the device
@@ -577,7 +580,7 @@ int fmx_evaluate_by_query(fmx_handle h, int slot, const fmx_eval_opts *opts, fmx
  * Refusals: everything fmx_evaluate_by_query refuses, with the same codes; FMX_E_ARG for NULL opts or out, n_cutoffs outside
  * 1 .. FMX_RANK_MAX_CUTOFFS, a k of 0 or above FMX_RANK_MAX_K, cutoffs that are not strictly ascending; FMX_E_UNSUPPORTED for a
  * feature shard passed to the per-handle call.  fmx_rank_discounts: FMX_E_ARG for NULL out or k_max above FMX_RANK_MAX_K.
- * Rows are not weighted; relevance is not graded.
+ * Row weights (fmx_set_row_weights) are ignored; relevance is not graded.
  * Added without an ABI version change: a caller detects the feature by the symbol fmx_evaluate_rank. */
 #define FMX_RANK_MAX_CUTOFFS 4
 #define FMX_RANK_MAX_K 65536u
@@ -654,7 +657,8 @@ int fmx_evaluate_rank(fmx_handle h, int slot, const fmx_rank_opts *opts, fmx_eva
  * shard's device, where fmx_group_predict's finished y-hat chunks are accumulated.  A one-handle group forwards.
  * Refusals: FMX_E_ARG: which > 2, flags != 0, eval_rows > n_rows, NULL out of _evaluate_ex.  FMX_E_STATE: a slot never uploaded or
  * without targets; _accumulate / _evaluate_ex / _get / _end without _begin.  FMX_E_UNSUPPORTED: a feature shard or communicator rank
- * passed to the per-handle calls, more than 2^31 - 1 rows.  An empty slot: FMX_OK with zero rows.  Rows are not weighted.
+ * passed to the per-handle calls, more than 2^31 - 1 rows.  An empty slot: FMX_OK with zero rows.  Row weights
+ * (fmx_set_row_weights) are ignored.
  * Added without an ABI version change: a caller detects the feature by the symbol fmx_post_begin. */
 #define FMX_POST_THIS 0u   /* the last accumulated draw             (pred_this) */
 #define FMX_POST_ALL  1u   /* mean over all accumulated draws       (pred_sum_all * 1 / draws) */
@@ -1132,6 +1136,73 @@ int fmx_ftrl_begin(fmx_handle h, const fmx_ftrl_opts *opts);
 int fmx_ftrl_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
 int fmx_ftrl_get_state_rows(fmx_handle h, const uint32_t *ids, uint32_t count, double *zw, double *zv, double *nw, double *nv);
 int fmx_ftrl_end(fmx_handle h);
+
+/* ---- per-row weights: weighted AdaGrad / FTRL epochs and a weighted log loss ---------------------------
+ * Click data is trained on a subsample: keep a fraction r of the negatives and give each kept one the weight 1 / r (the FTRL paper's
+ * recipe, whose L1 half is "fmx_ftrl_*").  Without the weight the model's bias and its log loss describe the subsampled stream, not
+ * the real one.  c_e is the weight of row e: finite and >= 0.  A caller detects the feature by the symbol fmx_set_row_weights.
+ *
+ * fmx_adapt_epoch and fmx_ftrl_epoch on a slot WITH weights: steps 1 and 3 of "fmx_adapt_*" / "fmx_ftrl_*" stay word for word.  Step 2
+ * becomes, per micro-chunk with its start bias w0s:
+ *        m_e  = c_e * multiplier(w0s + rest_e, y_e)              (fp32 product of the fp32 multiplier and the fp32 weight)
+ *        w0  -= lr * ( sum_chunk m_e + chunk_rows * reg0 * w0s )  (fp64)
+ *        mult_e = m_e
+ * The weight scales the LOSS only.  The regularisation terms keep counting occurrences and rows, not weight: nocc * regw * w_j,
+ * nocc * regv * v_jf, chunk_rows * reg0 * w0s; FTRL has no per-occurrence term, so for it this is the whole change.  A row of weight
+ * 0 adds nothing to any gradient but still counts in nocc and chunk_rows.  All-ones weights give the unweighted rule; integer
+ * weights with reg0 = regw = regv = 0 and the whole slot as one batch and one micro-chunk give the model of the set in which every
+ * row is repeated c_e times.
+ * The bias is plain SGD and its stability is the caller's responsibility, as the micro-chunk already is: its step per micro-chunk
+ * is lr * sum_chunk c_e * curvature, so weights of mean mu act like a micro-chunk mu times longer.  Nothing is cut for it.
+ * A weighted epoch runs the recurrence as a one-wavefront chain (k_scan_weighted) whatever the batch and the micro-chunk -- any
+ * micro-chunk >= 1 and any batch are valid -- and reports FMX_STAT_WEIGHTED | FMX_STAT_SCAN_SERIAL in fmx_epoch_stats::status, never
+ * FMX_STAT_SCAN_PIT.  Deterministic: two runs of the same calls are bit-identical.  On a slot without weights both epochs run
+ * exactly the code they ran before: same launches, same bits.
+ *
+ *   fmx_set_row_weights : weight[n_rows] (host), kept on the device at 4 bytes per row.  A new call replaces the weights; NULL drops
+ *                     them; fmx_upload_rows and its siblings, fmx_synth_rows* and fmx_free_rows drop them (free_slot), fmx_destroy
+ *                     frees them.  FMX_E_ARG for a NaN, infinite or negative weight (the message names the first offending row;
+ *                     nothing changes on failure), FMX_E_STATE for a slot never uploaded, FMX_E_UNSUPPORTED on a feature shard or
+ *                     communicator rank (there is no group form, so no sharded path can meet a weighted slot).  An empty slot with a
+ *                     non-NULL pointer is accepted.
+ *   fmx_get_row_weights : the weights as stored, out[n_rows].  FMX_E_STATE when the slot has none.
+ * Trainers without a weighted form REFUSE a weighted slot -- training on its targets without its weights would silently give the
+ * wrong model -- with FMX_E_UNSUPPORTED, before any launch, in a message that names fmx_set_row_weights: fmx_sgd_epoch,
+ * fmx_sgd_partial, fmx_sgd_finish, fmx_sgda_epoch and fmx_sgda_epoch_minibatch (for the train slot), fmx_als_begin.  Dropping the
+ * weights makes them work again; the handle stays usable.  Everything that only scores IGNORES the weights: fmx_predict,
+ * fmx_evaluate, fmx_evaluate_ex, fmx_evaluate_by_query, fmx_evaluate_rank, fmx_topk, fmx_compact_*, fmx_post_*, and the pair calls
+ * (fmx_pair_*, fmx_adapt_pair_* / fmx_ftrl_pair_*: their examples are pairs, not rows).
+ *
+ * fmx_evaluate_weighted: one scoring pass like fmx_evaluate_ex (its score path, its option and slot checks), then with p_i, s_i and
+ * l(z) exactly as defined there ("exact AUC and log loss of a slot"):
+ *        weight_sum     = sum_i c_i          pos_weight / neg_weight = sum of c_i over target_i >= 0 / < 0
+ *        correct_weight = sum_i c_i [ (p_i >= 0) == (target_i >= 0) ]                (a NaN score is never correct)
+ *        loss_sum       = sum_i c_i l(s_i p_i),  logloss = loss_sum / weight_sum      (classification)
+ *        sq_sum = sum_i c_i err_i^2,  abs_sum = sum_i c_i |err_i|,  rmse = sqrt(sq_sum / weight_sum),  mae = abs_sum / weight_sum
+ *                                                                                     (regression, clamped as fm_learn.h:138-152)
+ *        accuracy       = correct_weight / weight_sum                                 (classification)
+ *   every term in fp64 from the fp32 score and the fp32 weight.  A row of weight 0 adds exactly 0 to every sum, also where l is +inf
+ *   or its score NaN.  nan_rows (classification: rows whose score is NaN, whatever their weight) > 0 or weight_sum == 0 makes the four
+ *   ratios NaN; the sums and counts stay right (loss_sum itself is NaN when a NaN score has a positive weight).  Classification
+ *   handles leave sq_sum = abs_sum = 0 and rmse = mae = NaN; regression handles leave the classification sums 0, nan_rows 0 (a NaN
+ *   score clamps to max_target, as in fmx_evaluate) and logloss = accuracy = NaN.  An empty slot: FMX_OK with zeros and NaN ratios.
+ *   FMX_E_STATE when the slot has no weights; the other refusals are fmx_evaluate_ex's.
+ *   Every fp64 sum runs in fmx_evaluate_ex's fixed order (block partials on the same grid, summed in block order by a final kernel;
+ *   no float atomics): two calls with unchanged parameters are bit-identical except for the time.
+ *   There is no weighted AUC, and it is rarely missed: weights that are constant per class -- the subsampling case -- multiply
+ *   numerator and denominator of the AUC alike and cancel, so fmx_evaluate_ex's exact value is already the weighted one.
+ * Added without an ABI version change. */
+typedef struct fmx_eval_weighted {
+  uint64_t rows, nan_rows;
+  double   weight_sum, pos_weight, neg_weight, correct_weight;
+  double   loss_sum, sq_sum, abs_sum;
+  double   logloss, rmse, mae, accuracy;
+  double   device_seconds;      /* whole call */
+} fmx_eval_weighted;
+int fmx_set_row_weights(fmx_handle h, int slot, const float *weight);
+int fmx_get_row_weights(fmx_handle h, int slot, float *out);
+/* opts as fmx_evaluate_ex (NULL = logistic) */
+int fmx_evaluate_weighted(fmx_handle h, int slot, const fmx_eval_opts *opts, fmx_eval_weighted *out);
 
 /* ---- pairwise ranking (BPR) stepped by an open session's per-coordinate rule ------------------------------------------------
  * The pairwise batch rule multiplies a (batch, feature) segment's summed gradient by ONE learn_rate; a popular item's segment sums

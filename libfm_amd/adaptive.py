@@ -26,6 +26,19 @@ class AdaptState:
         self.n_v = np.full((int(k), int(n)), self.init_acc, dtype=np.float64)
 
 
+def row_weights(weights, n_rows, dtype):
+    """the per-row weights of a weighted epoch in the working dtype (None: unweighted): float32 first, as the device stores them"""
+    if weights is None:
+        return None
+    c = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if c.shape[0] != int(n_rows):
+        raise ValueError("weights: %d values for %d rows" % (c.shape[0], int(n_rows)))
+    c = c.astype(np.float32)
+    if not (np.isfinite(c).all() and (c >= 0).all()):
+        raise ValueError("weights must be finite and >= 0")
+    return c.astype(dtype)
+
+
 def _multiplier(task, p, y, min_target, max_target):
     """fm_learn_sgd_element.h:58-65"""
     if task == TASK_REGRESSION:
@@ -33,14 +46,17 @@ def _multiplier(task, p, y, min_target, max_target):
     return -y * (1.0 - 1.0 / (1.0 + np.exp(-y * p)))
 
 
-def epoch(model, data, task, lr, min_target, max_target, batch, w0_chunk, state, eta=None, rule="adagrad", dtype=np.float64):
+def epoch(model, data, task, lr, min_target, max_target, batch, w0_chunk, state, eta=None, rule="adagrad", dtype=np.float64,
+          weights=None):
     """one epoch over `data` (oracle.Data layout: entries {id, value}, row_ptr, target), in place on `model` (oracle.Model layout:
     w0, w[n], v[k][n], k0, k1, reg0, regw, regv) and `state`.  eta None = lr.  Returns the largest |change| of a w / v coordinate
-    over the epoch's batches."""
+    over the epoch's batches.  weights: None, or one finite weight >= 0 per row (fmx_set_row_weights): rounded to float32, then
+    multiplied into the multiplier in the working dtype -- it scales the loss only, nocc and the bias's reg0 term keep counting rows."""
     if rule not in ("adagrad", "sgd"):
         raise ValueError("unknown rule %r (adagrad | sgd)" % (rule,))
     T = np.dtype(dtype).type
     eta = T(lr if eta is None else eta)
+    cw = row_weights(weights, data.n_rows, dtype)
     ids_all = data.entries["id"].astype(np.int64)
     xs_all = data.entries["value"].astype(dtype)
     row_ptr = data.row_ptr.astype(np.int64)
@@ -75,6 +91,8 @@ def epoch(model, data, task, lr, min_target, max_target, batch, w0_chunk, state,
             c1 = min(nb, c0 + chunk)
             w0s = T(model.w0) if model.k0 else T(0)
             me = _multiplier(task, w0s + rest[c0:c1], y[c0:c1], T(min_target), T(max_target)).astype(dtype)
+            if cw is not None:
+                me = (me * cw[r0 + c0:r0 + c1]).astype(dtype)
             mult[c0:c1] = me
             if model.k0:
                 model.w0 -= float(lr) * (float(me.sum(dtype=np.float64)) + (c1 - c0) * float(model.reg0) * float(w0s))

@@ -27,6 +27,7 @@ STAT_WARN = 3   # FMX_STAT_WARN_MASK: the two bits that say something about the 
 STAT_SCAN_PIT, STAT_SCAN_SERIAL, STAT_SCAN_FALLBACK, STAT_EVENT_SYNC, STAT_HANDOFF_TIMEOUT, STAT_SEQ_RUNS, STAT_SMALL_ONE = 4, 8, 16, 32, 64, 256, 512
 # FMX_SGD_SEQUENTIAL: which kernels the epoch ran (ABI 9)
 STAT_SEQ_ENTRIES, STAT_SEQ_WG, STAT_SEQ_ROWS, STAT_RUN_ONE, STAT_RUN_TWO, STAT_RUN_THREE = 1024, 2048, 4096, 8192, 16384, 32768
+STAT_WEIGHTED = 65536   # FMX_STAT_WEIGHTED: an fmx_adapt / fmx_ftrl epoch on a slot with row weights (set_row_weights)
 SYNTH_UNIFORM, SYNTH_CRITEO = 0, 1
 BLOCKS_EXPAND, BLOCKS_KEEP = 0, 1
 COMM_ID_BYTES = 128
@@ -120,6 +121,13 @@ class EvalEx(C.Structure):
                 ("auc_num2", C.c_uint64), ("auc", C.c_double), ("logloss", C.c_double), ("rmse", C.c_double), ("mae", C.c_double),
                 ("accuracy", C.c_double), ("device_seconds", C.c_double), ("rank_seconds", C.c_double),
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class EvalWeighted(C.Structure):                   # fmx_eval_weighted
+    _fields_ = [("rows", C.c_uint64), ("nan_rows", C.c_uint64), ("weight_sum", C.c_double), ("pos_weight", C.c_double),
+                ("neg_weight", C.c_double), ("correct_weight", C.c_double), ("loss_sum", C.c_double), ("sq_sum", C.c_double),
+                ("abs_sum", C.c_double), ("logloss", C.c_double), ("rmse", C.c_double), ("mae", C.c_double), ("accuracy", C.c_double),
+                ("device_seconds", C.c_double)]
 
 
 class EvalQuery(C.Structure):
@@ -267,6 +275,9 @@ SYMBOLS = [
     ("fmx_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
     ("fmx_evaluate_ex", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalEx)]),
     ("fmx_set_row_queries", C.c_int, [H, C.c_int, C.c_void_p, C.c_uint32]),
+    ("fmx_set_row_weights", C.c_int, [H, C.c_int, C.c_void_p]),
+    ("fmx_get_row_weights", C.c_int, [H, C.c_int, C.c_void_p]),
+    ("fmx_evaluate_weighted", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalWeighted)]),
     ("fmx_evaluate_by_query", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalQuery), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("fmx_rank_discounts", C.c_int, [C.c_uint32, C.c_void_p]),
     ("fmx_evaluate_rank", C.c_int, [H, C.c_int, C.POINTER(RankOpts), C.POINTER(EvalRank), C.c_void_p, C.c_void_p]),
@@ -621,6 +632,35 @@ class Handle:
     def set_row_queries(self, slot, qid, n_queries=None):
         """per-row query ids of a slot (fmx_set_row_queries); n_queries None = max + 1, qid None drops them"""
         self._nq[slot] = _set_row_queries(self, self.lib.fmx_set_row_queries, self.h, slot, qid, n_queries)
+
+    def set_row_weights(self, slot, weights):
+        """per-row weights of a slot (fmx_set_row_weights): one finite float32 >= 0 per row; None drops them.  fmx_adapt / fmx_ftrl
+        epochs on the slot then scale every row's loss by its weight; the trainers without a weighted form refuse the slot"""
+        if weights is None:
+            self._chk(self.lib.fmx_set_row_weights(self.h, slot, None))
+            return
+        n_rows = C.c_uint32(0)
+        self._chk(self.lib.fmx_rows_info(self.h, slot, C.byref(n_rows), None))
+        w = np.ascontiguousarray(np.asarray(weights).reshape(-1), dtype=np.float32)
+        if len(w) != n_rows.value:
+            raise ValueError("set_row_weights: %d weights for %d rows" % (len(w), n_rows.value))
+        buf = w if len(w) else np.zeros(1, dtype=np.float32)           # (an empty slot still takes a non-NULL pointer: NULL drops)
+        self._chk(self.lib.fmx_set_row_weights(self.h, slot, _ptr(buf)))
+
+    def get_row_weights(self, slot):
+        """the weights as stored (fmx_get_row_weights): float32 [n_rows]"""
+        n_rows = C.c_uint32(0)
+        self._chk(self.lib.fmx_rows_info(self.h, slot, C.byref(n_rows), None))
+        out = np.zeros(n_rows.value, dtype=np.float32)
+        self._chk(self.lib.fmx_get_row_weights(self.h, slot, _ptr(out) if len(out) else None))
+        return out
+
+    def evaluate_weighted(self, slot, link=LINK_LOGISTIC):
+        """weighted log loss / accuracy (classification) or RMSE / MAE (regression) and the sums behind them, reduced on the device
+        in a fixed order (fmx_evaluate_weighted): the EvalWeighted struct"""
+        opts, ev = EvalOpts(link, 0), EvalWeighted()
+        self._chk(self.lib.fmx_evaluate_weighted(self.h, slot, C.byref(opts), C.byref(ev)))
+        return ev
 
     def evaluate_by_query(self, slot, link=LINK_LOGISTIC, per_query=False):
         """exact AUC inside every query (GAUC), reduced on the device (fmx_evaluate_by_query): the EvalQuery struct, or with

@@ -45,6 +45,11 @@ After training one line on stderr gives the zero counts of the model (fmx_param_
 -method bpr -optimizer adagrad|ftrl (with the same options): the pairwise batch rule with that per-coordinate step
 (fmx_adapt_pair_epoch* / fmx_ftrl_pair_epoch*, learner.FMLearnPairAdaptive), on -train_pairs and on -interactions; -gpu_mode then
 defaults to minibatch (batch 1 is the per-pair rule) and sequential is refused.
+-train_weights F [-test_weights F] (-method sgd with -optimizer adagrad | ftrl): one non-negative float per row of -train / -test,
+the row's weight (fmx_set_row_weights): the epochs scale every train row's loss by its weight -- the way to train on subsampled
+negatives, each kept one weighing 1 / rate.  -metrics then also knows wlogloss, the weighted log loss of the sets that have weights
+(fmx_evaluate_weighted; nan for a set without), as "#Iter=  i\twlogloss: Train=..\tTest=.." on stderr and wlogloss_* in -rlog.
+Any other method or optimizer refuses the flags: it has no weighted form.
 -serve bf16 (sgd, sgda, bpr, als): after training a frozen bf16 copy of the model is taken on the device (fmx_compact_begin) and the
 -out predictions and the -topk lists come from it.  One "compact" line on stderr carries the copy's bytes next to the fp32 tables',
 max_abs_err and nonfinite of the rounding, and the test metric -- with -metrics each named metric too -- from fp32 and from bf16 side
@@ -97,6 +102,9 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "ftrl_alpha": "-optimizer ftrl: per-coordinate rate of w and V (> 0); default=-learn_rate",
          "ftrl_beta": "-optimizer ftrl: beta (> 0); default=1",
          "l1": "-optimizer ftrl: 'w,v' = L1 strength of the linear weights and of the factors (>= 0); default=0,0",
+         "train_weights": "filename with one weight (float >= 0) per train row: -method sgd with -optimizer adagrad | ftrl scales every"
+                          " row's loss by it; -metrics then knows wlogloss",
+         "test_weights": "the same for the test rows (read by -metrics wlogloss only); needs -train_weights",
          "serve": "bf16 | int8: score -out, -metrics and -topk after training from a frozen bf16 or row-wise int8 copy of the model; sgd, sgda, bpr, als"}
 
 
@@ -135,6 +143,24 @@ def read_queries(path, n_rows):
     if len(ids) != n_rows:
         raise ValueError("%s has %d lines, the data set has %d rows" % (path, len(ids), n_rows))
     return np.array(ids, dtype=np.uint32)
+
+
+def read_weights(path, n_rows):
+    """a -train_weights / -test_weights file: one finite float >= 0 per line, the weight of the row with that line number; the line
+    count must equal the rows of the data file"""
+    ws = []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            t = line.split()
+            if len(t) != 1:
+                raise ValueError("cannot parse line %d of %s: want one weight" % (no, path))
+            w = float(t[0])
+            if not 0.0 <= w < float("inf"):
+                raise ValueError("line %d of %s: a weight is a finite number >= 0 (got %s)" % (no, path, t[0]))
+            ws.append(w)
+    if len(ws) != n_rows:
+        raise ValueError("%s has %d lines, the data set has %d rows" % (path, len(ws), n_rows))
+    return np.array(ws, dtype=np.float32)
 
 
 def read_exclude(path, n_query, n_cand):
@@ -299,10 +325,21 @@ def _main(argv):
             raise ValueError("-serve is not supported with -method mcmc: its prediction averages the draws, no single model scores it")
         if a.get("relation"):
             raise ValueError("-serve is not supported with -relation: the snapshot does not score kept blocks")
+    if "train_weights" in a or "test_weights" in a:
+        if method != "sgd" or optimizer not in ("adagrad", "ftrl"):
+            raise ValueError("-train_weights / -test_weights belong to -method sgd with -optimizer adagrad or ftrl: -method %s%s has no "
+                             "weighted form" % (method, " -optimizer " + optimizer if method in ("sgd", "bpr") else ""))
+        if not a.get("train_weights"):
+            raise ValueError("-test_weights needs -train_weights" if "train_weights" not in a else "-train_weights needs a filename")
+        if "test_weights" in a and not a["test_weights"]:
+            raise ValueError("-test_weights needs a filename")
     metrics = tuple(split_list(a.get("metrics", "")))
     if "metrics" in a:
         for m in metrics:
-            if m not in L.EXTRA_METRICS:
+            if m == L.WEIGHTED_METRIC:
+                if not a.get("train_weights"):
+                    raise ValueError("-metrics wlogloss needs -train_weights")
+            elif m not in L.EXTRA_METRICS:
                 raise ValueError("-metrics knows auc and logloss, not '%s'" % m)
         if method == "bpr" or (method == "mcmc" and not dev_avg):
             raise ValueError("-metrics is not supported with -method %s" % method +
@@ -355,6 +392,8 @@ def _main(argv):
 
     test_queries = read_queries(a["test_queries"], test.num_cases) if a.get("test_queries") else None
     train_queries = read_queries(a["train_queries"], train.num_cases) if a.get("train_queries") else None
+    train_weights = read_weights(a["train_weights"], train.num_cases) if a.get("train_weights") else None
+    test_weights = read_weights(a["test_weights"], test.num_cases) if a.get("test_weights") else None
 
     validation = None
     if method == "sgda":                                                             # libfm.cpp:173-194
@@ -502,6 +541,10 @@ def _main(argv):
         l.set_queries(train, train_queries)
     if rank_at:
         l.rank_cutoffs = rank_at
+    if train_weights is not None:
+        l.set_weights(train, train_weights)
+    if test_weights is not None:
+        l.set_weights(test, test_weights)
     if implicit:
         print("Loading interactions...\t")
         inter = read_interactions(a["interactions"], train.num_cases, cand.num_cases)
@@ -546,7 +589,7 @@ def _main(argv):
             serve, ci.bytes_compact, ci.bytes_params, ci.max_abs_err, ci.nonfinite, l.evaluate(test), serve, scorer.evaluate(test))
         if metrics and not dev_avg:
             ex32, ex16 = l.evaluate_ex(test), scorer.evaluate_ex(test)
-            line += "".join("\t%s(fp32)=%g\t%s(%s)=%g" % (m, getattr(ex32, m), m, serve, getattr(ex16, m)) for m in metrics)
+            line += "".join("\t%s(fp32)=%g\t%s(%s)=%g" % (m, getattr(ex32, m), m, serve, getattr(ex16, m)) for m in metrics if m in L.EXTRA_METRICS)
         print(line, file=sys.stderr)
     if "rlog" in a and a["rlog"]:
         with open(a["rlog"], "w") as f:                                              # rlog.h:60-103: TSV with a header

@@ -357,6 +357,7 @@ static int als_begin_shards(const std::vector<fmx_handle>& hs, fmx_group g, int 
 int fmx_als_begin(fmx_handle h, int train_slot) {
   touch_w(h);
   if (!h) return FMX_E_ARG;
+  { const int rw = refuse_weighted(h, train_slot, "fmx_als_begin"); if (rw) return rw; }
   size_t bad = 0;
   const int rc = als_begin_shards(std::vector<fmx_handle>(1, h), nullptr, train_slot, "fmx_als_begin", &bad);
   if (rc != FMX_OK && h->als.slot == train_slot) als_free(h);      // a failed set-up leaves no half-built session behind

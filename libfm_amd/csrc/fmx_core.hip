@@ -138,6 +138,7 @@ void free_slot(Slot& s) {
   if (s.lmask) fmx_dev_free(s.lmask);
   if (s.ids) fmx_dev_free(s.ids);
   if (s.qid) fmx_dev_free(s.qid);
+  if (s.weight) fmx_dev_free(s.weight);
   s = Slot();
 }
 

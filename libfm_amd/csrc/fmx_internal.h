@@ -1,5 +1,5 @@
 // fmx_internal.h -- shared by the translation units of libfmx.so (fmx_core.hip, fmx_sgd.hip, fmx_als.hip, fmx_comm.hip, fmx_pair.hip, fmx_topk.hip,
-// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip; fmx_io.hip needs none of it).
+// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip, fmx_weighted.hip; fmx_io.hip needs none of it).
 // The C-ABI is include/fmx.h; nothing declared here is exported.
 #pragma once
 #pragma GCC visibility push(default)      // the C-ABI is the only thing libfmx.so exports (-fvisibility=hidden)
@@ -93,6 +93,9 @@ struct Slot {
   // per-row query ids (fmx_set_row_queries, fmx_evalq.hip); on a group they live on the first shard's slot, next to the targets
   uint32_t* qid = nullptr;           // [n_rows]
   uint32_t  n_queries = 0;           // 0: the slot has no query ids
+  // per-row weights (fmx_set_row_weights, fmx_weighted.hip); single handles only
+  float*    weight = nullptr;        // [n_rows]
+  bool      weighted = false;        // the slot has weights (an empty slot has them without an array)
 };
 void free_pairs(Slot& s);                                                // fmx_pair.hip
 void free_interactions(Slot& s);                                         // fmx_pairneg.hip
@@ -315,6 +318,8 @@ int eval_ex_finish(fmx_handle h, uint32_t n, const double* d, uint64_t pos, uint
 // fmx_evalq.hip: the checks, the empty result and the whole reduction of fmx_evaluate_by_query (pooled metrics through eval_ex_scores,
 // then the by-query pipeline over the same scores), shared with fmx_group_evaluate_by_query (fmx_comm.hip)
 int set_row_queries_impl(fmx_handle h, const char* who, int slot, const uint32_t* qid, uint32_t n_queries);
+// fmx_weighted.hip: what every trainer without a weighted form says to a slot that has weights (FMX_E_UNSUPPORTED, before any launch)
+int refuse_weighted(fmx_handle h, int slot, const char* who);
 int evalq_check_slot(fmx_handle h, const char* who, int slot);
 void evalq_empty(fmx_eval_query* out, uint32_t n_queries);
 void evalq_zero_per_query(uint32_t n_queries, uint64_t* num2_q, uint32_t* pos_q, uint32_t* neg_q);

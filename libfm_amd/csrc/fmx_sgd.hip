@@ -7,6 +7,7 @@
 #include "fmx_small_kernels.h"
 #include "fmx_adapt_kernels.h"
 #include "fmx_ftrl_kernels.h"
+#include "fmx_weighted_kernels.h"
 
 namespace {
 // default micro-chunk of the bias recurrence.  The reference moves w0 after EVERY example (fm_sgd.h:34-37); summing the
@@ -91,6 +92,7 @@ int fmx_partial_floats(fmx_handle h, uint32_t batch, uint64_t* n_floats) {
 int fmx_sgd_partial(fmx_handle h, int slot, uint64_t row0, uint32_t n_rows, float* d_partial, void* stream) {
   int rc = check_slot(h, slot, false);
   if (rc) return rc;
+  rc = refuse_weighted(h, slot, "fmx_sgd_partial"); if (rc) return rc;
   const Slot& s = h->slots[slot];
   if (row0 + n_rows > s.n_rows) return fail(h, FMX_E_ARG, "fmx_sgd_partial: rows [%llu,+%u) outside slot (%u rows)",
                                             (unsigned long long)row0, n_rows, s.n_rows);
@@ -659,6 +661,7 @@ int fmx_sgd_finish(fmx_handle h, int slot, uint64_t row0, uint32_t n_rows, const
                    const fmx_sgd_opts* opts, void* stream) {
   touch_w(h);
   int rc = check_slot(h, slot, true); if (rc) return rc;
+  rc = refuse_weighted(h, slot, "fmx_sgd_finish"); if (rc) return rc;
   Slot& s = h->slots[slot];
   if (row0 + n_rows > s.n_rows) return fail(h, FMX_E_ARG, "fmx_sgd_finish: rows outside slot");
   if (!s.blocks.empty()) return fail(h, FMX_E_UNSUPPORTED, "relations are not supported with SGD");   // fm_learn_sgd.h:61-63
@@ -1276,6 +1279,7 @@ static int epoch_close(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, const fm
 
 int fmx_sgd_epoch(fmx_handle h, int slot, const fmx_sgd_opts* opts, fmx_epoch_stats* stats) {
   int rc = check_slot(h, slot, true); if (rc) return rc;
+  rc = refuse_weighted(h, slot, "fmx_sgd_epoch"); if (rc) return rc;
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   if (!opts) return fail(h, FMX_E_ARG, "fmx_sgd_epoch: opts is NULL");
   HIPCHK(h, hipSetDevice(h->device));
@@ -1387,6 +1391,7 @@ int fmx_sgda_epoch(fmx_handle h, int train_slot, int validation_slot, int do_lam
   rc = check_slot(h, validation_slot, true);
   if (rc) return rc;
   if (!h->sgda.reg) return fail(h, FMX_E_STATE, "fmx_sgda_epoch before fmx_sgda_begin");
+  rc = refuse_weighted(h, train_slot, "fmx_sgda_epoch"); if (rc) return rc;
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   HIPCHK(h, hipSetDevice(h->device));
   const Slot& s = h->slots[train_slot];
@@ -1431,6 +1436,7 @@ int fmx_sgda_epoch_minibatch(fmx_handle h, int train_slot, int validation_slot, 
   rc = check_slot(h, validation_slot, true);
   if (rc) return rc;
   if (!h->sgda.reg) return fail(h, FMX_E_STATE, "fmx_sgda_epoch_minibatch before fmx_sgda_begin");
+  rc = refuse_weighted(h, train_slot, "fmx_sgda_epoch_minibatch"); if (rc) return rc;
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   HIPCHK(h, hipSetDevice(h->device));
   Slot& s = h->slots[train_slot];
@@ -1581,6 +1587,24 @@ int fmx_adapt_get_state_rows(fmx_handle h, const uint32_t* ids, uint32_t count, 
   return state_rows(h, "fmx_adapt_get_state_rows", ids, count, tabs, outs, 1);
 }
 
+// step 2 of a batch on a slot with weights (include/fmx.h "fmx_set_row_weights"): k_scan_weighted, the one-wavefront chain with
+// mult_e = c_e * multiplier, on the caller's stream.  Never parallel in time, whatever the batch; without k0 the micro-chunk means
+// nothing and the batch is one chunk.  Micro-chunks of 16 / 32 / 64 examples (the defaults) take the kernel's sub-piece form.
+static int launch_scan_weighted(fmx_handle h, const float* rest, const float* target, const float* weight, uint32_t n_rows, uint32_t chunk,
+                                const Hyper& hy, float* mult, hipStream_t st) {
+  h->run_status |= FMX_STAT_WEIGHTED | FMX_STAT_SCAN_SERIAL;
+  const uint32_t ch = hy.k0 ? chunk : n_rows;
+  const uint32_t sub = (hy.k0 && (chunk == 16u || chunk == 32u || chunk == 64u)) ? chunk : 0u;   // the sub-piece form of the default micro-chunks
+#define FMX_SCANW(TK, CH) hipLaunchKernelGGL((k_scan_weighted<TK, CH>), dim3(1), dim3(64), 0, st, rest, target, weight, n_rows, ch, hy, h->w0, mult)
+#define FMX_SCANW_CH(TK) do { if (sub == 16u) FMX_SCANW(TK, 16); else if (sub == 32u) FMX_SCANW(TK, 32); \
+                              else if (sub == 64u) FMX_SCANW(TK, 64); else FMX_SCANW(TK, 0); } while (0)
+  if (hy.task == 0) FMX_SCANW_CH(0); else FMX_SCANW_CH(1);
+#undef FMX_SCANW_CH
+#undef FMX_SCANW
+  HIPCHK(h, hipGetLastError());
+  return FMX_OK;
+}
+
 // one epoch of an optimiser that keeps per-coordinate state (AdaGrad, FTRL), after its entry point's own session checks: per batch the
 // batch rule's row sums and bias recurrence (fmx_sgda_epoch_minibatch's three launches), then launch_owner(sw, hy, st) starts the one
 // kernel in which an owner per (batch, feature) segment takes the rule's step.  The bias stays plain SGD at fmx_config::learn_rate.
@@ -1614,7 +1638,8 @@ static int stateful_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_ch
     float* S = h->partial;
     float* rest = S + (size_t)nb * h->KP;
     KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, st, s.ent, s.row_ptr, row0, nb, RowsF32{h->tb}, h->cfg.k1, S, rest));
-    rc = launch_scan(h, rest, s.target + row0, nb, chunk, hy, h->mult, st);
+    rc = s.weighted ? launch_scan_weighted(h, rest, s.target + row0, s.weight + row0, nb, chunk, hy, h->mult, st)
+                    : launch_scan(h, rest, s.target + row0, nb, chunk, hy, h->mult, st);
     if (rc) return rc;
     const SegWork sw = seg_work_dense(h, s, (size_t)(row0 / B), S, h->mult);
     if (sw.nseg) { rc = launch_owner(sw, hy, st); if (rc) return rc; }

@@ -4,6 +4,7 @@ device to.  Pure Python on purpose -- the AUC numerator is counted with Python i
     classification_metrics(scores, target, link="logistic") -> dict with the fields of fmx_eval_ex
     query_metrics(scores, target, qid, n_queries, link="logistic") -> dict with the fields of fmx_eval_query
     rank_metrics(scores, target, qid, n_queries, cutoffs, link="logistic") -> dict with the fields of fmx_eval_rank (section 20)
+    weighted_metrics(scores, target, weights, link="logistic", task=1, ...) -> dict with the fields of fmx_eval_weighted (section 23)
 
 ... and of the posterior accumulator (fmx_post_*): PosteriorAverage keeps the three prediction vectors of
 fm_learn_mcmc_simultaneous in numpy fp64; posterior_metric / posterior_evaluate_ex score a vector of means.
@@ -70,6 +71,54 @@ def classification_metrics(scores, target, link="logistic"):
     if pos and neg:
         out["auc"] = out["auc_num2"] / (2 * pos * neg)
     out["logloss"] = math.fsum(loss_term(x if s else -x, link) for x, s in zip(p, positive)) / rows
+    return out
+
+
+def weighted_metrics(scores, target, weights, link="logistic", task=1, min_target=-math.inf, max_target=math.inf):
+    """CPU restatement of fmx_evaluate_weighted (include/fmx.h): a dict with the fields of fmx_eval_weighted.
+    weights: one finite weight >= 0 per row, rounded to float32 first (what fmx_set_row_weights stores).  task 1 (classification):
+    weight_sum, pos_weight, neg_weight, correct_weight, loss_sum and logloss / accuracy; task 0 (regression): sq_sum, abs_sum and
+    rmse / mae of the score clamped to [min_target, max_target] in fp32.  Every sum is math.fsum over fp64 terms c_i * term_i; a
+    row of weight 0 adds exactly 0, also where its loss is +inf or its score NaN.  nan_rows > 0 (classification) or
+    weight_sum == 0 makes the ratios NaN; the sums and counts stay right."""
+    if link not in LINKS:
+        raise ValueError("unknown link %r (want one of %s)" % (link, ", ".join(LINKS)))
+    p32 = np.asarray(scores, dtype=np.float32).reshape(-1)
+    y32 = np.asarray(target, dtype=np.float32).reshape(-1)
+    c32 = np.asarray(weights, dtype=np.float64).reshape(-1).astype(np.float32)
+    if not (len(p32) == len(y32) == len(c32)):
+        raise ValueError("%d scores, %d targets, %d weights" % (len(p32), len(y32), len(c32)))
+    if not (np.isfinite(c32).all() and (c32 >= 0).all()):
+        raise ValueError("weights must be finite and >= 0")
+    c = [float(x) for x in c32]
+    y = [float(x) for x in y32]
+    rows = len(c)
+    wsum = math.fsum(c)
+    out = {"rows": rows, "nan_rows": 0, "weight_sum": wsum, "pos_weight": 0.0, "neg_weight": 0.0, "correct_weight": 0.0,
+           "loss_sum": 0.0, "sq_sum": 0.0, "abs_sum": 0.0, "logloss": math.nan, "rmse": math.nan, "mae": math.nan,
+           "accuracy": math.nan, "device_seconds": 0.0}
+    if task == 0:
+        pc = np.maximum(np.float32(min_target), np.minimum(np.float32(max_target), p32))     # fm_learn.h:138-139 (a NaN score clamps to max_target)
+        pc = np.where(p32 != p32, np.float32(max_target), pc)
+        err = [float(a) - b for a, b in zip(pc, y)]
+        out["sq_sum"] = math.fsum(w * e * e if w else 0.0 for w, e in zip(c, err))
+        out["abs_sum"] = math.fsum(w * abs(e) if w else 0.0 for w, e in zip(c, err))
+        if wsum > 0:
+            out["rmse"] = math.sqrt(out["sq_sum"] / wsum)
+            out["mae"] = out["abs_sum"] / wsum
+        return out
+    p = [float(x) for x in p32]
+    positive = [t >= 0 for t in y]                                    # fm_learn.h:118
+    out["nan_rows"] = sum(1 for x in p if x != x)
+    out["pos_weight"] = math.fsum(w for w, s in zip(c, positive) if s)
+    out["neg_weight"] = math.fsum(w for w, s in zip(c, positive) if not s)
+    out["correct_weight"] = math.fsum(w for w, x, t in zip(c, p, y) if (x >= 0 and t >= 0) or (x < 0 and t < 0))
+    # (a NaN score of positive weight makes the sum NaN, as on the device; the ratios are NaN then anyway)
+    out["loss_sum"] = math.fsum(0.0 if not w else (math.nan if x != x else w * loss_term(x if s else -x, link))
+                                for w, x, s in zip(c, p, positive))
+    if out["nan_rows"] == 0 and wsum > 0:
+        out["logloss"] = out["loss_sum"] / wsum
+        out["accuracy"] = out["correct_weight"] / wsum
     return out
 
 

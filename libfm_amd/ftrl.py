@@ -16,7 +16,7 @@ A feature that no batch touches keeps theta, z and n.  dtype=np.float32 runs eve
 double, as on the device)."""
 import numpy as np
 
-from .adaptive import _multiplier
+from .adaptive import _multiplier, row_weights
 
 
 class FtrlState:
@@ -54,10 +54,12 @@ def _step(theta, z, n, g, alpha, beta, l1, l2, dtype):
     return new, z1, n1
 
 
-def epoch(model, data, task, lr, min_target, max_target, batch, w0_chunk, state, dtype=np.float64):
+def epoch(model, data, task, lr, min_target, max_target, batch, w0_chunk, state, dtype=np.float64, weights=None):
     """one epoch over `data` (oracle.Data layout), in place on `model` (oracle.Model layout; regw / regv are not read) and `state`.
-    lr is the bias's plain rate.  Returns the largest |change| of a w / v coordinate over the epoch's batches."""
+    lr is the bias's plain rate.  Returns the largest |change| of a w / v coordinate over the epoch's batches.  weights: as
+    adaptive.epoch (one weight per row, float32 first, multiplied into the multiplier)."""
     T = np.dtype(dtype).type
+    cw = row_weights(weights, data.n_rows, dtype)
     ids_all = data.entries["id"].astype(np.int64)
     xs_all = data.entries["value"].astype(dtype)
     row_ptr = data.row_ptr.astype(np.int64)
@@ -92,6 +94,8 @@ def epoch(model, data, task, lr, min_target, max_target, batch, w0_chunk, state,
             c1 = min(nb, c0 + chunk)
             w0s = T(model.w0) if model.k0 else T(0)
             me = _multiplier(task, w0s + rest[c0:c1], y[c0:c1], T(min_target), T(max_target)).astype(dtype)
+            if cw is not None:
+                me = (me * cw[r0 + c0:r0 + c1]).astype(dtype)
             mult[c0:c1] = me
             if model.k0:
                 model.w0 -= float(lr) * (float(me.sum(dtype=np.float64)) + (c1 - c0) * float(model.reg0) * float(w0s))

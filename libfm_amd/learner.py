@@ -114,6 +114,7 @@ class FMModel:
 
 
 EXTRA_METRICS = ("auc", "logloss")
+WEIGHTED_METRIC = "wlogloss"                                    # extra_metrics of a learner with set_weights: fmx_evaluate_weighted's log loss
 RANK_MAX_CUTOFFS, RANK_MAX_K = capi.RANK_MAX_CUTOFFS, capi.RANK_MAX_K   # of rank_cutoffs (fmx_evaluate_rank)
 
 
@@ -121,14 +122,18 @@ def _log_extra_metrics(learner, i, train, test):
     """learner.extra_metrics on a classification task: one stderr line per named metric (where the BPR learner puts its loss
     lines) and <metric>_train / <metric>_test in the iteration's log row.  stdout is not touched."""
     names = tuple(learner.extra_metrics)
+    weights = getattr(learner, "_weights", None)                # (only FMLearnSGD and its subclasses carry row weights)
     for m in names:
-        if m not in EXTRA_METRICS:
-            raise ValueError("unknown metric %r (want auc, logloss)" % (m,))
+        if m not in EXTRA_METRICS and not (m == WEIGHTED_METRIC and weights is not None):
+            raise ValueError("unknown metric %r (want auc, logloss%s)" % (m, ", wlogloss" if weights is not None else ""))
     if not names or learner.task != TASK_CLASSIFICATION:
         return
     tr, te = learner.evaluate_ex(train), learner.evaluate_ex(test)
     for m in names:
-        a, b = getattr(tr, m), getattr(te, m)
+        if m == WEIGHTED_METRIC:                                 # the weighted log loss of the sets that carry weights (set_weights); nan for the others
+            a, b = (learner.evaluate_weighted(d).logloss if id(d) in weights else float("nan") for d in (train, test))
+        else:
+            a, b = getattr(tr, m), getattr(te, m)
         print("#Iter=%3d\t%s: Train=%g\tTest=%g" % (i, m, a, b), file=sys.stderr)
         learner.log[-1][m + "_train"], learner.log[-1][m + "_test"] = a, b
 
@@ -157,6 +162,15 @@ def _log_query_metrics(learner, i, train, test):
             for m in ("ndcg", "recall", "precision"):
                 row["%s@%d_%s" % (m, k, name)] = getattr(rk.at[j], m) if rk is not None else nan
         print("#Iter=%3d\tndcg@%d: Train=%g\tTest=%g" % (i, k, row["ndcg@%d_train" % k], row["ndcg@%d_test" % k]), file=sys.stderr)
+
+
+def _check_weights(data, weights):
+    w = np.asarray(weights, dtype=np.float64).reshape(-1).astype(np.float32)
+    if len(w) != data.num_cases:
+        raise ValueError("set_weights: %d weights for %d rows" % (len(w), data.num_cases))
+    if not (np.isfinite(w).all() and (w >= 0).all()):
+        raise ValueError("set_weights: every weight must be finite and >= 0")
+    return w
 
 
 def _check_queries(data, qid):
@@ -247,6 +261,7 @@ class FMLearnSGD:
         self._h = None
         self._slots = {}
         self._queries = {}                                      # id(data) -> (qid, n_queries) of set_queries
+        self._weights = {}                                      # id(data) -> float32 weights of set_weights
         self.rank_cutoffs = ()                                  # with query ids: ndcg / recall / precision at these K per iteration
         self._adapt_open = False
         self._ftrl_open = False
@@ -292,6 +307,8 @@ class FMLearnSGD:
             self._slots[key] = slot
             if key in self._queries:
                 self._h.set_row_queries(slot, *self._queries[key])
+            if key in self._weights:
+                self._h.set_row_weights(slot, self._weights[key])
         return self._slots[key]
 
     def set_queries(self, data, qid, n_queries=None):
@@ -300,6 +317,25 @@ class FMLearnSGD:
         self._queries[id(data)] = (_check_queries(data, qid), n_queries)
         if id(data) in self._slots:
             self._h.set_row_queries(self._slots[id(data)], *self._queries[id(data)])
+
+    def set_weights(self, data, weights):
+        """one weight >= 0 per row of `data` (fmx_set_row_weights; None drops them): as the train set, optimizer 'adagrad' / 'ftrl'
+        scale every row's loss by its weight (the other trainers have no weighted form and learn() refuses); on any set,
+        evaluate_weighted(data) and extra_metrics 'wlogloss' report the weighted log loss.  The weights are stored and attached
+        when the set is uploaded, like set_queries' ids."""
+        if weights is None:
+            self._weights.pop(id(data), None)
+        else:
+            self._weights[id(data)] = _check_weights(data, weights)
+        if id(data) in self._slots:
+            self._h.set_row_weights(self._slots[id(data)], self._weights.get(id(data)))
+
+    def evaluate_weighted(self, data):
+        """weighted log loss / accuracy (classification) or RMSE / MAE (regression) of `data` under the current parameters
+        (capi.EvalWeighted), reduced on the device (fmx_evaluate_weighted)"""
+        if id(data) not in self._weights:
+            raise ValueError("evaluate_weighted: the data set has no weights (set_weights)")
+        return self._h.evaluate_weighted(self._slot(data), self.EVAL_LINK)
 
     def evaluate_by_query(self, data):
         """exact AUC inside every query of `data` under the current parameters: gauc, auc_macro, auc_within, the counts and the
@@ -321,6 +357,8 @@ class FMLearnSGD:
         self._check_optimizer()
         if (self.optimizer == "adagrad") != self._adapt_open or (self.optimizer == "ftrl") != self._ftrl_open:
             raise ValueError("optimizer was changed after init()")
+        if id(train) in self._weights and self.optimizer == "sgd":
+            raise ValueError("the train set has weights (set_weights): optimizer sgd has no weighted form, use adagrad or ftrl")
         print("learnrate=%g" % self.learn_rate, file=self.out)   # fm_learn_sgd.h:57-59
         print("#iterations=%d" % self.num_iter, file=self.out)
         print("SGD: DON'T FORGET TO SHUFFLE THE ROWS IN TRAINING DATA TO GET THE BEST RESULTS.", file=self.out)
