@@ -236,6 +236,8 @@ typedef struct fmx_epoch_stats {
 #define FMX_STAT_RUN_ONE       8192u /* at least one conflict-free run as ONE launch (k_run_fused) */
 #define FMX_STAT_RUN_TWO      16384u /* at least one run as two launches (k_rowsums + k_run_apply) */
 #define FMX_STAT_RUN_THREE    32768u /* at least one run as three launches (k_rowsums + the recurrence on its own + k_apply) */
+#define FMX_STAT_WSTREAM     131072u /* at least one batch of the one-pass minibatch epoch read the linear weights of the slot's once-only features from
+                                        the slot's packed training-side stream instead of gathering them (FMX_WTRAIN=0 at fmx_create: never) */
 #define FMX_STAT_WEIGHTED     65536u /* fmx_adapt_epoch / fmx_ftrl_epoch on a slot with row weights (fmx_set_row_weights): every batch's recurrence ran as
                                         k_scan_weighted, a one-wavefront chain (FMX_STAT_SCAN_SERIAL is set with it, FMX_STAT_SCAN_PIT never) */
 
@@ -397,6 +399,10 @@ int fmx_free_rows(fmx_handle h, int slot);
  * their LOCAL rows (kept entries only, ids = local row of the feature on this shard). Any pointer may be NULL. */
 int fmx_rows_info(fmx_handle h, int slot, uint32_t *n_rows, uint64_t *nnz);
 int fmx_download_rows(fmx_handle h, int slot, void *entries, uint64_t *row_ptr, float *target);
+/* (tests / debugging) the slot's training-side weight stream as its first one-pass epoch left it: *singles = entries whose feature occurs
+ * exactly once in the slot (and whose row the one-pass kernel keeps in registers), *kept = 1 when the stream was built for them
+ * (FMX_STAT_WSTREAM).  Both 0 before that epoch.  Either pointer may be NULL. */
+int fmx_wtrain_info(fmx_handle h, int slot, uint64_t *singles, int *kept);
 
 /* ---- host-side reader of libFM's text format (no device, no handle) ----------------------------------------
  * Data::load, text branch (src/libfm/src/Data.h:180-285): lines "target id:value id:value ...", blank lines and lines

@@ -28,6 +28,7 @@ STAT_SCAN_PIT, STAT_SCAN_SERIAL, STAT_SCAN_FALLBACK, STAT_EVENT_SYNC, STAT_HANDO
 # FMX_SGD_SEQUENTIAL: which kernels the epoch ran (ABI 9)
 STAT_SEQ_ENTRIES, STAT_SEQ_WG, STAT_SEQ_ROWS, STAT_RUN_ONE, STAT_RUN_TWO, STAT_RUN_THREE = 1024, 2048, 4096, 8192, 16384, 32768
 STAT_WEIGHTED = 65536   # FMX_STAT_WEIGHTED: an fmx_adapt / fmx_ftrl epoch on a slot with row weights (set_row_weights)
+STAT_WSTREAM = 131072   # FMX_STAT_WSTREAM: a one-pass minibatch epoch read the once-only features' linear weights from the slot's packed stream
 SYNTH_UNIFORM, SYNTH_CRITEO = 0, 1
 BLOCKS_EXPAND, BLOCKS_KEEP = 0, 1
 COMM_ID_BYTES = 128
@@ -271,6 +272,7 @@ SYMBOLS = [
     ("fmx_free_rows", C.c_int, [H, C.c_int]),
     ("fmx_rows_info", C.c_int, [H, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     ("fmx_download_rows", C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("fmx_wtrain_info", C.c_int, [H, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     ("fmx_predict", C.c_int, [H, C.c_int, C.c_void_p]),
     ("fmx_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
     ("fmx_evaluate_ex", C.c_int, [H, C.c_int, C.POINTER(EvalOpts), C.POINTER(EvalEx)]),
@@ -600,6 +602,12 @@ class Handle:
         y = np.zeros(n_rows.value, dtype=np.float32)
         self._chk(self.lib.fmx_download_rows(self.h, slot, _ptr(ent) if nnz.value else None, _ptr(rp), _ptr(y)))
         return ent, rp, y
+
+    def wtrain_info(self, slot):
+        """(singles of the slot, whether its training-side weight stream was kept) -- as the slot's first one-pass epoch left them"""
+        singles, kept = C.c_uint64(0), C.c_int(0)
+        self._chk(self.lib.fmx_wtrain_info(self.h, slot, C.byref(singles), C.byref(kept)))
+        return int(singles.value), bool(kept.value)
 
     def free_rows(self, slot):
         self._chk(self.lib.fmx_free_rows(self.h, slot))

@@ -137,6 +137,9 @@ void free_slot(Slot& s) {
   if (s.wside) fmx_dev_free(s.wside);
   if (s.lmask) fmx_dev_free(s.lmask);
   if (s.ids) fmx_dev_free(s.ids);
+  if (s.smask) fmx_dev_free(s.smask);
+  if (s.soff) fmx_dev_free(s.soff);
+  if (s.wtrain) fmx_dev_free(s.wtrain);
   if (s.qid) fmx_dev_free(s.qid);
   if (s.weight) fmx_dev_free(s.weight);
   s = Slot();
@@ -205,6 +208,58 @@ int ensure_ids(fmx_handle h, Slot& s) {
     if (er != hipSuccess) return fail(h, FMX_E_HIP, "id-only stream of the slot: %s", hipGetErrorString(er));
   }
   if (getenv("FMX_TRACE_SETUP")) fprintf(stderr, "[fmx setup] id-only stream %s %8.3f ms\n", s.ids ? "built" : "not unit-valued",
+                                         1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - acc_.t0).count());
+  return FMX_OK;
+}
+
+// the slot's training-side weight stream (WTrain, fmx_kernels.h): the entries whose feature occurs ONCE in the slot ("singles") get a packed
+// copy of their linear weight that k_fused<FUSED_EXACT> reads instead of gathering w[j].  Built once, by the first one-pass epoch after an
+// upload: one count per feature (at most 2^27 buckets, temporary), one mask per row, the exclusive sum of the rows' counts.  Kept only where
+// the singles are at least 1/16 of the entries (field data with skewed ids has next to none: 12 bytes per row would buy nothing); resident
+// then: 12 bytes per row + 4 per single.  Whatever goes wrong here -- an allocation above all -- leaves the slot gathering as before.
+int ensure_wtrain(fmx_handle h, Slot& s, uint32_t row_cap) {
+  if (s.wtrain_asked) return FMX_OK;
+  s.wtrain_asked = true;
+  if (!h->wtrain || s.nnz == 0 || s.nnz >= (1ull << 32) - 1 || s.n_rows >= 0x7FFFFFFEu) return FMX_OK;   // (soff counts in 32 bits)
+  struct Acc { fmx_handle h; std::chrono::steady_clock::time_point t0;
+               ~Acc() { h->setup_acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } acc_{h, std::chrono::steady_clock::now()};
+  const uint32_t M = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(h->n_local, 1), 1ull << 27);
+  const size_t n1 = (size_t)s.n_rows + 1;
+  uint32_t* cnt = nullptr; uint32_t* scount = nullptr; void* tmp = nullptr;
+  size_t tmp_bytes = 0;
+  uint32_t total = 0;
+  hipError_t er = hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n1, h->stream);
+  if (er == hipSuccess) er = fmx_dev_alloc(&cnt, (size_t)M * 4);
+  if (er == hipSuccess) er = fmx_dev_alloc(&scount, n1 * 4);
+  if (er == hipSuccess) er = fmx_dev_alloc(&tmp, std::max<size_t>(tmp_bytes, 256));
+  if (er == hipSuccess) er = fmx_dev_alloc(&s.smask, (size_t)s.n_rows * 8);
+  if (er == hipSuccess) er = fmx_dev_alloc(&s.soff, n1 * 4);
+  if (er == hipSuccess) er = hipMemsetAsync(cnt, 0, (size_t)M * 4, h->stream);
+  if (er == hipSuccess) er = hipMemsetAsync(scount + s.n_rows, 0, 4, h->stream);
+  if (er == hipSuccess) {
+    hipLaunchKernelGGL(k_wtrain_count, dim3((unsigned)std::min<uint64_t>((s.nnz + 255) / 256, 8192)), dim3(256), 0, h->stream, s.ent, s.nnz, M, cnt);
+    hipLaunchKernelGGL(k_wtrain_mask, dim3((unsigned)std::min<uint32_t>((s.n_rows + 3) / 4, 16384)), dim3(256), 0, h->stream, s.ent, s.row_ptr, s.n_rows, M,
+                       (const uint32_t*)cnt, row_cap, s.smask, scount);
+    er = hipGetLastError();
+  }
+  if (er == hipSuccess) er = hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, scount, s.soff, (int)n1, h->stream);
+  if (er == hipSuccess) er = hipMemcpyAsync(&total, s.soff + s.n_rows, 4, hipMemcpyDeviceToHost, h->stream);
+  if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
+  if (cnt) fmx_dev_free(cnt);
+  if (scount) fmx_dev_free(scount);
+  if (tmp) fmx_dev_free(tmp);
+  if (er == hipSuccess) s.wtrain_n = total;
+  const bool keep = er == hipSuccess && total != 0 && (uint64_t)total * 16u >= s.nnz;
+  if (keep) er = fmx_dev_alloc(&s.wtrain, (size_t)total * 4);
+  if (!keep || er != hipSuccess) {
+    if (er != hipSuccess) (void)hipGetLastError();               // (the stream is an extra: the epoch runs without it)
+    if (s.smask) fmx_dev_free(s.smask);
+    if (s.soff) fmx_dev_free(s.soff);
+    s.smask = nullptr; s.soff = nullptr; s.wtrain = nullptr;
+  }
+  s.wtrain_version = 0;                                          // nothing is in the stream yet: the first epoch gathers and fills it
+  if (getenv("FMX_TRACE_SETUP")) fprintf(stderr, "[fmx setup] training weight stream %s (%llu singles of %llu entries) %8.3f ms\n", s.wtrain ? "built" : "not kept",
+                                         (unsigned long long)s.wtrain_n, (unsigned long long)s.nnz,
                                          1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - acc_.t0).count());
   return FMX_OK;
 }
@@ -428,6 +483,8 @@ int fmx_create(const fmx_config* cfg, fmx_handle* out) {
     h->small_one = !(so && so[0] == '0');                       // small batches as one launch per batch (fmx_small_kernels.h); FMX_SMALL_ONE=0: two
     const char* si = getenv("FMX_IDS");
     h->ids = !(si && si[0] == '0');                             // id-only entry stream of unit-valued fixed-length slots (ensure_ids); FMX_IDS=0: entries
+    const char* sw = getenv("FMX_WTRAIN");
+    h->wtrain = !(sw && sw[0] == '0');                          // packed stream of the singles' linear weights (ensure_wtrain); FMX_WTRAIN=0: every w_j is gathered
     auto env_on = [](const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); };
     h->seq_rows = env_on("FMX_SEQ_ROWS");                       // FMX_SGD_SEQUENTIAL (fmx_sgd.hip fmx_sgd_epoch, seq_runs_epoch): =0 turns a form off
     h->seq_wg = env_on("FMX_SEQ_WG");
@@ -1094,6 +1151,14 @@ int fmx_rows_info(fmx_handle h, int slot, uint32_t* n_rows, uint64_t* nnz) {
   if (rc) return rc;
   if (n_rows) *n_rows = h->slots[slot].n_rows;
   if (nnz) *nnz = h->slots[slot].nnz;
+  return FMX_OK;
+}
+
+int fmx_wtrain_info(fmx_handle h, int slot, uint64_t* singles, int* kept) {
+  int rc = check_slot(h, slot, false);
+  if (rc) return rc;
+  if (singles) *singles = h->slots[slot].wtrain_n;
+  if (kept) *kept = h->slots[slot].wtrain != nullptr;
   return FMX_OK;
 }
 

@@ -67,6 +67,14 @@ struct Slot {
   float*    wside = nullptr;
   uint64_t* lmask = nullptr;
   uint64_t  wside_version = 0;
+  // training-side weight stream (fmx_kernels.h WTrain; ensure_wtrain): smask[row] = which entries are singles, soff[row] = singles in front
+  // of the row (n_rows + 1 elements), wtrain = one float per single; holds the current w while wtrain_version == the handle's w_version
+  uint64_t* smask = nullptr;
+  uint32_t* soff = nullptr;
+  float*    wtrain = nullptr;
+  uint64_t  wtrain_n = 0;            // singles of the slot (whether or not the stream was kept)
+  uint64_t  wtrain_version = 0;
+  bool      wtrain_asked = false;    // the slot's singles have been counted (wtrain == nullptr then: too few of them, or FMX_WTRAIN=0)
   // FMX_SGD_SEQUENTIAL: the slot cut into maximal runs of consecutive rows that share no feature (fmx_seq_kernels.h "Conflict-free runs")
   std::vector<uint32_t> run_start;   // [n_runs + 1]; empty: not built
   std::vector<uint8_t>  run_single;  // [n_runs] 1: one row that repeats an id (entry-by-entry kernel)
@@ -247,6 +255,7 @@ struct fmx_context_s {
   unsigned long long* small_slots = nullptr;        // [3 * SMALL_ONE_MAX]: multipliers, rest_e of even / odd batches
   bool small_one = true, small_one_used = false;
   bool ids = true;                                  // FMX_IDS=0 in the environment of fmx_create: k_fused keeps reading {id, value} entries (Slot::ids is never built)
+  bool wtrain = true;                               // FMX_WTRAIN=0 in the environment of fmx_create: every linear weight is gathered (Slot::wtrain is never built)
 };
 
 // ---- helpers shared between the translation units -------------------------------------------------------------
@@ -281,6 +290,7 @@ int ensure_segments(fmx_handle h, Slot& s, uint32_t B);                 // fmx_s
 int ensure_coll_mass(fmx_handle h, Slot& s);                             // fmx_core.hip
 int ensure_wside(fmx_handle h, Slot& s);                                 // fmx_core.hip
 int ensure_ids(fmx_handle h, Slot& s);                                   // fmx_core.hip
+int ensure_wtrain(fmx_handle h, Slot& s, uint32_t row_cap);              // fmx_core.hip (row_cap: longest row of k_fused's register path)
 inline void touch_w(fmx_handle h) { if (h) h->w_version++; }
 void resolve_batch(const fmx_config& cfg, double coll_mass, uint32_t requested, uint32_t dflt, double curv_scale, fmx_batch_info* out);
 constexpr uint32_t FMX_DEFAULT_BATCH = 262144u;                          // fmx_sgd_opts::batch = 0, before the stability cut

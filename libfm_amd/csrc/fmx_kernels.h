@@ -1602,6 +1602,30 @@ k_wside_mask(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr
   }
 }
 
+// ---- training-side weight stream (k_fused<FUSED_EXACT>): which entries are SINGLES -- the only occurrence of their feature in the slot ----
+// cnt[id mod M] = entries of the bucket; an entry is a single when its bucket holds ONE entry and its row takes k_fused's register path
+// (size <= cap).  A folded table -- M < n -- only loses singles: two features sharing a bucket count 2 and both keep gathering.
+static __global__ void __launch_bounds__(256)
+k_wtrain_count(const Entry* __restrict__ ent, uint64_t nnz, uint32_t M, uint32_t* __restrict__ cnt) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += (uint64_t)gridDim.x * blockDim.x)
+    atomicAdd(cnt + (ent[i].id % M), 1u);
+}
+// smask[r] = the singles of row r, scount[r] = how many (scount[n_rows] stays 0: the exclusive sum over n_rows + 1 elements ends on the total)
+static __global__ void __launch_bounds__(256)
+k_wtrain_mask(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, uint32_t n_rows, uint32_t M, const uint32_t* __restrict__ cnt,
+              uint32_t cap, uint64_t* __restrict__ smask, uint32_t* __restrict__ scount) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave0 = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
+  for (uint32_t r = wave0; r < n_rows; r += nwaves) {
+    const uint64_t a = row_ptr[r], b = row_ptr[r + 1];
+    bool flag = false;
+    if (b - a <= (uint64_t)cap && a + lane < b) flag = cnt[ent[a + lane].id % M] == 1u;   // (cap <= 64: a row of the two-pass branch has none)
+    const uint64_t bits = __ballot(flag);
+    if (lane == 0) { smask[r] = bits; scount[r] = (uint32_t)__popcll(bits); }
+  }
+}
+
 // ---- id-only stream (load_entry): ids[i] = the id of entry i; *not_one becomes 1 when some value of the slot is not 1.0f ---------
 static __global__ void __launch_bounds__(256)
 k_ids_build(const Entry* __restrict__ ent, uint64_t nnz, uint32_t* __restrict__ ids, uint32_t* __restrict__ not_one) {
@@ -2024,6 +2048,17 @@ k_apply_seg(const SegWork sw, const Tab tb, Hyper h) {
 //       batch-unique features are gathered, updated and written back, the others are left to k_apply_seg as above.
 // ----------------------------------------------------------------------------------------------
 enum { FUSED_STORE = 0, FUSED_ATOMIC = 1, FUSED_EXACT = 2, FUSED_APPLY = 3 };
+// the slot's TRAINING-SIDE WEIGHT STREAM (FUSED_EXACT; ensure_wtrain, fmx_core.hip).  A feature that occurs in exactly one entry of the slot
+// (a "single") has its w_j read and written, epoch after epoch, by the one lane that holds that entry: the rows of a slot are never
+// reordered (fm_learn_sgd_element.h:56).  That lane keeps a copy of what it stores to w[j] in a packed stream -- smask[row] bit i: entry i
+// is a single, soff[row]: singles in front of the row, the copy of entry i at w[soff[row] + popcount(smask[row] below bit i)] -- and reads
+// it back the next epoch with a coalesced load instead of a 64-byte gather.  w[j] is written all the same, so every other reader of w[] is
+// served and nothing is ever flushed.  read == 0: the stream does not hold the current w (something else has touched the linear weights
+// since the epoch that wrote it): every lane gathers, the singles' lanes rewrite the stream.
+// Two wavefronts on different dies may share a 64-byte sector of the stream: each reads and writes only its own 4 bytes, and nothing
+// written in a launch is read in that launch (an element belongs to one example of one batch), so the dies' L2s, which are not coherent
+// with each other inside a launch, cannot hand anybody a wrong value.
+struct WTrain { const uint64_t* smask = nullptr; const uint32_t* soff = nullptr; float* w = nullptr; uint32_t read = 0; };
 template <int KP, int ZR, int VAR>
 __global__ void __launch_bounds__(256)
 k_fused(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, const float* __restrict__ target,
@@ -2031,11 +2066,13 @@ k_fused(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, con
         const double* __restrict__ w0_ptr, float* __restrict__ rest_out,
         const uint64_t* __restrict__ cmask, float* __restrict__ S_out, float* __restrict__ mult_out, uint32_t fixed_nnz,
         uint32_t* __restrict__ handoff_err, const uint64_t* __restrict__ lmask, float* __restrict__ wside,
-        const uint32_t* __restrict__ ids) {
+        const uint32_t* __restrict__ ids, const WTrain wt) {
   // ids != nullptr: the slot's id-only stream stands in for the entries of the register path (load_entry; needs fixed_nnz != 0)
   // wside != nullptr (FUSED_EXACT, FMX_FLAG_KEEP_WSIDE): the slot's weight side stream is kept current -- entry i of a row gets the NEW
   // w_j when lmask says it is the last occurrence of its feature in the slot and this wavefront is the one that updates it (not deferred),
   // NaN otherwise: 128 coalesced bytes per example (see row_sums)
+  // wt.w != nullptr (FUSED_EXACT): the slot's training-side weight stream (WTrain above) -- the singles' lanes store their new w_j there as
+  // well, and take w_j from there instead of gathering it when wt.read says the stream holds the current w
   // handoff_err != nullptr: *w0_ptr is a hand-off slot (published by the recurrence kernel of an earlier batch on the side stream, possibly
   // still W0_PENDING): read it past the caches, and wait -- only where the multiplier needs it, behind the row gathers -- if it is not there yet
   // fixed_nnz != 0: every row of the slot holds exactly that many entries (one-hot field data): the entry list of example e starts at
@@ -2061,12 +2098,20 @@ k_fused(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, con
     uint64_t cm = 0, lm = 0;
     if constexpr (MASKED) cm = cmask[row0 + e];
     if constexpr (EXACT) { if (wside) lm = lmask[row0 + e]; }   // (with the mask: one round trip, long before it is needed)
+    uint64_t sm = 0; uint32_t so = 0;                           // wave-uniform: the singles of this example, where their copies start
+    if constexpr (EXACT) { if (wt.w) { sm = wt.smask[row0 + e]; so = wt.soff[row0 + e]; } }
     if (size <= (uint32_t)(ZR * EPI) && size <= 64u) {
       Entry en; en.id = 0; en.value = 0.f;
       float wv = 0.f;
+      // a single's lane: its element of the packed stream (sm has no bit at or beyond size, and none on a deferred entry: a single cannot
+      // occur twice in a batch).  The load hangs on sm / so alone, so it travels beside the entry load, not behind it
+      const bool single = EXACT && ((sm >> lane) & 1ull);
+      const uint32_t wi = so + __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+      const bool streamed = single && wt.read && h.k1;
+      if (streamed) wv = __builtin_nontemporal_load(wt.w + wi);
       if (lane < size) {
         en = load_entry(ent, ids, a + lane);
-        if (h.k1) wv = load_w(tb.w + (size_t)en.id * tb.ws);
+        if (h.k1 && !streamed) wv = load_w(tb.w + (size_t)en.id * tb.ws);
       }
       // hand-off: the bias slot was asked for before the entry list, so it is here when the entries are (loads return in order) and leaves
       // its registers before the row slots fill; a slot that is still pending (never, at bias_lag >= 2) is waited for here
@@ -2132,6 +2177,7 @@ k_fused(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, con
         if (ATOMIC) unsafeAtomicAdd(tb.w + (size_t)en.id * tb.ws, dw);
         else tb.w[(size_t)en.id * tb.ws] = wv + dw;
         w_keep = wv + dw;
+        if constexpr (EXACT) { if (single) __builtin_nontemporal_store(w_keep, wt.w + wi); }   // the value w[j] now holds, bit for bit
       }
       if constexpr (EXACT) {
         if (wside && lane < size) {

@@ -38,13 +38,13 @@ template <int KP> uint32_t fused_row_cap_kp(uint32_t max_row) {
 template <int KP, int VAR>
 int launch_fused_zr(fmx_handle h, const Slot& s, const Hyper& hy, uint64_t row0, uint32_t n_rows, hipStream_t st,
                     const double* w0_in, float* rest_out, const uint64_t* cmask = nullptr, float* S_out = nullptr,
-                    float* mult_out = nullptr, uint32_t* handoff_err = nullptr, bool keep_wside = false) {
+                    float* mult_out = nullptr, uint32_t* handoff_err = nullptr, bool keep_wside = false, const WTrain wt = WTrain()) {
 #define FMX_LAUNCH_ZR(ZRV)                                                                                  \
   if constexpr (fused_zr_ok<KP>(ZRV)) {                                                                     \
     FMX_LAUNCH_WAVES((k_fused<KP, ZRV, VAR>), n_rows, st, s.ent, s.row_ptr, s.target, row0,                 \
                      n_rows, h->tb, hy, w0_in, rest_out, cmask, S_out, mult_out, s.fixed_nnz, handoff_err,                  \
                      (const uint64_t*)(keep_wside ? s.lmask : nullptr), keep_wside ? s.wside : (float*)nullptr,             \
-                     (const uint32_t*)s.ids); }
+                     (const uint32_t*)s.ids, wt); }
   switch (fused_zr_select<KP>(s.max_row)) {
     case 8:  FMX_LAUNCH_ZR(8);  break;
     case 16: FMX_LAUNCH_ZR(16); break;
@@ -719,7 +719,9 @@ int fmx_predict_finish(fmx_handle h, uint32_t n_rows, const float* d_partial, fl
 }
 
 // what an epoch driver reports back to fmx_sgd_epoch
-struct EpochCounts { uint64_t batches = 0, launches = 0, deferred = 0; bool kept_wside = false; };
+// wtrain_fresh (in): the slot's training-side weight stream held the current w when fmx_sgd_epoch was entered; kept_wtrain (out): every
+// batch of the epoch went through the kernel that maintains it
+struct EpochCounts { uint64_t batches = 0, launches = 0, deferred = 0; bool kept_wside = false, wtrain_fresh = false, kept_wtrain = false; };
 
 // MINIBATCH rule, FMX_APPLY_FUSED: per batch ONE pass over the examples (k_fused<FUSED_EXACT>: gather, predict, multiplier,
 // write-back of every feature that occurs once in the batch) + k_apply_seg over the features that occur more than once.
@@ -731,6 +733,7 @@ struct FusedEpoch {
   fmx_handle h; Slot* s; Hyper hy;
   uint32_t B, Bc, d, chunk; uint64_t n_batch;   // batch, min(batch, rows), bias lag, micro-chunk of the recurrence, batches of the epoch
   bool keep, handoff;             // the slot's weight side stream is kept (FMX_FLAG_KEEP_WSIDE); side stream: device-side hand-off (else events)
+  WTrain wt;                      // the slot's training-side weight stream (w == nullptr: none; read: it holds the current w)
   double* W; unsigned long long hbase;   // hand-off: bias slots W[0 .. n_batch], the completion counter's value before this epoch
   int szr, small_cap;             // one launch: row slots of the k_small_one instance; workgroups of it the device holds (0: not asked yet)
   unsigned long long* small_trace;
@@ -808,7 +811,7 @@ static int fused_examples(const FusedEpoch& E, uint64_t b, const double* w0_in, 
   float* mult = h->mult + (size_t)(b & 1) * E.Bc;
   int rc = FMX_OK;
   KP_SWITCH(h->KP, { rc = launch_fused_zr<KP, FUSED_EXACT>(h, s, E.hy, b * E.B, rows_of_batch(E, b), h->stream, w0_in, rest, s.cmask, S, mult,
-                                                             E.handoff ? h->handoff_err : nullptr, E.keep); });
+                                                             E.handoff ? h->handoff_err : nullptr, E.keep, E.wt); });
   if (rc) return rc;
   HIPCHK(h, hipGetLastError());
   *sw = seg_work(h, s, (size_t)b, S, mult);
@@ -881,6 +884,9 @@ static int sgd_epoch_fused(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, cons
   const bool keep_wside = (opts->flags & FMX_FLAG_KEEP_WSIDE) && hy.k1 && h->cfg.shard_world == 1 && s.blocks.empty();
   if (keep_wside) { rc = ensure_wside(h, s); if (rc) return rc; }
   n->kept_wside = E.keep = keep_wside && s.wside != nullptr;
+  // the slot's training-side weight stream (WTrain): the linear weights of its once-only features, kept by this epoch whatever its flags
+  const bool wtrain_ok = hy.k1 && !hy.sgda && h->cfg.shard_world == 1 && s.blocks.empty() && !s.weight;
+  if (wtrain_ok) { rc = ensure_wtrain(h, s, s.fused_cap); if (rc) return rc; }
   const uint32_t Bc = E.Bc = std::min<uint32_t>(B, s.n_rows);
   rc = ensure_scratch(h, (size_t)Bc * 2, (size_t)Bc * (d + 1)); if (rc) return rc;   // S / mult of two consecutive batches, d (+ 1: hand-off) rest buffers
   const uint64_t n_batch = E.n_batch = ((uint64_t)s.n_rows + B - 1) / B;
@@ -912,6 +918,12 @@ static int sgd_epoch_fused(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, cons
     HIPCHK(h, hipMemcpyAsync(E.W, h->w0, sizeof(double), hipMemcpyDeviceToDevice, st));
   }
   const bool small_one = !side && h->small_one && (h->KP == 8 || h->KP == 16 || h->KP == 32 || h->KP == 64 || h->KP == 128) && s.cdesc && Bc <= SMALL_ONE_MAX && !hy.sgda;
+  // the singles' linear weights from their packed stream (k_fused<FUSED_EXACT> alone maintains it: not the one-launch form)
+  if (wtrain_ok && !small_one && s.wtrain) {
+    E.wt = WTrain{s.smask, s.soff, s.wtrain, n->wtrain_fresh ? 1u : 0u};
+    n->kept_wtrain = true;
+    if (E.wt.read) h->run_status |= FMX_STAT_WSTREAM;
+  }
   if (small_one) {
     if (h->KP < 64) E.szr = h->KP;                                // (k <= 32: 64 / KP entries per row slot, KP slots hold any row of <= 64 entries)
     else {
@@ -1250,6 +1262,7 @@ static int epoch_close(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, const fm
                               "events from now on", e);
   }
   if (n.kept_wside) s.wside_version = h->w_version;          // the epoch is complete: the stream holds this w
+  if (n.kept_wtrain) s.wtrain_version = h->w_version;        // ... and so does the training-side one
   if (stats) {
     float ms = 0;
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -1316,9 +1329,10 @@ int fmx_sgd_epoch(fmx_handle h, int slot, const fmx_sgd_opts* opts, fmx_epoch_st
       return fail(h, FMX_E_ARG, "HOGWILD on these rows: learn_rate * curvature * %u rows in flight * collision mass = %.3g > 2 -- the asynchronous "
                                 "step diverges (collision mass %.4g; use FMX_SGD_MINIBATCH with batch 0)", in_flight, bi.batch_gain, bi.collision_mass);
   }
+  EpochCounts n;
+  n.wtrain_fresh = s.wtrain && s.wtrain_version == h->w_version;   // (decided on the w this epoch starts from)
   touch_w(h);                                                // (every side stream is stale from here on; this epoch may re-validate ITS slot's)
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  EpochCounts n;
   switch (opts->mode) {
     case FMX_SGD_SEQUENTIAL: rc = epoch_sequential(h, s, hy, &n); break;
     case FMX_SGD_HOGWILD:    rc = epoch_hogwild(h, s, opts, hy, &n); break;

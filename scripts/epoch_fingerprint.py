@@ -5,7 +5,7 @@ is meant to move no number must leave every line as it was (FMX_STAT_EVENT_SYNC 
 bit says how the device scheduled the handle's two streams).
     python scripts/epoch_fingerprint.py [--only NAME ...] > profiles/epoch_fingerprint_<tag>.jsonl
     python scripts/epoch_fingerprint.py --compare BEFORE.jsonl AFTER.jsonl      (no device needed)
---compare: every line equal; where a build did not reproduce its own hash, that configuration is held to its counts and status only."""
+--compare: every line equal (FMX_STAT_WSTREAM aside: it says where the once-only features' linear weights were read from); where a build did not reproduce its own hash, that configuration is held to its counts and status only."""
 import hashlib
 import json
 import os
@@ -18,6 +18,8 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 import schedule_routes as R          # noqa: E402
+
+STAT_WSTREAM = 131072                # FMX_STAT_WSTREAM (include/fmx.h): set from a slot's second one-pass epoch on, FMX_WTRAIN=0 aside
 
 
 def digest(params):
@@ -32,6 +34,8 @@ def compare(before, after):
     a, b = ([json.loads(l) for l in open(f) if l.strip()] for f in (before, after))
     bad = len(a) != len(b)
     for x, y in zip(a, b):
+        for z in (x, y):                              # (where the singles' linear weights were read from moves no number: not the route's)
+            z["status"] = int(z["status"]) & ~STAT_WSTREAM
         if not (x.get("reproducible", True) and y.get("reproducible", True)):
             print("counts only (a build did not reproduce its own hash): %s" % x["config"])
             x, y = ({k: v for k, v in z.items() if k not in ("sha256", "reproducible")} for z in (x, y))
