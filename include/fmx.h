@@ -1322,6 +1322,60 @@ int fmx_compact_end(fmx_handle h);
  * fmx_compact_info::bytes_compact says so), P for int8 (which does not depend on the stride), 0 for an unknown format or num_factor < 0 */
 uint32_t fmx_compact_row_bytes(uint32_t format, int num_factor);
 
+/* ---- exact binary checkpoints of the model and the optimizer state (no counterpart in the reference) -------
+ * fmx_save_model / fmx_load_model speak the reference's text format: six significant digits per number, and nothing of an open
+ * AdaGrad or FTRL session.  A checkpoint is the other file: w0 in fp64, w and V in fp32 without the row padding and, if an
+ * fmx_adapt or fmx_ftrl session is open, that session's constants and tables -- written straight from the device tables and read
+ * straight back into them, bit for bit.  The stateful epochs are deterministic, so "train 2 epochs" and "train 1, save, new
+ * process, load, train 1" give the same bits.  The byte layout is csrc/fmx_ckpt_format.h (restated by libfm_amd/checkpoint.py).
+ * Added without an ABI version change: a caller detects the feature by the symbol fmx_checkpoint_save.
+ *
+ *   fmx_checkpoint_save : brings the model up to date (as fmx_save_model), synchronises, then streams the sections through two pinned
+ *                         buffers.  Writes to `path` + ".tmp" and renames, so a file at `path` is never a partial one; on failure
+ *                         the .tmp file is removed.  The file holds no time stamp, host name or pointer: equal state and equal flags
+ *                         give byte-identical files.  With a session the state is SPARSE by default: the file holds the state rows of
+ *                         the features whose row fmx_*_begin would NOT reproduce from the file's own parameters (AdaGrad: n_w or one
+ *                         of the num_factor n_v differs from init_acc; FTRL: some (z, n) differs from the start state of its
+ *                         parameter), as an ascending id list and one (1 + num_factor)-float row per id and table (the linear
+ *                         coordinate first).  FMX_CKPT_DENSE_STATE writes every feature's rows and no id list.  Both forms load to
+ *                         the same bits.  Without k1 the file holds no w and the criterion reads the handle's w table as it is.
+ *   fmx_checkpoint_load : the geometry (num_attribute, num_factor, k0, k1) must equal the handle's.  w0, w (with k1) and V are
+ *                         replaced bit for bit, the padding of a V row is left +0, and whatever is derived from the parameters is
+ *                         invalidated as fmx_load_model does it.  An open serving snapshot is a frozen copy and is untouched.
+ *                         A file WITH a session, without FMX_CKPT_MODEL_ONLY: any open fmx_adapt / fmx_ftrl session is replaced by
+ *                         the file's (the tables are reused when the kind matches, otherwise freed and allocated); its constants are
+ *                         the fp32 values the saved session used, not re-derived from doubles; its tables are the start state of the
+ *                         loaded parameters with the stored rows scattered over it -- the saved state on every coordinate.
+ *                         A file WITHOUT a session leaves an open session alone, as fmx_load_model does.
+ *   fmx_checkpoint_info : the header alone: no handle, no device.  Fills info (seconds = 0) or returns FMX_E_ARG with the reason in
+ *                         err (truncated to err_len; may be NULL).
+ *
+ * Refusals that change nothing, each decided from the header, its section table and the file's length before the first byte
+ * reaches the device; the handle stays usable.  FMX_E_ARG: NULL path, unknown flags, a file that cannot be opened or created, bad
+ * magic or version, a header whose checksum fails, a geometry mismatch (the message names the field and both values), section
+ * sizes that do not add up to the file's length (truncation), state_rows > num_attribute.  FMX_E_STATE: a load during an open SGDA
+ * or ALS / MCMC session.  FMX_E_UNSUPPORTED: a feature shard or communicator rank.
+ * Found while streaming: a section whose checksum -- computed over what ARRIVED IN DEVICE MEMORY, so it covers file, host and
+ * device -- does not match, or an id list that is not strictly ascending or holds an id >= num_attribute (checked on the device
+ * before any row is scattered).  FMX_E_ARG naming the section; the parameters are then unspecified and any fmx_adapt / fmx_ftrl
+ * session is closed, as the message says; the handle stays usable (fmx_set_params, or load again).
+ * Checksum of a section: pad it with zero bytes to a multiple of 8; the sum mod 2^64, over its little-endian 8-byte words u_i, of
+ * mix64(u_i ^ (i * 0x9E3779B97F4A7C15)), mix64 being the finaliser x ^= x >> 30, x *= 0xBF58476D1CE4E5B9, x ^= x >> 27,
+ * x *= 0x94D049BB133111EB, x ^= x >> 31. */
+#define FMX_CKPT_DENSE_STATE 1u   /* save: write every feature's state rows, not only those that differ from the start state */
+#define FMX_CKPT_MODEL_ONLY  2u   /* save: write no session even if one is open; load: ignore the file's session, leave the handle's alone */
+typedef struct fmx_ckpt_opts { uint32_t flags; uint32_t reserved; } fmx_ckpt_opts;      /* NULL = no flags */
+typedef struct fmx_ckpt_info {
+  uint32_t version, session;          /* session: 0 none, 1 AdaGrad, 2 FTRL */
+  uint64_t num_attribute; uint32_t num_factor, k0, k1, flags;
+  uint64_t state_rows;                /* rows of state in the file (= num_attribute when dense) */
+  uint64_t bytes;                     /* file size */
+  double   seconds, device_seconds;   /* whole call / kernels and copies */
+} fmx_ckpt_info;
+int fmx_checkpoint_save(fmx_handle h, const char *path, const fmx_ckpt_opts *opts, fmx_ckpt_info *info /* may be NULL */);
+int fmx_checkpoint_load(fmx_handle h, const char *path, const fmx_ckpt_opts *opts, fmx_ckpt_info *info /* may be NULL */);
+int fmx_checkpoint_info(const char *path, fmx_ckpt_info *info, char *err, size_t err_len);   /* header only; no handle, no GPU */
+
 /* ---- introspection --------------------------------------------------------------------------- */
 typedef struct fmx_info {
   uint64_t n_local;         /* features held by this handle */

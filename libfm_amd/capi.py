@@ -99,6 +99,20 @@ class CompactInfo(C.Structure):                    # fmx_compact_info
                 ("max_abs_err", C.c_double), ("sum_sq_err", C.c_double)]
 
 
+CKPT_DENSE_STATE, CKPT_MODEL_ONLY = 1, 2   # FMX_CKPT_*: fmx_ckpt_opts::flags
+CKPT_SESSIONS = ("none", "adagrad", "ftrl")   # fmx_ckpt_info::session
+
+
+class CkptOpts(C.Structure):                       # fmx_ckpt_opts
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CkptInfo(C.Structure):                       # fmx_ckpt_info
+    _fields_ = [("version", C.c_uint32), ("session", C.c_uint32), ("num_attribute", C.c_uint64), ("num_factor", C.c_uint32),
+                ("k0", C.c_uint32), ("k1", C.c_uint32), ("flags", C.c_uint32), ("state_rows", C.c_uint64), ("bytes", C.c_uint64),
+                ("seconds", C.c_double), ("device_seconds", C.c_double)]
+
+
 class BatchInfo(C.Structure):
     _fields_ = [("collision_mass", C.c_double), ("batch_gain", C.c_double), ("batch", C.c_uint32), ("status", C.c_uint32)]
 
@@ -347,6 +361,9 @@ SYMBOLS = [
     ("fmx_compact_get_rows", C.c_int, [H, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("fmx_compact_end", C.c_int, [H]),
     ("fmx_compact_row_bytes", C.c_uint32, [C.c_uint32, C.c_int]),
+    ("fmx_checkpoint_save", C.c_int, [H, C.c_char_p, C.POINTER(CkptOpts), C.POINTER(CkptInfo)]),
+    ("fmx_checkpoint_load", C.c_int, [H, C.c_char_p, C.POINTER(CkptOpts), C.POINTER(CkptInfo)]),
+    ("fmx_checkpoint_info", C.c_int, [C.c_char_p, C.POINTER(CkptInfo), C.c_char_p, C.c_size_t]),
     ("fmx_als_begin", C.c_int, [H, C.c_int]),
     ("fmx_als_moments", C.c_int, [H, C.c_void_p]),
     ("fmx_als_sweep", C.c_int, [H, C.POINTER(AlsOpts), C.POINTER(AlsStats)]),
@@ -562,6 +579,18 @@ class Handle:
     def load_model(self, path):
         """fm_model::loadModel (fm_model.h:160-190); raises FmxError "malformed model file" where the reference returns 0"""
         self._chk(self.lib.fmx_load_model(self.h, os.fsencode(path)))
+
+    def checkpoint_save(self, path, dense=False, model_only=False):
+        """the exact binary checkpoint of the model and the open AdaGrad / FTRL session (fmx_checkpoint_save); returns CkptInfo"""
+        opts, info = CkptOpts((CKPT_DENSE_STATE if dense else 0) | (CKPT_MODEL_ONLY if model_only else 0), 0), CkptInfo()
+        self._chk(self.lib.fmx_checkpoint_save(self.h, os.fsencode(path), C.byref(opts), C.byref(info)))
+        return info
+
+    def checkpoint_load(self, path, model_only=False):
+        """replace the parameters, and unless model_only the session, by a checkpoint's (fmx_checkpoint_load); returns CkptInfo"""
+        opts, info = CkptOpts(CKPT_MODEL_ONLY if model_only else 0, 0), CkptInfo()
+        self._chk(self.lib.fmx_checkpoint_load(self.h, os.fsencode(path), C.byref(opts), C.byref(info)))
+        return info
 
     def get_w0(self):
         w0 = C.c_double(0)
@@ -1060,6 +1089,15 @@ class Handle:
 
     def synchronize(self):
         self._chk(self.lib.fmx_synchronize(self.h))
+
+
+def checkpoint_info(path):
+    """the header of a checkpoint file (fmx_checkpoint_info: no handle, no device); raises FmxError with the parser's reason"""
+    info, err = CkptInfo(), C.create_string_buffer(256)
+    rc = load().fmx_checkpoint_info(os.fsencode(path), C.byref(info), err, len(err))
+    if rc:
+        raise FmxError(rc, err.value.decode())
+    return info
 
 
 def release_cached_memory():

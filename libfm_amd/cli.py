@@ -50,6 +50,12 @@ the row's weight (fmx_set_row_weights): the epochs scale every train row's loss 
 negatives, each kept one weighing 1 / rate.  -metrics then also knows wlogloss, the weighted log loss of the sets that have weights
 (fmx_evaluate_weighted; nan for a set without), as "#Iter=  i\twlogloss: Train=..\tTest=.." on stderr and wlogloss_* in -rlog.
 Any other method or optimizer refuses the flags: it has no weighted form.
+-save_checkpoint F [-checkpoint_dense 1] / -load_checkpoint F (-method sgd and -method bpr, any -optimizer): the exact binary
+checkpoint of the model and of the adagrad / ftrl session (fmx_checkpoint_save / _load; libfm_amd/checkpoint.py reads the file).
+-load_checkpoint takes the place of the random initialisation and of -load_model (giving both is an error) and, when the file holds
+a session, of the -optimizer options: training continues bit for bit where the saving run stopped.  -save_checkpoint writes the
+file after training (-checkpoint_dense 1: every feature's state rows, not only those that differ from the start state).  Each
+prints one "checkpoint" line on stderr: session, state rows, bytes, seconds.  Any other method refuses the flags.
 -serve bf16 (sgd, sgda, bpr, als): after training a frozen bf16 copy of the model is taken on the device (fmx_compact_begin) and the
 -out predictions and the -topk lists come from it.  One "compact" line on stderr carries the copy's bytes next to the fp32 tables',
 max_abs_err and nonfinite of the rounding, and the test metric -- with -metrics each named metric too -- from fp32 and from bf16 side
@@ -105,7 +111,16 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "train_weights": "filename with one weight (float >= 0) per train row: -method sgd with -optimizer adagrad | ftrl scales every"
                           " row's loss by it; -metrics then knows wlogloss",
          "test_weights": "the same for the test rows (read by -metrics wlogloss only); needs -train_weights",
+         "save_checkpoint": "sgd, bpr: filename for the exact binary checkpoint (model + adagrad / ftrl session) written after training",
+         "checkpoint_dense": "with -save_checkpoint: 1 = write every feature's state rows; default=0 (only rows that differ from the start state)",
+         "load_checkpoint": "sgd, bpr: filename of a checkpoint to continue from (instead of the random initialisation; not with -load_model)",
          "serve": "bf16 | int8: score -out, -metrics and -topk after training from a frozen bf16 or row-wise int8 copy of the model; sgd, sgda, bpr, als"}
+
+
+def checkpoint_line(what, info):
+    """the one stderr line of -save_checkpoint / -load_checkpoint (capi.CkptInfo)"""
+    return "checkpoint\t%s\tsession=%s\tstate_rows=%d\tbytes=%d\tseconds=%.3g" % (
+        what, L.capi.CKPT_SESSIONS[info.session], info.state_rows, info.bytes, info.seconds)
 
 
 def read_pairs(path, n_rows):
@@ -333,6 +348,18 @@ def _main(argv):
             raise ValueError("-test_weights needs -train_weights" if "train_weights" not in a else "-train_weights needs a filename")
         if "test_weights" in a and not a["test_weights"]:
             raise ValueError("-test_weights needs a filename")
+    if any(f in a for f in ("save_checkpoint", "load_checkpoint", "checkpoint_dense")):
+        if method not in ("sgd", "bpr"):
+            raise ValueError("-save_checkpoint / -load_checkpoint belong to -method sgd and -method bpr: -method %s has no checkpoint" % method)
+        for f in ("save_checkpoint", "load_checkpoint"):
+            if f in a and not a[f]:
+                raise ValueError("-%s needs a filename" % f)
+        if "load_checkpoint" in a and "load_model" in a:
+            raise ValueError("-load_checkpoint replaces -load_model: give one of them")
+        if a.get("checkpoint_dense", "0") not in ("0", "1"):
+            raise ValueError("-checkpoint_dense takes 0 or 1")
+        if "checkpoint_dense" in a and "save_checkpoint" not in a:
+            raise ValueError("-checkpoint_dense needs -save_checkpoint")
     metrics = tuple(split_list(a.get("metrics", "")))
     if "metrics" in a:
         for m in metrics:
@@ -534,7 +561,12 @@ def _main(argv):
         l.extra_metrics = metrics
     if dev_avg:
         l.device_average = True
+    if "load_checkpoint" in a:
+        l.load_checkpoint(a["load_checkpoint"])
     l.init()
+    if "load_checkpoint" in a:
+        optimizer = l.optimizer                                 # (a file with a session names it)
+        print(checkpoint_line("load", L.capi.checkpoint_info(a["load_checkpoint"])), file=sys.stderr)
     if test_queries is not None:
         l.set_queries(test, test_queries)
     if train_queries is not None:
@@ -604,6 +636,8 @@ def _main(argv):
     if "save_model" in a and a["save_model"]:
         print("Writing FM model to " + a["save_model"])
         fm.save_model(a["save_model"])
+    if "save_checkpoint" in a:
+        print(checkpoint_line("save", l.save_checkpoint(a["save_checkpoint"], dense=a.get("checkpoint_dense", "0") == "1")), file=sys.stderr)
     if want_topk:
         topk = int(a["topk"])
         if cand is None:

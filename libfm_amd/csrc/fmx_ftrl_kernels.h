@@ -60,13 +60,18 @@ k_ftrl_apply_seg(const SegWork sw, const Tab tb, const FtrlRule rule, Hyper h) {
 // the start state (fmx_ftrl_begin): n = init_acc and z0 = -theta0 D0 - sgn(theta0) l1 with D0 = (beta + sqrt(init_acc)) / alpha + l2, the z
 // at which the closed form returns theta0; theta0 = 0 (padding included) gives z0 = 0.  `count` elements of stride 1 (the whole V
 // table, padding included) or `count` linear weights `tstride` floats apart.
+// One coordinate's z0 is ftrl_start: the checkpoint's sparse criterion (k_ckpt_flag_ftrl, fmx_ckpt_kernels.h) asks whether a stored
+// z is still this value, bit for bit, so both call the one function.
+__device__ __forceinline__ float ftrl_start(float t, float D0, float l1) {
+  const float sg = (t > 0.f) ? l1 : (t < 0.f) ? -l1 : 0.f;
+  return -t * D0 - sg;
+}
+
 static __global__ void __launch_bounds__(256) k_ftrl_init(const float* __restrict__ theta, size_t tstride, float* __restrict__ z,
                                                           float* __restrict__ n, uint64_t count, float D0, float l1, float init_acc) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
-    const float t = theta[i * tstride];
-    const float sg = (t > 0.f) ? l1 : (t < 0.f) ? -l1 : 0.f;
-    z[i] = -t * D0 - sg;
+    z[i] = ftrl_start(theta[i * tstride], D0, l1);
     n[i] = init_acc;
   }
 }

@@ -1,5 +1,6 @@
 // fmx_internal.h -- shared by the translation units of libfmx.so (fmx_core.hip, fmx_sgd.hip, fmx_als.hip, fmx_comm.hip, fmx_pair.hip, fmx_topk.hip,
-// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip, fmx_weighted.hip; fmx_io.hip needs none of it).
+// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip, fmx_weighted.hip, fmx_ckpt.hip; fmx_io.hip needs
+// none of it).
 // The C-ABI is include/fmx.h; nothing declared here is exported.
 #pragma once
 #pragma GCC visibility push(default)      // the C-ABI is the only thing libfmx.so exports (-fvisibility=hidden)
@@ -171,10 +172,13 @@ struct LagState {                 // FMX_FLAG_BIAS_LAG bookkeeping (split step):
 struct SgdaState { float* gw = nullptr; float* gv = nullptr; double* reg = nullptr; double* dreg = nullptr;   // dreg: [workgroups][G][1 + KP] partial lambda changes
                    size_t dreg_cap = 0; };
 // an open fmx_adapt_* session (fmx_sgd.hip): the per-coordinate accumulators, n_v with V's row stride
-struct AdaptState { float* nw = nullptr; float* nv = nullptr; float eta = 0.f; };
+// (init_acc: the fp32 start value of every accumulator, kept for the checkpoint's sparse criterion and its load)
+struct AdaptState { float* nw = nullptr; float* nv = nullptr; float eta = 0.f; float init_acc = 0.f; };
 // an open fmx_ftrl_* session (fmx_sgd.hip): z and n per coordinate, the row tables with V's row stride, and the rule's constants
 struct FtrlState { float* zw = nullptr; float* zv = nullptr; float* nw = nullptr; float* nv = nullptr;
-                   float inv_alpha = 0.f, beta = 0.f, l1_w = 0.f, l1_v = 0.f, l2_w = 0.f, l2_v = 0.f; };
+                   float inv_alpha = 0.f, beta = 0.f, l1_w = 0.f, l1_v = 0.f, l2_w = 0.f, l2_v = 0.f, init_acc = 0.f;
+                   // the start denominator D0 of a coordinate with this l2, as fmx_ftrl_begin computes it (base + l2, all fp32)
+                   float start_D(float l2) const { const float base = (beta + sqrtf(init_acc)) * inv_alpha; return base + l2; } };
 // the serving snapshot (fmx_compact_*, fmx_compact.hip): a frozen copy of w0 and, by format,
 //   FMX_COMPACT_BF16  w (fp32, stride 1) and V as bf16 rows of tb.rs elements
 //   FMX_COMPACT_INT8  B: one block of P bytes per feature with its scale, its w and its int8 codes (V and w stay null)
@@ -373,6 +377,14 @@ int pair_rule_check_mode(fmx_handle h, PairRule r, int mode, const char* what);
 int pair_rule_check_session(fmx_handle h, PairRule r, const char* what);
 void adapt_free(fmx_handle h);                                           // fmx_sgd.hip
 void ftrl_free(fmx_handle h);                                            // fmx_sgd.hip
+// fmx_sgd.hip, shared by fmx_adapt_begin / fmx_ftrl_begin and fmx_checkpoint_load (fmx_ckpt.hip): the session's tables (allocated
+// where they are not there yet; on failure the session is closed) and its start state from the constants ALREADY in h->adapt /
+// h->ftrl -- every accumulator = init_acc, and for FTRL z derived from the current parameters (k_ftrl_init).  Launches on h->stream;
+// the caller synchronises.
+int adapt_tables(fmx_handle h, const char* who);
+int adapt_start_state(fmx_handle h);
+int ftrl_tables(fmx_handle h, const char* who);
+int ftrl_start_state(fmx_handle h);
 void als_free(fmx_handle h);                                             // fmx_als.hip
 enum { GROUP_SINGLE = 0, GROUP_LOOPBACK = 1, GROUP_RCCL = 2 };
 struct fmx_group_s {                      // fmx_comm.hip

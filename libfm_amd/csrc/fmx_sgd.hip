@@ -1545,6 +1545,23 @@ static int adapt_check_handle(fmx_handle h, const char* what) {
   return FMX_OK;
 }
 
+extern "C++" int adapt_tables(fmx_handle h, const char* who) {
+  if (h->adapt.nv) return FMX_OK;
+  const size_t nv = h->n_local * (size_t)h->tb.rs;
+  HIPCHK(h, fmx_dev_alloc(&h->adapt.nw, h->n_local * sizeof(float)));
+  hipError_t e = fmx_dev_alloc(&h->adapt.nv, nv * sizeof(float));
+  if (e != hipSuccess) { adapt_free(h); return fail(h, FMX_E_HIP, "%s: the accumulator table (%zu bytes): %s", who, nv * sizeof(float), hipGetErrorString(e)); }
+  return FMX_OK;
+}
+
+extern "C++" int adapt_start_state(fmx_handle h) {
+  const size_t nv = h->n_local * (size_t)h->tb.rs;
+  hipLaunchKernelGGL(k_adapt_fill, dim3((unsigned)std::min<size_t>((h->n_local + 255) / 256, 2048)), dim3(256), 0, h->stream, h->adapt.nw, (uint64_t)h->n_local, h->adapt.init_acc);
+  hipLaunchKernelGGL(k_adapt_fill, dim3((unsigned)std::min<size_t>((nv + 255) / 256, 2048)), dim3(256), 0, h->stream, h->adapt.nv, (uint64_t)nv, h->adapt.init_acc);
+  HIPCHK(h, hipGetLastError());
+  return FMX_OK;
+}
+
 int fmx_adapt_begin(fmx_handle h, const fmx_adapt_opts* opts) {
   if (!h) return FMX_E_ARG;
   if (!opts) return fail(h, FMX_E_ARG, "fmx_adapt_begin: opts is NULL");
@@ -1559,16 +1576,10 @@ int fmx_adapt_begin(fmx_handle h, const fmx_adapt_opts* opts) {
   if (!(init_acc > 0.f) || std::isinf(init_acc)) return fail(h, FMX_E_ARG, "fmx_adapt_begin: init_acc %g is not a positive fp32 number", opts->init_acc);
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  const size_t nv = h->n_local * (size_t)h->tb.rs;
-  if (!h->adapt.nv) {                                           // (again = reset: the tables are there)
-    HIPCHK(h, fmx_dev_alloc(&h->adapt.nw, h->n_local * sizeof(float)));
-    hipError_t e = fmx_dev_alloc(&h->adapt.nv, nv * sizeof(float));
-    if (e != hipSuccess) { adapt_free(h); return fail(h, FMX_E_HIP, "fmx_adapt_begin: the accumulator table (%zu bytes): %s", nv * sizeof(float), hipGetErrorString(e)); }
-  }
+  rc = adapt_tables(h, "fmx_adapt_begin"); if (rc) return rc;   // (again = reset: the tables are there)
   h->adapt.eta = (float)(opts->learn_rate > 0.0 ? opts->learn_rate : h->cfg.learn_rate);
-  hipLaunchKernelGGL(k_adapt_fill, dim3((unsigned)std::min<size_t>((h->n_local + 255) / 256, 2048)), dim3(256), 0, h->stream, h->adapt.nw, (uint64_t)h->n_local, init_acc);
-  hipLaunchKernelGGL(k_adapt_fill, dim3((unsigned)std::min<size_t>((nv + 255) / 256, 2048)), dim3(256), 0, h->stream, h->adapt.nv, (uint64_t)nv, init_acc);
-  HIPCHK(h, hipGetLastError());
+  h->adapt.init_acc = init_acc;
+  rc = adapt_start_state(h); if (rc) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return FMX_OK;
 }
@@ -1705,6 +1716,28 @@ extern "C++" void ftrl_free(fmx_handle h) {
 
 static bool ftrl_value_ok(double x) { return x >= 0.0 && !std::isinf(x); }                  // (NaN fails the comparison)
 
+extern "C++" int ftrl_tables(fmx_handle h, const char* who) {
+  if (h->ftrl.nv) return FMX_OK;
+  const size_t nv = h->n_local * (size_t)h->tb.rs, nw = h->n_local;
+  hipError_t e = fmx_dev_alloc(&h->ftrl.zw, nw * sizeof(float));
+  if (e == hipSuccess) e = fmx_dev_alloc(&h->ftrl.nw, nw * sizeof(float));
+  if (e == hipSuccess) e = fmx_dev_alloc(&h->ftrl.zv, nv * sizeof(float));
+  if (e == hipSuccess) e = fmx_dev_alloc(&h->ftrl.nv, nv * sizeof(float));
+  if (e != hipSuccess) { ftrl_free(h); return fail(h, FMX_E_HIP, "%s: the z and n tables (%zu bytes): %s", who, 2 * (nv + nw) * sizeof(float), hipGetErrorString(e)); }
+  return FMX_OK;
+}
+
+extern "C++" int ftrl_start_state(fmx_handle h) {
+  const FtrlState& f = h->ftrl;
+  const size_t nv = h->n_local * (size_t)h->tb.rs, nw = h->n_local;
+  hipLaunchKernelGGL(k_ftrl_init, dim3((unsigned)std::min<size_t>((nw + 255) / 256, 2048)), dim3(256), 0, h->stream, (const float*)h->tb.w, (size_t)h->tb.ws,
+                     f.zw, f.nw, (uint64_t)nw, f.start_D(f.l2_w), f.l1_w, f.init_acc);
+  hipLaunchKernelGGL(k_ftrl_init, dim3((unsigned)std::min<size_t>((nv + 255) / 256, 2048)), dim3(256), 0, h->stream, (const float*)h->tb.V, (size_t)1,
+                     f.zv, f.nv, (uint64_t)nv, f.start_D(f.l2_v), f.l1_v, f.init_acc);
+  HIPCHK(h, hipGetLastError());
+  return FMX_OK;
+}
+
 int fmx_ftrl_begin(fmx_handle h, const fmx_ftrl_opts* opts) {
   if (!h) return FMX_E_ARG;
   if (!opts) return fail(h, FMX_E_ARG, "fmx_ftrl_begin: opts is NULL");
@@ -1720,8 +1753,8 @@ int fmx_ftrl_begin(fmx_handle h, const fmx_ftrl_opts* opts) {
   FtrlState f;
   f.inv_alpha = inv_alpha; f.beta = (float)opts->beta;
   f.l1_w = (float)opts->l1_w; f.l1_v = (float)opts->l1_v; f.l2_w = (float)opts->l2_w; f.l2_v = (float)opts->l2_v;
-  const float init_acc = (float)opts->init_acc;
-  const float base = (f.beta + sqrtf(init_acc)) * inv_alpha;
+  const float init_acc = f.init_acc = (float)opts->init_acc;
+  const float base = (f.beta + sqrtf(init_acc)) * inv_alpha;     // (FtrlState::start_D is this expression + l2)
   if (std::isinf(f.beta) || std::isinf(f.l1_w) || std::isinf(f.l1_v) || std::isinf(init_acc) || std::isinf(base + f.l2_w) || std::isinf(base + f.l2_v) ||
       !(base + f.l2_w > 0.f) || !(base + f.l2_v > 0.f))
     return fail(h, FMX_E_ARG, "fmx_ftrl_begin: the options leave the fp32 range ((beta + sqrt(init_acc)) / alpha + l2 = %g)", (double)(base + f.l2_v));
@@ -1731,21 +1764,10 @@ int fmx_ftrl_begin(fmx_handle h, const fmx_ftrl_opts* opts) {
   { int _rc = lag_flush(h); if (_rc) return _rc; }              // (z is derived from the parameters: they have to be current)
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  const size_t nv = h->n_local * (size_t)h->tb.rs, nw = h->n_local;
-  if (!h->ftrl.nv) {                                            // (again = reset: the tables are there)
-    hipError_t e = fmx_dev_alloc(&h->ftrl.zw, nw * sizeof(float));
-    if (e == hipSuccess) e = fmx_dev_alloc(&h->ftrl.nw, nw * sizeof(float));
-    if (e == hipSuccess) e = fmx_dev_alloc(&h->ftrl.zv, nv * sizeof(float));
-    if (e == hipSuccess) e = fmx_dev_alloc(&h->ftrl.nv, nv * sizeof(float));
-    if (e != hipSuccess) { ftrl_free(h); return fail(h, FMX_E_HIP, "fmx_ftrl_begin: the z and n tables (%zu bytes): %s", 2 * (nv + nw) * sizeof(float), hipGetErrorString(e)); }
-  }
+  rc = ftrl_tables(h, "fmx_ftrl_begin"); if (rc) return rc;     // (again = reset: the tables are there)
   f.zw = h->ftrl.zw; f.zv = h->ftrl.zv; f.nw = h->ftrl.nw; f.nv = h->ftrl.nv;
   h->ftrl = f;
-  hipLaunchKernelGGL(k_ftrl_init, dim3((unsigned)std::min<size_t>((nw + 255) / 256, 2048)), dim3(256), 0, h->stream, (const float*)h->tb.w, (size_t)h->tb.ws,
-                     f.zw, f.nw, (uint64_t)nw, base + f.l2_w, f.l1_w, init_acc);
-  hipLaunchKernelGGL(k_ftrl_init, dim3((unsigned)std::min<size_t>((nv + 255) / 256, 2048)), dim3(256), 0, h->stream, (const float*)h->tb.V, (size_t)1,
-                     f.zv, f.nv, (uint64_t)nv, base + f.l2_v, f.l1_v, init_acc);
-  HIPCHK(h, hipGetLastError());
+  rc = ftrl_start_state(h); if (rc) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return FMX_OK;
 }

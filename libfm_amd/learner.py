@@ -265,6 +265,7 @@ class FMLearnSGD:
         self.rank_cutoffs = ()                                  # with query ids: ndcg / recall / precision at these K per iteration
         self._adapt_open = False
         self._ftrl_open = False
+        self._checkpoint = None                                 # load_checkpoint before init(): the file init() starts from
 
     def _check_optimizer(self):
         if self.optimizer not in self.OPTIMIZERS:
@@ -284,14 +285,71 @@ class FMLearnSGD:
         fm = self.fm
         self._h = capi.Handle(fm.num_attribute, fm.num_factor, fm.k0, fm.k1, self.task, fm.reg0, fm.regw, fm.regv,
                               self.learn_rate, self.min_target, self.max_target, device=self.device)
-        self._h.set_params(fm.w0, fm.w, fm.v)
-        if self.optimizer == "adagrad":
+        if self._checkpoint is not None:                        # the file's parameters and session, not fm's and a fresh one
+            self._load_checkpoint_now(self._checkpoint)
+        else:
+            self._h.set_params(fm.w0, fm.w, fm.v)
+        self._begin_session()
+
+    def _begin_session(self):
+        """open the optimizer's session unless it is open already (a checkpoint brought it)"""
+        fm = self.fm
+        if self.optimizer == "adagrad" and not self._adapt_open:
             self._h.adapt_begin("adagrad", self.init_acc, self.adapt_learn_rate)
             self._adapt_open = True
-        if self.optimizer == "ftrl":
+        if self.optimizer == "ftrl" and not self._ftrl_open:
             self._h.ftrl_begin(self.ftrl_alpha, self.ftrl_beta, self.l1_w, self.l1_v, fm.regw if self.l2_w is None else self.l2_w,
                                fm.regv if self.l2_v is None else self.l2_v, self.init_acc)
             self._ftrl_open = True
+
+    def save_checkpoint(self, path, dense=False):
+        """the exact binary checkpoint of the model on the device and of the open adagrad / ftrl session (fmx_checkpoint_save;
+        libfm_amd/checkpoint.py reads the file).  dense: every feature's state rows, not only those that differ from the start
+        state.  Returns capi.CkptInfo."""
+        if self._h is None:
+            raise ValueError("save_checkpoint before init()")
+        return self._h.checkpoint_save(path, dense=dense)
+
+    def load_checkpoint(self, path):
+        """continue from a file of save_checkpoint: the parameters are the file's bit for bit, and if it holds a session the
+        learner's optimizer and its constants become the file's (an optimizer other than 'sgd' set by the caller that is not the
+        file's raises ValueError; a file without a session leaves the optimizer alone, and a fresh session starts from the loaded
+        parameters).  Before init() the file is only looked at and init() loads it in place of fm's parameters; after init() it
+        is loaded at once.  Neither init() nor learn() begins the session again."""
+        from . import checkpoint
+        with open(path, "rb") as f:
+            head = checkpoint.read_header(f.read(checkpoint.HEADER_BYTES))
+        kind = checkpoint.SESSION_NAMES[head["session"]]
+        if kind != "none" and self.optimizer not in ("sgd", kind):
+            raise ValueError("load_checkpoint: optimizer is %s but the file's session is %s" % (self.optimizer, kind))
+        if kind != "none" and kind not in self.OPTIMIZERS:
+            raise ValueError("load_checkpoint: the file's session is %s but %s knows %s" % (kind, type(self).__name__, " | ".join(self.OPTIMIZERS)))
+        if self._h is None:
+            self._checkpoint = path
+            if kind != "none":
+                self.optimizer = kind
+            return None
+        return self._load_checkpoint_now(path)
+
+    def _load_checkpoint_now(self, path):
+        from . import checkpoint
+        info = self._h.checkpoint_load(path)
+        self._checkpoint = None
+        if info.session != checkpoint.SESSION_NONE:
+            with open(path, "rb") as f:
+                c = checkpoint.consts_dict(checkpoint.read_header(f.read(checkpoint.HEADER_BYTES)))
+            self.optimizer = checkpoint.SESSION_NAMES[info.session]
+            self._adapt_open, self._ftrl_open = self.optimizer == "adagrad", self.optimizer == "ftrl"
+            self.init_acc = c["init_acc"]
+            if self._adapt_open:
+                self.adapt_learn_rate = c["eta"]
+            else:                                               # (alpha is informational: the session keeps the fp32 reciprocal it was saved with)
+                self.ftrl_alpha, self.ftrl_beta = 1.0 / c["inv_alpha"], c["beta"]
+                self.l1_w, self.l1_v, self.l2_w, self.l2_v = c["l1_w"], c["l1_v"], c["l2_w"], c["l2_v"]
+        else:
+            self._begin_session()
+        self.sync_model()
+        return info
 
     def sparsity(self):
         """how many coordinates of the model on the device are exactly zero (capi.Sparsity, fmx_param_sparsity)"""
