@@ -1322,6 +1322,52 @@ int fmx_compact_end(fmx_handle h);
  * fmx_compact_info::bytes_compact says so), P for int8 (which does not depend on the stride), 0 for an unknown format or num_factor < 0 */
 uint32_t fmx_compact_row_bytes(uint32_t format, int num_factor);
 
+/* ---- a pruned serving snapshot: only the rows that can score ------------------------------------
+ * fmx_compact_begin stores one row per feature id, whatever the model holds there.  fmx_compact_begin_pruned stores a row only for
+ * the features that can contribute to a score, in ascending id order ("slots"), and a rank directory that maps a feature id to its
+ * slot: one 8-byte pair {bits, base} per 32 consecutive ids (bit b of bits: id 32 j + b is kept; base: kept ids below 32 j), so
+ * slot = base + popcount(bits below b) and bytes_directory = 8 * ceil(n_local / 32).  Added without an ABI version change: a caller
+ * detects the feature by the symbol fmx_compact_begin_pruned.
+ *
+ *   dead  : fmx_param_sparsity's dead_features rule -- all num_factor factors == 0.0f (-0 counts, NaN does not) and (w_j == 0.0f or
+ *           k1 == 0); with num_factor = 0 every factor row counts as all zero.
+ *   seen  : the id stands in at least one entry of keep_slot, whatever the value.
+ *   kept  : not dead, and seen when FMX_PRUNE_SEEN is set.
+ *
+ * The snapshot replaces any earlier snapshot of the handle, dense or pruned, and fmx_compact_begin replaces a pruned one; lifetime and
+ * independence from training sessions are those of fmx_compact_begin (keep_slot is read during the call only).  fmx_compact_predict /
+ * _evaluate / _evaluate_ex / _topk / _get_rows / _end work unchanged on it: a dropped feature behaves as a row of +0 with w_j = +0
+ * (fmx_compact_get_rows returns zeros for it), and every score is, bit for bit, the score from the dense snapshot of the model with
+ * the dropped rows set to +0.  fmx_compact_info: bytes_compact = bytes_directory + bytes_rows, bytes_rows = kept *
+ * fmx_compact_row_bytes(format, num_factor) (bf16: the factor rows and the w array both hold `kept` entries); nonfinite, max_abs_err
+ * and sum_sq_err run over the kept rows only.
+ *
+ *   fmx_compact_slot_of : the slot of each of `count` ids, 0xFFFFFFFF for a dropped one.  FMX_E_STATE without a pruned snapshot.
+ *
+ * Refusals, each before any launch, the handle usable afterwards.  FMX_E_ARG: NULL opts, an unknown format, flags without
+ * FMX_PRUNE_DEAD or with unknown bits, reserved != 0, keep_slot != -1 without FMX_PRUNE_SEEN, a keep_slot out of range, an id >=
+ * num_attribute.  FMX_E_STATE: FMX_PRUNE_SEEN with a slot that was never uploaded.  FMX_E_UNSUPPORTED: a feature shard or
+ * communicator rank; a keep_slot with kept `-relation` blocks. */
+#define FMX_PRUNE_DEAD 1u  /* drop features that contribute to no prediction */
+#define FMX_PRUNE_SEEN 2u  /* also drop features with no entry in keep_slot */
+typedef struct fmx_compact_prune_opts {
+  uint32_t format;     /* FMX_COMPACT_BF16 | FMX_COMPACT_INT8 */
+  uint32_t flags;      /* FMX_PRUNE_DEAD, or FMX_PRUNE_DEAD | FMX_PRUNE_SEEN */
+  int32_t  keep_slot;  /* with FMX_PRUNE_SEEN: an uploaded slot; else -1 */
+  uint32_t reserved;   /* 0 */
+} fmx_compact_prune_opts;
+typedef struct fmx_compact_prune_info {
+  uint64_t features;         /* n_local */
+  uint64_t kept;
+  uint64_t dropped_dead;
+  uint64_t dropped_unseen;   /* not dead, but absent from keep_slot */
+  uint64_t bytes_directory;
+  uint64_t bytes_rows;
+} fmx_compact_prune_info;
+int fmx_compact_begin_pruned(fmx_handle h, const fmx_compact_prune_opts *o,
+                             fmx_compact_info *info, fmx_compact_prune_info *pinfo); /* either may be NULL */
+int fmx_compact_slot_of(fmx_handle h, const uint32_t *ids, uint32_t count, uint32_t *slot_out);
+
 /* ---- exact binary checkpoints of the model and the optimizer state (no counterpart in the reference) -------
  * fmx_save_model / fmx_load_model speak the reference's text format: six significant digits per number, and nothing of an open
  * AdaGrad or FTRL session.  A checkpoint is the other file: w0 in fp64, w and V in fp32 without the row padding and, if an

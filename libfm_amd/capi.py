@@ -99,6 +99,19 @@ class CompactInfo(C.Structure):                    # fmx_compact_info
                 ("max_abs_err", C.c_double), ("sum_sq_err", C.c_double)]
 
 
+PRUNE_DEAD, PRUNE_SEEN = 1, 2   # FMX_PRUNE_*: fmx_compact_prune_opts::flags
+SLOT_NONE = 0xFFFFFFFF          # fmx_compact_slot_of: a dropped id
+
+
+class CompactPruneOpts(C.Structure):               # fmx_compact_prune_opts
+    _fields_ = [("format", C.c_uint32), ("flags", C.c_uint32), ("keep_slot", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class CompactPruneInfo(C.Structure):               # fmx_compact_prune_info
+    _fields_ = [("features", C.c_uint64), ("kept", C.c_uint64), ("dropped_dead", C.c_uint64), ("dropped_unseen", C.c_uint64),
+                ("bytes_directory", C.c_uint64), ("bytes_rows", C.c_uint64)]
+
+
 CKPT_DENSE_STATE, CKPT_MODEL_ONLY = 1, 2   # FMX_CKPT_*: fmx_ckpt_opts::flags
 CKPT_SESSIONS = ("none", "adagrad", "ftrl")   # fmx_ckpt_info::session
 
@@ -361,6 +374,8 @@ SYMBOLS = [
     ("fmx_compact_get_rows", C.c_int, [H, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("fmx_compact_end", C.c_int, [H]),
     ("fmx_compact_row_bytes", C.c_uint32, [C.c_uint32, C.c_int]),
+    ("fmx_compact_begin_pruned", C.c_int, [H, C.POINTER(CompactPruneOpts), C.POINTER(CompactInfo), C.POINTER(CompactPruneInfo)]),
+    ("fmx_compact_slot_of", C.c_int, [H, C.c_void_p, C.c_uint32, C.c_void_p]),
     ("fmx_checkpoint_save", C.c_int, [H, C.c_char_p, C.POINTER(CkptOpts), C.POINTER(CkptInfo)]),
     ("fmx_checkpoint_load", C.c_int, [H, C.c_char_p, C.POINTER(CkptOpts), C.POINTER(CkptInfo)]),
     ("fmx_checkpoint_info", C.c_int, [C.c_char_p, C.POINTER(CkptInfo), C.c_char_p, C.c_size_t]),
@@ -997,6 +1012,22 @@ class Handle:
         opts, info = CompactOpts(int(format), int(flags)), CompactInfo()
         self._chk(self.lib.fmx_compact_begin(self.h, C.byref(opts), C.byref(info)))
         return info
+
+    def compact_begin_pruned(self, format=COMPACT_BF16, seen_slot=None):
+        """takes (or replaces) a snapshot that keeps only the features that can score (fmx_compact_begin_pruned): the dead ones go, and
+        with seen_slot also those without an entry in that slot; returns (CompactInfo, CompactPruneInfo)"""
+        opts = CompactPruneOpts(int(format), PRUNE_DEAD | (PRUNE_SEEN if seen_slot is not None else 0),
+                                -1 if seen_slot is None else int(seen_slot), 0)
+        info, pinfo = CompactInfo(), CompactPruneInfo()
+        self._chk(self.lib.fmx_compact_begin_pruned(self.h, C.byref(opts), C.byref(info), C.byref(pinfo)))
+        return info, pinfo
+
+    def compact_slot_of(self, ids):
+        """the stored row of each feature id in the pruned snapshot, SLOT_NONE for a dropped one (fmx_compact_slot_of)"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        out = np.zeros(len(ids), dtype=np.uint32)
+        self._chk(self.lib.fmx_compact_slot_of(self.h, _ptr(ids), len(ids), _ptr(out)))
+        return out
 
     def compact_predict(self, slot, n_rows):
         out = np.zeros(n_rows, dtype=np.float64)

@@ -61,6 +61,9 @@ prints one "checkpoint" line on stderr: session, state rows, bytes, seconds.  An
 max_abs_err and nonfinite of the rounding, and the test metric -- with -metrics each named metric too -- from fp32 and from bf16 side
 by side.  -serve int8 takes the row-wise 8-bit copy instead (codes, scale and linear weight of a feature in one block; the line says
 format=int8 and names its metrics (int8)).  Without the option stdout and stderr are byte for byte what they are.
+-serve_prune dead|seen (with -serve): the copy keeps only the rows that can score (fmx_compact_begin_pruned) -- dead drops the features
+that contribute to no prediction, seen also those no -train row names (not with -interactions, whose training rows are two files).
+The "compact" line gains kept, dropped_dead, dropped_unseen, bytes_directory and bytes_rows; bytes is their sum.
 """
 import os
 import sys
@@ -114,7 +117,8 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "save_checkpoint": "sgd, bpr: filename for the exact binary checkpoint (model + adagrad / ftrl session) written after training",
          "checkpoint_dense": "with -save_checkpoint: 1 = write every feature's state rows; default=0 (only rows that differ from the start state)",
          "load_checkpoint": "sgd, bpr: filename of a checkpoint to continue from (instead of the random initialisation; not with -load_model)",
-         "serve": "bf16 | int8: score -out, -metrics and -topk after training from a frozen bf16 or row-wise int8 copy of the model; sgd, sgda, bpr, als"}
+         "serve": "bf16 | int8: score -out, -metrics and -topk after training from a frozen bf16 or row-wise int8 copy of the model; sgd, sgda, bpr, als",
+         "serve_prune": "dead | seen (with -serve): keep only the rows that can score -- dead: drop features that contribute to no prediction; seen: also those no -train row names"}
 
 
 def checkpoint_line(what, info):
@@ -340,6 +344,14 @@ def _main(argv):
             raise ValueError("-serve is not supported with -method mcmc: its prediction averages the draws, no single model scores it")
         if a.get("relation"):
             raise ValueError("-serve is not supported with -relation: the snapshot does not score kept blocks")
+    serve_prune = a.get("serve_prune")
+    if "serve_prune" in a:
+        if "serve" not in a:
+            raise ValueError("-serve_prune needs -serve (bf16 | int8)")
+        if serve_prune not in ("dead", "seen"):
+            raise ValueError("-serve_prune knows dead and seen, not '%s'" % serve_prune)
+        if serve_prune == "seen" and implicit:
+            raise ValueError("-serve_prune seen is not supported with -interactions: the training rows are two files (use dead)")
     if "train_weights" in a or "test_weights" in a:
         if method != "sgd" or optimizer not in ("adagrad", "ftrl"):
             raise ValueError("-train_weights / -test_weights belong to -method sgd with -optimizer adagrad or ftrl: -method %s%s has no "
@@ -615,10 +627,14 @@ def _main(argv):
               (sp.features, sp.w_zero, sp.v_coords, sp.v_zero, sp.v_zero_rows, sp.dead_features), file=sys.stderr)
     scorer = l                               # what -out and -topk read: the learner, or with -serve the frozen copy
     if serve:
-        scorer = l.compact(serve)
+        scorer = l.compact(serve, prune=serve_prune) if serve_prune else l.compact(serve)
         ci = scorer.info
         line = "compact\tformat=%s\tbytes=%d\tbytes_fp32=%d\tmax_abs_err=%g\tnonfinite=%d\tTest(fp32)=%g\tTest(%s)=%g" % (
             serve, ci.bytes_compact, ci.bytes_params, ci.max_abs_err, ci.nonfinite, l.evaluate(test), serve, scorer.evaluate(test))
+        if serve_prune:
+            pi = scorer.prune_info
+            line += "\tprune=%s\tkept=%d\tdropped_dead=%d\tdropped_unseen=%d\tbytes_directory=%d\tbytes_rows=%d" % (
+                serve_prune, pi.kept, pi.dropped_dead, pi.dropped_unseen, pi.bytes_directory, pi.bytes_rows)
         if metrics and not dev_avg:
             ex32, ex16 = l.evaluate_ex(test), scorer.evaluate_ex(test)
             line += "".join("\t%s(fp32)=%g\t%s(%s)=%g" % (m, getattr(ex32, m), m, serve, getattr(ex16, m)) for m in metrics if m in L.EXTRA_METRICS)

@@ -13,6 +13,11 @@ scale * float32(q_f).  A row with a non-finite factor has scale NaN and codes 0:
 
 CompactModel is what fmx_compact_begin freezes -- w0 and w unchanged, V rounded -- and predicts in fp64 by fm_model::predict
 (fm_model.h:105-127), the formula the fp64 oracle's predict_raw restates.  quant_report gives the three numbers of fmx_compact_info.
+
+The pruned snapshot (fmx_compact_begin_pruned) keeps a row only for the features of prune_mask: not dead
+(fmx_param_sparsity's dead_features rule, negated) and, with `seen`, met in the keep slot.  Rows stand in ascending id order; directory
+is the rank directory {bits, base} per 32 ids, slot_of the lookup through it.  CompactModel(..., keep=mask) packs the kept rows in that
+order, scores a dropped id as a row of +0 with w = +0, and reports fmx_compact_prune_info (prune_info) and fmx_compact_info (info).
 """
 import numpy as np
 
@@ -110,14 +115,80 @@ def quant_report(v, format="bf16"):
     return (float(err.max()) if err.size else 0.0), float(np.sum(err * err)), int((~fin).sum())
 
 
-class CompactModel:
-    """the snapshot of a model (w0, w[n], v[k][n]): w0 and w as given, v rounded to the format (bf16 | int8) from its fp32 value"""
+SLOT_NONE = 0xFFFFFFFF      # slot_of: a dropped id
 
-    def __init__(self, w0, w, v, k0=True, k1=True, format="bf16"):
+
+def dead_mask(w, v, k1):
+    """bool [n]: the features that contribute to no prediction -- all k factors == 0.0f (-0 counts, NaN does not; with k = 0 every
+    factor row counts as all zero) and (w_j == 0.0f or not k1).  Its sum is fmx_sparsity::dead_features."""
+    w32 = np.asarray(w, dtype=np.float32).reshape(-1)
+    v32 = np.asarray(v, dtype=np.float32)
+    vz = (v32 == 0).all(axis=0) if v32.ndim == 2 and v32.shape[0] > 0 else np.ones(len(w32), dtype=bool)
+    return vz & ((w32 == 0) | (not k1))
+
+
+def seen_mask(n, ids):
+    """bool [n]: the ids that stand in at least one entry (ids: the entry stream's ids, any order, repeats allowed)"""
+    m = np.zeros(int(n), dtype=bool)
+    m[np.asarray(ids, dtype=np.int64)] = True
+    return m
+
+
+def prune_mask(w, v, k1, seen=None):
+    """bool [n]: the features a pruned snapshot keeps -- not dead, and (with seen, a bool [n]) seen"""
+    keep = ~dead_mask(w, v, k1)
+    if seen is not None:
+        keep &= np.asarray(seen, dtype=bool)
+    return keep
+
+
+def directory(mask):
+    """the rank directory of a keep mask: uint32 [ceil(n / 32)][2], column 0 = bits (bit b: id 32 j + b is kept), column 1 = base (the
+    kept ids below 32 j)"""
+    m = np.asarray(mask, dtype=bool).reshape(-1)
+    nw = (len(m) + 31) // 32
+    pad = np.zeros(nw * 32, dtype=np.uint64)
+    pad[:len(m)] = m
+    bits = (pad.reshape(nw, 32) << np.arange(32, dtype=np.uint64)[None, :]).sum(axis=1, dtype=np.uint64)
+    cnt = pad.reshape(nw, 32).sum(axis=1, dtype=np.uint64)
+    base = np.cumsum(cnt) - cnt
+    return np.stack([bits, base], axis=1).astype(np.uint32)
+
+
+def _popc(x):
+    x = np.asarray(x, dtype=np.uint32).copy()
+    c = np.zeros(x.shape, dtype=np.uint32)
+    for _ in range(32):
+        c += x & np.uint32(1)
+        x >>= np.uint32(1)
+    return c
+
+
+def slot_of(dir, ids):
+    """the slot of each id through the directory (one pair per id: base + popcount of the bits below it), SLOT_NONE for a dropped id"""
+    d = np.asarray(dir, dtype=np.uint32).reshape(-1, 2)
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    bits, base = d[ids >> 5, 0], d[ids >> 5, 1]
+    b = (ids & 31).astype(np.uint32)
+    below = bits & ((np.uint32(1) << b) - np.uint32(1))
+    kept = ((bits >> b) & np.uint32(1)) != 0
+    return np.where(kept, base + _popc(below), np.uint32(SLOT_NONE)).astype(np.uint32)
+
+
+class CompactModel:
+    """the snapshot of a model (w0, w[n], v[k][n]): w0 and w as given, v rounded to the format (bf16 | int8) from its fp32 value.
+    keep (a bool [n], prune_mask): the pruned snapshot -- rows_w / rows_v hold the kept rows in slot order, dir is the directory, and
+    w / v (what predict and rows read) are those rows looked up through it, +0 for a dropped id."""
+
+    def __init__(self, w0, w, v, k0=True, k1=True, format="bf16", keep=None, seen=None):
         if format not in FORMATS:
             raise ValueError("unknown serving format %r (%s)" % (format, " | ".join(FORMATS)))
         self.format = format
         self.w0 = float(w0)
+        self.keep = None
+        if keep is not None:
+            self._init_pruned(w, v, k0, k1, np.asarray(keep, dtype=bool).reshape(-1), seen)
+            return
         self.w = np.array(w, dtype=np.float64)
         v32 = np.asarray(v, dtype=np.float32)
         if format == "int8" and v32.ndim == 2 and v32.shape[0] > 0:
@@ -128,6 +199,39 @@ class CompactModel:
             self.v = bf16_round(v32).astype(np.float64)
         self.k0, self.k1 = bool(k0), bool(k1)
         self.k, self.n = (self.v.shape if self.v.ndim == 2 else (0, len(self.w)))
+
+    def _init_pruned(self, w, v, k0, k1, keep, seen):
+        w64 = np.array(w, dtype=np.float64).reshape(-1)
+        v32 = np.asarray(v, dtype=np.float32)
+        n = len(w64)
+        if v32.ndim != 2 or v32.shape[0] == 0:
+            v32 = np.zeros((0, n), dtype=np.float32)
+        if len(keep) != n:
+            raise ValueError("CompactModel: keep has %d entries for %d features" % (len(keep), n))
+        self.keep = keep
+        self.dir = directory(keep)
+        kept_ids = np.flatnonzero(keep)
+        packed = CompactModel(self.w0, w64[kept_ids], v32[:, kept_ids], k0, k1, self.format)    # the rows, in slot order
+        self.rows_w, self.rows_v = packed.w, (packed.v if packed.v.ndim == 2 else np.zeros((0, len(kept_ids))))
+        slots = slot_of(self.dir, np.arange(n))
+        assert np.array_equal(slots[kept_ids], np.arange(len(kept_ids), dtype=np.uint32)) and np.all(slots[~keep] == SLOT_NONE)
+        at = np.where(keep, slots, 0).astype(np.int64)
+        zw, zv = np.append(self.rows_w, 0.0), np.concatenate([self.rows_v, np.zeros((v32.shape[0], 1))], axis=1)
+        at[~keep] = len(kept_ids)                                        # a dropped id reads the row of +0 behind the kept ones
+        self.w, self.v = zw[at], zv[:, at]
+        self.k0, self.k1 = bool(k0), bool(k1)
+        self.k, self.n = v32.shape[0], n
+        dead = dead_mask(w64, v32, k1)
+        gone_unseen = (~dead & ~np.asarray(seen, dtype=bool)) if seen is not None else np.zeros(n, dtype=bool)
+        kept = int(keep.sum())
+        self.prune_info = {"features": n, "kept": kept, "dropped_dead": int(dead.sum()), "dropped_unseen": int(gone_unseen.sum()),
+                           "bytes_directory": 8 * ((n + 31) // 32), "bytes_rows": kept * row_bytes(self.format, self.k)}
+        mx, ss, nf = quant_report(v32[:, kept_ids], self.format)                  # over the kept rows only
+        self.info = {"features": n, "bytes_compact": self.prune_info["bytes_directory"] + self.prune_info["bytes_rows"],
+                     "nonfinite": nf, "max_abs_err": mx, "sum_sq_err": ss}
+
+    def slot_of(self, ids):
+        return slot_of(self.dir, ids)
 
     def predict(self, entries, row_ptr):
         """raw scores of the rows (entries: structured id / value, row_ptr), fp64: fm_model::predict"""

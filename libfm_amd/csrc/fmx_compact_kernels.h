@@ -1,5 +1,6 @@
 // fmx_compact_kernels.h -- kernels of the serving snapshots (fmx_compact.hip; include/fmx.h "fmx_compact_*"; DESIGN.md sections 19, 21).
-// bf16 first; the int8 row-wise format (k_compact_quant8, RowsI8) is the second half of the file.
+// bf16 first; the int8 row-wise format (k_compact_quant8, RowsI8) is the second half of the file; the pruned snapshot (the rank
+// directory, its build kernels and the two sources that read through it) is the last part.
 //
 // k_compact_quant   one pass over V: the bf16 rows (same row stride in ELEMENTS, half the bytes) and the three numbers of
 //                   fmx_compact_info as BLOCK PARTIALS (no float atomics).
@@ -24,15 +25,36 @@ __host__ __device__ __forceinline__ uint32_t bf16_bits(uint32_t u) {
   return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
 }
 
+// The rank directory of a pruned snapshot: one 8-byte pair per 32 consecutive ids, x = bits (bit b: id 32 j + b is
+// kept), y = base (kept ids below 32 j).  ONE 8-byte load answers "is it kept" and "where": slot = base + popc(bits below b).  The pair
+// is read as one 64-bit value and both halves are used before anything is decided, so the load stays one global_load_dwordx2 and the
+// result is a select, not a branch: DIR_NONE for a dropped id.
+constexpr uint32_t DIR_NONE = 0xFFFFFFFFu;
+__device__ __forceinline__ uint32_t dir_slot(const uint2* __restrict__ dir, size_t id) {
+  const unsigned long long p = reinterpret_cast<const unsigned long long*>(dir)[id >> 5];
+  const uint32_t bits = (uint32_t)p, base = (uint32_t)(p >> 32), b = (uint32_t)id & 31u;
+  const uint32_t slot = base + (uint32_t)__popc(bits & ((1u << b) - 1u));
+  return ((bits >> b) & 1u) ? slot : DIR_NONE;
+}
+__device__ __forceinline__ bool dir_lookup(const uint2* __restrict__ dir, size_t id, size_t& slot) {
+  const uint32_t s = dir_slot(dir, id);
+  slot = (size_t)s;
+  return s != DIR_NONE;
+}
+
 constexpr uint32_t COMPACT_BLOCKS = 8192;    // cap of k_compact_quant's grid; a fixed function of the table (compact_grid)
 
 // L lanes (a power of two <= 64) share a feature and stride over its rs elements, 64 / L features per wavefront round (the map of
 // k_param_sparsity): 64 consecutive floats per wave-wide load for every k.  The padding (f >= k) is written as +0 and is not counted.
 //   dpart[2 * b + {0: max |v - q(v)|, 1: sum (v - q(v))^2}] over the finite q(v), cpart[b] = non-finite q(v)
 // v - q(v) is exact in fp32 (q(v) is within half an ulp_bf16 of v: Sterbenz), so the maximum does not depend on the order.
+// MAPPED (the pruned snapshot): row j goes to its slot of `dir` and takes w[j] along to wout[slot]; a dropped row is neither read nor
+// counted.  The blocks own the same ids either way, so the partials keep their order.
+template <bool MAPPED>
 static __global__ void __launch_bounds__(256)
 k_compact_quant(const float* __restrict__ V, uint32_t rs, uint64_t n, int k, uint32_t L, uint16_t* __restrict__ out,
-                double* __restrict__ dpart, unsigned long long* __restrict__ cpart) {
+                double* __restrict__ dpart, unsigned long long* __restrict__ cpart, const uint2* __restrict__ dir,
+                const float* __restrict__ w, float* __restrict__ wout) {
   __shared__ double dred[2][4];
   __shared__ unsigned long long cred[4];
   const uint32_t lane = threadIdx.x & 63u, grp = lane / L, sub = lane % L, rpw = 64u / L;
@@ -42,6 +64,11 @@ k_compact_quant(const float* __restrict__ V, uint32_t rs, uint64_t n, int k, uin
   for (uint64_t r0 = wave * rpw; r0 < n; r0 += nwaves * rpw) {
     const uint64_t j = r0 + grp;
     if (j < n) {
+      size_t dst = (size_t)j;
+      if constexpr (MAPPED) {
+        if (!dir_lookup(dir, (size_t)j, dst)) continue;
+        if (sub == 0u) wout[dst] = w[j];
+      }
       for (uint32_t f = sub; f < rs; f += L) {
         uint32_t q = 0u;
         if (f < (uint32_t)k) {
@@ -54,15 +81,15 @@ k_compact_quant(const float* __restrict__ V, uint32_t rs, uint64_t n, int k, uin
             ss += (double)err * (double)err;
           }
         }
-        out[j * rs + f] = (uint16_t)q;
+        out[dst * rs + f] = (uint16_t)q;
       }
     }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { mx = fmaxf(mx, __shfl_xor(mx, o)); nf += __shfl_xor(nf, o); }
   ss = wave_sum_d(ss);
-  const uint32_t w = threadIdx.x >> 6;
-  if (lane == 0) { dred[0][w] = (double)mx; dred[1][w] = ss; cred[w] = nf; }
+  const uint32_t wv = threadIdx.x >> 6;
+  if (lane == 0) { dred[0][wv] = (double)mx; dred[1][wv] = ss; cred[wv] = nf; }
   __syncthreads();
   if (threadIdx.x == 0) {
     dpart[2 * blockIdx.x + 0] = fmax(fmax(dred[0][0], dred[0][1]), fmax(dred[0][2], dred[0][3]));
@@ -169,9 +196,12 @@ constexpr int QUANT8_T = 5;      // dwords of a block per lane of k_compact_quan
 // sub, sub + L, ... of the block: dword 0 is the scale, dword 1 is w_j, dword d >= 2 the codes of factors 4 (d - 2) .. 4 (d - 2) + 3, whose
 // fp32 values the lane keeps in registers between the absmax butterfly and the rounding -- V is read once.
 //   dpart[2 * b + {0: max |v - deq|, 1: sum (v - deq)^2}] over the finite rows in fp64, cpart[b] = k per row with a non-finite factor
+// MAPPED: as k_compact_quant -- the block of row j is written at its slot of `dir`, a dropped row is neither read nor counted.
+template <bool MAPPED>
 static __global__ void __launch_bounds__(256)
 k_compact_quant8(const float* __restrict__ V, const float* __restrict__ w, uint32_t rs, uint64_t n, int k, uint32_t L, uint32_t P,
-                 uint8_t* __restrict__ out, double* __restrict__ dpart, unsigned long long* __restrict__ cpart) {
+                 uint8_t* __restrict__ out, double* __restrict__ dpart, unsigned long long* __restrict__ cpart,
+                 const uint2* __restrict__ dir) {
   __shared__ double dred[2][4];
   __shared__ unsigned long long cred[4];
   const uint32_t lane = threadIdx.x & 63u, grp = lane / L, sub = lane % L, rpw = 64u / L;
@@ -181,7 +211,9 @@ k_compact_quant8(const float* __restrict__ V, const float* __restrict__ w, uint3
   double mx = 0.0, ss = 0.0; unsigned long long nf = 0ull;
   for (uint64_t r0 = wave * rpw; r0 < n; r0 += nwaves * rpw) {     // (r0 is wave-uniform: every lane takes part in the butterflies)
     const uint64_t j = r0 + grp;
-    const bool live = j < n;
+    bool live = j < n;
+    size_t dst = (size_t)j;
+    if constexpr (MAPPED) { if (live) live = dir_lookup(dir, (size_t)j, dst); }
     float vals[QUANT8_T][4];
     float amax = 0.f; int bad = 0;
 #pragma unroll
@@ -203,7 +235,7 @@ k_compact_quant8(const float* __restrict__ V, const float* __restrict__ w, uint3
     const double inv = a > 0.0 ? 127.0 / a : 0.0;
     const float scale = bad ? __uint_as_float(0x7FC00000u) : (float)(a / 127.0);
     if (live) {
-      uint32_t* blk = reinterpret_cast<uint32_t*>(out + j * P);
+      uint32_t* blk = reinterpret_cast<uint32_t*>(out + dst * P);
 #pragma unroll
       for (int t = 0; t < QUANT8_T; t++) {
         const uint32_t d = sub + (uint32_t)t * L;
@@ -320,6 +352,145 @@ struct RowsI8 {
     const uint8_t* p = B + row * P;
     return *reinterpret_cast<const float*>(p) * (float)(int)(int8_t)p[FOFF + f];
   }
+};
+
+// ==============================================================================================
+// The pruned snapshot (fmx_compact_begin_pruned): only the features that can contribute to a score keep a row.
+// Rows stand in ascending id order ("slots"); the rank directory (dir_lookup above) maps a feature id to its slot.
+// Build: k_prune_live (one pass over w and V) -> [k_prune_mark over a slot's entries] -> k_prune_keep (AND, popcounts) -> an exclusive
+// scan of the popcounts (hipcub) -> k_prune_dir; then the quantisers above with MAPPED.
+// ==============================================================================================
+
+// bits[j] bit b = feature 32 j + b is NOT dead: one of its k factors is != 0.0f (NaN is, -0 is not), or k1 and w_j != 0.0f
+// (fmx_param_sparsity's dead_features rule, negated).  One wavefront per word: the 32 rows are one contiguous run of V, read with
+// wave-wide loads for every rs; each lane ORs the rows it met, a butterfly ORs the lanes.  Bits at or beyond n are 0.
+// *dead += the dead features: integer sums, one block reduction through LDS and one 64-bit integer atomic per block.
+static __global__ void __launch_bounds__(256)
+k_prune_live(const float* __restrict__ V, const float* __restrict__ w, uint32_t rs, uint64_t n, int k, int k1,
+             uint32_t* __restrict__ bits, unsigned long long* __restrict__ dead) {
+  __shared__ unsigned long long cred[4];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const uint64_t nwords = (n + 31u) / 32u;
+  unsigned long long nd = 0ull;
+  for (uint64_t j = wave; j < nwords; j += nwaves) {                 // (j is wave-uniform: every lane takes part in the butterfly)
+    const uint64_t id0 = j * 32u;
+    const uint32_t cnt = (uint32_t)min((uint64_t)32u, n - id0);
+    uint32_t nz = 0u;
+    if (k > 0) {
+      const float* p = V + id0 * rs;
+      const uint32_t tot = cnt * rs;
+      for (uint32_t e = lane; e < tot; e += 64u) {
+        const uint32_t r = e / rs, f = e - r * rs;
+        if (f < (uint32_t)k && !(p[e] == 0.0f)) nz |= 1u << r;
+      }
+    }
+    if (k1 && lane < cnt && !(w[id0 + lane] == 0.0f)) nz |= 1u << lane;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nz |= (uint32_t)__shfl_xor((int)nz, o);
+    const uint32_t valid = cnt == 32u ? 0xFFFFFFFFu : ((1u << cnt) - 1u);
+    if (lane == 0u) { bits[j] = nz; nd += (unsigned long long)__popc(~nz & valid); }
+  }
+  const uint32_t wv = threadIdx.x >> 6;
+  if (lane == 0u) cred[wv] = nd;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long t = (cred[0] + cred[1]) + (cred[2] + cred[3]);
+    if (t) atomicAdd(dead, t);
+  }
+}
+
+// seen[id / 32] |= 1 << id % 32 for every entry of a slot's stream: integer atomics, so the result does not depend on the order.  A word
+// that already holds the bit is left alone (the bits only ever get set, so a stale read costs one atomic and nothing else).
+static __global__ void __launch_bounds__(256)
+k_prune_mark(const Entry* __restrict__ ent, uint64_t nnz, uint64_t n, uint32_t* __restrict__ seen) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += stride) {
+    const uint32_t id = ent[i].id;
+    if (id >= n) continue;
+    const uint32_t m = 1u << (id & 31u);
+    uint32_t* p = seen + (id >> 5);
+    if (!(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & m)) atomicOr(p, m);
+  }
+}
+
+// bits[j] &= seen[j] (seen may be null: everything counts as seen), cnt[j] = popc(bits[j]), *unseen += the live features that went
+static __global__ void __launch_bounds__(256)
+k_prune_keep(uint32_t* __restrict__ bits, const uint32_t* __restrict__ seen, uint64_t nwords, uint32_t* __restrict__ cnt,
+             unsigned long long* __restrict__ unseen) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  unsigned long long nu = 0ull;
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nwords; j += stride) {
+    const uint32_t live = bits[j];
+    const uint32_t keep = seen ? (live & seen[j]) : live;
+    nu += (unsigned long long)__popc(live & ~keep);
+    bits[j] = keep;
+    cnt[j] = (uint32_t)__popc(keep);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) nu += __shfl_xor(nu, o);
+  if ((threadIdx.x & 63u) == 0u && nu) atomicAdd(unseen, nu);
+}
+
+static __global__ void __launch_bounds__(256)
+k_prune_dir(const uint32_t* __restrict__ bits, const uint32_t* __restrict__ base, uint64_t nwords, uint2* __restrict__ dir) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nwords; j += stride) dir[j] = make_uint2(bits[j], base[j]);
+}
+
+// fmx_compact_slot_of: the slot of each id, 0xFFFFFFFF for a dropped one
+static __global__ void __launch_bounds__(256)
+k_prune_slot_of(const uint2* __restrict__ dir, const uint32_t* __restrict__ ids, uint32_t count, uint32_t* __restrict__ out) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= count) return;
+  size_t slot;
+  out[t] = dir_lookup(dir, (size_t)ids[t], slot) ? (uint32_t)slot : 0xFFFFFFFFu;
+}
+
+// The pruned snapshots as row sources.  Each wraps the dense source of its format and differs in ONE thing: a feature id goes through
+// the directory first.  They set MAP_IDS (fmx_kernels.h "ROW SOURCE"): row_sums hands every entry's id to map() on the lane that
+// loaded the entry -- up to 64 independent 8-byte lookups in flight per block of entries, one extra memory latency per 64 entries, to a
+// table of a few MB that lives in the caches -- and broadcasts the SLOT where the other sources broadcast the id.  ld_raw / ld / lin
+// therefore take a slot (or DIR_NONE) and issue no lookup: a kept row is loaded from its slot exactly as the dense source loads row id;
+// a dropped id issues no row load and yields what a stored row of +0 with w_j = +0 yields -- int8: an all-zero block, which unpack
+// multiplies as it does a stored one (scale +0, codes 0); bf16: +0 factors and +0.f from lin -- so everything downstream runs on the
+// same bits.  w1 / v1 (k_fetch_rows) take a feature id and look it up themselves.
+struct RowsI8P {
+  static constexpr bool W_IN_ROW = true;
+  static constexpr bool MAP_IDS = true;
+  static constexpr int FOFF = RowsI8::FOFF;
+  template <int KP> using Lanes = MapI8<KP>;
+  template <int VEC> using Raw = RawI8<VEC>;
+  RowsI8 rows; const uint2* dir;
+  __device__ __forceinline__ uint32_t map(uint32_t id) const { return dir_slot(dir, (size_t)id); }
+  template <int VEC> __device__ __forceinline__ void ld_raw(size_t slot, uint32_t f, RawI8<VEC>& r) const {
+    if ((uint32_t)slot != DIR_NONE) rows.template ld_raw<VEC>(slot, f, r);
+    else r = RawI8<VEC>();
+  }
+  template <int KP, int VEC> __device__ __forceinline__ void unpack(const RawI8<VEC>& r, uint32_t f, float (&out)[VEC], float& wj) const {
+    rows.template unpack<KP, VEC>(r, f, out, wj);
+  }
+  __device__ __forceinline__ float w1(size_t row) const { size_t slot; return dir_lookup(dir, row, slot) ? rows.w1(slot) : 0.f; }
+  __device__ __forceinline__ float v1(size_t row, int f) const { size_t slot; return dir_lookup(dir, row, slot) ? rows.v1(slot, f) : 0.f; }
+};
+
+struct RowsBf16P {
+  static constexpr bool W_IN_ROW = false;
+  static constexpr bool MAP_IDS = true;
+  template <int KP> using Lanes = MapC<KP>;
+  RowsBf16 rows; const uint2* dir;
+  __device__ __forceinline__ uint32_t map(uint32_t id) const { return dir_slot(dir, (size_t)id); }
+  template <int VEC> __device__ __forceinline__ void ld(size_t slot, uint32_t off, float (&out)[VEC]) const {
+    if ((uint32_t)slot != DIR_NONE) rows.template ld<VEC>(slot, off, out);
+    else {
+#pragma unroll
+      for (int v = 0; v < VEC; v++) out[v] = 0.f;
+    }
+  }
+  __device__ __forceinline__ float w1(size_t row) const { size_t slot; return dir_lookup(dir, row, slot) ? rows.w1(slot) : 0.f; }
+  __device__ __forceinline__ float v1(size_t row, int f) const { size_t slot; return dir_lookup(dir, row, slot) ? rows.v1(slot, f) : 0.f; }
+  __device__ __forceinline__ float lin(uint32_t slot, uint64_t, uint32_t) const { return slot != DIR_NONE ? rows.w1((size_t)slot) : 0.f; }
 };
 
 }  // namespace fmx

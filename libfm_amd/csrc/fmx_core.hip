@@ -294,7 +294,11 @@ int launch_rest(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, float* r
   // the linear weights come out of the slot's side stream where it is current (it is after a one-pass epoch on THIS slot that kept it,
   // and until anything else touches w): 4 coalesced bytes per entry instead of a 64-byte fabric request
   const float* ws = (s.wside && s.wside_version == h->w_version && h->cfg.shard_world == 1) ? s.wside : nullptr;
-  if (snap && snap->format == FMX_COMPACT_INT8) { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, false, true, RowsI8>), n, st,
+  if (snap && snap->dir && snap->format == FMX_COMPACT_INT8) { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, false, true, RowsI8P>), n, st,
+                                                 s.ent, s.row_ptr, row0, n, compact_rows8_p(*snap), h->cfg.k1, (float*)nullptr, rest)); }
+  else if (snap && snap->dir) { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, false, true, RowsBf16P>), n, st,
+                                                 s.ent, s.row_ptr, row0, n, compact_rows_p(h, *snap), h->cfg.k1, (float*)nullptr, rest)); }
+  else if (snap && snap->format == FMX_COMPACT_INT8) { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, false, true, RowsI8>), n, st,
                                                  s.ent, s.row_ptr, row0, n, compact_rows8(*snap), h->cfg.k1, (float*)nullptr, rest)); }
   else if (snap) { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, false, true, RowsBf16>), n, st,
                                                  s.ent, s.row_ptr, row0, n, compact_rows(h, *snap), h->cfg.k1, (float*)nullptr, rest)); }

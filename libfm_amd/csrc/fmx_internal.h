@@ -182,7 +182,10 @@ struct FtrlState { float* zw = nullptr; float* zv = nullptr; float* nw = nullptr
 // the serving snapshot (fmx_compact_*, fmx_compact.hip): a frozen copy of w0 and, by format,
 //   FMX_COMPACT_BF16  w (fp32, stride 1) and V as bf16 rows of tb.rs elements
 //   FMX_COMPACT_INT8  B: one block of P bytes per feature with its scale, its w and its int8 codes (V and w stay null)
-struct CompactState { uint16_t* V = nullptr; float* w = nullptr; double* w0 = nullptr; uint8_t* B = nullptr; uint32_t P = 0; uint32_t format = 0; };
+// dir != nullptr: a pruned snapshot (fmx_compact_begin_pruned) -- the tables hold `kept` rows in slot order and dir, the rank directory
+// of ceil(n_local / 32) pairs (fmx_compact_kernels.h dir_lookup), maps a feature id to its slot
+struct CompactState { uint16_t* V = nullptr; float* w = nullptr; double* w0 = nullptr; uint8_t* B = nullptr; uint32_t P = 0; uint32_t format = 0;
+                      uint2* dir = nullptr; uint64_t kept = 0; };
 
 struct fmx_context_s {
   fmx_config cfg;
@@ -290,6 +293,8 @@ int predict_out(fmx_handle h, const Slot& s, const CompactState* snap, double* o
 int evaluate_out(fmx_handle h, const Slot& s, const CompactState* snap, fmx_eval* out);
 inline RowsBf16 compact_rows(fmx_handle h, const CompactState& c) { return RowsBf16{CTab{c.V, c.w, h->tb.rs}}; }
 inline RowsI8 compact_rows8(const CompactState& c) { return RowsI8{c.B, c.P}; }
+inline RowsBf16P compact_rows_p(fmx_handle h, const CompactState& c) { return RowsBf16P{compact_rows(h, c), c.dir}; }
+inline RowsI8P compact_rows8_p(const CompactState& c) { return RowsI8P{compact_rows8(c), c.dir}; }
 int ensure_segments(fmx_handle h, Slot& s, uint32_t B);                 // fmx_sgd.hip
 int ensure_coll_mass(fmx_handle h, Slot& s);                             // fmx_core.hip
 int ensure_wside(fmx_handle h, Slot& s);                                 // fmx_core.hip

@@ -426,17 +426,22 @@ static __global__ void k_handoff_arm(double* W, uint32_t n) {         // W[1 .. 
 //   ld<VEC>(id, off, out) VEC factors of row id from element offset off, zeros beyond the row's rs elements
 //   lin(id, i0, i)       the linear weight of entry i0 + i of the slot's stream, whose feature is id
 //   w1(row), v1(row, f)  one weight / one factor (k_fetch_rows)
+//   MAP_IDS (optional)   the source declares it and supplies map(id): row_sums replaces every entry's id by map(id) on the lane that
+//                        loaded the entry, and ld / ld_raw / lin receive that value instead of the id (the pruned snapshots: a slot)
 //   W_IN_ROW             false: lin() as above.  true: the weight travels IN the row -- the source supplies instead
 //                          FOFF                 slot v of lane f (of a row's LPR lanes) is factor f * VEC + v - FOFF; slots outside [0, KP) are
 //                                               not factors (a header, idle lanes) and hold zeros
 //                          Raw<VEC>, ld_raw     what one lane loads of row id, kept as loaded while the round is in flight
 //                          unpack<KP>           the lane's VEC factor slots of it, and w_j on the lane that holds it (0 elsewhere)
-// RowsF32 is the model (Tab); RowsBf16 and RowsI8 (fmx_compact_kernels.h) the bf16 and int8 snapshots.  The sums, their order and what
+// RowsF32 is the model (Tab); RowsBf16 and RowsI8 (fmx_compact_kernels.h) the bf16 and int8 snapshots, RowsBf16P and RowsI8P their pruned forms.  The sums, their order and what
 // k_rowsums does with them are written once, here.
 // wside (optional): the slot's WEIGHT SIDE STREAM -- wside[i] is either w[id_i] as it stands or NaN ("gather it").
 // A 4-byte w_j out of its own array costs a 64-byte fabric request per entry (a third of a predict pass's requests for 1.5 % of its
 // bytes); the stream costs 4 coalesced bytes.  Maintained by k_fused<EXACT> for the entries that are the LAST occurrence of their
 // feature in the slot and are updated by their own example (FMX_FLAG_KEEP_WSIDE; fmx_sgd.hip), NaN for everything else.
+template <class S, class = void> struct src_maps_ids { static constexpr bool value = false; };
+template <class S> struct src_maps_ids<S, decltype((void)S::MAP_IDS)> { static constexpr bool value = true; };
+
 struct RowsF32 {
   static constexpr bool W_IN_ROW = false;
   template <int KP> struct Lanes : Map<KP> { static constexpr int U = 8; };
@@ -471,7 +476,10 @@ __device__ __forceinline__ void row_sums_inrow(const Entry* __restrict__ ent, ui
   for (uint32_t base = 0; base < size; base += 64) {
     const uint32_t cnt = min(64u, size - base);
     Entry e; e.id = 0; e.value = 0.f;
-    if (lane < cnt) e = load_stream8(ent + base + lane);
+    if (lane < cnt) {
+      e = load_stream8(ent + base + lane);
+      if constexpr (src_maps_ids<Src>::value) e.id = src.map(e.id);
+    }
     for (uint32_t i = 0; i < cnt; i += EPI * U) {
       Raw raw[U]; float xs[U];
 #pragma unroll
@@ -518,6 +526,7 @@ __device__ __forceinline__ void row_sums_gather(const Entry* __restrict__ ent, u
     Entry e; e.id = 0; e.value = 0.f;
     if (lane < cnt) {
       e = load_stream8(ent + base + lane);
+      if constexpr (src_maps_ids<Src>::value) e.id = src.map(e.id);
       if (k1) lin += src.lin(e.id, i0, base + lane) * e.value;
     }
     for (uint32_t i = 0; i < cnt; i += EPI * U) {

@@ -112,7 +112,9 @@ extern "C++" int sgd_partial_rows(fmx_handle h, const Slot& s, uint64_t row0, ui
                                   const CompactState* snap) {
   if (n_rows == 0) return FMX_OK;
   if (snap) {
-    if (snap->format == FMX_COMPACT_INT8) { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false, RowsI8>), n_rows, st, s.ent, s.row_ptr, row0, n_rows, compact_rows8(*snap), h->cfg.k1, S, c)); }
+    if (snap->dir && snap->format == FMX_COMPACT_INT8) { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false, RowsI8P>), n_rows, st, s.ent, s.row_ptr, row0, n_rows, compact_rows8_p(*snap), h->cfg.k1, S, c)); }
+    else if (snap->dir) { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false, RowsBf16P>), n_rows, st, s.ent, s.row_ptr, row0, n_rows, compact_rows_p(h, *snap), h->cfg.k1, S, c)); }
+    else if (snap->format == FMX_COMPACT_INT8) { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false, RowsI8>), n_rows, st, s.ent, s.row_ptr, row0, n_rows, compact_rows8(*snap), h->cfg.k1, S, c)); }
     else { KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, false, RowsBf16>), n_rows, st, s.ent, s.row_ptr, row0, n_rows, compact_rows(h, *snap), h->cfg.k1, S, c)); }
     HIPCHK(h, hipGetLastError());
     return FMX_OK;

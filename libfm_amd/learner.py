@@ -184,14 +184,27 @@ class CompactView:
     """A frozen bf16 or int8 copy of a learner's model on the device (fmx_compact_*), scored like the learner itself: predict, evaluate,
     evaluate_ex and recommend mirror the learner's methods, link and clamping included, and read the copy, so training the
     learner further does not change what they return.  `info` is the capi.CompactInfo of the copy (bytes, max_abs_err,
-    nonfinite).  A handle holds one copy: learner.compact() again replaces it under every earlier view; close() frees it."""
+    nonfinite).  A handle holds one copy: learner.compact() again replaces it under every earlier view; close() frees it.
+    prune ("dead" | "seen"): the copy keeps only the rows that can score (fmx_compact_begin_pruned) -- "dead" drops the features that
+    contribute to no prediction, "seen" also those the training rows never name; `prune_info` is its capi.CompactPruneInfo (kept,
+    dropped_dead, dropped_unseen, bytes), None for a dense copy."""
 
-    def __init__(self, learner, format):
+    PRUNE = (None, "dead", "seen")
+
+    def __init__(self, learner, format, prune=None):
         if format not in compact_format.FORMATS:
             raise ValueError("unknown serving format %r (%s)" % (format, " | ".join(compact_format.FORMATS)))
+        if prune not in self.PRUNE:
+            raise ValueError("unknown prune rule %r (None | dead | seen)" % (prune,))
         self._l = learner
         self.format = format
-        self.info = learner._h.compact_begin(compact_format.FORMATS[format])
+        self.prune = prune
+        self.prune_info = None
+        if prune is None:
+            self.info = learner._h.compact_begin(compact_format.FORMATS[format])
+        else:
+            self.info, self.prune_info = learner._h.compact_begin_pruned(compact_format.FORMATS[format],
+                                                                         learner._compact_train_slot() if prune == "seen" else None)
 
     def predict_raw(self, data):
         return self._l._h.compact_predict(self._l._compact_slot(data), data.num_cases)
@@ -421,6 +434,7 @@ class FMLearnSGD:
         print("#iterations=%d" % self.num_iter, file=self.out)
         print("SGD: DON'T FORGET TO SHUFFLE THE ROWS IN TRAINING DATA TO GET THE BEST RESULTS.", file=self.out)
         st = self._slot(train)
+        self._train = train                                          # (compact(prune="seen") asks which features these rows name)
         for i in range(self.num_iter):
             apply_ = self.APPLY[self.apply]
             if self.mode != "minibatch" and apply_ == capi.APPLY_FUSED:
@@ -476,9 +490,17 @@ class FMLearnSGD:
 
     _compact_slot = _slot
 
-    def compact(self, format="bf16"):
-        """a CompactView: a frozen reduced-precision copy of the model as it stands, to score from (fmx_compact_begin)"""
-        return CompactView(self, format)
+    def _compact_train_slot(self):
+        """the slot whose entries say which features training has seen (compact(prune="seen"))"""
+        if getattr(self, "_train", None) is None:
+            raise ValueError("compact(prune='seen'): no single training set (learn() has not run, or learn_implicit() trained on "
+                             "query x candidate slots): use prune='dead'")
+        return self._compact_slot(self._train)
+
+    def compact(self, format="bf16", prune=None):
+        """a CompactView: a frozen reduced-precision copy of the model as it stands, to score from (fmx_compact_begin); with
+        prune = "dead" | "seen" one that keeps only the rows that can score (fmx_compact_begin_pruned)"""
+        return CompactView(self, format, prune)
 
     # fm_learn_sgd::predict (fm_learn_sgd.h:76-90)
     def predict(self, data):
@@ -726,13 +748,16 @@ class FMLearnALS:
             return np.maximum(self.min_target, np.minimum(self.max_target, p))
         return np.maximum(0.0, np.minimum(1.0, cdf_gaussian(p)))
 
-    def compact(self, format="bf16"):
-        """a CompactView of the parameters of the last sweep (fmx_compact_begin); its data sets are the train and test set of
-        learn().  Not on feature shards."""
+    def _compact_train_slot(self):
+        return 0
+
+    def compact(self, format="bf16", prune=None):
+        """a CompactView of the parameters of the last sweep (fmx_compact_begin, or fmx_compact_begin_pruned with prune = "dead" |
+        "seen"); its data sets are the train and test set of learn().  Not on feature shards."""
         if len(self._shards) > 1:
             raise NotImplementedError("compact: the serving snapshot is not supported on feature shards (devices lists %d GPUs)"
                                       % len(self._shards))
-        return CompactView(self, format)
+        return CompactView(self, format, prune)
 
     # fm_learn_mcmc::predict (fm_learn_mcmc.h:380-404)
     def predict(self, data):
@@ -763,7 +788,7 @@ class FMLearnMCMC(FMLearnALS):
         raise NotImplementedError("recommend: the MCMC prediction is the average over the draws (pred_sum_all / num_iter); "
                                   "no single parameter set scores it")
 
-    def compact(self, format="bf16"):
+    def compact(self, format="bf16", prune=None):
         raise NotImplementedError("compact: the MCMC prediction is the average over the draws (pred_sum_all / num_iter); "
                                   "a snapshot of one parameter set does not score it")
 
@@ -909,6 +934,7 @@ class FMLearnPairSGD(FMLearnSGD):
         print("#iterations=%d" % self.num_iter, file=self.out)
         st = self._pair_slot(train, train_pairs)
         se = self._pair_slot(test, test_pairs)
+        self._train = train
         for i in range(self.num_iter):
             stats = self._pair_epoch(st)
             tr, te = self._h.pair_evaluate(st), self._h.pair_evaluate(se)
@@ -965,6 +991,7 @@ class FMLearnPairSGD(FMLearnSGD):
         is the hardest of M accepted draws under the parameters at the start of its epoch (FMX_NEG_HARDEST).  The #Iter= lines
         come from fmx_pair_evaluate_sampled on one fixed epoch number and on UNIFORM negatives whatever neg_draws is, so the curves
         of different samplers measure the same thing; recommend() works on the trained model."""
+        self._train = None                                           # (two slots, not one training set: compact(prune="seen") refuses)
         neg_draws = int(neg_draws)
         if not 1 <= neg_draws <= capi.NEG_ATTEMPTS:
             raise ValueError("neg_draws must be in 1 .. %d" % capi.NEG_ATTEMPTS)
@@ -1068,6 +1095,7 @@ class FMLearnSGDA(FMLearnSGD):
         print("Training using self-adaptive-regularization SGD.", file=self.out)
         h = self._h
         st, sv = self._slot(train), self._slot(self.validation)
+        self._train = train
         self.fm.reg0 = self.fm.regw = self.fm.regv = 0.0                  # :257-259
         h.set_groups(self.groups)
         h.sgda_begin()
