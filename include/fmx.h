@@ -1252,6 +1252,48 @@ typedef struct fmx_sparsity {
 } fmx_sparsity;
 int fmx_param_sparsity(fmx_handle h, fmx_sparsity *out);
 
+/* ---- AdaGrad and FTRL over feature shards -----------------------------------------------------------
+ * The group forms of "fmx_adapt_*", "fmx_ftrl_*" and fmx_param_sparsity: the same rules, options, stats and start state on a model
+ * whose features are split over the members of an fmx_group.  The state of a coordinate lives with its feature: every member holds
+ * the session's tables for its own n_local rows (4 * n_local * (row stride + 1) bytes for AdaGrad, 8 * ... for FTRL, per shard).
+ * Per batch every shard takes its partial row sums, ONE exchange sums them over the shards, and from the summed buffer every shard
+ * derives rest_e, runs the bias recurrence (all shards compute the same w0 and multipliers from the same sums, as fmx_sgd_finish
+ * does) and steps the features it owns with the rule's owner kernel.  That is the rule of the per-handle call on the whole model;
+ * only the association of the fp32 factor sums differs (per-shard partial sums, then their sum).  Exact schedule only: there is no
+ * pipelined or bias-lag form.  One owner per (batch, feature), sums in a fixed order: two runs of the same calls are bit-identical.
+ *
+ *   fmx_group_adapt_begin / fmx_group_ftrl_begin : every refusal of the per-handle call, with its code and message, for every
+ *                     member before any member is touched; then the session opens on every member.  If a member cannot allocate its
+ *                     tables the sessions already opened by this call are closed and the error is returned: all or nothing.
+ *   fmx_group_adapt_epoch / fmx_group_ftrl_epoch : one epoch.  batch = 0 resolves to the batch ONE unsharded handle would choose on
+ *                     the same rows (the collision mass summed over the shards, as fmx_group_sgd_epoch); w0_chunk = 0:
+ *                     fmx_default_w0_chunk.  The stats are filled as fmx_adapt_epoch fills them; status is OR-ed over the shards,
+ *                     setup_seconds and max_feature_count are the largest of any shard.  An empty slot returns FMX_OK with zero rows.
+ *   fmx_group_adapt_get_state_rows / fmx_group_ftrl_get_state_rows : the layouts of the per-handle calls (FTRL: z before n).  ids
+ *                     are GLOBAL feature ids in any order, repeats allowed; each is read on the shard that owns it.
+ *   fmx_group_adapt_end / fmx_group_ftrl_end : closes the session on every member.  fmx_destroy of a member and fmx_group_destroy
+ *                     followed by it free the member's tables as always.
+ *   fmx_group_param_sparsity : the sum of the shards' counts; equal, field for field, to fmx_param_sparsity of one unsharded handle
+ *                     holding the same parameters.
+ * A group of one unsharded handle forwards every call to the per-handle form (same bits).  Shards that share a device and shards on
+ * distinct devices (RCCL) run the same driver.
+ * Refusals, each before any launch, the group usable afterwards.  FMX_E_STATE: _epoch, _get_state_rows or _end before _begin; _begin
+ * while the other optimiser's session or an SGDA session is open on any member; an open ALS / MCMC session on any member; members
+ * holding different row counts in the slot; a destroyed member.  FMX_E_UNSUPPORTED: a slot with kept `-relation` blocks; a slot with
+ * row weights on any member; a member that is a communicator rank (fmx_comm_init_rank).  FMX_E_ARG: as the per-handle calls.
+ * Not offered on shards: checkpoints, row weights, the pairwise epochs.  The per-handle fmx_adapt_*, fmx_ftrl_*, fmx_param_sparsity
+ * and fmx_checkpoint_* keep refusing a shard handle or group member with FMX_E_UNSUPPORTED.
+ * Added without an ABI version change: a caller detects the feature by the symbol fmx_group_adapt_begin. */
+int fmx_group_adapt_begin(fmx_group g, const fmx_adapt_opts *opts);
+int fmx_group_adapt_epoch(fmx_group g, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
+int fmx_group_adapt_get_state_rows(fmx_group g, const uint32_t *ids, uint32_t count, double *nw_out, double *nv_out);
+int fmx_group_adapt_end(fmx_group g);
+int fmx_group_ftrl_begin(fmx_group g, const fmx_ftrl_opts *opts);
+int fmx_group_ftrl_epoch(fmx_group g, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
+int fmx_group_ftrl_get_state_rows(fmx_group g, const uint32_t *ids, uint32_t count, double *zw, double *zv, double *nw, double *nv);
+int fmx_group_ftrl_end(fmx_group g);
+int fmx_group_param_sparsity(fmx_group g, fmx_sparsity *out);
+
 /* ---- a bf16 serving snapshot of the model (no counterpart in the reference) ------------------------
  * Every scoring pass is a random gather of factor rows and is paid for in the bytes of those rows.  Training needs them in fp32 (an
  * update adds learn_rate * g to values a thousand times larger); scoring does not.  fmx_compact_begin takes a frozen, read-only copy

@@ -366,6 +366,15 @@ SYMBOLS = [
     ("fmx_ftrl_get_state_rows", C.c_int, [H, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("fmx_ftrl_end", C.c_int, [H]),
     ("fmx_param_sparsity", C.c_int, [H, C.POINTER(Sparsity)]),
+    ("fmx_group_adapt_begin", C.c_int, [H, C.POINTER(AdaptOpts)]),
+    ("fmx_group_adapt_epoch", C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
+    ("fmx_group_adapt_get_state_rows", C.c_int, [H, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("fmx_group_adapt_end", C.c_int, [H]),
+    ("fmx_group_ftrl_begin", C.c_int, [H, C.POINTER(FtrlOpts)]),
+    ("fmx_group_ftrl_epoch", C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
+    ("fmx_group_ftrl_get_state_rows", C.c_int, [H, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("fmx_group_ftrl_end", C.c_int, [H]),
+    ("fmx_group_param_sparsity", C.c_int, [H, C.POINTER(Sparsity)]),
     ("fmx_compact_begin", C.c_int, [H, C.POINTER(CompactOpts), C.POINTER(CompactInfo)]),
     ("fmx_compact_predict", C.c_int, [H, C.c_int, C.c_void_p]),
     ("fmx_compact_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
@@ -1303,6 +1312,62 @@ class Group:
 
     def als_end(self):
         self._chk(self.lib.fmx_group_als_end(self.g))
+
+    # AdaGrad and FTRL over the shards (include/fmx.h "fmx_group_adapt_*"), mirroring Handle -------
+    def adapt_begin(self, rule="adagrad", init_acc=0.0, learn_rate=0.0):
+        """Handle.adapt_begin on every member, all or nothing (fmx_group_adapt_begin)"""
+        if isinstance(rule, str):
+            if rule != "adagrad":
+                raise ValueError("adapt_begin: unknown rule %r (adagrad)" % (rule,))
+            rule = ADAPT_ADAGRAD
+        opts = AdaptOpts(int(rule), 0, float(init_acc), float(learn_rate))
+        self._chk(self.lib.fmx_group_adapt_begin(self.g, C.byref(opts)))
+
+    def adapt_epoch(self, slot, batch=0, w0_chunk=0):
+        st = EpochStats()
+        self._chk(self.lib.fmx_group_adapt_epoch(self.g, int(slot), int(batch), int(w0_chunk), C.byref(st)))
+        return st
+
+    def adapt_state_rows(self, ids):
+        """(n_w[ids], n_v[:, ids]) for GLOBAL ids in any order, each read on the shard that owns it"""
+        k = self.handles[0].k
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        nw = np.zeros(len(ids), dtype=np.float64)
+        nv = np.zeros((len(ids), max(k, 1)), dtype=np.float64)
+        self._chk(self.lib.fmx_group_adapt_get_state_rows(self.g, _ptr(ids), len(ids), _ptr(nw), _ptr(nv) if k > 0 else None))
+        return nw, nv[:, :k].T.copy()
+
+    def adapt_end(self):
+        self._chk(self.lib.fmx_group_adapt_end(self.g))
+
+    def ftrl_begin(self, alpha=0.0, beta=1.0, l1_w=0.0, l1_v=0.0, l2_w=0.0, l2_v=0.0, init_acc=0.0):
+        """Handle.ftrl_begin on every member, all or nothing (fmx_group_ftrl_begin)"""
+        opts = FtrlOpts(0, 0, float(alpha), float(beta), float(l1_w), float(l1_v), float(l2_w), float(l2_v), float(init_acc))
+        self._chk(self.lib.fmx_group_ftrl_begin(self.g, C.byref(opts)))
+
+    def ftrl_epoch(self, slot, batch=0, w0_chunk=0):
+        st = EpochStats()
+        self._chk(self.lib.fmx_group_ftrl_epoch(self.g, int(slot), int(batch), int(w0_chunk), C.byref(st)))
+        return st
+
+    def ftrl_state_rows(self, ids):
+        """(z_w[ids], z_v[:, ids], n_w[ids], n_v[:, ids]) for GLOBAL ids in any order, each read on the shard that owns it"""
+        k = self.handles[0].k
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        zw, nw = np.zeros(len(ids), dtype=np.float64), np.zeros(len(ids), dtype=np.float64)
+        zv, nv = (np.zeros((len(ids), max(k, 1)), dtype=np.float64) for _ in range(2))
+        self._chk(self.lib.fmx_group_ftrl_get_state_rows(self.g, _ptr(ids), len(ids), _ptr(zw), _ptr(zv) if k > 0 else None,
+                                                         _ptr(nw), _ptr(nv) if k > 0 else None))
+        return zw, zv[:, :k].T.copy(), nw, nv[:, :k].T.copy()
+
+    def ftrl_end(self):
+        self._chk(self.lib.fmx_group_ftrl_end(self.g))
+
+    def param_sparsity(self):
+        """fmx_sparsity of the whole model: the shards' counts summed (fmx_group_param_sparsity)"""
+        sp = Sparsity()
+        self._chk(self.lib.fmx_group_param_sparsity(self.g, C.byref(sp)))
+        return sp
 
     def get_params(self, w=None, v=None):
         """the full model: every shard writes its own features into the same host arrays"""

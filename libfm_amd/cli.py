@@ -64,6 +64,10 @@ format=int8 and names its metrics (int8)).  Without the option stdout and stderr
 -serve_prune dead|seen (with -serve): the copy keeps only the rows that can score (fmx_compact_begin_pruned) -- dead drops the features
 that contribute to no prediction, seen also those no -train row names (not with -interactions, whose training rows are two files).
 The "compact" line gains kept, dropped_dead, dropped_unseen, bytes_directory and bytes_rows; bytes is their sum.
+-devices D0,D1[,...] (-method sgd with -optimizer adagrad | ftrl): the model is split into one feature shard per listed device
+ordinal ("0,0" = two shards on device 0) and the epochs run over the shards (fmx_group_adapt_epoch / fmx_group_ftrl_epoch,
+learner.FMLearnSGD.devices); the printed lines are those of one device.  Any other method or optimizer refuses the flag, and so do
+-serve, -topk, -save_checkpoint, -load_checkpoint and -train_weights, which have no sharded form.  Without the flag nothing changes.
 """
 import os
 import sys
@@ -118,7 +122,8 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "checkpoint_dense": "with -save_checkpoint: 1 = write every feature's state rows; default=0 (only rows that differ from the start state)",
          "load_checkpoint": "sgd, bpr: filename of a checkpoint to continue from (instead of the random initialisation; not with -load_model)",
          "serve": "bf16 | int8: score -out, -metrics and -topk after training from a frozen bf16 or row-wise int8 copy of the model; sgd, sgda, bpr, als",
-         "serve_prune": "dead | seen (with -serve): keep only the rows that can score -- dead: drop features that contribute to no prediction; seen: also those no -train row names"}
+         "serve_prune": "dead | seen (with -serve): keep only the rows that can score -- dead: drop features that contribute to no prediction; seen: also those no -train row names",
+         "devices": "'D0,D1,...': -method sgd with -optimizer adagrad | ftrl over one feature shard per listed device ordinal ('0,0': two shards on device 0)"}
 
 
 def checkpoint_line(what, info):
@@ -336,6 +341,20 @@ def _main(argv):
                 raise ValueError("-init_acc belongs to -optimizer adagrad")
             if not (0.0 < float(a["init_acc"]) < float("inf")):
                 raise ValueError("-init_acc needs a finite value > 0")
+    devices = None
+    if "devices" in a:
+        if method != "sgd" or optimizer not in L.FMLearnSGD.SHARDED_OPTIMIZERS:
+            raise ValueError("-devices belongs to -method sgd with -optimizer adagrad or ftrl: -method %s%s has no form on feature shards"
+                             % (method, " -optimizer " + optimizer if method in ("sgd", "bpr") else ""))
+        for f in ("serve", "topk", "save_checkpoint", "load_checkpoint", "train_weights"):
+            if f in a:
+                raise ValueError("-%s is not supported with -devices: it has no form on feature shards" % f)
+        try:
+            devices = [int(x) for x in split_list(a["devices"])]
+        except ValueError:
+            devices = []
+        if not devices or any(d < 0 for d in devices) or len(devices) > 16:
+            raise ValueError("-devices needs 1 .. 16 device ordinals >= 0: 'D0,D1,...'")
     serve = a.get("serve")
     if "serve" in a:
         if serve not in C.FORMATS:
@@ -569,6 +588,8 @@ def _main(argv):
     l.fm, l.num_iter, l.task = fm, num_iter, (0 if task == "r" else 1)
     l.min_target, l.max_target = min_t, max_t
     l.device = int(a.get("device", "-1"))
+    if devices is not None:
+        l.devices = devices
     if metrics:
         l.extra_metrics = metrics
     if dev_avg:

@@ -829,6 +829,240 @@ int fmx_group_sgd_epoch(fmx_group g, int slot, const fmx_sgd_opts* opts_in, fmx_
   return FMX_OK;
 }
 
+// ---- AdaGrad and FTRL over feature shards (include/fmx.h "fmx_group_adapt_*") ---------------------------
+// The per-coordinate state of a feature lives with the feature: every member holds the session's tables for its n_local rows, opened
+// and closed together.  A batch is the plain group step up to the exchange -- partial sums on every shard, one sum over the shards --
+// and then, on every shard from the same summed buffer, rest_e, the bias recurrence (redundantly, as fmx_sgd_finish runs it) and the
+// rule's owner kernel over the shard's own (batch, feature) segments (stateful_shard_step, fmx_sgd.hip): what one unsharded handle
+// computes, the association of the factor sums aside.  The general schedule only: each shard's own stream, the exchange on the comm
+// stream (RCCL) or shard 0's stream (loopback) with its events; no pipelined and no in-stream form.
+extern "C++" {
+namespace {
+struct RuleNames { const char* epoch; const char* end; const char* session; const char* other; };
+const RuleNames& rule_names(StatefulRule r) {
+  static const RuleNames a{"fmx_group_adapt_epoch", "fmx_group_adapt_end", "fmx_adapt", "fmx_ftrl"};
+  static const RuleNames f{"fmx_group_ftrl_epoch", "fmx_group_ftrl_end", "fmx_ftrl", "fmx_adapt"};
+  return r == STATEFUL_FTRL ? f : a;
+}
+bool rule_open(fmx_handle h, StatefulRule r) { return r == STATEFUL_FTRL ? h->ftrl.nv != nullptr : h->adapt.nv != nullptr; }
+}  // namespace
+}  // extern "C++"
+
+// what every group form refuses whatever the session's state: a destroyed member, a member that is a communicator rank (its peers live in
+// other processes, which this call does not reach)
+static int group_stateful_check(fmx_group g, const char* who) {
+  for (auto m : g->hs) if (!m) return gfail(g, FMX_E_STATE, "a member of the group was destroyed");
+  for (auto m : g->hs) if (m->comm) return gfail(g, FMX_E_UNSUPPORTED, "%s: not supported on communicator ranks (fmx_comm_init_rank)", who);
+  return FMX_OK;
+}
+// ... and a begin on several shards: an open ALS / MCMC session on any of them
+static int group_begin_no_als(fmx_group g, const char* who) {
+  if (g->kind == GROUP_SINGLE) return FMX_OK;                    // (one member: the per-handle call's own rules)
+  for (size_t i = 0; i < g->hs.size(); i++)
+    if (g->hs[i]->als.slot >= 0) return gfail(g, FMX_E_STATE, "%s: an ALS / MCMC session is open on shard %zu (call fmx_group_als_end first)", who, i);
+  return FMX_OK;
+}
+
+int fmx_group_adapt_begin(fmx_group g, const fmx_adapt_opts* opts) {
+  static const char who[] = "fmx_group_adapt_begin";
+  if (!g) return FMX_E_ARG;
+  for (auto m : g->hs) if (!m) return gfail(g, FMX_E_STATE, "a member of the group was destroyed");
+  fmx_handle cur = g->hs[0];
+  float init_acc = 0.f;
+  for (auto m : g->hs) { cur = m; GCHK(g, adapt_begin_check(m, opts, true, &init_acc)); }   // (every refusal of fmx_adapt_begin, on every member, first)
+  int rc = group_stateful_check(g, who); if (rc) return rc;
+  rc = group_begin_no_als(g, who); if (rc) return rc;
+  for (size_t i = 0; i < g->hs.size(); i++) {
+    cur = g->hs[i];
+    rc = adapt_begin_open(cur, opts, init_acc);
+    if (rc) { g->err = fmx_last_error(cur); for (size_t j = 0; j < i; j++) adapt_end_impl(g->hs[j], true); return rc; }   // all or nothing
+  }
+  return FMX_OK;
+}
+
+int fmx_group_ftrl_begin(fmx_group g, const fmx_ftrl_opts* opts) {
+  static const char who[] = "fmx_group_ftrl_begin";
+  if (!g) return FMX_E_ARG;
+  for (auto m : g->hs) if (!m) return gfail(g, FMX_E_STATE, "a member of the group was destroyed");
+  fmx_handle cur = g->hs[0];
+  FtrlState f;
+  for (auto m : g->hs) { cur = m; GCHK(g, ftrl_begin_check(m, opts, true, &f)); }
+  int rc = group_stateful_check(g, who); if (rc) return rc;
+  rc = group_begin_no_als(g, who); if (rc) return rc;
+  for (size_t i = 0; i < g->hs.size(); i++) {
+    cur = g->hs[i];
+    rc = ftrl_begin_open(cur, f);
+    if (rc) { g->err = fmx_last_error(cur); for (size_t j = 0; j < i; j++) ftrl_end_impl(g->hs[j], true); return rc; }
+  }
+  return FMX_OK;
+}
+
+static int group_stateful_end(fmx_group g, StatefulRule rule) {
+  if (!g) return FMX_E_ARG;
+  const RuleNames& nm = rule_names(rule);
+  int rc = group_stateful_check(g, nm.end); if (rc) return rc;
+  for (auto m : g->hs) if (!rule_open(m, rule)) return gfail(g, FMX_E_STATE, "%s before %s_begin", nm.end, nm.session);
+  fmx_handle cur = g->hs[0];
+  for (auto m : g->hs) { cur = m; GCHK(g, rule == STATEFUL_FTRL ? ftrl_end_impl(m, true) : adapt_end_impl(m, true)); }
+  return FMX_OK;
+}
+int fmx_group_adapt_end(fmx_group g) { return group_stateful_end(g, STATEFUL_ADAGRAD); }
+int fmx_group_ftrl_end(fmx_group g) { return group_stateful_end(g, STATEFUL_FTRL); }
+
+static int group_stateful_epoch(fmx_group g, StatefulRule rule, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
+  if (!g) return FMX_E_ARG;
+  const RuleNames& nm = rule_names(rule);
+  int rc = group_stateful_check(g, nm.epoch); if (rc) return rc;
+  const size_t n = g->hs.size();
+  fmx_handle cur = g->hs[0];
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (g->kind == GROUP_SINGLE) {
+    GCHK(g, rule == STATEFUL_FTRL ? ftrl_epoch_impl(cur, true, slot, batch, w0_chunk, stats) : adapt_epoch_impl(cur, true, slot, batch, w0_chunk, stats));
+    return FMX_OK;
+  }
+  // every refusal, on every member, before any launch
+  for (size_t i = 0; i < n; i++) {
+    cur = g->hs[i];
+    GCHK(g, check_slot(cur, slot, true));
+    if (!rule_open(cur, rule)) return gfail(g, FMX_E_STATE, "%s before %s_begin", nm.epoch, nm.session);
+    if (cur->sgda.reg || rule_open(cur, rule == STATEFUL_FTRL ? STATEFUL_ADAGRAD : STATEFUL_FTRL))
+      return gfail(g, FMX_E_STATE, "%s: an SGDA or %s session is open on shard %zu", nm.epoch, nm.other, i);
+    if (cur->als.slot >= 0) return gfail(g, FMX_E_STATE, "%s: an ALS / MCMC session is open on shard %zu (call fmx_group_als_end first)", nm.epoch, i);
+    const Slot& s = cur->slots[slot];
+    if (!s.blocks.empty()) return gfail(g, FMX_E_UNSUPPORTED, "relations are not supported with SGD");   // fm_learn_sgd.h:61-63
+    if (s.weighted) return gfail(g, FMX_E_UNSUPPORTED, "%s: slot %d has row weights on shard %zu; the weighted epochs have no sharded form", nm.epoch, slot, i);
+    if (s.n_rows != g->hs[0]->slots[slot].n_rows) return gfail(g, FMX_E_STATE, "the shards hold different numbers of rows in slot %d", slot);
+  }
+  fmx_handle h0 = g->hs[0];
+  const uint32_t n_rows = h0->slots[slot].n_rows;
+  if (n_rows == 0) return FMX_OK;
+  for (auto m : g->hs) { m->setup_acc = 0.0; m->run_status = 0; }
+  fmx_sgd_opts ro; memset(&ro, 0, sizeof(ro));                    // (only its batch is read: the batch one unsharded handle would choose)
+  ro.mode = FMX_SGD_MINIBATCH; ro.batch = batch;
+  fmx_batch_info bi;
+  cur = h0;
+  GCHK(g, sgd_resolve_batch(cur, cur->slots[slot], &ro, &bi));
+  const uint32_t B = bi.batch;
+  const uint32_t chunk = w0_chunk ? w0_chunk : fmx_default_w0_chunk(h0->cfg.learn_rate, h0->cfg.task);
+  const size_t kp1 = (size_t)h0->KP + 1;
+  const size_t cap = (size_t)std::min<uint32_t>(B, n_rows) * kp1;
+  for (size_t i = 0; i < n; i++) { cur = g->hs[i]; GCHK(g, ensure_xbuf(cur, cap)); GCHK(g, stateful_shard_prepare(cur, slot, B)); }
+  HIPCHK(h0, hipSetDevice(h0->device));
+  HIPCHK(h0, hipEventRecord(h0->ev0, h0->stream));
+  const uint64_t n_batch = ((uint64_t)n_rows + B - 1) / B;
+  for (uint64_t b = 0; b < n_batch; b++) {
+    const uint32_t nb = (uint32_t)std::min<uint64_t>(B, n_rows - b * B);
+    const int which = (int)(b & 1);
+    for (size_t i = 0; i < n; i++) { cur = g->hs[i]; GCHK(g, fmx_sgd_partial(cur, slot, b * B, nb, cur->xbuf[which], cur->stream)); }
+    rc = exchange_begin(g, which, (size_t)nb * kp1);
+    if (rc == FMX_OK) rc = exchange_end(g, which);
+    if (rc) { g->err = g->hs[0]->err; return rc; }
+    for (size_t i = 0; i < n; i++) { cur = g->hs[i]; GCHK(g, stateful_shard_step(cur, slot, rule, b * B, nb, B, chunk, sum_of(g, i, which))); }
+  }
+  for (size_t i = 0; i < n; i++) { cur = g->hs[i]; GCHK(g, fmx_synchronize(cur)); }
+  HIPCHK(h0, hipSetDevice(h0->device));
+  HIPCHK(h0, hipEventRecord(h0->ev1, h0->stream));
+  HIPCHK(h0, hipEventSynchronize(h0->ev1));
+  if (stats) {
+    float ms = 0;
+    HIPCHK(h0, hipEventElapsedTime(&ms, h0->ev0, h0->ev1));
+    stats->rows = n_rows; stats->batches = n_batch; stats->device_seconds = ms * 1e-3;
+    stats->main_kernel_seconds = stats->device_seconds; stats->main_kernel_launches = n_batch;
+    for (auto m : g->hs) stats->max_feature_count = std::max(stats->max_feature_count, m->slots[slot].max_seg_count);
+    stats->batch_used = bi.batch; stats->collision_mass = bi.collision_mass; stats->batch_gain = bi.batch_gain; stats->status = bi.status;
+    stats->w0_chunk_used = chunk;
+    for (auto m : g->hs) { stats->setup_seconds = std::max(stats->setup_seconds, m->setup_acc); stats->status |= m->run_status; }
+  }
+  return FMX_OK;
+}
+int fmx_group_adapt_epoch(fmx_group g, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
+  return group_stateful_epoch(g, STATEFUL_ADAGRAD, slot, batch, w0_chunk, stats);
+}
+int fmx_group_ftrl_epoch(fmx_group g, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
+  return group_stateful_epoch(g, STATEFUL_FTRL, slot, batch, w0_chunk, stats);
+}
+
+// the state rows of `count` features named by GLOBAL id, in any order, repeats allowed: every id goes to the shard that owns it (the
+// mapping of fmx_shard_place / fmx_get_param_rows), each shard gathers its list from its tables, and the rows return to the caller's
+// positions.  outs: nt pairs {linear weights' state [count], factors' state [count][num_factor]}
+static int group_state_rows(fmx_group g, StatefulRule rule, const uint32_t* ids, uint32_t count, double* const (*outs)[2], int nt) {
+  fmx_handle h0 = g->hs[0];
+  const int k = h0->cfg.num_factor;
+  const size_t n = g->hs.size();
+  for (uint32_t i = 0; i < count; i++)
+    if (ids[i] >= h0->cfg.num_attribute) return gfail(g, FMX_E_ARG, "feature id %u >= num_attribute", ids[i]);
+  const Shard sh = make_shard(h0->cfg);
+  const uint32_t W = (uint32_t)std::max(h0->cfg.shard_world, 1);
+  std::vector<std::vector<uint32_t>> own_ids(n), own_pos(n);
+  for (uint32_t i = 0; i < count; i++) {
+    const size_t o = W > 1 ? sh.placed(ids[i]) % W : 0;
+    own_ids[o].push_back(ids[i]); own_pos[o].push_back(i);
+  }
+  fmx_handle cur = h0;
+  std::vector<double> tw, tv;
+  for (size_t o = 0; o < n; o++) {
+    const uint32_t c = (uint32_t)own_ids[o].size();
+    if (!c) continue;
+    cur = g->hs[o];
+    tw.assign((size_t)nt * c, 0.0); tv.assign((size_t)nt * c * (size_t)std::max(k, 1), 0.0);
+    double* w0p = tw.data(); double* v0p = tv.data();
+    double* w1p = tw.data() + c; double* v1p = tv.data() + (size_t)c * std::max(k, 1);
+    if (rule == STATEFUL_FTRL) GCHK(g, ftrl_state_rows_impl(cur, true, own_ids[o].data(), c, w0p, v0p, w1p, v1p));
+    else GCHK(g, adapt_state_rows_impl(cur, true, own_ids[o].data(), c, w0p, v0p));
+    for (int t = 0; t < nt; t++) {
+      const double* sw = t ? w1p : w0p; const double* sv = t ? v1p : v0p;
+      for (uint32_t j = 0; j < c; j++) {
+        const uint32_t at = own_pos[o][j];
+        outs[t][0][at] = sw[j];
+        if (k > 0) memcpy(outs[t][1] + (size_t)at * k, sv + (size_t)j * k, (size_t)k * sizeof(double));
+      }
+    }
+  }
+  return FMX_OK;
+}
+
+int fmx_group_adapt_get_state_rows(fmx_group g, const uint32_t* ids, uint32_t count, double* nw_out, double* nv_out) {
+  static const char who[] = "fmx_group_adapt_get_state_rows";
+  if (!g) return FMX_E_ARG;
+  int rc = group_stateful_check(g, who); if (rc) return rc;
+  fmx_handle cur = g->hs[0];
+  if (g->kind == GROUP_SINGLE) { GCHK(g, adapt_state_rows_impl(cur, true, ids, count, nw_out, nv_out)); return FMX_OK; }
+  if (!ids || !nw_out || (cur->cfg.num_factor > 0 && !nv_out)) return gfail(g, FMX_E_ARG, "%s: ids / nw_out / nv_out is NULL", who);
+  for (auto m : g->hs) if (!m->adapt.nv) return gfail(g, FMX_E_STATE, "%s before fmx_adapt_begin", who);
+  double* const outs[1][2] = {{nw_out, nv_out}};
+  return group_state_rows(g, STATEFUL_ADAGRAD, ids, count, outs, 1);
+}
+
+int fmx_group_ftrl_get_state_rows(fmx_group g, const uint32_t* ids, uint32_t count, double* zw, double* zv, double* nw, double* nv) {
+  static const char who[] = "fmx_group_ftrl_get_state_rows";
+  if (!g) return FMX_E_ARG;
+  int rc = group_stateful_check(g, who); if (rc) return rc;
+  fmx_handle cur = g->hs[0];
+  if (g->kind == GROUP_SINGLE) { GCHK(g, ftrl_state_rows_impl(cur, true, ids, count, zw, zv, nw, nv)); return FMX_OK; }
+  if (!ids || !zw || !nw || (cur->cfg.num_factor > 0 && (!zv || !nv))) return gfail(g, FMX_E_ARG, "%s: ids / zw / zv / nw / nv is NULL", who);
+  for (auto m : g->hs) if (!m->ftrl.nv) return gfail(g, FMX_E_STATE, "%s before fmx_ftrl_begin", who);
+  double* const outs[2][2] = {{zw, zv}, {nw, nv}};
+  return group_state_rows(g, STATEFUL_FTRL, ids, count, outs, 2);
+}
+
+// fmx_param_sparsity over the shards: every feature has one owner, so the shards' integer counts add up to the unsharded handle's
+int fmx_group_param_sparsity(fmx_group g, fmx_sparsity* out) {
+  static const char who[] = "fmx_group_param_sparsity";
+  if (!g) return FMX_E_ARG;
+  int rc = group_stateful_check(g, who); if (rc) return rc;
+  if (!out) return gfail(g, FMX_E_ARG, "%s: out is NULL", who);
+  fmx_handle cur = g->hs[0];
+  memset(out, 0, sizeof(*out));
+  for (auto m : g->hs) {
+    cur = m;
+    fmx_sparsity sp;
+    GCHK(g, param_sparsity_impl(m, true, &sp));
+    out->features += sp.features; out->w_zero += sp.w_zero; out->v_coords += sp.v_coords; out->v_zero += sp.v_zero;
+    out->v_zero_rows += sp.v_zero_rows; out->dead_features += sp.dead_features;
+  }
+  return FMX_OK;
+}
+
 // kept blocks on a shard: the partial sums of every block's rows over the shard's own block attributes (into BlockRows::pbuf, once
 // per fmx_group_predict), and of a chunk of main rows (S [nb][KP], c [nb]) plus -- through the mappings -- those block sums
 static int kept_block_partials(fmx_handle h, const Slot& s) {

@@ -390,6 +390,26 @@ int adapt_tables(fmx_handle h, const char* who);
 int adapt_start_state(fmx_handle h);
 int ftrl_tables(fmx_handle h, const char* who);
 int ftrl_start_state(fmx_handle h);
+// fmx_sgd.hip, for the group forms fmx_group_adapt_* / fmx_group_ftrl_* / fmx_group_param_sparsity (fmx_comm.hip).  The *_impl functions
+// are the per-handle entry points with in_group = true: the call comes from the group the handle is a member of, so the refusal of
+// feature shards and group members is left out and everything else -- codes, messages, work -- is the entry point's own.  *_begin_check
+// is every refusal of a begin (no device work), *_begin_open the tables and the start state: a group checks all members before it opens any.
+int adapt_begin_check(fmx_handle h, const fmx_adapt_opts* opts, bool in_group, float* init_acc_out);
+int adapt_begin_open(fmx_handle h, const fmx_adapt_opts* opts, float init_acc);
+int adapt_epoch_impl(fmx_handle h, bool in_group, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats);
+int adapt_state_rows_impl(fmx_handle h, bool in_group, const uint32_t* ids, uint32_t count, double* nw_out, double* nv_out);
+int adapt_end_impl(fmx_handle h, bool in_group);
+int ftrl_begin_check(fmx_handle h, const fmx_ftrl_opts* opts, bool in_group, FtrlState* out);
+int ftrl_begin_open(fmx_handle h, const FtrlState& constants);
+int ftrl_epoch_impl(fmx_handle h, bool in_group, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats);
+int ftrl_state_rows_impl(fmx_handle h, bool in_group, const uint32_t* ids, uint32_t count, double* zw, double* zv, double* nw, double* nv);
+int ftrl_end_impl(fmx_handle h, bool in_group);
+int param_sparsity_impl(fmx_handle h, bool in_group, fmx_sparsity* out);
+// one shard's share of a stateful epoch over feature shards: what stateful_epoch does in front of its loop, and steps 3 - 6 of a batch
+// from the exchanged sums (rest_e, the bias recurrence, the shard's segments, the owner kernel of `rule`) on the shard's own stream
+enum StatefulRule { STATEFUL_ADAGRAD = 1, STATEFUL_FTRL = 2 };
+int stateful_shard_prepare(fmx_handle h, int slot, uint32_t B);
+int stateful_shard_step(fmx_handle h, int slot, StatefulRule rule, uint64_t row0, uint32_t nb, uint32_t B, uint32_t chunk, const float* d_sum);
 void als_free(fmx_handle h);                                             // fmx_als.hip
 enum { GROUP_SINGLE = 0, GROUP_LOOPBACK = 1, GROUP_RCCL = 2 };
 struct fmx_group_s {                      // fmx_comm.hip

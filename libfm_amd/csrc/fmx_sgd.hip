@@ -1564,21 +1564,28 @@ extern "C++" int adapt_start_state(fmx_handle h) {
   return FMX_OK;
 }
 
-int fmx_adapt_begin(fmx_handle h, const fmx_adapt_opts* opts) {
+// fmx_adapt_begin in two halves, so that fmx_group_adapt_begin (fmx_comm.hip) can refuse for every member before it opens a session on
+// any: adapt_begin_check is every refusal (no device work; in_group: the handle is a member of the group that asks, so the handle-kind
+// refusal is the group's business), adapt_begin_open the tables and the start state
+extern "C++" int adapt_begin_check(fmx_handle h, const fmx_adapt_opts* opts, bool in_group, float* init_acc_out) {
   if (!h) return FMX_E_ARG;
   if (!opts) return fail(h, FMX_E_ARG, "fmx_adapt_begin: opts is NULL");
   if (opts->rule != FMX_ADAPT_ADAGRAD) return fail(h, FMX_E_ARG, "fmx_adapt_begin: unknown rule %u", opts->rule);
   if (opts->flags != 0) return fail(h, FMX_E_ARG, "fmx_adapt_begin: flags must be 0");
   if (!(opts->init_acc >= 0.0) || std::isinf(opts->init_acc)) return fail(h, FMX_E_ARG, "fmx_adapt_begin: init_acc must be finite and >= 0 (0 = 1.0)");
   if (!(opts->learn_rate >= 0.0)) return fail(h, FMX_E_ARG, "fmx_adapt_begin: learn_rate must be >= 0 (0 = fmx_config::learn_rate)");
-  int rc = adapt_check_handle(h, "fmx_adapt_begin"); if (rc) return rc;
+  if (!in_group) { int rc = adapt_check_handle(h, "fmx_adapt_begin"); if (rc) return rc; }
   if (h->sgda.reg) return fail(h, FMX_E_STATE, "fmx_adapt_begin: an SGDA session is open (call fmx_sgda_end first)");
   if (h->ftrl.nv) return fail(h, FMX_E_STATE, "fmx_adapt_begin: an fmx_ftrl session is open (call fmx_ftrl_end first)");
   const float init_acc = opts->init_acc > 0.0 ? (float)opts->init_acc : 1.0f;
   if (!(init_acc > 0.f) || std::isinf(init_acc)) return fail(h, FMX_E_ARG, "fmx_adapt_begin: init_acc %g is not a positive fp32 number", opts->init_acc);
+  *init_acc_out = init_acc;
+  return FMX_OK;
+}
+extern "C++" int adapt_begin_open(fmx_handle h, const fmx_adapt_opts* opts, float init_acc) {
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  rc = adapt_tables(h, "fmx_adapt_begin"); if (rc) return rc;   // (again = reset: the tables are there)
+  int rc = adapt_tables(h, "fmx_adapt_begin"); if (rc) return rc;   // (again = reset: the tables are there)
   h->adapt.eta = (float)(opts->learn_rate > 0.0 ? opts->learn_rate : h->cfg.learn_rate);
   h->adapt.init_acc = init_acc;
   rc = adapt_start_state(h); if (rc) return rc;
@@ -1586,32 +1593,49 @@ int fmx_adapt_begin(fmx_handle h, const fmx_adapt_opts* opts) {
   return FMX_OK;
 }
 
-int fmx_adapt_end(fmx_handle h) {
+int fmx_adapt_begin(fmx_handle h, const fmx_adapt_opts* opts) {
+  float init_acc = 0.f;
+  int rc = adapt_begin_check(h, opts, false, &init_acc); if (rc) return rc;
+  return adapt_begin_open(h, opts, init_acc);
+}
+
+// (in_group, here and below: the call comes from the group the handle is a member of -- fmx_group_adapt_* / fmx_group_ftrl_*,
+// fmx_comm.hip; a member's session belongs to its group, so the per-handle entry points keep refusing it)
+extern "C++" int adapt_end_impl(fmx_handle h, bool in_group) {
   if (!h) return FMX_E_ARG;
   if (!h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_adapt_end before fmx_adapt_begin");
+  if (!in_group) { int rc = adapt_check_handle(h, "fmx_adapt_end"); if (rc) return rc; }
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   adapt_free(h);
   return FMX_OK;
 }
+int fmx_adapt_end(fmx_handle h) { return adapt_end_impl(h, false); }
 
 // the gather of fmx_get_param_rows over nt state tables, one after the other: outs[t] = {the linear weights' state, the factors' state}
 static int state_rows(fmx_handle h, const char* what, const uint32_t* ids, uint32_t count, const Tab* tabs, double* const (*outs)[2], int nt) {
-  for (uint32_t i = 0; i < count; i++)
+  const Shard sh = make_shard(h->cfg);
+  for (uint32_t i = 0; i < count; i++) {
     if (ids[i] >= h->cfg.num_attribute) return fail(h, FMX_E_ARG, "feature id %u >= num_attribute", ids[i]);
+    if (!sh.owns(ids[i])) return fail(h, FMX_E_ARG, "feature id %u is not on this shard", ids[i]);   // (the group routes every id to its owner)
+  }
   if (count == 0) return FMX_OK;
   return gather_rows(h, what, ids, count, nt, outs, [&](int t, dim3 grid, const uint32_t* d_ids, double* d_w, double* d_v) {
-    hipLaunchKernelGGL(k_fetch_rows<RowsF32>, grid, dim3(256), 0, h->stream, d_ids, count, h->cfg.num_factor, make_shard(h->cfg), RowsF32{tabs[t]}, d_w, d_v);
+    hipLaunchKernelGGL(k_fetch_rows<RowsF32>, grid, dim3(256), 0, h->stream, d_ids, count, h->cfg.num_factor, sh, RowsF32{tabs[t]}, d_w, d_v);
   });
 }
 
-int fmx_adapt_get_state_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double* nw_out, double* nv_out) {
+extern "C++" int adapt_state_rows_impl(fmx_handle h, bool in_group, const uint32_t* ids, uint32_t count, double* nw_out, double* nv_out) {
   if (!h) return FMX_E_ARG;
   if (!ids || !nw_out || (h->cfg.num_factor > 0 && !nv_out)) return fail(h, FMX_E_ARG, "fmx_adapt_get_state_rows: ids / nw_out / nv_out is NULL");
   if (!h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_adapt_get_state_rows before fmx_adapt_begin");
+  if (!in_group) { int rc = adapt_check_handle(h, "fmx_adapt_get_state_rows"); if (rc) return rc; }
   const Tab tabs[1] = {Tab{h->adapt.nv, h->adapt.nw, h->tb.rs, 1u}};
   double* const outs[1][2] = {{nw_out, nv_out}};
   return state_rows(h, "fmx_adapt_get_state_rows", ids, count, tabs, outs, 1);
+}
+int fmx_adapt_get_state_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double* nw_out, double* nv_out) {
+  return adapt_state_rows_impl(h, false, ids, count, nw_out, nv_out);
 }
 
 // step 2 of a batch on a slot with weights (include/fmx.h "fmx_set_row_weights"): k_scan_weighted, the one-wavefront chain with
@@ -1636,6 +1660,21 @@ static int launch_scan_weighted(fmx_handle h, const float* rest, const float* ta
 // batch rule's row sums and bias recurrence (fmx_sgda_epoch_minibatch's three launches), then launch_owner(sw, hy, st) starts the one
 // kernel in which an owner per (batch, feature) segment takes the rule's step.  The bias stays plain SGD at fmx_config::learn_rate.
 extern "C++" {
+// the tail of one batch, shared by stateful_epoch and the group driver's shard step (stateful_shard_step): from the batch's factor sums S
+// and rest[] -- the handle's own (k_rowsums) or derived from the exchanged sums of the shards -- the bias recurrence with the
+// multipliers into h->mult, then the owner kernel over the (batch, feature) segments the handle holds of batch row0 / B
+template <class Owner>
+static int stateful_batch_tail(fmx_handle h, const Slot& s, uint64_t row0, uint32_t nb, uint32_t B, uint32_t chunk, const Hyper& hy,
+                               const float* S, const float* rest, hipStream_t st, Owner launch_owner) {
+  int rc = s.weighted ? launch_scan_weighted(h, rest, s.target + row0, s.weight + row0, nb, chunk, hy, h->mult, st)
+                      : launch_scan(h, rest, s.target + row0, nb, chunk, hy, h->mult, st);
+  if (rc) return rc;
+  const SegWork sw = seg_work_dense(h, s, (size_t)(row0 / B), S, h->mult);
+  if (sw.nseg) { rc = launch_owner(sw, hy, st); if (rc) return rc; }
+  HIPCHK(h, hipGetLastError());
+  return FMX_OK;
+}
+
 template <class Owner>
 static int stateful_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats, Owner launch_owner) {
   { int _rc = lag_flush(h); if (_rc) return _rc; }
@@ -1665,12 +1704,7 @@ static int stateful_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_ch
     float* S = h->partial;
     float* rest = S + (size_t)nb * h->KP;
     KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, st, s.ent, s.row_ptr, row0, nb, RowsF32{h->tb}, h->cfg.k1, S, rest));
-    rc = s.weighted ? launch_scan_weighted(h, rest, s.target + row0, s.weight + row0, nb, chunk, hy, h->mult, st)
-                    : launch_scan(h, rest, s.target + row0, nb, chunk, hy, h->mult, st);
-    if (rc) return rc;
-    const SegWork sw = seg_work_dense(h, s, (size_t)(row0 / B), S, h->mult);
-    if (sw.nseg) { rc = launch_owner(sw, hy, st); if (rc) return rc; }
-    HIPCHK(h, hipGetLastError());
+    rc = stateful_batch_tail(h, s, row0, nb, B, chunk, hy, S, rest, st, launch_owner); if (rc) return rc;
     batches++;
   }
   HIPCHK(h, hipEventRecord(h->ev1, st));
@@ -1691,17 +1725,61 @@ static int stateful_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_ch
 }
 }  // extern "C++"
 
-int fmx_adapt_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
+// the owner kernels of the two rules on the handle's own tables (a shard's: n_local rows, local feature ids)
+static int launch_adapt_owner(fmx_handle h, const SegWork& sw, const Hyper& hy, hipStream_t st) {
+  const AdagradRule rule{{Tab{h->adapt.nv, h->adapt.nw, h->tb.rs, 1u}}, h->adapt.eta};
+  KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_adapt_apply_seg<KP, AdaptU<KP>::value>), ((uint64_t)sw.nseg + 63) / 64, st, sw, h->tb, rule, hy));
+  return FMX_OK;
+}
+static int launch_ftrl_owner(fmx_handle h, const SegWork& sw, const Hyper& hy, hipStream_t st) {
+  const FtrlState& fs = h->ftrl;
+  const FtrlRule rule{{Tab{fs.zv, fs.zw, h->tb.rs, 1u}, Tab{fs.nv, fs.nw, h->tb.rs, 1u}}, FtrlHyper{fs.inv_alpha, fs.beta, fs.l1_w, fs.l1_v, fs.l2_w, fs.l2_v}};
+  KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_ftrl_apply_seg<KP, FtrlU<KP>::value>), ((uint64_t)sw.nseg + 63) / 64, st, sw, h->tb, rule, hy));
+  return FMX_OK;
+}
+
+extern "C++" int adapt_epoch_impl(fmx_handle h, bool in_group, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
   int rc = check_slot(h, slot, true);
   if (rc) return rc;
   if (!h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_adapt_epoch before fmx_adapt_begin");
-  rc = adapt_check_handle(h, "fmx_adapt_epoch"); if (rc) return rc;
+  if (!in_group) { rc = adapt_check_handle(h, "fmx_adapt_epoch"); if (rc) return rc; }
   if (h->sgda.reg) return fail(h, FMX_E_STATE, "fmx_adapt_epoch: an SGDA session is open (call fmx_sgda_end first)");
   rc = slot_in_session(h, slot, "fmx_adapt_epoch"); if (rc) return rc;
-  const AdagradRule rule{{Tab{h->adapt.nv, h->adapt.nw, h->tb.rs, 1u}}, h->adapt.eta};
   return stateful_epoch(h, slot, batch, w0_chunk, stats, [&](const SegWork& sw, const Hyper& hy, hipStream_t st) -> int {
-    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_adapt_apply_seg<KP, AdaptU<KP>::value>), ((uint64_t)sw.nseg + 63) / 64, st, sw, h->tb, rule, hy));
-    return FMX_OK;
+    return launch_adapt_owner(h, sw, hy, st);
+  });
+}
+int fmx_adapt_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
+  return adapt_epoch_impl(h, false, slot, batch, w0_chunk, stats);
+}
+
+// ---- one shard's share of a stateful epoch over feature shards (fmx_group_adapt_epoch / fmx_group_ftrl_epoch, fmx_comm.hip) ----
+// The driver has checked the group, the slot and the session on every member.  stateful_shard_prepare: what stateful_epoch does in
+// front of its loop (the bias back in h->w0, the shard's segments for batch B, its scratch).  stateful_shard_step: steps 3 - 6 of a batch
+// on the shard's own stream from the EXCHANGED sums d_sum ([nb][KP] factor sums, then [nb] scalars) -- rest_e, then the batch tail of
+// stateful_epoch with the owner kernel of `rule` on the shard's tables.  Every shard runs the same recurrence from the same sums.
+extern "C++" int stateful_shard_prepare(fmx_handle h, int slot, uint32_t B) {
+  { int _rc = lag_flush(h); if (_rc) return _rc; }
+  HIPCHK(h, hipSetDevice(h->device));
+  Slot& s = h->slots[slot];
+  int rc = ensure_segments(h, s, B); if (rc) return rc;
+  const uint32_t Bc = std::min<uint32_t>(B, std::max<uint32_t>(s.n_rows, 1u));
+  rc = ensure_scratch(h, Bc, Bc); if (rc) return rc;
+  touch_w(h);
+  return FMX_OK;
+}
+extern "C++" int stateful_shard_step(fmx_handle h, int slot, StatefulRule rule, uint64_t row0, uint32_t nb, uint32_t B, uint32_t chunk, const float* d_sum) {
+  HIPCHK(h, hipSetDevice(h->device));
+  const Slot& s = h->slots[slot];
+  if (nb == 0 || row0 + nb > s.n_rows || nb > h->cap || nb > h->cap_rest) return fail(h, FMX_E_ARG, "stateful_shard_step: rows outside the slot or the scratch");
+  const Hyper hy = make_hyper(h->cfg);
+  hipStream_t st = h->stream;
+  const float* S = d_sum;
+  const float* c = d_sum + (size_t)nb * h->KP;
+  KP_SWITCH(h->KP, hipLaunchKernelGGL((k_rest_from_partial<KP>), dim3(wave_grid((nb + Map<KP>::EPI - 1) / Map<KP>::EPI)), dim3(256), 0, st, S, c, nb, h->rest));
+  HIPCHK(h, hipGetLastError());
+  return stateful_batch_tail(h, s, row0, nb, B, chunk, hy, S, h->rest, st, [&](const SegWork& sw, const Hyper& hyp, hipStream_t stp) -> int {
+    return rule == STATEFUL_FTRL ? launch_ftrl_owner(h, sw, hyp, stp) : launch_adapt_owner(h, sw, hyp, stp);
   });
 }
 
@@ -1740,7 +1818,9 @@ extern "C++" int ftrl_start_state(fmx_handle h) {
   return FMX_OK;
 }
 
-int fmx_ftrl_begin(fmx_handle h, const fmx_ftrl_opts* opts) {
+// fmx_ftrl_begin in two halves, as fmx_adapt_begin: ftrl_begin_check is every refusal and leaves the rule's constants in *out (its table
+// pointers null), ftrl_begin_open the tables and the start state
+extern "C++" int ftrl_begin_check(fmx_handle h, const fmx_ftrl_opts* opts, bool in_group, FtrlState* out) {
   if (!h) return FMX_E_ARG;
   if (!opts) return fail(h, FMX_E_ARG, "fmx_ftrl_begin: opts is NULL");
   if (opts->flags != 0) return fail(h, FMX_E_ARG, "fmx_ftrl_begin: flags must be 0");
@@ -1760,13 +1840,18 @@ int fmx_ftrl_begin(fmx_handle h, const fmx_ftrl_opts* opts) {
   if (std::isinf(f.beta) || std::isinf(f.l1_w) || std::isinf(f.l1_v) || std::isinf(init_acc) || std::isinf(base + f.l2_w) || std::isinf(base + f.l2_v) ||
       !(base + f.l2_w > 0.f) || !(base + f.l2_v > 0.f))
     return fail(h, FMX_E_ARG, "fmx_ftrl_begin: the options leave the fp32 range ((beta + sqrt(init_acc)) / alpha + l2 = %g)", (double)(base + f.l2_v));
-  int rc = adapt_check_handle(h, "fmx_ftrl_begin"); if (rc) return rc;
+  if (!in_group) { int rc = adapt_check_handle(h, "fmx_ftrl_begin"); if (rc) return rc; }
   if (h->sgda.reg) return fail(h, FMX_E_STATE, "fmx_ftrl_begin: an SGDA session is open (call fmx_sgda_end first)");
   if (h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_ftrl_begin: an fmx_adapt session is open (call fmx_adapt_end first)");
+  *out = f;
+  return FMX_OK;
+}
+extern "C++" int ftrl_begin_open(fmx_handle h, const FtrlState& constants) {
+  FtrlState f = constants;
   { int _rc = lag_flush(h); if (_rc) return _rc; }              // (z is derived from the parameters: they have to be current)
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  rc = ftrl_tables(h, "fmx_ftrl_begin"); if (rc) return rc;     // (again = reset: the tables are there)
+  int rc = ftrl_tables(h, "fmx_ftrl_begin"); if (rc) return rc; // (again = reset: the tables are there)
   f.zw = h->ftrl.zw; f.zv = h->ftrl.zv; f.nw = h->ftrl.nw; f.nv = h->ftrl.nv;
   h->ftrl = f;
   rc = ftrl_start_state(h); if (rc) return rc;
@@ -1774,48 +1859,63 @@ int fmx_ftrl_begin(fmx_handle h, const fmx_ftrl_opts* opts) {
   return FMX_OK;
 }
 
-int fmx_ftrl_end(fmx_handle h) {
+int fmx_ftrl_begin(fmx_handle h, const fmx_ftrl_opts* opts) {
+  FtrlState f;
+  int rc = ftrl_begin_check(h, opts, false, &f); if (rc) return rc;
+  return ftrl_begin_open(h, f);
+}
+
+extern "C++" int ftrl_end_impl(fmx_handle h, bool in_group) {
   if (!h) return FMX_E_ARG;
   if (!h->ftrl.nv) return fail(h, FMX_E_STATE, "fmx_ftrl_end before fmx_ftrl_begin");
+  if (!in_group) { int rc = adapt_check_handle(h, "fmx_ftrl_end"); if (rc) return rc; }
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   ftrl_free(h);
   return FMX_OK;
 }
+int fmx_ftrl_end(fmx_handle h) { return ftrl_end_impl(h, false); }
 
-int fmx_ftrl_get_state_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double* zw, double* zv, double* nw, double* nv) {
+extern "C++" int ftrl_state_rows_impl(fmx_handle h, bool in_group, const uint32_t* ids, uint32_t count, double* zw, double* zv, double* nw, double* nv) {
   if (!h) return FMX_E_ARG;
   if (!ids || !zw || !nw || (h->cfg.num_factor > 0 && (!zv || !nv))) return fail(h, FMX_E_ARG, "fmx_ftrl_get_state_rows: ids / zw / zv / nw / nv is NULL");
   if (!h->ftrl.nv) return fail(h, FMX_E_STATE, "fmx_ftrl_get_state_rows before fmx_ftrl_begin");
+  if (!in_group) { int rc = adapt_check_handle(h, "fmx_ftrl_get_state_rows"); if (rc) return rc; }
   const Tab tabs[2] = {Tab{h->ftrl.zv, h->ftrl.zw, h->tb.rs, 1u}, Tab{h->ftrl.nv, h->ftrl.nw, h->tb.rs, 1u}};
   double* const outs[2][2] = {{zw, zv}, {nw, nv}};
   return state_rows(h, "fmx_ftrl_get_state_rows", ids, count, tabs, outs, 2);
 }
+int fmx_ftrl_get_state_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double* zw, double* zv, double* nw, double* nv) {
+  return ftrl_state_rows_impl(h, false, ids, count, zw, zv, nw, nv);
+}
 
 // one epoch: stateful_epoch with k_ftrl_apply_seg as the owner kernel.  regw / regv are not read (L2 lives in the proximal step).
-int fmx_ftrl_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
+extern "C++" int ftrl_epoch_impl(fmx_handle h, bool in_group, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
   int rc = check_slot(h, slot, true);
   if (rc) return rc;
   if (!h->ftrl.nv) return fail(h, FMX_E_STATE, "fmx_ftrl_epoch before fmx_ftrl_begin");
-  rc = adapt_check_handle(h, "fmx_ftrl_epoch"); if (rc) return rc;
+  if (!in_group) { rc = adapt_check_handle(h, "fmx_ftrl_epoch"); if (rc) return rc; }
   if (h->sgda.reg || h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_ftrl_epoch: an SGDA or fmx_adapt session is open");
   rc = slot_in_session(h, slot, "fmx_ftrl_epoch"); if (rc) return rc;
-  const FtrlState& fs = h->ftrl;
-  const FtrlRule rule{{Tab{fs.zv, fs.zw, h->tb.rs, 1u}, Tab{fs.nv, fs.nw, h->tb.rs, 1u}}, FtrlHyper{fs.inv_alpha, fs.beta, fs.l1_w, fs.l1_v, fs.l2_w, fs.l2_v}};
   return stateful_epoch(h, slot, batch, w0_chunk, stats, [&](const SegWork& sw, const Hyper& hy, hipStream_t st) -> int {
-    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_ftrl_apply_seg<KP, FtrlU<KP>::value>), ((uint64_t)sw.nseg + 63) / 64, st, sw, h->tb, rule, hy));
-    return FMX_OK;
+    return launch_ftrl_owner(h, sw, hy, st);
   });
+}
+int fmx_ftrl_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
+  return ftrl_epoch_impl(h, false, slot, batch, w0_chunk, stats);
 }
 
 // how many coordinates of the model are exactly zero (include/fmx.h "fmx_param_sparsity"): one pass of k_param_sparsity
-int fmx_param_sparsity(fmx_handle h, fmx_sparsity* out) {
+// (in_group on a feature shard: the counts over the features the shard owns -- its table holds exactly those rows, rank r of W owning
+// ceil((n - r) / W) of n; fmx_group_param_sparsity sums the shards' counts)
+extern "C++" int param_sparsity_impl(fmx_handle h, bool in_group, fmx_sparsity* out) {
   if (!h) return FMX_E_ARG;
   if (!out) return fail(h, FMX_E_ARG, "fmx_param_sparsity: out is NULL");
-  int rc = adapt_check_handle(h, "fmx_param_sparsity"); if (rc) return rc;
+  if (!in_group) { int rc = adapt_check_handle(h, "fmx_param_sparsity"); if (rc) return rc; }
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   HIPCHK(h, hipSetDevice(h->device));
-  const uint64_t n = h->cfg.num_attribute;
+  const uint64_t W = (uint64_t)std::max(h->cfg.shard_world, 1), R = (uint64_t)h->cfg.shard_rank;
+  const uint64_t n = W > 1 ? (h->cfg.num_attribute > R ? (h->cfg.num_attribute - R + W - 1) / W : 0) : h->cfg.num_attribute;
   const int k = h->cfg.num_factor;
   unsigned long long host[4] = {0ull, 0ull, 0ull, 0ull};
   if (n) {
@@ -1837,5 +1937,6 @@ int fmx_param_sparsity(fmx_handle h, fmx_sparsity* out) {
   out->v_zero_rows = host[2]; out->dead_features = host[3];
   return FMX_OK;
 }
+int fmx_param_sparsity(fmx_handle h, fmx_sparsity* out) { return param_sparsity_impl(h, false, out); }
 
 }  // extern "C"

@@ -240,9 +240,15 @@ class FMLearnSGD:
     'ftrl': FTRL-proximal with L1 on the minibatch rule, fmx_ftrl_*, which sets coordinates to exactly zero: ftrl_alpha (0 =
     learn_rate; the bias keeps learn_rate), ftrl_beta, l1_w / l1_v, l2_w / l2_v (None = fm.regw / fm.regv).  Under 'ftrl' an l2 is ONE
     strength per coordinate inside the proximal step, not one per occurrence as regw / regv are in the plain rule, and init_acc is the
-    start value of n as it is given (0 stays 0).  sparsity() counts the zeros of the model under any optimizer."""
+    start value of n as it is given (0 stays 0).  sparsity() counts the zeros of the model under any optimizer.
+    `devices` (None: one handle on `device`) lists device ordinals as on FMLearnALS: with more than one entry the model is split into
+    one feature shard per entry (hashed ownership; "[0, 0]" = two shards on one device) and optimizer 'adagrad' / 'ftrl' train over
+    the shards (capi.Group, fmx_group_adapt_* / fmx_group_ftrl_*): learn, predict, evaluate, evaluate_ex, extra_metrics, set_queries
+    and sparsity() run through the group.  Optimizer 'sgd' has no sharded form here, nor have compact(), recommend(), checkpoints and
+    row weights: each raises NotImplementedError before any device is touched."""
 
     OPTIMIZERS = ("sgd", "adagrad", "ftrl")
+    SHARDED_OPTIMIZERS = ("adagrad", "ftrl")                    # what `devices` with more than one entry is honoured for
     MODES = {"sequential": capi.SGD_SEQUENTIAL, "minibatch": capi.SGD_MINIBATCH, "hogwild": capi.SGD_HOGWILD}
     APPLY = {"default": capi.APPLY_DEFAULT, "atomic": capi.APPLY_ATOMIC, "store": capi.APPLY_STORE,
              "segmented": capi.APPLY_SEGMENTED, "fused": capi.APPLY_FUSED}
@@ -268,10 +274,12 @@ class FMLearnSGD:
         self.l1_w, self.l1_v = 0.0, 0.0
         self.l2_w, self.l2_v = None, None
         self.device = -1
+        self.devices = None                                     # device ordinals of the feature shards (more than one: a capi.Group)
         self.log = []                                           # one dict per iteration (rlog fields)
         self.extra_metrics = ()                                 # classification: "auc" and / or "logloss" per iteration, on stderr and in log
         self.out = sys.stdout
-        self._h = None
+        self._h = None                                          # a capi.Handle, or the capi.Group of the shards
+        self._shards = []
         self._slots = {}
         self._queries = {}                                      # id(data) -> (qid, n_queries) of set_queries
         self._weights = {}                                      # id(data) -> float32 weights of set_weights
@@ -288,6 +296,28 @@ class FMLearnSGD:
         if self.optimizer == "ftrl" and self.mode != "minibatch":
             raise ValueError("optimizer ftrl runs on the minibatch rule: mode %s is not supported" % self.mode)
 
+    def _sharded(self):
+        """`devices` asks for feature shards (more than one entry); decided from the field alone, so that it holds before init()"""
+        return self.devices is not None and len(self.devices) > 1
+
+    def _not_on_shards(self, what):
+        if self._sharded():
+            raise NotImplementedError("%s is not supported on feature shards (devices lists %d GPUs)" % (what, len(self.devices)))
+
+    def _check_devices(self):
+        if not self._sharded():
+            return
+        if type(self) is not FMLearnSGD:
+            raise NotImplementedError("%s has no form on feature shards (devices lists %d GPUs): FMLearnSGD with optimizer %s has"
+                                      % (type(self).__name__, len(self.devices), " | ".join(self.SHARDED_OPTIMIZERS)))
+        if self.optimizer not in self.SHARDED_OPTIMIZERS:
+            raise NotImplementedError("optimizer %s is not supported on feature shards (devices lists %d GPUs): use %s"
+                                      % (self.optimizer, len(self.devices), " | ".join(self.SHARDED_OPTIMIZERS)))
+        if self._checkpoint is not None:
+            self._not_on_shards("load_checkpoint")
+        if self._weights:
+            self._not_on_shards("set_weights")
+
     # fm_learn::init (fm_learn.h:73-91): here it creates the device context and uploads the parameters
     def init(self):
         if self.task not in (TASK_REGRESSION, TASK_CLASSIFICATION):
@@ -295,7 +325,19 @@ class FMLearnSGD:
         if self.learn_rate is None:
             raise ValueError("learn_rate must be set")          # the reference asserts (libfm.cpp:391-392)
         self._check_optimizer()
+        self._check_devices()
         fm = self.fm
+        if self._sharded():
+            devs = [int(d) for d in self.devices]
+            self._shards = [capi.Handle(fm.num_attribute, fm.num_factor, fm.k0, fm.k1, self.task, fm.reg0, fm.regw, fm.regv,
+                                        self.learn_rate, self.min_target, self.max_target, device=d, shard_rank=r,
+                                        shard_world=len(devs), shard_hash=1) for r, d in enumerate(devs)]
+            self._h = capi.Group(self._shards)
+            self._h.set_params(fm.w0, fm.w, fm.v)
+            self._begin_session()
+            return
+        if self.devices is not None and len(self.devices) == 1:
+            self.device = int(self.devices[0])
         self._h = capi.Handle(fm.num_attribute, fm.num_factor, fm.k0, fm.k1, self.task, fm.reg0, fm.regw, fm.regv,
                               self.learn_rate, self.min_target, self.max_target, device=self.device)
         if self._checkpoint is not None:                        # the file's parameters and session, not fm's and a fresh one
@@ -319,6 +361,7 @@ class FMLearnSGD:
         """the exact binary checkpoint of the model on the device and of the open adagrad / ftrl session (fmx_checkpoint_save;
         libfm_amd/checkpoint.py reads the file).  dense: every feature's state rows, not only those that differ from the start
         state.  Returns capi.CkptInfo."""
+        self._not_on_shards("save_checkpoint")
         if self._h is None:
             raise ValueError("save_checkpoint before init()")
         return self._h.checkpoint_save(path, dense=dense)
@@ -329,6 +372,7 @@ class FMLearnSGD:
         file's raises ValueError; a file without a session leaves the optimizer alone, and a fresh session starts from the loaded
         parameters).  Before init() the file is only looked at and init() loads it in place of fm's parameters; after init() it
         is loaded at once.  Neither init() nor learn() begins the session again."""
+        self._not_on_shards("load_checkpoint")
         from . import checkpoint
         with open(path, "rb") as f:
             head = checkpoint.read_header(f.read(checkpoint.HEADER_BYTES))
@@ -394,6 +438,8 @@ class FMLearnSGD:
         scale every row's loss by its weight (the other trainers have no weighted form and learn() refuses); on any set,
         evaluate_weighted(data) and extra_metrics 'wlogloss' report the weighted log loss.  The weights are stored and attached
         when the set is uploaded, like set_queries' ids."""
+        if weights is not None:
+            self._not_on_shards("set_weights")
         if weights is None:
             self._weights.pop(id(data), None)
         else:
@@ -426,6 +472,7 @@ class FMLearnSGD:
     # fm_learn_sgd_element::learn (fm_learn_sgd_element.h:48-78)
     def learn(self, train, test):
         self._check_optimizer()
+        self._check_devices()
         if (self.optimizer == "adagrad") != self._adapt_open or (self.optimizer == "ftrl") != self._ftrl_open:
             raise ValueError("optimizer was changed after init()")
         if id(train) in self._weights and self.optimizer == "sgd":
@@ -483,6 +530,7 @@ class FMLearnSGD:
         prediction of the joined row queries[q] ++ candidates[c], without ever writing it out.  Returns (idx uint32
         [queries, topk], score float64 [queries, topk]), padded with (capi.TOPK_NONE, -inf).  exclude: per query, the candidate
         rows it must not get back (a list of iterables, or a CSR (ptr, idx))."""
+        self._not_on_shards("recommend: top-K retrieval")
         return self._h.topk(*self._topk_slots(queries, candidates), topk, 0, queries.num_cases, exclude)
 
     def _topk_slots(self, queries, candidates):
@@ -499,7 +547,8 @@ class FMLearnSGD:
 
     def compact(self, format="bf16", prune=None):
         """a CompactView: a frozen reduced-precision copy of the model as it stands, to score from (fmx_compact_begin); with
-        prune = "dead" | "seen" one that keeps only the rows that can score (fmx_compact_begin_pruned)"""
+        prune = "dead" | "seen" one that keeps only the rows that can score (fmx_compact_begin_pruned).  Not on feature shards."""
+        self._not_on_shards("compact: the serving snapshot")
         return CompactView(self, format, prune)
 
     # fm_learn_sgd::predict (fm_learn_sgd.h:76-90)
@@ -526,6 +575,9 @@ class FMLearnSGD:
                 self._ftrl_open = False
             self._h.close()
             self._h = None
+        for s in self._shards:
+            s.close()
+        self._shards = []
 
 
 cdf_gaussian = evalmetrics.ref_cdf_gaussian       # random.h:65-67 with the reference's erf polynomial (:45-59)
