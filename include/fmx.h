@@ -1464,6 +1464,64 @@ int fmx_checkpoint_save(fmx_handle h, const char *path, const fmx_ckpt_opts *opt
 int fmx_checkpoint_load(fmx_handle h, const char *path, const fmx_ckpt_opts *opts, fmx_ckpt_info *info /* may be NULL */);
 int fmx_checkpoint_info(const char *path, fmx_ckpt_info *info, char *err, size_t err_len);   /* header only; no handle, no GPU */
 
+/* ---- a serving snapshot as a file, and a handle that serves from it without the model -------------------
+ * fmx_compact_begin* need the fp32 model beside the snapshot they take.  These four calls let a snapshot leave the handle that made it:
+ * fmx_compact_save writes it, straight from its device tables, to a file of its own format (csrc/fmx_snap_format.h, restated by
+ * libfm_amd/compact.py: same conventions and section checksum as the checkpoint, magic "FMXSNAP\0", version 1), and fmx_serve_open
+ * makes a SERVE-ONLY handle from such a file alone: no parameter tables, no placement probe -- its device memory and start-up are the
+ * snapshot's.  Added without an ABI version change: a caller detects the feature by the symbol fmx_compact_save.
+ *
+ * The file holds the format, the geometry (num_attribute, num_factor, k0, k1), task / min_target / max_target (scoring clamps and
+ * links by them), pruned and kept, the int8 block size, the figures of fmx_compact_info and fmx_compact_prune_info as they were when
+ * the snapshot was taken, then the sections w0 (f64); dir (pruned: the rank directory as the device holds it); int8: rows (the P-byte
+ * blocks verbatim); bf16: w (f32) and V (rows of num_factor bf16, WITHOUT the device table's row padding: the file does not depend on
+ * FMX_ROW_STRIDE_KP).  No time stamp, host name or pointer: equal snapshots give byte-identical files.
+ *
+ *   fmx_compact_save  : needs a snapshot (FMX_E_STATE otherwise).  Streams the sections through two pinned buffers, each section's
+ *                       checksum formed on the device; writes `path` + ".tmp" and renames, the .tmp file removed on failure.  Touches
+ *                       neither the model nor the snapshot.  Works on a serve-only handle: saving what was loaded gives the same bytes.
+ *   fmx_compact_load  : the file's num_attribute, num_factor, k0, k1 must equal the handle's (FMX_E_ARG naming the field and both
+ *                       values); task / min / max are NOT compared, the handle's own hold.  The new snapshot is built beside the
+ *                       handle's and replaces it only after every section's checksum -- over what arrived in device memory -- has
+ *                       matched and, for a pruned file, the directory has been validated on the device (bases = running popcounts
+ *                       from 0, no bit at or beyond num_attribute, total = kept: without it a file with valid checksums and a wrong
+ *                       directory would send scoring kernels out of bounds).  ANY failure leaves the handle's snapshot, if any, and
+ *                       its model exactly as they were.  bf16 rows are unpacked to the handle's own row stride, padding +0.
+ *   fmx_snapshot_info : the header alone: no handle, no device.  Fills info (seconds = bytes_compact = 0) or returns FMX_E_ARG with
+ *                       the reason in err (truncated to err_len; may be NULL).
+ *   fmx_serve_open    : a serve-only handle on `device` (-1: the current one), unsharded, whose config is the file's geometry, task
+ *                       and target range; then fmx_compact_load.  On any failure *out = NULL and fmx_last_error(NULL) has the reason.
+ *
+ * A serve-only handle has everything fmx_create makes except the parameter tables.  These calls work on it: fmx_destroy,
+ * fmx_last_error, fmx_get_info (bytes_params = 0), fmx_get_place_info (method 0, no chunks, 0 seconds), fmx_synchronize, the row side
+ * (fmx_upload_rows, fmx_upload_block_rows[_ex], fmx_synth_rows[_ex], fmx_free_rows, fmx_rows_info, fmx_download_rows), and
+ * fmx_compact_predict / _evaluate / _evaluate_ex / _topk / _get_rows / _slot_of / _end / _save / _load.  EVERY other call that takes a
+ * handle -- fmx_compact_begin and fmx_compact_begin_pruned, fmx_comm_init_rank and fmx_group_create with such a member included --
+ * refuses it first thing: FMX_E_STATE "a serve-only handle holds no model", nothing launched, the handle usable afterwards.
+ *
+ * Other refusals, the handle usable afterwards.  FMX_E_ARG: NULL path; a file that cannot be opened or created; whatever the header,
+ * its section table and the file's length show before any byte reaches the device (bad magic or version, a header checksum
+ * mismatch, an unknown format, a geometry no handle can have, kept > num_attribute or kept without pruned, a block size other than
+ * fmx_compact_row_bytes(FMX_COMPACT_INT8, num_factor), a section table that is not the plan of the header's fields, a planned length
+ * other than the file's); a section checksum mismatch or an inconsistent directory, naming the section.  FMX_E_UNSUPPORTED:
+ * fmx_compact_save / _load on a feature shard or communicator rank. */
+typedef struct fmx_snap_info {
+  uint32_t version, format;           /* format: FMX_COMPACT_BF16 | FMX_COMPACT_INT8 */
+  uint64_t num_attribute; uint32_t num_factor, k0, k1; int32_t task;
+  double   min_target, max_target;
+  uint32_t pruned, row_bytes;         /* row_bytes: the int8 block size P, 0 for bf16 */
+  uint64_t kept, rows;                /* kept: 0 unless pruned; rows the tables hold: kept, or num_attribute */
+  uint64_t nonfinite; double max_abs_err, sum_sq_err;   /* fmx_compact_info, as the snapshot was taken */
+  uint64_t dropped_dead, dropped_unseen;                /* fmx_compact_prune_info (features = num_attribute, kept above) */
+  uint64_t bytes;                     /* file size */
+  uint64_t bytes_compact;             /* device bytes of the snapshot on the handle (its row stride); 0 from fmx_snapshot_info */
+  double   seconds, device_seconds;   /* whole call / kernels and copies */
+} fmx_snap_info;
+int fmx_compact_save(fmx_handle h, const char *path, fmx_snap_info *info /* may be NULL */);
+int fmx_compact_load(fmx_handle h, const char *path, fmx_snap_info *info /* may be NULL */);
+int fmx_snapshot_info(const char *path, fmx_snap_info *info, char *err, size_t err_len);   /* header only; no handle, no GPU */
+int fmx_serve_open(const char *path, int device, fmx_handle *out, fmx_snap_info *info /* may be NULL */);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 typedef struct fmx_info {
   uint64_t n_local;         /* features held by this handle */

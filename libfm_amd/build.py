@@ -2,8 +2,8 @@
 
     python -m libfm_amd.build [--force]
 
-Sixteen translation units (csrc/fmx_core.hip, fmx_sgd.hip, fmx_als.hip, fmx_io.hip, fmx_comm.hip, fmx_pair.hip, fmx_topk.hip,
-fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip, fmx_weighted.hip, fmx_ckpt.hip) are compiled in parallel and linked.
+Seventeen translation units (csrc/fmx_core.hip, fmx_sgd.hip, fmx_als.hip, fmx_io.hip, fmx_comm.hip, fmx_pair.hip, fmx_topk.hip,
+fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip, fmx_weighted.hip, fmx_ckpt.hip, fmx_snap.hip) are compiled in parallel and linked.
 """
 import os
 import subprocess
@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-SRC = [os.path.join(CSRC, f) for f in ("fmx_core.hip", "fmx_sgd.hip", "fmx_als.hip", "fmx_io.hip", "fmx_comm.hip", "fmx_pair.hip", "fmx_topk.hip", "fmx_pairneg.hip", "fmx_eval.hip", "fmx_post.hip", "fmx_evalq.hip", "fmx_compact.hip", "fmx_rankq.hip", "fmx_mem.hip", "fmx_weighted.hip", "fmx_ckpt.hip")]
+SRC = [os.path.join(CSRC, f) for f in ("fmx_core.hip", "fmx_sgd.hip", "fmx_als.hip", "fmx_io.hip", "fmx_comm.hip", "fmx_pair.hip", "fmx_topk.hip", "fmx_pairneg.hip", "fmx_eval.hip", "fmx_post.hip", "fmx_evalq.hip", "fmx_compact.hip", "fmx_rankq.hip", "fmx_mem.hip", "fmx_weighted.hip", "fmx_ckpt.hip", "fmx_snap.hip")]
 DEPS = SRC + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(ROOT, "include", "fmx.h")]   # every header under csrc/
 # experiments: FMX_DEFS="-DFMX_V_NT=1" FMX_OUT=libfmx_nt.so python -m libfm_amd.build --force ; run with FMX_LIB=<that file>
 EXTRA = os.environ.get("FMX_DEFS", "").split()

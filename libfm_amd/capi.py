@@ -126,6 +126,15 @@ class CkptInfo(C.Structure):                       # fmx_ckpt_info
                 ("seconds", C.c_double), ("device_seconds", C.c_double)]
 
 
+class SnapInfo(C.Structure):                       # fmx_snap_info
+    _fields_ = [("version", C.c_uint32), ("format", C.c_uint32), ("num_attribute", C.c_uint64), ("num_factor", C.c_uint32),
+                ("k0", C.c_uint32), ("k1", C.c_uint32), ("task", C.c_int32), ("min_target", C.c_double), ("max_target", C.c_double),
+                ("pruned", C.c_uint32), ("row_bytes", C.c_uint32), ("kept", C.c_uint64), ("rows", C.c_uint64),
+                ("nonfinite", C.c_uint64), ("max_abs_err", C.c_double), ("sum_sq_err", C.c_double),
+                ("dropped_dead", C.c_uint64), ("dropped_unseen", C.c_uint64), ("bytes", C.c_uint64), ("bytes_compact", C.c_uint64),
+                ("seconds", C.c_double), ("device_seconds", C.c_double)]
+
+
 class BatchInfo(C.Structure):
     _fields_ = [("collision_mass", C.c_double), ("batch_gain", C.c_double), ("batch", C.c_uint32), ("status", C.c_uint32)]
 
@@ -405,6 +414,10 @@ SYMBOLS = [
     ("fmx_adapt_pair_epoch_sampled", C.c_int, [H, C.c_int, C.POINTER(PairNegOpts), C.POINTER(EpochStats), C.POINTER(C.c_uint64)]),
     ("fmx_ftrl_pair_epoch", C.c_int, [H, C.c_int, C.POINTER(PairOpts), C.POINTER(EpochStats)]),
     ("fmx_ftrl_pair_epoch_sampled", C.c_int, [H, C.c_int, C.POINTER(PairNegOpts), C.POINTER(EpochStats), C.POINTER(C.c_uint64)]),
+    ("fmx_compact_save", C.c_int, [H, C.c_char_p, C.POINTER(SnapInfo)]),
+    ("fmx_compact_load", C.c_int, [H, C.c_char_p, C.POINTER(SnapInfo)]),
+    ("fmx_snapshot_info", C.c_int, [C.c_char_p, C.POINTER(SnapInfo), C.c_char_p, C.c_size_t]),
+    ("fmx_serve_open", C.c_int, [C.c_char_p, C.c_int, C.POINTER(H), C.POINTER(SnapInfo)]),
     ("fmx_get_info", C.c_int, [H, C.POINTER(Info)]),
     ("fmx_synchronize", C.c_int, [H]),
 ]
@@ -546,10 +559,16 @@ class Handle:
         rc = self.lib.fmx_create(C.byref(self.cfg), C.byref(self.h))
         if rc != FMX_OK:
             raise FmxError(rc, self.lib.fmx_last_error(None).decode())
-        self.n, self.k = int(num_attribute), int(num_factor)
+        self._opened()
+
+    def _opened(self):
+        """what every way of making a Handle sets once self.lib, self.cfg and self.h stand (__init__, serve_open)"""
+        self.n, self.k = int(self.cfg.num_attribute), int(self.cfg.num_factor)
         self._nq = {}                                # slot -> n_queries of the last set_row_queries (sizes the per-query arrays)
         self.G = 1                                   # attribute groups (set_groups)
         self.n_local = int(self.info().n_local)
+        self.serve_only = False                      # serve_open: the handle holds a snapshot and no model
+        self.snap_info = None                        # ... and this is its file's SnapInfo
 
     def _chk(self, rc):
         if rc != FMX_OK:
@@ -1068,6 +1087,19 @@ class Handle:
     def compact_end(self):
         self._chk(self.lib.fmx_compact_end(self.h))
 
+    def compact_save(self, path):
+        """the snapshot as a file, straight from its device tables (fmx_compact_save); returns SnapInfo"""
+        info = SnapInfo()
+        self._chk(self.lib.fmx_compact_save(self.h, os.fsencode(path), C.byref(info)))
+        return info
+
+    def compact_load(self, path):
+        """take (or replace) the snapshot from a file (fmx_compact_load): the model is untouched, and so is the earlier snapshot when
+        the file is refused; returns SnapInfo"""
+        info = SnapInfo()
+        self._chk(self.lib.fmx_compact_load(self.h, os.fsencode(path), C.byref(info)))
+        return info
+
     # ALS / MCMC ----------------------------------------------------------------------------
     def als_begin(self, train_slot):
         self._chk(self.lib.fmx_als_begin(self.h, train_slot))
@@ -1138,6 +1170,34 @@ def checkpoint_info(path):
     if rc:
         raise FmxError(rc, err.value.decode())
     return info
+
+
+def snapshot_info(path):
+    """the header of a snapshot file (fmx_snapshot_info: no handle, no device); raises FmxError with the parser's reason"""
+    info, err = SnapInfo(), C.create_string_buffer(256)
+    rc = load().fmx_snapshot_info(os.fsencode(path), C.byref(info), err, len(err))
+    if rc:
+        raise FmxError(rc, err.value.decode())
+    return info
+
+
+def serve_open(path, device=-1):
+    """a SERVE-ONLY Handle from a snapshot file alone (fmx_serve_open): it holds the file's snapshot and no model, so only the row side,
+    the compact_* calls, info, place_info, synchronize and close work on it -- everything else raises FmxError(FMX_E_STATE).
+    snap_info is the file's SnapInfo."""
+    lib = load()
+    h, info = H(), SnapInfo()
+    rc = lib.fmx_serve_open(os.fsencode(path), int(device), C.byref(h), C.byref(info))
+    if rc != FMX_OK:
+        raise FmxError(rc, (lib.fmx_last_error(None) or b"").decode())
+    obj = Handle.__new__(Handle)
+    obj.lib, obj.h = lib, h
+    obj.cfg = Config(num_attribute=int(info.num_attribute), num_factor=int(info.num_factor), k0=int(info.k0), k1=int(info.k1),
+                     task=int(info.task), min_target=float(info.min_target), max_target=float(info.max_target), device=int(device),
+                     shard_world=1)                  # (what fmx_serve_open made the handle's config: the file's, everything else 0)
+    obj._opened()
+    obj.serve_only, obj.snap_info = True, info
+    return obj
 
 
 def release_cached_memory():

@@ -64,10 +64,18 @@ format=int8 and names its metrics (int8)).  Without the option stdout and stderr
 -serve_prune dead|seen (with -serve): the copy keeps only the rows that can score (fmx_compact_begin_pruned) -- dead drops the features
 that contribute to no prediction, seen also those no -train row names (not with -interactions, whose training rows are two files).
 The "compact" line gains kept, dropped_dead, dropped_unseen, bytes_directory and bytes_rows; bytes is their sum.
+-save_snapshot F (with -serve): the frozen copy is written to F after it is taken (fmx_compact_save; libfm_amd/compact.py reads the
+file); one "snapshot" line on stderr: format, pruned, rows, bytes, seconds.
+-method serve -load_snapshot F -test T [-out P] [-metrics ...] [-topk K -candidates C [-queries Q] [-exclude E] [-topk_out O]]: scores
+from a snapshot file and creates NO model (fmx_serve_open: the device holds the snapshot alone).  -train and -dim are not needed -- the
+geometry, the task and the target range are the file's -- and every training option is refused by name.  -out is written as the
+training run's -out with -serve is (the link of -method sgd); one "serve" line on stderr carries the test metric, with -metrics each
+named metric too.
 -devices D0,D1[,...] (-method sgd with -optimizer adagrad | ftrl): the model is split into one feature shard per listed device
 ordinal ("0,0" = two shards on device 0) and the epochs run over the shards (fmx_group_adapt_epoch / fmx_group_ftrl_epoch,
 learner.FMLearnSGD.devices); the printed lines are those of one device.  Any other method or optimizer refuses the flag, and so do
--serve, -topk, -save_checkpoint, -load_checkpoint and -train_weights, which have no sharded form.  Without the flag nothing changes.
+-serve, -topk, -save_checkpoint, -load_checkpoint, -save_snapshot, -load_snapshot and -train_weights, which have no sharded form.
+Without the flag nothing changes.
 """
 import os
 import sys
@@ -84,7 +92,8 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "test": "filename for test data [MANDATORY]", "validation": "", "out": "filename for output",
          "dim": "'k0,k1,k2': k0=use bias, k1=use 1-way interactions, k2=dim of 2-way interactions; default=1,1,8",
          "regular": "'r0,r1,r2' for SGD and ALS", "init_stdev": "stdev for initialization of 2-way factors; default=0.1",
-         "iter": "number of iterations; default=100", "learn_rate": "learn_rate for SGD", "method": "sgd, sgda, als, mcmc, bpr; default=mcmc",
+         "iter": "number of iterations; default=100", "learn_rate": "learn_rate for SGD",
+         "method": "sgd, sgda, als, mcmc, bpr; default=mcmc.  serve: score from -load_snapshot, no model, no training",
          "verbosity": "", "rlog": "write measurements within iterations to a file", "seed": "integer value", "help": "",
          "relation": "BS: filenames for the relations, default=''", "cache_size": "", "save_model": "filename for writing the FM model",
          "load_model": "filename for reading the FM model",
@@ -123,6 +132,8 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "load_checkpoint": "sgd, bpr: filename of a checkpoint to continue from (instead of the random initialisation; not with -load_model)",
          "serve": "bf16 | int8: score -out, -metrics and -topk after training from a frozen bf16 or row-wise int8 copy of the model; sgd, sgda, bpr, als",
          "serve_prune": "dead | seen (with -serve): keep only the rows that can score -- dead: drop features that contribute to no prediction; seen: also those no -train row names",
+         "save_snapshot": "with -serve: filename for the snapshot file of the frozen copy, written after it is taken",
+         "load_snapshot": "-method serve: filename of the snapshot file to score from (no model is created; -train and -dim are not needed)",
          "devices": "'D0,D1,...': -method sgd with -optimizer adagrad | ftrl over one feature shard per listed device ordinal ('0,0': two shards on device 0)"}
 
 
@@ -130,6 +141,76 @@ def checkpoint_line(what, info):
     """the one stderr line of -save_checkpoint / -load_checkpoint (capi.CkptInfo)"""
     return "checkpoint\t%s\tsession=%s\tstate_rows=%d\tbytes=%d\tseconds=%.3g" % (
         what, L.capi.CKPT_SESSIONS[info.session], info.state_rows, info.bytes, info.seconds)
+
+
+def snapshot_line(what, info):
+    """the one stderr line of -save_snapshot / -load_snapshot (capi.SnapInfo)"""
+    return "snapshot\t%s\tformat=%s\tpruned=%d\trows=%d\tbytes=%d\tseconds=%.3g" % (
+        what, C.FORMAT_NAMES.get(int(info.format), "?"), info.pruned, info.rows, info.bytes, info.seconds)
+
+
+# what -method serve takes; every other flag is a training option and is refused by name
+SERVE_FLAGS = ("method", "load_snapshot", "test", "out", "metrics", "topk", "topk_out", "candidates", "queries", "exclude", "device", "task",
+               "verbosity")
+
+
+def _serve_main(a):
+    """-method serve: score -test (and -topk lists) from the snapshot file -load_snapshot names, through a handle that holds no model"""
+    for f in a:
+        if f not in SERVE_FLAGS:
+            raise ValueError("-%s is not supported with -method serve: it creates no model and trains nothing (it takes %s)"
+                             % (f, ", ".join("-" + x for x in SERVE_FLAGS[1:])))
+    if not a.get("load_snapshot"):
+        raise ValueError("-method serve needs -load_snapshot with a filename")
+    if not a.get("test"):
+        raise ValueError("-test is mandatory")
+    want_topk = any(f in a for f in ("topk", "topk_out", "candidates", "queries", "exclude"))
+    if want_topk and ("topk" not in a or "candidates" not in a):
+        raise ValueError("top-K retrieval needs -topk and -candidates")
+    head = C.snapshot_header(a["load_snapshot"])                 # (refused from the header alone, before any device)
+    task = "c" if head["task"] == L.TASK_CLASSIFICATION else "r"
+    if a.get("task", task) != task:
+        raise ValueError("-task %s but the snapshot was taken for -task %s" % (a["task"], task))
+    metrics = tuple(split_list(a.get("metrics", "")))
+    for m in metrics:
+        if m not in L.EXTRA_METRICS:
+            raise ValueError("-metrics knows auc and logloss, not '%s'" % m)
+    if metrics and task != "c":
+        raise ValueError("-metrics needs a snapshot of -task c: AUC and log loss are classification metrics")
+    print("Loading test... \t")
+    test = L.Data(*D.load(a["test"]))
+    print("num_rows=%d\tnum_values=%d\tnum_features=%d\tmin_target=%g\tmax_target=%g" %
+          (test.num_cases, len(test.entries), test.num_feature, test.min_target, test.max_target))
+    if test.num_feature > head["num_attribute"]:
+        raise ValueError("-test names feature %d, the snapshot holds %d features" % (test.num_feature - 1, head["num_attribute"]))
+    if task == "c":                                                                  # libfm.cpp:302-306
+        test.target[:] = np.where(test.target <= 0.0, -1.0, 1.0)
+    view = L.load_snapshot(a["load_snapshot"], int(a.get("device", "-1")))
+    try:
+        print(snapshot_line("load", view.info), file=sys.stderr)
+        line = "serve\tformat=%s\tbytes=%d\tTest(%s)=%g" % (view.format, view.info.bytes_compact, view.format, view.evaluate(test))
+        if metrics:
+            ex = view.evaluate_ex(test)
+            line += "".join("\t%s(%s)=%g" % (m, view.format, getattr(ex, m)) for m in metrics)
+        print(line, file=sys.stderr)
+        if a.get("out"):
+            with open(a["out"], "w") as f:                                               # DVector::save, matrix.h:332-342
+                f.write("".join("%g\n" % p for p in view.predict(test)))
+        if want_topk:
+            topk = int(a["topk"])
+            cand = L.Data(*D.load(a["candidates"]))
+            queries = L.Data(*D.load(a["queries"])) if a.get("queries") else test
+            for d, name in ((cand, "-candidates"), (queries, "-queries")):
+                if d.num_feature > head["num_attribute"]:
+                    raise ValueError("%s names feature %d, the snapshot holds %d features" % (name, d.num_feature - 1, head["num_attribute"]))
+            exclude = read_exclude(a["exclude"], queries.num_cases, cand.num_cases) if a.get("exclude") else None
+            idx, score = view.recommend(queries, cand, topk, exclude)
+            print("Top-K\tqueries=%d\tcandidates=%d\tK=%d" % (queries.num_cases, cand.num_cases, topk))
+            if a.get("topk_out"):
+                write_topk(a["topk_out"], idx, score)
+    finally:
+        view.close()
+    return 0
 
 
 def read_pairs(path, n_rows):
@@ -280,6 +361,10 @@ def _main(argv):
     a = parse(argv)
     seed = int(a["seed"]) if "seed" in a else int(time.time())
     method = a.get("method", "mcmc")
+    if method == "serve":
+        return _serve_main(a)
+    if "load_snapshot" in a:
+        raise ValueError("-load_snapshot belongs to -method serve")
     init_stdev = float(a.get("init_stdev", "0.1"))
     dim = [int(x) for x in split_list(a.get("dim", "1,1,8"))]
     if len(dim) != 3:
@@ -346,7 +431,7 @@ def _main(argv):
         if method != "sgd" or optimizer not in L.FMLearnSGD.SHARDED_OPTIMIZERS:
             raise ValueError("-devices belongs to -method sgd with -optimizer adagrad or ftrl: -method %s%s has no form on feature shards"
                              % (method, " -optimizer " + optimizer if method in ("sgd", "bpr") else ""))
-        for f in ("serve", "topk", "save_checkpoint", "load_checkpoint", "train_weights"):
+        for f in ("serve", "topk", "save_checkpoint", "load_checkpoint", "save_snapshot", "load_snapshot", "train_weights"):
             if f in a:
                 raise ValueError("-%s is not supported with -devices: it has no form on feature shards" % f)
         try:
@@ -371,6 +456,11 @@ def _main(argv):
             raise ValueError("-serve_prune knows dead and seen, not '%s'" % serve_prune)
         if serve_prune == "seen" and implicit:
             raise ValueError("-serve_prune seen is not supported with -interactions: the training rows are two files (use dead)")
+    if "save_snapshot" in a:
+        if "serve" not in a:
+            raise ValueError("-save_snapshot needs -serve (bf16 | int8): it writes the frozen copy")
+        if not a["save_snapshot"]:
+            raise ValueError("-save_snapshot needs a filename")
     if "train_weights" in a or "test_weights" in a:
         if method != "sgd" or optimizer not in ("adagrad", "ftrl"):
             raise ValueError("-train_weights / -test_weights belong to -method sgd with -optimizer adagrad or ftrl: -method %s%s has no "
@@ -660,6 +750,8 @@ def _main(argv):
             ex32, ex16 = l.evaluate_ex(test), scorer.evaluate_ex(test)
             line += "".join("\t%s(fp32)=%g\t%s(%s)=%g" % (m, getattr(ex32, m), m, serve, getattr(ex16, m)) for m in metrics if m in L.EXTRA_METRICS)
         print(line, file=sys.stderr)
+        if "save_snapshot" in a:
+            print(snapshot_line("save", scorer.save(a["save_snapshot"])), file=sys.stderr)
     if "rlog" in a and a["rlog"]:
         with open(a["rlog"], "w") as f:                                              # rlog.h:60-103: TSV with a header
             keys = sorted(l.log[0].keys()) if l.log else []

@@ -20,6 +20,8 @@ extern "C++" void als_free(fmx_handle h) {
 }
 
 int fmx_als_end(fmx_handle h) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_als_end"); if (_sr) return _sr; }
   touch_w(h);
   if (!h) return FMX_E_ARG;
   HIPCHK(h, hipSetDevice(h->device));
@@ -355,6 +357,8 @@ static int als_begin_shards(const std::vector<fmx_handle>& hs, fmx_group g, int 
 }
 
 int fmx_als_begin(fmx_handle h, int train_slot) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_als_begin"); if (_sr) return _sr; }
   touch_w(h);
   if (!h) return FMX_E_ARG;
   { const int rw = refuse_weighted(h, train_slot, "fmx_als_begin"); if (rw) return rw; }
@@ -366,6 +370,7 @@ int fmx_als_begin(fmx_handle h, int train_slot) {
 
 int fmx_als_moments(fmx_handle h, double* out) {
   if (!h || !out) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_als_moments"); if (_sr) return _sr; }
   AlsState& a = h->als;
   if (a.slot < 0) return fail(h, FMX_E_STATE, "fmx_als_moments before fmx_als_begin");
   HIPCHK(h, hipSetDevice(h->device));
@@ -736,6 +741,7 @@ int fmx_group_als_end(fmx_group g) {
 
 int fmx_als_sweep(fmx_handle h, const fmx_als_opts* opts, fmx_als_stats* stats) {
   if (!h || !opts) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_als_sweep"); if (_sr) return _sr; }
   if (h->cfg.shard_world > 1) return fail(h, FMX_E_STATE, "fmx_als_sweep on a feature shard: use fmx_group_als_sweep");
   return als_sweep_shards(std::vector<fmx_handle>(1, h), nullptr, opts, stats);
 }

@@ -1,119 +1,30 @@
 // fmx_ckpt.hip -- C-ABI (include/fmx.h "fmx_checkpoint_*"): exact binary checkpoints of the model and of an open AdaGrad / FTRL
 // session.  The byte layout and everything a load refuses from the header alone is fmx_ckpt_format.h (host
-// only); the kernels are fmx_ckpt_kernels.h.  A section is streamed in chunks through two device staging buffers and two pinned host
-// buffers on h->stream: on save the pack kernel and the device-to-host copy of chunk i + 1 run while the host writes chunk i, on load
-// the host reads chunk i + 1 while chunk i is copied up and unpacked.  The checksum of a section is formed on the device, by the
-// kernel that moves it, over what is in device memory.
-#include "fmx_internal.h"
+// only); the kernels are fmx_ckpt_kernels.h; the two-buffer pipe a section is streamed through, and the checksum formed on the device
+// by the kernel that moves it, are fmx_pipe.h (shared with fmx_snap.hip).
+#include "fmx_pipe.h"
 #include "fmx_ckpt_kernels.h"
 #include "fmx_ckpt_format.h"
-
-#include <cerrno>
 
 namespace {
 
 namespace ck = fmx_ckpt;
-
-// Bytes of one chunk.  Large enough that a chunk's launch, copy call and fwrite / fread call (tens of microseconds together) are
-// under 1 % of the ~0.3 ms the chunk takes at PCIe rate, small enough that the four buffers (two pinned, two on the device: 64 MiB)
-// cost nothing next to a model, and that a file of a few MiB still gets both buffers busy.
-constexpr size_t CKPT_CHUNK = size_t(16) << 20;
-
-struct Pipe {
-  void* pin[2] = {nullptr, nullptr};
-  unsigned long long* dev[2] = {nullptr, nullptr};
-  hipEvent_t start[2] = {nullptr, nullptr}, end[2] = {nullptr, nullptr};
-  bool pending[2] = {false, false};
-  unsigned long long* d_sum = nullptr;      // [0] the running checksum, [1] low word: the id list's error flag
-  double device_seconds = 0.0;
-  hipError_t open() {
-    hipError_t e = hipSuccess;
-    for (int b = 0; b < 2 && e == hipSuccess; b++) {
-      e = hipHostMalloc(&pin[b], CKPT_CHUNK, hipHostMallocDefault);
-      if (e == hipSuccess) e = fmx_dev_alloc(&dev[b], CKPT_CHUNK);
-      if (e == hipSuccess) e = hipEventCreate(&start[b]);
-      if (e == hipSuccess) e = hipEventCreate(&end[b]);
-    }
-    if (e == hipSuccess) e = fmx_dev_alloc(&d_sum, 16);
-    return e;
-  }
-  // chunk b's device work is done: its pinned buffer may be read (save) or overwritten (load)
-  hipError_t finish(int b) {
-    if (!pending[b]) return hipSuccess;
-    hipError_t e = hipEventSynchronize(end[b]);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, start[b], end[b]);
-    device_seconds += ms * 1e-3;
-    pending[b] = false;
-    return e;
-  }
-  ~Pipe() {
-    for (int b = 0; b < 2; b++) {
-      if (pin[b]) hipHostFree(pin[b]);
-      fmx_dev_free(dev[b]);
-      if (start[b]) hipEventDestroy(start[b]);
-      if (end[b]) hipEventDestroy(end[b]);
-    }
-    fmx_dev_free(d_sum);
-  }
-};
 
 struct DevBufs {                             // the sparse path's arrays, freed on every path out of a call
   uint32_t* flag = nullptr; uint32_t* pos = nullptr; uint32_t* ids = nullptr; void* tmp = nullptr;
   ~DevBufs() { fmx_dev_free(flag); fmx_dev_free(pos); fmx_dev_free(ids); fmx_dev_free(tmp); }
 };
 
-struct File {                                // closes (and on a failed save removes) the file on every path out of a call
-  FILE* f = nullptr; std::string remove_path;
-  ~File() { if (f) fclose(f); if (!remove_path.empty()) remove(remove_path.c_str()); }
-};
-
-inline uint32_t stream_grid(uint64_t items) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + 255) / 256, 1), 2048); }
-
-#define CK_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return fail(h, FMX_E_HIP, "%s: %s failed: %s", who, #expr, hipGetErrorString(_e)); } while (0)
-
-// the stream's checksum word: zero it before a section, read it after (the stream is drained by the read)
-int sum_reset(fmx_handle h, const char* who, Pipe& P) { CK_HIP(hipMemsetAsync(P.d_sum, 0, 16, h->stream)); return FMX_OK; }
-int sum_read(fmx_handle h, const char* who, Pipe& P, uint64_t* sum, uint32_t* bad) {
-  unsigned long long host[2] = {0ull, 0ull};
-  CK_HIP(hipMemcpyAsync(host, P.d_sum, 16, hipMemcpyDeviceToHost, h->stream));
-  CK_HIP(hipStreamSynchronize(h->stream));
-  *sum = host[0];
-  if (bad) *bad = (uint32_t)host[1];
-  return FMX_OK;
-}
-
 // rows of a chunk: as many as fit, an even number so that every chunk but the last ends on a word boundary
 inline uint64_t chunk_rows(uint32_t cols) { return std::max<uint64_t>(2, (CKPT_CHUNK / ((size_t)cols * 4)) & ~size_t(1)); }
 
-// one section of table rows, device -> file.  *sum_out = its checksum.
+// one section of table rows, device -> file (fmx_pipe.h pipe_save around k_ckpt_rows).  *sum_out = its checksum.
 int save_rows(fmx_handle h, const char* who, Pipe& P, FILE* f, const CkptRows& t, uint64_t n_rows, uint64_t* sum_out) {
   *sum_out = 0;
   if (n_rows == 0 || t.cols == 0) return FMX_OK;
-  int rc = sum_reset(h, who, P); if (rc) return rc;
-  const uint64_t per = chunk_rows(t.cols);
-  uint64_t word0 = 0;
-  size_t prev_bytes = 0;
-  int i = 0;
-  for (uint64_t r0 = 0; r0 < n_rows; r0 += per, i++) {
-    const int b = i & 1;
-    const uint32_t n_elems = (uint32_t)(std::min<uint64_t>(per, n_rows - r0) * t.cols), n_words = (n_elems + 1u) / 2u;
-    CK_HIP(hipEventRecord(P.start[b], h->stream));
-    hipLaunchKernelGGL(k_ckpt_rows<true>, dim3(stream_grid(n_words)), dim3(256), 0, h->stream, t, r0, n_elems, word0, P.dev[b], P.d_sum);
-    CK_HIP(hipGetLastError());
-    CK_HIP(hipMemcpyAsync(P.pin[b], P.dev[b], (size_t)n_words * 8, hipMemcpyDeviceToHost, h->stream));
-    CK_HIP(hipEventRecord(P.end[b], h->stream));
-    P.pending[b] = true;
-    if (i > 0) {                                                 // (the host writes chunk i - 1 while the device works on chunk i)
-      CK_HIP(P.finish(b ^ 1));
-      if (fwrite(P.pin[b ^ 1], 1, prev_bytes, f) != prev_bytes) return fail(h, FMX_E_ARG, "%s: write error (%s)", who, strerror(errno));
-    }
-    prev_bytes = (size_t)n_words * 8;
-    word0 += n_words;
-  }
-  CK_HIP(P.finish((i - 1) & 1));
-  if (fwrite(P.pin[(i - 1) & 1], 1, prev_bytes, f) != prev_bytes) return fail(h, FMX_E_ARG, "%s: write error (%s)", who, strerror(errno));
-  return sum_read(h, who, P, sum_out, nullptr);
+  return pipe_save(h, who, P, f, n_rows, chunk_rows(t.cols), (uint64_t)t.cols * 4, [&](int b, uint64_t r0, uint64_t rows, uint64_t word0, uint32_t n_words) {
+    hipLaunchKernelGGL(k_ckpt_rows<true>, dim3(stream_grid(n_words)), dim3(256), 0, h->stream, t, r0, (uint32_t)(rows * t.cols), word0, P.dev[b], P.d_sum);
+  }, sum_out);
 }
 
 // one section of table rows, file -> device; with ids the rows are scattered (the list has been validated).  *sum_out = the checksum
@@ -121,25 +32,9 @@ int save_rows(fmx_handle h, const char* who, Pipe& P, FILE* f, const CkptRows& t
 int load_rows(fmx_handle h, const char* who, Pipe& P, FILE* f, const CkptRows& t, uint64_t n_rows, uint64_t* sum_out) {
   *sum_out = 0;
   if (n_rows == 0 || t.cols == 0) return FMX_OK;
-  int rc = sum_reset(h, who, P); if (rc) return rc;
-  const uint64_t per = chunk_rows(t.cols);
-  uint64_t word0 = 0;
-  int i = 0;
-  for (uint64_t r0 = 0; r0 < n_rows; r0 += per, i++) {
-    const int b = i & 1;
-    const uint32_t n_elems = (uint32_t)(std::min<uint64_t>(per, n_rows - r0) * t.cols), n_words = (n_elems + 1u) / 2u;
-    CK_HIP(P.finish(b));                                         // (chunk i - 2 has left this pinned buffer; chunk i - 1 is on its way up meanwhile)
-    if (fread(P.pin[b], 1, (size_t)n_words * 8, f) != (size_t)n_words * 8) return fail(h, FMX_E_ARG, "%s: read error", who);
-    CK_HIP(hipEventRecord(P.start[b], h->stream));
-    CK_HIP(hipMemcpyAsync(P.dev[b], P.pin[b], (size_t)n_words * 8, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_ckpt_rows<false>, dim3(stream_grid(n_words)), dim3(256), 0, h->stream, t, r0, n_elems, word0, P.dev[b], P.d_sum);
-    CK_HIP(hipGetLastError());
-    CK_HIP(hipEventRecord(P.end[b], h->stream));
-    P.pending[b] = true;
-    word0 += n_words;
-  }
-  CK_HIP(P.finish(0)); CK_HIP(P.finish(1));
-  return sum_read(h, who, P, sum_out, nullptr);
+  return pipe_load(h, who, P, f, n_rows, chunk_rows(t.cols), (uint64_t)t.cols * 4, [&](int b, uint64_t r0, uint64_t rows, uint64_t word0, uint32_t n_words) {
+    hipLaunchKernelGGL(k_ckpt_rows<false>, dim3(stream_grid(n_words)), dim3(256), 0, h->stream, t, r0, (uint32_t)(rows * t.cols), word0, P.dev[b], P.d_sum);
+  }, sum_out);
 }
 
 // the id list (padded to a multiple of 8 bytes on the device too) between the device and the file, in chunks through the pinned buffers
@@ -201,8 +96,6 @@ void fill_info(fmx_ckpt_info* info, const ck::Header& hd, uint64_t bytes, double
   info->seconds = seconds; info->device_seconds = device_seconds;
 }
 
-double since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
-
 // read the header of an open file; *file_len = the file's length
 bool read_header(FILE* f, ck::Header* hd, uint64_t* file_len, char* err, size_t err_len) {
   uint8_t buf[ck::HEADER_BYTES];
@@ -221,6 +114,7 @@ extern "C" {
 int fmx_checkpoint_save(fmx_handle h, const char* path, const fmx_ckpt_opts* opts, fmx_ckpt_info* info) {
   static const char who[] = "fmx_checkpoint_save";
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_checkpoint_save"); if (_sr) return _sr; }
   const auto t0 = std::chrono::steady_clock::now();
   uint32_t flags = 0;
   int rc = ckpt_check(h, who, path, opts, &flags); if (rc) return rc;
@@ -337,6 +231,7 @@ int fmx_checkpoint_save(fmx_handle h, const char* path, const fmx_ckpt_opts* opt
 int fmx_checkpoint_load(fmx_handle h, const char* path, const fmx_ckpt_opts* opts, fmx_ckpt_info* info) {
   static const char who[] = "fmx_checkpoint_load";
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_checkpoint_load"); if (_sr) return _sr; }
   const auto t0 = std::chrono::steady_clock::now();
   uint32_t flags = 0;
   int rc = ckpt_check(h, who, path, opts, &flags); if (rc) return rc;

@@ -396,6 +396,7 @@ int fmx_comm_unique_id(void* id128) {
 
 int fmx_comm_init_rank(fmx_handle h, const void* id128, int rank, int world) {
   if (!h || !id128) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_comm_init_rank"); if (_sr) return _sr; }
   if (h->cfg.shard_rank != rank || h->cfg.shard_world != world)
     return fail(h, FMX_E_ARG, "fmx_comm_init_rank: rank %d of %d but the handle is shard %d of %d", rank, world, h->cfg.shard_rank, h->cfg.shard_world);
   if (h->comm) return fail(h, FMX_E_STATE, "fmx_comm_init_rank: the handle already has a communicator");
@@ -422,6 +423,7 @@ int fmx_comm_init_rank(fmx_handle h, const void* id128, int rank, int world) {
 
 int fmx_comm_destroy(fmx_handle h) {
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_comm_destroy"); if (_sr) return _sr; }
   if (h->comm) {
     hipSetDevice(h->device);
     hipStreamSynchronize(h->stream);
@@ -438,6 +440,7 @@ int fmx_group_create(fmx_handle* handles, int n, fmx_group* out) {
   for (int i = 0; i < n; i++) {
     fmx_handle h = handles[i];
     if (!h) return fail(nullptr, FMX_E_ARG, "fmx_group_create: handle %d is NULL", i);
+    { const int _sr = serve_refuse(h, "fmx_group_create"); if (_sr) return _sr; }
     if (h->cfg.shard_world != n || h->cfg.shard_rank != i)
       return fail(h, FMX_E_ARG, "fmx_group_create: handle %d must be shard %d of %d (is %d of %d)", i, i, n, h->cfg.shard_rank, h->cfg.shard_world);
     if (h->KP != handles[0]->KP || h->cfg.num_attribute != handles[0]->cfg.num_attribute || h->cfg.shard_hash != handles[0]->cfg.shard_hash)

@@ -27,11 +27,6 @@ int compact_check_slot(fmx_handle h, const char* who, int slot, bool need_target
   return FMX_OK;
 }
 
-void compact_release(CompactState& c) {
-  fmx_dev_free(c.V); fmx_dev_free(c.w); fmx_dev_free(c.w0); fmx_dev_free(c.B); fmx_dev_free(c.dir);
-  c = CompactState();
-}
-
 // The rank directory of a pruned snapshot: which features keep a row (not dead; with `keep`, also met in that slot's entries) and where.
 // Device memory beside the directory itself: two bit arrays and the popcounts of its size class and hipcub's scan scratch, all freed
 // before the rows are allocated.  *dir_out is a plain allocation the caller owns; *kept the rows to allocate.
@@ -154,6 +149,8 @@ int compact_build(fmx_handle h, const char* who, uint32_t format, const Slot* ke
     compact_release(c);
     return fail(h, FMX_E_HIP, "%s: the snapshot (%zu bytes): %s", who, (size_t)bytes, hipGetErrorString(er));
   }
+  c.nonfinite = res.c; c.max_abs_err = res.d[0]; c.sum_sq_err = res.d[1];       // (kept for fmx_compact_save's header)
+  if (pinfo) { c.dropped_dead = pinfo->dropped_dead; c.dropped_unseen = pinfo->dropped_unseen; }
   compact_release(h->compact);
   h->compact = c;
   if (pinfo) pinfo->bytes_rows = bytes_rows;
@@ -170,6 +167,11 @@ int compact_build(fmx_handle h, const char* who, uint32_t format, const Slot* ke
 }
 
 }  // namespace
+
+void compact_release(CompactState& c) {
+  fmx_dev_free(c.V); fmx_dev_free(c.w); fmx_dev_free(c.w0); fmx_dev_free(c.B); fmx_dev_free(c.dir);
+  c = CompactState();
+}
 
 void compact_free(fmx_handle h) { compact_release(h->compact); }
 
@@ -189,6 +191,7 @@ uint32_t fmx_compact_row_bytes(uint32_t format, int num_factor) {
 int fmx_compact_begin(fmx_handle h, const fmx_compact_opts* opts, fmx_compact_info* info) {
   static const char who[] = "fmx_compact_begin";
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_compact_begin"); if (_sr) return _sr; }
   if (!opts) return fail(h, FMX_E_ARG, "%s: opts is NULL", who);
   if (opts->format != FMX_COMPACT_BF16 && opts->format != FMX_COMPACT_INT8)
     return fail(h, FMX_E_ARG, "%s: unknown format %u (FMX_COMPACT_BF16, FMX_COMPACT_INT8)", who, opts->format);
@@ -200,6 +203,7 @@ int fmx_compact_begin(fmx_handle h, const fmx_compact_opts* opts, fmx_compact_in
 int fmx_compact_begin_pruned(fmx_handle h, const fmx_compact_prune_opts* o, fmx_compact_info* info, fmx_compact_prune_info* pinfo) {
   static const char who[] = "fmx_compact_begin_pruned";
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_compact_begin_pruned"); if (_sr) return _sr; }
   if (!o) return fail(h, FMX_E_ARG, "%s: opts is NULL", who);
   if (o->format != FMX_COMPACT_BF16 && o->format != FMX_COMPACT_INT8)
     return fail(h, FMX_E_ARG, "%s: unknown format %u (FMX_COMPACT_BF16, FMX_COMPACT_INT8)", who, o->format);

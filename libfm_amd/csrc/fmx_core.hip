@@ -417,7 +417,11 @@ int fmx_device_count(void) {
 
 const char* fmx_last_error(fmx_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-int fmx_create(const fmx_config* cfg, fmx_handle* out) {
+int fmx_create(const fmx_config* cfg, fmx_handle* out) { return create_handle(cfg, out, false); }
+
+}  // extern "C"
+
+int create_handle(const fmx_config* cfg, fmx_handle* out, bool serve_only) {
   if (!cfg || !out) return fail(nullptr, FMX_E_ARG, "fmx_create: null argument");
   *out = nullptr;
   if (cfg->num_attribute == 0) return fail(nullptr, FMX_E_ARG, "num_attribute must be > 0");
@@ -467,7 +471,9 @@ int fmx_create(const fmx_config* cfg, fmx_handle* out) {
     h->tb.rs = (uint32_t)h->KP;
     { const char* rk = getenv("FMX_ROW_STRIDE_KP");
       if (h->KP >= 32 && !(rk && rk[0] == '1')) h->tb.rs = std::min<uint32_t>((uint32_t)h->KP, ((uint32_t)cfg->num_factor + 15u) / 16u * 16u); }
-    if (place_tables(h) != FMX_OK) { fmx_destroy(h); return FMX_E_HIP; }      // fmx_mem.hip: the arena, or the best of place_candidates allocations
+    // a serve-only handle (fmx_serve_open) gets everything below but no parameter tables: tb.V, tb.w and w_sep stay null
+    h->serve_only = serve_only;
+    if (!serve_only && place_tables(h) != FMX_OK) { fmx_destroy(h); return FMX_E_HIP; }      // fmx_mem.hip: the arena, or the best of place_candidates allocations
     h->tb.w = h->w_sep; h->tb.ws = 1;
   }
   CREATE_CHK(fmx_dev_alloc(&h->w0, sizeof(double)));
@@ -513,6 +519,8 @@ int fmx_create(const fmx_config* cfg, fmx_handle* out) {
   *out = h;
   return FMX_OK;
 }
+
+extern "C" {
 
 int fmx_batch_rule(int32_t task, double learn_rate, double collision_mass, uint32_t requested, fmx_batch_info* out) {
   if (!out || (task != FMX_TASK_REGRESSION && task != FMX_TASK_CLASSIFICATION) || !(learn_rate >= 0.0) || !(collision_mass >= 0.0)) return FMX_E_ARG;
@@ -567,7 +575,7 @@ int fmx_get_info(fmx_handle h, fmx_info* out) {
   out->n_local = h->n_local;
   out->k_padded = h->KP;
   out->device = h->device;
-  out->bytes_params = h->n_local * (size_t)(h->tb.rs + (h->w_sep ? 1 : 0)) * sizeof(float);
+  out->bytes_params = h->serve_only ? 0 : h->n_local * (size_t)(h->tb.rs + (h->w_sep ? 1 : 0)) * sizeof(float);
   snprintf(out->device_name, sizeof(out->device_name), "%s", h->prop.name);
   snprintf(out->arch, sizeof(out->arch), "%s", h->prop.gcnArchName);
   return FMX_OK;
@@ -648,6 +656,7 @@ done:
 
 int fmx_set_params(fmx_handle h, double w0, const double* w, const double* v) {
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_set_params"); if (_sr) return _sr; }
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   if (h->cfg.num_factor > 0 && !v) return fail(h, FMX_E_ARG, "fmx_set_params: v is NULL but num_factor > 0");
   double w0c = w0;
@@ -656,12 +665,14 @@ int fmx_set_params(fmx_handle h, double w0, const double* w, const double* v) {
 
 int fmx_get_params(fmx_handle h, double* w0, double* w, double* v) {
   if (!h || !w0) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_get_params"); if (_sr) return _sr; }
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   return stage_params(h, false, w0, w, v);
 }
 
 int fmx_get_param_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double* w_out, double* v_out) {
   if (!h || !ids || !w_out) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_get_param_rows"); if (_sr) return _sr; }
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   const int k = h->cfg.num_factor;
   const Shard sh = make_shard(h->cfg);
@@ -684,6 +695,7 @@ int fmx_get_param_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double
 // (6 significant digits, printf "%g").
 int fmx_save_model(fmx_handle h, const char* path) {
   if (!h || !path) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_save_model"); if (_sr) return _sr; }
   if (h->cfg.shard_world > 1) return fail(h, FMX_E_UNSUPPORTED, "fmx_save_model on a feature shard: collect the parameters with fmx_get_params");
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   HIPCHK(h, hipSetDevice(h->device));
@@ -730,6 +742,8 @@ int fmx_save_model(fmx_handle h, const char* path) {
 // returns FMX_E_ARG ("malformed model file") where fm_model::loadModel returns 0 (libfm.cpp:264-267).  Every shard of a
 // sharded model may load the same file: it keeps its own features.
 int fmx_load_model(fmx_handle h, const char* path) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_load_model"); if (_sr) return _sr; }
   touch_w(h);
   if (!h || !path) return FMX_E_ARG;
   { int _rc = lag_flush(h); if (_rc) return _rc; }
@@ -825,6 +839,7 @@ int fmx_load_model(fmx_handle h, const char* path) {
 
 int fmx_get_w0(fmx_handle h, double* w0) {
   if (!h || !w0) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_get_w0"); if (_sr) return _sr; }
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipMemcpyAsync(w0, h->w0, sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -834,6 +849,7 @@ int fmx_get_w0(fmx_handle h, double* w0) {
 
 int fmx_set_groups(fmx_handle h, const uint32_t* group_of_feature, uint32_t num_groups) {
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_set_groups"); if (_sr) return _sr; }
   if (h->als.slot >= 0 || h->sgda.reg) return fail(h, FMX_E_STATE, "fmx_set_groups while an ALS / SGDA session is open");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -856,6 +872,8 @@ int fmx_set_groups(fmx_handle h, const uint32_t* group_of_feature, uint32_t num_
 }
 
 int fmx_init_params(fmx_handle h, double init_mean, double init_stdev, uint64_t seed) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_init_params"); if (_sr) return _sr; }
   touch_w(h);
   if (!h) return FMX_E_ARG;
   { int _rc = lag_flush(h); if (_rc) return _rc; }
@@ -1159,6 +1177,8 @@ int fmx_rows_info(fmx_handle h, int slot, uint32_t* n_rows, uint64_t* nnz) {
 }
 
 int fmx_wtrain_info(fmx_handle h, int slot, uint64_t* singles, int* kept) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_wtrain_info"); if (_sr) return _sr; }
   int rc = check_slot(h, slot, false);
   if (rc) return rc;
   if (singles) *singles = h->slots[slot].wtrain_n;
@@ -1244,6 +1264,8 @@ int fmx_synth_rows_ex(fmx_handle h, int slot, uint64_t seed, uint64_t row0, uint
 // predict / evaluate
 // ---------------------------------------------------------------------------------------------
 int fmx_predict(fmx_handle h, int slot, double* out) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_predict"); if (_sr) return _sr; }
   int rc = check_slot(h, slot, false); if (rc) return rc;
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   if (!out) return fail(h, FMX_E_ARG, "fmx_predict: out is NULL");
@@ -1252,6 +1274,8 @@ int fmx_predict(fmx_handle h, int slot, double* out) {
 }
 
 int fmx_evaluate(fmx_handle h, int slot, fmx_eval* out) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_evaluate"); if (_sr) return _sr; }
   int rc = check_slot(h, slot, true); if (rc) return rc;
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   if (!out) return fail(h, FMX_E_ARG, "fmx_evaluate: out is NULL");

@@ -142,6 +142,7 @@ extern "C" {
 int fmx_evaluate_ex(fmx_handle h, int slot, const fmx_eval_opts* opts, fmx_eval_ex* out) {
   static const char who[] = "fmx_evaluate_ex";
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_evaluate_ex"); if (_sr) return _sr; }
   if (!out) return fail(h, FMX_E_ARG, "%s: out is NULL", who);
   uint32_t link;
   int rc = eval_ex_check_opts(h, who, opts, &link);

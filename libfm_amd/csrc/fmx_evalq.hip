@@ -143,6 +143,7 @@ extern "C" {
 
 int fmx_set_row_queries(fmx_handle h, int slot, const uint32_t* qid, uint32_t n_queries) {
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_set_row_queries"); if (_sr) return _sr; }
   return set_row_queries_impl(h, "fmx_set_row_queries", slot, qid, n_queries);
 }
 
@@ -150,6 +151,7 @@ int fmx_evaluate_by_query(fmx_handle h, int slot, const fmx_eval_opts* opts, fmx
                           uint64_t* num2_q, uint32_t* pos_q, uint32_t* neg_q) {
   static const char who[] = "fmx_evaluate_by_query";
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_evaluate_by_query"); if (_sr) return _sr; }
   if (!out) return fail(h, FMX_E_ARG, "%s: out is NULL", who);
   uint32_t link;
   int rc = eval_ex_check_opts(h, who, opts, &link);

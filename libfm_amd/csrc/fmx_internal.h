@@ -1,5 +1,5 @@
 // fmx_internal.h -- shared by the translation units of libfmx.so (fmx_core.hip, fmx_sgd.hip, fmx_als.hip, fmx_comm.hip, fmx_pair.hip, fmx_topk.hip,
-// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip, fmx_weighted.hip, fmx_ckpt.hip; fmx_io.hip needs
+// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip, fmx_weighted.hip, fmx_ckpt.hip, fmx_snap.hip; fmx_io.hip needs
 // none of it).
 // The C-ABI is include/fmx.h; nothing declared here is exported.
 #pragma once
@@ -184,8 +184,11 @@ struct FtrlState { float* zw = nullptr; float* zv = nullptr; float* nw = nullptr
 //   FMX_COMPACT_INT8  B: one block of P bytes per feature with its scale, its w and its int8 codes (V and w stay null)
 // dir != nullptr: a pruned snapshot (fmx_compact_begin_pruned) -- the tables hold `kept` rows in slot order and dir, the rank directory
 // of ceil(n_local / 32) pairs (fmx_compact_kernels.h dir_lookup), maps a feature id to its slot
+// nonfinite .. dropped_unseen: the figures of fmx_compact_info / fmx_compact_prune_info as they were when the snapshot was taken (or as the
+// file it was loaded from holds them), for fmx_compact_save's header
 struct CompactState { uint16_t* V = nullptr; float* w = nullptr; double* w0 = nullptr; uint8_t* B = nullptr; uint32_t P = 0; uint32_t format = 0;
-                      uint2* dir = nullptr; uint64_t kept = 0; };
+                      uint2* dir = nullptr; uint64_t kept = 0;
+                      uint64_t nonfinite = 0; double max_abs_err = 0.0, sum_sq_err = 0.0; uint64_t dropped_dead = 0, dropped_unseen = 0; };
 
 struct fmx_context_s {
   fmx_config cfg;
@@ -204,6 +207,8 @@ struct fmx_context_s {
   hipStream_t stream = nullptr;
   Tab        tb = {nullptr, nullptr, 0, 0};   // V rows (+ co-located w), see fmx_kernels.h
   float*     w_sep = nullptr;    // the w[] array
+  bool       serve_only = false; // fmx_serve_open (fmx_snap.hip): the handle holds a snapshot and NO model -- tb.V, tb.w and w_sep are null and
+                                 // every entry point that is not on the allow-list of DESIGN.md section 27 refuses it first (serve_refuse)
   Placed     placed;             // fmx_place_plan.h: the report, and for a big model the ARENA both tables are parts of (nothing to hipFree): one
                                  // virtual range of 1 GiB physical chunks taken alternately from two memory classes
   double*    w0 = nullptr;       // device scalar
@@ -267,6 +272,13 @@ struct fmx_context_s {
 
 // ---- helpers shared between the translation units -------------------------------------------------------------
 int fail(fmx_handle h, int code, const char* fmt, ...);                 // fmx_core.hip
+// fmx_create behind its argument checks, for fmx_serve_open too (fmx_core.hip): serve_only = everything but the parameter tables
+int create_handle(const fmx_config* cfg, fmx_handle* out, bool serve_only);
+// what every entry point that reads or writes the model says to a serve-only handle, as its first statement after the NULL check:
+// FMX_E_STATE, nothing launched, the handle usable afterwards.  FMX_OK on an ordinary handle.
+inline int serve_refuse(fmx_handle h, const char* who) {
+  return h->serve_only ? fail(h, FMX_E_STATE, "%s: a serve-only handle holds no model", who) : FMX_OK;
+}
 Hyper make_hyper(const fmx_config& c);
 Shard make_shard(const fmx_config& c);
 constexpr int FMX_GRID_OVER_SGD = 1 << 16;   // effectively uncapped
@@ -319,6 +331,7 @@ int prep_rows(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, int k0, fl
 int topk_impl(fmx_handle h, const char* who, int query_slot, int cand_slot, const fmx_topk_opts* opts, uint32_t* idx_out, double* score_out,
               fmx_topk_stats* stats, const CompactState* snap);
 void compact_free(fmx_handle h);                                         // fmx_compact.hip
+void compact_release(CompactState& c);                                   // fmx_compact.hip: frees a snapshot's tables, leaves an empty state
 int lag_flush(fmx_handle h);                                             // fmx_sgd.hip
 // fmx_eval.hip: the argument checks, the empty result and the reduction of fmx_evaluate_ex, shared with fmx_group_evaluate_ex (fmx_comm.hip)
 int eval_ex_check_opts(fmx_handle h, const char* who, const fmx_eval_opts* opts, uint32_t* link);

@@ -139,6 +139,8 @@ done:
 extern "C" {
 
 int fmx_upload_pairs(fmx_handle h, int slot, const uint32_t* row_a, const uint32_t* row_b, uint64_t n_pairs) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_upload_pairs"); if (_sr) return _sr; }
   int rc = check_slot(h, slot, false);
   if (rc) return rc;
   if (n_pairs && (!row_a || !row_b)) return fail(h, FMX_E_ARG, "fmx_upload_pairs: row_a / row_b is NULL");
@@ -270,17 +272,24 @@ static int pair_epoch_run(fmx_handle h, int slot, const fmx_pair_opts* opts, fmx
 }
 
 int fmx_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts* opts, fmx_epoch_stats* stats) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_pair_epoch"); if (_sr) return _sr; }
   return pair_epoch_run(h, slot, opts, stats, "fmx_pair_epoch", PAIR_PLAIN);
 }
 int fmx_adapt_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts* opts, fmx_epoch_stats* stats) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_adapt_pair_epoch"); if (_sr) return _sr; }
   return pair_epoch_run(h, slot, opts, stats, "fmx_adapt_pair_epoch", PAIR_ADAGRAD);
 }
 int fmx_ftrl_pair_epoch(fmx_handle h, int slot, const fmx_pair_opts* opts, fmx_epoch_stats* stats) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_ftrl_pair_epoch"); if (_sr) return _sr; }
   return pair_epoch_run(h, slot, opts, stats, "fmx_ftrl_pair_epoch", PAIR_FTRL);
 }
 
 int fmx_pair_evaluate(fmx_handle h, int slot, fmx_pair_eval* out) {
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_pair_evaluate"); if (_sr) return _sr; }
   if (!out) return fail(h, FMX_E_ARG, "fmx_pair_evaluate: out is NULL");
   memset(out, 0, sizeof(*out));
   int rc = pair_check(h, slot, "fmx_pair_evaluate");

@@ -262,6 +262,8 @@ extern "C" {
 
 int fmx_upload_interactions(fmx_handle h, int query_slot, int cand_slot, const uint32_t* q_row, const uint32_t* c_row, uint64_t n,
                             const uint64_t* exclude_ptr, const uint32_t* exclude_idx) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_upload_interactions"); if (_sr) return _sr; }
   int rc = check_slot(h, query_slot, false);
   if (rc) return rc;
   rc = check_slot(h, cand_slot, false);
@@ -323,6 +325,8 @@ int fmx_upload_interactions(fmx_handle h, int query_slot, int cand_slot, const u
 }
 
 int fmx_interactions_info(fmx_handle h, int query_slot, int* cand_slot, uint64_t* n) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_interactions_info"); if (_sr) return _sr; }
   int rc = check_slot(h, query_slot, false);
   if (rc) return rc;
   const PairNeg* pn = h->slots[query_slot].pneg;
@@ -334,6 +338,8 @@ int fmx_interactions_info(fmx_handle h, int query_slot, int* cand_slot, uint64_t
 
 int fmx_pair_sample(fmx_handle h, int query_slot, const fmx_pairneg_opts* o, uint32_t* neg_out, uint64_t* forced_out) {
   if (forced_out) *forced_out = 0;
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_pair_sample"); if (_sr) return _sr; }
   int rc = pairneg_check(h, query_slot, o, "fmx_pair_sample");
   if (rc) return rc;
   PairNeg& pn = *h->slots[query_slot].pneg;
@@ -461,17 +467,24 @@ static int pairneg_epoch_run(fmx_handle h, int query_slot, const fmx_pairneg_opt
 }
 
 int fmx_pair_epoch_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts* o, fmx_epoch_stats* stats, uint64_t* forced_out) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_pair_epoch_sampled"); if (_sr) return _sr; }
   return pairneg_epoch_run(h, query_slot, o, stats, forced_out, "fmx_pair_epoch_sampled", PAIR_PLAIN);
 }
 int fmx_adapt_pair_epoch_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts* o, fmx_epoch_stats* stats, uint64_t* forced_out) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_adapt_pair_epoch_sampled"); if (_sr) return _sr; }
   return pairneg_epoch_run(h, query_slot, o, stats, forced_out, "fmx_adapt_pair_epoch_sampled", PAIR_ADAGRAD);
 }
 int fmx_ftrl_pair_epoch_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts* o, fmx_epoch_stats* stats, uint64_t* forced_out) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_ftrl_pair_epoch_sampled"); if (_sr) return _sr; }
   return pairneg_epoch_run(h, query_slot, o, stats, forced_out, "fmx_ftrl_pair_epoch_sampled", PAIR_FTRL);
 }
 
 int fmx_pair_evaluate_sampled(fmx_handle h, int query_slot, const fmx_pairneg_opts* o, fmx_pair_eval* out) {
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_pair_evaluate_sampled"); if (_sr) return _sr; }
   if (!out) return fail(h, FMX_E_ARG, "fmx_pair_evaluate_sampled: out is NULL");
   memset(out, 0, sizeof(*out));
   int rc = pairneg_check(h, query_slot, o, "fmx_pair_evaluate_sampled");

@@ -219,12 +219,16 @@ extern "C" {
 
 int fmx_post_begin(fmx_handle h, int slot, const fmx_post_opts* opts) {
   static const char who[] = "fmx_post_begin";
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_post_begin"); if (_sr) return _sr; }
   POST_NO_SHARD(h, who);
   return post_begin_impl(h, who, slot, opts);
 }
 
 int fmx_post_accumulate(fmx_handle h, int slot, fmx_post_stats* out) {
   static const char who[] = "fmx_post_accumulate";
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_post_accumulate"); if (_sr) return _sr; }
   POST_NO_SHARD(h, who);
   int rc = post_check(h, who, slot, true);
   if (rc) return rc;
@@ -241,18 +245,24 @@ int fmx_post_accumulate(fmx_handle h, int slot, fmx_post_stats* out) {
 
 int fmx_post_evaluate_ex(fmx_handle h, int slot, uint32_t which, fmx_eval_ex* out) {
   static const char who[] = "fmx_post_evaluate_ex";
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_post_evaluate_ex"); if (_sr) return _sr; }
   POST_NO_SHARD(h, who);
   return post_evaluate_impl(h, who, slot, which, out);
 }
 
 int fmx_post_get(fmx_handle h, int slot, uint32_t which, double* out, uint64_t* draws) {
   static const char who[] = "fmx_post_get";
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_post_get"); if (_sr) return _sr; }
   POST_NO_SHARD(h, who);
   return post_get_impl(h, who, slot, which, out, draws);
 }
 
 int fmx_post_end(fmx_handle h, int slot) {
   static const char who[] = "fmx_post_end";
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_post_end"); if (_sr) return _sr; }
   POST_NO_SHARD(h, who);
   return post_end_impl(h, who, slot);
 }

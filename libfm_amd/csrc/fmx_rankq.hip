@@ -135,6 +135,7 @@ int fmx_rank_discounts(uint32_t k_max, double* out) {
 int fmx_evaluate_rank(fmx_handle h, int slot, const fmx_rank_opts* opts, fmx_eval_rank* out, double* dcg_q, double* hits_q) {
   static const char who[] = "fmx_evaluate_rank";
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_evaluate_rank"); if (_sr) return _sr; }
   if (!out) return fail(h, FMX_E_ARG, "%s: out is NULL", who);
   uint32_t link;
   int rc = rankq_check_opts(h, who, opts, &link);

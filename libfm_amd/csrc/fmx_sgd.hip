@@ -84,12 +84,15 @@ uint32_t fmx_default_w0_chunk(double learn_rate, int task) {
 }
 int fmx_partial_floats(fmx_handle h, uint32_t batch, uint64_t* n_floats) {
   if (!h || !n_floats) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_partial_floats"); if (_sr) return _sr; }
   *n_floats = (uint64_t)batch * (uint64_t)(h->KP + 1);
   return FMX_OK;
 }
 
 // partial buffer layout: [n_rows][KP] factor sums, then [n_rows] scalars
 int fmx_sgd_partial(fmx_handle h, int slot, uint64_t row0, uint32_t n_rows, float* d_partial, void* stream) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_sgd_partial"); if (_sr) return _sr; }
   int rc = check_slot(h, slot, false);
   if (rc) return rc;
   rc = refuse_weighted(h, slot, "fmx_sgd_partial"); if (rc) return rc;
@@ -157,6 +160,8 @@ extern "C++" int sgd_resolve_batch(fmx_handle h, Slot& s, const fmx_sgd_opts* op
 }
 
 int fmx_sgd_batch_info(fmx_handle h, int slot, const fmx_sgd_opts* opts, fmx_batch_info* out) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_sgd_batch_info"); if (_sr) return _sr; }
   int rc = check_slot(h, slot, false);
   if (rc) return rc;
   if (!out) return fail(h, FMX_E_ARG, "fmx_sgd_batch_info: out is NULL");
@@ -661,6 +666,8 @@ static int sgd_finish_impl(fmx_handle h, const Slot& s, uint64_t row0, uint32_t 
 
 int fmx_sgd_finish(fmx_handle h, int slot, uint64_t row0, uint32_t n_rows, const float* d_partial,
                    const fmx_sgd_opts* opts, void* stream) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_sgd_finish"); if (_sr) return _sr; }
   touch_w(h);
   int rc = check_slot(h, slot, true); if (rc) return rc;
   rc = refuse_weighted(h, slot, "fmx_sgd_finish"); if (rc) return rc;
@@ -703,6 +710,7 @@ int fmx_sgd_finish(fmx_handle h, int slot, uint64_t row0, uint32_t n_rows, const
 
 int fmx_predict_finish(fmx_handle h, uint32_t n_rows, const float* d_partial, float* d_yhat, void* stream) {
   if (!h || !d_partial || !d_yhat) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_predict_finish"); if (_sr) return _sr; }
   if (((uintptr_t)d_partial & 15u) != 0) return fail(h, FMX_E_ARG, "fmx_predict_finish: d_partial must be 16-byte aligned");
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   if (n_rows == 0) return FMX_OK;
@@ -1293,6 +1301,8 @@ static int epoch_close(fmx_handle h, Slot& s, const fmx_sgd_opts* opts, const fm
 }
 
 int fmx_sgd_epoch(fmx_handle h, int slot, const fmx_sgd_opts* opts, fmx_epoch_stats* stats) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_sgd_epoch"); if (_sr) return _sr; }
   int rc = check_slot(h, slot, true); if (rc) return rc;
   rc = refuse_weighted(h, slot, "fmx_sgd_epoch"); if (rc) return rc;
   { int _rc = lag_flush(h); if (_rc) return _rc; }
@@ -1358,6 +1368,7 @@ extern "C++" void sgda_free(fmx_handle h) {
 
 int fmx_sgda_end(fmx_handle h) {
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_sgda_end"); if (_sr) return _sr; }
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   sgda_free(h);
@@ -1365,6 +1376,8 @@ int fmx_sgda_end(fmx_handle h) {
 }
 
 int fmx_sgda_begin(fmx_handle h) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_sgda_begin"); if (_sr) return _sr; }
   touch_w(h);
   if (!h) return FMX_E_ARG;
   if (h->adapt.nv) return fail(h, FMX_E_STATE, "fmx_sgda_begin: an fmx_adapt session is open (call fmx_adapt_end first)");
@@ -1390,6 +1403,7 @@ int fmx_sgda_begin(fmx_handle h) {
 
 int fmx_sgda_get_reg(fmx_handle h, double* reg) {
   if (!h || !reg) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_sgda_get_reg"); if (_sr) return _sr; }
   if (!h->sgda.reg) return fail(h, FMX_E_STATE, "fmx_sgda_get_reg before fmx_sgda_begin");
   HIPCHK(h, hipSetDevice(h->device));
   const size_t G = h->num_groups, k = (size_t)h->cfg.num_factor, KP = (size_t)h->KP;
@@ -1401,6 +1415,8 @@ int fmx_sgda_get_reg(fmx_handle h, double* reg) {
 }
 
 int fmx_sgda_epoch(fmx_handle h, int train_slot, int validation_slot, int do_lambda_steps, fmx_epoch_stats* stats) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_sgda_epoch"); if (_sr) return _sr; }
   touch_w(h);
   int rc = check_slot(h, train_slot, true);
   if (rc) return rc;
@@ -1446,6 +1462,8 @@ int fmx_sgda_epoch(fmx_handle h, int train_slot, int validation_slot, int do_lam
 // minibatch rule, then -- do_lambda_steps -- the lambda steps of the next `batch` validation rows, summed and applied once
 int fmx_sgda_epoch_minibatch(fmx_handle h, int train_slot, int validation_slot, int do_lambda_steps, uint32_t batch,
                              uint32_t w0_chunk, fmx_epoch_stats* stats) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_sgda_epoch_minibatch"); if (_sr) return _sr; }
   touch_w(h);
   int rc = check_slot(h, train_slot, true);
   if (rc) return rc;
@@ -1594,6 +1612,8 @@ extern "C++" int adapt_begin_open(fmx_handle h, const fmx_adapt_opts* opts, floa
 }
 
 int fmx_adapt_begin(fmx_handle h, const fmx_adapt_opts* opts) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_adapt_begin"); if (_sr) return _sr; }
   float init_acc = 0.f;
   int rc = adapt_begin_check(h, opts, false, &init_acc); if (rc) return rc;
   return adapt_begin_open(h, opts, init_acc);
@@ -1610,7 +1630,11 @@ extern "C++" int adapt_end_impl(fmx_handle h, bool in_group) {
   adapt_free(h);
   return FMX_OK;
 }
-int fmx_adapt_end(fmx_handle h) { return adapt_end_impl(h, false); }
+int fmx_adapt_end(fmx_handle h) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_adapt_end"); if (_sr) return _sr; }
+  return adapt_end_impl(h, false);
+}
 
 // the gather of fmx_get_param_rows over nt state tables, one after the other: outs[t] = {the linear weights' state, the factors' state}
 static int state_rows(fmx_handle h, const char* what, const uint32_t* ids, uint32_t count, const Tab* tabs, double* const (*outs)[2], int nt) {
@@ -1635,6 +1659,8 @@ extern "C++" int adapt_state_rows_impl(fmx_handle h, bool in_group, const uint32
   return state_rows(h, "fmx_adapt_get_state_rows", ids, count, tabs, outs, 1);
 }
 int fmx_adapt_get_state_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double* nw_out, double* nv_out) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_adapt_get_state_rows"); if (_sr) return _sr; }
   return adapt_state_rows_impl(h, false, ids, count, nw_out, nv_out);
 }
 
@@ -1750,6 +1776,8 @@ extern "C++" int adapt_epoch_impl(fmx_handle h, bool in_group, int slot, uint32_
   });
 }
 int fmx_adapt_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_adapt_epoch"); if (_sr) return _sr; }
   return adapt_epoch_impl(h, false, slot, batch, w0_chunk, stats);
 }
 
@@ -1860,6 +1888,8 @@ extern "C++" int ftrl_begin_open(fmx_handle h, const FtrlState& constants) {
 }
 
 int fmx_ftrl_begin(fmx_handle h, const fmx_ftrl_opts* opts) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_ftrl_begin"); if (_sr) return _sr; }
   FtrlState f;
   int rc = ftrl_begin_check(h, opts, false, &f); if (rc) return rc;
   return ftrl_begin_open(h, f);
@@ -1874,7 +1904,11 @@ extern "C++" int ftrl_end_impl(fmx_handle h, bool in_group) {
   ftrl_free(h);
   return FMX_OK;
 }
-int fmx_ftrl_end(fmx_handle h) { return ftrl_end_impl(h, false); }
+int fmx_ftrl_end(fmx_handle h) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_ftrl_end"); if (_sr) return _sr; }
+  return ftrl_end_impl(h, false);
+}
 
 extern "C++" int ftrl_state_rows_impl(fmx_handle h, bool in_group, const uint32_t* ids, uint32_t count, double* zw, double* zv, double* nw, double* nv) {
   if (!h) return FMX_E_ARG;
@@ -1886,6 +1920,8 @@ extern "C++" int ftrl_state_rows_impl(fmx_handle h, bool in_group, const uint32_
   return state_rows(h, "fmx_ftrl_get_state_rows", ids, count, tabs, outs, 2);
 }
 int fmx_ftrl_get_state_rows(fmx_handle h, const uint32_t* ids, uint32_t count, double* zw, double* zv, double* nw, double* nv) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_ftrl_get_state_rows"); if (_sr) return _sr; }
   return ftrl_state_rows_impl(h, false, ids, count, zw, zv, nw, nv);
 }
 
@@ -1902,6 +1938,8 @@ extern "C++" int ftrl_epoch_impl(fmx_handle h, bool in_group, int slot, uint32_t
   });
 }
 int fmx_ftrl_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_ftrl_epoch"); if (_sr) return _sr; }
   return ftrl_epoch_impl(h, false, slot, batch, w0_chunk, stats);
 }
 
@@ -1937,6 +1975,10 @@ extern "C++" int param_sparsity_impl(fmx_handle h, bool in_group, fmx_sparsity* 
   out->v_zero_rows = host[2]; out->dead_features = host[3];
   return FMX_OK;
 }
-int fmx_param_sparsity(fmx_handle h, fmx_sparsity* out) { return param_sparsity_impl(h, false, out); }
+int fmx_param_sparsity(fmx_handle h, fmx_sparsity* out) {
+  if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_param_sparsity"); if (_sr) return _sr; }
+  return param_sparsity_impl(h, false, out);
+}
 
 }  // extern "C"

@@ -218,6 +218,7 @@ extern "C" {
 int fmx_topk(fmx_handle h, int query_slot, int cand_slot, const fmx_topk_opts* opts, uint32_t* idx_out, double* score_out,
              fmx_topk_stats* stats) {
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_topk"); if (_sr) return _sr; }
   return topk_impl(h, "fmx_topk", query_slot, cand_slot, opts, idx_out, score_out, stats, nullptr);
 }
 

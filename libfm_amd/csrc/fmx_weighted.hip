@@ -24,6 +24,7 @@ extern "C" {
 int fmx_set_row_weights(fmx_handle h, int slot, const float* weight) {
   static const char who[] = "fmx_set_row_weights";
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_set_row_weights"); if (_sr) return _sr; }
   if (slot < 0 || slot >= FMX_MAX_SLOTS) return fail(h, FMX_E_ARG, "%s: slot %d out of range", who, slot);
   if (h->cfg.shard_world > 1 || h->comm || (h->group && !h->owns_group))
     return fail(h, FMX_E_UNSUPPORTED, "%s: not supported on feature shards / communicator ranks", who);
@@ -54,6 +55,7 @@ int fmx_set_row_weights(fmx_handle h, int slot, const float* weight) {
 int fmx_get_row_weights(fmx_handle h, int slot, float* out) {
   static const char who[] = "fmx_get_row_weights";
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_get_row_weights"); if (_sr) return _sr; }
   if (slot < 0 || slot >= FMX_MAX_SLOTS) return fail(h, FMX_E_ARG, "%s: slot %d out of range", who, slot);
   const Slot& s = h->slots[slot];
   if (!s.used) return fail(h, FMX_E_STATE, "%s: slot %d holds no rows (call fmx_upload_rows first)", who, slot);
@@ -68,6 +70,7 @@ int fmx_get_row_weights(fmx_handle h, int slot, float* out) {
 int fmx_evaluate_weighted(fmx_handle h, int slot, const fmx_eval_opts* opts, fmx_eval_weighted* out) {
   static const char who[] = "fmx_evaluate_weighted";
   if (!h) return FMX_E_ARG;
+  { const int _sr = serve_refuse(h, "fmx_evaluate_weighted"); if (_sr) return _sr; }
   if (!out) return fail(h, FMX_E_ARG, "%s: out is NULL", who);
   uint32_t link;
   int rc = eval_ex_check_opts(h, who, opts, &link);

@@ -223,10 +223,69 @@ class CompactView:
         qs, cs = self._l._topk_slots(queries, candidates)
         return self._l._h.compact_topk(qs, cs, topk, 0, queries.num_cases, exclude)
 
+    topk = recommend
+
+    def rows(self, ids):
+        """(w[ids], v[:, ids]) as the copy holds them, dequantised; zeros for a feature a pruned copy dropped (fmx_compact_get_rows)"""
+        return self._l._h.compact_rows(ids)
+
+    def save(self, path):
+        """the copy as a snapshot file, written straight from its device tables (fmx_compact_save): load_snapshot(path) serves from it
+        in a process that never holds the model.  Returns the capi.SnapInfo of the file."""
+        return self._l._h.compact_save(path)
+
     def close(self):
         if self._l is not None and self._l._h is not None:
-            self._l._h.compact_end()
+            if getattr(self._l, "owns_handle", False):           # load_snapshot: the view is all there is -- the handle goes with it
+                self._l._h.close()
+                self._l._h = None
+            else:
+                self._l._h.compact_end()
         self._l = None
+
+
+class _SnapshotSource:
+    """what a CompactView asks of its learner, over a serve-only handle (load_snapshot): the handle, a slot per data set, and the link
+    of fm_learn_sgd::predict under the file's task and target range"""
+    EVAL_LINK = capi.LINK_LOGISTIC
+    owns_handle = True
+
+    def __init__(self, h):
+        self._h = h
+        self._slots = {}
+        self.task, self.min_target, self.max_target = int(h.snap_info.task), float(h.snap_info.min_target), float(h.snap_info.max_target)
+
+    def _compact_slot(self, data):
+        key = id(data)
+        if key not in self._slots:
+            if len(self._slots) >= capi.MAX_SLOTS:
+                raise RuntimeError("too many data sets")
+            data.upload(self._h, len(self._slots))
+            self._slots[key] = len(self._slots)
+        return self._slots[key]
+
+    def _topk_slots(self, queries, candidates):
+        return self._compact_slot(queries), self._compact_slot(candidates)
+
+    def _link(self, p):
+        if self.task == TASK_REGRESSION:
+            return np.maximum(self.min_target, np.minimum(self.max_target, p))
+        return 1.0 / (1.0 + np.exp(-p))
+
+
+def load_snapshot(path, device=-1):
+    """a CompactView over a SERVE-ONLY handle made from a snapshot file alone (fmx_serve_open): no model is created or loaded, the
+    device holds the snapshot and nothing else.  predict / evaluate / evaluate_ex / recommend (topk) / rows / save work as on a view of a
+    learner; predict links as fm_learn_sgd::predict does under the file's task and target range.  close() destroys the handle.
+    `info` is the file's capi.SnapInfo."""
+    h = capi.serve_open(path, device)
+    view = CompactView.__new__(CompactView)
+    view._l = _SnapshotSource(h)
+    view.info = h.snap_info
+    view.format = compact_format.FORMAT_NAMES[int(view.info.format)]
+    view.prune = None if not view.info.pruned else ("seen" if view.info.dropped_unseen else "dead")
+    view.prune_info = None
+    return view
 
 
 class FMLearnSGD:
