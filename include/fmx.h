@@ -1281,8 +1281,9 @@ int fmx_param_sparsity(fmx_handle h, fmx_sparsity *out);
  * while the other optimiser's session or an SGDA session is open on any member; an open ALS / MCMC session on any member; members
  * holding different row counts in the slot; a destroyed member.  FMX_E_UNSUPPORTED: a slot with kept `-relation` blocks; a slot with
  * row weights on any member; a member that is a communicator rank (fmx_comm_init_rank).  FMX_E_ARG: as the per-handle calls.
- * Not offered on shards: checkpoints, row weights, the pairwise epochs.  The per-handle fmx_adapt_*, fmx_ftrl_*, fmx_param_sparsity
- * and fmx_checkpoint_* keep refusing a shard handle or group member with FMX_E_UNSUPPORTED.
+ * Not offered on shards: row weights, the pairwise epochs.  The per-handle fmx_adapt_*, fmx_ftrl_*, fmx_param_sparsity
+ * and fmx_checkpoint_* keep refusing a shard handle or group member with FMX_E_UNSUPPORTED; the group form of the checkpoint is
+ * fmx_group_checkpoint_save / _load (declared after fmx_checkpoint_*, whose types it takes).
  * Added without an ABI version change: a caller detects the feature by the symbol fmx_group_adapt_begin. */
 int fmx_group_adapt_begin(fmx_group g, const fmx_adapt_opts *opts);
 int fmx_group_adapt_epoch(fmx_group g, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
@@ -1463,6 +1464,37 @@ typedef struct fmx_ckpt_info {
 int fmx_checkpoint_save(fmx_handle h, const char *path, const fmx_ckpt_opts *opts, fmx_ckpt_info *info /* may be NULL */);
 int fmx_checkpoint_load(fmx_handle h, const char *path, const fmx_ckpt_opts *opts, fmx_ckpt_info *info /* may be NULL */);
 int fmx_checkpoint_info(const char *path, fmx_ckpt_info *info, char *err, size_t err_len);   /* header only; no handle, no GPU */
+
+/* ---- group checkpoints: the same file in global feature order, whatever the shard count ------------------
+ * The group forms of fmx_checkpoint_save / _load, for the model and the fmx_group_adapt_* / fmx_group_ftrl_* session that the members
+ * of an fmx_group hold between them.  Everything said above holds with "the handle" read as "the model the group holds".  The file
+ * is the SAME file: the group writes, byte for byte, what one unsharded handle holding the same parameters and session would write,
+ * so it does not record how the model was sharded.  A group of any shard count and either shard_hash loads it, one unsharded handle
+ * loads it through fmx_checkpoint_load (and goes on to fmx_save_model, fmx_compact_*, fmx_serve_open), and two saves of equal state
+ * from any two groups are byte-identical.  Same format, same version.
+ * Added without an ABI version change: a caller detects the feature by the symbol fmx_group_checkpoint_save.
+ *
+ *   fmx_group_checkpoint_save : every member packs the rows it owns into a chunk of its own, the chunks meet on member 0's device
+ *                         (the lead) and are merged there into the chunk the file gets; the lead forms the checksums and writes.
+ *                         The sparse id list is the members' flagged rows as global ids, sorted on the lead.  w0 is replicated:
+ *                         member 0's is written.
+ *   fmx_group_checkpoint_load : the lead reads, forms every checksum over what arrived in ITS device memory and validates the id
+ *                         list over its whole length before the list reaches a member and before a row is scattered; every member
+ *                         stores the rows it owns.  w0 is set on every member.  Sessions, all members or none: a file with a
+ *                         session replaces the session of every member; a file without one, or FMX_CKPT_MODEL_ONLY, leaves
+ *                         every member's alone.
+ *   info is filled as by the per-handle calls; device_seconds is the sum over the lead's chunks.
+ *
+ * Refusals that change nothing, the group usable afterwards, the message in fmx_group_last_error: every refusal fmx_checkpoint_load
+ * decides from the header, with its code and message shape, against the group's GLOBAL geometry; FMX_E_ARG for a NULL group, a NULL
+ * path or unknown flags; FMX_E_STATE for a load during an open SGDA or ALS / MCMC session on any member, for a destroyed member and
+ * for members that hold different kinds of session or describe different models; FMX_E_UNSUPPORTED for a member that is a
+ * communicator rank (fmx_comm_init_rank: its peers live in other processes).
+ * Found while streaming (checksum, bad id list, read error): FMX_E_ARG naming the section; the parameters are then unspecified on
+ * every member and every member's fmx_adapt / fmx_ftrl session is closed, as the message says; the group stays usable.
+ * A group of one unsharded handle takes the per-handle path: same bits, same bytes. */
+int fmx_group_checkpoint_save(fmx_group g, const char *path, const fmx_ckpt_opts *opts, fmx_ckpt_info *info /* may be NULL */);
+int fmx_group_checkpoint_load(fmx_group g, const char *path, const fmx_ckpt_opts *opts, fmx_ckpt_info *info /* may be NULL */);
 
 /* ---- a serving snapshot as a file, and a handle that serves from it without the model -------------------
  * fmx_compact_begin* need the fp32 model beside the snapshot they take.  These four calls let a snapshot leave the handle that made it:

@@ -397,6 +397,8 @@ SYMBOLS = [
     ("fmx_checkpoint_save", C.c_int, [H, C.c_char_p, C.POINTER(CkptOpts), C.POINTER(CkptInfo)]),
     ("fmx_checkpoint_load", C.c_int, [H, C.c_char_p, C.POINTER(CkptOpts), C.POINTER(CkptInfo)]),
     ("fmx_checkpoint_info", C.c_int, [C.c_char_p, C.POINTER(CkptInfo), C.c_char_p, C.c_size_t]),
+    ("fmx_group_checkpoint_save", C.c_int, [H, C.c_char_p, C.POINTER(CkptOpts), C.POINTER(CkptInfo)]),
+    ("fmx_group_checkpoint_load", C.c_int, [H, C.c_char_p, C.POINTER(CkptOpts), C.POINTER(CkptInfo)]),
     ("fmx_als_begin", C.c_int, [H, C.c_int]),
     ("fmx_als_moments", C.c_int, [H, C.c_void_p]),
     ("fmx_als_sweep", C.c_int, [H, C.POINTER(AlsOpts), C.POINTER(AlsStats)]),
@@ -1428,6 +1430,21 @@ class Group:
         sp = Sparsity()
         self._chk(self.lib.fmx_group_param_sparsity(self.g, C.byref(sp)))
         return sp
+
+    # group checkpoints (include/fmx.h "fmx_group_checkpoint_*"): the unsharded handle's file, in global feature order
+    def checkpoint_save(self, path, dense=False, model_only=False):
+        """Handle.checkpoint_save of the model and the session the members hold between them: byte for byte the file one unsharded
+        handle with the same state writes, loadable by a group of any shard count or by a Handle (fmx_group_checkpoint_save)"""
+        opts, info = CkptOpts((CKPT_DENSE_STATE if dense else 0) | (CKPT_MODEL_ONLY if model_only else 0), 0), CkptInfo()
+        self._chk(self.lib.fmx_group_checkpoint_save(self.g, None if path is None else os.fsencode(path), C.byref(opts), C.byref(info)))
+        return info
+
+    def checkpoint_load(self, path, model_only=False):
+        """Handle.checkpoint_load on every member, each taking the rows it owns; sessions on all members or none
+        (fmx_group_checkpoint_load)"""
+        opts, info = CkptOpts(CKPT_MODEL_ONLY if model_only else 0, 0), CkptInfo()
+        self._chk(self.lib.fmx_group_checkpoint_load(self.g, None if path is None else os.fsencode(path), C.byref(opts), C.byref(info)))
+        return info
 
     def get_params(self, w=None, v=None):
         """the full model: every shard writes its own features into the same host arrays"""

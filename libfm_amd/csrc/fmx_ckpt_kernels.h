@@ -15,6 +15,19 @@
 //                      (AdaGrad: any of n_w, n_v[0 .. k) differs from init_acc; FTRL: any (z, n) differs from ftrl_start of its
 //                      theta), bit for bit.  L lanes (a power of two <= 64) share a feature, as in k_param_sparsity.
 //   k_ckpt_compact     ids[pos[j]] = j for the flagged rows, pos the exclusive scan of the flags: ascending by construction.
+//
+// The group form (fmx_group_checkpoint_*): the file is in GLOBAL feature order, every member of the group holds
+// the rows of the features it owns, and no kernel dereferences another device's table -- staging buffers travel, tables do not.
+//   k_ckpt_rows_shard<PACK>  k_ckpt_rows on one member: element e of the chunk belongs to global row ids ? ids[r0 + r] : r0 + r, and
+//                      Shard::place says whether this member owns that row and where.  The filter is per 4-byte ELEMENT, not per
+//                      word: a word of w (cols = 1) holds two features, a word of a state row with odd cols = k + 1 straddles two
+//                      rows, and either pair may have two owners.  PACK = true writes the whole chunk, 0 where the row is someone
+//                      else's (a complete chunk with holes) and forms no checksum: a word is not complete on one member.
+//                      PACK = false stores the owned elements only; with sum != nullptr (the lead) it adds the terms of ALL words
+//                      of the staging buffer -- what arrived in device memory -- as k_ckpt_rows<false> does.
+//   k_ckpt_merge       on the lead: one thread per word ORs the members' chunks (the owners are disjoint, so OR is select), writes
+//                      the pipe's staging buffer and adds the word's checksum term; one integer atomic per wavefront.
+//   k_ckpt_global_ids  rows[i] = the global id of this member's local row rows[i] (Shard::global), in place.
 #pragma once
 #include "fmx_ftrl_kernels.h"
 
@@ -64,6 +77,68 @@ k_ckpt_rows(CkptRows t, uint64_t r0, uint32_t n_elems, uint64_t word0, unsigned 
     }
   }
   ckpt_wave_add(acc, sum);
+}
+
+// (the two elements of a word share a row more often than not: the permutation is evaluated once for both then)
+template <bool PACK>
+__global__ void __launch_bounds__(256)
+k_ckpt_rows_shard(CkptRows t, Shard sh, uint64_t r0, uint32_t n_elems, uint64_t word0, unsigned long long* __restrict__ stage,
+                  unsigned long long* __restrict__ sum) {
+  const uint32_t n_words = (n_elems + 1u) >> 1;
+  const uint32_t stride = gridDim.x * blockDim.x;
+  const uint32_t first = t.lin ? 1u : 0u;
+  unsigned long long acc = 0ull;
+  for (uint32_t w0 = blockIdx.x * blockDim.x; w0 < n_words; w0 += stride) {
+    const uint32_t w = w0 + threadIdx.x;
+    if (w < n_words) {
+      unsigned long long u = PACK ? 0ull : stage[w];
+      uint32_t half[2] = {(uint32_t)u, (uint32_t)(u >> 32)};
+      uint32_t seen_r = 0xFFFFFFFFu, local = 0u;
+      bool mine = false;
+#pragma unroll
+      for (int q = 0; q < 2; q++) {
+        const uint32_t e = 2u * w + (uint32_t)q;
+        if (e < n_elems) {
+          const uint32_t r = e / t.cols, c = e - r * t.cols;
+          if (r != seen_r) {
+            seen_r = r;
+            mine = sh.place(t.ids ? t.ids[r0 + r] : (uint32_t)(r0 + r), &local);
+          }
+          if (mine) {
+            float* p = (c < first) ? t.lin + (uint64_t)local * t.ls : t.tab + (uint64_t)local * t.rs + (c - first);
+            if (PACK) half[q] = __float_as_uint(*p); else *p = __uint_as_float(half[q]);
+          }
+        }
+      }
+      if (PACK) stage[w] = (unsigned long long)half[0] | (unsigned long long)half[1] << 32;
+      else acc += mix64(u ^ ((word0 + w) * CKPT_GOLDEN));
+    }
+  }
+  if (!PACK && sum) ckpt_wave_add(acc, sum);                     // (sum is a kernel argument: the whole grid takes the same side)
+}
+
+struct CkptParts { const unsigned long long* p[16]; int n; };   // the members' chunks, all on the lead's device (a group has <= 16 members)
+
+static __global__ void __launch_bounds__(256)
+k_ckpt_merge(CkptParts parts, uint32_t n_words, uint64_t word0, unsigned long long* __restrict__ out, unsigned long long* __restrict__ sum) {
+  const uint32_t stride = gridDim.x * blockDim.x;
+  unsigned long long acc = 0ull;
+  for (uint32_t w0 = blockIdx.x * blockDim.x; w0 < n_words; w0 += stride) {
+    const uint32_t w = w0 + threadIdx.x;
+    if (w < n_words) {
+      unsigned long long u = 0ull;
+      for (int i = 0; i < parts.n; i++) u |= parts.p[i][w];
+      out[w] = u;
+      acc += mix64(u ^ ((word0 + w) * CKPT_GOLDEN));
+    }
+  }
+  ckpt_wave_add(acc, sum);
+}
+
+static __global__ void __launch_bounds__(256)
+k_ckpt_global_ids(Shard sh, uint32_t* __restrict__ rows, uint64_t count) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) rows[i] = sh.global(rows[i]);
 }
 
 static __global__ void __launch_bounds__(256)

@@ -304,7 +304,10 @@ class FMLearnSGD:
     one feature shard per entry (hashed ownership; "[0, 0]" = two shards on one device) and optimizer 'adagrad' / 'ftrl' train over
     the shards (capi.Group, fmx_group_adapt_* / fmx_group_ftrl_*): learn, predict, evaluate, evaluate_ex, extra_metrics, set_queries
     and sparsity() run through the group.  Optimizer 'sgd' has no sharded form here, nor have compact(), recommend(), checkpoints and
-    row weights: each raises NotImplementedError before any device is touched."""
+    row weights: each raises NotImplementedError before any device is touched.  Checkpoints of a sharded model exist one layer down:
+    capi.Group.checkpoint_save / checkpoint_load (fmx_group_checkpoint_*) write and read the unsharded handle's file in global
+    feature order, so the route from shards to this learner is the file itself -- load_checkpoint of an unsharded FMLearnSGD
+    continues from a file a group wrote."""
 
     OPTIMIZERS = ("sgd", "adagrad", "ftrl")
     SHARDED_OPTIMIZERS = ("adagrad", "ftrl")                    # what `devices` with more than one entry is honoured for
