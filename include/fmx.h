@@ -1554,6 +1554,54 @@ int fmx_compact_load(fmx_handle h, const char *path, fmx_snap_info *info /* may 
 int fmx_snapshot_info(const char *path, fmx_snap_info *info, char *err, size_t err_len);   /* header only; no handle, no GPU */
 int fmx_serve_open(const char *path, int device, fmx_handle *out, fmx_snap_info *info /* may be NULL */);
 
+/* ---- the field-weighted FM (FwFM, Pan et al., WWW 2018) -------------------------------------------------
+ *   y(x) = w0 + sum_j w_j x_j + sum_{i<j} r[g(i)][g(j)] <v_i, v_j> x_i x_j
+ * g() is the feature -> field map of fmx_set_groups (none: one field), r a symmetric F x F matrix learned with everything else.
+ * w and V stay the handle's tables; the session owns only r and its AdaGrad accumulators n_r.  r belongs to the SESSION: fmx_predict,
+ * fmx_evaluate and every other existing call keep scoring the plain FM whatever r holds (r == 1 everywhere IS the plain FM).
+ * Added without an ABI version change: a caller detects the feature by the symbol fmx_fwfm_begin.
+ *
+ * With S_g = sum_{i in g} v_i x_i (the field sums of a row), T = r S and D_g = sum_{i in g} |v_i|^2 x_i^2:
+ *   pair term = 1/2 sum_g <S_g, T_g> - 1/2 sum_g r_gg D_g
+ *   d/dv_i = x_i (T_g(i) - r_g(i)g(i) v_i x_i)      d/dr_gh = <S_g, S_h> (g != h)      d/dr_gg = 1/2 (|S_g|^2 - D_g)
+ *
+ *   fmx_fwfm_begin    : r = all ones, n_r = init_acc_r.  Called again it resets both.
+ *   fmx_fwfm_set_r    : r[F][F] row-major; refuses a matrix that is not symmetric or not finite.  n_r keeps its values.
+ *   fmx_fwfm_get_r    : r and, where n_r is not NULL, the accumulators (both [F][F]).
+ *   fmx_fwfm_predict  : fmx_predict's contract under the session's r.
+ *   fmx_fwfm_evaluate : fmx_evaluate's contract under the session's r.
+ *   fmx_fwfm_epoch    : fmx_adapt_epoch's contract (batch, w0_chunk, stats, an empty slot) with the FwFM's sums and gradients.  It needs
+ *                       an open fmx_adapt session and steps w and V on THAT session's accumulators with its eta; per batch it then
+ *                       takes, from the batch-start r, g_gh = sum_e mult_e dy_e/dr_gh + reg_r r_gh (once per batch), n_r += g^2,
+ *                       r -= eta_r g / sqrt(n_r) on the upper triangle and the diagonal, mirrored so that r stays exactly symmetric.
+ *                       The bias keeps its micro-chunk SGD.  No float atomics anywhere: two runs give the same bits.
+ *   fmx_fwfm_end      : frees r, n_r and the session's scratch.
+ * Limits: at most FMX_FWFM_MAX_FIELDS fields and 1 <= num_factor <= FMX_FWFM_MAX_FACTORS (FMX_E_UNSUPPORTED beyond).  Scratch of an epoch:
+ * batch * F_pad * (2 * k_padded + 1) * 4 bytes, F_pad = F rounded up to 16.
+ * Refusals, each before any launch, the handle usable afterwards.  FMX_E_ARG: NULL opts, r or out; flags != 0; a negative, NaN or
+ * infinite option.  FMX_E_STATE: any call but _begin without a session; num_groups changed under the session (fmx_set_groups);
+ * fmx_fwfm_epoch without an fmx_adapt session; a slot never uploaded, or without targets for _epoch and _evaluate; an open SGDA or
+ * ALS / MCMC session.  FMX_E_UNSUPPORTED: a feature shard or communicator rank; kept `-relation` blocks; a slot with row weights;
+ * F or num_factor beyond the limits.
+ * Not offered under r: FTRL, the pairwise epochs, fmx_evaluate_ex / _by_query / _rank, fmx_topk, checkpoints and snapshots of r,
+ * feature shards and groups, row weights. */
+#define FMX_FWFM_MAX_FIELDS 64
+#define FMX_FWFM_MAX_FACTORS 128
+typedef struct fmx_fwfm_opts {
+  uint32_t flags;          /* 0 */
+  uint32_t reserved;
+  double   learn_rate_r;   /* 0 = the AdaGrad session's eta at the time of the epoch */
+  double   init_acc_r;     /* 0 = 1.0 */
+  double   reg_r;          /* L2 on r, default 0 */
+} fmx_fwfm_opts;
+int fmx_fwfm_begin(fmx_handle h, const fmx_fwfm_opts *opts);
+int fmx_fwfm_set_r(fmx_handle h, const double *r /* [F][F] */);
+int fmx_fwfm_get_r(fmx_handle h, double *r, double *n_r /* may be NULL */);
+int fmx_fwfm_predict(fmx_handle h, int slot, double *out);
+int fmx_fwfm_evaluate(fmx_handle h, int slot, fmx_eval *out);
+int fmx_fwfm_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
+int fmx_fwfm_end(fmx_handle h);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 typedef struct fmx_info {
   uint64_t n_local;         /* features held by this handle */

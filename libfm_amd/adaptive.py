@@ -46,6 +46,26 @@ def _multiplier(task, p, y, min_target, max_target):
     return -y * (1.0 - 1.0 / (1.0 + np.exp(-y * p)))
 
 
+def bias_steps(model, rest, target, task, lr, min_target, max_target, batch, w0_chunk, dtype=np.float64, cw=None):
+    """step 2 of a batch, for every model on the batch rule (fwfm.py too): the bias advances in micro-chunks with plain SGD, in place
+    on model.w0; returns mult[nb], every example's multiplier taken with its micro-chunk's own bias (times its weight cw[e], if any)"""
+    T = np.dtype(dtype).type
+    nb = len(rest)
+    y = np.asarray(target).astype(dtype)
+    mult = np.zeros(nb, dtype=dtype)
+    chunk = nb if (w0_chunk == 0 or w0_chunk > batch) else int(w0_chunk)
+    for c0 in range(0, nb, chunk):
+        c1 = min(nb, c0 + chunk)
+        w0s = T(model.w0) if model.k0 else T(0)
+        me = _multiplier(task, w0s + rest[c0:c1], y[c0:c1], T(min_target), T(max_target)).astype(dtype)
+        if cw is not None:
+            me = (me * cw[c0:c1]).astype(dtype)
+        mult[c0:c1] = me
+        if model.k0:
+            model.w0 -= float(lr) * (float(me.sum(dtype=np.float64)) + (c1 - c0) * float(model.reg0) * float(w0s))
+    return mult
+
+
 def epoch(model, data, task, lr, min_target, max_target, batch, w0_chunk, state, eta=None, rule="adagrad", dtype=np.float64,
           weights=None):
     """one epoch over `data` (oracle.Data layout: entries {id, value}, row_ptr, target), in place on `model` (oracle.Model layout:
@@ -84,18 +104,8 @@ def epoch(model, data, task, lr, min_target, max_target, batch, w0_chunk, state,
             np.add.at(Q, ex, d * d)
             rest += (T(0.5) * (S * S - Q)).sum(axis=1, dtype=dtype)
         # step 2: the bias in micro-chunks, plain SGD
-        y = data.target[r0:r0 + nb].astype(dtype)
-        mult = np.zeros(nb, dtype=dtype)
-        chunk = nb if (w0_chunk == 0 or w0_chunk > batch) else int(w0_chunk)
-        for c0 in range(0, nb, chunk):
-            c1 = min(nb, c0 + chunk)
-            w0s = T(model.w0) if model.k0 else T(0)
-            me = _multiplier(task, w0s + rest[c0:c1], y[c0:c1], T(min_target), T(max_target)).astype(dtype)
-            if cw is not None:
-                me = (me * cw[r0 + c0:r0 + c1]).astype(dtype)
-            mult[c0:c1] = me
-            if model.k0:
-                model.w0 -= float(lr) * (float(me.sum(dtype=np.float64)) + (c1 - c0) * float(model.reg0) * float(w0s))
+        mult = bias_steps(model, rest, data.target[r0:r0 + nb], task, lr, min_target, max_target, batch, w0_chunk, dtype,
+                          None if cw is None else cw[r0:r0 + nb])
         # step 3: one gradient sum per touched feature, occurrences in row order
         feats, inv = np.unique(ids, return_inverse=True)
         nocc = np.bincount(inv, minlength=len(feats)).astype(dtype)

@@ -76,6 +76,14 @@ class AdaptOpts(C.Structure):
     _fields_ = [("rule", C.c_uint32), ("flags", C.c_uint32), ("init_acc", C.c_double), ("learn_rate", C.c_double)]
 
 
+FWFM_MAX_FIELDS, FWFM_MAX_FACTORS = 64, 128        # FMX_FWFM_MAX_FIELDS, FMX_FWFM_MAX_FACTORS
+
+
+class FwfmOpts(C.Structure):                       # fmx_fwfm_opts
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("learn_rate_r", C.c_double), ("init_acc_r", C.c_double),
+                ("reg_r", C.c_double)]
+
+
 class FtrlOpts(C.Structure):                       # fmx_ftrl_opts
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("alpha", C.c_double), ("beta", C.c_double),
                 ("l1_w", C.c_double), ("l1_v", C.c_double), ("l2_w", C.c_double), ("l2_v", C.c_double), ("init_acc", C.c_double)]
@@ -420,6 +428,13 @@ SYMBOLS = [
     ("fmx_compact_load", C.c_int, [H, C.c_char_p, C.POINTER(SnapInfo)]),
     ("fmx_snapshot_info", C.c_int, [C.c_char_p, C.POINTER(SnapInfo), C.c_char_p, C.c_size_t]),
     ("fmx_serve_open", C.c_int, [C.c_char_p, C.c_int, C.POINTER(H), C.POINTER(SnapInfo)]),
+    ("fmx_fwfm_begin", C.c_int, [H, C.POINTER(FwfmOpts)]),
+    ("fmx_fwfm_set_r", C.c_int, [H, C.c_void_p]),
+    ("fmx_fwfm_get_r", C.c_int, [H, C.c_void_p, C.c_void_p]),
+    ("fmx_fwfm_predict", C.c_int, [H, C.c_int, C.c_void_p]),
+    ("fmx_fwfm_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
+    ("fmx_fwfm_epoch", C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
+    ("fmx_fwfm_end", C.c_int, [H]),
     ("fmx_get_info", C.c_int, [H, C.POINTER(Info)]),
     ("fmx_synchronize", C.c_int, [H]),
 ]
@@ -973,6 +988,41 @@ class Handle:
 
     def adapt_end(self):
         self._chk(self.lib.fmx_adapt_end(self.h))
+
+    # the field-weighted FM (include/fmx.h "fmx_fwfm_*"): fields = the groups of set_groups ------
+    def fwfm_begin(self, learn_rate_r=0.0, init_acc_r=0.0, reg_r=0.0):
+        opts = FwfmOpts(0, 0, float(learn_rate_r), float(init_acc_r), float(reg_r))
+        self._chk(self.lib.fmx_fwfm_begin(self.h, C.byref(opts)))
+
+    def fwfm_set_r(self, r):
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if r.shape != (self.G, self.G):
+            raise ValueError("fwfm_set_r: need a %d x %d matrix, got %r" % (self.G, self.G, r.shape))
+        self._chk(self.lib.fmx_fwfm_set_r(self.h, _ptr(r)))
+
+    def fwfm_get_r(self):
+        """(r, n_r), both [F][F]"""
+        r, nr = np.zeros((self.G, self.G), dtype=np.float64), np.zeros((self.G, self.G), dtype=np.float64)
+        self._chk(self.lib.fmx_fwfm_get_r(self.h, _ptr(r), _ptr(nr)))
+        return r, nr
+
+    def fwfm_predict(self, slot, n_rows):
+        out = np.zeros(n_rows, dtype=np.float64)
+        self._chk(self.lib.fmx_fwfm_predict(self.h, slot, _ptr(out)))
+        return out
+
+    def fwfm_evaluate(self, slot):
+        ev = Eval()
+        self._chk(self.lib.fmx_fwfm_evaluate(self.h, slot, C.byref(ev)))
+        return ev
+
+    def fwfm_epoch(self, slot, batch=0, w0_chunk=0):
+        st = EpochStats()
+        self._chk(self.lib.fmx_fwfm_epoch(self.h, int(slot), int(batch), int(w0_chunk), C.byref(st)))
+        return st
+
+    def fwfm_end(self):
+        self._chk(self.lib.fmx_fwfm_end(self.h))
 
     # FTRL-proximal with L1 on the minibatch rule (include/fmx.h "fmx_ftrl_*") -------------------
     def ftrl_begin(self, alpha=0.0, beta=1.0, l1_w=0.0, l1_v=0.0, l2_w=0.0, l2_v=0.0, init_acc=0.0):

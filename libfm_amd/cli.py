@@ -76,6 +76,10 @@ ordinal ("0,0" = two shards on device 0) and the epochs run over the shards (fmx
 learner.FMLearnSGD.devices); the printed lines are those of one device.  Any other method or optimizer refuses the flag, and so do
 -serve, -topk, -save_checkpoint, -load_checkpoint, -save_snapshot, -load_snapshot and -train_weights, which have no sharded form.
 Without the flag nothing changes.
+-model fwfm -meta F [-r_out FILE] (-method sgd -optimizer adagrad): the field-weighted FM (fmx_fwfm_*, learner.FMLearnSGD.model): one
+learned interaction strength per pair of the fields -meta names; the printed lines, -out and -save_model are as before, under the
+learned matrix, which -r_out writes as text, one row per line.  Any other method or optimizer, a missing -meta, -devices, -relation,
+-serve, -topk, -metrics, -train_weights and the checkpoint flags are refused before any device is touched.  Without -model nothing changes.
 """
 import os
 import sys
@@ -134,7 +138,9 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "serve_prune": "dead | seen (with -serve): keep only the rows that can score -- dead: drop features that contribute to no prediction; seen: also those no -train row names",
          "save_snapshot": "with -serve: filename for the snapshot file of the frozen copy, written after it is taken",
          "load_snapshot": "-method serve: filename of the snapshot file to score from (no model is created; -train and -dim are not needed)",
-         "devices": "'D0,D1,...': -method sgd with -optimizer adagrad | ftrl over one feature shard per listed device ordinal ('0,0': two shards on device 0)"}
+         "devices": "'D0,D1,...': -method sgd with -optimizer adagrad | ftrl over one feature shard per listed device ordinal ('0,0': two shards on device 0)",
+         "model": "fm | fwfm: fwfm (-method sgd -optimizer adagrad -meta F) learns one interaction strength per pair of the fields -meta names; default=fm",
+         "r_out": "-model fwfm: filename for the learned field matrix as text, one row per line"}
 
 
 def checkpoint_line(what, info):
@@ -440,6 +446,24 @@ def _main(argv):
             devices = []
         if not devices or any(d < 0 for d in devices) or len(devices) > 16:
             raise ValueError("-devices needs 1 .. 16 device ordinals >= 0: 'D0,D1,...'")
+    model = a.get("model", "fm")
+    if "model" in a or "r_out" in a:
+        if model not in L.FMLearnSGD.MODELS:
+            raise ValueError("-model knows fm and fwfm, not '%s'" % model)
+        if model != "fwfm":
+            if "r_out" in a:
+                raise ValueError("-r_out belongs to -model fwfm")
+        else:
+            if method != "sgd" or optimizer != "adagrad":
+                raise ValueError("-model fwfm belongs to -method sgd with -optimizer adagrad, not -method %s%s"
+                                 % (method, " -optimizer " + optimizer if method in ("sgd", "bpr") else ""))
+            if not a.get("meta"):
+                raise ValueError("-model fwfm needs -meta: the fields are its groups")
+            for f in ("devices", "relation", "serve", "topk", "metrics", "train_weights", "save_checkpoint", "load_checkpoint"):
+                if f in a:
+                    raise ValueError("-%s is not supported with -model fwfm" % f)
+            if "r_out" in a and not a["r_out"]:
+                raise ValueError("-r_out needs a filename")
     serve = a.get("serve")
     if "serve" in a:
         if serve not in C.FORMATS:
@@ -664,6 +688,8 @@ def _main(argv):
             if optimizer == "ftrl":
                 l.ftrl_alpha, l.ftrl_beta = float(a.get("ftrl_alpha", "0")), float(a.get("ftrl_beta", "1"))
                 l.l1_w, l.l1_v = ftrl_l1
+        if model == "fwfm":
+            l.model, l.groups = "fwfm", groups
     else:
         if method == "als":
             l = L.FMLearnALS()
@@ -732,6 +758,9 @@ def _main(argv):
         print("Final\tTrain=%g\tTest=%g" % (l.evaluate_pairs(train), l.evaluate_pairs(test)))
     if method in ("sgd", "sgda"):
         print("Final\tTrain=%g\tTest=%g" % (l.evaluate(train), l.evaluate(test)))   # libfm.cpp:418-420
+    if "r_out" in a:
+        with open(a["r_out"], "w") as f:
+            f.write("".join(" ".join("%g" % x for x in row) + "\n" for row in l.r))
     if optimizer == "ftrl":
         sp = l.sparsity()
         print("sparsity\tfeatures=%d\tw_zero=%d\tv_coords=%d\tv_zero=%d\tv_zero_rows=%d\tdead_features=%d" %

@@ -25,8 +25,19 @@
 
 namespace fmx {
 
-template <class R, int KP, int U>
-__device__ __forceinline__ void stateful_seg_block(const SegWork& sw, uint32_t blk, const Tab tb, const R& rule, const Hyper& h) {
+// Where an occurrence's sum row comes from is the block's SUM SOURCE.  PlainSums, the default: row e of the batch's [nb][KP] factor
+// sums, and the feature's own term is v A.  A source that is not PLAIN (the field-weighted FM, fmx_fwfm_kernels.h) supplies
+//     base<KP>(S, j)   where example 0's row for feature j stands,     stride()  how far apart the examples' rows lie,
+//     self(j)          the factor of the feature's own term: g_vf = sum_occ mult_e x row_ef - self(j) v_jf sum_occ mult_e x x.
+struct PlainSums {
+  static constexpr bool PLAIN = true;
+  template <int KP> __device__ __forceinline__ const float* base(const float* S, uint32_t) const { return S; }
+  __device__ __forceinline__ RowStrideKP stride() const { return RowStrideKP(); }
+};
+
+template <class R, int KP, int U, class Sum = PlainSums>
+__device__ __forceinline__ void stateful_seg_block(const SegWork& sw, uint32_t blk, const Tab tb, const R& rule, const Hyper& h,
+                                                   const Sum sum = Sum()) {
   constexpr int VEC = Map<KP>::VEC, LPR = Map<KP>::LPR, EPI = Map<KP>::EPI, NT = R::NT;
   const uint32_t lane = threadIdx.x & 63u, g = lane / LPR, f = lane % LPR;
   const TEntry* __restrict__ t_ent = sw.t_ent;
@@ -63,7 +74,7 @@ __device__ __forceinline__ void stateful_seg_block(const SegWork& sw, uint32_t b
         row_ld<VEC, 8>(tb, (size_t)j, f * VEC, v0[u]);
 #pragma unroll
         for (int t = 0; t < NT; t++) row_ld<VEC, 8>(rule.st[t], (size_t)j, f * VEC, s0[u][t]);
-        load_vec<VEC>(S + (size_t)e * KP + f * VEC, sf[u]);
+        load_vec<VEC>(sum.template base<KP>(S, j) + (size_t)e * sum.stride().template of<KP>() + f * VEC, sf[u]);
       }
     }
 #pragma unroll
@@ -80,7 +91,8 @@ __device__ __forceinline__ void stateful_seg_block(const SegWork& sw, uint32_t b
 #pragma unroll
         for (int v = 0; v < VEC; v++) G[v] = mx * sf[u][v];
         A = mx * x; Gw = mx;
-        seg_tail<KP>(t_ent, S, mult, a + 1, b, lane, f, G, A, Gw);
+        seg_tail<KP>(t_ent, sum.template base<KP>(S, j), mult, a + 1, b, lane, f, G, A, Gw, TEntry{0u, 0.f}, 0.f, sum.stride());
+        if constexpr (!Sum::PLAIN) A *= sum.self(j);
         const float nocc = (float)(b - a);
         float nv[VEC];
 #pragma unroll

@@ -308,10 +308,10 @@ int launch_rest(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, float* r
   return FMX_OK;
 }
 
-int slot_scores(fmx_handle h, const Slot& s, const CompactState* snap, bool want_yhat, const float** score) {
+int slot_scores(fmx_handle h, const Slot& s, const CompactState* snap, bool want_yhat, const float** score, RestFn rest_fn) {
   int rc = ensure_scratch(h, 0, (size_t)s.n_rows * 2); if (rc) return rc;
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  rc = launch_rest(h, s, 0, s.n_rows, h->rest, h->stream, snap); if (rc) return rc;
+  rc = rest_fn ? rest_fn(h, s, h->rest, h->stream) : launch_rest(h, s, 0, s.n_rows, h->rest, h->stream, snap); if (rc) return rc;
   *score = h->rest;
   if (!want_yhat) return FMX_OK;
   float* yhat = h->rest + s.n_rows;
@@ -323,10 +323,10 @@ int slot_scores(fmx_handle h, const Slot& s, const CompactState* snap, bool want
   return FMX_OK;
 }
 
-int predict_out(fmx_handle h, const Slot& s, const CompactState* snap, double* out) {
+int predict_out(fmx_handle h, const Slot& s, const CompactState* snap, double* out, RestFn rest_fn) {
   if (s.n_rows == 0) return FMX_OK;
   const float* yhat;
-  const int rc = slot_scores(h, s, snap, true, &yhat); if (rc) return rc;
+  const int rc = slot_scores(h, s, snap, true, &yhat, rest_fn); if (rc) return rc;
   std::vector<float> tmp(s.n_rows);
   HIPCHK(h, hipMemcpyAsync(tmp.data(), yhat, (size_t)s.n_rows * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -334,9 +334,9 @@ int predict_out(fmx_handle h, const Slot& s, const CompactState* snap, double* o
   return FMX_OK;
 }
 
-int evaluate_out(fmx_handle h, const Slot& s, const CompactState* snap, fmx_eval* out) {
+int evaluate_out(fmx_handle h, const Slot& s, const CompactState* snap, fmx_eval* out, RestFn rest_fn) {
   const float* rest;
-  const int rc = slot_scores(h, s, snap, false, &rest); if (rc) return rc;
+  const int rc = slot_scores(h, s, snap, false, &rest, rest_fn); if (rc) return rc;
   HIPCHK(h, hipMemsetAsync(h->acc, 0, 4 * sizeof(double), h->stream));
   hipLaunchKernelGGL(k_eval, dim3(std::min<uint32_t>((s.n_rows + 255) / 256, 2048)), dim3(256), 0, h->stream,
                      rest, s.target, s.n_rows, make_hyper(h->cfg), snap ? snap->w0 : h->w0, h->acc);
@@ -539,6 +539,7 @@ int fmx_destroy(fmx_handle h) {
   sgda_free(h);
   adapt_free(h);
   ftrl_free(h);
+  fwfm_free(h);
   compact_free(h);
   for (auto& s : h->slots) free_slot(s);
   if (h->grp) fmx_dev_free(h->grp);

@@ -1,5 +1,5 @@
 // fmx_internal.h -- shared by the translation units of libfmx.so (fmx_core.hip, fmx_sgd.hip, fmx_als.hip, fmx_comm.hip, fmx_pair.hip, fmx_topk.hip,
-// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip, fmx_weighted.hip, fmx_ckpt.hip, fmx_snap.hip; fmx_io.hip needs
+// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip, fmx_weighted.hip, fmx_ckpt.hip, fmx_snap.hip, fmx_fwfm.hip; fmx_io.hip needs
 // none of it).
 // The C-ABI is include/fmx.h; nothing declared here is exported.
 #pragma once
@@ -179,6 +179,10 @@ struct FtrlState { float* zw = nullptr; float* zv = nullptr; float* nw = nullptr
                    float inv_alpha = 0.f, beta = 0.f, l1_w = 0.f, l1_v = 0.f, l2_w = 0.f, l2_v = 0.f, init_acc = 0.f;
                    // the start denominator D0 of a coordinate with this l2, as fmx_ftrl_begin computes it (base + l2, all fp32)
                    float start_D(float l2) const { const float base = (beta + sqrtf(init_acc)) * inv_alpha; return base + l2; } };
+// an open fmx_fwfm_* session (fmx_fwfm.hip): the field matrix r and its AdaGrad accumulators in fp64 ([F][F]), the zero-padded fp32
+// copy the kernels read ([FP][FP], FP = F rounded up to 16), and the scratch of an epoch's largest batch (T, S, D, the r partials)
+struct FwfmState { bool open = false; uint32_t F = 0, FP = 0; double* r = nullptr; double* nr = nullptr; float* R32 = nullptr;
+                   double eta_r = 0.0, init_acc = 1.0, reg_r = 0.0; float* scratch = nullptr; size_t scratch_rows = 0; };
 // the serving snapshot (fmx_compact_*, fmx_compact.hip): a frozen copy of w0 and, by format,
 //   FMX_COMPACT_BF16  w (fp32, stride 1) and V as bf16 rows of tb.rs elements
 //   FMX_COMPACT_INT8  B: one block of P bytes per feature with its scale, its w and its int8 codes (V and w stay null)
@@ -196,6 +200,7 @@ struct fmx_context_s {
   SgdaState  sgda;
   AdaptState adapt;
   FtrlState  ftrl;
+  FwfmState  fwfm;
   CompactState compact;
   LagState   lag;
   int        KP = 1;
@@ -298,11 +303,13 @@ int launch_rest(fmx_handle h, const Slot& s, uint64_t row0, uint32_t n, float* r
 // the scores of all n_rows >= 1 rows of a slot, on h->stream and in h->rest: ensure_scratch, h->ev0 (where the call's device work begins),
 // the rest pass, and *score = rest (y-hat minus the bias: the reductions add it, add_w0 = 1) or, with want_yhat, the finished y-hat
 // (the source's own bias; on a feature shard rank 0 alone adds it)
-int slot_scores(fmx_handle h, const Slot& s, const CompactState* snap, bool want_yhat, const float** score);
+// rest_fn (fmx_fwfm.hip): the caller's own rest pass (s, rest, stream) in place of launch_rest -- another model over the same tables
+typedef int (*RestFn)(fmx_handle h, const Slot& s, float* rest, hipStream_t st);
+int slot_scores(fmx_handle h, const Slot& s, const CompactState* snap, bool want_yhat, const float** score, RestFn rest_fn = nullptr);
 // fmx_predict / fmx_evaluate after their checks, for the snapshot's entry points too: slot_scores, then the y-hat to the host /
 // k_eval with the source's bias to rmse, mae, accuracy and device_seconds (n_rows >= 1; predict_out takes an empty slot too)
-int predict_out(fmx_handle h, const Slot& s, const CompactState* snap, double* out);
-int evaluate_out(fmx_handle h, const Slot& s, const CompactState* snap, fmx_eval* out);
+int predict_out(fmx_handle h, const Slot& s, const CompactState* snap, double* out, RestFn rest_fn = nullptr);
+int evaluate_out(fmx_handle h, const Slot& s, const CompactState* snap, fmx_eval* out, RestFn rest_fn = nullptr);
 inline RowsBf16 compact_rows(fmx_handle h, const CompactState& c) { return RowsBf16{CTab{c.V, c.w, h->tb.rs}}; }
 inline RowsI8 compact_rows8(const CompactState& c) { return RowsI8{c.B, c.P}; }
 inline RowsBf16P compact_rows_p(fmx_handle h, const CompactState& c) { return RowsBf16P{compact_rows(h, c), c.dir}; }
@@ -423,6 +430,18 @@ int param_sparsity_impl(fmx_handle h, bool in_group, fmx_sparsity* out);
 enum StatefulRule { STATEFUL_ADAGRAD = 1, STATEFUL_FTRL = 2 };
 int stateful_shard_prepare(fmx_handle h, int slot, uint32_t B);
 int stateful_shard_step(fmx_handle h, int slot, StatefulRule rule, uint64_t row0, uint32_t nb, uint32_t B, uint32_t chunk, const float* d_sum);
+// fmx_sgd.hip, for fmx_fwfm_epoch (fmx_fwfm.hip): stateful_epoch with the caller's own batch steps.  rows(s, row0, nb, rest, st) leaves
+// rest[] of the batch (in place of k_rowsums); owner(sw, hy, st) is the owner kernel over the batch's segments; after(nb, st) runs
+// behind it on every batch, whether or not the batch has segments.  Three plain functions and the caller's own state (ctx), called in
+// that order for every batch on the epoch's stream.  The caller has made every check of its entry point.
+struct StatefulSteps {
+  void* ctx;
+  int (*rows)(void* ctx, const Slot& s, uint64_t row0, uint32_t nb, float* rest, hipStream_t st);
+  int (*owner)(void* ctx, const SegWork& sw, const Hyper& hy, hipStream_t st);
+  int (*after)(void* ctx, uint32_t nb, hipStream_t st);
+};
+int stateful_epoch_steps(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats, const StatefulSteps& steps);
+void fwfm_free(fmx_handle h);                                            // fmx_fwfm.hip
 void als_free(fmx_handle h);                                             // fmx_als.hip
 enum { GROUP_SINGLE = 0, GROUP_LOOPBACK = 1, GROUP_RCCL = 2 };
 struct fmx_group_s {                      // fmx_comm.hip

@@ -1749,10 +1749,14 @@ struct SegWork {
 // in occurrence order -- the order that makes two runs, and the device and its restatements, agree bit for bit.
 // PRE: the caller has already asked for the first 64 descriptors and their multipliers (te_pre, tm_pre: lane-parallel from i2; the
 // one-segment-per-wavefront path of apply_seg_block), so the first wave-wide load is not issued again.
-template <int KP, bool PRE = false>
+// RS: how far apart the sum rows of consecutive examples lie -- RowStrideKP, the batch's [nb][KP] factor sums, or a runtime stride (the
+// field-weighted FM's T rows, fmx_fwfm_kernels.h).
+struct RowStrideKP { template <int KP> __device__ __forceinline__ constexpr size_t of() const { return (size_t)KP; } };
+template <int KP, bool PRE = false, class RS = RowStrideKP>
 __device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const float* __restrict__ S, const float* __restrict__ mult,
                                          uint32_t i2, const uint32_t b, const uint32_t lane, const uint32_t f,
-                                         float (&G)[Map<KP>::VEC], float& A, float& Gw, const TEntry te_pre = TEntry{0u, 0.f}, const float tm_pre = 0.f) {
+                                         float (&G)[Map<KP>::VEC], float& A, float& Gw, const TEntry te_pre = TEntry{0u, 0.f}, const float tm_pre = 0.f,
+                                         const RS rs = RS()) {
   constexpr int VEC = Map<KP>::VEC, EPI = Map<KP>::EPI;
   // further occurrences of the feature in this batch (a frequent feature of Criteo-shaped rows has dozens to thousands per
   // batch).  Added in occurrence order, so the result does not depend on how they are fetched:
@@ -1773,7 +1777,7 @@ __device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const
 #pragma unroll
         for (int q = 0; q < TL; q++) {
           const uint32_t e2 = bcast_u32<1>(te.e, (q0 + q) & 63u);
-          if (q0 + q < cc) load_vec<VEC>(S + (size_t)e2 * KP + f * VEC, s2[q]);
+          if (q0 + q < cc) load_vec<VEC>(S + (size_t)e2 * rs.template of<KP>() + f * VEC, s2[q]);
           else {
 #pragma unroll
             for (int v = 0; v < VEC; v++) s2[q][v] = 0.f;
@@ -1801,7 +1805,7 @@ __device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const
 #pragma unroll
       for (int q = 0; q < TL; q++) {
         mm[q] = 0.f;
-        if (i2 + q < b) { mm[q] = mult[tt[q].e]; load_vec<VEC>(S + (size_t)tt[q].e * KP + f * VEC, s2[q]); }
+        if (i2 + q < b) { mm[q] = mult[tt[q].e]; load_vec<VEC>(S + (size_t)tt[q].e * rs.template of<KP>() + f * VEC, s2[q]); }
         else {
 #pragma unroll
           for (int v = 0; v < VEC; v++) s2[q][v] = 0.f;

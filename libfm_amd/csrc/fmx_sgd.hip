@@ -1701,8 +1701,19 @@ static int stateful_batch_tail(fmx_handle h, const Slot& s, uint64_t row0, uint3
   return FMX_OK;
 }
 
-template <class Owner>
-static int stateful_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats, Owner launch_owner) {
+// the batch's first step as stateful_epoch takes it unless told otherwise: k_rowsums leaves S and rest[]
+struct RowsumsStep {
+  fmx_handle h;
+  int operator()(const Slot& s, uint64_t row0, uint32_t nb, float* S, float* rest, hipStream_t st) const {
+    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, st, s.ent, s.row_ptr, row0, nb, RowsF32{h->tb}, h->cfg.k1, S, rest));
+    return FMX_OK;
+  }
+};
+struct NoAfterStep { int operator()(uint32_t, hipStream_t) const { return FMX_OK; } };
+
+template <class Owner, class Rows, class After>
+static int stateful_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats, Owner launch_owner,
+                          Rows launch_rows, After after_batch) {
   { int _rc = lag_flush(h); if (_rc) return _rc; }
   HIPCHK(h, hipSetDevice(h->device));
   Slot& s = h->slots[slot];
@@ -1729,8 +1740,9 @@ static int stateful_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_ch
     const uint32_t nb = (uint32_t)std::min<uint64_t>(B, s.n_rows - row0);
     float* S = h->partial;
     float* rest = S + (size_t)nb * h->KP;
-    KP_SWITCH(h->KP, FMX_LAUNCH_WAVES((k_rowsums<KP, true, true>), nb, st, s.ent, s.row_ptr, row0, nb, RowsF32{h->tb}, h->cfg.k1, S, rest));
+    rc = launch_rows(s, row0, nb, S, rest, st); if (rc) return rc;
     rc = stateful_batch_tail(h, s, row0, nb, B, chunk, hy, S, rest, st, launch_owner); if (rc) return rc;
+    rc = after_batch(nb, st); if (rc) return rc;
     batches++;
   }
   HIPCHK(h, hipEventRecord(h->ev1, st));
@@ -1748,6 +1760,17 @@ static int stateful_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_ch
     stats->setup_seconds = h->setup_acc;
   }
   return FMX_OK;
+}
+template <class Owner>
+static int stateful_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats, Owner launch_owner) {
+  return stateful_epoch(h, slot, batch, w0_chunk, stats, launch_owner, RowsumsStep{h}, NoAfterStep{});
+}
+int stateful_epoch_steps(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats* stats, const StatefulSteps& steps) {
+  const StatefulSteps k = steps;
+  return stateful_epoch(h, slot, batch, w0_chunk, stats,
+                        [k](const SegWork& sw, const Hyper& hy, hipStream_t st) { return k.owner(k.ctx, sw, hy, st); },
+                        [k](const Slot& s, uint64_t row0, uint32_t nb, float*, float* rest, hipStream_t st) { return k.rows(k.ctx, s, row0, nb, rest, st); },
+                        [k](uint32_t nb, hipStream_t st) { return k.after(k.ctx, nb, st); });
 }
 }  // extern "C++"
 

@@ -307,9 +307,15 @@ class FMLearnSGD:
     row weights: each raises NotImplementedError before any device is touched.  Checkpoints of a sharded model exist one layer down:
     capi.Group.checkpoint_save / checkpoint_load (fmx_group_checkpoint_*) write and read the unsharded handle's file in global
     feature order, so the route from shards to this learner is the file itself -- load_checkpoint of an unsharded FMLearnSGD
-    continues from a file a group wrote."""
+    continues from a file a group wrote.
+    model ('fm' | 'fwfm'): 'fwfm' is the field-weighted FM (fmx_fwfm_*): `groups` (attribute -> field, the `-meta` map) is required
+    and so is optimizer 'adagrad'; learn, evaluate, predict_raw and predict then run under the learned field matrix, which `.r`
+    returns ([F][F]); fwfm_learn_rate (0 = the AdaGrad eta), fwfm_init_acc (0 = 1.0) and fwfm_reg are the matrix's own step
+    constants.  Everything else that scores -- evaluate_ex, extra_metrics, the by-query and rank metrics, recommend, compact -- and
+    row weights, checkpoints and feature shards have no form under it and raise before any device is touched."""
 
     OPTIMIZERS = ("sgd", "adagrad", "ftrl")
+    MODELS = ("fm", "fwfm")
     SHARDED_OPTIMIZERS = ("adagrad", "ftrl")                    # what `devices` with more than one entry is honoured for
     MODES = {"sequential": capi.SGD_SEQUENTIAL, "minibatch": capi.SGD_MINIBATCH, "hogwild": capi.SGD_HOGWILD}
     APPLY = {"default": capi.APPLY_DEFAULT, "atomic": capi.APPLY_ATOMIC, "store": capi.APPLY_STORE,
@@ -329,6 +335,9 @@ class FMLearnSGD:
         self.bias_lag = 2
         self.reject_unstable = True                             # an explicit batch the rule diverges at raises instead of training
         self.optimizer = "sgd"
+        self.model = "fm"
+        self.groups = None                                      # model 'fwfm': attribute -> field
+        self.fwfm_learn_rate, self.fwfm_init_acc, self.fwfm_reg = 0.0, 0.0, 0.0
         self.init_acc = 0.0
         self.adapt_learn_rate = 0.0
         self.ftrl_alpha = 0.0
@@ -348,9 +357,39 @@ class FMLearnSGD:
         self.rank_cutoffs = ()                                  # with query ids: ndcg / recall / precision at these K per iteration
         self._adapt_open = False
         self._ftrl_open = False
+        self._fwfm_open = False
         self._checkpoint = None                                 # load_checkpoint before init(): the file init() starts from
 
+    def _check_model(self):
+        if self.model not in self.MODELS:
+            raise ValueError("unknown model for %s: %s (%s)" % (type(self).__name__, self.model, " | ".join(self.MODELS)))
+        if self.model != "fwfm":
+            return
+        if type(self) is not FMLearnSGD:
+            raise NotImplementedError("%s has no field-weighted form: model fwfm belongs to FMLearnSGD" % type(self).__name__)
+        if self.optimizer != "adagrad":
+            raise ValueError("model fwfm trains with optimizer adagrad, not %s" % self.optimizer)
+        if self.groups is None:
+            raise ValueError("model fwfm needs groups: the attribute -> field map")
+        self._not_on_shards("model fwfm")
+        for what, on in (("load_checkpoint", self._checkpoint is not None), ("set_weights", bool(self._weights)),
+                         ("extra_metrics", bool(self.extra_metrics)), ("set_queries", bool(self._queries))):
+            if on:
+                raise NotImplementedError("%s is not supported with model fwfm" % what)
+
+    def _not_under_fwfm(self, what):
+        if self.model == "fwfm":
+            raise NotImplementedError("%s is not supported with model fwfm: it scores the plain FM" % what)
+
+    @property
+    def r(self):
+        """model 'fwfm': the learned field matrix [F][F] as the device holds it"""
+        if not self._fwfm_open:
+            raise ValueError("r: model fwfm after init() only")
+        return self._h.fwfm_get_r()[0]
+
     def _check_optimizer(self):
+        self._check_model()
         if self.optimizer not in self.OPTIMIZERS:
             raise ValueError("unknown optimizer for %s: %s (%s)" % (type(self).__name__, self.optimizer, " | ".join(self.OPTIMIZERS)))
         if self.optimizer == "adagrad" and self.mode != "minibatch":
@@ -418,12 +457,17 @@ class FMLearnSGD:
             self._h.ftrl_begin(self.ftrl_alpha, self.ftrl_beta, self.l1_w, self.l1_v, fm.regw if self.l2_w is None else self.l2_w,
                                fm.regv if self.l2_v is None else self.l2_v, self.init_acc)
             self._ftrl_open = True
+        if self.model == "fwfm" and not self._fwfm_open:
+            self._h.set_groups(self.groups)
+            self._h.fwfm_begin(self.fwfm_learn_rate, self.fwfm_init_acc, self.fwfm_reg)
+            self._fwfm_open = True
 
     def save_checkpoint(self, path, dense=False):
         """the exact binary checkpoint of the model on the device and of the open adagrad / ftrl session (fmx_checkpoint_save;
         libfm_amd/checkpoint.py reads the file).  dense: every feature's state rows, not only those that differ from the start
         state.  Returns capi.CkptInfo."""
         self._not_on_shards("save_checkpoint")
+        self._not_under_fwfm("save_checkpoint")
         if self._h is None:
             raise ValueError("save_checkpoint before init()")
         return self._h.checkpoint_save(path, dense=dense)
@@ -537,6 +581,8 @@ class FMLearnSGD:
         self._check_devices()
         if (self.optimizer == "adagrad") != self._adapt_open or (self.optimizer == "ftrl") != self._ftrl_open:
             raise ValueError("optimizer was changed after init()")
+        if (self.model == "fwfm") != self._fwfm_open:
+            raise ValueError("model was changed after init()")
         if id(train) in self._weights and self.optimizer == "sgd":
             raise ValueError("the train set has weights (set_weights): optimizer sgd has no weighted form, use adagrad or ftrl")
         print("learnrate=%g" % self.learn_rate, file=self.out)   # fm_learn_sgd.h:57-59
@@ -550,7 +596,9 @@ class FMLearnSGD:
                 apply_ = capi.APPLY_DEFAULT
             flags = capi.FLAG_REJECT_UNSTABLE if (self.reject_unstable and self.mode == "minibatch") else 0
             flags |= capi.FLAG_KEEP_WSIDE                # the train set is evaluated after every epoch (fm_learn_sgd_element.h:69-70)
-            if self._adapt_open:
+            if self._fwfm_open:
+                stats = self._h.fwfm_epoch(st, self.batch, self.w0_chunk)
+            elif self._adapt_open:
                 stats = self._h.adapt_epoch(st, self.batch, self.w0_chunk)
             elif self._ftrl_open:
                 stats = self._h.ftrl_epoch(st, self.batch, self.w0_chunk)
@@ -574,17 +622,20 @@ class FMLearnSGD:
 
     # fm_learn::evaluate (fm_learn.h:93-153): rmse for regression, accuracy for classification
     def evaluate(self, data):
-        ev = self._h.evaluate(self._slot(data))
+        ev = self._h.fwfm_evaluate(self._slot(data)) if self._fwfm_open else self._h.evaluate(self._slot(data))
         return ev.rmse if self.task == TASK_REGRESSION else ev.accuracy
 
     EVAL_LINK = capi.LINK_LOGISTIC       # fm_learn_sgd::predict maps a classification score through the sigmoid (fm_learn_sgd.h:80-87)
 
     def evaluate_ex(self, data):
         """exact AUC, log loss and the counts behind them under the current parameters, reduced on the device (fmx_evaluate_ex)"""
+        self._not_under_fwfm("evaluate_ex")
         return self._h.evaluate_ex(self._slot(data), self.EVAL_LINK)
 
     def predict_raw(self, data):
         """fm_learn::predict_case over the data set (fm_learn.h:63-65)."""
+        if self._fwfm_open:
+            return self._h.fwfm_predict(self._slot(data), data.num_cases)
         return self._h.predict(self._slot(data), data.num_cases)
 
     def recommend(self, queries, candidates, topk, exclude=None):
@@ -593,6 +644,7 @@ class FMLearnSGD:
         [queries, topk], score float64 [queries, topk]), padded with (capi.TOPK_NONE, -inf).  exclude: per query, the candidate
         rows it must not get back (a list of iterables, or a CSR (ptr, idx))."""
         self._not_on_shards("recommend: top-K retrieval")
+        self._not_under_fwfm("recommend")
         return self._h.topk(*self._topk_slots(queries, candidates), topk, 0, queries.num_cases, exclude)
 
     def _topk_slots(self, queries, candidates):
@@ -611,6 +663,7 @@ class FMLearnSGD:
         """a CompactView: a frozen reduced-precision copy of the model as it stands, to score from (fmx_compact_begin); with
         prune = "dead" | "seen" one that keeps only the rows that can score (fmx_compact_begin_pruned).  Not on feature shards."""
         self._not_on_shards("compact: the serving snapshot")
+        self._not_under_fwfm("compact")
         return CompactView(self, format, prune)
 
     # fm_learn_sgd::predict (fm_learn_sgd.h:76-90)
@@ -629,6 +682,9 @@ class FMLearnSGD:
 
     def close(self):
         if self._h is not None:
+            if self._fwfm_open:
+                self._h.fwfm_end()
+                self._fwfm_open = False
             if self._adapt_open:
                 self._h.adapt_end()
                 self._adapt_open = False
