@@ -1602,6 +1602,47 @@ int fmx_fwfm_evaluate(fmx_handle h, int slot, fmx_eval *out);
 int fmx_fwfm_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
 int fmx_fwfm_end(fmx_handle h);
 
+/* ---- the field-aware FM (FFM, Juan et al., RecSys 2016) ---------------------------------------------------
+ *   y(x) = w0 + sum_j w_j x_j + sum_{a<b} < v_ja[g(jb)], v_jb[g(ja)] > x_a x_b        (a, b: the row's entries, in row order)
+ * g() is the feature -> field map of fmx_set_groups (none: one field), F = num_groups.  A feature keeps one vector of num_latent
+ * factors per field: its row of the handle's V, created with num_factor = F * num_latent, holds them side by side -- column
+ * h * num_latent + f is factor f of the vector used against field h.  The session owns NO parameters: w, V and the accumulators of the
+ * open fmx_adapt session stay the handle's tables, so fmx_get_params / fmx_set_params, checkpoints and fmx_save_model see them as they
+ * are; fmx_predict, fmx_evaluate and every other existing call keep scoring the plain FM of width num_factor.  With F = 1 the model
+ * IS the plain FM.  An id repeated inside a row counts as separate entries.
+ * Added without an ABI version change: a caller detects the feature by the symbol fmx_ffm_begin.
+ *
+ * With the field tile Q[h][:] = sum_{b: g(jb) = h} x_b V[jb][:] of a row (Q[h][g]: block g of row h) and D = sum_b x_b^2 |v_jb[g(jb)]|^2:
+ *   pair term = 1/2 sum_{g,h} <Q[h][g], Q[g][h]> - 1/2 D          d/dv_ja[h] = x_a (Q[h][g(ja)] - [h = g(ja)] x_a v_ja[g(ja)])
+ *
+ *   fmx_ffm_begin    : opens the session for num_latent factors per field; called again it starts over.
+ *   fmx_ffm_predict  : fmx_predict's contract under the field-aware model.
+ *   fmx_ffm_evaluate : fmx_evaluate's contract under the field-aware model.
+ *   fmx_ffm_epoch    : fmx_adapt_epoch's contract (batch, w0_chunk, stats, an empty slot) with the FFM's sums and gradients.  It needs
+ *                      an open fmx_adapt session and steps w and every column of V on THAT session's accumulators with its eta, from
+ *                      the batch-start parameters; the bias keeps its micro-chunk SGD.  There is no other state.  No float atomics
+ *                      anywhere: two runs give the same bits.  This is the library's minibatch rule, not libffm's online loop, and
+ *                      there is no instance normalisation.
+ *   fmx_ffm_end      : closes the session and frees its scratch.
+ * Limits (FMX_E_UNSUPPORTED beyond): at most 64 fields, num_factor = F * num_latent <= 1024, and a field tile that fits one
+ * workgroup's LDS: F * LD * 4 <= 160 KiB, LD = F * num_latent rounded up to a multiple of 4 plus less than 64 floats of padding
+ * (everything with F * F * num_latent * 4 <= 64 KiB fits).  Scratch of an epoch: batch * F * (num_factor rounded up to 16) * 4 bytes.
+ * Refusals, each before any launch, the handle usable afterwards.  FMX_E_ARG: NULL opts or out; flags != 0; num_factor !=
+ * num_groups * num_latent.  FMX_E_STATE: any call but _begin without a session; num_groups changed under the session; fmx_ffm_epoch
+ * without an fmx_adapt session; a slot never uploaded, or without targets for _epoch and _evaluate; an open SGDA or ALS / MCMC
+ * session; fmx_ffm_begin while an fmx_fwfm session is open, and fmx_fwfm_begin while this one is.  FMX_E_UNSUPPORTED: a feature shard
+ * or communicator rank; kept `-relation` blocks; a slot with row weights; the limits above.
+ * Not offered under it: FTRL, the pairwise epochs, fmx_evaluate_ex / _by_query / _rank, fmx_topk, snapshots, feature shards, row weights. */
+typedef struct fmx_ffm_opts {
+  uint32_t num_latent;     /* factors per (feature, field) vector; num_factor must be num_groups * num_latent */
+  uint32_t flags;          /* 0 */
+} fmx_ffm_opts;
+int fmx_ffm_begin(fmx_handle h, const fmx_ffm_opts *opts);
+int fmx_ffm_predict(fmx_handle h, int slot, double *out);
+int fmx_ffm_evaluate(fmx_handle h, int slot, fmx_eval *out);
+int fmx_ffm_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
+int fmx_ffm_end(fmx_handle h);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 typedef struct fmx_info {
   uint64_t n_local;         /* features held by this handle */

@@ -3,7 +3,7 @@
     python -m libfm_amd.build [--force]
 
 Eighteen translation units (csrc/fmx_core.hip, fmx_sgd.hip, fmx_als.hip, fmx_io.hip, fmx_comm.hip, fmx_pair.hip, fmx_topk.hip,
-fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip, fmx_weighted.hip, fmx_ckpt.hip, fmx_snap.hip, fmx_fwfm.hip) are compiled in parallel and linked.
+fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip, fmx_weighted.hip, fmx_ckpt.hip, fmx_snap.hip, fmx_fwfm.hip, fmx_ffm.hip) are compiled in parallel and linked.
 """
 import os
 import subprocess
@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-SRC = [os.path.join(CSRC, f) for f in ("fmx_core.hip", "fmx_sgd.hip", "fmx_als.hip", "fmx_io.hip", "fmx_comm.hip", "fmx_pair.hip", "fmx_topk.hip", "fmx_pairneg.hip", "fmx_eval.hip", "fmx_post.hip", "fmx_evalq.hip", "fmx_compact.hip", "fmx_rankq.hip", "fmx_mem.hip", "fmx_weighted.hip", "fmx_ckpt.hip", "fmx_snap.hip", "fmx_fwfm.hip")]
+SRC = [os.path.join(CSRC, f) for f in ("fmx_core.hip", "fmx_sgd.hip", "fmx_als.hip", "fmx_io.hip", "fmx_comm.hip", "fmx_pair.hip", "fmx_topk.hip", "fmx_pairneg.hip", "fmx_eval.hip", "fmx_post.hip", "fmx_evalq.hip", "fmx_compact.hip", "fmx_rankq.hip", "fmx_mem.hip", "fmx_weighted.hip", "fmx_ckpt.hip", "fmx_snap.hip", "fmx_fwfm.hip", "fmx_ffm.hip")]
 DEPS = SRC + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(ROOT, "include", "fmx.h")]   # every header under csrc/
 # experiments: FMX_DEFS="-DFMX_V_NT=1" FMX_OUT=libfmx_nt.so python -m libfm_amd.build --force ; run with FMX_LIB=<that file>
 EXTRA = os.environ.get("FMX_DEFS", "").split()
@@ -27,7 +27,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-
 # <128, 4, true> 156 against 260, scratch 0 either way.  It is an internal clang feature switch (the host pass
 # prints "not a recognized feature" for it): should a compiler drop it, removing the entry costs occupancy, not correctness.  The
 # unit's instance of stateful_seg_block (k_fwfm_apply_seg) is compiled this way too; fmx_sgd.hip's instances are not touched.
-FILE_FLAGS = {"fmx_fwfm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# fmx_ffm.hip is compiled the same way (its resource table is in DESIGN.md section 30).
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FILE_FLAGS = {"fmx_fwfm.hip": NO_PACKED_FP32, "fmx_ffm.hip": NO_PACKED_FP32}
 
 
 def needs_build():

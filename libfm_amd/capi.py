@@ -79,6 +79,10 @@ class AdaptOpts(C.Structure):
 FWFM_MAX_FIELDS, FWFM_MAX_FACTORS = 64, 128        # FMX_FWFM_MAX_FIELDS, FMX_FWFM_MAX_FACTORS
 
 
+class FfmOpts(C.Structure):                        # fmx_ffm_opts
+    _fields_ = [("num_latent", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class FwfmOpts(C.Structure):                       # fmx_fwfm_opts
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("learn_rate_r", C.c_double), ("init_acc_r", C.c_double),
                 ("reg_r", C.c_double)]
@@ -435,6 +439,11 @@ SYMBOLS = [
     ("fmx_fwfm_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
     ("fmx_fwfm_epoch", C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
     ("fmx_fwfm_end", C.c_int, [H]),
+    ("fmx_ffm_begin", C.c_int, [H, C.POINTER(FfmOpts)]),
+    ("fmx_ffm_predict", C.c_int, [H, C.c_int, C.c_void_p]),
+    ("fmx_ffm_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
+    ("fmx_ffm_epoch", C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
+    ("fmx_ffm_end", C.c_int, [H]),
     ("fmx_get_info", C.c_int, [H, C.POINTER(Info)]),
     ("fmx_synchronize", C.c_int, [H]),
 ]
@@ -1023,6 +1032,28 @@ class Handle:
 
     def fwfm_end(self):
         self._chk(self.lib.fmx_fwfm_end(self.h))
+
+    # the field-aware FM (include/fmx.h "fmx_ffm_*"): fields = the groups of set_groups, num_factor = fields x num_latent ------
+    def ffm_begin(self, num_latent):
+        self._chk(self.lib.fmx_ffm_begin(self.h, C.byref(FfmOpts(int(num_latent), 0))))
+
+    def ffm_predict(self, slot, n_rows):
+        out = np.zeros(n_rows, dtype=np.float64)
+        self._chk(self.lib.fmx_ffm_predict(self.h, slot, _ptr(out)))
+        return out
+
+    def ffm_evaluate(self, slot):
+        ev = Eval()
+        self._chk(self.lib.fmx_ffm_evaluate(self.h, slot, C.byref(ev)))
+        return ev
+
+    def ffm_epoch(self, slot, batch=0, w0_chunk=0):
+        st = EpochStats()
+        self._chk(self.lib.fmx_ffm_epoch(self.h, int(slot), int(batch), int(w0_chunk), C.byref(st)))
+        return st
+
+    def ffm_end(self):
+        self._chk(self.lib.fmx_ffm_end(self.h))
 
     # FTRL-proximal with L1 on the minibatch rule (include/fmx.h "fmx_ftrl_*") -------------------
     def ftrl_begin(self, alpha=0.0, beta=1.0, l1_w=0.0, l1_v=0.0, l2_w=0.0, l2_v=0.0, init_acc=0.0):

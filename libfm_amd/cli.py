@@ -80,6 +80,9 @@ Without the flag nothing changes.
 learned interaction strength per pair of the fields -meta names; the printed lines, -out and -save_model are as before, under the
 learned matrix, which -r_out writes as text, one row per line.  Any other method or optimizer, a missing -meta, -devices, -relation,
 -serve, -topk, -metrics, -train_weights and the checkpoint flags are refused before any device is touched.  Without -model nothing changes.
+-model ffm -meta F (-method sgd -optimizer adagrad): the field-aware FM (fmx_ffm_*): -dim 1,1,k gives every feature one vector of k
+factors per field, so -save_model / -load_model carry F k columns per feature (field-major).  The same flags are refused as with
+-model fwfm, in the same words, and so is -r_out.
 """
 import os
 import sys
@@ -139,7 +142,8 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "save_snapshot": "with -serve: filename for the snapshot file of the frozen copy, written after it is taken",
          "load_snapshot": "-method serve: filename of the snapshot file to score from (no model is created; -train and -dim are not needed)",
          "devices": "'D0,D1,...': -method sgd with -optimizer adagrad | ftrl over one feature shard per listed device ordinal ('0,0': two shards on device 0)",
-         "model": "fm | fwfm: fwfm (-method sgd -optimizer adagrad -meta F) learns one interaction strength per pair of the fields -meta names; default=fm",
+         "model": "fm | fwfm | ffm (-method sgd -optimizer adagrad -meta F): fwfm learns one interaction strength per pair of the fields -meta names, "
+                  "ffm one vector of -dim's k factors per feature and field; default=fm",
          "r_out": "-model fwfm: filename for the learned field matrix as text, one row per line"}
 
 
@@ -449,19 +453,18 @@ def _main(argv):
     model = a.get("model", "fm")
     if "model" in a or "r_out" in a:
         if model not in L.FMLearnSGD.MODELS:
-            raise ValueError("-model knows fm and fwfm, not '%s'" % model)
-        if model != "fwfm":
-            if "r_out" in a:
-                raise ValueError("-r_out belongs to -model fwfm")
-        else:
+            raise ValueError("-model knows fm, fwfm and ffm, not '%s'" % model)
+        if model != "fwfm" and "r_out" in a:
+            raise ValueError("-r_out belongs to -model fwfm")
+        if model != "fm":
             if method != "sgd" or optimizer != "adagrad":
-                raise ValueError("-model fwfm belongs to -method sgd with -optimizer adagrad, not -method %s%s"
-                                 % (method, " -optimizer " + optimizer if method in ("sgd", "bpr") else ""))
+                raise ValueError("-model %s belongs to -method sgd with -optimizer adagrad, not -method %s%s"
+                                 % (model, method, " -optimizer " + optimizer if method in ("sgd", "bpr") else ""))
             if not a.get("meta"):
-                raise ValueError("-model fwfm needs -meta: the fields are its groups")
+                raise ValueError("-model %s needs -meta: the fields are its groups" % model)
             for f in ("devices", "relation", "serve", "topk", "metrics", "train_weights", "save_checkpoint", "load_checkpoint"):
                 if f in a:
-                    raise ValueError("-%s is not supported with -model fwfm" % f)
+                    raise ValueError("-%s is not supported with -model %s" % (f, model))
             if "r_out" in a and not a["r_out"]:
                 raise ValueError("-r_out needs a filename")
     serve = a.get("serve")
@@ -607,7 +610,11 @@ def _main(argv):
     R.srand(seed)                                                                     # libfm.cpp:115-116
     fm.w0 = 0.0
     fm.w = np.zeros(fm.num_attribute)
-    fm.v = R.init_v(fm.num_factor, fm.num_attribute, fm.init_mean, fm.init_stdev)    # fm_model.h:96
+    v_rows = fm.num_factor
+    if model == "ffm":                                   # one vector of -dim's k per field: F k columns per feature (F: the -meta map's)
+        with open(a["meta"]) as f:
+            v_rows *= max([int(x) for x in f.read().split()[:fm.num_attribute]], default=0) + 1
+    fm.v = R.init_v(v_rows, fm.num_attribute, fm.init_mean, fm.init_stdev)           # fm_model.h:96
     if "load_model" in a:
         print("Reading FM model... \t")
         if not fm.load_model(a["load_model"]):
@@ -688,8 +695,8 @@ def _main(argv):
             if optimizer == "ftrl":
                 l.ftrl_alpha, l.ftrl_beta = float(a.get("ftrl_alpha", "0")), float(a.get("ftrl_beta", "1"))
                 l.l1_w, l.l1_v = ftrl_l1
-        if model == "fwfm":
-            l.model, l.groups = "fwfm", groups
+        if model != "fm":
+            l.model, l.groups = model, groups
     else:
         if method == "als":
             l = L.FMLearnALS()

@@ -29,8 +29,11 @@ namespace fmx {
 // sums, and the feature's own term is v A.  A source that is not PLAIN (the field-weighted FM, fmx_fwfm_kernels.h) supplies
 //     base<KP>(S, j)   where example 0's row for feature j stands,     stride()  how far apart the examples' rows lie,
 //     self(j)          the factor of the feature's own term: g_vf = sum_occ mult_e x row_ef - self(j) v_jf sum_occ mult_e x x.
+// A source with COLUMN_SELF (the field-aware FM, fmx_ffm_kernels.h) has an own term in the columns [own_begin(j), own_begin(j) +
+// own_width()) alone, with the factor 1, in place of self(j); and a stride() whose live(off) is not constantly true masks the loads of
+// a sum row to the lanes it covers (the others read zeros).
 struct PlainSums {
-  static constexpr bool PLAIN = true;
+  static constexpr bool PLAIN = true, COLUMN_SELF = false;
   template <int KP> __device__ __forceinline__ const float* base(const float* S, uint32_t) const { return S; }
   __device__ __forceinline__ RowStrideKP stride() const { return RowStrideKP(); }
 };
@@ -74,7 +77,11 @@ __device__ __forceinline__ void stateful_seg_block(const SegWork& sw, uint32_t b
         row_ld<VEC, 8>(tb, (size_t)j, f * VEC, v0[u]);
 #pragma unroll
         for (int t = 0; t < NT; t++) row_ld<VEC, 8>(rule.st[t], (size_t)j, f * VEC, s0[u][t]);
-        load_vec<VEC>(sum.template base<KP>(S, j) + (size_t)e * sum.stride().template of<KP>() + f * VEC, sf[u]);
+        if (sum.stride().live(f * VEC)) load_vec<VEC>(sum.template base<KP>(S, j) + (size_t)e * sum.stride().template of<KP>() + f * VEC, sf[u]);
+        else {
+#pragma unroll
+          for (int v = 0; v < VEC; v++) sf[u][v] = 0.f;
+        }
       }
     }
 #pragma unroll
@@ -92,15 +99,19 @@ __device__ __forceinline__ void stateful_seg_block(const SegWork& sw, uint32_t b
         for (int v = 0; v < VEC; v++) G[v] = mx * sf[u][v];
         A = mx * x; Gw = mx;
         seg_tail<KP>(t_ent, sum.template base<KP>(S, j), mult, a + 1, b, lane, f, G, A, Gw, TEntry{0u, 0.f}, 0.f, sum.stride());
-        if constexpr (!Sum::PLAIN) A *= sum.self(j);
+        uint32_t own0 = 0;
+        if constexpr (Sum::COLUMN_SELF) own0 = sum.own_begin(j);
+        else if constexpr (!Sum::PLAIN) A *= sum.self(j);
         const float nocc = (float)(b - a);
         float nv[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; v++) {
           const float vv = v0[u][v];
           float gr, s[NT];
-          if constexpr (R::REG) gr = G[v] - vv * A + nocc * h.regv * vv;
-          else gr = G[v] - vv * A;
+          float Av = A;
+          if constexpr (Sum::COLUMN_SELF) Av = (f * VEC + (uint32_t)v - own0 < sum.own_width()) ? A : 0.f;
+          if constexpr (R::REG) gr = G[v] - vv * Av + nocc * h.regv * vv;
+          else gr = G[v] - vv * Av;
 #pragma unroll
           for (int t = 0; t < NT; t++) s[t] = s0[u][t][v];
           nv[v] = rule.step_v(gr, vv, s);

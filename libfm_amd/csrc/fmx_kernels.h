@@ -1751,7 +1751,11 @@ struct SegWork {
 // one-segment-per-wavefront path of apply_seg_block), so the first wave-wide load is not issued again.
 // RS: how far apart the sum rows of consecutive examples lie -- RowStrideKP, the batch's [nb][KP] factor sums, or a runtime stride (the
 // field-weighted FM's T rows, fmx_fwfm_kernels.h).
-struct RowStrideKP { template <int KP> __device__ __forceinline__ constexpr size_t of() const { return (size_t)KP; } };
+// live(off): does the lane whose floats begin at column off take part in a sum row's load (a source with rows shorter than KP, fmx_ffm_kernels.h)
+struct RowStrideKP {
+  template <int KP> __device__ __forceinline__ constexpr size_t of() const { return (size_t)KP; }
+  __device__ __forceinline__ constexpr bool live(uint32_t) const { return true; }
+};
 template <int KP, bool PRE = false, class RS = RowStrideKP>
 __device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const float* __restrict__ S, const float* __restrict__ mult,
                                          uint32_t i2, const uint32_t b, const uint32_t lane, const uint32_t f,
@@ -1777,7 +1781,7 @@ __device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const
 #pragma unroll
         for (int q = 0; q < TL; q++) {
           const uint32_t e2 = bcast_u32<1>(te.e, (q0 + q) & 63u);
-          if (q0 + q < cc) load_vec<VEC>(S + (size_t)e2 * rs.template of<KP>() + f * VEC, s2[q]);
+          if (q0 + q < cc && rs.live(f * VEC)) load_vec<VEC>(S + (size_t)e2 * rs.template of<KP>() + f * VEC, s2[q]);
           else {
 #pragma unroll
             for (int v = 0; v < VEC; v++) s2[q][v] = 0.f;
@@ -1805,7 +1809,8 @@ __device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const
 #pragma unroll
       for (int q = 0; q < TL; q++) {
         mm[q] = 0.f;
-        if (i2 + q < b) { mm[q] = mult[tt[q].e]; load_vec<VEC>(S + (size_t)tt[q].e * rs.template of<KP>() + f * VEC, s2[q]); }
+        if (i2 + q < b) mm[q] = mult[tt[q].e];
+        if (i2 + q < b && rs.live(f * VEC)) load_vec<VEC>(S + (size_t)tt[q].e * rs.template of<KP>() + f * VEC, s2[q]);
         else {
 #pragma unroll
           for (int v = 0; v < VEC; v++) s2[q][v] = 0.f;

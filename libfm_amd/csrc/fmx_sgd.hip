@@ -1770,7 +1770,7 @@ int stateful_epoch_steps(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chu
   return stateful_epoch(h, slot, batch, w0_chunk, stats,
                         [k](const SegWork& sw, const Hyper& hy, hipStream_t st) { return k.owner(k.ctx, sw, hy, st); },
                         [k](const Slot& s, uint64_t row0, uint32_t nb, float*, float* rest, hipStream_t st) { return k.rows(k.ctx, s, row0, nb, rest, st); },
-                        [k](uint32_t nb, hipStream_t st) { return k.after(k.ctx, nb, st); });
+                        [k](uint32_t nb, hipStream_t st) { return k.after ? k.after(k.ctx, nb, st) : FMX_OK; });
 }
 }  // extern "C++"
 

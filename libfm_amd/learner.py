@@ -105,9 +105,10 @@ class FMModel:
                 pos += self.num_attribute
             pos += 1
             rows = [[float(x) for x in ln.split(" ") if x != ""] for ln in lines[pos:pos + self.num_attribute]]
-            if len(rows) != self.num_attribute or any(len(r) != self.num_factor for r in rows):
+            width = self.num_factor if self.v is None else self.v.shape[0]      # (model ffm: one vector of num_factor per field)
+            if len(rows) != self.num_attribute or any(len(r) != width for r in rows):
                 return False
-            self.v = np.ascontiguousarray(np.array(rows, dtype=np.float64).reshape(self.num_attribute, self.num_factor).T)
+            self.v = np.ascontiguousarray(np.array(rows, dtype=np.float64).reshape(self.num_attribute, width).T)
             return True                                          # (-dim 1,1,0: n empty lines, as fm_model.h:160-190 reads them)
         except (OSError, ValueError, IndexError):
             return False
@@ -312,10 +313,14 @@ class FMLearnSGD:
     and so is optimizer 'adagrad'; learn, evaluate, predict_raw and predict then run under the learned field matrix, which `.r`
     returns ([F][F]); fwfm_learn_rate (0 = the AdaGrad eta), fwfm_init_acc (0 = 1.0) and fwfm_reg are the matrix's own step
     constants.  Everything else that scores -- evaluate_ex, extra_metrics, the by-query and rank metrics, recommend, compact -- and
-    row weights, checkpoints and feature shards have no form under it and raise before any device is touched."""
+    row weights, checkpoints and feature shards have no form under it and raise before any device is touched.
+    'ffm' is the field-aware FM (fmx_ffm_*), under the same requirements and with the same refusals: fm.num_factor is then the
+    latent factors of ONE (feature, field) vector, fm.v holds F x num_factor rows -- row h * num_factor + f is factor f of the vector
+    used against field h, F the number of fields `groups` names -- and the handle is created with that many factors."""
 
     OPTIMIZERS = ("sgd", "adagrad", "ftrl")
-    MODELS = ("fm", "fwfm")
+    MODELS = ("fm", "fwfm", "ffm")
+    FIELD_MODELS = {"fwfm": "field-weighted", "ffm": "field-aware"}      # the models over `groups`, with what the messages call them
     SHARDED_OPTIMIZERS = ("adagrad", "ftrl")                    # what `devices` with more than one entry is honoured for
     MODES = {"sequential": capi.SGD_SEQUENTIAL, "minibatch": capi.SGD_MINIBATCH, "hogwild": capi.SGD_HOGWILD}
     APPLY = {"default": capi.APPLY_DEFAULT, "atomic": capi.APPLY_ATOMIC, "store": capi.APPLY_STORE,
@@ -358,28 +363,34 @@ class FMLearnSGD:
         self._adapt_open = False
         self._ftrl_open = False
         self._fwfm_open = False
+        self._ffm_open = False
         self._checkpoint = None                                 # load_checkpoint before init(): the file init() starts from
 
     def _check_model(self):
         if self.model not in self.MODELS:
             raise ValueError("unknown model for %s: %s (%s)" % (type(self).__name__, self.model, " | ".join(self.MODELS)))
-        if self.model != "fwfm":
+        if self.model not in self.FIELD_MODELS:
             return
         if type(self) is not FMLearnSGD:
-            raise NotImplementedError("%s has no field-weighted form: model fwfm belongs to FMLearnSGD" % type(self).__name__)
+            raise NotImplementedError("%s has no %s form: model %s belongs to FMLearnSGD"
+                                      % (type(self).__name__, self.FIELD_MODELS[self.model], self.model))
         if self.optimizer != "adagrad":
-            raise ValueError("model fwfm trains with optimizer adagrad, not %s" % self.optimizer)
+            raise ValueError("model %s trains with optimizer adagrad, not %s" % (self.model, self.optimizer))
         if self.groups is None:
-            raise ValueError("model fwfm needs groups: the attribute -> field map")
-        self._not_on_shards("model fwfm")
+            raise ValueError("model %s needs groups: the attribute -> field map" % self.model)
+        self._not_on_shards("model %s" % self.model)
         for what, on in (("load_checkpoint", self._checkpoint is not None), ("set_weights", bool(self._weights)),
                          ("extra_metrics", bool(self.extra_metrics)), ("set_queries", bool(self._queries))):
             if on:
-                raise NotImplementedError("%s is not supported with model fwfm" % what)
+                raise NotImplementedError("%s is not supported with model %s" % (what, self.model))
 
     def _not_under_fwfm(self, what):
-        if self.model == "fwfm":
-            raise NotImplementedError("%s is not supported with model fwfm: it scores the plain FM" % what)
+        if self.model in self.FIELD_MODELS:
+            raise NotImplementedError("%s is not supported with model %s: it scores the plain FM" % (what, self.model))
+
+    def _ffm_fields(self):
+        """model 'ffm': the number of fields `groups` names"""
+        return int(np.max(self.groups)) + 1 if len(self.groups) else 1
 
     @property
     def r(self):
@@ -439,7 +450,8 @@ class FMLearnSGD:
             return
         if self.devices is not None and len(self.devices) == 1:
             self.device = int(self.devices[0])
-        self._h = capi.Handle(fm.num_attribute, fm.num_factor, fm.k0, fm.k1, self.task, fm.reg0, fm.regw, fm.regv,
+        width = fm.num_factor * self._ffm_fields() if self.model == "ffm" else fm.num_factor
+        self._h = capi.Handle(fm.num_attribute, width, fm.k0, fm.k1, self.task, fm.reg0, fm.regw, fm.regv,
                               self.learn_rate, self.min_target, self.max_target, device=self.device)
         if self._checkpoint is not None:                        # the file's parameters and session, not fm's and a fresh one
             self._load_checkpoint_now(self._checkpoint)
@@ -461,6 +473,10 @@ class FMLearnSGD:
             self._h.set_groups(self.groups)
             self._h.fwfm_begin(self.fwfm_learn_rate, self.fwfm_init_acc, self.fwfm_reg)
             self._fwfm_open = True
+        if self.model == "ffm" and not self._ffm_open:
+            self._h.set_groups(self.groups)
+            self._h.ffm_begin(fm.num_factor)
+            self._ffm_open = True
 
     def save_checkpoint(self, path, dense=False):
         """the exact binary checkpoint of the model on the device and of the open adagrad / ftrl session (fmx_checkpoint_save;
@@ -581,7 +597,7 @@ class FMLearnSGD:
         self._check_devices()
         if (self.optimizer == "adagrad") != self._adapt_open or (self.optimizer == "ftrl") != self._ftrl_open:
             raise ValueError("optimizer was changed after init()")
-        if (self.model == "fwfm") != self._fwfm_open:
+        if (self.model == "fwfm") != self._fwfm_open or (self.model == "ffm") != self._ffm_open:
             raise ValueError("model was changed after init()")
         if id(train) in self._weights and self.optimizer == "sgd":
             raise ValueError("the train set has weights (set_weights): optimizer sgd has no weighted form, use adagrad or ftrl")
@@ -598,6 +614,8 @@ class FMLearnSGD:
             flags |= capi.FLAG_KEEP_WSIDE                # the train set is evaluated after every epoch (fm_learn_sgd_element.h:69-70)
             if self._fwfm_open:
                 stats = self._h.fwfm_epoch(st, self.batch, self.w0_chunk)
+            elif self._ffm_open:
+                stats = self._h.ffm_epoch(st, self.batch, self.w0_chunk)
             elif self._adapt_open:
                 stats = self._h.adapt_epoch(st, self.batch, self.w0_chunk)
             elif self._ftrl_open:
@@ -622,7 +640,8 @@ class FMLearnSGD:
 
     # fm_learn::evaluate (fm_learn.h:93-153): rmse for regression, accuracy for classification
     def evaluate(self, data):
-        ev = self._h.fwfm_evaluate(self._slot(data)) if self._fwfm_open else self._h.evaluate(self._slot(data))
+        scorer = self._h.fwfm_evaluate if self._fwfm_open else self._h.ffm_evaluate if self._ffm_open else self._h.evaluate
+        ev = scorer(self._slot(data))
         return ev.rmse if self.task == TASK_REGRESSION else ev.accuracy
 
     EVAL_LINK = capi.LINK_LOGISTIC       # fm_learn_sgd::predict maps a classification score through the sigmoid (fm_learn_sgd.h:80-87)
@@ -636,6 +655,8 @@ class FMLearnSGD:
         """fm_learn::predict_case over the data set (fm_learn.h:63-65)."""
         if self._fwfm_open:
             return self._h.fwfm_predict(self._slot(data), data.num_cases)
+        if self._ffm_open:
+            return self._h.ffm_predict(self._slot(data), data.num_cases)
         return self._h.predict(self._slot(data), data.num_cases)
 
     def recommend(self, queries, candidates, topk, exclude=None):
@@ -685,6 +706,9 @@ class FMLearnSGD:
             if self._fwfm_open:
                 self._h.fwfm_end()
                 self._fwfm_open = False
+            if self._ffm_open:
+                self._h.ffm_end()
+                self._ffm_open = False
             if self._adapt_open:
                 self._h.adapt_end()
                 self._adapt_open = False
