@@ -1643,6 +1643,55 @@ int fmx_ffm_evaluate(fmx_handle h, int slot, fmx_eval *out);
 int fmx_ffm_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
 int fmx_ffm_end(fmx_handle h);
 
+/* ---- the field-matrixed FM (FmFM, Sun et al., WWW 2021) -----------------------------------------------------
+ *   y(x) = w0 + sum_j w_j x_j + sum_{a<b} x_a x_b  v_ja^T M[g(ja)][g(jb)] v_jb        (a, b: the row's entries, in row order)
+ * g() is the feature -> field map of fmx_set_groups (none: one field), F = num_groups, k = num_factor.  M[g][h] is a k x k matrix with
+ * M[h][g] = M[g][h]^T, so the order of a pair does not matter; the diagonal blocks M[g][g] are the identity and are NOT learned (two
+ * entries of one field interact as in the plain FM).  An id repeated inside a row counts as separate entries.  With every block the
+ * identity the model IS the plain FM; M[g][h] = r_gh I is the field-weighted FM with a unit diagonal.  The session owns M and its
+ * AdaGrad accumulators; w, V and their accumulators stay the handle's, and fmx_predict and every other existing call keep scoring the
+ * plain FM.  Added without an ABI version change: a caller detects the feature by the symbol fmx_fmfm_begin.
+ *
+ * With the field sums S_g = sum_{i in g} v_i x_i of a row side by side in one vector s, D = sum_i |v_i x_i|^2 and MM the symmetric
+ * (F k) x (F k) matrix of all blocks:  t = MM s,  pair term = 1/2 <s, t> - 1/2 D,  d/dv_i = x_i (t_g(i) - v_i x_i),  d/dM[g][h] = S_g S_h^T.
+ *
+ *   fmx_fmfm_begin    : every block the identity, n_M = init_acc_m.  Called again it resets both.
+ *   fmx_fmfm_set_m    : m[((g F + h) k + a) k + b] multiplies v_i[a] v_j[b] for i in field g and j in field h.  Refuses a value that is not
+ *                       finite, a lower block that is not exactly the transpose of its upper block, and a diagonal block that is not
+ *                       exactly the identity.  n_M keeps its values.
+ *   fmx_fmfm_get_m    : all F^2 blocks of M and, where n_m is not NULL, of the accumulators (diagonal blocks of n_m read as init_acc_m).
+ *   fmx_fmfm_predict  : fmx_predict's contract under the session's M.
+ *   fmx_fmfm_evaluate : fmx_evaluate's contract under the session's M.
+ *   fmx_fmfm_epoch    : fmx_adapt_epoch's contract (batch, w0_chunk, stats, an empty slot) with the FmFM's sums and gradients.  It needs
+ *                       an open fmx_adapt session and steps w and V on THAT session's accumulators with its eta, from the batch-start
+ *                       parameters; the bias keeps its micro-chunk SGD.  Per batch every block g < h then takes
+ *                       g_M = sum_e mult_e S_e,g S_e,h^T + reg_m M[g][h],  n_M += g^2,  M -= eta_m g / sqrt(n_M)  in fp64, and M[h][g] is
+ *                       written as its transpose.  No float atomics anywhere: two runs give the same bits.
+ *   fmx_fmfm_end      : frees M, n_M and the session's scratch.
+ * Limits (FMX_E_UNSUPPORTED beyond): at most 64 fields, 1 <= num_factor <= 128, and F x (num_factor rounded up to a power of two),
+ * rounded up to 16, at most 2048 columns (WP).  Scratch: rows x (2 WP + 2) x 4 bytes plus at most 8 x WP x WP x 4 bytes for an epoch's
+ * largest batch; scoring works through pieces of at most 2^25 / WP rows.  All of it is kept until fmx_fmfm_end.
+ * Refusals, each before any launch, the handle usable afterwards.  FMX_E_ARG: NULL opts, m or out; flags != 0; an option that is negative
+ * or not finite; what fmx_fmfm_set_m refuses.  FMX_E_STATE: any call but _begin without a session; num_groups changed under the
+ * session; fmx_fmfm_epoch without an fmx_adapt session; a slot never uploaded, or without targets for _epoch and _evaluate; an open
+ * SGDA or ALS / MCMC session; fmx_fmfm_begin while an fmx_fwfm or fmx_ffm session is open, and their _begin while this one is.
+ * FMX_E_UNSUPPORTED: a feature shard or communicator rank; kept `-relation` blocks; a slot with row weights; the limits above.
+ * Not offered under it: FTRL, the pairwise epochs, fmx_evaluate_ex / _by_query / _rank, fmx_topk, M in checkpoints or snapshots,
+ * feature shards, row weights. */
+typedef struct fmx_fmfm_opts {
+  double learn_rate_m;     /* eta of M's AdaGrad step; 0 = the eta of the fmx_adapt session */
+  double init_acc_m;       /* n_M at _begin; 0 = 1.0 */
+  double reg_m;            /* L2 on the learned blocks, once per batch; 0 = none */
+  uint32_t flags;          /* 0 */
+} fmx_fmfm_opts;
+int fmx_fmfm_begin(fmx_handle h, const fmx_fmfm_opts *opts);
+int fmx_fmfm_set_m(fmx_handle h, const double *m /* [F][F][k][k] */);
+int fmx_fmfm_get_m(fmx_handle h, double *m, double *n_m /* may be NULL */);
+int fmx_fmfm_predict(fmx_handle h, int slot, double *out);
+int fmx_fmfm_evaluate(fmx_handle h, int slot, fmx_eval *out);
+int fmx_fmfm_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
+int fmx_fmfm_end(fmx_handle h);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 typedef struct fmx_info {
   uint64_t n_local;         /* features held by this handle */

@@ -83,6 +83,10 @@ class FfmOpts(C.Structure):                        # fmx_ffm_opts
     _fields_ = [("num_latent", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class FmfmOpts(C.Structure):                       # fmx_fmfm_opts
+    _fields_ = [("learn_rate_m", C.c_double), ("init_acc_m", C.c_double), ("reg_m", C.c_double), ("flags", C.c_uint32)]
+
+
 class FwfmOpts(C.Structure):                       # fmx_fwfm_opts
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("learn_rate_r", C.c_double), ("init_acc_r", C.c_double),
                 ("reg_r", C.c_double)]
@@ -444,6 +448,13 @@ SYMBOLS = [
     ("fmx_ffm_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
     ("fmx_ffm_epoch", C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
     ("fmx_ffm_end", C.c_int, [H]),
+    ("fmx_fmfm_begin", C.c_int, [H, C.POINTER(FmfmOpts)]),
+    ("fmx_fmfm_set_m", C.c_int, [H, C.c_void_p]),
+    ("fmx_fmfm_get_m", C.c_int, [H, C.c_void_p, C.c_void_p]),
+    ("fmx_fmfm_predict", C.c_int, [H, C.c_int, C.c_void_p]),
+    ("fmx_fmfm_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
+    ("fmx_fmfm_epoch", C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
+    ("fmx_fmfm_end", C.c_int, [H]),
     ("fmx_get_info", C.c_int, [H, C.POINTER(Info)]),
     ("fmx_synchronize", C.c_int, [H]),
 ]
@@ -1054,6 +1065,40 @@ class Handle:
 
     def ffm_end(self):
         self._chk(self.lib.fmx_ffm_end(self.h))
+
+    # the field-matrixed FM (include/fmx.h "fmx_fmfm_*"): fields = the groups of set_groups, one k x k matrix per pair of fields ------
+    def fmfm_begin(self, learn_rate_m=0.0, init_acc_m=0.0, reg_m=0.0):
+        self._chk(self.lib.fmx_fmfm_begin(self.h, C.byref(FmfmOpts(float(learn_rate_m), float(init_acc_m), float(reg_m), 0))))
+
+    def fmfm_set_m(self, m):
+        m = np.ascontiguousarray(m, dtype=np.float64)
+        if m.shape != (self.G, self.G, self.k, self.k):
+            raise ValueError("fmfm_set_m: need %d x %d blocks of %d x %d, got %r" % (self.G, self.G, self.k, self.k, m.shape))
+        self._chk(self.lib.fmx_fmfm_set_m(self.h, _ptr(m)))
+
+    def fmfm_get_m(self):
+        """(M, n_M), both [F][F][k][k]"""
+        m, nm = (np.zeros((self.G, self.G, self.k, self.k), dtype=np.float64) for _ in range(2))
+        self._chk(self.lib.fmx_fmfm_get_m(self.h, _ptr(m), _ptr(nm)))
+        return m, nm
+
+    def fmfm_predict(self, slot, n_rows):
+        out = np.zeros(n_rows, dtype=np.float64)
+        self._chk(self.lib.fmx_fmfm_predict(self.h, slot, _ptr(out)))
+        return out
+
+    def fmfm_evaluate(self, slot):
+        ev = Eval()
+        self._chk(self.lib.fmx_fmfm_evaluate(self.h, slot, C.byref(ev)))
+        return ev
+
+    def fmfm_epoch(self, slot, batch=0, w0_chunk=0):
+        st = EpochStats()
+        self._chk(self.lib.fmx_fmfm_epoch(self.h, int(slot), int(batch), int(w0_chunk), C.byref(st)))
+        return st
+
+    def fmfm_end(self):
+        self._chk(self.lib.fmx_fmfm_end(self.h))
 
     # FTRL-proximal with L1 on the minibatch rule (include/fmx.h "fmx_ftrl_*") -------------------
     def ftrl_begin(self, alpha=0.0, beta=1.0, l1_w=0.0, l1_v=0.0, l2_w=0.0, l2_v=0.0, init_acc=0.0):

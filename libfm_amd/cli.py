@@ -83,6 +83,9 @@ learned matrix, which -r_out writes as text, one row per line.  Any other method
 -model ffm -meta F (-method sgd -optimizer adagrad): the field-aware FM (fmx_ffm_*): -dim 1,1,k gives every feature one vector of k
 factors per field, so -save_model / -load_model carry F k columns per feature (field-major).  The same flags are refused as with
 -model fwfm, in the same words, and so is -r_out.
+-model fmfm -meta F [-m_out FILE] (-method sgd -optimizer adagrad): the field-matrixed FM (fmx_fmfm_*): one learned k x k matrix per
+pair of fields over the same w and V.  -m_out writes the learned blocks g < h as text: one line `g h`, then the block's k rows.  The
+same flags are refused as with -model fwfm, in the same words, and so is -r_out; -m_out is refused without -model fmfm.
 """
 import os
 import sys
@@ -142,8 +145,9 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "save_snapshot": "with -serve: filename for the snapshot file of the frozen copy, written after it is taken",
          "load_snapshot": "-method serve: filename of the snapshot file to score from (no model is created; -train and -dim are not needed)",
          "devices": "'D0,D1,...': -method sgd with -optimizer adagrad | ftrl over one feature shard per listed device ordinal ('0,0': two shards on device 0)",
-         "model": "fm | fwfm | ffm (-method sgd -optimizer adagrad -meta F): fwfm learns one interaction strength per pair of the fields -meta names, "
-                  "ffm one vector of -dim's k factors per feature and field; default=fm",
+         "model": "fm | fwfm | ffm | fmfm (-method sgd -optimizer adagrad -meta F): fwfm learns one interaction strength per pair of the fields -meta names, "
+                  "ffm one vector of -dim's k factors per feature and field, fmfm one k x k matrix per pair of fields; default=fm",
+         "m_out": "-model fmfm: filename for the learned blocks g < h as text, one line 'g h' and then k rows each",
          "r_out": "-model fwfm: filename for the learned field matrix as text, one row per line"}
 
 
@@ -451,11 +455,13 @@ def _main(argv):
         if not devices or any(d < 0 for d in devices) or len(devices) > 16:
             raise ValueError("-devices needs 1 .. 16 device ordinals >= 0: 'D0,D1,...'")
     model = a.get("model", "fm")
-    if "model" in a or "r_out" in a:
+    if "model" in a or "r_out" in a or "m_out" in a:
         if model not in L.FMLearnSGD.MODELS:
-            raise ValueError("-model knows fm, fwfm and ffm, not '%s'" % model)
+            raise ValueError("-model knows fm, fwfm, ffm and fmfm, not '%s'" % model)
         if model != "fwfm" and "r_out" in a:
             raise ValueError("-r_out belongs to -model fwfm")
+        if model != "fmfm" and "m_out" in a:
+            raise ValueError("-m_out belongs to -model fmfm")
         if model != "fm":
             if method != "sgd" or optimizer != "adagrad":
                 raise ValueError("-model %s belongs to -method sgd with -optimizer adagrad, not -method %s%s"
@@ -467,6 +473,8 @@ def _main(argv):
                     raise ValueError("-%s is not supported with -model %s" % (f, model))
             if "r_out" in a and not a["r_out"]:
                 raise ValueError("-r_out needs a filename")
+            if "m_out" in a and not a["m_out"]:
+                raise ValueError("-m_out needs a filename")
     serve = a.get("serve")
     if "serve" in a:
         if serve not in C.FORMATS:
@@ -768,6 +776,12 @@ def _main(argv):
     if "r_out" in a:
         with open(a["r_out"], "w") as f:
             f.write("".join(" ".join("%g" % x for x in row) + "\n" for row in l.r))
+    if "m_out" in a:
+        m = l.m
+        with open(a["m_out"], "w") as f:
+            for g in range(m.shape[0]):
+                for h in range(g + 1, m.shape[0]):
+                    f.write("%d %d\n" % (g, h) + "".join(" ".join("%g" % x for x in row) + "\n" for row in m[g, h]))
     if optimizer == "ftrl":
         sp = l.sparsity()
         print("sparsity\tfeatures=%d\tw_zero=%d\tv_coords=%d\tv_zero=%d\tv_zero_rows=%d\tdead_features=%d" %

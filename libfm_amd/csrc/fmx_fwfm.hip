@@ -168,6 +168,7 @@ int fmx_fwfm_begin(fmx_handle h, const fmx_fwfm_opts* opts) {
   if (!(opts->reg_r >= 0.0) || std::isinf(opts->reg_r)) return fail(h, FMX_E_ARG, "fmx_fwfm_begin: reg_r must be finite and >= 0");
   int rc = fwfm_check_handle(h, "fmx_fwfm_begin"); if (rc) return rc;
   if (h->ffm.open) return fail(h, FMX_E_STATE, "fmx_fwfm_begin: a field-aware FM session is open (call fmx_ffm_end first)");
+  if (h->fmfm.open) return fail(h, FMX_E_STATE, "fmx_fwfm_begin: a field-matrixed FM session is open (call fmx_fmfm_end first)");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   fwfm_free(h);

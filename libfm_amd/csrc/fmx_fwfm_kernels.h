@@ -166,11 +166,6 @@ k_fwfm_rows(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr,
 // The owner of a (batch, feature) segment: stateful_seg_block with AdagradRule, its sum rows taken from T.  Feature j of field g reads
 // row (e FP + g) KP of T for its occurrence in example e -- T + g KP with a stride of FP KP floats -- and its own term carries r_gg.
 // ----------------------------------------------------------------------------------------------
-struct RowStrideRT {
-  uint32_t s;
-  template <int KP> __device__ __forceinline__ size_t of() const { return (size_t)s; }
-  __device__ __forceinline__ constexpr bool live(uint32_t) const { return true; }
-};
 struct FwfmSums {
   static constexpr bool PLAIN = false, COLUMN_SELF = false;
   const float* T; const uint32_t* grp; const float* R;             // R: the fp32 copy [FP][FP]

@@ -1756,6 +1756,12 @@ struct RowStrideKP {
   template <int KP> __device__ __forceinline__ constexpr size_t of() const { return (size_t)KP; }
   __device__ __forceinline__ constexpr bool live(uint32_t) const { return true; }
 };
+// a stride known at run time only: the T rows of the field-weighted and the field-matrixed FM (fmx_fwfm_kernels.h, fmx_fmfm_kernels.h)
+struct RowStrideRT {
+  uint32_t s;
+  template <int KP> __device__ __forceinline__ size_t of() const { return (size_t)s; }
+  __device__ __forceinline__ constexpr bool live(uint32_t) const { return true; }
+};
 template <int KP, bool PRE = false, class RS = RowStrideKP>
 __device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const float* __restrict__ S, const float* __restrict__ mult,
                                          uint32_t i2, const uint32_t b, const uint32_t lane, const uint32_t f,

@@ -316,11 +316,14 @@ class FMLearnSGD:
     row weights, checkpoints and feature shards have no form under it and raise before any device is touched.
     'ffm' is the field-aware FM (fmx_ffm_*), under the same requirements and with the same refusals: fm.num_factor is then the
     latent factors of ONE (feature, field) vector, fm.v holds F x num_factor rows -- row h * num_factor + f is factor f of the vector
-    used against field h, F the number of fields `groups` names -- and the handle is created with that many factors."""
+    used against field h, F the number of fields `groups` names -- and the handle is created with that many factors.
+    'fmfm' is the field-matrixed FM (fmx_fmfm_*), again under the same requirements and with the same refusals: one learned k x k
+    matrix per pair of fields over the same w and V, which `.m` returns ([F][F][k][k]); fmfm_learn_rate (0 = the AdaGrad eta),
+    fmfm_init_acc (0 = 1.0) and fmfm_reg are the matrices' own step constants."""
 
     OPTIMIZERS = ("sgd", "adagrad", "ftrl")
-    MODELS = ("fm", "fwfm", "ffm")
-    FIELD_MODELS = {"fwfm": "field-weighted", "ffm": "field-aware"}      # the models over `groups`, with what the messages call them
+    MODELS = ("fm", "fwfm", "ffm", "fmfm")
+    FIELD_MODELS = {"fwfm": "field-weighted", "ffm": "field-aware", "fmfm": "field-matrixed"}      # the models over `groups`, with what the messages call them
     SHARDED_OPTIMIZERS = ("adagrad", "ftrl")                    # what `devices` with more than one entry is honoured for
     MODES = {"sequential": capi.SGD_SEQUENTIAL, "minibatch": capi.SGD_MINIBATCH, "hogwild": capi.SGD_HOGWILD}
     APPLY = {"default": capi.APPLY_DEFAULT, "atomic": capi.APPLY_ATOMIC, "store": capi.APPLY_STORE,
@@ -343,6 +346,7 @@ class FMLearnSGD:
         self.model = "fm"
         self.groups = None                                      # model 'fwfm': attribute -> field
         self.fwfm_learn_rate, self.fwfm_init_acc, self.fwfm_reg = 0.0, 0.0, 0.0
+        self.fmfm_learn_rate, self.fmfm_init_acc, self.fmfm_reg = 0.0, 0.0, 0.0
         self.init_acc = 0.0
         self.adapt_learn_rate = 0.0
         self.ftrl_alpha = 0.0
@@ -364,6 +368,7 @@ class FMLearnSGD:
         self._ftrl_open = False
         self._fwfm_open = False
         self._ffm_open = False
+        self._fmfm_open = False
         self._checkpoint = None                                 # load_checkpoint before init(): the file init() starts from
 
     def _check_model(self):
@@ -398,6 +403,13 @@ class FMLearnSGD:
         if not self._fwfm_open:
             raise ValueError("r: model fwfm after init() only")
         return self._h.fwfm_get_r()[0]
+
+    @property
+    def m(self):
+        """model 'fmfm': the learned field matrices [F][F][k][k] as the device holds them"""
+        if not self._fmfm_open:
+            raise ValueError("m: model fmfm after init() only")
+        return self._h.fmfm_get_m()[0]
 
     def _check_optimizer(self):
         self._check_model()
@@ -477,6 +489,10 @@ class FMLearnSGD:
             self._h.set_groups(self.groups)
             self._h.ffm_begin(fm.num_factor)
             self._ffm_open = True
+        if self.model == "fmfm" and not self._fmfm_open:
+            self._h.set_groups(self.groups)
+            self._h.fmfm_begin(self.fmfm_learn_rate, self.fmfm_init_acc, self.fmfm_reg)
+            self._fmfm_open = True
 
     def save_checkpoint(self, path, dense=False):
         """the exact binary checkpoint of the model on the device and of the open adagrad / ftrl session (fmx_checkpoint_save;
@@ -597,7 +613,7 @@ class FMLearnSGD:
         self._check_devices()
         if (self.optimizer == "adagrad") != self._adapt_open or (self.optimizer == "ftrl") != self._ftrl_open:
             raise ValueError("optimizer was changed after init()")
-        if (self.model == "fwfm") != self._fwfm_open or (self.model == "ffm") != self._ffm_open:
+        if (self.model == "fwfm") != self._fwfm_open or (self.model == "ffm") != self._ffm_open or (self.model == "fmfm") != self._fmfm_open:
             raise ValueError("model was changed after init()")
         if id(train) in self._weights and self.optimizer == "sgd":
             raise ValueError("the train set has weights (set_weights): optimizer sgd has no weighted form, use adagrad or ftrl")
@@ -616,6 +632,8 @@ class FMLearnSGD:
                 stats = self._h.fwfm_epoch(st, self.batch, self.w0_chunk)
             elif self._ffm_open:
                 stats = self._h.ffm_epoch(st, self.batch, self.w0_chunk)
+            elif self._fmfm_open:
+                stats = self._h.fmfm_epoch(st, self.batch, self.w0_chunk)
             elif self._adapt_open:
                 stats = self._h.adapt_epoch(st, self.batch, self.w0_chunk)
             elif self._ftrl_open:
@@ -640,7 +658,8 @@ class FMLearnSGD:
 
     # fm_learn::evaluate (fm_learn.h:93-153): rmse for regression, accuracy for classification
     def evaluate(self, data):
-        scorer = self._h.fwfm_evaluate if self._fwfm_open else self._h.ffm_evaluate if self._ffm_open else self._h.evaluate
+        scorer = (self._h.fwfm_evaluate if self._fwfm_open else self._h.ffm_evaluate if self._ffm_open else
+                  self._h.fmfm_evaluate if self._fmfm_open else self._h.evaluate)
         ev = scorer(self._slot(data))
         return ev.rmse if self.task == TASK_REGRESSION else ev.accuracy
 
@@ -657,6 +676,8 @@ class FMLearnSGD:
             return self._h.fwfm_predict(self._slot(data), data.num_cases)
         if self._ffm_open:
             return self._h.ffm_predict(self._slot(data), data.num_cases)
+        if self._fmfm_open:
+            return self._h.fmfm_predict(self._slot(data), data.num_cases)
         return self._h.predict(self._slot(data), data.num_cases)
 
     def recommend(self, queries, candidates, topk, exclude=None):
@@ -709,6 +730,9 @@ class FMLearnSGD:
             if self._ffm_open:
                 self._h.ffm_end()
                 self._ffm_open = False
+            if self._fmfm_open:
+                self._h.fmfm_end()
+                self._fmfm_open = False
             if self._adapt_open:
                 self._h.adapt_end()
                 self._adapt_open = False
