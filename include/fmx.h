@@ -1692,6 +1692,47 @@ int fmx_fmfm_evaluate(fmx_handle h, int slot, fmx_eval *out);
 int fmx_fmfm_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
 int fmx_fmfm_end(fmx_handle h);
 
+/* ---- the third-order FM (the higher-order FM of Blondel et al., NIPS 2016, at order 3) ----------------------
+ *   y(x) = w0 + sum_j w_j x_j + sum_{c < k2} sum_{a<b} z_a z_b + sum_{c >= k2} sum_{a<b<d} z_a z_b z_d,     z_a = x_a v[j_a][c]
+ * (a, b, d: the row's entries, in row order).  The handle is created with num_factor = k2 + k3: columns [0, k2) of a row of V are the
+ * pairwise factors and behave as in the plain FM, columns [k2, k2 + k3) are the third-order factors, k3 = num_factor3.  The session
+ * owns NO parameters: w, V and the accumulators of the open fmx_adapt session stay the handle's tables, so fmx_get_params /
+ * fmx_set_params, checkpoints and fmx_save_model see them as they are; fmx_predict, fmx_evaluate and every other existing call keep
+ * scoring the plain FM of width num_factor.  With num_factor3 = 0 the model IS the plain FM (and fmx_hofm_epoch leaves
+ * fmx_adapt_epoch's bits); num_factor3 = num_factor leaves no pair part.  An id repeated inside a row counts as separate entries; a
+ * row of fewer than three entries has no third-order term.  No field map is read.
+ * Added without an ABI version change: a caller detects the feature by the symbol fmx_hofm_begin.
+ *
+ * With the power sums p_m[c] = sum_a z_a^m of a row and E2 = 1/2 (p1^2 - p2):
+ *   third-order term = (p1^3 - 3 p1 p2 + 2 p3) / 6          d/dv[j_a][c] = x_a (E2 - z_a p1 + z_a^2)       (c >= k2)
+ *
+ *   fmx_hofm_begin    : opens the session for num_factor3 third-order factors; called again it starts over.
+ *   fmx_hofm_predict  : fmx_predict's contract under the third-order model.
+ *   fmx_hofm_evaluate : fmx_evaluate's contract under the third-order model.
+ *   fmx_hofm_epoch    : fmx_adapt_epoch's contract (batch, w0_chunk, stats, an empty slot) with the model's sums and gradients.  It
+ *                       needs an open fmx_adapt session and steps w and every column of V on THAT session's accumulators with its
+ *                       eta, from the batch-start parameters; the bias keeps its micro-chunk SGD.  There is no other state.  No
+ *                       float atomics anywhere: two runs give the same bits.
+ *   fmx_hofm_end      : closes the session and frees its scratch.
+ * Limits (FMX_E_UNSUPPORTED beyond): 1 <= num_factor <= 1024.  Scratch of an epoch: at most batch * 2 * (num_factor rounded up to 16)
+ * * 4 bytes, kept until fmx_hofm_end.
+ * Refusals, each before any launch, the handle usable afterwards.  FMX_E_ARG: NULL opts or out; flags != 0; num_factor3 > num_factor.
+ * FMX_E_STATE: any call but _begin without a session; fmx_hofm_epoch without an fmx_adapt session; a slot never uploaded, or without
+ * targets for _epoch and _evaluate; an open SGDA or ALS / MCMC session; fmx_hofm_begin while an fmx_fwfm, fmx_ffm or fmx_fmfm session
+ * is open, and their _begin while this one is.  FMX_E_UNSUPPORTED: a feature shard or communicator rank; kept `-relation` blocks; a
+ * slot with row weights; the limit above.
+ * Not offered under it: FTRL, the pairwise epochs, fmx_evaluate_ex / _by_query / _rank, fmx_topk, snapshots, feature shards, row
+ * weights, orders above 3, a field model on top. */
+typedef struct fmx_hofm_opts {
+  uint32_t num_factor3;    /* third-order factors: the LAST num_factor3 columns of a row; 0 .. num_factor */
+  uint32_t flags;          /* 0 */
+} fmx_hofm_opts;
+int fmx_hofm_begin(fmx_handle h, const fmx_hofm_opts *opts);
+int fmx_hofm_predict(fmx_handle h, int slot, double *out);
+int fmx_hofm_evaluate(fmx_handle h, int slot, fmx_eval *out);
+int fmx_hofm_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
+int fmx_hofm_end(fmx_handle h);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 typedef struct fmx_info {
   uint64_t n_local;         /* features held by this handle */

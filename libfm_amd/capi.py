@@ -83,6 +83,10 @@ class FfmOpts(C.Structure):                        # fmx_ffm_opts
     _fields_ = [("num_latent", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class HofmOpts(C.Structure):                       # fmx_hofm_opts
+    _fields_ = [("num_factor3", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class FmfmOpts(C.Structure):                       # fmx_fmfm_opts
     _fields_ = [("learn_rate_m", C.c_double), ("init_acc_m", C.c_double), ("reg_m", C.c_double), ("flags", C.c_uint32)]
 
@@ -455,6 +459,11 @@ SYMBOLS = [
     ("fmx_fmfm_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
     ("fmx_fmfm_epoch", C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
     ("fmx_fmfm_end", C.c_int, [H]),
+    ("fmx_hofm_begin", C.c_int, [H, C.POINTER(HofmOpts)]),
+    ("fmx_hofm_predict", C.c_int, [H, C.c_int, C.c_void_p]),
+    ("fmx_hofm_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
+    ("fmx_hofm_epoch", C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
+    ("fmx_hofm_end", C.c_int, [H]),
     ("fmx_get_info", C.c_int, [H, C.POINTER(Info)]),
     ("fmx_synchronize", C.c_int, [H]),
 ]
@@ -1099,6 +1108,28 @@ class Handle:
 
     def fmfm_end(self):
         self._chk(self.lib.fmx_fmfm_end(self.h))
+
+    # the third-order FM (include/fmx.h "fmx_hofm_*"): the last num_factor3 columns of a row are third-order factors ------
+    def hofm_begin(self, num_factor3):
+        self._chk(self.lib.fmx_hofm_begin(self.h, C.byref(HofmOpts(int(num_factor3), 0))))
+
+    def hofm_predict(self, slot, n_rows):
+        out = np.zeros(n_rows, dtype=np.float64)
+        self._chk(self.lib.fmx_hofm_predict(self.h, slot, _ptr(out)))
+        return out
+
+    def hofm_evaluate(self, slot):
+        ev = Eval()
+        self._chk(self.lib.fmx_hofm_evaluate(self.h, slot, C.byref(ev)))
+        return ev
+
+    def hofm_epoch(self, slot, batch=0, w0_chunk=0):
+        st = EpochStats()
+        self._chk(self.lib.fmx_hofm_epoch(self.h, int(slot), int(batch), int(w0_chunk), C.byref(st)))
+        return st
+
+    def hofm_end(self):
+        self._chk(self.lib.fmx_hofm_end(self.h))
 
     # FTRL-proximal with L1 on the minibatch rule (include/fmx.h "fmx_ftrl_*") -------------------
     def ftrl_begin(self, alpha=0.0, beta=1.0, l1_w=0.0, l1_v=0.0, l2_w=0.0, l2_v=0.0, init_acc=0.0):

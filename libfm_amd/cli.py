@@ -86,6 +86,9 @@ factors per field, so -save_model / -load_model carry F k columns per feature (f
 -model fmfm -meta F [-m_out FILE] (-method sgd -optimizer adagrad): the field-matrixed FM (fmx_fmfm_*): one learned k x k matrix per
 pair of fields over the same w and V.  -m_out writes the learned blocks g < h as text: one line `g h`, then the block's k rows.  The
 same flags are refused as with -model fwfm, in the same words, and so is -r_out; -m_out is refused without -model fmfm.
+-model hofm -dim k0,k1,k2,k3 (-method sgd -optimizer adagrad): the third-order FM (fmx_hofm_*): k2 pairwise and k3 third-order factors
+per feature, so -save_model / -load_model carry k2 + k3 columns, the third-order ones last.  No -meta is needed; the other flags are
+refused as with -model fwfm, in the same words.  A fourth -dim number without -model hofm stays the error it was.
 """
 import os
 import sys
@@ -145,8 +148,8 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "save_snapshot": "with -serve: filename for the snapshot file of the frozen copy, written after it is taken",
          "load_snapshot": "-method serve: filename of the snapshot file to score from (no model is created; -train and -dim are not needed)",
          "devices": "'D0,D1,...': -method sgd with -optimizer adagrad | ftrl over one feature shard per listed device ordinal ('0,0': two shards on device 0)",
-         "model": "fm | fwfm | ffm | fmfm (-method sgd -optimizer adagrad -meta F): fwfm learns one interaction strength per pair of the fields -meta names, "
-                  "ffm one vector of -dim's k factors per feature and field, fmfm one k x k matrix per pair of fields; default=fm",
+         "model": "fm | fwfm | ffm | fmfm | hofm (-method sgd -optimizer adagrad; -meta F but for hofm): fwfm learns one interaction strength per pair of the fields -meta names, "
+                  "ffm one vector of -dim's k factors per feature and field, fmfm one k x k matrix per pair of fields, hofm adds k3 third-order factors (-dim k0,k1,k2,k3); default=fm",
          "m_out": "-model fmfm: filename for the learned blocks g < h as text, one line 'g h' and then k rows each",
          "r_out": "-model fwfm: filename for the learned field matrix as text, one row per line"}
 
@@ -381,6 +384,11 @@ def _main(argv):
         raise ValueError("-load_snapshot belongs to -method serve")
     init_stdev = float(a.get("init_stdev", "0.1"))
     dim = [int(x) for x in split_list(a.get("dim", "1,1,8"))]
+    k3 = 0                                               # -model hofm: a fourth number, the third-order factors
+    if len(dim) == 4 and a.get("model") == "hofm":
+        k3 = dim.pop()
+        if k3 < 0:
+            raise ValueError("-dim needs k3 >= 0 with -model hofm")
     if len(dim) != 3:
         raise ValueError("-dim needs k0,k1,k2")
     if method == "mcmc" and ("save_model" in a or "load_model" in a):
@@ -457,7 +465,7 @@ def _main(argv):
     model = a.get("model", "fm")
     if "model" in a or "r_out" in a or "m_out" in a:
         if model not in L.FMLearnSGD.MODELS:
-            raise ValueError("-model knows fm, fwfm, ffm and fmfm, not '%s'" % model)
+            raise ValueError("-model knows fm, fwfm, ffm, fmfm and hofm, not '%s'" % model)
         if model != "fwfm" and "r_out" in a:
             raise ValueError("-r_out belongs to -model fwfm")
         if model != "fmfm" and "m_out" in a:
@@ -466,7 +474,7 @@ def _main(argv):
             if method != "sgd" or optimizer != "adagrad":
                 raise ValueError("-model %s belongs to -method sgd with -optimizer adagrad, not -method %s%s"
                                  % (model, method, " -optimizer " + optimizer if method in ("sgd", "bpr") else ""))
-            if not a.get("meta"):
+            if model in L.FMLearnSGD.FIELD_MODELS and not a.get("meta"):
                 raise ValueError("-model %s needs -meta: the fields are its groups" % model)
             for f in ("devices", "relation", "serve", "topk", "metrics", "train_weights", "save_checkpoint", "load_checkpoint"):
                 if f in a:
@@ -622,6 +630,7 @@ def _main(argv):
     if model == "ffm":                                   # one vector of -dim's k per field: F k columns per feature (F: the -meta map's)
         with open(a["meta"]) as f:
             v_rows *= max([int(x) for x in f.read().split()[:fm.num_attribute]], default=0) + 1
+    v_rows += k3                                         # -model hofm: the third-order factors follow the pairwise ones
     fm.v = R.init_v(v_rows, fm.num_attribute, fm.init_mean, fm.init_stdev)           # fm_model.h:96
     if "load_model" in a:
         print("Reading FM model... \t")
@@ -704,7 +713,7 @@ def _main(argv):
                 l.ftrl_alpha, l.ftrl_beta = float(a.get("ftrl_alpha", "0")), float(a.get("ftrl_beta", "1"))
                 l.l1_w, l.l1_v = ftrl_l1
         if model != "fm":
-            l.model, l.groups = model, groups
+            l.model, l.groups, l.num_factor3 = model, groups, k3
     else:
         if method == "als":
             l = L.FMLearnALS()

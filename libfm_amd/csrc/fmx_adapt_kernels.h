@@ -32,11 +32,17 @@ namespace fmx {
 // A source with COLUMN_SELF (the field-aware FM, fmx_ffm_kernels.h) has an own term in the columns [own_begin(j), own_begin(j) +
 // own_width()) alone, with the factor 1, in place of self(j); and a stride() whose live(off) is not constantly true masks the loads of
 // a sum row to the lanes it covers (the others read zeros).
+// A source with SECOND (the third-order FM, fmx_hofm_kernels.h) brings a second row per occurrence, weighted by mult x x, and the
+// scalar sum of mult x x x (seg_tail's SEC, fmx_kernels.h): second<VEC>() is that SEC with its sums at zero, and in the columns where
+// third(col) holds the own term is v G2 - v v A3 in place of v A.  SECOND is a compile-time constant, false for every other source:
+// their owners are compiled from the expressions they had before it existed.
 struct PlainSums {
-  static constexpr bool PLAIN = true, COLUMN_SELF = false;
+  static constexpr bool PLAIN = true, COLUMN_SELF = false, SECOND = false;
   template <int KP> __device__ __forceinline__ const float* base(const float* S, uint32_t) const { return S; }
   __device__ __forceinline__ RowStrideKP stride() const { return RowStrideKP(); }
 };
+template <class Sum, int VEC, bool ON = Sum::SECOND> struct SecondOf { typedef NoSecond type; };
+template <class Sum, int VEC> struct SecondOf<Sum, VEC, true> { typedef typename Sum::template Second<VEC> type; };
 
 template <class R, int KP, int U, class Sum = PlainSums>
 __device__ __forceinline__ void stateful_seg_block(const SegWork& sw, uint32_t blk, const Tab tb, const R& rule, const Hyper& h,
@@ -60,6 +66,7 @@ __device__ __forceinline__ void stateful_seg_block(const SegWork& sw, uint32_t b
   for (uint32_t i = 0; i < cnt; i += EPI * U) {
     float v0[U][VEC], s0[U][NT][VEC], sf[U][VEC];
     float wv0[U], sw0[U][NT];
+    [[maybe_unused]] float sf2[U][Sum::SECOND ? VEC : 1];
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const uint32_t idx = i + u * EPI + g;
@@ -82,6 +89,14 @@ __device__ __forceinline__ void stateful_seg_block(const SegWork& sw, uint32_t b
 #pragma unroll
           for (int v = 0; v < VEC; v++) sf[u][v] = 0.f;
         }
+        if constexpr (Sum::SECOND) {
+          const auto sec = sum.template second<VEC>();
+          if (sec.live(f * VEC)) load_vec<VEC>(sec.row(e, f * VEC), sf2[u]);
+          else {
+#pragma unroll
+            for (int v = 0; v < VEC; v++) sf2[u][v] = 0.f;
+          }
+        }
       }
     }
 #pragma unroll
@@ -98,10 +113,18 @@ __device__ __forceinline__ void stateful_seg_block(const SegWork& sw, uint32_t b
 #pragma unroll
         for (int v = 0; v < VEC; v++) G[v] = mx * sf[u][v];
         A = mx * x; Gw = mx;
-        seg_tail<KP>(t_ent, sum.template base<KP>(S, j), mult, a + 1, b, lane, f, G, A, Gw, TEntry{0u, 0.f}, 0.f, sum.stride());
+        typename SecondOf<Sum, VEC>::type sec;
+        if constexpr (Sum::SECOND) {
+          sec = sum.template second<VEC>();
+          const float mxx = mx * x;
+#pragma unroll
+          for (int v = 0; v < VEC; v++) sec.G2[v] = mxx * sf2[u][v];
+          sec.A3 = mxx * x;
+        }
+        seg_tail<KP>(t_ent, sum.template base<KP>(S, j), mult, a + 1, b, lane, f, G, A, Gw, TEntry{0u, 0.f}, 0.f, sum.stride(), sec);
         uint32_t own0 = 0;
         if constexpr (Sum::COLUMN_SELF) own0 = sum.own_begin(j);
-        else if constexpr (!Sum::PLAIN) A *= sum.self(j);
+        else if constexpr (!Sum::PLAIN && !Sum::SECOND) A *= sum.self(j);
         const float nocc = (float)(b - a);
         float nv[VEC];
 #pragma unroll
@@ -112,6 +135,12 @@ __device__ __forceinline__ void stateful_seg_block(const SegWork& sw, uint32_t b
           if constexpr (Sum::COLUMN_SELF) Av = (f * VEC + (uint32_t)v - own0 < sum.own_width()) ? A : 0.f;
           if constexpr (R::REG) gr = G[v] - vv * Av + nocc * h.regv * vv;
           else gr = G[v] - vv * Av;
+          if constexpr (Sum::SECOND) {
+            if (sum.third(f * VEC + (uint32_t)v)) {
+              if constexpr (R::REG) gr = G[v] - vv * sec.G2[v] + vv * vv * sec.A3 + nocc * h.regv * vv;
+              else gr = G[v] - vv * sec.G2[v] + vv * vv * sec.A3;
+            }
+          }
 #pragma unroll
           for (int t = 0; t < NT; t++) s[t] = s0[u][t][v];
           nv[v] = rule.step_v(gr, vv, s);

@@ -542,6 +542,7 @@ int fmx_destroy(fmx_handle h) {
   fwfm_free(h);
   ffm_free(h);
   fmfm_free(h);
+  hofm_free(h);
   compact_free(h);
   for (auto& s : h->slots) free_slot(s);
   if (h->grp) fmx_dev_free(h->grp);

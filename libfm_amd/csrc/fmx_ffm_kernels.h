@@ -188,7 +188,7 @@ struct FfmStride {
   __device__ __forceinline__ bool live(uint32_t off) const { return off < rw; }
 };
 struct FfmSums {
-  static constexpr bool PLAIN = false, COLUMN_SELF = true;
+  static constexpr bool PLAIN = false, COLUMN_SELF = true, SECOND = false;
   const float* Qt; const uint32_t* grp;
   uint32_t kf, rw, ex_stride;                                      // ex_stride = F * rw floats between two examples' rows
   __device__ __forceinline__ uint32_t field(uint32_t j) const { return grp ? grp[j] : 0u; }

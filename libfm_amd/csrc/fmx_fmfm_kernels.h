@@ -231,7 +231,7 @@ k_fmfm_gemm_t(const float* __restrict__ S, const float* __restrict__ MM, const f
 // T[e][g KP ..] for its occurrence in example e -- T + g KP with a stride of WP floats -- and its own term has the factor 1 (M[g][g] = I).
 // ----------------------------------------------------------------------------------------------
 struct FmfmSums {
-  static constexpr bool PLAIN = false, COLUMN_SELF = false;
+  static constexpr bool PLAIN = false, COLUMN_SELF = false, SECOND = false;
   const float* T; const uint32_t* grp; uint32_t WP;
   __device__ __forceinline__ uint32_t field(uint32_t j) const { return grp ? grp[j] : 0u; }
   template <int KP> __device__ __forceinline__ const float* base(const float*, uint32_t j) const { return T + (size_t)field(j) * KP; }

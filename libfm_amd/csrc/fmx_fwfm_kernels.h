@@ -167,7 +167,7 @@ k_fwfm_rows(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr,
 // row (e FP + g) KP of T for its occurrence in example e -- T + g KP with a stride of FP KP floats -- and its own term carries r_gg.
 // ----------------------------------------------------------------------------------------------
 struct FwfmSums {
-  static constexpr bool PLAIN = false, COLUMN_SELF = false;
+  static constexpr bool PLAIN = false, COLUMN_SELF = false, SECOND = false;
   const float* T; const uint32_t* grp; const float* R;             // R: the fp32 copy [FP][FP]
   uint32_t FP, ex_stride;                                          // ex_stride = FP * KP floats between two examples' T rows
   __device__ __forceinline__ uint32_t field(uint32_t j) const { return grp ? grp[j] : 0u; }

@@ -1762,12 +1762,20 @@ struct RowStrideRT {
   template <int KP> __device__ __forceinline__ size_t of() const { return (size_t)s; }
   __device__ __forceinline__ constexpr bool live(uint32_t) const { return true; }
 };
-template <int KP, bool PRE = false, class RS = RowStrideKP>
+// SEC: a SECOND sum row per occurrence, weighted by mult x x, and a third scalar (the third-order FM, fmx_hofm_kernels.h).  A SEC with ON
+// carries its own sums and says where an example's second row stands:
+//     live(off), row(e, off)   as rs.live and S + e stride + off, for the second rows;
+//     G2[VEC], A3              the sums of mult x x row2_f and of mult x x x, added here in the same occurrence order.
+// Its rounds hold half as many occurrences, since each brings two rows.  NoSecond, the default, adds nothing: ON is a compile-time
+// constant and every owner without a second row compiles from the expressions it had before.
+struct NoSecond { static constexpr bool ON = false; };
+template <int KP, bool PRE = false, class RS = RowStrideKP, class SEC = NoSecond>
 __device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const float* __restrict__ S, const float* __restrict__ mult,
                                          uint32_t i2, const uint32_t b, const uint32_t lane, const uint32_t f,
                                          float (&G)[Map<KP>::VEC], float& A, float& Gw, const TEntry te_pre = TEntry{0u, 0.f}, const float tm_pre = 0.f,
-                                         const RS rs = RS()) {
+                                         const RS rs = RS(), SEC&& sec = SEC()) {
   constexpr int VEC = Map<KP>::VEC, EPI = Map<KP>::EPI;
+  constexpr bool SECOND = std::remove_reference_t<SEC>::ON;
   // further occurrences of the feature in this batch (a frequent feature of Criteo-shaped rows has dozens to thousands per
   // batch).  Added in occurrence order, so the result does not depend on how they are fetched:
   if constexpr (EPI == 1) {
@@ -1776,7 +1784,7 @@ __device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const
     // v_readlane -- per TL occurrences ONE dependent round trip instead of three per occurrence.
     // (32 rows per round for the one-segment-per-wavefront path was measured in round 4: k_apply_seg_scan 7.6 -> 8.1 us per
     //  512-row batch of Criteo-shaped rows -- most segments there hold ~8 occurrences and pay for the longer unrolled round)
-    constexpr int TL = (VEC == 1) ? 16 : 8;
+    constexpr int TL = ((VEC == 1) ? 16 : 8) / (SECOND ? 2 : 1);
     for (uint32_t base = i2; base < b; base += 64) {
       const uint32_t cc = min(64u, b - base);
       TEntry te; te.e = 0; te.x = 0.f; float tm = 0.f;
@@ -1784,6 +1792,7 @@ __device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const
       else if (lane < cc) { te = load_stream8(t_ent + base + lane); tm = mult[te.e]; }
       for (uint32_t q0 = 0; q0 < cc; q0 += TL) {
         float s2[TL][VEC];
+        [[maybe_unused]] float r2[TL][SECOND ? VEC : 1];
 #pragma unroll
         for (int q = 0; q < TL; q++) {
           const uint32_t e2 = bcast_u32<1>(te.e, (q0 + q) & 63u);
@@ -1791,6 +1800,13 @@ __device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const
           else {
 #pragma unroll
             for (int v = 0; v < VEC; v++) s2[q][v] = 0.f;
+          }
+          if constexpr (SECOND) {
+            if (q0 + q < cc && sec.live(f * VEC)) load_vec<VEC>(sec.row(e2, f * VEC), r2[q]);
+            else {
+#pragma unroll
+              for (int v = 0; v < VEC; v++) r2[q][v] = 0.f;
+            }
           }
         }
 #pragma unroll
@@ -1801,15 +1817,22 @@ __device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const
 #pragma unroll
             for (int v = 0; v < VEC; v++) G[v] = fmaf(mx2, s2[q][v], G[v]);
             A = fmaf(mx2, x2, A); Gw += mx2;
+            if constexpr (SECOND) {
+              const float mxx2 = mx2 * x2;
+#pragma unroll
+              for (int v = 0; v < VEC; v++) sec.G2[v] = fmaf(mxx2, r2[q][v], sec.G2[v]);
+              sec.A3 = fmaf(mxx2, x2, sec.A3);
+            }
           }
         }
       }
     }
   } else {
     // several rows per wave-wide load (KP < 64): every lane group walks its own segment, TL occurrences at a time
-    constexpr int TL = 8;
+    constexpr int TL = SECOND ? 4 : 8;
     for (; i2 < b; i2 += TL) {
       TEntry tt[TL]; float mm[TL]; float s2[TL][VEC];
+      [[maybe_unused]] float r2[TL][SECOND ? VEC : 1];
 #pragma unroll
       for (int q = 0; q < TL; q++) { tt[q].e = 0; tt[q].x = 0.f; if (i2 + q < b) tt[q] = t_ent[i2 + q]; }
 #pragma unroll
@@ -1821,6 +1844,13 @@ __device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const
 #pragma unroll
           for (int v = 0; v < VEC; v++) s2[q][v] = 0.f;
         }
+        if constexpr (SECOND) {
+          if (i2 + q < b && sec.live(f * VEC)) load_vec<VEC>(sec.row(tt[q].e, f * VEC), r2[q]);
+          else {
+#pragma unroll
+            for (int v = 0; v < VEC; v++) r2[q][v] = 0.f;
+          }
+        }
       }
 #pragma unroll
       for (int q = 0; q < TL; q++) {
@@ -1829,6 +1859,12 @@ __device__ __forceinline__ void seg_tail(const TEntry* __restrict__ t_ent, const
 #pragma unroll
           for (int v = 0; v < VEC; v++) G[v] = fmaf(mx2, s2[q][v], G[v]);
           A = fmaf(mx2, tt[q].x, A); Gw += mx2;
+          if constexpr (SECOND) {
+            const float mxx2 = mx2 * tt[q].x;
+#pragma unroll
+            for (int v = 0; v < VEC; v++) sec.G2[v] = fmaf(mxx2, r2[q][v], sec.G2[v]);
+            sec.A3 = fmaf(mxx2, tt[q].x, sec.A3);
+          }
         }
       }
     }

@@ -105,7 +105,7 @@ class FMModel:
                 pos += self.num_attribute
             pos += 1
             rows = [[float(x) for x in ln.split(" ") if x != ""] for ln in lines[pos:pos + self.num_attribute]]
-            width = self.num_factor if self.v is None else self.v.shape[0]      # (model ffm: one vector of num_factor per field)
+            width = self.num_factor if self.v is None else self.v.shape[0]      # (model ffm: one vector of num_factor per field; hofm: num_factor3 more)
             if len(rows) != self.num_attribute or any(len(r) != width for r in rows):
                 return False
             self.v = np.ascontiguousarray(np.array(rows, dtype=np.float64).reshape(self.num_attribute, width).T)
@@ -319,11 +319,16 @@ class FMLearnSGD:
     used against field h, F the number of fields `groups` names -- and the handle is created with that many factors.
     'fmfm' is the field-matrixed FM (fmx_fmfm_*), again under the same requirements and with the same refusals: one learned k x k
     matrix per pair of fields over the same w and V, which `.m` returns ([F][F][k][k]); fmfm_learn_rate (0 = the AdaGrad eta),
-    fmfm_init_acc (0 = 1.0) and fmfm_reg are the matrices' own step constants."""
+    fmfm_init_acc (0 = 1.0) and fmfm_reg are the matrices' own step constants.
+    'hofm' is the third-order FM (fmx_hofm_*): optimizer 'adagrad' is required, `groups` is not read, and everything the field
+    models refuse is refused here too.  fm.num_factor stays the number of pairwise factors k2 and num_factor3 adds k3 third-order
+    factors: fm.v holds k2 + num_factor3 rows, the last num_factor3 of them the third-order factors, and the handle is created with
+    that many."""
 
     OPTIMIZERS = ("sgd", "adagrad", "ftrl")
-    MODELS = ("fm", "fwfm", "ffm", "fmfm")
+    MODELS = ("fm", "fwfm", "ffm", "fmfm", "hofm")
     FIELD_MODELS = {"fwfm": "field-weighted", "ffm": "field-aware", "fmfm": "field-matrixed"}      # the models over `groups`, with what the messages call them
+    SESSION_MODELS = dict(FIELD_MODELS, hofm="third-order")     # every model that is a session next to the AdaGrad session
     SHARDED_OPTIMIZERS = ("adagrad", "ftrl")                    # what `devices` with more than one entry is honoured for
     MODES = {"sequential": capi.SGD_SEQUENTIAL, "minibatch": capi.SGD_MINIBATCH, "hogwild": capi.SGD_HOGWILD}
     APPLY = {"default": capi.APPLY_DEFAULT, "atomic": capi.APPLY_ATOMIC, "store": capi.APPLY_STORE,
@@ -347,6 +352,7 @@ class FMLearnSGD:
         self.groups = None                                      # model 'fwfm': attribute -> field
         self.fwfm_learn_rate, self.fwfm_init_acc, self.fwfm_reg = 0.0, 0.0, 0.0
         self.fmfm_learn_rate, self.fmfm_init_acc, self.fmfm_reg = 0.0, 0.0, 0.0
+        self.num_factor3 = 0                                    # model 'hofm': third-order factors, next to fm.num_factor pairwise ones
         self.init_acc = 0.0
         self.adapt_learn_rate = 0.0
         self.ftrl_alpha = 0.0
@@ -369,19 +375,22 @@ class FMLearnSGD:
         self._fwfm_open = False
         self._ffm_open = False
         self._fmfm_open = False
+        self._hofm_open = False
         self._checkpoint = None                                 # load_checkpoint before init(): the file init() starts from
 
     def _check_model(self):
         if self.model not in self.MODELS:
             raise ValueError("unknown model for %s: %s (%s)" % (type(self).__name__, self.model, " | ".join(self.MODELS)))
-        if self.model not in self.FIELD_MODELS:
+        if self.model not in self.SESSION_MODELS:
             return
         if type(self) is not FMLearnSGD:
             raise NotImplementedError("%s has no %s form: model %s belongs to FMLearnSGD"
-                                      % (type(self).__name__, self.FIELD_MODELS[self.model], self.model))
+                                      % (type(self).__name__, self.SESSION_MODELS[self.model], self.model))
         if self.optimizer != "adagrad":
             raise ValueError("model %s trains with optimizer adagrad, not %s" % (self.model, self.optimizer))
-        if self.groups is None:
+        if self.model == "hofm" and int(self.num_factor3) < 0:
+            raise ValueError("model hofm: num_factor3 must be >= 0")
+        if self.model in self.FIELD_MODELS and self.groups is None:
             raise ValueError("model %s needs groups: the attribute -> field map" % self.model)
         self._not_on_shards("model %s" % self.model)
         for what, on in (("load_checkpoint", self._checkpoint is not None), ("set_weights", bool(self._weights)),
@@ -390,7 +399,7 @@ class FMLearnSGD:
                 raise NotImplementedError("%s is not supported with model %s" % (what, self.model))
 
     def _not_under_fwfm(self, what):
-        if self.model in self.FIELD_MODELS:
+        if self.model in self.SESSION_MODELS:
             raise NotImplementedError("%s is not supported with model %s: it scores the plain FM" % (what, self.model))
 
     def _ffm_fields(self):
@@ -463,6 +472,8 @@ class FMLearnSGD:
         if self.devices is not None and len(self.devices) == 1:
             self.device = int(self.devices[0])
         width = fm.num_factor * self._ffm_fields() if self.model == "ffm" else fm.num_factor
+        if self.model == "hofm":
+            width += int(self.num_factor3)
         self._h = capi.Handle(fm.num_attribute, width, fm.k0, fm.k1, self.task, fm.reg0, fm.regw, fm.regv,
                               self.learn_rate, self.min_target, self.max_target, device=self.device)
         if self._checkpoint is not None:                        # the file's parameters and session, not fm's and a fresh one
@@ -493,6 +504,9 @@ class FMLearnSGD:
             self._h.set_groups(self.groups)
             self._h.fmfm_begin(self.fmfm_learn_rate, self.fmfm_init_acc, self.fmfm_reg)
             self._fmfm_open = True
+        if self.model == "hofm" and not self._hofm_open:
+            self._h.hofm_begin(self.num_factor3)
+            self._hofm_open = True
 
     def save_checkpoint(self, path, dense=False):
         """the exact binary checkpoint of the model on the device and of the open adagrad / ftrl session (fmx_checkpoint_save;
@@ -613,7 +627,8 @@ class FMLearnSGD:
         self._check_devices()
         if (self.optimizer == "adagrad") != self._adapt_open or (self.optimizer == "ftrl") != self._ftrl_open:
             raise ValueError("optimizer was changed after init()")
-        if (self.model == "fwfm") != self._fwfm_open or (self.model == "ffm") != self._ffm_open or (self.model == "fmfm") != self._fmfm_open:
+        if (self.model == "fwfm") != self._fwfm_open or (self.model == "ffm") != self._ffm_open or (self.model == "fmfm") != self._fmfm_open \
+                or (self.model == "hofm") != self._hofm_open:
             raise ValueError("model was changed after init()")
         if id(train) in self._weights and self.optimizer == "sgd":
             raise ValueError("the train set has weights (set_weights): optimizer sgd has no weighted form, use adagrad or ftrl")
@@ -634,6 +649,8 @@ class FMLearnSGD:
                 stats = self._h.ffm_epoch(st, self.batch, self.w0_chunk)
             elif self._fmfm_open:
                 stats = self._h.fmfm_epoch(st, self.batch, self.w0_chunk)
+            elif self._hofm_open:
+                stats = self._h.hofm_epoch(st, self.batch, self.w0_chunk)
             elif self._adapt_open:
                 stats = self._h.adapt_epoch(st, self.batch, self.w0_chunk)
             elif self._ftrl_open:
@@ -659,7 +676,7 @@ class FMLearnSGD:
     # fm_learn::evaluate (fm_learn.h:93-153): rmse for regression, accuracy for classification
     def evaluate(self, data):
         scorer = (self._h.fwfm_evaluate if self._fwfm_open else self._h.ffm_evaluate if self._ffm_open else
-                  self._h.fmfm_evaluate if self._fmfm_open else self._h.evaluate)
+                  self._h.fmfm_evaluate if self._fmfm_open else self._h.hofm_evaluate if self._hofm_open else self._h.evaluate)
         ev = scorer(self._slot(data))
         return ev.rmse if self.task == TASK_REGRESSION else ev.accuracy
 
@@ -678,6 +695,8 @@ class FMLearnSGD:
             return self._h.ffm_predict(self._slot(data), data.num_cases)
         if self._fmfm_open:
             return self._h.fmfm_predict(self._slot(data), data.num_cases)
+        if self._hofm_open:
+            return self._h.hofm_predict(self._slot(data), data.num_cases)
         return self._h.predict(self._slot(data), data.num_cases)
 
     def recommend(self, queries, candidates, topk, exclude=None):
@@ -733,6 +752,9 @@ class FMLearnSGD:
             if self._fmfm_open:
                 self._h.fmfm_end()
                 self._fmfm_open = False
+            if self._hofm_open:
+                self._h.hofm_end()
+                self._hofm_open = False
             if self._adapt_open:
                 self._h.adapt_end()
                 self._adapt_open = False
