@@ -1733,6 +1733,58 @@ int fmx_hofm_evaluate(fmx_handle h, int slot, fmx_eval *out);
 int fmx_hofm_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
 int fmx_hofm_end(fmx_handle h);
 
+/* ---- DeepFM with one hidden layer (Guo et al., IJCAI 2017) -------------------------------------------------
+ *   s    = (S[0], ..., S[F-1])          S[g] = sum_{b: g(j_b) = g} x_b v_jb        (k floats per field; b: the row's entries)
+ *   a    = relu(W1^T s + b1)            W1: [F k][H], b1: [H]
+ *   y(x) = w0 + sum_j w_j x_j + 1/2 (|sum_g S[g]|^2 - D) + <w2, a>                 w2: [H];  D = sum_b |x_b v_jb|^2
+ * g() is the feature -> field map of fmx_set_groups (none: one field), F = num_groups, k = num_factor, H = num_hidden.  The FM part and
+ * the net read the same V.  There is no output bias (w0 is one).  The ReLU mask is `pre-activation > 0`: a net that is all zero IS the
+ * plain FM and stays the plain FM, because nothing in it ever receives a gradient.  An id repeated inside a row counts as separate
+ * entries.  The session owns W1, b1, w2 and their AdaGrad accumulators; w, V and their accumulators stay the handle's, and fmx_predict
+ * and every other existing call keep scoring the plain FM.  Added without an ABI version change: a caller detects the feature by the
+ * symbol fmx_dfm_begin.
+ *
+ * With dh = [a > 0] w2, z = W1 dh and Stot = sum_g S[g]:  d/dv_i = x_i (Stot + z_g(i) - v_i x_i),  d/dW1 = s dh^T,  d/db1 = dh,  d/dw2 = a.
+ *
+ *   fmx_dfm_begin    : the net zero, its accumulators init_acc.  Called again it resets both.  The caller sets start values.
+ *   fmx_dfm_set_net  : W1[(g k + c) H + u] multiplies factor c of field g's sum into unit u; b1[u]; w2[u].  Refuses a value that is not
+ *                      finite.  The accumulators keep their values.
+ *   fmx_dfm_get_net  : the net and / or its accumulators in the same layouts; any pointer may be NULL.
+ *   fmx_dfm_predict  : fmx_predict's contract under the session's net.
+ *   fmx_dfm_evaluate : fmx_evaluate's contract under the session's net.
+ *   fmx_dfm_epoch    : fmx_adapt_epoch's contract (batch, w0_chunk, stats, an empty slot) with DeepFM's sums and gradients.  It needs an
+ *                      open fmx_adapt session and steps w and V on THAT session's accumulators with its eta, from the batch-start
+ *                      parameters; the bias keeps its micro-chunk SGD.  Per batch every element of W1, b1 and w2 then takes
+ *                      g = sum_e mult_e d y_e / d theta + reg theta,  n += g^2,  theta -= learn_rate g / sqrt(n)  in fp64.  No float
+ *                      atomics anywhere: two runs give the same bits.
+ *   fmx_dfm_end      : frees the net, its accumulators and the session's scratch.
+ * Limits (FMX_E_UNSUPPORTED beyond): at most 64 fields, 1 <= num_factor <= 128, F x (num_factor rounded up to a power of two), rounded
+ * up to 16, at most 2048 columns (WP), 1 <= num_hidden <= 512.  Scratch: rows x (2 WP + HP + KP + 1) x 4 bytes (HP: num_hidden rounded
+ * up to 16) plus at most 8 x (WP + 2) x HP x 4 bytes for an epoch's largest batch; scoring works through pieces of at most 2^25 / WP rows.
+ * All of it is kept until fmx_dfm_end.
+ * Refusals, each before any launch, the handle usable afterwards.  FMX_E_ARG: NULL opts, W1, b1, w2 (_set_net) or out; flags != 0; an
+ * option that is negative or not finite; a value of the net that is not finite.  FMX_E_STATE: any call but _begin without a session;
+ * num_groups changed under the session; fmx_dfm_epoch without an fmx_adapt session; a slot never uploaded, or without targets for
+ * _epoch and _evaluate; an open SGDA or ALS / MCMC session; fmx_dfm_begin while an fmx_fwfm, fmx_ffm, fmx_fmfm or fmx_hofm session is
+ * open, and their _begin while this one is.  FMX_E_UNSUPPORTED: a feature shard or communicator rank; kept `-relation` blocks; a slot
+ * with row weights; the limits above.
+ * Not offered under it: more than one hidden layer, dropout, batch normalisation, other activations, FTRL, the pairwise epochs,
+ * fmx_evaluate_ex / _by_query / _rank, fmx_topk, the net in checkpoints or snapshots, feature shards, row weights. */
+typedef struct fmx_dfm_opts {
+  uint32_t num_hidden;     /* H: hidden units, 1 .. 512 */
+  double learn_rate;       /* eta of the net's AdaGrad step; 0 = the eta of the fmx_adapt session */
+  double init_acc;         /* the net's accumulators at _begin; 0 = 1.0 */
+  double reg;              /* L2 on W1, b1 and w2, once per batch; 0 = none */
+  uint32_t flags;          /* 0 */
+} fmx_dfm_opts;
+int fmx_dfm_begin(fmx_handle h, const fmx_dfm_opts *opts);
+int fmx_dfm_set_net(fmx_handle h, const double *W1 /* [F k][H] */, const double *b1 /* [H] */, const double *w2 /* [H] */);
+int fmx_dfm_get_net(fmx_handle h, double *W1, double *b1, double *w2, double *n_W1, double *n_b1, double *n_w2 /* any may be NULL */);
+int fmx_dfm_predict(fmx_handle h, int slot, double *out);
+int fmx_dfm_evaluate(fmx_handle h, int slot, fmx_eval *out);
+int fmx_dfm_epoch(fmx_handle h, int slot, uint32_t batch, uint32_t w0_chunk, fmx_epoch_stats *stats);
+int fmx_dfm_end(fmx_handle h);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 typedef struct fmx_info {
   uint64_t n_local;         /* features held by this handle */

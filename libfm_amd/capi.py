@@ -87,6 +87,10 @@ class HofmOpts(C.Structure):                       # fmx_hofm_opts
     _fields_ = [("num_factor3", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class DfmOpts(C.Structure):                        # fmx_dfm_opts
+    _fields_ = [("num_hidden", C.c_uint32), ("learn_rate", C.c_double), ("init_acc", C.c_double), ("reg", C.c_double), ("flags", C.c_uint32)]
+
+
 class FmfmOpts(C.Structure):                       # fmx_fmfm_opts
     _fields_ = [("learn_rate_m", C.c_double), ("init_acc_m", C.c_double), ("reg_m", C.c_double), ("flags", C.c_uint32)]
 
@@ -464,6 +468,13 @@ SYMBOLS = [
     ("fmx_hofm_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
     ("fmx_hofm_epoch", C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
     ("fmx_hofm_end", C.c_int, [H]),
+    ("fmx_dfm_begin", C.c_int, [H, C.POINTER(DfmOpts)]),
+    ("fmx_dfm_set_net", C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("fmx_dfm_get_net", C.c_int, [H] + [C.c_void_p] * 6),
+    ("fmx_dfm_predict", C.c_int, [H, C.c_int, C.c_void_p]),
+    ("fmx_dfm_evaluate", C.c_int, [H, C.c_int, C.POINTER(Eval)]),
+    ("fmx_dfm_epoch", C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(EpochStats)]),
+    ("fmx_dfm_end", C.c_int, [H]),
     ("fmx_get_info", C.c_int, [H, C.POINTER(Info)]),
     ("fmx_synchronize", C.c_int, [H]),
 ]
@@ -1130,6 +1141,46 @@ class Handle:
 
     def hofm_end(self):
         self._chk(self.lib.fmx_hofm_end(self.h))
+
+    # DeepFM with one hidden layer (include/fmx.h "fmx_dfm_*"): fields = the groups of set_groups, an MLP over the field sums ------
+    def dfm_begin(self, num_hidden, learn_rate=0.0, init_acc=0.0, reg=0.0):
+        self._chk(self.lib.fmx_dfm_begin(self.h, C.byref(DfmOpts(int(num_hidden), float(learn_rate), float(init_acc), float(reg), 0))))
+        self._dfm_hidden = int(num_hidden)
+
+    def _dfm_arrays(self):
+        H = self._dfm_hidden
+        return np.zeros((self.G * self.k, H), dtype=np.float64), np.zeros(H, dtype=np.float64), np.zeros(H, dtype=np.float64)
+
+    def dfm_set_net(self, W1, b1, w2):
+        net = [np.ascontiguousarray(a, dtype=np.float64) for a in (W1, b1, w2)]
+        want = [a.shape for a in self._dfm_arrays()]
+        if [a.shape for a in net] != want:
+            raise ValueError("dfm_set_net: need W1, b1, w2 of shapes %r, got %r" % (want, [a.shape for a in net]))
+        self._chk(self.lib.fmx_dfm_set_net(self.h, *[_ptr(a) for a in net]))
+
+    def dfm_get_net(self):
+        """((W1, b1, w2), (n_W1, n_b1, n_w2)): W1 is [F k][H]"""
+        net, acc = self._dfm_arrays(), self._dfm_arrays()
+        self._chk(self.lib.fmx_dfm_get_net(self.h, *[_ptr(a) for a in net + acc]))
+        return net, acc
+
+    def dfm_predict(self, slot, n_rows):
+        out = np.zeros(n_rows, dtype=np.float64)
+        self._chk(self.lib.fmx_dfm_predict(self.h, slot, _ptr(out)))
+        return out
+
+    def dfm_evaluate(self, slot):
+        ev = Eval()
+        self._chk(self.lib.fmx_dfm_evaluate(self.h, slot, C.byref(ev)))
+        return ev
+
+    def dfm_epoch(self, slot, batch=0, w0_chunk=0):
+        st = EpochStats()
+        self._chk(self.lib.fmx_dfm_epoch(self.h, int(slot), int(batch), int(w0_chunk), C.byref(st)))
+        return st
+
+    def dfm_end(self):
+        self._chk(self.lib.fmx_dfm_end(self.h))
 
     # FTRL-proximal with L1 on the minibatch rule (include/fmx.h "fmx_ftrl_*") -------------------
     def ftrl_begin(self, alpha=0.0, beta=1.0, l1_w=0.0, l1_v=0.0, l2_w=0.0, l2_v=0.0, init_acc=0.0):

@@ -89,6 +89,10 @@ same flags are refused as with -model fwfm, in the same words, and so is -r_out;
 -model hofm -dim k0,k1,k2,k3 (-method sgd -optimizer adagrad): the third-order FM (fmx_hofm_*): k2 pairwise and k3 third-order factors
 per feature, so -save_model / -load_model carry k2 + k3 columns, the third-order ones last.  No -meta is needed; the other flags are
 refused as with -model fwfm, in the same words.  A fourth -dim number without -model hofm stays the error it was.
+-model dfm -meta F -hidden H [-net_out FILE] (-method sgd -optimizer adagrad): DeepFM with one hidden layer (fmx_dfm_*): an MLP of H
+ReLU units (default 16) over the per-field sums of the same V, added to the FM's score; its start values are drawn from -seed with
+-init_stdev.  -net_out writes the net as text: b1, w2, then the F k rows of W1.  The same flags are refused as with -model fwfm, in the
+same words, and so are -r_out and -m_out; -hidden and -net_out are refused without -model dfm.
 """
 import os
 import sys
@@ -148,8 +152,11 @@ FLAGS = {"task": "r=regression, c=binary classification [MANDATORY]", "meta": "f
          "save_snapshot": "with -serve: filename for the snapshot file of the frozen copy, written after it is taken",
          "load_snapshot": "-method serve: filename of the snapshot file to score from (no model is created; -train and -dim are not needed)",
          "devices": "'D0,D1,...': -method sgd with -optimizer adagrad | ftrl over one feature shard per listed device ordinal ('0,0': two shards on device 0)",
-         "model": "fm | fwfm | ffm | fmfm | hofm (-method sgd -optimizer adagrad; -meta F but for hofm): fwfm learns one interaction strength per pair of the fields -meta names, "
-                  "ffm one vector of -dim's k factors per feature and field, fmfm one k x k matrix per pair of fields, hofm adds k3 third-order factors (-dim k0,k1,k2,k3); default=fm",
+         "model": "fm | fwfm | ffm | fmfm | hofm | dfm (-method sgd -optimizer adagrad; -meta F but for hofm): fwfm learns one interaction strength per pair of the fields -meta names, "
+                  "ffm one vector of -dim's k factors per feature and field, fmfm one k x k matrix per pair of fields, hofm adds k3 third-order factors (-dim k0,k1,k2,k3), "
+                  "dfm an MLP of -hidden ReLU units over the field sums; default=fm",
+         "hidden": "-model dfm: hidden units of the MLP; default=16",
+         "net_out": "-model dfm: filename for the learned net as text: b1, w2, then the rows of W1",
          "m_out": "-model fmfm: filename for the learned blocks g < h as text, one line 'g h' and then k rows each",
          "r_out": "-model fwfm: filename for the learned field matrix as text, one row per line"}
 
@@ -463,13 +470,18 @@ def _main(argv):
         if not devices or any(d < 0 for d in devices) or len(devices) > 16:
             raise ValueError("-devices needs 1 .. 16 device ordinals >= 0: 'D0,D1,...'")
     model = a.get("model", "fm")
-    if "model" in a or "r_out" in a or "m_out" in a:
+    if "model" in a or "r_out" in a or "m_out" in a or "hidden" in a or "net_out" in a:
         if model not in L.FMLearnSGD.MODELS:
-            raise ValueError("-model knows fm, fwfm, ffm, fmfm and hofm, not '%s'" % model)
+            raise ValueError("-model knows fm, fwfm, ffm, fmfm, hofm and dfm, not '%s'" % model)
         if model != "fwfm" and "r_out" in a:
             raise ValueError("-r_out belongs to -model fwfm")
         if model != "fmfm" and "m_out" in a:
             raise ValueError("-m_out belongs to -model fmfm")
+        for f in ("hidden", "net_out"):
+            if model != "dfm" and f in a:
+                raise ValueError("-%s belongs to -model dfm" % f)
+        if model == "dfm" and int(a.get("hidden", "16")) < 1:
+            raise ValueError("-hidden needs H >= 1")
         if model != "fm":
             if method != "sgd" or optimizer != "adagrad":
                 raise ValueError("-model %s belongs to -method sgd with -optimizer adagrad, not -method %s%s"
@@ -483,6 +495,8 @@ def _main(argv):
                 raise ValueError("-r_out needs a filename")
             if "m_out" in a and not a["m_out"]:
                 raise ValueError("-m_out needs a filename")
+            if "net_out" in a and not a["net_out"]:
+                raise ValueError("-net_out needs a filename")
     serve = a.get("serve")
     if "serve" in a:
         if serve not in C.FORMATS:
@@ -714,6 +728,7 @@ def _main(argv):
                 l.l1_w, l.l1_v = ftrl_l1
         if model != "fm":
             l.model, l.groups, l.num_factor3 = model, groups, k3
+            l.num_hidden, l.seed, l.dfm_init_stdev = int(a.get("hidden", "16")), seed, init_stdev
     else:
         if method == "als":
             l = L.FMLearnALS()
@@ -791,6 +806,10 @@ def _main(argv):
             for g in range(m.shape[0]):
                 for h in range(g + 1, m.shape[0]):
                     f.write("%d %d\n" % (g, h) + "".join(" ".join("%g" % x for x in row) + "\n" for row in m[g, h]))
+    if "net_out" in a:
+        W1, b1, w2 = l.net
+        with open(a["net_out"], "w") as f:
+            f.write("".join(" ".join("%g" % x for x in row) + "\n" for row in [b1, w2] + list(W1)))
     if optimizer == "ftrl":
         sp = l.sparsity()
         print("sparsity\tfeatures=%d\tw_zero=%d\tv_coords=%d\tv_zero=%d\tv_zero_rows=%d\tdead_features=%d" %

@@ -543,6 +543,7 @@ int fmx_destroy(fmx_handle h) {
   ffm_free(h);
   fmfm_free(h);
   hofm_free(h);
+  dfm_free(h);
   compact_free(h);
   for (auto& s : h->slots) free_slot(s);
   if (h->grp) fmx_dev_free(h->grp);

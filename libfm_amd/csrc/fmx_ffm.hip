@@ -98,6 +98,7 @@ int fmx_ffm_begin(fmx_handle h, const fmx_ffm_opts* opts) {
   if (h->fwfm.open) return fail(h, FMX_E_STATE, "fmx_ffm_begin: a field-weighted FM session is open (call fmx_fwfm_end first)");
   if (h->fmfm.open) return fail(h, FMX_E_STATE, "fmx_ffm_begin: a field-matrixed FM session is open (call fmx_fmfm_end first)");
   if (h->hofm.open) return fail(h, FMX_E_STATE, "fmx_ffm_begin: a third-order FM session is open (call fmx_hofm_end first)");
+  if (h->dfm.open) return fail(h, FMX_E_STATE, "fmx_ffm_begin: a DeepFM session is open (call fmx_dfm_end first)");
   const uint32_t F = h->num_groups, kf = opts->num_latent;
   if (kf < 1 || (uint64_t)F * kf != (uint64_t)h->cfg.num_factor)
     return fail(h, FMX_E_ARG, "fmx_ffm_begin: num_factor %d is not %u fields x %u latent factors: create the handle with num_factor = fields x latent",

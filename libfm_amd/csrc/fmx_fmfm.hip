@@ -168,6 +168,7 @@ int fmx_fmfm_begin(fmx_handle h, const fmx_fmfm_opts* opts) {
   if (h->fwfm.open) return fail(h, FMX_E_STATE, "fmx_fmfm_begin: a field-weighted FM session is open (call fmx_fwfm_end first)");
   if (h->ffm.open) return fail(h, FMX_E_STATE, "fmx_fmfm_begin: a field-aware FM session is open (call fmx_ffm_end first)");
   if (h->hofm.open) return fail(h, FMX_E_STATE, "fmx_fmfm_begin: a third-order FM session is open (call fmx_hofm_end first)");
+  if (h->dfm.open) return fail(h, FMX_E_STATE, "fmx_fmfm_begin: a DeepFM session is open (call fmx_dfm_end first)");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   fmfm_free(h);

@@ -35,9 +35,12 @@ template <int KP> struct FmfmU { static constexpr int value = (KP <= 64) ? 8 : 4
 // of one round that fall into the SAME field are serialised by k_fwfm_rows' rule: a lane group counts the earlier groups of its round
 // with its field (c) and adds in pass c; passes are separated by a barrier (the workgroup is the wavefront).  Different fields never
 // share an address.  Stored: S_e (WP floats, zeros from F KP on), D_e and the linear part L_e -- scoring and training need the same
-// three, so the kernel has one form.
+// three, so the kernel has one form.  FOLD is the DeepFM's gather (fmx_dfm.hip; a compile-time switch, false for the FmFM): the tile
+// holds all field rows when the row ends, and the wavefront also sums them into Stot_e (KP floats, lane c column c, fields ascending),
+// which goes to Dg ([rows][KP]) in place of D_e, and stores base_e = L_e + 1/2 |Stot_e|^2 - 1/2 D_e in Lg in place of L_e (a lane's
+// columns squared in ascending order, then wave_sum_dpp).
 // ----------------------------------------------------------------------------------------------
-template <int KP>
+template <int KP, bool FOLD = false>
 __global__ void __launch_bounds__(64)
 k_fmfm_sums(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr, uint64_t row0, uint32_t n_rows, const Tab tb,
             const uint32_t* __restrict__ grp, uint32_t F, uint32_t WP, int k1, float* __restrict__ Sg, float* __restrict__ Dg,
@@ -115,7 +118,19 @@ k_fmfm_sums(const Entry* __restrict__ ent, const uint64_t* __restrict__ row_ptr,
     for (uint32_t t = lane; t < WP; t += 64u) Sg[(size_t)e * WP + t] = t < W ? tile[t] : 0.f;
     lin = wave_sum_dpp(lin);
     dl = wave_sum_dpp(dl);
-    if (lane == 0) { Lg[e] = lin; Dg[e] = dl; }
+    if constexpr (FOLD) {
+      float sq = 0.f;
+      for (uint32_t c = lane; c < (uint32_t)KP; c += 64u) {
+        float stot = 0.f;
+        for (uint32_t fg = 0; fg < F; fg++) stot += tile[fg * KP + c];
+        Dg[(size_t)e * KP + c] = stot;
+        sq = fmaf(stot, stot, sq);
+      }
+      sq = wave_sum_dpp(sq);
+      if (lane == 0) Lg[e] = fmaf(0.5f, sq, fmaf(-0.5f, dl, lin));
+    } else {
+      if (lane == 0) { Lg[e] = lin; Dg[e] = dl; }
+    }
     __syncthreads();
   }
 }

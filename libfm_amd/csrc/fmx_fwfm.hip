@@ -170,6 +170,7 @@ int fmx_fwfm_begin(fmx_handle h, const fmx_fwfm_opts* opts) {
   if (h->ffm.open) return fail(h, FMX_E_STATE, "fmx_fwfm_begin: a field-aware FM session is open (call fmx_ffm_end first)");
   if (h->fmfm.open) return fail(h, FMX_E_STATE, "fmx_fwfm_begin: a field-matrixed FM session is open (call fmx_fmfm_end first)");
   if (h->hofm.open) return fail(h, FMX_E_STATE, "fmx_fwfm_begin: a third-order FM session is open (call fmx_hofm_end first)");
+  if (h->dfm.open) return fail(h, FMX_E_STATE, "fmx_fwfm_begin: a DeepFM session is open (call fmx_dfm_end first)");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   fwfm_free(h);

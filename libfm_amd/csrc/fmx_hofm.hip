@@ -80,6 +80,7 @@ int fmx_hofm_begin(fmx_handle h, const fmx_hofm_opts* opts) {
   if (h->fwfm.open) return fail(h, FMX_E_STATE, "fmx_hofm_begin: a field-weighted FM session is open (call fmx_fwfm_end first)");
   if (h->ffm.open) return fail(h, FMX_E_STATE, "fmx_hofm_begin: a field-aware FM session is open (call fmx_ffm_end first)");
   if (h->fmfm.open) return fail(h, FMX_E_STATE, "fmx_hofm_begin: a field-matrixed FM session is open (call fmx_fmfm_end first)");
+  if (h->dfm.open) return fail(h, FMX_E_STATE, "fmx_hofm_begin: a DeepFM session is open (call fmx_dfm_end first)");
   if (opts->num_factor3 > (uint32_t)h->cfg.num_factor)
     return fail(h, FMX_E_ARG, "fmx_hofm_begin: num_factor3 %u exceeds num_factor %d: create the handle with num_factor = pairwise + third-order factors",
                 opts->num_factor3, h->cfg.num_factor);

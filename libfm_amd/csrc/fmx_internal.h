@@ -1,5 +1,5 @@
 // fmx_internal.h -- shared by the translation units of libfmx.so (fmx_core.hip, fmx_sgd.hip, fmx_als.hip, fmx_comm.hip, fmx_pair.hip, fmx_topk.hip,
-// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip, fmx_weighted.hip, fmx_ckpt.hip, fmx_snap.hip, fmx_fwfm.hip, fmx_ffm.hip, fmx_fmfm.hip, fmx_hofm.hip; fmx_io.hip needs
+// fmx_pairneg.hip, fmx_eval.hip, fmx_post.hip, fmx_evalq.hip, fmx_compact.hip, fmx_rankq.hip, fmx_mem.hip, fmx_weighted.hip, fmx_ckpt.hip, fmx_snap.hip, fmx_fwfm.hip, fmx_ffm.hip, fmx_fmfm.hip, fmx_hofm.hip, fmx_dfm.hip; fmx_io.hip needs
 // none of it).
 // The C-ABI is include/fmx.h; nothing declared here is exported.
 #pragma once
@@ -195,6 +195,11 @@ struct FmfmState { bool open = false; uint32_t F = 0, k = 0, WP = 0; double* m =
 // the column c0 the second rows begin at (k2 rounded down to the lane map's granularity), and the scratch of an epoch's largest batch
 // (H [rows][RW], then P [rows][RW - c0])
 struct HofmState { bool open = false; uint32_t k2 = 0, k3 = 0, RW = 0, c0 = 0; float* scratch = nullptr; size_t scratch_rows = 0; };
+// an open fmx_dfm_* session (fmx_dfm.hip): the net in fp64 (net64: W1 [F k][H], b1 [H], w2 [H], one behind the other) and its AdaGrad
+// accumulators in the same layout (acc64), the zero-padded fp32 copies the kernels read (net32: W1p [WP][HP], W1t [HP][WP], b1p [HP],
+// w2p [HP]; WP = F KP rounded up to 16, HP = H rounded up to 16), and the scratch of the largest batch seen
+struct DfmState { bool open = false; uint32_t F = 0, k = 0, WP = 0, H = 0, HP = 0; double* net64 = nullptr; double* acc64 = nullptr;
+                  float* net32 = nullptr; double eta = 0.0, init_acc = 1.0, reg = 0.0; float* scratch = nullptr; size_t scratch_floats = 0; };
 // the serving snapshot (fmx_compact_*, fmx_compact.hip): a frozen copy of w0 and, by format,
 //   FMX_COMPACT_BF16  w (fp32, stride 1) and V as bf16 rows of tb.rs elements
 //   FMX_COMPACT_INT8  B: one block of P bytes per feature with its scale, its w and its int8 codes (V and w stay null)
@@ -216,6 +221,7 @@ struct fmx_context_s {
   FfmState   ffm;
   FmfmState  fmfm;
   HofmState  hofm;
+  DfmState   dfm;
   CompactState compact;
   LagState   lag;
   int        KP = 1;
@@ -445,7 +451,7 @@ int param_sparsity_impl(fmx_handle h, bool in_group, fmx_sparsity* out);
 enum StatefulRule { STATEFUL_ADAGRAD = 1, STATEFUL_FTRL = 2 };
 int stateful_shard_prepare(fmx_handle h, int slot, uint32_t B);
 int stateful_shard_step(fmx_handle h, int slot, StatefulRule rule, uint64_t row0, uint32_t nb, uint32_t B, uint32_t chunk, const float* d_sum);
-// fmx_sgd.hip, for fmx_fwfm_epoch (fmx_fwfm.hip), fmx_ffm_epoch (fmx_ffm.hip), fmx_fmfm_epoch (fmx_fmfm.hip) and fmx_hofm_epoch (fmx_hofm.hip): stateful_epoch with the caller's own batch steps.  rows(s, row0, nb, rest, st) leaves
+// fmx_sgd.hip, for fmx_fwfm_epoch (fmx_fwfm.hip), fmx_ffm_epoch (fmx_ffm.hip), fmx_fmfm_epoch (fmx_fmfm.hip), fmx_hofm_epoch (fmx_hofm.hip) and fmx_dfm_epoch (fmx_dfm.hip): stateful_epoch with the caller's own batch steps.  rows(s, row0, nb, rest, st) leaves
 // rest[] of the batch (in place of k_rowsums); owner(sw, hy, st) is the owner kernel over the batch's segments; after(nb, st) runs
 // behind it on every batch, whether or not the batch has segments (nullptr: nothing does).  Three plain functions and the caller's own state (ctx), called in
 // that order for every batch on the epoch's stream.  The caller has made every check of its entry point.
@@ -460,6 +466,7 @@ void fwfm_free(fmx_handle h);                                            // fmx_
 void ffm_free(fmx_handle h);                                             // fmx_ffm.hip
 void fmfm_free(fmx_handle h);                                            // fmx_fmfm.hip
 void hofm_free(fmx_handle h);                                            // fmx_hofm.hip
+void dfm_free(fmx_handle h);                                             // fmx_dfm.hip
 void als_free(fmx_handle h);                                             // fmx_als.hip
 enum { GROUP_SINGLE = 0, GROUP_LOOPBACK = 1, GROUP_RCCL = 2 };
 struct fmx_group_s {                      // fmx_comm.hip

@@ -323,11 +323,15 @@ class FMLearnSGD:
     'hofm' is the third-order FM (fmx_hofm_*): optimizer 'adagrad' is required, `groups` is not read, and everything the field
     models refuse is refused here too.  fm.num_factor stays the number of pairwise factors k2 and num_factor3 adds k3 third-order
     factors: fm.v holds k2 + num_factor3 rows, the last num_factor3 of them the third-order factors, and the handle is created with
-    that many."""
+    that many.
+    'dfm' is DeepFM with one hidden layer (fmx_dfm_*), a field model under the same requirements and with the same refusals: an MLP of
+    num_hidden ReLU units over the per-field sums of the same V, added to the FM's score.  The start net is drawn at init() with numpy
+    from `seed`: W1, b1 and w2 from N(0, dfm_init_stdev^2), b1 too, so that no unit starts on the kink.  `.net` returns (W1, b1, w2);
+    dfm_learn_rate (0 = the AdaGrad eta), dfm_init_acc (0 = 1.0) and dfm_reg are the net's own step constants."""
 
     OPTIMIZERS = ("sgd", "adagrad", "ftrl")
-    MODELS = ("fm", "fwfm", "ffm", "fmfm", "hofm")
-    FIELD_MODELS = {"fwfm": "field-weighted", "ffm": "field-aware", "fmfm": "field-matrixed"}      # the models over `groups`, with what the messages call them
+    MODELS = ("fm", "fwfm", "ffm", "fmfm", "hofm", "dfm")
+    FIELD_MODELS = {"fwfm": "field-weighted", "ffm": "field-aware", "fmfm": "field-matrixed", "dfm": "deep"}      # the models over `groups`, with what the messages call them
     SESSION_MODELS = dict(FIELD_MODELS, hofm="third-order")     # every model that is a session next to the AdaGrad session
     SHARDED_OPTIMIZERS = ("adagrad", "ftrl")                    # what `devices` with more than one entry is honoured for
     MODES = {"sequential": capi.SGD_SEQUENTIAL, "minibatch": capi.SGD_MINIBATCH, "hogwild": capi.SGD_HOGWILD}
@@ -352,6 +356,8 @@ class FMLearnSGD:
         self.groups = None                                      # model 'fwfm': attribute -> field
         self.fwfm_learn_rate, self.fwfm_init_acc, self.fwfm_reg = 0.0, 0.0, 0.0
         self.fmfm_learn_rate, self.fmfm_init_acc, self.fmfm_reg = 0.0, 0.0, 0.0
+        self.num_hidden = 16                                    # model 'dfm': hidden units; the net's start values and step constants
+        self.dfm_learn_rate, self.dfm_init_acc, self.dfm_reg, self.dfm_init_stdev, self.seed = 0.0, 0.0, 0.0, 0.1, 0
         self.num_factor3 = 0                                    # model 'hofm': third-order factors, next to fm.num_factor pairwise ones
         self.init_acc = 0.0
         self.adapt_learn_rate = 0.0
@@ -376,6 +382,7 @@ class FMLearnSGD:
         self._ffm_open = False
         self._fmfm_open = False
         self._hofm_open = False
+        self._dfm_open = False
         self._checkpoint = None                                 # load_checkpoint before init(): the file init() starts from
 
     def _check_model(self):
@@ -390,6 +397,8 @@ class FMLearnSGD:
             raise ValueError("model %s trains with optimizer adagrad, not %s" % (self.model, self.optimizer))
         if self.model == "hofm" and int(self.num_factor3) < 0:
             raise ValueError("model hofm: num_factor3 must be >= 0")
+        if self.model == "dfm" and int(self.num_hidden) < 1:
+            raise ValueError("model dfm: num_hidden must be >= 1")
         if self.model in self.FIELD_MODELS and self.groups is None:
             raise ValueError("model %s needs groups: the attribute -> field map" % self.model)
         self._not_on_shards("model %s" % self.model)
@@ -419,6 +428,13 @@ class FMLearnSGD:
         if not self._fmfm_open:
             raise ValueError("m: model fmfm after init() only")
         return self._h.fmfm_get_m()[0]
+
+    @property
+    def net(self):
+        """model 'dfm': (W1 [F k][H], b1 [H], w2 [H]) as the device holds them"""
+        if not self._dfm_open:
+            raise ValueError("net: model dfm after init() only")
+        return self._h.dfm_get_net()[0]
 
     def _check_optimizer(self):
         self._check_model()
@@ -507,6 +523,12 @@ class FMLearnSGD:
         if self.model == "hofm" and not self._hofm_open:
             self._h.hofm_begin(self.num_factor3)
             self._hofm_open = True
+        if self.model == "dfm" and not self._dfm_open:
+            self._h.set_groups(self.groups)
+            self._h.dfm_begin(self.num_hidden, self.dfm_learn_rate, self.dfm_init_acc, self.dfm_reg)
+            rng, H = np.random.default_rng(self.seed), int(self.num_hidden)
+            self._h.dfm_set_net(*(rng.normal(0.0, self.dfm_init_stdev, size=shape) for shape in ((self._ffm_fields() * fm.num_factor, H), H, H)))
+            self._dfm_open = True
 
     def save_checkpoint(self, path, dense=False):
         """the exact binary checkpoint of the model on the device and of the open adagrad / ftrl session (fmx_checkpoint_save;
@@ -628,7 +650,7 @@ class FMLearnSGD:
         if (self.optimizer == "adagrad") != self._adapt_open or (self.optimizer == "ftrl") != self._ftrl_open:
             raise ValueError("optimizer was changed after init()")
         if (self.model == "fwfm") != self._fwfm_open or (self.model == "ffm") != self._ffm_open or (self.model == "fmfm") != self._fmfm_open \
-                or (self.model == "hofm") != self._hofm_open:
+                or (self.model == "hofm") != self._hofm_open or (self.model == "dfm") != self._dfm_open:
             raise ValueError("model was changed after init()")
         if id(train) in self._weights and self.optimizer == "sgd":
             raise ValueError("the train set has weights (set_weights): optimizer sgd has no weighted form, use adagrad or ftrl")
@@ -651,6 +673,8 @@ class FMLearnSGD:
                 stats = self._h.fmfm_epoch(st, self.batch, self.w0_chunk)
             elif self._hofm_open:
                 stats = self._h.hofm_epoch(st, self.batch, self.w0_chunk)
+            elif self._dfm_open:
+                stats = self._h.dfm_epoch(st, self.batch, self.w0_chunk)
             elif self._adapt_open:
                 stats = self._h.adapt_epoch(st, self.batch, self.w0_chunk)
             elif self._ftrl_open:
@@ -676,7 +700,8 @@ class FMLearnSGD:
     # fm_learn::evaluate (fm_learn.h:93-153): rmse for regression, accuracy for classification
     def evaluate(self, data):
         scorer = (self._h.fwfm_evaluate if self._fwfm_open else self._h.ffm_evaluate if self._ffm_open else
-                  self._h.fmfm_evaluate if self._fmfm_open else self._h.hofm_evaluate if self._hofm_open else self._h.evaluate)
+                  self._h.fmfm_evaluate if self._fmfm_open else self._h.hofm_evaluate if self._hofm_open else
+                  self._h.dfm_evaluate if self._dfm_open else self._h.evaluate)
         ev = scorer(self._slot(data))
         return ev.rmse if self.task == TASK_REGRESSION else ev.accuracy
 
@@ -697,6 +722,8 @@ class FMLearnSGD:
             return self._h.fmfm_predict(self._slot(data), data.num_cases)
         if self._hofm_open:
             return self._h.hofm_predict(self._slot(data), data.num_cases)
+        if self._dfm_open:
+            return self._h.dfm_predict(self._slot(data), data.num_cases)
         return self._h.predict(self._slot(data), data.num_cases)
 
     def recommend(self, queries, candidates, topk, exclude=None):
@@ -755,6 +782,9 @@ class FMLearnSGD:
             if self._hofm_open:
                 self._h.hofm_end()
                 self._hofm_open = False
+            if self._dfm_open:
+                self._h.dfm_end()
+                self._dfm_open = False
             if self._adapt_open:
                 self._h.adapt_end()
                 self._adapt_open = False
